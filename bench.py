@@ -7,14 +7,26 @@ missing blob, so the stand-in SURVEY.md 8(d) specifies is generated: a 709x709-v
 depth 10.  A "step" is one full frame (every pixel once).  A "ray" is one closest-hit query (one hit()
 call, kernel.cu K:800).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--dump-outputs DIR] [--full]
 
-What is timed: after W warm-up frames, the K-frame region (inputs resident, barrier + synchronize on
-both sides) is run R times (default 10); `ms_per_step` is the MEDIAN region time / K (min and max are
-reported beside it) and `value` = rays of one region / median time.  The library renders the K frames
-of a region in launches of up to --batch frames (one work queue over all their tiles: BATCHED
-throughput); `single_frame_ms` is the same scene with ONE frame per launch, what the reference's
-present loop does (one CudaStarter call per displayed frame, K:2154-2224).
+What is timed: after W warm-up frames and a short settle (untimed launches of the timed region's first
+launch for SETTLE_S, see settle()), the K-frame region (inputs resident, accumulator cleared, barrier +
+synchronize on both sides) is run R times (default 1; 10 with --full); `ms_per_step` is the MEDIAN region
+time / K (min and max are reported beside it) and `value` = rays of one region / median time.  The library
+renders the K frames of a region in launches of up to --batch frames (one work queue over all their tiles:
+BATCHED throughput).  The rays are counted afterwards by one more, untimed pass over the same frames with
+the counting build of the kernel.
+
+A plain run does only that.  --full adds what takes runs of its own: the rocprofv3 counter passes behind
+`roofline`, `cpu_baseline`, `single_frame_ms` (the same scene with ONE frame per launch, what the reference's
+present loop does: one CudaStarter call per displayed frame, K:2154-2224) and the pipelined single frames,
+the gather probe, the visit counts of the reference's traversal order (`per_ray.reference_order`,
+`roofline.hbm_algorithmic`, `simd_efficiency`) and, for N > 1 in one process, the check of the assembled
+frame against one context.  The --no-* switches still leave single parts of that out.
+
+--dump-outputs DIR: after the timed steps, the accumulator of the last timed region (int32 sums of its K
+frames, the array a caller of render_accumulate reads back) is written as DIR/accumulator.npy in float64.
+The scene and the seeds depend on the arguments only, so two builds can be compared output for output.
 
 N > 1: the framebuffer is tiled by interleaved 8-pixel block columns, one rank per GPU, and gathered to
 rank 0 over RCCL every --gather-every frames (scaling: strong, the frame is fixed).  Started by
@@ -30,11 +42,15 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 VALU_PEAK_LANE_OPS = 78.65e12   # 256 CUs x 4 SIMDs x 32 lanes/clk x 2.4 GHz = the 157.3 TFLOP/s fp32 vector peak / 2 flops per fma (same guide)
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024     # --dump-outputs: at most this much in all
+SETTLE_S = 0.25                          # settle(): untimed rendering between the warm-up and the timed region
 
 
 def log(*a):
@@ -169,6 +185,33 @@ def measure_counters(args):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def settle(launch):
+    """Repeats launch() (the timed region's first launch, untimed) until the GPU has rendered for SETTLE_S.  A single timed region
+    straight after a short warm-up runs slower than the regions after it: on MI355X 0.54 instead of 0.49 ms/frame after 4 warm-up
+    frames, partly at a lower shader clock (2200 against 2370 MHz), partly because the launch before it was a short one (0.52 at
+    full clock).  After this the first region times like the later ones."""
+    t0 = time.perf_counter()
+    launch()
+    while time.perf_counter() - t0 < SETTLE_S:
+        launch()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the accumulator's integer sums are exact in it).  An array
+    beyond the budget is replaced by a fixed sample of 2^20 of its pixels (seed 0, ascending) and DIR/<name>_pixels.npy,
+    the flat pixel indices of the sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > DUMP_LIMIT_BYTES:
+            px = a.reshape(-1, a.shape[-1])
+            idx = np.sort(np.random.default_rng(0).choice(px.shape[0], 1 << 20, replace=False))
+            np.save(os.path.join(out_dir, name + "_pixels.npy"), idx.astype(np.float64))
+            a = px[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs written to %s: %s" % (out_dir, ", ".join(sorted(arrays))))
+
+
 def algorithmic_bytes(c, frames, W, H):
     """32 B per node visit, 36 B per triangle test, 128 B per shaded hit, 4 B per texel,
     12 B per pixel written per frame."""
@@ -186,7 +229,6 @@ def main_group(args):
     """`python bench.py --gpus N` without a launcher: the N ranks are the library's dr_group -- one context and one host thread
     per GPU in THIS process, stripes gathered to rank 0 by ncclSend / grouped ncclRecv on a second stream per rank (peer copies
     when ranks share a device: DOGERAY_GROUP_DEVICES=0,0).  Same frames, same seeds, same JSON line as the one-GPU run."""
-    import numpy as np
     import dogeray_amd as dr
     N = args.gpus
     env_dev = [int(x) for x in os.environ.get("DOGERAY_GROUP_DEVICES", "").split(",") if x.strip() != ""]
@@ -219,8 +261,10 @@ def main_group(args):
         grp.render_accumulate(st, W, H, s.background, seed_base + first * seed_stride, seed_stride, count, args.gather_every)
 
     run_frames(0, args.warmup)
+    settle(lambda: run_frames(args.warmup, min(args.steps, args.gather_every, args.batch, 256)))
     region_s, reps = [], []
     for rep in range(max(1, args.repeats)):
+        grp.accum_reset(W, H)
         for c in ctxs:
             c.stats_reset()
         t0 = time.perf_counter()
@@ -231,10 +275,14 @@ def main_group(args):
     srt = sorted(region_s)
     elapsed = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
     timed = min(reps, key=lambda r: abs(r[0] - elapsed))      # the statistics of the MEDIAN repeat, the one `value` is quoted on (as the one-GPU path does)
-    # the assembled accumulator against one context rendering the whole frame: the same frames, bit for bit
-    grp.accum_reset(W, H)
-    run_frames(args.warmup, min(args.steps, 4))
-    assembled = grp.accum_read()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accumulator": grp.accum_read()})
+    assembled = None
+    if args.full:
+        # the assembled accumulator against one context rendering the whole frame: the same frames, bit for bit
+        grp.accum_reset(W, H)
+        run_frames(args.warmup, min(args.steps, 4))
+        assembled = grp.accum_read()
     # rays: count what the timed frames traced, every rank its stripe
     for c in ctxs:
         c.enable_counters(True); c.stats_reset()
@@ -247,12 +295,14 @@ def main_group(args):
     ranks_transport = grp.rccl_ranks
     uses_rccl = grp.uses_rccl
     grp.close()
-    whole = dr.Context(devices[0]).upload(scene)
-    whole.set_traversal(mode)
-    whole.accum_reset(W, H)
-    whole.render_accumulate(st, W, H, s.background, seed_base + args.warmup * seed_stride, seed_stride, min(args.steps, 4))
-    identical = bool(np.array_equal(whole.accum_read(), assembled))
-    whole.close()
+    identical = None
+    if assembled is not None:
+        whole = dr.Context(devices[0]).upload(scene)
+        whole.set_traversal(mode)
+        whole.accum_reset(W, H)
+        whole.render_accumulate(st, W, H, s.background, seed_base + args.warmup * seed_stride, seed_stride, min(args.steps, 4))
+        identical = bool(np.array_equal(whole.accum_read(), assembled))
+        whole.close()
     frames = args.steps
     per_rank_ms = [x["kernel_ms"] for x in timed[1]]
     result = {
@@ -280,9 +330,10 @@ def main_group(args):
         "setup_s": {"parse": t_parse, "bvh_build": t_bvh, "upload": t_upload},
         "roofline": None, "cpu_baseline": None,
         "note": "roofline and cpu_baseline are reported by the one-GPU run (same kernels; N = 1 is the configuration the metric is quoted on)",
+        "full": args.full,
     }
     print(json.dumps(result), flush=True)
-    return 0 if identical else 1
+    return 1 if identical is False else 0
 
 
 def main():
@@ -298,13 +349,20 @@ def main():
     ap.add_argument("--traversal", choices=["wide", "threaded", "ordered"], default="wide")
     ap.add_argument("--batch", type=int, default=0, help="frames per kernel launch (default 32 x GPUs, at most 256: a launch has to outlast its longest pixel, ~3 ms)")
     ap.add_argument("--gather-every", type=int, default=0, help="frames between two gathers to rank 0 (default: --batch)")
-    ap.add_argument("--repeats", type=int, default=10, help="how often the K-step timed region is run; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="how often the K-step timed region is run; the median is reported (default 1, with --full 10)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes that fill roofline (traffic, VALU counters)")
     ap.add_argument("--no-extras", action="store_true", help="skip single_frame_ms and the gather-ceiling probe")
     ap.add_argument("--cpu-col-mod", type=int, default=1, help="cpu_baseline renders every n-th block column")
     ap.add_argument("--cache", default=os.environ.get("DOGERAY_BENCH_CACHE", "/tmp/dogeray_bench"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the accumulator of the last timed region as DIR/accumulator.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: rocprofv3 counter passes (roofline), CPU baseline, single-frame and "
+                         "pipelined figures, gather probe, reference-order visit counts, the N > 1 assembled-frame check; 10 repeats by default")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -319,11 +377,11 @@ def main():
     # HBM traffic of the timed kernel: rocprofv3 PMC passes over child runs of this same command.  Done first,
     # before this process touches the GPU (a process that has initialised HIP should not spawn programs).
     traffic_probe = None
-    if world == 1 and not args.no_traffic and not under_profiler():
+    if world == 1 and args.full and not args.no_traffic and not under_profiler():
         select_workload(args)
         t0 = time.time()
         traffic_probe = measure_counters(args)
-        log("counter probe (3 rocprofv3 passes): %.1f s -> %s" % (time.time() - t0, "ok" if traffic_probe else "unavailable"))
+        log("counter probe (5 rocprofv3 passes): %.1f s -> %s" % (time.time() - t0, "ok" if traffic_probe else "unavailable"))
 
     import torch
     import dogeray_amd as dr
@@ -409,8 +467,11 @@ def main():
 
     # ---- warmup, then the timed region, `repeats` times (same frames, same seeds: same work every time)
     run_frames(0, args.warmup)
+    if world == 1:        # N > 1: every rank would have to settle for the same number of launches
+        settle(lambda: run_frames(args.warmup, min(args.steps, args.batch, 256)))
     region_s, rep_stats = [], []
     for rep in range(max(1, args.repeats)):
+        ctx.accum_reset(W, H)
         ctx.stats_reset()
         fence()
         t0 = time.perf_counter()
@@ -427,10 +488,12 @@ def main():
     elapsed = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
     # launch statistics (HIP events on the render stream, clock stamps) of the MEDIAN repeat: the one `value` is quoted on
     timed = rep_stats[min(range(len(region_s)), key=lambda i: (abs(region_s[i] - elapsed), i))]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"accumulator": ctx.accum_read()})
 
     # ---- one frame per launch (the reference's call pattern), same frames
     single = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         ctx.set_option("batch_frames", 1)
         n1 = min(args.steps, 16)
         ctx.accum_reset(W, H)
@@ -484,7 +547,7 @@ def main():
 
     # ---- gather ceiling of this GPU on the resident walk array (roofline.gather)
     gather = None
-    if world == 1 and not args.no_extras and ctx.get_option("traversal") == dr.TRAVERSAL_WIDE:
+    if world == 1 and args.full and not args.no_extras and ctx.get_option("traversal") == dr.TRAVERSAL_WIDE:
         try:
             gather = {"l2_resident_3MB": ctx.probe_gather(3 * 1024 * 1024 // 64, 4000), "whole_array": ctx.probe_gather(0, 2000),
                       "array_bytes": 64 * (ctx.get_option("wide_nodes") + ntris)}
@@ -497,8 +560,8 @@ def main():
     ctx.accum_reset(W, H)
     ctx.render_accumulate(st, W, H, s.background, seed_base + args.warmup * seed_stride, seed_stride, args.steps)
     own = ctx.stats()
-    ref_order = own
-    if mode != dr.TRAVERSAL_THREADED:
+    ref_order = own if args.full else None
+    if args.full and mode != dr.TRAVERSAL_THREADED:
         # algorithmic bytes are defined on the reference's traversal order: count that too
         ctx.set_traversal(dr.TRAVERSAL_THREADED)
         ctx.stats_reset()
@@ -524,9 +587,19 @@ def main():
     kernel_ms = timed["kernel_ms"] / max(1, timed["frames"])          # HIP events on the render stream, rank 0; per FRAME
     launch_ms = timed["kernel_ms"] / max(1, timed["launches"])        # per kernel launch (a launch may cover a batch of frames)
     frames_per_launch = timed["frames"] / max(1, timed["launches"])
-    abytes = algorithmic_bytes(ref_order, frames, W if world == 1 else W // world, H) / frames
     kbytes = algorithmic_bytes(own, frames, W if world == 1 else W // world, H) / frames
-    algorithmic_gbs = abytes / (kernel_ms * 1e-3) / 1e9
+    hbm_algorithmic = reference_order = simd_efficiency = None
+    if ref_order is not None:
+        abytes = algorithmic_bytes(ref_order, frames, W if world == 1 else W // world, H) / frames
+        algorithmic_gbs = abytes / (kernel_ms * 1e-3) / 1e9
+        hbm_algorithmic = {"bytes_per_launch": abytes * frames_per_launch, "GBs": algorithmic_gbs, "frac_of_hbm_peak": algorithmic_gbs / HBM_PEAK_GBS,
+                           "note": "SURVEY 8(d): 32 V + 36 L + 128 S + 4 T + 12 W H with the REFERENCE traversal's visit counts; these bytes are what the "
+                                   "reference algorithm asks for, not what reaches HBM"}
+        reference_order = {"V": ref_order["node_visits"] / ref_order["rays"], "L": ref_order["prim_tests"] / ref_order["rays"],
+                           "S": ref_order["shades"] / ref_order["rays"], "T": ref_order["texels"] / ref_order["rays"],
+                           "bytes": abytes * frames / ref_order["rays"]}
+        simd_efficiency = {"node_loop": ref_order["node_visits"] / max(1, ref_order["trav_slots"]),
+                           "bounce_loop": ref_order["rays"] / max(1, ref_order["ray_slots"])}
     records_per_s = own["node_visits"] / frames / (kernel_ms * 1e-3)          # records the kernel's own walk fetched (nodes + leaves)
     result = {
         "metric": "Mrays/sec + ms/frame, 1M-tri .rts at 1920x1080" if args.config == "C4" else "Mrays/sec + ms/frame, config %s" % args.config,
@@ -559,9 +632,7 @@ def main():
         "primary_samples_per_s": (W * H * frames) / elapsed,
         "kernel_ms_per_frame": kernel_ms,
         "per_ray": {
-            "reference_order": {"V": ref_order["node_visits"] / ref_order["rays"], "L": ref_order["prim_tests"] / ref_order["rays"],
-                                "S": ref_order["shades"] / ref_order["rays"], "T": ref_order["texels"] / ref_order["rays"],
-                                "bytes": abytes * frames / ref_order["rays"]},
+            "reference_order": reference_order,
             "kernel": {"V": own["node_visits"] / own["rays"], "L": own["prim_tests"] / own["rays"],
                        "bytes": kbytes * frames / own["rays"]},
         },
@@ -577,9 +648,7 @@ def main():
             "traffic": None,
             "valu": None,
             "hbm": None,
-            "hbm_algorithmic": {"bytes_per_launch": abytes * frames_per_launch, "GBs": algorithmic_gbs, "frac_of_hbm_peak": algorithmic_gbs / HBM_PEAK_GBS,
-                                "note": "SURVEY 8(d): 32 V + 36 L + 128 S + 4 T + 12 W H with the REFERENCE traversal's visit counts; these bytes are what the "
-                                        "reference algorithm asks for, not what reaches HBM"},
+            "hbm_algorithmic": hbm_algorithmic,
             "gather": None,
             "kernel_own_visit_bytes_per_launch": 64 * own["node_visits"] / frames * frames_per_launch,      # records visited x their 64-byte stride (a node's fourth 16 bytes are not fetched)
             "launch_ms": launch_ms,
@@ -592,8 +661,8 @@ def main():
         "setup_s": {"parse": t_parse, "bvh_build": t_bvh, "upload": t_upload},
         "diag": own.get("diag"),
 
-        "simd_efficiency": {"node_loop": ref_order["node_visits"] / max(1, ref_order["trav_slots"]),
-                            "bounce_loop": ref_order["rays"] / max(1, ref_order["ray_slots"])},
+        "simd_efficiency": simd_efficiency,
+        "full": args.full,
     }
 
     rf = result["roofline"]
@@ -641,7 +710,7 @@ def main():
                      "note": "rocprofv3 PMC, separate passes, per launch of the timed kernel: 2 x FETCH_SIZE (%.3g B raw; gfx950 reports half of 16-B/lane reads) "
                              "+ WRITE_SIZE (%.3g B)" % (t["FETCH_SIZE"], t["WRITE_SIZE"])}
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             from oracle import orc
             ncpu = usable_cpus()
@@ -664,7 +733,6 @@ def main():
             ctx.accum_reset(W, H)
             ctx.render_accumulate(st, W, H, s.background, seed_base + args.warmup * seed_stride, 0, 1)
             gpu = ctx.accum_read()
-            import numpy as np
             cols = (np.arange(W) // 8) % args.cpu_col_mod == 0
             same = float(np.all(gpu[cols] == img[cols], axis=2).mean())
             # one thread, every 2nd block column of the first frame (about 1.5 s of work)
