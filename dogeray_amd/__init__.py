@@ -66,6 +66,18 @@ class DrStats(C.Structure):
         return d
 
 
+class DrAovBuffers(C.Structure):
+    """struct dr_aov_buffers: one pointer per first-hit channel (NULL: not computed)."""
+    _fields_ = [("t", C.c_void_p), ("distance", C.c_void_p), ("depth", C.c_void_p), ("object", C.c_void_p), ("material", C.c_void_p),
+                ("normal", C.c_void_p), ("uv", C.c_void_p), ("albedo", C.c_void_p), ("dir", C.c_void_p)]
+
+
+# the channels of Context.render_aov: name -> (dtype, components per pixel)
+AOV_CHANNELS = {"t": (np.float32, 1), "distance": (np.float32, 1), "depth": (np.float32, 1), "object": (np.int32, 1), "material": (np.int32, 1),
+                "normal": (np.float32, 3), "uv": (np.float32, 2), "albedo": (np.float32, 3), "dir": (np.float32, 3)}
+ALL = tuple(AOV_CHANNELS)
+
+
 # every symbol include/dogeray_amd.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _API = [
@@ -112,6 +124,7 @@ _API = [
     ("dr_accum_pack_stripe", C.c_int, [_VP, C.c_int, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     ("dr_accum_unpack_stripes", C.c_int, [_VP, _VP, C.c_uint64, C.c_int, C.c_int, _VP]),
     ("dr_accum_reserve_pack", C.c_int, [_VP, C.c_int]),
+    ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
     ("dr_group_create", C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
     ("dr_group_destroy", None, [_VP]),
     ("dr_group_size", C.c_int, [_VP]),
@@ -181,6 +194,52 @@ def _f32(a):
 
 def device_count():
     return lib().dr_device_count()
+
+
+def pixel_grid(settings13, W, H):
+    """(width, height) of the pixel grid dr_render_frame renders: (W / div / 8) * 8 x (H / div / 8) * 8, div = settings13[11]."""
+    div = float(np.float32(settings13[11]))
+    div = int(div) if np.isfinite(div) else 0
+    if div < 1:
+        return 0, 0
+    return W // div // 8 * 8, H // div // 8 * 8
+
+
+def write_pfm(path, img):
+    """Portable float map: float32[h, w] ("Pf") or float32[h, w, 3] ("PF"), little-endian; row 0 of the array is the top row of the
+    image (the file stores the bottom row first)."""
+    a = np.asarray(img, dtype=np.float32)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError("write_pfm: need [h, w] or [h, w, 3], got %s" % (a.shape,))
+    with open(path, "wb") as f:
+        f.write(b"%s\n%d %d\n-1.0\n" % (b"PF" if a.ndim == 3 else b"Pf", a.shape[1], a.shape[0]))
+        f.write(np.ascontiguousarray(a[::-1], dtype="<f4").tobytes())
+    return path
+
+
+def read_pfm(path):
+    """The array write_pfm wrote (either byte order on input; float32, row 0 = top row)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    fields, pos = [], 0
+    while len(fields) < 4:                 # magic, width, height, scale: whitespace-separated, one whitespace byte after the scale
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        end = pos
+        while not data[end:end + 1].isspace():
+            end += 1
+        fields.append(data[pos:end])
+        pos = end
+    pos += 1
+    magic, w, h, scale = fields[0], int(fields[1]), int(fields[2]), float(fields[3])
+    if magic not in (b"PF", b"Pf"):
+        raise ValueError("%s is not a PFM file" % path)
+    ch = 3 if magic == b"PF" else 1
+    a = np.frombuffer(data, dtype="<f4" if scale < 0 else ">f4", count=w * h * ch, offset=pos).astype(np.float32)
+    a = a.reshape((h, w, 3) if ch == 3 else (h, w))
+    return np.ascontiguousarray(a[::-1])
 
 
 def pack_settings13(s, divisor, spp=None, depth=None):
@@ -460,6 +519,62 @@ class Context:
         v = C.c_double()
         _check(lib().dr_context_probe_gather(self._h, int(hot_records), int(iters), C.byref(v)))
         return v.value
+
+    # ---- first-hit AOVs (dr_render_aov)
+    def render_aov(self, settings13, W, H, window=None, channels=ALL, device=False):
+        """First-hit buffers of the pinhole rays through the pixel centres (include/dogeray_amd.h dr_render_aov): a dict channel -> array
+        [h, w] (t, distance, depth: float32; object, material: int32) or [h, w, k] (normal, albedo, dir: 3; uv: 2), row index = the
+        renderer's y.  window (x0, y0, w, h) inside the pixel grid, None = all of it.  device=True: torch tensors on this context's GPU,
+        written on the library's stream, which waits for torch's current stream first; torch's current stream waits for it afterwards."""
+        st = _f32(settings13)
+        assert st.shape == (13,)
+        if window is None:
+            gw, gh = pixel_grid(st, W, H)
+            window = (0, 0, gw, gh)
+        x0, y0, w, h = (int(v) for v in window)
+        channels = tuple(channels)
+        for k in channels:
+            if k not in AOV_CHANNELS:
+                raise ValueError("unknown AOV channel %r (known: %s)" % (k, ", ".join(ALL)))
+        shape = lambda k: (max(h, 0), max(w, 0)) + ((AOV_CHANNELS[k][1],) if AOV_CHANNELS[k][1] > 1 else ())
+        bufs = DrAovBuffers()
+        if not device:
+            out = {k: np.empty(shape(k), dtype=AOV_CHANNELS[k][0]) for k in channels}
+            for k, a in out.items():
+                setattr(bufs, k, a.ctypes.data)
+            _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 0))
+            return out
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty(shape(k), dtype=tdt[AOV_CHANNELS[k][0]], device=dev) for k in channels}
+        for k, a in out.items():
+            setattr(bufs, k, a.data_ptr())
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 1))
+        cur.wait_stream(lib_stream)
+        return out
+
+    def pick(self, settings13, W, H, x, y):
+        """Every channel of pixel (x, y) of the grid: t, distance, depth (float), object, material (int; -1 on a miss), normal, albedo,
+        dir (3-tuples) and uv (2-tuple)."""
+        a = self.render_aov(settings13, W, H, window=(x, y, 1, 1))
+        return {k: (tuple(float(c) for c in v[0, 0]) if v.ndim == 3 else (int(v[0, 0]) if v.dtype == np.int32 else float(v[0, 0])))
+                for k, v in a.items()}
+
+    def autofocus(self, settings13, W, H, x=None, y=None):
+        """A copy of settings13 with the focus distance [7] set to the depth of what pixel (x, y) sees (default: the centre of the grid) --
+        the reference's Z/X keys (K:2471-2483) as one call.  On a miss settings13 comes back unchanged."""
+        st = _f32(settings13).copy()
+        gw, gh = pixel_grid(st, W, H)
+        x = gw // 2 if x is None else x
+        y = gh // 2 if y is None else y
+        a = self.render_aov(st, W, H, window=(x, y, 1, 1), channels=("object", "depth"))
+        if a["object"][0, 0] >= 0:
+            st[7] = a["depth"][0, 0]
+        return st
 
     # ---- known-answer hooks (tests)
     def kat_rng(self, seed, n):

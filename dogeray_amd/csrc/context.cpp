@@ -35,6 +35,9 @@ struct dr_context {
   uint32_t* texels = nullptr;
   int n_prims = 0, n_tex = 0, tree_depth = 0;
   std::vector<int> slot_to_orig;
+  int32_t* slot_to_orig_dev = nullptr;     // the same map on the device: uploaded by the first dr_render_aov after a scene upload
+  // dr_render_aov with host pointers: the channels are written here, then downloaded
+  uint8_t* aov_staging = nullptr; size_t aov_staging_bytes = 0;
   // frame + accumulator
   int32_t* frame = nullptr; size_t frame_elems = 0;
   int32_t* accum = nullptr; size_t accum_elems = 0; int accW = 0, accH = 0;
@@ -422,7 +425,8 @@ void dr_context_destroy(dr_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (int k = 1; k < dr_context::PIPE_STREAMS; k++) if (c->pipe_stream[k]) (void)hipStreamSynchronize(c->pipe_stream[k]);
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
-  void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start};
+  void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
+                  c->slot_to_orig_dev, c->aov_staging};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -472,6 +476,10 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   c->n_prims = (int)img.prims.size();
   c->n_tex = (int)img.tex.size();
   c->slot_to_orig = img.slot_to_orig;
+  if (c->slot_to_orig_dev) {       // the old scene's map (dr_render_aov uploads the new one when it first needs it)
+    (void)hipFree(c->slot_to_orig_dev);
+    c->slot_to_orig_dev = nullptr;
+  }
   int depth = 0;
   while (((size_t)1 << depth) < img.prims.size()) depth++;
   c->tree_depth = depth;
@@ -568,6 +576,68 @@ int dr_accum_reset(dr_context* c, int W, int H) {
   if (rc != DR_OK) return rc;
   c->accW = W; c->accH = H;
   HIP_TRY(hipMemsetAsync(c->accum, 0, elems * sizeof(int32_t), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
+                  int device_pointers) {
+  if (!c || !settings13 || !buffers) { set_error("null argument"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  // the settings are judged as dr_render_frame judges them (make_params), without touching the context's state
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
+  if (P.backtex >= c->n_tex) { set_error("backtex refers to a texture that is not loaded"); return DR_ERR_INVALID; }
+  const int traversal = traversal_of(c);
+  if (traversal == DR_TRAVERSAL_ORDERED && c->tree_depth > ORDERED_STACK) { set_error("tree too deep for ordered traversal"); return DR_ERR_SCENE; }
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  if (w <= 0 || h <= 0) { set_error("empty AOV window"); return DR_ERR_INVALID; }
+  if (x0 < 0 || y0 < 0 || x0 > gw - w || y0 > gh - h) {
+    set_error("AOV window (" + std::to_string(x0) + ", " + std::to_string(y0) + ", " + std::to_string(w) + ", " + std::to_string(h) +
+              ") is not inside the " + std::to_string(gw) + " x " + std::to_string(gh) + " pixel grid");
+    return DR_ERR_INVALID;
+  }
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
+  if (!c->slot_to_orig_dev) {
+    HIP_TRY(hipMalloc((void**)&c->slot_to_orig_dev, (c->slot_to_orig.empty() ? 1 : c->slot_to_orig.size()) * sizeof(int32_t)));
+    if (!c->slot_to_orig.empty())
+      HIP_TRY(hipMemcpyAsync(c->slot_to_orig_dev, c->slot_to_orig.data(), c->slot_to_orig.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  P.walk = c->walk; P.walk_bytes = (uint32_t)c->walk_bytes; P.pairs = c->pairs; P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
+  P.wide = c->wide; P.wide_bytes = (uint32_t)c->wide_bytes; P.wide_pmax = c->wide_pmax; P.wide_mu = c->wide_mu;
+  AovLaunch A;
+  A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+  A.focus = settings13[7];
+  A.slot_to_orig = c->slot_to_orig_dev;
+  // channel k: where the caller wants it, the device buffer it is written to, its words per pixel
+  void* const want[9] = {buffers->t, buffers->distance, buffers->depth, buffers->object, buffers->material, buffers->normal, buffers->uv, buffers->albedo, buffers->dir};
+  const int words[9] = {1, 1, 1, 1, 1, 3, 2, 3, 3};
+  void* dev[9] = {nullptr};
+  const size_t npix = (size_t)w * (size_t)h;
+  bool any = false;
+  if (device_pointers) {
+    for (int k = 0; k < 9; k++) { dev[k] = want[k]; any = any || want[k]; }
+  } else {
+    size_t bytes = 0;
+    for (int k = 0; k < 9; k++) if (want[k]) bytes += npix * (size_t)words[k] * 4;
+    if (bytes > c->aov_staging_bytes) {
+      if (c->aov_staging) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->aov_staging); c->aov_staging = nullptr; c->aov_staging_bytes = 0; }
+      HIP_TRY(hipMalloc((void**)&c->aov_staging, bytes));
+      c->aov_staging_bytes = bytes;
+    }
+    size_t off = 0;
+    for (int k = 0; k < 9; k++) if (want[k]) { dev[k] = c->aov_staging + off; off += npix * (size_t)words[k] * 4; any = true; }
+  }
+  if (!any) return DR_OK;
+  A.t = (float*)dev[0]; A.distance = (float*)dev[1]; A.depth = (float*)dev[2]; A.object = (int32_t*)dev[3]; A.material = (int32_t*)dev[4];
+  A.normal = (float*)dev[5]; A.uv = (float*)dev[6]; A.albedo = (float*)dev[7]; A.dir = (float*)dev[8];
+  launch_aov(c->stream, P, traversal, A);
+  HIP_TRY(hipGetLastError());
+  if (device_pointers) return DR_OK;
+  for (int k = 0; k < 9; k++)
+    if (want[k]) HIP_TRY(hipMemcpyAsync(want[k], dev[k], npix * (size_t)words[k] * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DR_OK;
 }

@@ -74,10 +74,39 @@ bool write_bmp(const std::string& path, const std::vector<uint8_t>& rgb, int W, 
   return ok;
 }
 
+// Portable float map, little-endian, bottom row first (row 0 of `v` = the top row, y = 0, as in the presented image); comps = 1 or 3
+bool write_pfm(const std::string& path, const std::vector<float>& v, int w, int h, int comps) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "%s\n%d %d\n-1.0\n", comps == 3 ? "PF" : "Pf", w, h);
+  bool ok = true;
+  for (int y = h - 1; y >= 0 && ok; y--) ok = fwrite(&v[(size_t)y * w * comps], sizeof(float), (size_t)w * comps, f) == (size_t)w * comps;
+  fclose(f);
+  return ok;
+}
+
+// --aov PREFIX: the first-hit buffers of the final view (dr_render_aov) as PREFIX.depth.pfm, .distance.pfm, .normal.pfm, .albedo.pfm, .object.pfm
+// (object ids as floats: exact below 2^24; a miss is -1)
+bool write_aovs(dr_context* ctx, const float st[13], int W, int H, const std::string& prefix) {
+  const int div = (int)st[11], gw = div >= 1 ? W / div / 8 * 8 : 0, gh = div >= 1 ? H / div / 8 * 8 : 0;
+  const size_t n = (size_t)gw * gh;
+  std::vector<float> depth(n), distance(n), normal(n * 3), albedo(n * 3), object_f(n);
+  std::vector<int32_t> object(n);
+  dr_aov_buffers b;
+  memset(&b, 0, sizeof(b));
+  b.depth = depth.data(); b.distance = distance.data(); b.normal = normal.data(); b.albedo = albedo.data(); b.object = object.data();
+  if (dr_render_aov(ctx, st, W, H, 0, 0, gw, gh, &b, 0) != DR_OK) return false;
+  for (size_t i = 0; i < n; i++) object_f[i] = (float)object[i];
+  return write_pfm(prefix + ".depth.pfm", depth, gw, gh, 1) && write_pfm(prefix + ".distance.pfm", distance, gw, gh, 1) &&
+         write_pfm(prefix + ".normal.pfm", normal, gw, gh, 3) && write_pfm(prefix + ".albedo.pfm", albedo, gw, gh, 3) &&
+         write_pfm(prefix + ".object.pfm", object_f, gw, gh, 1);
+}
+
 void usage() {
   fprintf(stderr,
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
+          "               [--aov PREFIX] [--autofocus]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -86,17 +115,20 @@ void usage() {
           "               host thread each); the stripes are gathered to GPU 0 over RCCL every --gather-every frames (default: once per\n"
           "               present), the gather of one batch running beside the rendering of the next\n"
           "  --cache      keep a binary image of the parsed scene + BVH next to the scene (scene.rtsb) and start from\n"
-          "               it while it is newer than the .rts ('r' fields and textures are frozen in it: delete it to redraw)\n");
+          "               it while it is newer than the .rts ('r' fields and textures are frozen in it: delete it to redraw)\n"
+          "  --aov        after the render, write the first-hit buffers of the view (pinhole rays through the pixel centres) as\n"
+          "               PREFIX.depth.pfm, .distance.pfm, .normal.pfm, .albedo.pfm and .object.pfm (object ids as floats, exact below 2^24)\n"
+          "  --autofocus  before rendering, set the focus distance to the depth of what the centre pixel sees (the reference's Z/X keys)\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string scene_path = "scene.rts", out_path;
+  std::string scene_path = "scene.rts", out_path, aov_prefix;
   const char* texdir = nullptr;
   int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0;
   uint64_t seed = 1;
-  bool quiet = false, have_scene = false, use_cache = false;
+  bool quiet = false, have_scene = false, use_cache = false, autofocus = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
@@ -114,6 +146,8 @@ int main(int argc, char** argv) {
     else if (a == "--gather-every") gather_every = atoi(next());
     else if (a == "--quiet") quiet = true;
     else if (a == "--cache") use_cache = true;
+    else if (a == "--aov") aov_prefix = next();
+    else if (a == "--autofocus") autofocus = true;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
@@ -162,6 +196,22 @@ int main(int argc, char** argv) {
     if (dr_context_create(device, &ctx) != DR_OK) die("cannot create the device context");
     if (dr_context_upload_scene(ctx, scene) != DR_OK) die("cannot upload the scene");
     if (dr_accum_reset(ctx, W, H) != DR_OK) die("cannot allocate the accumulator");
+  }
+  if (autofocus) {                       // K:2471-2483 sets the focus by hand; here: what the centre pixel of the full-resolution grid sees
+    float st[13];
+    pack13(s, 1, s.spp, s.max_depth, st);
+    float depth_at = 0;
+    int32_t object_at = -1;
+    dr_aov_buffers b;
+    memset(&b, 0, sizeof(b));
+    b.depth = &depth_at; b.object = &object_at;
+    if (dr_render_aov(ctx, st, W, H, W / 8 * 4, H / 8 * 4, 1, 1, &b, 0) != DR_OK) die("autofocus");
+    if (object_at >= 0) {
+      printf("autofocus: object %d, focus distance %g -> %g\n", object_at, s.focus_dist, depth_at);
+      s.focus_dist = depth_at;
+    } else {
+      printf("autofocus: nothing under the centre pixel, focus distance stays %g\n", s.focus_dist);
+    }
   }
   auto reset = [&]() { return grp ? dr_group_accum_reset(grp, W, H) : dr_accum_reset(ctx, W, H); };
   auto render = [&](const float* st13, uint64_t sd, int n) {
@@ -244,6 +294,12 @@ int main(int argc, char** argv) {
     bool ok = ends_with(out_path, ".ppm") ? write_ppm(out_path, rgb, W, H) : write_bmp(out_path, rgb, W, H);
     if (!ok) { fprintf(stderr, "dogeray: cannot write %s\n", out_path.c_str()); return 1; }
     printf("exported image:%s\n", out_path.c_str());                  // K:2515
+  }
+  if (!aov_prefix.empty()) {
+    float st[13];
+    pack13(s, 1, s.spp, s.max_depth, st);
+    if (!write_aovs(ctx, st, W, H, aov_prefix)) { fprintf(stderr, "dogeray: cannot write the AOVs %s.*.pfm: %s\n", aov_prefix.c_str(), dr_last_error()); return 1; }
+    printf("exported AOVs:%s.{depth,distance,normal,albedo,object}.pfm\n", aov_prefix.c_str());
   }
   if (grp) dr_group_destroy(grp); else dr_context_destroy(ctx);
   dr_scene_free(scene);

@@ -1,6 +1,7 @@
 // Launchers of the device code, one translation unit per family of kernels:
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
 //   kernels_aux.hip           tile-order feedback, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
+//   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
 #pragma once
@@ -55,5 +56,17 @@ void launch_kat_sphere(hipStream_t stream, int n, const float* o, const float* d
 void launch_kat_optics(hipStream_t stream, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* sch);
 void launch_kat_normal(hipStream_t stream, const RenderParams& P, int n, const int32_t* slot, const float* o, const float* d, const float* t, float* nrm, float* texco);
 void launch_kat_hit(hipStream_t stream, const RenderParams& P, int traversal, int n, const float* o, const float* d, float* t, int32_t* slot, int32_t* visits);
+
+// kernels_aov.hip: the window (x0, y0, w, h) of the pixel grid and the channels to write (null: not written), each a row-major w x h plane
+// (pixel (x, y) at (y - y0) * w + (x - x0); normal / albedo / dir 3 floats per pixel, uv 2)
+struct AovLaunch {
+  int x0, y0, w, h;
+  float focus;                    // settings13[7]
+  const int32_t* slot_to_orig;    // slot -> object index of the file
+  float* t; float* distance; float* depth;
+  int32_t* object; int32_t* material;
+  float* normal; float* uv; float* albedo; float* dir;
+};
+void launch_aov(hipStream_t stream, const RenderParams& P, int traversal, const AovLaunch& A);
 
 }  // namespace dr

@@ -269,6 +269,47 @@ int dr_accum_reserve_pack(dr_context* c, int slot);
 int dr_accum_unpack_stripes(dr_context* c, const void* packed_dev, uint64_t rank_stride_bytes, int world, int first_rank,
                             void* hip_stream);
 
+/* ------------------------------------------------------------------ first-hit AOVs ------ */
+/* What a pixel SEES, as buffers ("arbitrary output variables"): depth, normal, albedo, object id ... of the first hit of one camera ray per pixel
+ * -- for picking the object under a cursor, focusing on it (the reference sets the focus distance by hand, Z/X keys K:2471-2483), denoiser
+ * guides, datasets.
+ *   pixel grid  the one dr_render_frame renders: (W / div / 8) * 8 x (H / div / 8) * 8 pixels, div = (int)settings13[11] (K:2633-2636)
+ *   ray         the pinhole ray through the pixel CENTRE: nu = (float)(((double)x + 0.5) / den_w), nv likewise with y (den_w / den_h as
+ *               K:1067-1068); origin = lookfrom, direction = llc + nu * horizontal + nv * vertical - lookfrom (K:1030-1073 without the jitter
+ *               and without the lens offset: the aperture is ignored)
+ *   first hit   hit() K:468-512 on the uploaded scene with the context's traversal (dr_context_set_traversal: all give the same hit)
+ * Channels (NULL: not computed), each a buffer of its own, row-major: pixel (x, y) of the window at (y - y0) * w + (x - x0) -- row index = the
+ * renderer's y, the order of dr_accum_present's image --, vector channels with their components consecutive per pixel:
+ *   t         f32    hit()'s ray parameter (bit-identical to dr_kat_hit on the same ray); on a miss -1
+ *   distance  f32    t * sqrtf(dx * dx + dy * dy + dz * dz), in that order; +inf on a miss
+ *   depth     f32    t * settings13[7]: the distance along the view axis (every pinhole direction's component along -w is the focus distance,
+ *                    K:1047-1049); +inf on a miss
+ *   object    i32    index of the object in dr_scene_get_objects order, as dr_kat_hit reports it; -1 on a miss (hit() says 0, K:507)
+ *   material  i32    the object's mat (K:852-944); -1 on a miss
+ *   normal    3 f32  the shading normal as raycolor forms it: getnormal, flipped to face the ray (K:807-825); 0 on a miss
+ *   uv        2 f32  the interpolated texture coordinate texco.x, texco.y (K:728-745); 0 on a miss
+ *   albedo    3 f32  ocolor as raycolor forms it (K:826-844): the texture at (u, 1 - v), the checker, or col -- for emissive materials the
+ *                    emitted colour; 0 on a miss
+ *   dir       3 f32  the ray direction as traced (unnormalised) */
+typedef struct dr_aov_buffers {
+  float* t;
+  float* distance;
+  float* depth;
+  int32_t* object;
+  int32_t* material;
+  float* normal;   /* w * h * 3 */
+  float* uv;       /* w * h * 2 */
+  float* albedo;   /* w * h * 3 */
+  float* dir;      /* w * h * 3 */
+} dr_aov_buffers;
+/* The channels of the window (x0, y0, w, h) of the pixel grid (1 x 1: a pick).  device_pointers = 0: host buffers, the call returns when they are
+ * filled; 1: device buffers on this context's GPU, the work is queued on dr_context_stream and the call returns at once.  Ordered behind the
+ * frames submitted before it (dr_pipeline_submit); changes neither the accumulator, nor dr_stats, the stripe or any option.  The settings are
+ * accepted or refused as by dr_render_frame; no scene, an empty window or one not inside the grid: DR_ERR_INVALID.  The first call after a scene
+ * upload copies the slot -> object map to the device. */
+int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
+                  int device_pointers);
+
 /* ------------------------------------------------------------------ multi-GPU group ----- */
 /* One process, one context and one host thread per GPU (the reference is single-device, K:2614-2615).  Rank r of n
  * renders the block columns bx % n == r of every frame (scene replicated); every `gather_every` frames each rank packs

@@ -194,4 +194,55 @@ int hk_render(void* hv, const float* settings13, int W, int H, float background,
   return 0;
 }
 
+// dr_render_aov on the host: device_core.hpp aov_first_hit for every pixel of the window (x0, y0, w, h) of the pixel grid, with the given traversal;
+// the channels (null: not written) in dr_render_aov's layout.  Returns 0, or -1 with hk_last_error.
+int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int w, int h, int traversal, int nthreads, float* t, float* distance,
+           float* depth, int32_t* object, int32_t* material, float* normal, float* uv, float* albedo, float* dir) {
+  HkScene* h_ = (HkScene*)hv;
+  if (!h_ || !settings13) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  const DeviceImage& img = h_->img;
+  if (P.backtex >= (int)img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
+  if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > P.gx * 8 - w || y0 > P.gy * 8 - h) { hk_err = "window is empty or not inside the pixel grid"; return -1; }
+  P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
+  P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
+  P.pairs = img.pairs.data(); P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
+  const float focus = settings13[7];
+  if (nthreads < 1) nthreads = 1;
+  std::vector<std::thread> th;
+  for (int k = 0; k < nthreads; k++)
+    th.emplace_back([&, k] {
+      std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
+      const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
+      for (int wy = k; wy < h; wy += nthreads)
+        for (int wx = 0; wx < w; wx++) {
+          AovHit a;
+          if (traversal == DR_TRAVERSAL_WIDE && P.wide) {
+            auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_wide<false>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, o, d, cc, stack.data()); };
+            a = aov_first_hit(P, closest, focus, x0 + wx, y0 + wy);
+          } else if (traversal == DR_TRAVERSAL_ORDERED) {
+            auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_ordered<false>(P.pairs, P.prims, o, d, cc, stack.data()); };
+            a = aov_first_hit(P, closest, focus, x0 + wx, y0 + wy);
+          } else {
+            auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_threaded<false>(walk, o, d, cc); };
+            a = aov_first_hit(P, closest, focus, x0 + wx, y0 + wy);
+          }
+          const size_t i = (size_t)wy * (size_t)w + (size_t)wx;
+          if (t) t[i] = a.t;
+          if (distance) distance[i] = a.distance;
+          if (depth) depth[i] = a.depth;
+          if (object) object[i] = a.slot >= 0 ? img.slot_to_orig[(size_t)a.slot] : -1;
+          if (material) material[i] = a.mat;
+          if (normal) { normal[3 * i] = a.normal.x; normal[3 * i + 1] = a.normal.y; normal[3 * i + 2] = a.normal.z; }
+          if (uv) { uv[2 * i] = a.u; uv[2 * i + 1] = a.v; }
+          if (albedo) { albedo[3 * i] = a.albedo.x; albedo[3 * i + 1] = a.albedo.y; albedo[3 * i + 2] = a.albedo.z; }
+          if (dir) { dir[3 * i] = a.dir.x; dir[3 * i + 1] = a.dir.y; dir[3 * i + 2] = a.dir.z; }
+        }
+    });
+  for (std::thread& x : th) x.join();
+  return 0;
+}
+
 }  // extern "C"

@@ -47,6 +47,7 @@ def lib():
         L.hk_check_reject.restype = C.c_longlong
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
         L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hk_aov.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 9
         _lib = L
     return _lib
 
@@ -82,3 +83,20 @@ class Scene:
         if rc != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return out, (dict(zip(("rays", "V", "L", "S", "T", "samples"), [int(v) for v in ctr])) if count else None)
+
+    def aov(self, settings13, W, H, window=None, traversal=2, nthreads=4):
+        """dr_render_aov on the host (device_core.hpp aov_first_hit): every channel of the window (x0, y0, w, h) of the pixel grid
+        (None: all of it) as a dict of arrays shaped like dogeray_amd.Context.render_aov's."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        if window is None:
+            div = int(st[11])
+            window = (0, 0, W // div // 8 * 8, H // div // 8 * 8)
+        x0, y0, w, h = (int(v) for v in window)
+        out = {"t": np.zeros((h, w), np.float32), "distance": np.zeros((h, w), np.float32), "depth": np.zeros((h, w), np.float32),
+               "object": np.zeros((h, w), np.int32), "material": np.zeros((h, w), np.int32), "normal": np.zeros((h, w, 3), np.float32),
+               "uv": np.zeros((h, w, 2), np.float32), "albedo": np.zeros((h, w, 3), np.float32), "dir": np.zeros((h, w, 3), np.float32)}
+        rc = lib().hk_aov(self.h, st.ctypes.data, W, H, x0, y0, w, h, traversal, nthreads,
+                          *[out[k].ctypes.data for k in ("t", "distance", "depth", "object", "material", "normal", "uv", "albedo", "dir")])
+        if rc != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return out
