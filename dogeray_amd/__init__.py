@@ -78,6 +78,12 @@ AOV_CHANNELS = {"t": (np.float32, 1), "distance": (np.float32, 1), "depth": (np.
 ALL = tuple(AOV_CHANNELS)
 
 
+class DrDenoiseParams(C.Structure):
+    """struct dr_denoise_params (include/dogeray_amd.h dr_accum_denoise)."""
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_int), ("material_stop", C.c_int)]
+
+
 # every symbol include/dogeray_amd.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _API = [
@@ -125,6 +131,8 @@ _API = [
     ("dr_accum_unpack_stripes", C.c_int, [_VP, _VP, C.c_uint64, C.c_int, C.c_int, _VP]),
     ("dr_accum_reserve_pack", C.c_int, [_VP, C.c_int]),
     ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
+    ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
+    ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_group_create", C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
     ("dr_group_destroy", None, [_VP]),
     ("dr_group_size", C.c_int, [_VP]),
@@ -240,6 +248,17 @@ def read_pfm(path):
     a = np.frombuffer(data, dtype="<f4" if scale < 0 else ">f4", count=w * h * ch, offset=pos).astype(np.float32)
     a = a.reshape((h, w, 3) if ch == 3 else (h, w))
     return np.ascontiguousarray(a[::-1])
+
+
+def denoise_params(**params):
+    """A DrDenoiseParams: the library's defaults (dr_denoise_defaults) with the given fields replaced."""
+    p = DrDenoiseParams()
+    _check(lib().dr_denoise_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in dict(DrDenoiseParams._fields_):
+            raise TypeError("unknown denoise parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrDenoiseParams._fields_)))
+        setattr(p, k, v)
+    return p
 
 
 def pack_settings13(s, divisor, spp=None, depth=None):
@@ -576,6 +595,36 @@ class Context:
             st[7] = a["depth"][0, 0]
         return st
 
+    # ---- denoiser (dr_accum_denoise)
+    def denoise(self, settings13, W, H, divide_by, out="rgb8", device=False, **params):
+        """The accumulator divided by divide_by, filtered by the AOV-guided a-trous denoiser (include/dogeray_amd.h dr_accum_denoise), in
+        accum_present's layout: out="rgb8" -> uint8[H, W, 3], "f32" -> float32[H, W, 3] (0..255 units, unclamped), "both" -> (rgb8, f32).
+        params: the fields of dr_denoise_params (iterations, sigma_luminance, normal_power_log2, sigma_depth, demodulate, material_stop), the
+        rest at their defaults.  device=True: torch tensors on this context's GPU, with render_aov's stream handshake."""
+        st = _f32(settings13)
+        assert st.shape == (13,)
+        if out not in ("rgb8", "f32", "both"):
+            raise ValueError("out must be 'rgb8', 'f32' or 'both', not %r" % (out,))
+        p = denoise_params(**params)
+        want_rgb, want_f32 = out in ("rgb8", "both"), out in ("f32", "both")
+        if not device:
+            rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
+            f = np.empty((H, W, 3), np.float32) if want_f32 else None
+            _check(lib().dr_accum_denoise(self._h, _p(st), W, H, int(divide_by), C.byref(p), _p(f) if f is not None else None,
+                                          _p(rgb) if rgb is not None else None, 0))
+        else:
+            import torch
+            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+            rgb = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev) if want_rgb else None
+            f = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev) if want_f32 else None
+            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+            cur = torch.cuda.current_stream(dev)
+            lib_stream.wait_stream(cur)
+            _check(lib().dr_accum_denoise(self._h, _p(st), W, H, int(divide_by), C.byref(p), f.data_ptr() if f is not None else None,
+                                          rgb.data_ptr() if rgb is not None else None, 1))
+            cur.wait_stream(lib_stream)
+        return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
+
     # ---- known-answer hooks (tests)
     def kat_rng(self, seed, n):
         out = np.zeros(n, dtype=np.float64)
@@ -742,8 +791,21 @@ class ProgressiveRenderer:
         self.iter += 1
         return td, self.iter - pnum
 
-    def image(self, divide_by):
-        return self.ctx.accum_present(divide_by)
+    def image(self, divide_by, denoise=None):
+        """The displayed image: accum_present(divide_by); with denoise (True, or a dict of dr_denoise_params fields) the same image through
+        Context.denoise, guided by the AOVs of the settings the last step() rendered with."""
+        if denoise is None or denoise is False:
+            return self.ctx.accum_present(divide_by)
+        params = {} if denoise is True else dict(denoise)
+        return self.ctx.denoise(self.settings13(), self.W, self.H, divide_by, **params)
+
+    def settings13(self):
+        """The settings13 of the last step(): the preview ladder's divisor / spp / depth for the first four, the file's after them."""
+        s = self.s
+        if 1 <= self.iter <= 4:
+            k = self.iter - 1
+            return pack_settings13(s, self.LADDER[k], spp=s.spp if k == 0 else 1, depth=s.max_depth if k == 0 else 2)
+        return pack_settings13(s, 1)
 
     def run_pipelined(self, nframes, on_image=None, in_flight=None):
         """The accumulating part of the loop (iter >= 4), `nframes` frames, pipelined (dr_pipeline_submit / dr_pipeline_wait): up to `in_flight` frames

@@ -38,6 +38,13 @@ struct dr_context {
   int32_t* slot_to_orig_dev = nullptr;     // the same map on the device: uploaded by the first dr_render_aov after a scene upload
   // dr_render_aov with host pointers: the channels are written here, then downloaded
   uint8_t* aov_staging = nullptr; size_t aov_staging_bytes = 0;
+  // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
+  // guides' key (settings13, W, H, scene generation), and the staging of host outputs
+  float* dn_planes = nullptr; size_t dn_planes_floats = 0;
+  bool dn_valid = false; float dn_key[13] = {0}; int dn_W = 0, dn_H = 0; uint64_t dn_gen = 0;
+  uint8_t* dn_staging = nullptr; size_t dn_staging_bytes = 0;
+  uint64_t scene_gen = 0;                  // scene uploads so far
+  int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
   // frame + accumulator
   int32_t* frame = nullptr; size_t frame_elems = 0;
   int32_t* accum = nullptr; size_t accum_elems = 0; int accW = 0, accH = 0;
@@ -289,6 +296,7 @@ int set_option(dr_context* c, const std::string& name, int v) {
   else if (name == "order_follows_camera") { c->order_follows_camera = v != 0; }
   else if (name == "feedback_every") { if (v < 1) goto bad; c->feedback_every = v; }
   else if (name == "wide_tree") { if (v < 0 || v > 2) goto bad; c->wide_tree = v; }      // takes effect at the next dr_context_upload_scene
+  else if (name == "denoise_tiles") { if (v != 0 && v != 1) goto bad; c->denoise_tiles = v; }
   else { set_error("unknown option '" + name + "'"); return DR_ERR_INVALID; }
   return DR_OK;
 bad:
@@ -426,7 +434,7 @@ void dr_context_destroy(dr_context* c) {
   for (int k = 1; k < dr_context::PIPE_STREAMS; k++) if (c->pipe_stream[k]) (void)hipStreamSynchronize(c->pipe_stream[k]);
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
   void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
-                  c->slot_to_orig_dev, c->aov_staging};
+                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -451,6 +459,8 @@ void dr_context_destroy(dr_context* c) {
 int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   if (!c || !s) { set_error("null argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  c->scene_gen++;                  // the denoiser's cached guides belong to the old scene
+  c->dn_valid = false;
   DeviceImage img;
   int rc = DR_OK;
   try {
@@ -527,6 +537,7 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
   else if (n == "wide_own_bounds") *value = c->wide ? c->wide_own_bounds : 0;
   else if (n == "wide_depth") *value = c->wide ? c->wide_depth : 0;          // 0: the scene has no wide structure
   else if (n == "wide_nodes") *value = c->wide ? c->wide_nodes : 0;
+  else if (n == "denoise_tiles") *value = c->denoise_tiles;
   else if (n == "traversal") *value = traversal_of(c);                        // the traversal launches really use
   else { set_error("unknown option " + n); return DR_ERR_INVALID; }
   return DR_OK;
@@ -580,18 +591,35 @@ int dr_accum_reset(dr_context* c, int W, int H) {
   return DR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The view of a first-hit AOV pass (dr_render_aov, dr_accum_denoise): the settings judged as dr_render_frame judges them (make_params), without
+// touching the context's state, and the resident scene's buffers
+int aov_view(dr_context* c, const float settings13[13], int W, int H, RenderParams& P, int& traversal) {
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
+  if (P.backtex >= c->n_tex) { set_error("backtex refers to a texture that is not loaded"); return DR_ERR_INVALID; }
+  traversal = traversal_of(c);
+  if (traversal == DR_TRAVERSAL_ORDERED && c->tree_depth > ORDERED_STACK) { set_error("tree too deep for ordered traversal"); return DR_ERR_SCENE; }
+  P.walk = c->walk; P.walk_bytes = (uint32_t)c->walk_bytes; P.pairs = c->pairs; P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
+  P.wide = c->wide; P.wide_bytes = (uint32_t)c->wide_bytes; P.wide_pmax = c->wide_pmax; P.wide_mu = c->wide_mu;
+  return DR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
                   int device_pointers) {
   if (!c || !settings13 || !buffers) { set_error("null argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
-  // the settings are judged as dr_render_frame judges them (make_params), without touching the context's state
   RenderParams P;
-  memset(&P, 0, sizeof(P));
-  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
-  if (P.backtex >= c->n_tex) { set_error("backtex refers to a texture that is not loaded"); return DR_ERR_INVALID; }
-  const int traversal = traversal_of(c);
-  if (traversal == DR_TRAVERSAL_ORDERED && c->tree_depth > ORDERED_STACK) { set_error("tree too deep for ordered traversal"); return DR_ERR_SCENE; }
+  int traversal = 0;
+  { const int rc = aov_view(c, settings13, W, H, P, traversal); if (rc != DR_OK) return rc; }
   const int gw = P.gx * 8, gh = P.gy * 8;
   if (w <= 0 || h <= 0) { set_error("empty AOV window"); return DR_ERR_INVALID; }
   if (x0 < 0 || y0 < 0 || x0 > gw - w || y0 > gh - h) {
@@ -605,8 +633,6 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
     if (!c->slot_to_orig.empty())
       HIP_TRY(hipMemcpyAsync(c->slot_to_orig_dev, c->slot_to_orig.data(), c->slot_to_orig.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
-  P.walk = c->walk; P.walk_bytes = (uint32_t)c->walk_bytes; P.pairs = c->pairs; P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
-  P.wide = c->wide; P.wide_bytes = (uint32_t)c->wide_bytes; P.wide_pmax = c->wide_pmax; P.wide_mu = c->wide_mu;
   AovLaunch A;
   A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
   A.focus = settings13[7];
@@ -638,6 +664,113 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
   if (device_pointers) return DR_OK;
   for (int k = 0; k < 9; k++)
     if (want[k]) HIP_TRY(hipMemcpyAsync(want[k], dev[k], npix * (size_t)words[k] * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+int dr_denoise_defaults(dr_denoise_params* p) {
+  if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
+  p->iterations = 5; p->sigma_luminance = 4.0f; p->normal_power_log2 = 7; p->sigma_depth = 1.0f; p->demodulate = 1; p->material_stop = 1;
+  return DR_OK;
+}
+
+int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_denoise_params* params, float* out_f32,
+                     uint8_t* out_rgb8, int device_pointers) {
+  if (!c || !settings13) { set_error("null argument"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  RenderParams P;
+  int traversal = 0;
+  { const int rc = aov_view(c, settings13, W, H, P, traversal); if (rc != DR_OK) return rc; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  if (W != c->accW || H != c->accH) {
+    set_error("denoise: " + std::to_string(W) + " x " + std::to_string(H) + " is not the accumulator's " + std::to_string(c->accW) + " x " + std::to_string(c->accH));
+    return DR_ERR_INVALID;
+  }
+  if (divide_by < 1) { set_error("denoise: divide_by must be >= 1"); return DR_ERR_INVALID; }
+  dr_denoise_params p;
+  dr_denoise_defaults(&p);
+  if (params) p = *params;
+  if (p.iterations < 0 || p.iterations > DN_MAX_ITERATIONS) { set_error("denoise: iterations must be 0 .. 10"); return DR_ERR_INVALID; }
+  if (!(p.sigma_luminance >= 0.0f) || !(p.sigma_depth >= 0.0f)) { set_error("denoise: sigma_luminance and sigma_depth must be >= 0"); return DR_ERR_INVALID; }
+  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { set_error("denoise: normal_power_log2 must be 0 .. 16"); return DR_ERR_INVALID; }
+  if (!out_f32 && !out_rgb8) { set_error("denoise: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
+
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  const size_t n = (size_t)gw * (size_t)gh, npix = (size_t)W * (size_t)H;
+  DnLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
+  L.D.iterations = p.iterations; L.D.sigma_luminance = p.sigma_luminance; L.D.normal_power_log2 = p.normal_power_log2;
+  L.D.sigma_depth = p.sigma_depth; L.D.demodulate = p.demodulate != 0; L.D.material_stop = p.material_stop != 0;
+  L.acc = c->accum;
+  if (p.iterations > 0 && n > 0) {
+    // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
+    const size_t need = 17 * n;
+    if (need > c->dn_planes_floats) {
+      if (c->dn_planes) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_planes); c->dn_planes = nullptr; c->dn_planes_floats = 0; }
+      c->dn_valid = false;
+      HIP_TRY(hipMalloc((void**)&c->dn_planes, need * sizeof(float)));
+      c->dn_planes_floats = need;
+    }
+    float* const guide = c->dn_planes;
+    float* const pa = guide + 4 * n;
+    float* const pb = pa + 4 * n;
+    float* const albedo = pb + 4 * n;
+    int32_t* const mat = reinterpret_cast<int32_t*>(albedo + 3 * n);
+    float* const gz = reinterpret_cast<float*>(mat + n);
+    L.albedo = albedo; L.mat = mat; L.guide = guide; L.gz = gz;
+    const bool same = c->dn_valid && c->dn_W == W && c->dn_H == H && c->dn_gen == c->scene_gen && memcmp(c->dn_key, settings13, sizeof(c->dn_key)) == 0;
+    if (!same) {
+      // the guides: launch_aov writes normal and depth into colour plane A (3n + n floats), albedo and material into their planes; the guide
+      // prepare packs (n, z) and forms gz from them
+      AovLaunch A;
+      memset(&A, 0, sizeof(A));
+      A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
+      A.focus = settings13[7];
+      A.slot_to_orig = c->slot_to_orig_dev;
+      A.normal = pa; A.depth = pa + 3 * n; A.albedo = albedo; A.material = mat;
+      launch_aov(c->stream, P, traversal, A);
+      HIP_TRY(hipGetLastError());
+      L.normal = pa; L.depth = pa + 3 * n;
+      launch_denoise_guides(c->stream, L);
+      HIP_TRY(hipGetLastError());
+      memcpy(c->dn_key, settings13, sizeof(c->dn_key));
+      c->dn_W = W; c->dn_H = H; c->dn_gen = c->scene_gen; c->dn_valid = true;
+      L.normal = nullptr; L.depth = nullptr;
+    }
+    L.dst = pa;
+    launch_denoise_colour(c->stream, L, 0);                 // acc -> (e, l) in A
+    L.src = pa; L.dst = pb;
+    launch_denoise_colour(c->stream, L, 1);                 // (e, l) -> (e, var) in B
+    L.src = pb; L.dst = pa;                                 // the passes: B -> A -> B ...
+    for (int it = 0; it < p.iterations; it++) {
+      launch_denoise_pass(c->stream, L, 1 << it, c->denoise_tiles);
+      float* const t = const_cast<float*>(L.src);
+      L.src = L.dst; L.dst = t;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  // the outputs: where the caller wants them, or staged and downloaded
+  float* f32_dev = out_f32;
+  uint8_t* rgb_dev = out_rgb8;
+  if (!device_pointers) {
+    const size_t bytes = (out_f32 ? npix * 3 * sizeof(float) : 0) + (out_rgb8 ? npix * 3 : 0);
+    if (bytes > c->dn_staging_bytes) {
+      if (c->dn_staging) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_staging); c->dn_staging = nullptr; c->dn_staging_bytes = 0; }
+      HIP_TRY(hipMalloc((void**)&c->dn_staging, bytes));
+      c->dn_staging_bytes = bytes;
+    }
+    f32_dev = out_f32 ? reinterpret_cast<float*>(c->dn_staging) : nullptr;
+    rgb_dev = out_rgb8 ? c->dn_staging + (out_f32 ? npix * 3 * sizeof(float) : 0) : nullptr;
+  }
+  L.out_f32 = f32_dev; L.out_rgb8 = rgb_dev;
+  launch_denoise_finish(c->stream, L);
+  HIP_TRY(hipGetLastError());
+  if (device_pointers) return DR_OK;
+  if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, f32_dev, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, rgb_dev, npix * 3, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DR_OK;
 }

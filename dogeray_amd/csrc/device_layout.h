@@ -155,4 +155,18 @@ struct RenderParams {
   WideMu wide_mu;                 // wide walk: the margin's scene constants (e = 0: none)
 };
 
+// The denoiser's parameters (dr_denoise_params, validated by dr_accum_denoise / hk_denoise) and its material markers (device_denoise.hpp)
+constexpr int DN_MISS = -1;                    // material of a pixel whose pinhole ray hits nothing (aov_first_hit)
+constexpr int DN_OUTSIDE = -2147483647 - 1;    // material of a tap outside the pixel grid (never a real material)
+constexpr int DN_MAX_ITERATIONS = 10;
+constexpr int DN_MAX_NORMAL_POWER_LOG2 = 16;
+struct DnParams {
+  int iterations;
+  float sigma_luminance;
+  int normal_power_log2;
+  float sigma_depth;
+  int demodulate;
+  int material_stop;
+};
+
 }  // namespace dr

@@ -102,11 +102,21 @@ bool write_aovs(dr_context* ctx, const float st[13], int W, int H, const std::st
          write_pfm(prefix + ".object.pfm", object_f, gw, gh, 1);
 }
 
+// --denoise FILE: the final image through dr_accum_denoise (default parameters), .pfm as floats (0..255 units), .ppm / .bmp as RGB8
+bool write_denoised(dr_context* ctx, const float st[13], int W, int H, int divide_by, const std::string& path) {
+  const bool pfm = ends_with(path, ".pfm");
+  std::vector<float> f(pfm ? (size_t)W * H * 3 : 0);
+  std::vector<uint8_t> rgb(pfm ? 0 : (size_t)W * H * 3);
+  if (dr_accum_denoise(ctx, st, W, H, divide_by, nullptr, pfm ? f.data() : nullptr, pfm ? nullptr : rgb.data(), 0) != DR_OK) return false;
+  if (pfm) return write_pfm(path, f, W, H, 3);
+  return ends_with(path, ".ppm") ? write_ppm(path, rgb, W, H) : write_bmp(path, rgb, W, H);
+}
+
 void usage() {
   fprintf(stderr,
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
-          "               [--aov PREFIX] [--autofocus]\n"
+          "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -118,13 +128,15 @@ void usage() {
           "               it while it is newer than the .rts ('r' fields and textures are frozen in it: delete it to redraw)\n"
           "  --aov        after the render, write the first-hit buffers of the view (pinhole rays through the pixel centres) as\n"
           "               PREFIX.depth.pfm, .distance.pfm, .normal.pfm, .albedo.pfm and .object.pfm (object ids as floats, exact below 2^24)\n"
-          "  --autofocus  before rendering, set the focus distance to the depth of what the centre pixel sees (the reference's Z/X keys)\n");
+          "  --autofocus  before rendering, set the focus distance to the depth of what the centre pixel sees (the reference's Z/X keys)\n"
+          "  --denoise    after the render, also write the final image through the AOV-guided a-trous denoiser (dr_accum_denoise, default\n"
+          "               parameters): .bmp / .ppm as RGB8, .pfm as floats in 0..255 units (--gpus N: on rank 0's context after the final gather)\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string scene_path = "scene.rts", out_path, aov_prefix;
+  std::string scene_path = "scene.rts", out_path, aov_prefix, denoise_path;
   const char* texdir = nullptr;
   int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0;
   uint64_t seed = 1;
@@ -148,6 +160,7 @@ int main(int argc, char** argv) {
     else if (a == "--cache") use_cache = true;
     else if (a == "--aov") aov_prefix = next();
     else if (a == "--autofocus") autofocus = true;
+    else if (a == "--denoise") denoise_path = next();
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
@@ -300,6 +313,12 @@ int main(int argc, char** argv) {
     pack13(s, 1, s.spp, s.max_depth, st);
     if (!write_aovs(ctx, st, W, H, aov_prefix)) { fprintf(stderr, "dogeray: cannot write the AOVs %s.*.pfm: %s\n", aov_prefix.c_str(), dr_last_error()); return 1; }
     printf("exported AOVs:%s.{depth,distance,normal,albedo,object}.pfm\n", aov_prefix.c_str());
+  }
+  if (!denoise_path.empty()) {
+    float st[13];
+    pack13(s, 1, s.spp, s.max_depth, st);
+    if (!write_denoised(ctx, st, W, H, divide_by, denoise_path)) { fprintf(stderr, "dogeray: cannot write the denoised image %s: %s\n", denoise_path.c_str(), dr_last_error()); return 1; }
+    printf("exported denoised image:%s\n", denoise_path.c_str());
   }
   if (grp) dr_group_destroy(grp); else dr_context_destroy(ctx);
   dr_scene_free(scene);

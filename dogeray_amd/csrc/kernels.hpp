@@ -2,6 +2,7 @@
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
 //   kernels_aux.hip           tile-order feedback, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
+//   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
 #pragma once
@@ -68,5 +69,28 @@ struct AovLaunch {
   float* normal; float* uv; float* albedo; float* dir;
 };
 void launch_aov(hipStream_t stream, const RenderParams& P, int traversal, const AovLaunch& A);
+
+// kernels_denoise.hip: planes of the gw x gh pixel grid, row-major (pixel (x, y) at y * gw + x), as launch_aov writes them
+struct DnLaunch {
+  int gw, gh;                     // pixel grid
+  int W, H;                       // accumulator (column-major, (x * H + y) * 3) and output (row-major W x H x 3)
+  int divide_by;
+  DnParams D;
+  const int32_t* acc;
+  const float* normal;            // launch_aov's normal (3 per pixel) and depth: read by the guide prepare only
+  const float* depth;
+  const float* albedo;            // launch_aov's albedo (3 per pixel)
+  const int32_t* mat;             // launch_aov's material (-1: miss)
+  float* guide;                   // float4 (n.x, n.y, n.z, z)
+  float* gz;                      // depth gradient
+  const float* src;               // colour planes, float4 per pixel: (e, l) or (e, var)
+  float* dst;
+  float* out_f32;                 // W x H x 3 (null: not written)
+  uint8_t* out_rgb8;
+};
+void launch_denoise_guides(hipStream_t stream, const DnLaunch& L);                 // normal, depth, mat -> guide, gz
+void launch_denoise_colour(hipStream_t stream, const DnLaunch& L, int stage);      // 0: acc -> (e, l) in dst; 1: src (e, l) -> (e, var) in dst
+void launch_denoise_pass(hipStream_t stream, const DnLaunch& L, int step, int lattice);   // src -> dst, one a-trous iteration
+void launch_denoise_finish(hipStream_t stream, const DnLaunch& L);                 // src (or, iterations 0, acc) -> out_f32 / out_rgb8
 
 }  // namespace dr

@@ -188,6 +188,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   triangles entered with their own bounds instead of the reference's leaf box (those bounds padded by 0.01, K:353-354)
  *                   and every ray carrying the margin that keeps the accepted hits the reference's; 1 the same tree
  *                   over the reference's leaf boxes; 0 the reference's own topology (K:1745-1861) collapsed 4-way
+ *   "denoise_tiles" dr_accum_denoise's a-trous passes: 1 (default) one workgroup per 16x16 lattice tile staged in LDS, 0 every tap loaded from
+ *                   the planes; the same bits either way
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -309,6 +311,56 @@ typedef struct dr_aov_buffers {
  * upload copies the slot -> object map to the device. */
 int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
                   int device_pointers);
+
+/* ------------------------------------------------------------------ denoiser ------------ */
+/* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by
+ * the first-hit AOVs of the same settings13 (dr_render_aov).  No temporal reprojection: the accumulator is the temporal mean already.  Every
+ * weight is + - * /, sqrtf, fminf / fmaxf and comparisons in the order written here (dogeray_amd/csrc/device_denoise.hpp, no FMA contraction),
+ * so the GPU is bit-identical to the host build of the same source and to the numpy restatement in the tests.
+ *   grid       the pixel grid of dr_render_aov: gw x gh = (W / div / 8) * 8 x (H / div / 8) * 8; pixel p = (x, y)
+ *   guides     normal n (3 f32), albedo a (3 f32), depth z, material m (-1: a miss) of p's pinhole ray (dr_render_aov's channels)
+ *   colour     c = (float)acc / (float)divide_by per channel, acc the column-major accumulator at (x * H + y) * 3
+ *   demodulate e = c / a', a' = (m == -1 || a <= 1e-3f || !demodulate) ? 1 : a, per channel; l = (0.2126f e.r + 0.7152f e.g) + 0.0722f e.b
+ *   q(x)       (1 + x) + (0.5 x) x; phi(x) = 1 / q(x) (phi(inf) = 0) is the rational stand-in for exp(-x)
+ *   gz_p       fmaxf(gx, gy), gx = fminf(|z(x+1) - z_p|, |z_p - z(x-1)|), a neighbour outside the grid or a miss counting as +inf, an axis with
+ *              no usable neighbour giving 0; gy likewise along y
+ *   pair       g(p, q) = num / den for q = p + step (dx, dy), k = |dx| + |dy|:
+ *                q outside the grid, exactly one of p, q a miss, or material_stop and m_p != m_q: no tap
+ *                q = p, or both miss: 1 / 1
+ *                otherwise num = wn = fmaxf((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0), squared normal_power_log2 times;
+ *                den = q(xz), xz = dz > 0 ? dz * rz_k : 0, dz = |z_p - z_q|, rz_k = 1 / ((sigma_depth * gz_p) * (float)(step * k) + 1e-3f * z_p)
+ *   variance   var_p = fmaxf(mu2 - mu1 * mu1, 0), mu1 = s1 / sw, mu2 = s2 / sw: over the 5x5 taps at step 1 inside the grid (dy = -2 .. 2
+ *              outer, dx = -2 .. 2 inner) w = num / den, sw += w, s1 += w * l_q, s2 += w * (l_q * l_q)
+ *   iteration  i = 0 .. iterations - 1, step = 2^i, l recomputed from the current e:
+ *                gv_p = (sum kk var_q) / (sum kk) over the 3x3 taps at the same step that are not "no tap" above (dy outer, dx inner),
+ *                       kk = k[dx] * k[dy], k = (1/4, 1/2, 1/4): the variance crosses no edge stop either, so pixels of one material (and
+ *                       hit pixels against misses) are filtered independently of the others' colour, bit for bit
+ *                rl = 1 / (sigma_luminance * sqrtf(gv_p) + 1e-4f)
+ *                w = ((h[dx] * h[dy]) * num) / (den * q(|l_p - l_q| * rl)), h = (1/16, 1/4, 3/8, 1/4, 1/16), over the 5x5 taps as above
+ *                e' = (sum w e_q) / sw per channel, var' = (sum (w * w) var_q) / (sw * sw); the centre's w is h[0]^2 > 0
+ *   output     f = e * a' per channel: out_f32 row-major W x H x 3 in the accumulator's 0..255 units, unclamped; out_rgb8 =
+ *              (uint8)(int)fminf(fmaxf(f, 0), 255) -- dr_accum_present's layout; pixels outside the grid are 0
+ *   iterations 0: no filter and no demodulation, f = c: out_rgb8 is dr_accum_present(divide_by) byte for byte for divide_by < 65536 and
+ *              |acc| < 2^24
+ * The guides are pinhole rays through the pixel centres: with aperture > 0 the defocused parts of the image are filtered against sharp guides. */
+typedef struct dr_denoise_params {
+  int iterations;          /* 0 .. 10, default 5 */
+  float sigma_luminance;   /* >= 0, default 4 */
+  int normal_power_log2;   /* 0 .. 16, default 7 (wn^128, as SVGF) */
+  float sigma_depth;       /* >= 0, default 1 */
+  int demodulate;          /* default 1: filter c / albedo, then multiply the albedo back */
+  int material_stop;       /* default 1: no weight between pixels of different materials */
+} dr_denoise_params;
+int dr_denoise_defaults(dr_denoise_params* p);
+/* The denoised image of the accumulator (divided by divide_by) into out_f32 (W * H * 3 floats) and / or out_rgb8 (W * H * 3 bytes), either NULL
+ * (not both).  params NULL: the defaults.  device_pointers = 0: host buffers, the call returns when they are filled; 1: device buffers on this
+ * context's GPU, the work is queued on dr_context_stream.  The guides are computed by the AOV kernel into context-owned planes and kept for the
+ * next call with the same settings13, W, H and scene (dr_context_upload_scene drops them); a context that never denoises allocates nothing for
+ * it.  Ordered behind the frames submitted before it (dr_pipeline_submit); changes neither the accumulator, nor dr_stats, the stripe or any
+ * option.  The settings are accepted or refused as by dr_render_aov; DR_ERR_INVALID for no scene, no accumulator, W / H not the accumulator's,
+ * divide_by < 1, iterations outside 0 .. 10, a negative sigma, normal_power_log2 outside 0 .. 16, or no output. */
+int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_denoise_params* params, float* out_f32,
+                     uint8_t* out_rgb8, int device_pointers);
 
 /* ------------------------------------------------------------------ multi-GPU group ----- */
 /* One process, one context and one host thread per GPU (the reference is single-device, K:2614-2615).  Rank r of n

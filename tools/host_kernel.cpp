@@ -10,12 +10,14 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
+#include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
 #include "../dogeray_amd/csrc/scene_host.hpp"
@@ -242,6 +244,111 @@ int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int 
         }
     });
   for (std::thread& x : th) x.join();
+  return 0;
+}
+
+// dr_accum_denoise on the host: device_denoise.hpp over the pixel grid of settings13, stage by stage as kernels_denoise.hip runs it, from guides given
+// as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
+// W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
+// Returns 0, or -1 with hk_last_error.
+int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads) {
+  if (!acc || !settings13 || !normal || !albedo || !depth || !material) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  DnParams D = {5, 4.0f, 7, 1.0f, 1, 1};
+  if (params) {                      // dr_denoise_params: int, float, int, float, int, int
+    memcpy(&D.iterations, params, 4); memcpy(&D.sigma_luminance, params + 1, 4); memcpy(&D.normal_power_log2, params + 2, 4);
+    memcpy(&D.sigma_depth, params + 3, 4); memcpy(&D.demodulate, params + 4, 4); memcpy(&D.material_stop, params + 5, 4);
+  }
+  if (divide_by < 1 || D.iterations < 0 || D.iterations > DN_MAX_ITERATIONS || !(D.sigma_luminance >= 0.0f) || !(D.sigma_depth >= 0.0f) ||
+      D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { hk_err = "bad denoise parameters"; return -1; }
+  D.demodulate = D.demodulate != 0; D.material_stop = D.material_stop != 0;
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  const size_t n = (size_t)gw * gh;
+  if (nthreads < 1) nthreads = 1;
+  auto rows = [&](int count, const std::function<void(int)>& f) {          // f(row) for every row, rows interleaved over the threads
+    std::vector<std::thread> th;
+    for (int k = 0; k < nthreads; k++) th.emplace_back([&, k] { for (int r = k; r < count; r += nthreads) f(r); });
+    for (std::thread& t : th) t.join();
+  };
+  std::vector<float4> guide(n), pa(n), pb(n);
+  std::vector<float> gz(n);
+  auto mat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? DN_OUTSIDE : (int)material[(size_t)y * gw + x]; };
+  auto zat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? 0.0f : depth[(size_t)y * gw + x]; };
+  if (D.iterations > 0) {
+    rows(gh, [&](int y) {                                                  // guide prepare
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        gz[i] = dn_gradient(zat(x, y), mat(x, y), zat(x - 1, y), mat(x - 1, y), zat(x + 1, y), mat(x + 1, y), zat(x, y - 1), mat(x, y - 1), zat(x, y + 1), mat(x, y + 1));
+        guide[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+      }
+    });
+    rows(gh, [&](int y) {                                                  // colour prepare, stage 0
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        const int32_t* a = acc + ((size_t)x * (size_t)H + (size_t)y) * 3;
+        const float nd = (float)divide_by;
+        const int m = material[i];
+        const float er = ((float)a[0] / nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
+        const float eg = ((float)a[1] / nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
+        const float eb = ((float)a[2] / nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
+        pa[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
+      }
+    });
+    auto tap = [&](const std::vector<float4>& src, int x, int y) {
+      DnTap q;
+      q.m = mat(x, y);
+      if (q.m == DN_OUTSIDE) { q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
+      const size_t j = (size_t)y * gw + x;
+      q.c = src[j]; q.g = guide[j];
+      return q;
+    };
+    rows(gh, [&](int y) {                                                  // colour prepare, stage 1: the variance pre-pass
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        const float var = dn_variance(D, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
+        pb[i] = make_float4(pa[i].x, pa[i].y, pa[i].z, var);
+      }
+    });
+    std::vector<float4>* src = &pb;
+    std::vector<float4>* dst = &pa;
+    for (int it = 0; it < D.iterations; it++) {
+      const int step = 1 << it;
+      rows(gh, [&](int y) {
+        for (int x = 0; x < gw; x++) {
+          const size_t i = (size_t)y * gw + x;
+          (*dst)[i] = dn_atrous(D, step, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(*src, x + step * dx, y + step * dy); });
+        }
+      });
+      std::swap(src, dst);
+    }
+    pa.swap(*src);                                                         // pa: the filtered (e, var)
+  }
+  rows(H, [&](int y) {                                                     // finish
+    for (int x = 0; x < W; x++) {
+      float f[3] = {0.0f, 0.0f, 0.0f};
+      if (x < gw && y < gh) {
+        const size_t i = (size_t)y * gw + x;
+        if (D.iterations == 0) {
+          const int32_t* a = acc + ((size_t)x * (size_t)H + (size_t)y) * 3;
+          const float nd = (float)divide_by;
+          f[0] = (float)a[0] / nd; f[1] = (float)a[1] / nd; f[2] = (float)a[2] / nd;
+        } else {
+          const int m = material[i];
+          f[0] = pa[i].x * dn_albedo(albedo[3 * i], m, D.demodulate);
+          f[1] = pa[i].y * dn_albedo(albedo[3 * i + 1], m, D.demodulate);
+          f[2] = pa[i].z * dn_albedo(albedo[3 * i + 2], m, D.demodulate);
+        }
+      }
+      const size_t o = ((size_t)y * W + x) * 3;
+      for (int k = 0; k < 3; k++) {
+        if (out_f32) out_f32[o + k] = f[k];
+        if (out_rgb8) out_rgb8[o + k] = dn_rgb8(f[k]);
+      }
+    }
+  });
   return 0;
 }
 

@@ -48,6 +48,7 @@ def lib():
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
         L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.hk_aov.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 9
+        L.hk_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int]
         _lib = L
     return _lib
 
@@ -100,3 +101,31 @@ class Scene:
         if rc != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return out
+
+
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "normal_power_log2": 7, "sigma_depth": 1.0, "demodulate": 1, "material_stop": 1}
+
+
+def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthreads=4, **params):
+    """dr_accum_denoise on the host (device_denoise.hpp): the accumulator acc (int32[W, H, 3], column-major as dr_accum_read returns it) and the
+    guides as arrays shaped like dogeray_amd.Context.render_aov's (normal / albedo [gh, gw, 3], depth / material [gh, gw]) -> (f32[H, W, 3],
+    uint8[H, W, 3]) in dr_accum_present's layout.  params: the fields of dr_denoise_params (the rest default)."""
+    acc = np.ascontiguousarray(acc, dtype=np.int32)
+    W, H = acc.shape[0], acc.shape[1]
+    st = np.ascontiguousarray(settings13, dtype=np.float32)
+    p = dict(DENOISE_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError("unknown denoise parameter %r" % k)
+        p[k] = v
+    raw = np.array([p["iterations"], 0, p["normal_power_log2"], 0, p["demodulate"], p["material_stop"]], dtype=np.int32)
+    raw[1] = np.array([p["sigma_luminance"]], np.float32).view(np.int32)[0]
+    raw[3] = np.array([p["sigma_depth"]], np.float32).view(np.int32)[0]
+    guides = [np.ascontiguousarray(a, dtype=t) for a, t in ((normal, np.float32), (albedo, np.float32), (depth, np.float32), (material, np.int32))]
+    f32 = np.zeros((H, W, 3), np.float32)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    rc = lib().hk_denoise(acc.ctypes.data, W, H, int(divide_by), st.ctypes.data, *[g.ctypes.data for g in guides], raw.ctypes.data,
+                          f32.ctypes.data, rgb.ctypes.data, nthreads)
+    if rc != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    return f32, rgb
