@@ -147,6 +147,7 @@ _API = [
     ("dr_stats_get", C.c_int, [_VP, C.POINTER(DrStats)]),
     ("dr_context_probe_trace", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("dr_stats_phase_counts", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int]),
+    ("dr_stats_cert_mask", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
@@ -507,6 +508,16 @@ class Context:
         buf = (C.c_ulonglong * n)()
         _check(lib().dr_stats_phase_counts(self._h, buf, n))
         return [int(v) for v in buf]
+
+    def cert_mask(self):
+        """uint32 words of the last certified view's tile mask (dr_stats_cert_mask; bit set = the tile's camera rays keep the scene's margin),
+        or an empty array when no certificate is in use."""
+        n = C.c_int()
+        _check(lib().dr_stats_cert_mask(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value + 31) // 32, dtype=np.uint32)
+        if len(out):
+            _check(lib().dr_stats_cert_mask(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
+        return out
 
     def wave_log(self, max_waves=16384):
         """(n, 16) uint64: begin, queue-empty, end stamps (100 MHz ticks) and iterations after the queue was empty, per wave of the

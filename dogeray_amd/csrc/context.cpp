@@ -45,6 +45,17 @@ struct dr_context {
   uint8_t* dn_staging = nullptr; size_t dn_staging_bytes = 0;
   uint64_t scene_gen = 0;                  // scene uploads so far
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
+  // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
+  // computed on `stream` by launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload and cert_factor
+  int camera_cert = 1;                     // option: camera rays of tiles the certificate clears carry the certified margin (0: every ray the scene's)
+  int cert_factor = 40;                    // option: the certified |a^| in units of hit_tri's 1e-4 cut-off (a_star = cert_factor * 1e-4)
+  uint32_t* cert_mask = nullptr; size_t cert_words = 0;
+  bool cert_valid = false;                 // cert_key's mask is computed (or known to be unusable: cert_ok false)
+  bool cert_ok = false;
+  float cert_key[21] = {0};
+  float cert_seen[21] = {0};               // the key of the last single-frame launch that found no mask
+  float cert_k = 1;                        // the certified margin's factor (1e-4 / a_star, rounded up)
+  int cert_tiles = 0;                      // tiles of the keyed launch
   // frame + accumulator
   int32_t* frame = nullptr; size_t frame_elems = 0;
   int32_t* accum = nullptr; size_t accum_elems = 0; int accW = 0, accH = 0;
@@ -220,6 +231,42 @@ PersistentCfg persistent_cfg(const dr_context* c) {
   return cfg;
 }
 
+// The camera rays' grazing certificate of the launch's view: reuses the cached mask when the key matches, recomputes it on `stream`
+// otherwise -- except in a pipelined launch that may run beside others reading the mask (pipe_hold_order): that one keeps the scene's margin.
+// Without a usable certificate P keeps cert_mask = null and wide_cert_k = 1: every ray carries the scene's margin, as before.
+void cert_prepare(dr_context* c, RenderParams& P, int tiles) {
+  P.cert_mask = nullptr; P.wide_cert_k = 1.0f;
+  if (!c->camera_cert || traversal_of(c) != DR_TRAVERSAL_WIDE || !c->wide || c->wide_own_bounds <= 0 || !(c->wide_mu.e > 0.0f) || tiles <= 0) return;
+  float key[21] = {0};
+  memcpy(key, c->cur_settings, 13 * sizeof(float));
+  key[13] = (float)P.W; key[14] = (float)P.H; key[15] = (float)P.stripe_mod; key[16] = (float)P.stripe_rem; key[17] = (float)P.ncols; key[18] = (float)P.gy;
+  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor;
+  if (!(c->cert_valid && memcmp(c->cert_key, key, sizeof(key)) == 0)) {
+    if (c->pipe_hold_order) return;
+    // a single-frame launch of a view not seen before (a moving camera: every frame a new view) does not pay for the mask (0.16 ms, more than it
+    // saves in one frame): the view's second launch, or any launch of several frames, computes it
+    if (P.batch < 2 && memcmp(c->cert_seen, key, sizeof(key)) != 0) { memcpy(c->cert_seen, key, sizeof(key)); return; }
+    const double a_star = 1e-4 * (double)c->cert_factor;
+    CertView cv;
+    c->cert_valid = false;
+    c->cert_ok = fill_cert_view(P, a_star, c->wide_mu.e, cv);
+    if (c->cert_ok) {
+      const size_t words = (size_t)(tiles + 31) / 32 + 2;
+      if (c->cert_words < words) {
+        if (c->cert_mask) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->cert_mask); c->cert_mask = nullptr; c->cert_words = 0; }
+        if (hipMalloc((void**)&c->cert_mask, words * sizeof(uint32_t)) != hipSuccess) { c->cert_mask = nullptr; return; }
+        c->cert_words = words;
+      }
+      launch_cert_mask(c->stream, c->prims, c->n_prims, cv, c->cert_mask, tiles);
+      c->cert_k = cert_factor_k(a_star);
+    }
+    memcpy(c->cert_key, key, sizeof(key));
+    c->cert_tiles = tiles;
+    c->cert_valid = true;
+  }
+  if (c->cert_ok) { P.cert_mask = c->cert_mask; P.wide_cert_k = c->cert_k; }
+}
+
 // enqueue one launch (P.batch frames); no events, no sync
 void enqueue_frame(dr_context* c, const RenderParams& P_in) {
   RenderParams P = P_in;
@@ -239,6 +286,7 @@ void enqueue_frame(dr_context* c, const RenderParams& P_in) {
       pcost = nullptr;
     } else feedback_buffers(c, P, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
+    cert_prepare(c, P, tiles);
     c->wave_log_waves = launch_persistent_kernel(c->stream, P, persistent_cfg(c), counter, order, c->region_start, pcost);
     // next launch's order from this launch's costs (stream-ordered, no host sync).  The view does not change between the frames of
     // a progressive render, so after the first two launches of a view the order is refreshed every feedback_every-th launch only
@@ -257,6 +305,7 @@ void enqueue_frame(dr_context* c, const RenderParams& P_in) {
 
 int join_pipeline(dr_context* c);
 
+int pipeline_flush(dr_context* c);
 int set_option(dr_context* c, const std::string& name, int v) {
   if (name == "kernel") { if (v != DR_KERNEL_TILE && v != DR_KERNEL_PERSISTENT) goto bad; c->kernel = v; }
   else if (name == "occupancy") { if (v != 4 && v != 5 && v != 6) goto bad; c->occupancy = v; }
@@ -297,6 +346,13 @@ int set_option(dr_context* c, const std::string& name, int v) {
   else if (name == "feedback_every") { if (v < 1) goto bad; c->feedback_every = v; }
   else if (name == "wide_tree") { if (v < 0 || v > 2) goto bad; c->wide_tree = v; }      // takes effect at the next dr_context_upload_scene
   else if (name == "denoise_tiles") { if (v != 0 && v != 1) goto bad; c->denoise_tiles = v; }
+  else if (name == "camera_cert" || name == "cert_factor") {
+    if (name == "camera_cert" ? (v != 0 && v != 1) : (v < 1 || v > 10000)) goto bad;
+    // frames submitted before the change are launched with the setting they were submitted under
+    if (!c->pipe_pending.empty()) { const int rc = pipeline_flush(c); if (rc != DR_OK) return rc; }
+    if (name == "camera_cert") c->camera_cert = v; else c->cert_factor = v;
+    c->cert_valid = false;
+  }
   else { set_error("unknown option '" + name + "'"); return DR_ERR_INVALID; }
   return DR_OK;
 bad:
@@ -434,7 +490,7 @@ void dr_context_destroy(dr_context* c) {
   for (int k = 1; k < dr_context::PIPE_STREAMS; k++) if (c->pipe_stream[k]) (void)hipStreamSynchronize(c->pipe_stream[k]);
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
   void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
-                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging};
+                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->cert_mask};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -538,6 +594,18 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
   else if (n == "wide_depth") *value = c->wide ? c->wide_depth : 0;          // 0: the scene has no wide structure
   else if (n == "wide_nodes") *value = c->wide ? c->wide_nodes : 0;
   else if (n == "denoise_tiles") *value = c->denoise_tiles;
+  else if (n == "camera_cert") *value = c->camera_cert;
+  else if (n == "cert_factor") *value = c->cert_factor;
+  else if (n == "cert_flagged_permille") {
+    // read-only: per mille of the last certified view's tiles whose camera rays keep the scene's margin (-1: no certificate in use)
+    *value = -1;
+    if (c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0) {
+      uint32_t n_flagged = 0;
+      if (hipStreamSynchronize(c->stream) != hipSuccess ||
+          hipMemcpy(&n_flagged, c->cert_mask + (c->cert_tiles + 31) / 32 + 1, sizeof(n_flagged), hipMemcpyDeviceToHost) != hipSuccess) { set_error("cannot read the certificate mask"); return DR_ERR_DEVICE; }
+      *value = (int)((1000ull * n_flagged + (unsigned)c->cert_tiles / 2) / (unsigned)c->cert_tiles);
+    }
+  }
   else if (n == "traversal") *value = traversal_of(c);                        // the traversal launches really use
   else { set_error("unknown option " + n); return DR_ERR_INVALID; }
   return DR_OK;
@@ -1208,6 +1276,18 @@ int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (n > 0) HIP_TRY(hipMemcpy(out, c->counters + 16, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles) {
+  if (!c || !n_tiles || max_words < 0 || (max_words > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n_tiles = 0;
+  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0)) return DR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const int words = (c->cert_tiles + 31) / 32;
+  *n_tiles = c->cert_tiles;
+  if (max_words > 0) HIP_TRY(hipMemcpy(out, c->cert_mask, (size_t)(words < max_words ? words : max_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return DR_OK;
 }
 

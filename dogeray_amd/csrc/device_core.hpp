@@ -610,18 +610,21 @@ __device__ __forceinline__ WideRay wide_ray_none() {      // a lane without a ra
 // Above the cap the margin is the reference's own padding (B + 0.01 (1 + 2^-16) + the absolute term encloses the padded box): such rays -- camera rays with a
 // long direction vector, mostly -- walk the tree exactly as they would the tree over padded boxes.  Rays or scenes beyond 2^30 take the cap too (no overflow
 // inside the bound's arithmetic below that).
-__device__ __forceinline__ float wide_ray_margin(V3 o, V3 d, float mu_e, float mu_l, float mu_v) {
+// cert: 1, or -- a camera ray whose tile the view's grazing certificate clears (|a^| >= a_star for every triangle it can be accepted on) -- the factor
+// 1e-4 / a_star rounded up (params_host.hpp cert_factor_k): step 2 of the lemma divides by a_star instead of 1e-4, and every |d|-proportional term scales with it.
+// The tame guard keeps the scene's E (a stronger condition than the scaled one).  With cert = 1 the arithmetic is the uncertified one, bit for bit.
+__device__ __forceinline__ float wide_ray_margin(V3 o, V3 d, float mu_e, float mu_l, float mu_v, float cert = 1.0f) {
   if (!(mu_e > 0.0f)) return 0.0f;
   const float on = __builtin_sqrtf(dot(o, o)) * 1.0001f, dn = __builtin_sqrtf(dot(d, d)) * 1.0001f, s = on + mu_v;
   const float abs_term = (s + 4.0f * mu_l + 1.0f) * 0x1p-21f;
   const float cap = 0.01f * (1.0f + 0x1p-16f) + abs_term;
-  const float m = dn * mu_e * 1.0001f * (0.021f * s + 0.015f * mu_l + 1.2e-4f) * 1.0001f + abs_term;
+  const float m = dn * mu_e * cert * 1.0001f * (0.021f * s + 0.015f * mu_l + 1.2e-4f) * 1.0001f + abs_term;
   const bool tame = dn <= 0x1p30f && s <= 0x1p30f && dn * mu_e <= 2.0f;      // (false for NaNs)
   return (tame && m < cap) ? m : cap;
 }
-__device__ __forceinline__ WideRay wide_ray(V3 o, V3 d, V3 inv, float pmax, float mu_e, float mu_l, float mu_v) {      // (mu_*: the scene's WideMu)
+__device__ __forceinline__ WideRay wide_ray(V3 o, V3 d, V3 inv, float pmax, float mu_e, float mu_l, float mu_v, float cert = 1.0f) {      // (mu_*: the scene's WideMu)
   WideRay w;
-  const float extra = wide_ray_margin(o, d, mu_e, mu_l, mu_v);
+  const float extra = wide_ray_margin(o, d, mu_e, mu_l, mu_v, cert);
   auto one = [pmax, extra](float oa, float ia, float& ic, float& on, float& of) {
     ic = __builtin_fminf(__builtin_fmaxf(ia, -0x1p60f), 0x1p60f);                    // NaN -> -2^60, and the margin below is NaN
     const float k = __builtin_fmaf(pmax + __builtin_fabsf(oa), 0x1p-21f, 0x1p-40f) + extra;
@@ -632,6 +635,79 @@ __device__ __forceinline__ WideRay wide_ray(V3 o, V3 d, V3 inv, float pmax, floa
   };
   one(o.x, inv.x, w.inv.x, w.on.x, w.of.x); one(o.y, inv.y, w.inv.y, w.on.y, w.of.y); one(o.z, inv.z, w.inv.z, w.on.z, w.of.z);
   return w;
+}
+
+// The per-view grazing certificate of one triangle (CertView).  In double, for the triangle (v0, e1, e2) of a leaf:
+//  * its padded box is taken as a superset of the reference's (own bounds + 0.01 (1 + 1e-4) + a rounding term per axis: K:353-354 pads v1, v2, v3 in double and
+//    narrows, v0 + e1 is v1 up to one rounding of the edge), widened by what lets a float ray pass it while the real one misses (slab rounding; the float origin
+//    and direction against the real ones of the same camera sample);
+//  * every point X of that box and every origin O within r_o of `from`: |(X - O) . n| >= |(C - from) . n| - sum h_i |n_i| - r_o |n| and |X - O| <= |C - from| + |h| + r_o
+//    (n = e1 x e2, C / h: the box's centre and half extents).  A float camera ray through X has d_f parallel to X - o_f, so
+//    |a^| = |d_f . n| >= dmin (that numerator) / (that denominator): A_T, with a relative 1e-6 off for the double arithmetic;
+//  * A_T >= a_star: 0 (certified).  Otherwise the tiles whose camera rays can pass the box: the box must lie in front of every lens point (else 2: every tile);
+//    the pinhole images of its corners on the focus plane bound it from `from`, a lens offset moves an image by at most
+//    r_o (1 + (D + r_o) / (zmin - r_o) + Rmax (D + zmax) / (zmin (zmin - r_o))); in pixels a sample's jitter adds one, the float nu another: 1 (rect = tile columns
+//    [rect[0], rect[1]] of the LAUNCH and rows [rect[2], rect[3]]; an empty column range: none of the launch's tiles).
+// Any NaN gives 1 with every tile, or 2.  A triangle that did not enter with its own bounds (|e1| |e2| > e_own) needs nothing: 0.
+__device__ __forceinline__ int cert_leaf(const CertView& cv, const float* v0f, const float* e1f, const float* e2f, int* rect) {
+  double v0[3], e1[3], e2[3];
+  for (int a = 0; a < 3; a++) { v0[a] = v0f[a]; e1[a] = e1f[a]; e2[a] = e2f[a]; }
+  const double n1 = __builtin_sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), n2 = __builtin_sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+  if (!(n1 * n2 <= cv.e_own)) return 0;
+  double c[3], h[3], rc[3], n[3];
+  double cn = 0, hn = 0;
+  for (int a = 0; a < 3; a++) {
+    const double p = v0[a] + e1[a], q = v0[a] + e2[a];
+    const double lo = __builtin_fmin(v0[a], __builtin_fmin(p, q)), hi = __builtin_fmax(v0[a], __builtin_fmax(p, q));
+    const double pad = 0.01 * 1.0001 + 0x1p-22 * (__builtin_fabs(v0[a]) + __builtin_fabs(e1[a]) + __builtin_fabs(e2[a]) + 1.0);
+    c[a] = 0.5 * (lo + hi); h[a] = 0.5 * (hi - lo) + pad;
+    cn += c[a] * c[a]; hn += h[a] * h[a];
+  }
+  cn = __builtin_sqrt(cn); hn = __builtin_sqrt(hn);
+  const double fn = __builtin_sqrt(cv.from[0] * cv.from[0] + cv.from[1] * cv.from[1] + cv.from[2] * cv.from[2]);
+  double rcn = 0;
+  for (int a = 0; a < 3; a++) { rc[a] = c[a] - cv.from[a]; rcn += rc[a] * rc[a]; }
+  rcn = __builtin_sqrt(rcn);
+  const double slop = 0x1p-19 * (cn + hn + fn + 1.0) + cv.eps_d * (rcn + hn + cv.r_o) / cv.dmin;
+  hn = 0;
+  for (int a = 0; a < 3; a++) { h[a] += slop; hn += h[a] * h[a]; }
+  hn = __builtin_sqrt(hn);
+  n[0] = e1[1] * e2[2] - e1[2] * e2[1]; n[1] = e1[2] * e2[0] - e1[0] * e2[2]; n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  const double nn = __builtin_sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  const double num = __builtin_fabs(rc[0] * n[0] + rc[1] * n[1] + rc[2] * n[2]) - (h[0] * __builtin_fabs(n[0]) + h[1] * __builtin_fabs(n[1]) + h[2] * __builtin_fabs(n[2])) - cv.r_o * nn;
+  const double den = rcn + hn + cv.r_o;
+  const double a_t = num > 0.0 ? cv.dmin * (num / den) * (1.0 - 1e-6) : 0.0;
+  if (a_t >= cv.a_star) return 0;
+  // ---- flagged: the tiles its box can be seen from
+  const double zc = rc[0] * cv.w[0] + rc[1] * cv.w[1] + rc[2] * cv.w[2];
+  const double zh = h[0] * __builtin_fabs(cv.w[0]) + h[1] * __builtin_fabs(cv.w[1]) + h[2] * __builtin_fabs(cv.w[2]);
+  const double zmin = zc - zh, zmax = zc + zh;
+  if (!(zmin > 2.0 * cv.r_o + 1e-9 * (fn + cn + hn) && zmin == zmin && zmax < 1e300)) return 2;
+  double ulo = 1e300, uhi = -1e300, vlo = 1e300, vhi = -1e300;
+  for (int k = 0; k < 8; k++) {
+    double x[3];
+    for (int a = 0; a < 3; a++) x[a] = rc[a] + (((k >> a) & 1) ? h[a] : -h[a]);
+    const double z = x[0] * cv.w[0] + x[1] * cv.w[1] + x[2] * cv.w[2], s = cv.D / z;
+    double pl[3];
+    for (int a = 0; a < 3; a++) pl[a] = cv.from[a] + x[a] * s - cv.llc[a];
+    const double nu = cv.du[0] * pl[0] + cv.du[1] * pl[1] + cv.du[2] * pl[2], nv = cv.dv[0] * pl[0] + cv.dv[1] * pl[1] + cv.dv[2] * pl[2];
+    ulo = __builtin_fmin(ulo, nu); uhi = __builtin_fmax(uhi, nu); vlo = __builtin_fmin(vlo, nv); vhi = __builtin_fmax(vhi, nv);
+  }
+  const double rmax = rcn + hn;
+  const double lens = cv.r_o * (1.0 + (cv.D + cv.r_o) / (zmin - cv.r_o) + rmax * (cv.D + zmax) / (zmin * (zmin - cv.r_o)));
+  const double xlo = (ulo - cv.du_n * lens) * cv.den_w, xhi = (uhi + cv.du_n * lens) * cv.den_w;
+  const double ylo = (vlo - cv.dv_n * lens) * cv.den_h, yhi = (vhi + cv.dv_n * lens) * cv.den_h;
+  if (!(xlo == xlo && xhi == xhi && ylo == ylo && yhi == yhi)) return 2;
+  auto pix = [](double f, int hi) { return f < -8.0 ? -8 : (f > (double)hi + 8.0 ? hi + 8 : (int)__builtin_floor(f)); };
+  const int px0 = pix(xlo, cv.nx) - 2, px1 = pix(xhi, cv.nx) + 1, py0 = pix(ylo, cv.ny) - 2, py1 = pix(yhi, cv.ny) + 1;
+  const int gc0 = (px0 < 0 ? 0 : px0) >> 3, gc1 = (px1 >= cv.nx ? cv.nx - 1 : px1) >> 3;
+  rect[2] = (py0 < 0 ? 0 : py0) >> 3; rect[3] = (py1 >= cv.ny ? cv.ny - 1 : py1) >> 3;
+  // global block columns [gc0, gc1] -> the launch's local columns (global = stripe_rem + local * stripe_mod)
+  const int l0 = gc0 <= cv.stripe_rem ? 0 : (gc0 - cv.stripe_rem + cv.stripe_mod - 1) / cv.stripe_mod;
+  const int l1 = gc1 < cv.stripe_rem ? -1 : (gc1 - cv.stripe_rem) / cv.stripe_mod;
+  rect[0] = l0; rect[1] = l1 < cv.ncols - 1 ? l1 : cv.ncols - 1;
+  if (px1 < 0 || py1 < 0 || px0 >= cv.nx || py0 >= cv.ny) rect[1] = rect[0] - 1;       // off the grid: no tile
+  return 1;
 }
 
 // The four plane bytes of a word as f16 denormals: (byte0, byte2) and (byte1, byte3), each pair in one register

@@ -57,6 +57,29 @@ struct WideMu {
   float l;      // largest |e1| + |e2| of them
   float v;      // largest |v0| of them
 };
+// Per-view grazing certificate of the camera rays (option camera_cert; device_core.hpp cert_leaf).  Every camera ray starts within r_o of
+// `from`; a small triangle that such a ray can be ACCEPTED on has its padded box on the ray, and the view gives a lower bound A_T of |d . (e1 x e2)| over
+// every such ray.  Triangles with A_T >= a_star certify nothing more is needed; the others set the bits of the tiles whose rays can reach their box.  A ray
+// of an unflagged tile therefore has |a^| >= a_star for every triangle it can be accepted on and carries the margin scaled by 1e-4 / a_star.
+// All of it is double, filled on the host from the launch's float camera block (params_host.hpp fill_cert_view).
+struct CertView {
+  double from[3];      // the camera centre (float P.from)
+  double w[3];         // unit normal of hor x ver, oriented towards the focus plane
+  double llc[3];       // lower-left corner of the focus plane (float P.llc)
+  double du[3], dv[3]; // dual vectors: nu = du . (P - llc), nv = dv . (P - llc) for a point P of the focus plane
+  double du_n, dv_n;   // their norms
+  double D;            // (llc - from) . w: depth of the focus plane
+  double r_o;          // every camera ray's float origin is within r_o of `from` (lens disk + rounding)
+  double eps_d;        // |d_f - d| for the float direction of a camera ray against the real one of the same (nu, nv, offset)
+  double dmin;         // lower bound of |d_f| over all camera rays
+  double den_w, den_h; // pixels per unit of nu / nv (P.den_w, P.den_h)
+  double a_star;       // the certified lower bound of |a^|
+  double e_own;        // triangles with |e1| |e2| above this did not enter the tree with their own bounds (WideMu e, widened)
+  int32_t nx, ny;      // pixels of the rendered grid: 8 gx, 8 gy
+  int32_t gy;          // tile rows (a tile's bit: local column * gy + row)
+  int32_t stripe_mod, stripe_rem, ncols;      // the launch's block columns: global column = stripe_rem + local column * stripe_mod
+};
+
 constexpr int WIDE_UNITS = 4;
 constexpr int WIDE_INDEX_BITS = 24;                   // records < 2^24 (1 GiB of them)
 constexpr int WIDE_STACK = 16;                        // stack words per lane kept in LDS (one more lives in a register)
@@ -153,6 +176,8 @@ struct RenderParams {
   uint32_t out_frame_stride;      // int32 words between the output buffers of two frames of a batch (0: one buffer for all: accumulation)
   int32_t region_start[9];        // identity order: region r owns tiles [region_start[r], region_start[r+1])
   WideMu wide_mu;                 // wide walk: the margin's scene constants (e = 0: none)
+  float wide_cert_k;              // ... the factor on it for camera rays of tiles the grazing certificate clears (>= 1e-4 / a_star; 1 without one)
+  const uint32_t* cert_mask;      // null, or one bit per tile of this launch (local column * gy + row): set = a camera ray of the tile may graze (carries wide_mu.e)
 };
 
 // The denoiser's parameters (dr_denoise_params, validated by dr_accum_denoise / hk_denoise) and its material markers (device_denoise.hpp)

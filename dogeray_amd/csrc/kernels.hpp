@@ -41,6 +41,9 @@ bool persistent_kernel_can_store_per_frame(const PersistentCfg& cfg);
 // kernels_aux.hip
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,
                           int heavy_factor, int split_steps, int split_limit);
+// the camera rays' grazing certificate of a view: mask = (ntiles + 31) / 32 words of tile bits (set: the tile's camera rays keep the scene's margin),
+// then the "every tile" word and the number of flagged tiles (device_core.hpp cert_leaf)
+void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, int ntiles);
 void launch_present(hipStream_t stream, const int32_t* acc, uint8_t* rgb, int W, int H, int div);
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n);      // acc += frame (pipelined single frames)
 void launch_stripe_copy(hipStream_t stream, int32_t* dst, const int32_t* src, int ncols, int run4, long long dst_first4, long long dst_stride4,

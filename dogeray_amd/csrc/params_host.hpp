@@ -65,4 +65,52 @@ inline const char* fill_view_params(const float* st, int W, int H, float backgro
   return nullptr;
 }
 
+// The camera rays' grazing certificate of a view (CertView, device_layout.h; device_core.hpp cert_leaf): from the launch's float camera block, in double.
+// a_star: the certified |a^| (>= 1e-4); e_own: the scene's WideMu e.  Returns false when the view gives nothing to certify with (no own-bounds tree,
+// degenerate camera, non-finite values): its camera rays then keep the scene's margin.
+inline bool fill_cert_view(const RenderParams& P, double a_star, float e_own, CertView& cv) {
+  memset(&cv, 0, sizeof(cv));
+  if (!(e_own > 0.0f) || !(a_star >= 1e-4)) return false;
+  double hor[3], ver[3], uu[3], vu[3];
+  for (int a = 0; a < 3; a++) { cv.from[a] = P.from[a]; cv.llc[a] = P.llc[a]; hor[a] = P.hor[a]; ver[a] = P.ver[a]; uu[a] = P.uu[a]; vu[a] = P.vu[a]; }
+  auto dot = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+  auto norm = [&](const double* a) { return std::sqrt(dot(a, a)); };
+  double w[3] = {hor[1] * ver[2] - hor[2] * ver[1], hor[2] * ver[0] - hor[0] * ver[2], hor[0] * ver[1] - hor[1] * ver[0]};
+  const double wn = norm(w);
+  if (!(wn > 0) || !std::isfinite(wn)) return false;
+  double lf[3] = {cv.llc[0] - cv.from[0], cv.llc[1] - cv.from[1], cv.llc[2] - cv.from[2]};
+  for (int a = 0; a < 3; a++) w[a] /= wn;
+  if (dot(lf, w) < 0) for (int a = 0; a < 3; a++) w[a] = -w[a];
+  memcpy(cv.w, w, sizeof(w));
+  cv.D = dot(lf, w);
+  const double hh = dot(hor, hor), hv = dot(hor, ver), vv = dot(ver, ver), det = hh * vv - hv * hv;
+  if (!(det > 0)) return false;
+  for (int a = 0; a < 3; a++) { cv.du[a] = (vv * hor[a] - hv * ver[a]) / det; cv.dv[a] = (hh * ver[a] - hv * hor[a]) / det; }
+  cv.du_n = norm(cv.du); cv.dv_n = norm(cv.dv);
+  const double r = std::fabs((double)P.lens_radius), fn = norm(cv.from);
+  // lens offset uu rd.x + vu rd.y with |rd.x|, |rd.y| <= r (a point of the unit disk, times r, rounded), and the float sum from + offset
+  cv.r_o = 1.001 * r * (norm(uu) + norm(vu)) + 0x1p-22 * (fn + 2.0 * r) + 1e-30;
+  // d_f = llc + nu hor + nv ver - from - offset (0 <= nu, nv <= 1): two products and four sums, each rounded once per component
+  cv.eps_d = 0x1p-20 * (norm(cv.llc) + norm(hor) + norm(ver) + fn + cv.r_o);
+  // |d| >= d . w = D + nu hor . w + nv ver . w - offset . w (hor, ver are orthogonal to w up to the double rounding)
+  cv.dmin = cv.D - cv.r_o - 1e-9 * (norm(hor) + norm(ver)) - cv.eps_d;
+  cv.den_w = P.den_w; cv.den_h = P.den_h;
+  cv.a_star = a_star;
+  cv.e_own = (double)e_own * (1.0 + 1e-6);
+  cv.nx = 8 * P.gx; cv.ny = 8 * P.gy; cv.gy = P.gy;
+  cv.stripe_mod = P.stripe_mod; cv.stripe_rem = P.stripe_rem; cv.ncols = P.ncols;
+  const double all[] = {cv.D, cv.r_o, cv.eps_d, cv.dmin, cv.du_n, cv.dv_n, fn};
+  for (double v : all) if (!std::isfinite(v)) return false;
+  // (a view whose focus plane is not clearly in front of the lens certifies nothing)
+  return cv.dmin > 8.0 * cv.r_o && cv.dmin > 0;
+}
+
+// The factor a certified camera ray's |d|-proportional margin carries: 1e-4 / a_star, rounded up (step 2 divides by a_star instead of 1e-4)
+inline float cert_factor_k(double a_star) {
+  const double x = 1e-4 / a_star;
+  float f = (float)x;
+  if ((double)f < x) f = std::nextafter(f, INFINITY);
+  return f;
+}
+
 }  // namespace dr

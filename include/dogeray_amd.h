@@ -190,6 +190,12 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   over the reference's leaf boxes; 0 the reference's own topology (K:1745-1861) collapsed 4-way
  *   "denoise_tiles" dr_accum_denoise's a-trous passes: 1 (default) one workgroup per 16x16 lattice tile staged in LDS, 0 every tap loaded from
  *                   the planes; the same bits either way
+ *   "camera_cert"   1 (default): per view, the camera rays of tiles where no small triangle can be hit near-grazing carry a smaller margin
+ *                   (the grazing certificate); 0 every ray carries the scene's margin.  The same bits either way.  Used by the
+ *                   lean and counting builds of the persistent kernel, for the first sample of each pixel (spp > 1: later samples keep the scene's
+ *                   margin); a single-frame launch of a view not seen before computes no mask
+ *   "cert_factor"   the certified |d . (e1 x e2)| in units of the 1e-4 cut-off (default 40)
+ *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -406,6 +412,11 @@ int dr_stats_get(dr_context* c, dr_stats* out);
  * [17] turns summed over phases, [18] lanes that drew a point in the unit sphere (scatter, K:640-648), [19] lanes that drew a point in the unit disk
  * (new path, K:988-994), [20] retired lanes summed over phases.  With dr_stats.diag (phases, lanes shaded, cycles in phases) this prices the phase. */
 int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n);
+
+/* The tile mask of the camera rays' grazing certificate of the last certified view (option camera_cert): one bit per tile of
+ * that launch (bit t of word t / 32; tile = local block column * tile rows + row), set = the tile's camera rays keep the scene's margin.
+ * *n_tiles = 0 when no certificate is in use; otherwise the tiles, and the first min(max_words, (n_tiles + 31) / 32) words are copied to out. */
+int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles);
 
 /* Timeline of the last SHORT persistent-kernel launch (fewer than coop_tiles_per_wave tiles per wave: one frame, a thin stripe;
  * option "wave_log" = 1 before the launch): sixteen words per wave --

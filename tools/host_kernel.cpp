@@ -128,6 +128,113 @@ long long hk_check_reject(long long n, unsigned long long seed, double* max_d2_g
 void hk_ray_margin(long long n, const float* o, const float* d, float e, float l, float v, float* out) {
   for (long long i = 0; i < n; i++) out[i] = wide_ray_margin(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), e, l, v);
 }
+// The camera rays' grazing certificate (device_core.hpp cert_leaf) of the scene's triangles for one view, as kernels_aux.hip
+// cert_mask_kernel builds it, and a check of what it promises against the kernel's own camera rays (camera_ray: camera_prepare, the lens disk,
+// camera_finish).  n_samples times: a triangle, a random point X of its padded box (own bounds + 0.01), the pixel X projects to (+-1), a random
+// sample seed; a ray that enters that box (slab(), entry > -0.01, as K:484-488) must have |d . (e1 x e2)| >= a_star if the triangle is certified,
+// and lie in a flagged tile if it is not.  e_own: triangles with |e1| |e2| above it are skipped (as never entered with their own bounds).
+// out[0..7]: rays through certified boxes, of them below a_star (must be 0), rays through flagged boxes, of them in unflagged tiles (must be 0),
+// flagged tiles, tiles, triangles flagged, "every tile" set.  Returns 0, or -1 with hk_last_error.
+int hk_cert_check(void* hv, const float* settings13, int W, int H, double a_star, float e_own, long long n_samples, uint64_t seed, long long* out, uint32_t* mask_out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || !out) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 1, 1, 0, P)) { hk_err = why; return -1; }
+  CertView cv;
+  if (!fill_cert_view(P, a_star, e_own, cv)) { hk_err = "the view gives no certificate"; return -1; }
+  const std::vector<DevPrim>& prims = h->img.prims;
+  const int tiles = P.ncols * P.gy, nwords = (tiles + 31) / 32;
+  std::vector<uint32_t> mask((size_t)nwords + 2, 0u);
+  std::vector<int> kind(prims.size(), 0);
+  for (size_t i = 0; i < prims.size(); i++) {
+    const DevPrim& p = prims[i];
+    if (p.type != 2) continue;
+    const float e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
+    int rect[4] = {0, -1, 0, -1};
+    const int k = cert_leaf(cv, p.v0, e1, e2, rect);
+    kind[i] = k;
+    if (k == 2) mask[(size_t)nwords] = 1u;
+    if (k == 1)
+      for (int col = rect[0]; col <= rect[1]; col++)
+        for (int r = rect[2]; r <= rect[3]; r++) { const int b = col * cv.gy + r; mask[(size_t)(b >> 5)] |= 1u << (b & 31); }
+  }
+  long long flagged = 0, flagged_prims = 0;
+  for (int b = 0; b < tiles; b++) flagged += (mask[(size_t)nwords] || ((mask[(size_t)(b >> 5)] >> (b & 31)) & 1u)) ? 1 : 0;
+  for (int k : kind) flagged_prims += k != 0;
+  if (mask_out) memcpy(mask_out, mask.data(), (size_t)(nwords + 2) * sizeof(uint32_t));
+  for (int k = 0; k < 8; k++) out[k] = 0;
+  out[4] = flagged; out[5] = tiles; out[6] = flagged_prims; out[7] = mask[(size_t)nwords];
+  uint64_t st = seed * 0x9E3779B97F4A7C15ull + 1;
+  auto rnd = [&st]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (double)(st >> 11) * 0x1p-53; };
+  std::vector<size_t> tri;
+  for (size_t i = 0; i < prims.size(); i++) {
+    const DevPrim& p = prims[i];
+    const double n1 = std::sqrt((double)p.e1x * p.e1x + (double)p.e1y * p.e1y + (double)p.e1z * p.e1z), n2 = std::sqrt((double)p.e2x * p.e2x + (double)p.e2y * p.e2y + (double)p.e2z * p.e2z);
+    if (p.type == 2 && n1 * n2 <= cv.e_own) tri.push_back(i);
+  }
+  if (tri.empty()) return 0;
+  // half the samples from flagged triangles (when there are any), half from all
+  std::vector<size_t> flagged_tri;
+  for (size_t i : tri) if (kind[i] != 0) flagged_tri.push_back(i);
+  for (long long s = 0; s < n_samples; s++) {
+    const bool pick_flagged = !flagged_tri.empty() && (s & 1);
+    const size_t i = pick_flagged ? flagged_tri[(size_t)(rnd() * (double)flagged_tri.size()) % flagged_tri.size()] : tri[(size_t)(rnd() * (double)tri.size()) % tri.size()];
+    const DevPrim& p = prims[i];
+    const double v0[3] = {p.v0[0], p.v0[1], p.v0[2]}, e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
+    float mn[3], mx[3];
+    double X[3];
+    for (int a = 0; a < 3; a++) {
+      const double lo = std::min(v0[a], std::min(v0[a] + e1[a], v0[a] + e2[a])) - 0.01, hi = std::max(v0[a], std::max(v0[a] + e1[a], v0[a] + e2[a])) + 0.01;
+      mn[a] = (float)lo; mx[a] = (float)hi;
+      X[a] = lo + (hi - lo) * rnd();
+    }
+    // the pixel X projects to through the pinhole
+    double rel[3], z = 0;
+    for (int a = 0; a < 3; a++) { rel[a] = X[a] - cv.from[a]; z += rel[a] * cv.w[a]; }
+    if (!(z > 0)) continue;
+    double pl[3];
+    for (int a = 0; a < 3; a++) pl[a] = cv.from[a] + rel[a] * (cv.D / z) - cv.llc[a];
+    const double nu = cv.du[0] * pl[0] + cv.du[1] * pl[1] + cv.du[2] * pl[2], nv = cv.dv[0] * pl[0] + cv.dv[1] * pl[1] + cv.dv[2] * pl[2];
+    const double fx = std::floor(nu * cv.den_w) + (double)((int)(rnd() * 3.0) - 1), fy = std::floor(nv * cv.den_h) + (double)((int)(rnd() * 3.0) - 1);
+    if (!(fx >= 0 && fy >= 0 && fx < cv.nx && fy < cv.ny)) continue;
+    const int x = (int)fx, y = (int)fy;
+    Xorwow rng;
+    rng.init(sample_seed(P, x, y, 0, (int)(rnd() * 1000.0)));
+    V3 o, d;
+    camera_ray(P, x, y, rng, o, d);
+    const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    float dist = 0;
+    if (!slab(o, inv, mn, mx, dist) || !(dist > -0.01f)) continue;
+    if (kind[i] == 0) {
+      const double dd[3] = {d.x, d.y, d.z};
+      const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+      const double a = std::fabs(dd[0] * nx + dd[1] * ny + dd[2] * nz);
+      out[0]++;
+      if (!(a >= a_star)) out[1]++;
+    } else {
+      const int b = (x >> 3) * cv.gy + (y >> 3);
+      out[2]++;
+      if (!(mask[(size_t)nwords] || ((mask[(size_t)(b >> 5)] >> (b & 31)) & 1u))) out[3]++;
+    }
+  }
+  return 0;
+}
+// the same with the certificate's factor (wide_ray_margin's last argument: 1e-4 / a_star for a certified camera ray, 1 otherwise)
+void hk_ray_margin_k(long long n, const float* o, const float* d, float e, float l, float v, float k, float* out) {
+  for (long long i = 0; i < n; i++) out[i] = wide_ray_margin(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), e, l, v, k);
+}
+// params_host.hpp cert_factor_k: the factor a certified camera ray carries for a_star
+float hk_cert_factor_k(double a_star) { return cert_factor_k(a_star); }
+// the scene's WideMu (e, l, v) as the product computes it (wide_tree = 2), for the certificate's own-bounds test (CertView e_own)
+int hk_wide_mu(void* hv, float* out3) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !out3) { hk_err = "bad argument"; return -1; }
+  DeviceImage img;
+  if (linearise(h->scene->host, img, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+  out3[0] = img.wide_mu.e; out3[1] = img.wide_mu.l; out3[2] = img.wide_mu.v;
+  return img.wide_own_bounds;
+}
 // hit_tri (device_core.hpp tri_hit) on n ray / triangle pairs: t or -1
 void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* t) {
   for (long long i = 0; i < n; i++)

@@ -42,6 +42,14 @@ def lib():
         L.hk_check_uniform.argtypes = [C.c_longlong, C.c_ulonglong]
         L.hk_ray_margin.restype = None
         L.hk_ray_margin.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.hk_ray_margin_k.restype = None
+        L.hk_ray_margin_k.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.hk_cert_factor_k.restype = C.c_float
+        L.hk_cert_factor_k.argtypes = [C.c_double]
+        L.hk_wide_mu.restype = C.c_int
+        L.hk_wide_mu.argtypes = [C.c_void_p, C.c_void_p]
+        L.hk_cert_check.restype = C.c_int
+        L.hk_cert_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_longlong, C.c_uint64, C.c_void_p, C.c_void_p]
         L.hk_tri_hit.restype = None
         L.hk_tri_hit.argtypes = [C.c_longlong] + [C.c_void_p] * 6
         L.hk_check_reject.restype = C.c_longlong

@@ -4,7 +4,9 @@
 // tools/host_kernel.cpp), checked at every node against the plain decode-and-slab test it must cover.  Build from the repo root:
 //   /opt/rocm/lib/llvm/bin/clang++ -std=c++17 -O2 -ffp-contract=off -mfma -DDR_HOST_BUILD=1 -I tools/host_kernel -I dogeray_amd/csrc -I include -o /tmp/widewalk tools/study_wide_walk.cpp \
 //       dogeray_amd/csrc/linearise.cpp dogeray_amd/csrc/wide_builder.cpp dogeray_amd/csrc/rts_reader.cpp \
-//       dogeray_amd/csrc/bvh_builder.cpp dogeray_amd/csrc/capi_host.cpp -pthread && /tmp/widewalk scene.rts 20000 [tree_mode]
+//       dogeray_amd/csrc/bvh_builder.cpp dogeray_amd/csrc/capi_host.cpp -pthread && /tmp/widewalk scene.rts 20000 [tree_mode] [cert_factor]
+// cert_factor > 0 (with tree_mode 2): the camera rays are the kernel's own (camera_ray through a random pixel, lens and jitter included) and, in tiles the
+// view's grazing certificate clears (device_core.hpp cert_leaf with a_star = cert_factor * 1e-4), carry the certified margin.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -15,6 +17,7 @@
 
 #include "linearise.hpp"
 #include "device_core.hpp"
+#include "params_host.hpp"
 using namespace dr;
 
 static bool slab(const float o[3], const float inv[3], const float mn[3], const float mx[3], float& dist) {
@@ -35,9 +38,10 @@ static float tri(const float o[3], const float d[3], const float* v0, const floa
 
 struct WideStats { long nodes = 0, leaves = 0, tests = 0, maxsp = 0, cull_nodes = 0, cull_leaves = 0, cull_entry = 0, extra_children = 0, leafkids[5] = {0, 0, 0, 0, 0}; };
 
-static void wide_hit(const std::vector<DevUnit>& rec, float pmax, WideMu mu, const float o[3], const float d[3], const float inv[3], float& best_t, int& best_slot, WideStats& ws) {
+static void wide_hit(const std::vector<DevUnit>& rec, float pmax, WideMu mu, const float o[3], const float d[3], const float inv[3], float& best_t, int& best_slot, WideStats& ws,
+                     float cert = 1.0f) {
   best_t = 10000.0f; best_slot = -1;      // trav_begin
-  const WideRay wr = wide_ray(mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]), mk(inv[0], inv[1], inv[2]), pmax, mu.e, mu.l, mu.v);
+  const WideRay wr = wide_ray(mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]), mk(inv[0], inv[1], inv[2]), pmax, mu.e, mu.l, mu.v, cert);
   unsigned stack[WIDE_STACK]; int sp = 0; unsigned top = 0;
   float sd[WIDE_STACK + 1][4]; float topd[4] = {0, 0, 0, 0};   // study only: entry distance of every pending child
   unsigned cur = 0;   // index << 1 | leaf
@@ -174,11 +178,41 @@ int main(int argc, char** argv) {
   long bin_int = 0, bin_leaf = 0, bin_tests = 0, rays = 0; WideStats ws;
   std::vector<float> bx(img.wide.size() / WIDE_UNITS * 6); exact_boxes(img.wide, 0, false, bx);
   long ex_nodes = 0, ex_leaves = 0;
+  // the view's grazing certificate (cert_factor > 0): the kernel's camera block, the mask as cert_mask_kernel builds it
+  const int cert_factor = argc > 4 ? atoi(argv[4]) : 0;
+  RenderParams P; memset(&P, 0, sizeof(P));
+  const float st13[13] = {st.campos[0], st.campos[1], st.campos[2], st.look[0], st.look[1], st.look[2], st.aperture, st.focus_dist, (float)st.fov, (float)st.max_depth, 1.0f, 1.0f, (float)st.backtex};
+  CertView cv; std::vector<uint8_t> flagged; bool cert_on = false; float cert_k = 1.0f; long cert_rays = 0;
+  if (cert_factor > 0 && !fill_view_params(st13, W, H, 0.0f, 1, 1, 0, P) && fill_cert_view(P, 1e-4 * cert_factor, img.wide_mu.e, cv)) {
+    cert_on = true; cert_k = cert_factor_k(1e-4 * cert_factor);
+    flagged.assign((size_t)P.ncols * P.gy, 0);
+    bool all = false;
+    for (const DevPrim& p : img.prims) {
+      if (p.type != 2) continue;
+      const float e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
+      int rect[4] = {0, -1, 0, -1};
+      const int k = cert_leaf(cv, p.v0, e1, e2, rect);
+      if (k == 2) all = true;
+      if (k == 1) for (int c = rect[0]; c <= rect[1]; c++) for (int rr = rect[2]; rr <= rect[3]; rr++) flagged[(size_t)c * P.gy + rr] = 1;
+    }
+    if (all) std::fill(flagged.begin(), flagged.end(), 1);
+    long nf = 0; for (uint8_t f : flagged) nf += f;
+    printf("grazing certificate a_star = %g: %ld of %zu tiles flagged, factor %g\n", 1e-4 * cert_factor, nf, flagged.size(), cert_k);
+  }
   for (int r = 0; r < nr; r++) {
     float o[3], d[3], inv[3];
     float s = U(rng2), t = U(rng2);
-    for (int a = 0; a < 3; a++) { o[a] = from[a]; d[a] = (s - 0.5f) * vw * u[a] + (t - 0.5f) * vh * v[a] - w[a]; }
-    norm(d);
+    float cert = 1.0f;
+    if (cert_on) {      // the kernel's camera ray through a random pixel of the grid
+      const int x = std::min((int)(s * 8 * P.gx), 8 * P.gx - 1), y = std::min((int)(t * 8 * P.gy), 8 * P.gy - 1);
+      Xorwow xr; xr.init(sample_seed(P, x, y, 0, r));
+      V3 vo, vd; camera_ray(P, x, y, xr, vo, vd);
+      o[0] = vo.x; o[1] = vo.y; o[2] = vo.z; d[0] = vd.x; d[1] = vd.y; d[2] = vd.z;
+      if (!flagged[(size_t)(x >> 3) * P.gy + (y >> 3)]) { cert = cert_k; cert_rays++; }
+    } else {
+      for (int a = 0; a < 3; a++) { o[a] = from[a]; d[a] = (s - 0.5f) * vw * u[a] + (t - 0.5f) * vh * v[a] - w[a]; }
+      norm(d);
+    }
     for (int bounce = 0; bounce < 3; bounce++) {
       for (int a = 0; a < 3; a++) inv[a] = 1.0f / d[a];
       float best = 1e7f; int bs = -1;
@@ -187,7 +221,7 @@ int main(int argc, char** argv) {
               float tt = p.type == 2 ? tri(o, d, p.v0, e1, e2) : -1; if (tt > 0 && tt < 10000.0f && tt < best) { best = tt; bs = slot[node]; } } node = b.miss_node; }
           else { bin_int++; node = h ? b.hit_node : b.miss_node; } } }
       float wb; int wsl;
-      wide_hit(img.wide, img.wide_pmax, img.wide_mu, o, d, inv, wb, wsl, ws);
+      wide_hit(img.wide, img.wide_pmax, img.wide_mu, o, d, inv, wb, wsl, ws, bounce == 0 ? cert : 1.0f);
       exact_hit(img.wide, bx, o, d, inv, ex_nodes, ex_leaves);
       if (wsl != bs || (bs >= 0 && wb != best)) { printf("MISMATCH ray %d bounce %d: wide %d %g vs reference %d %g\n", r, bounce, wsl, wb, bs, best); return 1; }
       rays++;
@@ -201,6 +235,7 @@ int main(int argc, char** argv) {
   }
   printf("%ld rays, hits identical.  reference walk: %.1f internal + %.1f leaf visits, %.2f primitive tests per ray;  wide walk (tree mode %d): %.1f node + %.1f leaf records, %.2f primitive tests per ray, deepest stack %ld; fetched although already farther than the best t when popped: %.2f nodes + %.2f leaves per ray; children entered by the folded test only: %.3f per ray\n",
          rays, (double)bin_int / rays, (double)bin_leaf / rays, (double)bin_tests / rays, mode, (double)ws.nodes / rays, (double)ws.leaves / rays, (double)ws.tests / rays, ws.maxsp, (double)ws.cull_nodes / rays, (double)ws.cull_leaves / rays, (double)ws.extra_children / rays);
+  if (cert_on) printf("camera rays with the certified margin: %ld of %d\n", cert_rays, nr);
   printf("nodes with leaf children, by how many of them the ray enters: 0: %ld  1: %ld  2: %ld  3: %ld  4: %ld\n", ws.leafkids[0], ws.leafkids[1], ws.leafkids[2], ws.leafkids[3], ws.leafkids[4]);
   printf("the same tree with exact child boxes, fully sorted children and pruning at pop time (the ideal this layout approximates): %.1f node + %.1f leaf records per ray\n", (double)ex_nodes / rays, (double)ex_leaves / rays);
   return 0;
