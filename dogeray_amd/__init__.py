@@ -84,6 +84,16 @@ class DrDenoiseParams(C.Structure):
                 ("demodulate", C.c_int), ("material_stop", C.c_int)]
 
 
+class DrReprojectParams(C.Structure):
+    """struct dr_reproject_params (include/dogeray_amd.h dr_accum_reproject)."""
+    _fields_ = [("max_history", C.c_int), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float), ("material_mask", C.c_uint32), ("sky", C.c_int)]
+
+
+class DrReprojectResult(C.Structure):
+    """struct dr_reproject_result: grid pixels per class; pixels = valid + masked + offscreen + rejected."""
+    _fields_ = [("pixels", C.c_int64), ("valid", C.c_int64), ("masked", C.c_int64), ("offscreen", C.c_int64), ("rejected", C.c_int64)]
+
+
 # every symbol include/dogeray_amd.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _API = [
@@ -120,6 +130,10 @@ _API = [
     ("dr_accum_read", C.c_int, [_VP, _VP]),
     ("dr_accum_present", C.c_int, [_VP, C.c_int, _VP]),
     ("dr_accum_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("dr_accum_history_read", C.c_int, [_VP, _VP]),
+    ("dr_accum_history_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("dr_reproject_defaults", C.c_int, [C.POINTER(DrReprojectParams)]),
+    ("dr_accum_reproject", C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrReprojectParams), C.POINTER(DrReprojectResult)]),
     ("dr_render_accumulate_async", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int]),
     ("dr_context_synchronize", C.c_int, [_VP]),
     ("dr_pipeline_submit", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
@@ -258,6 +272,17 @@ def denoise_params(**params):
     for k, v in params.items():
         if k not in dict(DrDenoiseParams._fields_):
             raise TypeError("unknown denoise parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrDenoiseParams._fields_)))
+        setattr(p, k, v)
+    return p
+
+
+def reproject_params(**params):
+    """A DrReprojectParams: the library's defaults (dr_reproject_defaults) with the given fields replaced."""
+    p = DrReprojectParams()
+    _check(lib().dr_reproject_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in dict(DrReprojectParams._fields_):
+            raise TypeError("unknown reproject parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrReprojectParams._fields_)))
         setattr(p, k, v)
     return p
 
@@ -636,6 +661,28 @@ class Context:
             cur.wait_stream(lib_stream)
         return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
 
+    # ---- temporal reprojection (dr_accum_reproject)
+    def reproject(self, from_settings13, to_settings13, W, H, frames, **params):
+        """Carries the accumulator from the view it was rendered in to another one (include/dogeray_amd.h dr_accum_reproject): frames = the
+        frames added since the last accum_reset / reproject.  Afterwards the accumulator and its history plane (accum_history) belong to the new
+        view and the caller's frame count starts again at 0.  params: the fields of dr_reproject_params (max_history, normal_cos,
+        plane_tolerance, material_mask, sky), the rest at their defaults.  Returns the counts of grid pixels per class:
+        {"pixels", "valid", "masked", "offscreen", "rejected"}."""
+        a, b = _f32(from_settings13), _f32(to_settings13)
+        assert a.shape == (13,) and b.shape == (13,)
+        p = reproject_params(**params)
+        r = DrReprojectResult()
+        _check(lib().dr_accum_reproject(self._h, _p(a), _p(b), W, H, int(frames), C.byref(p), C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in DrReprojectResult._fields_}
+
+    def accum_history(self):
+        """int32[W, H] indexed [x, y]: the samples each pixel of the accumulator carries in addition to the frames added since the last
+        reproject (all zeros when there is no history plane)."""
+        W, H, _ = self._acc_shape
+        out = np.empty((W, H), dtype=np.int32)
+        _check(lib().dr_accum_history_read(self._h, _p(out)))
+        return out
+
     # ---- known-answer hooks (tests)
     def kat_rng(self, seed, n):
         out = np.zeros(n, dtype=np.float64)
@@ -777,6 +824,7 @@ class ProgressiveRenderer:
         self.seed_base, self.seed_stride = seed_base, seed_stride
         self.iter = 0
         self.frames_rendered = 0
+        self._pnum = 3                  # iterations that do not count as samples of the accumulating phase: divide_by = iter - _pnum
         self.ctx.accum_reset(self.W, self.H)
 
     def _seed(self):
@@ -796,11 +844,32 @@ class ProgressiveRenderer:
         else:
             st = pack_settings13(s, 1)
             c.render_accumulate(st, self.W, self.H, s.background, self._seed(), 0, 1)
-            pnum = 3
+            pnum = self._pnum
             td = 1
         self.frames_rendered += 1
         self.iter += 1
         return td, self.iter - pnum
+
+    def move_camera(self, scene_settings, reproject=True, **params):
+        """Switches the renderer to other settings (a DrSettings of the same width and height: a camera or focus move).  reproject=True
+        carries the image into the new view (Context.reproject with the divide_by of the last step(), params = fields of
+        dr_reproject_params) and skips the preview ladder: the following step() calls add full-resolution frames and return divide_by
+        1, 2, ... -- the frames since the move; the carried samples are in the history plane, which image() divides by as well.  Returns
+        the counts Context.reproject returns.  reproject=False, or a move before the ladder is complete (there is no full-resolution image
+        to carry yet): the reference's behaviour, the accumulator is reset and the ladder starts again; returns None."""
+        assert (scene_settings.width, scene_settings.height) == (self.W, self.H), "move_camera cannot change the image size"
+        if not reproject or self.iter < 4:
+            self.s = scene_settings
+            self.iter = 0
+            self._pnum = 3
+            self.ctx.accum_reset(self.W, self.H)
+            return None
+        self.ctx._acc_shape = (self.W, self.H, 3)
+        counts = self.ctx.reproject(self.settings13(), pack_settings13(scene_settings, 1), self.W, self.H, self.iter - self._pnum, **params)
+        self.s = scene_settings
+        self.iter = max(self.iter, 5)   # past the ladder: settings13() is the full-resolution view from here on
+        self._pnum = self.iter
+        return counts
 
     def image(self, divide_by, denoise=None):
         """The displayed image: accum_present(divide_by); with denoise (True, or a dict of dr_denoise_params fields) the same image through
@@ -831,7 +900,7 @@ class ProgressiveRenderer:
         pending = []
         for k in range(nframes):
             self.iter += 1
-            div = self.iter - 3
+            div = self.iter - self._pnum
             pending.append((c.pipeline_submit(st, self.W, self.H, s.background, self._seed(), div), self.iter, div))
             self.frames_rendered += 1
             if len(pending) >= in_flight:

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <exception>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernels.hpp"
@@ -44,6 +45,16 @@ struct dr_context {
   bool dn_valid = false; float dn_key[13] = {0}; int dn_W = 0, dn_H = 0; uint64_t dn_gen = 0;
   uint8_t* dn_staging = nullptr; size_t dn_staging_bytes = 0;
   uint64_t scene_gen = 0;                  // scene uploads so far
+  // dr_accum_reproject: the second accumulator of the pair (swapped with `accum` by every reprojection), the two history planes (hist: the
+  // current one, null until the first reprojection and after dr_accum_reset), the guide planes of two views (t n | normal 3n | material n
+  // floats each; set rp_cur holds the cached `to` view, keyed like the denoiser's guides), the class counts and the AOV passes of the last call
+  int32_t* accum2 = nullptr; size_t accum2_elems = 0;
+  int32_t* hist_buf[2] = {nullptr, nullptr}; size_t hist_elems[2] = {0, 0};
+  int32_t* hist = nullptr; int hist_cur = 0;
+  float* rp_planes[2] = {nullptr, nullptr}; size_t rp_floats[2] = {0, 0};
+  bool rp_valid = false; int rp_cur = 0; float rp_key[13] = {0}; int rp_W = 0, rp_H = 0; uint64_t rp_gen = 0;
+  unsigned long long* rp_counts = nullptr;
+  int rp_passes = 0;
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
   // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
   // computed on `stream` by launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload and cert_factor
@@ -490,7 +501,8 @@ void dr_context_destroy(dr_context* c) {
   for (int k = 1; k < dr_context::PIPE_STREAMS; k++) if (c->pipe_stream[k]) (void)hipStreamSynchronize(c->pipe_stream[k]);
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
   void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
-                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->cert_mask};
+                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->cert_mask,
+                  c->accum2, c->hist_buf[0], c->hist_buf[1], c->rp_planes[0], c->rp_planes[1], c->rp_counts};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -517,6 +529,7 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   HIP_TRY(hipSetDevice(c->device));
   c->scene_gen++;                  // the denoiser's cached guides belong to the old scene
   c->dn_valid = false;
+  c->rp_valid = false;
   DeviceImage img;
   int rc = DR_OK;
   try {
@@ -606,6 +619,7 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
       *value = (int)((1000ull * n_flagged + (unsigned)c->cert_tiles / 2) / (unsigned)c->cert_tiles);
     }
   }
+  else if (n == "reproject_aov_passes") *value = c->rp_passes;               // read-only: AOV passes the last dr_accum_reproject traced
   else if (n == "traversal") *value = traversal_of(c);                        // the traversal launches really use
   else { set_error("unknown option " + n); return DR_ERR_INVALID; }
   return DR_OK;
@@ -654,6 +668,7 @@ int dr_accum_reset(dr_context* c, int W, int H) {
   int rc = ensure(c->accum, c->accum_elems, elems);
   if (rc != DR_OK) return rc;
   c->accW = W; c->accH = H;
+  c->hist = nullptr;               // the history plane goes with the sums it counted
   HIP_TRY(hipMemsetAsync(c->accum, 0, elems * sizeof(int32_t), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DR_OK;
@@ -772,7 +787,7 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
   L.D.iterations = p.iterations; L.D.sigma_luminance = p.sigma_luminance; L.D.normal_power_log2 = p.normal_power_log2;
   L.D.sigma_depth = p.sigma_depth; L.D.demodulate = p.demodulate != 0; L.D.material_stop = p.material_stop != 0;
-  L.acc = c->accum;
+  L.acc = c->accum; L.hist = c->hist;
   if (p.iterations > 0 && n > 0) {
     // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
     const size_t need = 17 * n;
@@ -840,6 +855,105 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, f32_dev, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, rgb_dev, npix * 3, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+int dr_reproject_defaults(dr_reproject_params* p) {
+  if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
+  p->max_history = 32; p->normal_cos = 0.9f; p->plane_tolerance = 0.01f; p->material_mask = 0xFFFFFFC3u; p->sky = 1;
+  return DR_OK;
+}
+
+int dr_accum_reproject(dr_context* c, const float from_settings13[13], const float to_settings13[13], int W, int H, int frames,
+                       const dr_reproject_params* params, dr_reproject_result* result) {
+  if (!c || !from_settings13 || !to_settings13) { set_error("null argument"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  RenderParams Pf, Pt;
+  int traversal = 0;
+  { const int rc = aov_view(c, from_settings13, W, H, Pf, traversal); if (rc != DR_OK) return rc; }
+  { const int rc = aov_view(c, to_settings13, W, H, Pt, traversal); if (rc != DR_OK) return rc; }
+  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { set_error("reproject: the two views have different divisors"); return DR_ERR_INVALID; }
+  if (c->stripe_mod != 1 || c->stripe_rem != 0) { set_error("reproject: the context renders a stripe (dr_context_set_stripe); only (1, 0) is supported"); return DR_ERR_INVALID; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  if (W != c->accW || H != c->accH) {
+    set_error("reproject: " + std::to_string(W) + " x " + std::to_string(H) + " is not the accumulator's " + std::to_string(c->accW) + " x " + std::to_string(c->accH));
+    return DR_ERR_INVALID;
+  }
+  if (frames < 1) { set_error("reproject: frames must be >= 1"); return DR_ERR_INVALID; }
+  dr_reproject_params p;
+  dr_reproject_defaults(&p);
+  if (params) p = *params;
+  RpLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.R.max_history = p.max_history; L.R.normal_cos = p.normal_cos; L.R.plane_tolerance = p.plane_tolerance; L.R.material_mask = p.material_mask; L.R.sky = p.sky != 0;
+  if (const char* why = check_reproject_params(L.R)) { set_error(why); return DR_ERR_INVALID; }
+  fill_reproject_camera(Pt, L.to);
+  fill_reproject_camera(Pf, L.from);
+  if (!fill_reproject_proj(L.from, L.J)) { set_error("reproject: the `from` view is degenerate (its focus plane has no normal facing the camera)"); return DR_ERR_INVALID; }
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
+
+  const int gw = Pt.gx * 8, gh = Pt.gy * 8;
+  const size_t n = (size_t)gw * (size_t)gh, npix = (size_t)W * (size_t)H;
+  int rc;
+  if ((rc = ensure(c->accum2, c->accum2_elems, npix * 3)) != DR_OK) return rc;
+  const int hto = c->hist ? 1 - c->hist_cur : 0;
+  if ((rc = ensure(c->hist_buf[hto], c->hist_elems[hto], npix)) != DR_OK) return rc;
+  if (!c->rp_counts) HIP_TRY(hipMalloc((void**)&c->rp_counts, 4 * sizeof(unsigned long long)));
+  // the guides: the cached planes serve as `from` when their key matches; the `to` view is traced into the other set (into none when it is
+  // the `from` view itself) and becomes the cache
+  const bool warm = c->rp_valid && c->rp_W == W && c->rp_H == H && c->rp_gen == c->scene_gen && memcmp(c->rp_key, from_settings13, sizeof(c->rp_key)) == 0;
+  const bool same_view = memcmp(from_settings13, to_settings13, 13 * sizeof(float)) == 0;
+  const int sf = warm ? c->rp_cur : 0, st = same_view ? sf : 1 - sf;
+  c->rp_valid = false;
+  c->rp_passes = 0;
+  auto trace = [&](int set, const RenderParams& P, const float* st13) -> int {
+    if (n == 0) return DR_OK;
+    if (5 * n > c->rp_floats[set]) {
+      if (c->rp_planes[set]) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->rp_planes[set]); c->rp_planes[set] = nullptr; c->rp_floats[set] = 0; }
+      HIP_TRY(hipMalloc((void**)&c->rp_planes[set], 5 * n * sizeof(float)));
+      c->rp_floats[set] = 5 * n;
+    }
+    AovLaunch A;
+    memset(&A, 0, sizeof(A));
+    A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
+    A.focus = st13[7];
+    A.t = c->rp_planes[set]; A.normal = c->rp_planes[set] + n; A.material = reinterpret_cast<int32_t*>(c->rp_planes[set] + 4 * n);
+    launch_aov(c->stream, P, traversal, A);
+    HIP_TRY(hipGetLastError());
+    c->rp_passes++;
+    return DR_OK;
+  };
+  if (!warm && (rc = trace(sf, Pf, from_settings13)) != DR_OK) return rc;
+  if (!same_view && (rc = trace(st, Pt, to_settings13)) != DR_OK) return rc;
+  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.frames = frames;
+  if (n > 0) {
+    L.t_from = c->rp_planes[sf]; L.normal_from = c->rp_planes[sf] + n; L.mat_from = reinterpret_cast<const int32_t*>(c->rp_planes[sf] + 4 * n);
+    L.t_to = c->rp_planes[st]; L.normal_to = c->rp_planes[st] + n; L.mat_to = reinterpret_cast<const int32_t*>(c->rp_planes[st] + 4 * n);
+  }
+  L.acc_from = c->accum; L.hist_from = c->hist;
+  L.acc_to = c->accum2; L.hist_to = c->hist_buf[hto];
+  L.counts = c->rp_counts;
+  HIP_TRY(hipMemsetAsync(c->rp_counts, 0, 4 * sizeof(unsigned long long), c->stream));
+  if (gw < W || gh < H) {                                     // pixels outside the grid are 0
+    HIP_TRY(hipMemsetAsync(c->accum2, 0, npix * 3 * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->hist_buf[hto], 0, npix * sizeof(int32_t), c->stream));
+  }
+  launch_reproject(c->stream, L);
+  HIP_TRY(hipGetLastError());
+  unsigned long long counts[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(counts, c->rp_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // the pair of the `to` view is the current one from here on
+  std::swap(c->accum, c->accum2); std::swap(c->accum_elems, c->accum2_elems);
+  c->hist = c->hist_buf[hto]; c->hist_cur = hto;
+  memcpy(c->rp_key, to_settings13, sizeof(c->rp_key));
+  c->rp_W = W; c->rp_H = H; c->rp_gen = c->scene_gen; c->rp_cur = st; c->rp_valid = n > 0;
+  if (result) {
+    result->pixels = (int64_t)n;
+    result->valid = (int64_t)counts[RP_VALID]; result->masked = (int64_t)counts[RP_MASKED];
+    result->offscreen = (int64_t)counts[RP_OFFSCREEN]; result->rejected = (int64_t)counts[RP_REJECTED];
+  }
   return DR_OK;
 }
 
@@ -1055,7 +1169,7 @@ int pipeline_flush_some(dr_context* c, int n) {
         HIP_TRY(hipHostMalloc((void**)&sl.rgb_host[f], bytes, hipHostMallocDefault));
         sl.rgb_bytes[f] = bytes;
       }
-      launch_present(c->acc_stream, c->accum, sl.rgb_dev[f], W, H, div);
+      launch_present(c->acc_stream, c->accum, c->hist, sl.rgb_dev[f], W, H, div);
       HIP_TRY(hipMemcpyAsync(sl.rgb_host[f], sl.rgb_dev[f], bytes, hipMemcpyDeviceToHost, c->acc_stream));
       sl.div[f] = div;
     }
@@ -1217,6 +1331,24 @@ int dr_accum_read(dr_context* c, int32_t* out_int3) {
   return DR_OK;
 }
 
+int dr_accum_history_read(dr_context* c, int32_t* out) {
+  if (!c || !out || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }
+  const size_t n = (size_t)c->accW * c->accH;
+  if (!c->hist) { memset(out, 0, n * sizeof(int32_t)); return DR_OK; }
+  HIP_TRY(hipMemcpyAsync(out, c->hist, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
+  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  *dev_ptr = c->hist;
+  if (bytes) *bytes = c->hist ? (uint64_t)c->accW * c->accH * sizeof(int32_t) : 0;
+  return DR_OK;
+}
+
 int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8) {
   if (!c || !out_rgb8 || !c->accum || divide_by == 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
@@ -1228,7 +1360,7 @@ int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8) {
     HIP_TRY(hipMalloc((void**)&c->present, bytes));
     c->present_bytes = bytes;
   }
-  launch_present(c->stream, c->accum, c->present, c->accW, c->accH, divide_by);
+  launch_present(c->stream, c->accum, c->hist, c->present, c->accW, c->accH, divide_by);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_rgb8, c->present, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

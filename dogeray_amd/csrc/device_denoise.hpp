@@ -27,6 +27,11 @@ __device__ __forceinline__ float dn_q(float x) { return (1.0f + x) + (0.5f * x) 
 
 __device__ __forceinline__ float dn_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
+// c of one channel: the sum over the pixel's divisor -- divide_by, plus the pixel's entry of the history plane when the accumulator has one
+// (dr_accum_reproject); a divisor of 0 gives 0
+__device__ __forceinline__ int dn_divisor(const int32_t* hist, size_t pixel, int divide_by) { return hist ? hist[pixel] + divide_by : divide_by; }
+__device__ __forceinline__ float dn_colour(int32_t sum, int divisor) { return divisor == 0 ? 0.0f : (float)sum / (float)divisor; }
+
 // a' of one channel: 1 for a miss, an albedo <= 1e-3, or demodulation off
 __device__ __forceinline__ float dn_albedo(float a, int m, int demodulate) { return (!demodulate || m == DN_MISS || a <= 1e-3f) ? 1.0f : a; }
 

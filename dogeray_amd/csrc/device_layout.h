@@ -194,4 +194,28 @@ struct DnParams {
   int material_stop;
 };
 
+// Temporal reprojection (dr_accum_reproject; device_reproject.hpp): the parameters (dr_reproject_params, validated by dr_accum_reproject /
+// hk_reproject), one view's float camera block as fill_view_params forms it, and the projection into the `from` camera, formed once per call
+// in double (params_host.hpp fill_reproject_proj)
+constexpr int RP_VALID = 0, RP_MASKED = 1, RP_OFFSCREEN = 2, RP_REJECTED = 3;      // the class of a grid pixel
+constexpr int RP_MAX_HISTORY = 65535;
+struct RpParams {
+  int max_history;
+  float normal_cos;
+  float plane_tolerance;
+  uint32_t material_mask;
+  int sky;
+};
+struct RpCamera {
+  float from[3], llc[3], hor[3], ver[3];
+  double den_w, den_h;
+};
+struct RpProj {
+  double L[3];         // llc - from
+  double cN[3];        // hor x ver, oriented so that cN . L > 0
+  double hor[3], ver[3];
+  double LcN;          // L . cN
+  double hh, vv;       // hor . hor, ver . ver
+};
+
 }  // namespace dr

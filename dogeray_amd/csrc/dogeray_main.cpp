@@ -116,7 +116,7 @@ void usage() {
   fprintf(stderr,
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
-          "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm]\n"
+          "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm] [--move-to CX,CY,CZ,LX,LY,LZ] [--move-frames N]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -130,13 +130,19 @@ void usage() {
           "               PREFIX.depth.pfm, .distance.pfm, .normal.pfm, .albedo.pfm and .object.pfm (object ids as floats, exact below 2^24)\n"
           "  --autofocus  before rendering, set the focus distance to the depth of what the centre pixel sees (the reference's Z/X keys)\n"
           "  --denoise    after the render, also write the final image through the AOV-guided a-trous denoiser (dr_accum_denoise, default\n"
-          "               parameters): .bmp / .ppm as RGB8, .pfm as floats in 0..255 units (--gpus N: on rank 0's context after the final gather)\n");
+          "               parameters): .bmp / .ppm as RGB8, .pfm as floats in 0..255 units (--gpus N: on rank 0's context after the final gather)\n"
+          "  --move-to    after the --frames frames in the file's view, move the camera to CX,CY,CZ looking at LX,LY,LZ: the accumulated image is\n"
+          "               reprojected into the new view (dr_accum_reproject, default parameters; one line reports the pixel counts), --move-frames\n"
+          "               more frames (default 1) are added there, and --out / --aov / --denoise show the new view (one context only: not with --gpus)\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
   std::string scene_path = "scene.rts", out_path, aov_prefix, denoise_path;
+  bool move = false;
+  float move_to[6] = {0, 0, 0, 0, 0, 0};
+  int move_frames = 1;
   const char* texdir = nullptr;
   int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0;
   uint64_t seed = 1;
@@ -161,11 +167,17 @@ int main(int argc, char** argv) {
     else if (a == "--aov") aov_prefix = next();
     else if (a == "--autofocus") autofocus = true;
     else if (a == "--denoise") denoise_path = next();
+    else if (a == "--move-to") {
+      if (sscanf(next(), "%f,%f,%f,%f,%f,%f", &move_to[0], &move_to[1], &move_to[2], &move_to[3], &move_to[4], &move_to[5]) != 6) { usage(); return 2; }
+      move = true;
+    }
+    else if (a == "--move-frames") move_frames = atoi(next());
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
   }
   if (group < 1) group = 1;
+  if (move && (gpus >= 1 || move_frames < 1)) { fprintf(stderr, "dogeray: --move-to needs a single context (no --gpus) and --move-frames >= 1\n"); return 2; }
 
   if (!quiet) printf("DOGERAY render path on MI355X (dogeray_amd, C ABI v%d)\n", dr_abi_version());
   printf("%s%s\n", have_scene ? "Opening:" : "Opening Default Scene: ", scene_path.c_str());   // K:2045-2050
@@ -238,6 +250,7 @@ int main(int argc, char** argv) {
   const uint64_t seed_stride = 1000003;
   std::vector<uint8_t> rgb((size_t)W * H * 3);
   int divide_by = 1;
+  float last_st[13] = {0};               // the settings of the newest frames in the accumulator
   const int total_iters = 4 + frames;
   while (iter < total_iters) {
     auto begin = std::chrono::steady_clock::now();
@@ -265,6 +278,7 @@ int main(int argc, char** argv) {
           iter++;
           uint64_t t = 0;
           if (dr_pipeline_submit(ctx, st, W, H, s.background, seed + frame_no * seed_stride, iter - 3, &t) != DR_OK) die("submit");      // K:2287
+          memcpy(last_st, st, sizeof(last_st));
           tickets.push_back(t); divs.push_back(iter - 3);
           frame_no++;
           if (iter < total_iters && tickets.size() < window) continue;
@@ -287,6 +301,7 @@ int main(int argc, char** argv) {
       pnum = 3;
     }
     if (render(st, seed + frame_no * seed_stride, n) != DR_OK) die("render");
+    memcpy(last_st, st, sizeof(last_st));
     frame_no += (uint64_t)n;
     iter += n;
     divide_by = iter - pnum;                                          // K:2287
@@ -298,6 +313,20 @@ int main(int argc, char** argv) {
     }
   }
   if (!quiet) printf("\n");
+
+  if (move) {                            // a camera move: carry the image into the new view, then add frames there
+    float to_st[13];
+    for (int k = 0; k < 3; k++) { s.campos[k] = move_to[k]; s.look[k] = move_to[3 + k]; }
+    pack13(s, 1, s.spp, s.max_depth, to_st);
+    dr_reproject_result rr;
+    if (dr_accum_reproject(ctx, last_st, to_st, W, H, divide_by, nullptr, &rr) != DR_OK) die("reproject");
+    printf("reprojected: %lld pixels, %lld valid, %lld masked, %lld offscreen, %lld rejected\n", (long long)rr.pixels, (long long)rr.valid,
+           (long long)rr.masked, (long long)rr.offscreen, (long long)rr.rejected);
+    if (dr_render_accumulate(ctx, to_st, W, H, s.background, seed + frame_no * seed_stride, seed_stride, move_frames) != DR_OK) die("render");
+    frame_no += (uint64_t)move_frames;
+    divide_by = move_frames;             // the frames since the move; the carried samples are in the history plane
+    if (dr_accum_present(ctx, divide_by, rgb.data()) != DR_OK) die("present");
+  }
 
   dr_stats stats;
   if (dr_stats_get(ctx, &stats) == DR_OK && stats.frames > 0)

@@ -3,6 +3,7 @@
 //   kernels_aux.hip           tile-order feedback, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
+//   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
 #pragma once
@@ -44,7 +45,8 @@ void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsign
 // the camera rays' grazing certificate of a view: mask = (ntiles + 31) / 32 words of tile bits (set: the tile's camera rays keep the scene's margin),
 // then the "every tile" word and the number of flagged tiles (device_core.hpp cert_leaf)
 void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, int ntiles);
-void launch_present(hipStream_t stream, const int32_t* acc, uint8_t* rgb, int W, int H, int div);
+// hist: the history plane (int32 per pixel at x * H + y; the divisor of pixel p is hist[p] + div, a divisor of 0 gives 0), or null: acc / div
+void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div);
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n);      // acc += frame (pipelined single frames)
 void launch_stripe_copy(hipStream_t stream, int32_t* dst, const int32_t* src, int ncols, int run4, long long dst_first4, long long dst_stride4,
                         long long src_first4, long long src_stride4);
@@ -80,6 +82,7 @@ struct DnLaunch {
   int divide_by;
   DnParams D;
   const int32_t* acc;
+  const int32_t* hist;            // the accumulator's history plane (pixel (x, y) at x * H + y: its divisor is hist + divide_by), or null
   const float* normal;            // launch_aov's normal (3 per pixel) and depth: read by the guide prepare only
   const float* depth;
   const float* albedo;            // launch_aov's albedo (3 per pixel)
@@ -95,5 +98,24 @@ void launch_denoise_guides(hipStream_t stream, const DnLaunch& L);              
 void launch_denoise_colour(hipStream_t stream, const DnLaunch& L, int stage);      // 0: acc -> (e, l) in dst; 1: src (e, l) -> (e, var) in dst
 void launch_denoise_pass(hipStream_t stream, const DnLaunch& L, int step, int lattice);   // src -> dst, one a-trous iteration
 void launch_denoise_finish(hipStream_t stream, const DnLaunch& L);                 // src (or, iterations 0, acc) -> out_f32 / out_rgb8
+
+// kernels_reproject.hip: the guides of both views are row-major gw x gh planes as launch_aov writes them; the accumulators are column-major W x H x 3
+// ((x * H + y) * 3) and the history planes W x H (x * H + y).  Pixels outside the grid are not written (the caller clears the `to` pair).
+struct RpLaunch {
+  int gw, gh;                     // pixel grid of both views
+  int W, H;
+  int frames;                     // frames the `from` accumulator holds beyond its history plane
+  RpParams R;
+  RpCamera to, from;
+  RpProj J;                       // projection into the `from` camera
+  const float* t_to; const float* normal_to; const int32_t* mat_to;
+  const float* t_from; const float* normal_from; const int32_t* mat_from;
+  const int32_t* acc_from;
+  const int32_t* hist_from;       // null: no history yet (0 everywhere)
+  int32_t* acc_to;
+  int32_t* hist_to;
+  unsigned long long* counts;     // [4]: pixels of class RP_VALID, RP_MASKED, RP_OFFSCREEN, RP_REJECTED are added
+};
+void launch_reproject(hipStream_t stream, const RpLaunch& L);
 
 }  // namespace dr

@@ -155,12 +155,16 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const unsigned* __rest
 }
 
 // clamp(acc / divide_by, 0, 255) into row-major RGB8 (draw loop K:2281-2287)
-__global__ void present_kernel(const int32_t* acc, uint8_t* rgb, int W, int H, int div) {
+__global__ void present_kernel(const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div) {
   int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= W * H) return;
   int x = idx / H, y = idx - x * H;          // consecutive threads walk a column (coalesced read)
   const int32_t* p = acc + (size_t)idx * 3;
   uint8_t* q = rgb + ((size_t)y * W + x) * 3;
+  if (hist) {                                // a history plane (dr_accum_reproject): the pixel's own divisor, 0 giving 0
+    div += hist[idx];
+    if (div == 0) { q[0] = 0; q[1] = 0; q[2] = 0; return; }
+  }
   for (int k = 0; k < 3; k++) {
     int v = p[k] / div;
     v = v < 0 ? 0 : (v > 255 ? 255 : v);
@@ -418,9 +422,9 @@ void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsign
   hipLaunchKernelGGL(tile_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, pixel_cost, tile_cost, tiles);
   hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, tile_cost, tile_order, region_start, tiles, regions, heavy_factor, split_steps, split_limit);
 }
-void launch_present(hipStream_t stream, const int32_t* acc, uint8_t* rgb, int W, int H, int div) {
+void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div) {
   const int n = W * H;
-  hipLaunchKernelGGL(present_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc, rgb, W, H, div);
+  hipLaunchKernelGGL(present_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, acc, hist, rgb, W, H, div);
 }
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n) {      // n int32
   const size_t n4 = n / 4;

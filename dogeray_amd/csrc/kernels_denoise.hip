@@ -40,12 +40,13 @@ __global__ __launch_bounds__(256) void dn_colour_kernel(DnLaunch L) {
   if (idx >= (long long)L.gw * L.gh) return;
   const int x = (int)(idx / L.gh), y = (int)(idx - (long long)x * L.gh);
   const size_t i = (size_t)y * L.gw + x;
-  const int32_t* a = L.acc + ((size_t)x * (size_t)L.H + (size_t)y) * 3;
-  const float n = (float)L.divide_by;
+  const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
+  const int32_t* a = L.acc + px * 3;
+  const int n = dn_divisor(L.hist, px, L.divide_by);
   const int m = L.mat[i];
-  const float er = ((float)a[0] / n) / dn_albedo(L.albedo[3 * i], m, L.D.demodulate);
-  const float eg = ((float)a[1] / n) / dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate);
-  const float eb = ((float)a[2] / n) / dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate);
+  const float er = dn_colour(a[0], n) / dn_albedo(L.albedo[3 * i], m, L.D.demodulate);
+  const float eg = dn_colour(a[1], n) / dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate);
+  const float eb = dn_colour(a[2], n) / dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate);
   reinterpret_cast<float4*>(L.dst)[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
 }
 
@@ -116,9 +117,10 @@ __global__ __launch_bounds__(256) void dn_finish_kernel(DnLaunch L) {
   if (x < L.gw && y < L.gh) {
     const size_t i = (size_t)y * L.gw + x;
     if (L.D.iterations == 0) {               // no filter, no demodulation: c itself
-      const int32_t* a = L.acc + ((size_t)x * (size_t)L.H + (size_t)y) * 3;
-      const float n = (float)L.divide_by;
-      f[0] = (float)a[0] / n; f[1] = (float)a[1] / n; f[2] = (float)a[2] / n;
+      const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
+      const int32_t* a = L.acc + px * 3;
+      const int n = dn_divisor(L.hist, px, L.divide_by);
+      f[0] = dn_colour(a[0], n); f[1] = dn_colour(a[1], n); f[2] = dn_colour(a[2], n);
     } else {
       const float4 e = reinterpret_cast<const float4*>(L.src)[i];
       const int m = L.mat[i];

@@ -105,6 +105,32 @@ inline bool fill_cert_view(const RenderParams& P, double a_star, float e_own, Ce
   return cv.dmin > 8.0 * cv.r_o && cv.dmin > 0;
 }
 
+// Temporal reprojection (dr_accum_reproject): a view's float camera block, and the projection into it in double -- L = llc - from,
+// cN = hor x ver (negated when cN . L < 0), L . cN, hor . hor, ver . ver, every dot product (a.x b.x + a.y b.y) + a.z b.z.  Returns false
+// for a degenerate view: L . cN zero or not finite.
+inline void fill_reproject_camera(const RenderParams& P, RpCamera& C) {
+  for (int a = 0; a < 3; a++) { C.from[a] = P.from[a]; C.llc[a] = P.llc[a]; C.hor[a] = P.hor[a]; C.ver[a] = P.ver[a]; }
+  C.den_w = P.den_w; C.den_h = P.den_h;
+}
+inline bool fill_reproject_proj(const RpCamera& C, RpProj& J) {
+  auto dot = [](const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+  for (int a = 0; a < 3; a++) { J.L[a] = (double)C.llc[a] - (double)C.from[a]; J.hor[a] = (double)C.hor[a]; J.ver[a] = (double)C.ver[a]; }
+  J.cN[0] = J.hor[1] * J.ver[2] - J.hor[2] * J.ver[1];
+  J.cN[1] = J.hor[2] * J.ver[0] - J.hor[0] * J.ver[2];
+  J.cN[2] = J.hor[0] * J.ver[1] - J.hor[1] * J.ver[0];
+  if (dot(J.cN, J.L) < 0) for (int a = 0; a < 3; a++) J.cN[a] = -J.cN[a];
+  J.LcN = dot(J.L, J.cN);
+  J.hh = dot(J.hor, J.hor); J.vv = dot(J.ver, J.ver);
+  return std::isfinite(J.LcN) && J.LcN != 0.0;
+}
+// dr_reproject_params' ranges; null, or what is wrong
+inline const char* check_reproject_params(const RpParams& R) {
+  if (R.max_history < 1 || R.max_history > RP_MAX_HISTORY) return "reproject: max_history must be 1 .. 65535";
+  if (!(R.normal_cos >= -1.0f && R.normal_cos <= 1.0f)) return "reproject: normal_cos must be -1 .. 1";
+  if (!(R.plane_tolerance >= 0.0f)) return "reproject: plane_tolerance must be >= 0";
+  return nullptr;
+}
+
 // The factor a certified camera ray's |d|-proportional margin carries: 1e-4 / a_star, rounded up (step 2 divides by a_star instead of 1e-4)
 inline float cert_factor_k(double a_star) {
   const double x = 1e-4 / a_star;

@@ -196,6 +196,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   margin); a single-frame launch of a view not seen before computes no mask
  *   "cert_factor"   the certified |d . (e1 x e2)| in units of the 1e-4 cut-off (default 40)
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
+ *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
+ *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -258,10 +260,17 @@ int dr_render_accumulate_pipelined(dr_context* c, const float settings13[13], in
  * (a collective on packed stripes) against it with events. */
 int dr_context_stream(dr_context* c, void** hip_stream);
 int dr_accum_read(dr_context* c, int32_t* out_int3 /* W*H*3 */);
-/* The display divide of K:2287: rgb8[(y*W + x)*3 + ch] = clamp(acc / divide_by, 0, 255). */
+/* The display divide of K:2287: rgb8[(y*W + x)*3 + ch] = clamp(acc / divide_by, 0, 255).  While the accumulator has a history plane
+ * (dr_accum_reproject) pixel p divides by hist[p] + divide_by, and a divisor of 0 gives 0. */
 int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8 /* W*H*3, row-major */);
-/* Device address of the accumulator (int32[W*H*3]) for device-side gathers (RCCL). */
+/* Device address of the accumulator (int32[W*H*3]) for device-side gathers (RCCL); dr_accum_reproject swaps between two buffers, this is
+ * the current one. */
 int dr_accum_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes);
+/* The history plane (dr_accum_reproject): int32 per pixel, pixel (x, y) at x * H + y like the accumulator -- the samples acc[p] carries in
+ * addition to the frames the caller counts itself.  Without a plane (no reprojection since the last dr_accum_reset) dr_accum_history_read
+ * writes zeros and dr_accum_history_device_ptr gives NULL / 0 bytes. */
+int dr_accum_history_read(dr_context* c, int32_t* out /* W*H */);
+int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes);
 /* Multi-GPU gather, device side.  The framebuffer is column-major (K:1006), so one 8-pixel block column is one
  * contiguous run of 8*H*3 int32 and a context's stripe (dr_context_set_stripe: columns rem, rem+mod, ...) packs into
  * [ncols][8*H*3].  dr_accum_pack_stripe queues that copy on the context's stream into one of two library-owned
@@ -320,12 +329,14 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
 
 /* ------------------------------------------------------------------ denoiser ------------ */
 /* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by
- * the first-hit AOVs of the same settings13 (dr_render_aov).  No temporal reprojection: the accumulator is the temporal mean already.  Every
+ * the first-hit AOVs of the same settings13 (dr_render_aov).  No temporal reprojection here: the accumulator is the temporal mean already
+ * (dr_accum_reproject carries it across a camera move; the filter then reads each pixel's own divisor).  Every
  * weight is + - * /, sqrtf, fminf / fmaxf and comparisons in the order written here (dogeray_amd/csrc/device_denoise.hpp, no FMA contraction),
  * so the GPU is bit-identical to the host build of the same source and to the numpy restatement in the tests.
  *   grid       the pixel grid of dr_render_aov: gw x gh = (W / div / 8) * 8 x (H / div / 8) * 8; pixel p = (x, y)
  *   guides     normal n (3 f32), albedo a (3 f32), depth z, material m (-1: a miss) of p's pinhole ray (dr_render_aov's channels)
- *   colour     c = (float)acc / (float)divide_by per channel, acc the column-major accumulator at (x * H + y) * 3
+ *   colour     c = (float)acc / (float)divide_by per channel, acc the column-major accumulator at (x * H + y) * 3; while the accumulator
+ *              has a history plane (dr_accum_reproject) c = (float)acc / (float)(hist_p + divide_by), and 0 where that divisor is 0
  *   demodulate e = c / a', a' = (m == -1 || a <= 1e-3f || !demodulate) ? 1 : a, per channel; l = (0.2126f e.r + 0.7152f e.g) + 0.0722f e.b
  *   q(x)       (1 + x) + (0.5 x) x; phi(x) = 1 / q(x) (phi(inf) = 0) is the rational stand-in for exp(-x)
  *   gz_p       fmaxf(gx, gy), gx = fminf(|z(x+1) - z_p|, |z_p - z(x-1)|), a neighbour outside the grid or a miss counting as +inf, an axis with
@@ -367,6 +378,58 @@ int dr_denoise_defaults(dr_denoise_params* p);
  * divide_by < 1, iterations outside 0 .. 10, a negative sigma, normal_power_log2 outside 0 .. 16, or no output. */
 int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_denoise_params* params, float* out_f32,
                      uint8_t* out_rgb8, int device_pointers);
+
+/* ------------------------------------------------------------------ temporal reprojection */
+/* Carries the accumulator across a camera move: the temporal half of SVGF (Schied et al. 2017) as a nearest-neighbour BACKWARD reprojection.
+ * The accumulated sums of the `from` view are moved to where the same surface points appear in the `to` view, and a per-pixel HISTORY PLANE
+ * keeps how many samples each pixel carries.  All arithmetic is double on the float camera blocks (from, llc, hor, ver, den_w, den_h as
+ * dr_render_frame forms them from settings13, K:1016-1068) and the float first-hit AOVs, only + - * /, sqrt, floor and comparisons in the
+ * order written here (dogeray_amd/csrc/device_reproject.hpp, no FMA contraction), every dot product a . b = (a.x b.x + a.y b.y) + a.z b.z, so
+ * the GPU is bit-identical to the host build of the same source and to the numpy restatement in the tests.
+ *   grid       the pixel grid of dr_render_aov, gw x gh, the same for both views; p = (x, y) a pixel of the `to` view
+ *   guides     t, shading normal n, material m (-1: a miss) of both views' pinhole rays (dr_render_aov's channels)
+ *   d(view, x, y)   the float pinhole direction of dr_render_aov: nu = (float)(((double)x + 0.5) / den_w), nv likewise with y and den_h,
+ *              d = ((llc + nu * hor) + nv * ver) - from per component in float; then widened to double
+ *   masked     m_p is not allowed: a miss when sky == 0; a hit when bit b of material_mask is clear, b = m_p for 0 <= m_p <= 30, else 31
+ *   world point  d_p = d(to, x, y).  A hit: X = from_to + (double)t_p * d_p per component, v = X - from_from.  A miss: v = d_p (the sky is at
+ *              infinity)
+ *   projection (once per call) L = llc_from - from_from; cN = hor_from x ver_from = (hor.y ver.z - hor.z ver.y, hor.z ver.x - hor.x ver.z,
+ *              hor.x ver.y - hor.y ver.x), negated when cN . L < 0; L . cN zero or not finite: DR_ERR_INVALID (a degenerate view).
+ *              (per pixel) a = v . cN; !(a > 0): offscreen.  s = (L . cN) / a; r = s * v - L per component; nu = (r . hor) / (hor . hor),
+ *              nv = (r . ver) / (ver . ver); fx = floor(nu * den_w), fy = floor(nv * den_h); unless 0 <= fx < gw and 0 <= fy < gh: offscreen;
+ *              q = (fx, fy).  Pixel centres sit at (x + 0.5) / den_w, so an unchanged view maps every pixel to itself.
+ *   validation m_q != m_p: rejected.  Both miss: valid.  Hits: n_p . n_q < normal_cos (or unordered): rejected; d_q = d(from, q),
+ *              e = X - (from_from + (double)t_q * d_q) per component, |e . n_p| <= plane_tolerance * sqrt(v . v) or rejected (the plane
+ *              distance of SVGF).  There is no object-id test: an object is one triangle, and triangles may be pixel-sized.
+ *   carry      valid: cnt = hist_from[q] + frames (hist_from = 0 without a plane).  cnt <= max_history: acc_to[p] = acc_from[q] and
+ *              hist_to[p] = cnt; otherwise acc_to[p] = (int32)(((int64)acc_from[q] * max_history) / cnt) per channel (division towards
+ *              zero) and hist_to[p] = max_history.  Every other pixel, and every pixel outside the grid: acc_to = 0, hist_to = 0.
+ * The classes are tested in the order masked, offscreen, rejected, valid; dr_reproject_result counts the grid's pixels in each. */
+typedef struct dr_reproject_params {
+  int max_history;         /* 1 .. 65535, default 32: most samples a pixel carries over */
+  float normal_cos;        /* -1 .. 1, default 0.9 */
+  float plane_tolerance;   /* >= 0, default 0.01: in units of the distance from the `from` camera */
+  uint32_t material_mask;  /* default 0xFFFFFFC3: diffuse 0, emissive 1 and every id from 6 on are carried; mirror 2, metal 3, glass 4 and
+                              glossy 5 are view-dependent and start again */
+  int sky;                 /* default 1: misses are carried */
+} dr_reproject_params;
+typedef struct dr_reproject_result {
+  int64_t pixels;          /* gw * gh = valid + masked + offscreen + rejected */
+  int64_t valid, masked, offscreen, rejected;
+} dr_reproject_result;
+int dr_reproject_defaults(dr_reproject_params* p);
+/* frames >= 1: the frames added to the accumulator since the last dr_accum_reset or dr_accum_reproject (the caller's divide_by).  params
+ * NULL: the defaults; result may be NULL.  The context owns two accumulator / history pairs; the call reads the current pair, writes the other
+ * and makes it the current one: afterwards accumulator and history plane belong to the `to` view and the caller's frame count starts again at
+ * 0.  While a plane exists, dr_accum_present, dr_accum_denoise and dr_pipeline_submit's presents divide pixel p by hist[p] + divide_by;
+ * dr_accum_reset drops the plane, and a context that never reprojects allocates nothing for it.  The guides of the `to` view are kept and keyed
+ * like the denoiser's (settings13, W, H, scene; dr_context_upload_scene drops them): a later call whose `from` is that view traces one AOV
+ * pass instead of two (option "reproject_aov_passes").  Ordered behind the frames submitted before it (dr_pipeline_submit); returns when the
+ * counts are known; changes neither dr_stats nor any option.  Both settings are accepted or refused as by dr_render_aov; DR_ERR_INVALID for no
+ * scene, no accumulator, W / H not the accumulator's, frames < 1, views with different divisors, a stripe other than (1, 0), a degenerate
+ * `from` view, or parameters outside their ranges.  The guides are pinhole rays: the lens is ignored, as by the denoiser. */
+int dr_accum_reproject(dr_context* c, const float from_settings13[13], const float to_settings13[13], int W, int H, int frames,
+                       const dr_reproject_params* params, dr_reproject_result* result);
 
 /* ------------------------------------------------------------------ multi-GPU group ----- */
 /* One process, one context and one host thread per GPU (the reference is single-device, K:2614-2615).  Rank r of n

@@ -18,6 +18,7 @@
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
+#include "../dogeray_amd/csrc/device_reproject.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
 #include "../dogeray_amd/csrc/scene_host.hpp"
@@ -357,9 +358,10 @@ int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int 
 // dr_accum_denoise on the host: device_denoise.hpp over the pixel grid of settings13, stage by stage as kernels_denoise.hip runs it, from guides given
 // as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
 // W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
+// hist (may be NULL): the accumulator's history plane, W x H at x * H + y -- pixel p's divisor is hist[p] + divide_by.
 // Returns 0, or -1 with hk_last_error.
 int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
-               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads) {
+               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist) {
   if (!acc || !settings13 || !normal || !albedo || !depth || !material) { hk_err = "bad argument"; return -1; }
   RenderParams P;
   memset(&P, 0, sizeof(P));
@@ -395,12 +397,13 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
     rows(gh, [&](int y) {                                                  // colour prepare, stage 0
       for (int x = 0; x < gw; x++) {
         const size_t i = (size_t)y * gw + x;
-        const int32_t* a = acc + ((size_t)x * (size_t)H + (size_t)y) * 3;
-        const float nd = (float)divide_by;
+        const size_t px = (size_t)x * (size_t)H + (size_t)y;
+        const int32_t* a = acc + px * 3;
+        const int nd = dn_divisor(hist, px, divide_by);
         const int m = material[i];
-        const float er = ((float)a[0] / nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
-        const float eg = ((float)a[1] / nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
-        const float eb = ((float)a[2] / nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
+        const float er = dn_colour(a[0], nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
+        const float eg = dn_colour(a[1], nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
+        const float eb = dn_colour(a[2], nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
         pa[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
       }
     });
@@ -439,9 +442,10 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
       if (x < gw && y < gh) {
         const size_t i = (size_t)y * gw + x;
         if (D.iterations == 0) {
-          const int32_t* a = acc + ((size_t)x * (size_t)H + (size_t)y) * 3;
-          const float nd = (float)divide_by;
-          f[0] = (float)a[0] / nd; f[1] = (float)a[1] / nd; f[2] = (float)a[2] / nd;
+          const size_t px = (size_t)x * (size_t)H + (size_t)y;
+          const int32_t* a = acc + px * 3;
+          const int nd = dn_divisor(hist, px, divide_by);
+          f[0] = dn_colour(a[0], nd); f[1] = dn_colour(a[1], nd); f[2] = dn_colour(a[2], nd);
         } else {
           const int m = material[i];
           f[0] = pa[i].x * dn_albedo(albedo[3 * i], m, D.demodulate);
@@ -456,6 +460,71 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
       }
     }
   });
+  return 0;
+}
+
+// The float camera block of a view as fill_view_params forms it (what dr_accum_reproject's definition starts from): out12 = from, llc, hor, ver;
+// den2 = den_w, den_h; grid2 = gw, gh.  Returns 0, or -1 with hk_last_error.
+int hk_camera_block(const float* settings13, int W, int H, float* out12, double* den2, int* grid2) {
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  memcpy(out12, P.from, 12); memcpy(out12 + 3, P.llc, 12); memcpy(out12 + 6, P.hor, 12); memcpy(out12 + 9, P.ver, 12);
+  den2[0] = P.den_w; den2[1] = P.den_h;
+  grid2[0] = P.gx * 8; grid2[1] = P.gy * 8;
+  return 0;
+}
+
+// dr_accum_reproject on the host: device_reproject.hpp over the pixel grid, from guides given as arrays in dr_render_aov's layout (t / material
+// gw x gh, normal gw x gh x 3) for both views -- hk_aov's or the GPU's own.  acc_from / acc_to: column-major W x H x 3; hist_from (may be NULL) /
+// hist_to: W x H at x * H + y; params: a dr_reproject_params (NULL: the defaults); counts[5]: pixels, valid, masked, offscreen, rejected.
+// Returns 0, or -1 with hk_last_error.
+int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H, int frames, const float* from_settings13, const float* to_settings13,
+                 const float* t_from, const float* normal_from, const int32_t* mat_from, const float* t_to, const float* normal_to, const int32_t* mat_to,
+                 const int32_t* params, int32_t* acc_to, int32_t* hist_to, long long* counts, int nthreads) {
+  if (!acc_from || !from_settings13 || !to_settings13 || !t_from || !normal_from || !mat_from || !t_to || !normal_to || !mat_to || !acc_to || !hist_to || !counts) { hk_err = "bad argument"; return -1; }
+  RenderParams Pf, Pt;
+  memset(&Pf, 0, sizeof(Pf)); memset(&Pt, 0, sizeof(Pt));
+  if (const char* why = fill_view_params(from_settings13, W, H, 0.0f, 0, 1, 0, Pf)) { hk_err = why; return -1; }
+  if (const char* why = fill_view_params(to_settings13, W, H, 0.0f, 0, 1, 0, Pt)) { hk_err = why; return -1; }
+  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { hk_err = "reproject: the two views have different divisors"; return -1; }
+  if (frames < 1) { hk_err = "reproject: frames must be >= 1"; return -1; }
+  RpParams R = {32, 0.9f, 0.01f, 0xFFFFFFC3u, 1};
+  if (params) {                      // dr_reproject_params: int, float, float, uint32, int
+    memcpy(&R.max_history, params, 4); memcpy(&R.normal_cos, params + 1, 4); memcpy(&R.plane_tolerance, params + 2, 4);
+    memcpy(&R.material_mask, params + 3, 4); memcpy(&R.sky, params + 4, 4);
+  }
+  R.sky = R.sky != 0;
+  if (const char* why = check_reproject_params(R)) { hk_err = why; return -1; }
+  RpCamera to, fr;
+  RpProj J;
+  fill_reproject_camera(Pt, to);
+  fill_reproject_camera(Pf, fr);
+  if (!fill_reproject_proj(fr, J)) { hk_err = "reproject: the `from` view is degenerate"; return -1; }
+  const int gw = Pt.gx * 8, gh = Pt.gy * 8;
+  memset(acc_to, 0, (size_t)W * H * 3 * sizeof(int32_t));
+  memset(hist_to, 0, (size_t)W * H * sizeof(int32_t));
+  RpGuides Gt, Gf;
+  Gt.t = t_to; Gt.normal = normal_to; Gt.mat = mat_to;
+  Gf.t = t_from; Gf.normal = normal_from; Gf.mat = mat_from;
+  if (nthreads < 1) nthreads = 1;
+  std::vector<long long> part((size_t)nthreads * 4, 0);
+  std::vector<std::thread> th;
+  for (int k = 0; k < nthreads; k++)
+    th.emplace_back([&, k] {
+      for (int y = k; y < gh; y += nthreads)
+        for (int x = 0; x < gw; x++) {
+          int qx = 0, qy = 0;
+          const int cls = rp_classify(R, to, fr, J, gw, gh, x, y, Gt, Gf, qx, qy);
+          part[(size_t)k * 4 + (size_t)cls]++;
+          if (cls != RP_VALID) continue;
+          const size_t q = (size_t)qx * (size_t)H + (size_t)qy, p = (size_t)x * (size_t)H + (size_t)y;
+          rp_carry(R, frames, acc_from + q * 3, hist_from ? hist_from[q] : 0, acc_to + p * 3, hist_to[p]);
+        }
+    });
+  for (std::thread& t : th) t.join();
+  counts[0] = (long long)gw * gh;
+  for (int c = 0; c < 4; c++) { counts[1 + c] = 0; for (int k = 0; k < nthreads; k++) counts[1 + c] += part[(size_t)k * 4 + (size_t)c]; }
   return 0;
 }
 

@@ -56,7 +56,9 @@ def lib():
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
         L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.hk_aov.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 9
-        L.hk_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int]
+        L.hk_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
+        L.hk_camera_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hk_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int]
         _lib = L
     return _lib
 
@@ -114,10 +116,11 @@ class Scene:
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "normal_power_log2": 7, "sigma_depth": 1.0, "demodulate": 1, "material_stop": 1}
 
 
-def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthreads=4, **params):
+def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthreads=4, hist=None, **params):
     """dr_accum_denoise on the host (device_denoise.hpp): the accumulator acc (int32[W, H, 3], column-major as dr_accum_read returns it) and the
     guides as arrays shaped like dogeray_amd.Context.render_aov's (normal / albedo [gh, gw, 3], depth / material [gh, gw]) -> (f32[H, W, 3],
-    uint8[H, W, 3]) in dr_accum_present's layout.  params: the fields of dr_denoise_params (the rest default)."""
+    uint8[H, W, 3]) in dr_accum_present's layout.  hist: the accumulator's history plane (int32[W, H], dr_accum_history_read) -- pixel p then
+    divides by hist[p] + divide_by.  params: the fields of dr_denoise_params (the rest default)."""
     acc = np.ascontiguousarray(acc, dtype=np.int32)
     W, H = acc.shape[0], acc.shape[1]
     st = np.ascontiguousarray(settings13, dtype=np.float32)
@@ -132,8 +135,61 @@ def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthread
     guides = [np.ascontiguousarray(a, dtype=t) for a, t in ((normal, np.float32), (albedo, np.float32), (depth, np.float32), (material, np.int32))]
     f32 = np.zeros((H, W, 3), np.float32)
     rgb = np.zeros((H, W, 3), np.uint8)
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.int32)
+        assert hist.shape == (W, H)
     rc = lib().hk_denoise(acc.ctypes.data, W, H, int(divide_by), st.ctypes.data, *[g.ctypes.data for g in guides], raw.ctypes.data,
-                          f32.ctypes.data, rgb.ctypes.data, nthreads)
+                          f32.ctypes.data, rgb.ctypes.data, nthreads, hist.ctypes.data if hist is not None else None)
     if rc != 0:
         raise RuntimeError(lib().hk_last_error().decode())
     return f32, rgb
+
+
+def camera_block(settings13, W, H):
+    """The float camera block of a view as the library forms it from settings13 (params_host.hpp fill_view_params): a dict with float32
+    "from", "llc", "hor", "ver", float64 "den_w", "den_h" and the pixel grid "gw", "gh"."""
+    st = np.ascontiguousarray(settings13, dtype=np.float32)
+    out, den, grid = np.zeros(12, np.float32), np.zeros(2, np.float64), np.zeros(2, np.int32)
+    if lib().hk_camera_block(st.ctypes.data, W, H, out.ctypes.data, den.ctypes.data, grid.ctypes.data) != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    return {"from": out[0:3].copy(), "llc": out[3:6].copy(), "hor": out[6:9].copy(), "ver": out[9:12].copy(), "den_w": float(den[0]), "den_h": float(den[1]),
+            "gw": int(grid[0]), "gh": int(grid[1])}
+
+
+REPROJECT_DEFAULTS = {"max_history": 32, "normal_cos": 0.9, "plane_tolerance": 0.01, "material_mask": 0xFFFFFFC3, "sky": 1}
+
+
+def reproject(acc, hist, frames, from_settings13, to_settings13, guides_from, guides_to, nthreads=4, **params):
+    """dr_accum_reproject on the host (device_reproject.hpp): the accumulator acc (int32[W, H, 3] as dr_accum_read returns it), its history
+    plane hist (int32[W, H] or None), the frames added since, both views' settings13 and guides (dicts with "t", "normal", "material" shaped
+    like dogeray_amd.Context.render_aov's) -> (acc int32[W, H, 3], hist int32[W, H], counts dict) of the `to` view.  params: the fields of
+    dr_reproject_params (the rest default)."""
+    acc = np.ascontiguousarray(acc, dtype=np.int32)
+    W, H = acc.shape[0], acc.shape[1]
+    a, b = np.ascontiguousarray(from_settings13, dtype=np.float32), np.ascontiguousarray(to_settings13, dtype=np.float32)
+    p = dict(REPROJECT_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError("unknown reproject parameter %r" % k)
+        p[k] = v
+    raw = np.zeros(5, dtype=np.int32)
+    raw[0] = p["max_history"]
+    raw[1:3] = np.array([p["normal_cos"], p["plane_tolerance"]], np.float32).view(np.int32)
+    raw[3] = np.array([p["material_mask"] & 0xFFFFFFFF], np.uint32).view(np.int32)[0]
+    raw[4] = p["sky"]
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.int32)
+        assert hist.shape == (W, H)
+    g = [np.ascontiguousarray(d[k], dtype=t) for d in (guides_from, guides_to) for k, t in (("t", np.float32), ("normal", np.float32), ("material", np.int32))]
+    for k, st in ((0, a), (3, b)):          # each view's guides are its own pixel grid (the call refuses two different grids)
+        div = int(st[11]) if np.isfinite(st[11]) and st[11] >= 1 else 1
+        gw, gh = W // div // 8 * 8, H // div // 8 * 8
+        assert g[k].shape == (gh, gw) and g[k + 1].shape == (gh, gw, 3) and g[k + 2].shape == (gh, gw), "guides are not the %d x %d pixel grid" % (gw, gh)
+    out_acc = np.zeros((W, H, 3), np.int32)
+    out_hist = np.zeros((W, H), np.int32)
+    counts = (C.c_longlong * 5)()
+    rc = lib().hk_reproject(acc.ctypes.data, hist.ctypes.data if hist is not None else None, W, H, int(frames), a.ctypes.data, b.ctypes.data,
+                            *[x.ctypes.data for x in g], raw.ctypes.data, out_acc.ctypes.data, out_hist.ctypes.data, C.cast(counts, C.c_void_p), nthreads)
+    if rc != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    return out_acc, out_hist, dict(zip(("pixels", "valid", "masked", "offscreen", "rejected"), [int(v) for v in counts]))
