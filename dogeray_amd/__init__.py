@@ -94,6 +94,16 @@ class DrReprojectResult(C.Structure):
     _fields_ = [("pixels", C.c_int64), ("valid", C.c_int64), ("masked", C.c_int64), ("offscreen", C.c_int64), ("rejected", C.c_int64)]
 
 
+class DrErrorResult(C.Structure):
+    """struct dr_error_result (include/dogeray_amd.h dr_accum_error): counts over the pixel grid and the fixed-point sum of the variances."""
+    _fields_ = [("pixels", C.c_int64), ("estimated", C.c_int64), ("above", C.c_int64), ("sum_var_q16", C.c_uint64), ("bins", C.c_int64 * 16)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "bins"}
+        d["bins"] = [int(v) for v in self.bins]
+        return d
+
+
 # every symbol include/dogeray_amd.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _API = [
@@ -132,6 +142,9 @@ _API = [
     ("dr_accum_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     ("dr_accum_history_read", C.c_int, [_VP, _VP]),
     ("dr_accum_history_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("dr_accum_moments_read", C.c_int, [_VP, _VP]),
+    ("dr_accum_moments_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    ("dr_accum_error", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.POINTER(DrErrorResult), C.c_int]),
     ("dr_reproject_defaults", C.c_int, [C.POINTER(DrReprojectParams)]),
     ("dr_accum_reproject", C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrReprojectParams), C.POINTER(DrReprojectResult)]),
     ("dr_render_accumulate_async", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int]),
@@ -165,6 +178,7 @@ _API = [
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
+    ("dr_context_probe_frame_add", C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("dr_kat_rng", C.c_int, [_VP, C.c_uint64, C.c_int, _VP]),
     ("dr_kat_aabb", C.c_int, [_VP, C.c_int] + [_VP] * 6),
     ("dr_kat_tri", C.c_int, [_VP, C.c_int] + [_VP] * 6),
@@ -575,6 +589,13 @@ class Context:
         _check(lib().dr_context_probe_gather(self._h, int(hot_records), int(iters), C.byref(v)))
         return v.value
 
+    def probe_frame_add(self, iters=10):
+        """(plain add ms[iters], fused add ms[iters]) of the kernels that fold a frame into the accumulator, each launch timed alone
+        (dr_context_probe_frame_add; the fused times are zeros without a second-moment plane)."""
+        a, b = (C.c_double * iters)(), (C.c_double * iters)()
+        _check(lib().dr_context_probe_frame_add(self._h, int(iters), a, b))
+        return [float(v) for v in a], [float(v) for v in b]
+
     # ---- first-hit AOVs (dr_render_aov)
     def render_aov(self, settings13, W, H, window=None, channels=ALL, device=False):
         """First-hit buffers of the pinhole rays through the pixel centres (include/dogeray_amd.h dr_render_aov): a dict channel -> array
@@ -682,6 +703,65 @@ class Context:
         out = np.empty((W, H), dtype=np.int32)
         _check(lib().dr_accum_history_read(self._h, _p(out)))
         return out
+
+    # ---- second moments (option "moments", dr_accum_error)
+    def accum_moments(self):
+        """uint64[W, H] indexed [x, y]: the second-moment plane, the sum over the frames folded into the accumulator of their capped luma x 256,
+        squared (all zeros when there is no plane: set_option("moments", 1) before accum_reset)."""
+        W, H, _ = self._acc_shape
+        out = np.empty((W, H), dtype=np.uint64)
+        _check(lib().dr_accum_moments_read(self._h, _p(out)))
+        return out
+
+    def error(self, settings13, W, H, divide_by, tolerance, sigma=False, device=False):
+        """The noise estimate of the accumulator (include/dogeray_amd.h dr_accum_error): a dict with the fields of dr_error_result -- pixels,
+        estimated, above (estimated pixels whose sigma exceeds tolerance), sum_var_q16, bins[16] -- and, with sigma=True, "sigma": float32[H, W],
+        the standard error of each pixel's displayed mean luma in 0..255 units (accum_present's layout; device=True: a torch tensor on this
+        context's GPU, with render_aov's stream handshake)."""
+        st = _f32(settings13)
+        assert st.shape == (13,)
+        r = DrErrorResult()
+        plane = None
+        if not sigma:
+            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), None, C.byref(r), 0))
+        elif not device:
+            plane = np.empty((max(H, 0), max(W, 0)), np.float32)
+            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), _p(plane), C.byref(r), 0))
+        else:
+            import torch
+            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+            plane = torch.empty((max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+            cur = torch.cuda.current_stream(dev)
+            lib_stream.wait_stream(cur)
+            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), plane.data_ptr(), C.byref(r), 1))
+            cur.wait_stream(lib_stream)
+        d = r.as_dict()
+        if sigma:
+            d["sigma"] = plane
+        return d
+
+    @staticmethod
+    def converged(result, permille):
+        """The stopping rule of render_until: the pixels above the tolerance and the pixels without an estimate are at most permille / 1000 of the grid."""
+        return (result["above"] + (result["pixels"] - result["estimated"])) * 1000 <= permille * result["pixels"]
+
+    def render_until(self, settings13, W, H, background, seed, stride, tolerance, permille, max_frames, check_every=8, frames_before=0):
+        """Adds frames (seeds seed + k * stride) through the pipeline in chunks of check_every until the noise estimate says stop -- above +
+        (pixels - estimated) <= permille * pixels / 1000 at `tolerance` -- or max_frames have been added.  Needs a second-moment plane.
+        frames_before: frames already in the accumulator since the last accum_reset / reproject (they count in divide_by, not in max_frames).
+        Returns (frames added, the last error() dict)."""
+        assert check_every >= 1 and max_frames >= 1
+        st = _f32(settings13)
+        frames, result = 0, None
+        while frames < max_frames:
+            n = min(check_every, max_frames - frames)
+            self.render_accumulate_pipelined(st, W, H, background, int(seed) + frames * int(stride), stride, n)
+            frames += n
+            result = self.error(st, W, H, frames_before + frames, tolerance)
+            if self.converged(result, permille):
+                break
+        return frames, result
 
     # ---- known-answer hooks (tests)
     def kat_rng(self, seed, n):
@@ -912,3 +992,17 @@ class ProgressiveRenderer:
             img = c.pipeline_wait(t, want_image=True)
             if on_image:
                 on_image(it, dv, img)
+
+    def run_until(self, tolerance, permille, max_frames, check_every=8):
+        """The accumulating part of the loop (iter >= 4) until the noise estimate says stop (Context.render_until: the context needs
+        set_option("moments", 1) before the renderer is made): at most max_frames more frames, in chunks of check_every.  Returns (frames added,
+        the last Context.error dict); step() / image() go on from there."""
+        assert self.iter >= 4, "run the preview ladder (four step() calls) first"
+        s, c = self.s, self.ctx
+        c._acc_shape = (self.W, self.H, 3)
+        before = self.iter - self._pnum
+        frames, result = c.render_until(pack_settings13(s, 1), self.W, self.H, s.background, self._seed(), self.seed_stride, tolerance, permille,
+                                        max_frames, check_every=check_every, frames_before=before)
+        self.frames_rendered += frames
+        self.iter += frames
+        return frames, result

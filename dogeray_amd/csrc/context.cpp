@@ -55,6 +55,15 @@ struct dr_context {
   bool rp_valid = false; int rp_cur = 0; float rp_key[13] = {0}; int rp_W = 0, rp_H = 0; uint64_t rp_gen = 0;
   unsigned long long* rp_counts = nullptr;
   int rp_passes = 0;
+  // the second-moment plane (option "moments", read by dr_accum_reset): m2 is the current plane (null: none), one of m2_buf -- the second one
+  // appears with the first reprojection, as for the history; the allocations outlive resets of the same size.  dr_accum_error's counts and the
+  // staging of its host output
+  int moments_opt = 0;                     // option: dr_accum_reset gives the accumulator a plane
+  int denoise_variance = 0;                // option: the denoiser's variance pre-pass takes the temporal variance from the plane (n >= 4)
+  unsigned long long* m2_buf[2] = {nullptr, nullptr}; size_t m2_elems[2] = {0, 0};
+  unsigned long long* m2 = nullptr; int m2_cur = 0;
+  unsigned long long* err_counts = nullptr;
+  float* err_staging = nullptr; size_t err_staging_bytes = 0;
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
   // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
   // computed on `stream` by launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload and cert_factor
@@ -164,10 +173,11 @@ int upload(T*& dst, const std::vector<T>& src) {
   return DR_OK;
 }
 
-int ensure(int32_t*& buf, size_t& have, size_t need) {
+template <class T>
+int ensure(T*& buf, size_t& have, size_t need) {
   if (have >= need && buf) return DR_OK;
   if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }
-  HIP_TRY(hipMalloc((void**)&buf, need * sizeof(int32_t)));
+  HIP_TRY(hipMalloc((void**)&buf, need * sizeof(T)));
   have = need;
   return DR_OK;
 }
@@ -357,6 +367,8 @@ int set_option(dr_context* c, const std::string& name, int v) {
   else if (name == "feedback_every") { if (v < 1) goto bad; c->feedback_every = v; }
   else if (name == "wide_tree") { if (v < 0 || v > 2) goto bad; c->wide_tree = v; }      // takes effect at the next dr_context_upload_scene
   else if (name == "denoise_tiles") { if (v != 0 && v != 1) goto bad; c->denoise_tiles = v; }
+  else if (name == "moments") { if (v != 0 && v != 1) goto bad; c->moments_opt = v; }      // takes effect at the next dr_accum_reset
+  else if (name == "denoise_variance") { if (v != 0 && v != 1) goto bad; c->denoise_variance = v; }
   else if (name == "camera_cert" || name == "cert_factor") {
     if (name == "camera_cert" ? (v != 0 && v != 1) : (v < 1 || v > 10000)) goto bad;
     // frames submitted before the change are launched with the setting they were submitted under
@@ -502,7 +514,8 @@ void dr_context_destroy(dr_context* c) {
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
   void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
                   c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->cert_mask,
-                  c->accum2, c->hist_buf[0], c->hist_buf[1], c->rp_planes[0], c->rp_planes[1], c->rp_counts};
+                  c->accum2, c->hist_buf[0], c->hist_buf[1], c->rp_planes[0], c->rp_planes[1], c->rp_counts,
+                  c->m2_buf[0], c->m2_buf[1], c->err_counts, c->err_staging};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -607,6 +620,8 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
   else if (n == "wide_depth") *value = c->wide ? c->wide_depth : 0;          // 0: the scene has no wide structure
   else if (n == "wide_nodes") *value = c->wide ? c->wide_nodes : 0;
   else if (n == "denoise_tiles") *value = c->denoise_tiles;
+  else if (n == "moments") *value = c->moments_opt;
+  else if (n == "denoise_variance") *value = c->denoise_variance;
   else if (n == "camera_cert") *value = c->camera_cert;
   else if (n == "cert_factor") *value = c->cert_factor;
   else if (n == "cert_flagged_permille") {
@@ -670,7 +685,17 @@ int dr_accum_reset(dr_context* c, int W, int H) {
   c->accW = W; c->accH = H;
   c->hist = nullptr;               // the history plane goes with the sums it counted
   HIP_TRY(hipMemsetAsync(c->accum, 0, elems * sizeof(int32_t), c->stream));
+  if (c->moments_opt) {            // a zeroed second-moment plane (the allocation is kept across resets of the same size: the preview ladder resets four times)
+    c->m2 = nullptr;
+    if ((rc = ensure(c->m2_buf[0], c->m2_elems[0], (size_t)W * H)) != DR_OK) return rc;
+    c->m2 = c->m2_buf[0]; c->m2_cur = 0;
+    HIP_TRY(hipMemsetAsync(c->m2, 0, (size_t)W * H * sizeof(unsigned long long), c->stream));
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!c->moments_opt && (c->m2_buf[0] || c->m2_buf[1])) {      // the plane is dropped (nothing uses it any more: the stream has drained)
+    c->m2 = nullptr;
+    for (int k = 0; k < 2; k++) { if (c->m2_buf[k]) (void)hipFree(c->m2_buf[k]); c->m2_buf[k] = nullptr; c->m2_elems[k] = 0; }
+  }
   return DR_OK;
 }
 
@@ -788,6 +813,7 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   L.D.iterations = p.iterations; L.D.sigma_luminance = p.sigma_luminance; L.D.normal_power_log2 = p.normal_power_log2;
   L.D.sigma_depth = p.sigma_depth; L.D.demodulate = p.demodulate != 0; L.D.material_stop = p.material_stop != 0;
   L.acc = c->accum; L.hist = c->hist;
+  L.m2 = c->denoise_variance ? c->m2 : nullptr;
   if (p.iterations > 0 && n > 0) {
     // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
     const size_t need = 17 * n;
@@ -899,6 +925,8 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   if ((rc = ensure(c->accum2, c->accum2_elems, npix * 3)) != DR_OK) return rc;
   const int hto = c->hist ? 1 - c->hist_cur : 0;
   if ((rc = ensure(c->hist_buf[hto], c->hist_elems[hto], npix)) != DR_OK) return rc;
+  const int mto = 1 - c->m2_cur;                               // (a second-moment plane is carried into the other buffer of its pair)
+  if (c->m2 && (rc = ensure(c->m2_buf[mto], c->m2_elems[mto], npix)) != DR_OK) return rc;
   if (!c->rp_counts) HIP_TRY(hipMalloc((void**)&c->rp_counts, 4 * sizeof(unsigned long long)));
   // the guides: the cached planes serve as `from` when their key matches; the `to` view is traced into the other set (into none when it is
   // the `from` view itself) and becomes the cache
@@ -933,11 +961,13 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   }
   L.acc_from = c->accum; L.hist_from = c->hist;
   L.acc_to = c->accum2; L.hist_to = c->hist_buf[hto];
+  L.m2_from = c->m2; L.m2_to = c->m2 ? c->m2_buf[mto] : nullptr;
   L.counts = c->rp_counts;
   HIP_TRY(hipMemsetAsync(c->rp_counts, 0, 4 * sizeof(unsigned long long), c->stream));
   if (gw < W || gh < H) {                                     // pixels outside the grid are 0
     HIP_TRY(hipMemsetAsync(c->accum2, 0, npix * 3 * sizeof(int32_t), c->stream));
     HIP_TRY(hipMemsetAsync(c->hist_buf[hto], 0, npix * sizeof(int32_t), c->stream));
+    if (L.m2_to) HIP_TRY(hipMemsetAsync(L.m2_to, 0, npix * sizeof(unsigned long long), c->stream));
   }
   launch_reproject(c->stream, L);
   HIP_TRY(hipGetLastError());
@@ -947,6 +977,7 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   // the pair of the `to` view is the current one from here on
   std::swap(c->accum, c->accum2); std::swap(c->accum_elems, c->accum2_elems);
   c->hist = c->hist_buf[hto]; c->hist_cur = hto;
+  if (c->m2) { c->m2 = c->m2_buf[mto]; c->m2_cur = mto; }
   memcpy(c->rp_key, to_settings13, sizeof(c->rp_key));
   c->rp_W = W; c->rp_H = H; c->rp_gen = c->scene_gen; c->rp_cur = st; c->rp_valid = n > 0;
   if (result) {
@@ -1016,6 +1047,8 @@ int dr_render_accumulate(dr_context* c, const float settings13[13], int W, int H
                          uint64_t seed_stride, int nframes) {
   if (!c) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (nframes == 0) return DR_OK;
+  // a second-moment plane needs every frame in a buffer of its own: the same sums through the pipeline, whose add squares the frame as well
+  if (c->m2) return dr_render_accumulate_pipelined(c, settings13, W, H, background, frame_seed, seed_stride, nframes);
   uint64_t samples = 0;
   int rc = accumulate_enqueue(c, settings13, W, H, background, frame_seed, seed_stride, nframes, c->ev0, c->ev1, samples);
   if (rc != DR_OK) return rc;
@@ -1028,6 +1061,7 @@ int dr_render_accumulate_async(dr_context* c, const float settings13[13], int W,
                                uint64_t seed_stride, int nframes) {
   if (!c) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (nframes == 0) return DR_OK;
+  if (c->m2) { set_error("dr_render_accumulate_async cannot feed a second-moment plane (option moments): use dr_render_accumulate or the pipeline"); return DR_ERR_INVALID; }
   const int k = c->pending_next;
   int rc = collect_pending(c, k);           // at most two batches in flight: reusing a pair of events waits for the batch before last
   if (rc != DR_OK) return rc;
@@ -1155,7 +1189,8 @@ int pipeline_flush_some(dr_context* c, int n) {
   // fold into the accumulator, in ticket order (K:2213-2218), and make the image of exactly the frames so far (K:2287)
   HIP_TRY(hipStreamWaitEvent(c->acc_stream, sl.rendered, 0));
   for (int f = 0; f < n; f++) {
-    launch_frame_add(c->acc_stream, c->accum, sl.frames + (size_t)f * elems, elems);
+    if (c->m2) launch_moments_add(c->acc_stream, c->accum, sl.frames + (size_t)f * elems, c->m2, (size_t)W * H);      // acc += frame; M2 += yc^2
+    else launch_frame_add(c->acc_stream, c->accum, sl.frames + (size_t)f * elems, elems);
     const int div = c->pipe_pending[(size_t)f].div;
     sl.div[f] = 0; sl.fwaited[f] = false;
     if (div != 0) {
@@ -1349,6 +1384,78 @@ int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) 
   return DR_OK;
 }
 
+int dr_accum_moments_read(dr_context* c, uint64_t* out) {
+  if (!c || !out || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }
+  const size_t n = (size_t)c->accW * c->accH;
+  if (!c->m2) { memset(out, 0, n * sizeof(uint64_t)); return DR_OK; }
+  HIP_TRY(hipMemcpyAsync(out, c->m2, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+int dr_accum_moments_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
+  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  *dev_ptr = c->m2;
+  if (bytes) *bytes = c->m2 ? (uint64_t)c->accW * c->accH * sizeof(uint64_t) : 0;
+  return DR_OK;
+}
+
+int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int divide_by, float tolerance, float* out_sigma, dr_error_result* result,
+                   int device_pointers) {
+  if (!c || !settings13) { set_error("null argument"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  RenderParams P;
+  int traversal = 0;
+  { const int rc = aov_view(c, settings13, W, H, P, traversal); if (rc != DR_OK) return rc; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  if (W != c->accW || H != c->accH) {
+    set_error("error: " + std::to_string(W) + " x " + std::to_string(H) + " is not the accumulator's " + std::to_string(c->accW) + " x " + std::to_string(c->accH));
+    return DR_ERR_INVALID;
+  }
+  if (!c->m2) { set_error("error: no moments plane (set option moments = 1 before dr_accum_reset)"); return DR_ERR_INVALID; }
+  if (divide_by < 0) { set_error("error: divide_by must be >= 0"); return DR_ERR_INVALID; }
+  if (!(tolerance >= 0.0f)) { set_error("error: tolerance must be >= 0"); return DR_ERR_INVALID; }
+  if (!out_sigma && !result) { set_error("error: no output (both out_sigma and result are NULL)"); return DR_ERR_INVALID; }
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
+
+  const size_t npix = (size_t)W * (size_t)H;
+  MoLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by; L.tolerance = tolerance;
+  L.acc = c->accum; L.hist = c->hist; L.m2 = c->m2;
+  float* sigma_dev = out_sigma;
+  if (out_sigma && !device_pointers) {
+    if (npix * sizeof(float) > c->err_staging_bytes) {
+      if (c->err_staging) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->err_staging); c->err_staging = nullptr; c->err_staging_bytes = 0; }
+      HIP_TRY(hipMalloc((void**)&c->err_staging, npix * sizeof(float)));
+      c->err_staging_bytes = npix * sizeof(float);
+    }
+    sigma_dev = c->err_staging;
+  }
+  L.out_sigma = sigma_dev;
+  if (sigma_dev && (L.gw < W || L.gh < H)) HIP_TRY(hipMemsetAsync(sigma_dev, 0, npix * sizeof(float), c->stream));      // pixels outside the grid are 0
+  if (result) {
+    if (!c->err_counts) HIP_TRY(hipMalloc((void**)&c->err_counts, MO_WORDS * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(c->err_counts, 0, MO_WORDS * sizeof(unsigned long long), c->stream));
+    L.counts = c->err_counts;
+  }
+  launch_moments_error(c->stream, L);
+  HIP_TRY(hipGetLastError());
+  unsigned long long counts[MO_WORDS] = {0};
+  if (result) HIP_TRY(hipMemcpyAsync(counts, c->err_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+  if (out_sigma && !device_pointers) HIP_TRY(hipMemcpyAsync(out_sigma, sigma_dev, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (result || !device_pointers) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (result) {
+    result->pixels = (int64_t)L.gw * (int64_t)L.gh;
+    result->estimated = (int64_t)counts[MO_ESTIMATED]; result->above = (int64_t)counts[MO_ABOVE]; result->sum_var_q16 = counts[MO_SUM_VAR];
+    for (int k = 0; k < MO_BINS; k++) result->bins[k] = (int64_t)counts[MO_BIN0 + k];
+  }
+  return DR_OK;
+}
+
 int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8) {
   if (!c || !out_rgb8 || !c->accum || divide_by == 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
@@ -1442,6 +1549,32 @@ int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n
   const size_t m = have < capacity ? have : capacity;
   if (m > 0) HIP_TRY(hipMemcpy(out, c->pixel_cost, m * sizeof(unsigned), hipMemcpyDeviceToHost));
   *n = m;
+  return DR_OK;
+}
+
+int dr_context_probe_frame_add(dr_context* c, int iters, double* plain_ms, double* fused_ms) {
+  if (!c || iters < 1 || !plain_ms || !fused_ms) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }
+  const size_t npix = (size_t)c->accW * c->accH, elems = npix * 3;
+  int rc = ensure(c->frame, c->frame_elems, elems);
+  if (rc != DR_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->frame, 0, elems * sizeof(int32_t), c->stream));      // a black frame: neither the sums nor the plane change
+  for (int k = 0; k < 2 * iters; k++) {
+    const bool fused = k >= iters;
+    float ms = 0;
+    if (!fused || c->m2) {
+      HIP_TRY(hipEventRecord(c->ev0, c->stream));
+      if (fused) launch_moments_add(c->stream, c->accum, c->frame, c->m2, npix);
+      else launch_frame_add(c->stream, c->accum, c->frame, elems);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->ev1, c->stream));
+      HIP_TRY(hipEventSynchronize(c->ev1));
+      HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    }
+    (fused ? fused_ms : plain_ms)[k % iters] = (double)ms;
+  }
   return DR_OK;
 }
 

@@ -218,4 +218,10 @@ struct RpProj {
   double hh, vv;       // hor . hor, ver . ver
 };
 
+// The second-moment plane (option "moments"; device_moments.hpp) and the words dr_accum_error counts into
+constexpr long long MO_CAP = 1ll << 26;          // firefly cap of a frame's luma x 256: 1028 x a white pixel's 65280; MO_CAP^2 = 2^52
+constexpr int MO_BINS = 16;
+constexpr int MO_WORDS = 3 + MO_BINS;            // estimated, above, sum_var_q16, bins[16]
+constexpr int MO_ESTIMATED = 0, MO_ABOVE = 1, MO_SUM_VAR = 2, MO_BIN0 = 3;
+
 }  // namespace dr

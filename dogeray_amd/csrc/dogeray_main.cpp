@@ -117,6 +117,7 @@ void usage() {
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
           "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm] [--move-to CX,CY,CZ,LX,LY,LZ] [--move-frames N]\n"
+          "               [--until-sigma T[,PERMILLE]] [--max-frames N] [--sigma-out FILE.pfm]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -133,7 +134,11 @@ void usage() {
           "               parameters): .bmp / .ppm as RGB8, .pfm as floats in 0..255 units (--gpus N: on rank 0's context after the final gather)\n"
           "  --move-to    after the --frames frames in the file's view, move the camera to CX,CY,CZ looking at LX,LY,LZ: the accumulated image is\n"
           "               reprojected into the new view (dr_accum_reproject, default parameters; one line reports the pixel counts), --move-frames\n"
-          "               more frames (default 1) are added there, and --out / --aov / --denoise show the new view (one context only: not with --gpus)\n");
+          "               more frames (default 1) are added there, and --out / --aov / --denoise show the new view (one context only: not with --gpus)\n"
+          "  --until-sigma  instead of --frames: add full-resolution frames, eight at a time, until at most PERMILLE per mille (default 10) of the pixels\n"
+          "               have a standard error of the displayed mean luma above T (0..255 units; dr_accum_error, option moments) or --max-frames N\n"
+          "               (default 1024) have been added; one line reports which (one context only: not with --gpus)\n"
+          "  --sigma-out  after the render, write that standard error per pixel as a one-channel .pfm (needs no --until-sigma)\n");
 }
 
 }  // namespace
@@ -143,6 +148,10 @@ int main(int argc, char** argv) {
   bool move = false;
   float move_to[6] = {0, 0, 0, 0, 0, 0};
   int move_frames = 1;
+  std::string sigma_path;
+  bool until = false;
+  float until_sigma = 0;
+  int until_permille = 10, max_frames = 1024;
   const char* texdir = nullptr;
   int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0;
   uint64_t seed = 1;
@@ -172,12 +181,24 @@ int main(int argc, char** argv) {
       move = true;
     }
     else if (a == "--move-frames") move_frames = atoi(next());
+    else if (a == "--until-sigma") {
+      const int got = sscanf(next(), "%f,%d", &until_sigma, &until_permille);
+      if (got < 1 || !(until_sigma >= 0.0f) || until_permille < 0) { usage(); return 2; }
+      until = true;
+    }
+    else if (a == "--max-frames") max_frames = atoi(next());
+    else if (a == "--sigma-out") sigma_path = next();
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
   }
   if (group < 1) group = 1;
   if (move && (gpus >= 1 || move_frames < 1)) { fprintf(stderr, "dogeray: --move-to needs a single context (no --gpus) and --move-frames >= 1\n"); return 2; }
+
+  const bool moments = until || !sigma_path.empty();
+  if (moments && gpus >= 1) { fprintf(stderr, "dogeray: --until-sigma / --sigma-out need a single context (no --gpus)\n"); return 2; }
+  if (until && max_frames < 1) { fprintf(stderr, "dogeray: --max-frames must be >= 1\n"); return 2; }
+  if (until) frames = 0;                 // the frames after the preview ladder are counted by the noise estimate
 
   if (!quiet) printf("DOGERAY render path on MI355X (dogeray_amd, C ABI v%d)\n", dr_abi_version());
   printf("%s%s\n", have_scene ? "Opening:" : "Opening Default Scene: ", scene_path.c_str());   // K:2045-2050
@@ -220,6 +241,7 @@ int main(int argc, char** argv) {
   } else {
     if (dr_context_create(device, &ctx) != DR_OK) die("cannot create the device context");
     if (dr_context_upload_scene(ctx, scene) != DR_OK) die("cannot upload the scene");
+    if (moments && dr_context_set_option(ctx, "moments", 1) != DR_OK) die("cannot enable the second-moment plane");
     if (dr_accum_reset(ctx, W, H) != DR_OK) die("cannot allocate the accumulator");
   }
   if (autofocus) {                       // K:2471-2483 sets the focus by hand; here: what the centre pixel of the full-resolution grid sees
@@ -314,6 +336,28 @@ int main(int argc, char** argv) {
   }
   if (!quiet) printf("\n");
 
+  if (until) {                           // frames in chunks of eight until the noise estimate says stop (the stopping rule of Context.render_until)
+    float st[13];
+    pack13(s, 1, s.spp, s.max_depth, st);
+    const int before = divide_by;        // the preview ladder's full-resolution frame is in the accumulator and counts as a sample (K:2287)
+    int added = 0;
+    dr_error_result er;
+    memset(&er, 0, sizeof(er));
+    bool converged = false;
+    while (added < max_frames && !converged) {
+      const int n = max_frames - added < 8 ? max_frames - added : 8;
+      if (dr_render_accumulate_pipelined(ctx, st, W, H, s.background, seed + frame_no * seed_stride, seed_stride, n) != DR_OK) die("render");
+      frame_no += (uint64_t)n; added += n;
+      if (dr_accum_error(ctx, st, W, H, before + added, until_sigma, nullptr, &er, 0) != DR_OK) die("error estimate");
+      converged = (er.above + (er.pixels - er.estimated)) * 1000 <= (int64_t)until_permille * er.pixels;
+    }
+    memcpy(last_st, st, sizeof(last_st));
+    divide_by = before + added;
+    if (dr_accum_present(ctx, divide_by, rgb.data()) != DR_OK) die("present");
+    printf("%s after %d frames: %lld of %lld pixels above %g\n", converged ? "converged" : "not converged", added, (long long)er.above, (long long)er.pixels,
+           (double)until_sigma);
+  }
+
   if (move) {                            // a camera move: carry the image into the new view, then add frames there
     float to_st[13];
     for (int k = 0; k < 3; k++) { s.campos[k] = move_to[k]; s.look[k] = move_to[3 + k]; }
@@ -348,6 +392,16 @@ int main(int argc, char** argv) {
     pack13(s, 1, s.spp, s.max_depth, st);
     if (!write_denoised(ctx, st, W, H, divide_by, denoise_path)) { fprintf(stderr, "dogeray: cannot write the denoised image %s: %s\n", denoise_path.c_str(), dr_last_error()); return 1; }
     printf("exported denoised image:%s\n", denoise_path.c_str());
+  }
+  if (!sigma_path.empty()) {
+    float st[13];
+    pack13(s, 1, s.spp, s.max_depth, st);
+    std::vector<float> sigma((size_t)W * H);
+    if (dr_accum_error(ctx, st, W, H, divide_by, 0.0f, sigma.data(), nullptr, 0) != DR_OK || !write_pfm(sigma_path, sigma, W, H, 1)) {
+      fprintf(stderr, "dogeray: cannot write the noise estimate %s: %s\n", sigma_path.c_str(), dr_last_error());
+      return 1;
+    }
+    printf("exported noise estimate:%s\n", sigma_path.c_str());
   }
   if (grp) dr_group_destroy(grp); else dr_context_destroy(ctx);
   dr_scene_free(scene);

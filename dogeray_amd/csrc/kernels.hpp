@@ -4,6 +4,7 @@
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
+//   kernels_moments.hip       the second-moment plane: the fused frame add and the per-pixel noise estimate (option "moments", dr_accum_error)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
 #pragma once
@@ -87,6 +88,8 @@ struct DnLaunch {
   const float* depth;
   const float* albedo;            // launch_aov's albedo (3 per pixel)
   const int32_t* mat;             // launch_aov's material (-1: miss)
+  const unsigned long long* m2;   // the second-moment plane (pixel (x, y) at x * H + y) when stage 1 takes the temporal variance from it (option
+                                  // "denoise_variance"), or null: the spatial estimate everywhere
   float* guide;                   // float4 (n.x, n.y, n.z, z)
   float* gz;                      // depth gradient
   const float* src;               // colour planes, float4 per pixel: (e, l) or (e, var)
@@ -114,8 +117,28 @@ struct RpLaunch {
   const int32_t* hist_from;       // null: no history yet (0 everywhere)
   int32_t* acc_to;
   int32_t* hist_to;
+  const unsigned long long* m2_from;   // the second-moment planes (W x H at x * H + y), or both null: no plane is carried
+  unsigned long long* m2_to;
   unsigned long long* counts;     // [4]: pixels of class RP_VALID, RP_MASKED, RP_OFFSCREEN, RP_REJECTED are added
 };
 void launch_reproject(hipStream_t stream, const RpLaunch& L);
+
+// kernels_moments.hip
+// acc += frame and m2 += the frame's capped luma squared, in one pass (npix pixels; acc / frame column-major x 3, m2 one word per pixel)
+void launch_moments_add(hipStream_t stream, int32_t* acc, const int32_t* frame, unsigned long long* m2, size_t npix);
+// the noise estimate over the gw x gh pixel grid: sigma row-major W x H (null: not written; pixels outside the grid are not written) and the
+// counts (MO_WORDS words, device_moments.hpp: estimated, above, sum_var_q16, bins; added to; null: not counted)
+struct MoLaunch {
+  int gw, gh;
+  int W, H;
+  int divide_by;
+  float tolerance;
+  const int32_t* acc;
+  const int32_t* hist;            // null: no history plane (0 everywhere)
+  const unsigned long long* m2;
+  float* out_sigma;
+  unsigned long long* counts;
+};
+void launch_moments_error(hipStream_t stream, const MoLaunch& L);
 
 }  // namespace dr

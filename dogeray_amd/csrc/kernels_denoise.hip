@@ -2,7 +2,8 @@
 // device_denoise.hpp.
 //   guide prepare   (n, z) packed into a float4 plane, the material plane completed, the depth gradient gz
 //   colour prepare  stage 0: the column-major accumulator -> c = acc / divide_by -> e = c / a' -> (e, l) plane
-//                   stage 1: (e, l) -> the variance pre-pass -> (e, var) plane
+//                   stage 1: (e, l) -> the variance pre-pass -> (e, var) plane (option "denoise_variance": the temporal variance of the second-moment
+//                            plane for pixels with four samples or more)
 //   a-trous pass    (e, var) -> (e', var') at step 2^i, ping-pong between two planes; two shapes (option denoise_tiles):
 //                   1: one workgroup per 16x16 LATTICE tile -- at step s it filters the pixels (x0 + s i, y0 + s j), whose taps lie on the same
 //                      lattice, so one 20x20-point LDS tile of colour, guides and materials serves every step (the apron does not grow with s)
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_denoise.hpp"
+#include "device_moments.hpp"
 #include "kernels.hpp"
 
 namespace dr {
@@ -66,7 +68,16 @@ __global__ __launch_bounds__(256) void dn_variance_kernel(DnLaunch L) {
   if (x >= L.gw || y >= L.gh) return;
   const size_t i = (size_t)y * L.gw + x;
   const float4 gp = reinterpret_cast<const float4*>(L.guide)[i];
-  const float var = dn_variance(L.D, gp, (int)L.mat[i], L.gz[i], [&](int dx, int dy) { return dn_tap_global(L, x + dx, y + dy); });
+  const int m = L.mat[i];
+  float var = 0.0f;
+  bool temporal = false;
+  if (L.m2) {                                // option "denoise_variance": SVGF's rule, the temporal second moment once the pixel has four samples
+    const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
+    const int32_t* a = L.acc + px * 3;
+    temporal = mo_denoise_variance(a[0], a[1], a[2], L.m2[px], (long long)dn_divisor(L.hist, px, L.divide_by), dn_albedo(L.albedo[3 * i], m, L.D.demodulate),
+                                   dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate), dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate), var);
+  }
+  if (!temporal) var = dn_variance(L.D, gp, m, L.gz[i], [&](int dx, int dy) { return dn_tap_global(L, x + dx, y + dy); });
   const float4 c = reinterpret_cast<const float4*>(L.src)[i];
   reinterpret_cast<float4*>(L.dst)[i] = make_float4(c.x, c.y, c.z, var);
 }

@@ -198,6 +198,11 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
+ *   "moments"       read by dr_accum_reset: 1 gives the accumulator a second-moment plane (one uint64 per pixel, see dr_accum_error below), 0
+ *                   (default) drops it; a context that never sets it allocates nothing and runs the code it ran before.  No pixel of the
+ *                   accumulator changes; dr_render_accumulate then runs through the pipeline
+ *   "denoise_variance" 1: while the accumulator has a second-moment plane, dr_accum_denoise's variance pre-pass takes the temporal variance of pixels
+ *                   with four samples or more from it (SVGF's rule; see dr_accum_error below); 0 (default): the spatial estimate everywhere, the bits as before
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -217,7 +222,9 @@ int dr_render_frame(dr_context* c, const float settings13[13], int W, int H, flo
 /* Progressive accumulation kept on the device (the reference accumulates on the CPU,
  * K:2213-2218).  dr_accum_reset zeroes the W*H*3 int32 accumulator; dr_render_accumulate
  * renders `nframes` frames with seeds frame_seed + k*seed_stride and adds each into it
- * (no host synchronisation between frames; returns after the last one has finished). */
+ * (no host synchronisation between frames; returns after the last one has finished).  While the accumulator has a second-moment
+ * plane (option "moments") dr_render_accumulate runs as dr_render_accumulate_pipelined -- the same sums, every kernel and traversal option;
+ * dr_stats are what that call leaves -- and dr_render_accumulate_async returns DR_ERR_INVALID. */
 int dr_accum_reset(dr_context* c, int W, int H);
 int dr_render_accumulate(dr_context* c, const float settings13[13], int W, int H, float background,
                          uint64_t frame_seed, uint64_t seed_stride, int nframes);
@@ -431,6 +438,55 @@ int dr_reproject_defaults(dr_reproject_params* p);
 int dr_accum_reproject(dr_context* c, const float from_settings13[13], const float to_settings13[13], int W, int H, int frames,
                        const dr_reproject_params* params, dr_reproject_result* result);
 
+/* ------------------------------------------------------------------ second moments ------ */
+/* How noisy is this pixel, and when can the render stop: a per-pixel SECOND-MOMENT PLANE beside the accumulator -- the "variance estimate carried
+ * along with the sums" of SVGF (Schied et al. 2017) -- and the noise estimate formed from it.  Option "moments" = 1 before dr_accum_reset gives the
+ * accumulator the plane; all integer arithmetic below is exact, the estimate is double with only + - * /, sqrt, floor and comparisons in the order
+ * written here (dogeray_amd/csrc/device_moments.hpp, no FMA contraction), so the GPU is bit-identical to the host build of the same source and to
+ * the numpy restatement in the tests.
+ *   plane      M2: one uint64 per pixel, pixel (x, y) at x * H + y like the history plane
+ *   add        for every frame folded into the accumulator, with that frame's int32 values (r, g, b) at the pixel:
+ *                y  = (54 r + 183 g) + 19 b in int64: Rec.709 luma x 256 (the weights sum to 256), |y| < 2^39
+ *                yc = min(max(y, -2^26), 2^26): the firefly cap, 1028 x a white pixel's 65280; yc^2 <= 2^52
+ *                M2 = M2 + (uint64)(yc * yc), saturating at 2^64 - 1
+ *              dr_pipeline_submit and dr_render_accumulate_pipelined fold each frame with ONE kernel, acc += frame and M2 += yc^2;
+ *              dr_render_accumulate runs as dr_render_accumulate_pipelined; dr_render_accumulate_async returns DR_ERR_INVALID ("moments")
+ *   first moment  not stored: S1 = (54 accR + 183 accG) + 19 accB in int64 equals the sum of y exactly, because y is linear -- as long as no
+ *              frame was capped (a capped frame enters M2 with yc and S1 with y)
+ *   reproject  dr_accum_reproject carries the plane (a second buffer appears with the first reprojection, as for the history): a valid pixel with
+ *              cnt <= max_history takes M2_to[p] = M2_from[q]; with cnt > max_history M2_to[p] = (M2 / cnt) * max_history + ((M2 % cnt) *
+ *              max_history) / cnt, which is floor(M2 * max_history / cnt) exactly; every other pixel 0.  Sums and squares scaled by the same
+ *              factor leave M2 / n - (S1 / n)^2 unchanged
+ *   estimate   n = hist_p + divide_by (hist_p = 0 without a history plane; divide_by >= 0: a reprojected image with no new frame has 0).  n < 2:
+ *              not estimated, sigma_p = 0.  Otherwise, all in double:
+ *                S1d = (double)S1; M2d = (double)M2
+ *                ss = M2d - (S1d * S1d) / (double)n; ss = ss > 0 ? ss : 0
+ *                var_p = (ss / ((double)(n - 1) * (double)n)) / 65536.0: the variance of the displayed mean luma, in (0..255 units)^2
+ *                sigma_p = (float)sqrt(var_p)
+ *              pixels outside the pixel grid: sigma = 0
+ *   denoiser   option "denoise_variance" = 1 and a plane: dr_accum_denoise's variance of a pixel with n_p >= 4 is var = (float)(var_p / ((double)la *
+ *              (double)la)), la = (0.2126f a'.r + 0.7152f a'.g) + 0.0722f a'.b with a' the albedo the demodulation uses; la == 0 or n_p < 4: the
+ *              spatial estimate.  An approximation: the moments are of the luma before demodulation.  It feeds the luminance edge stop only. */
+typedef struct dr_error_result {
+  int64_t pixels;        /* gw * gh, the pixel grid of settings13 (dr_render_aov's) */
+  int64_t estimated;     /* pixels with n_p >= 2 */
+  int64_t above;         /* estimated pixels with sigma_p > tolerance */
+  uint64_t sum_var_q16;  /* sum over estimated pixels of min(floor(var_p * 65536), 2^40) */
+  int64_t bins[16];      /* estimated pixels by sigma_p: bin 0 < 2^-6; bin k: 2^(k-7) <= sigma < 2^(k-6), k = 1..14; bin 15 >= 2^8 */
+} dr_error_result;
+/* The noise estimate of the accumulator: sigma_p of every pixel into out_sigma (W * H floats, row-major, dr_accum_present's layout; may be NULL) and /
+ * or the counts into result (may be NULL, not both).  Every field of the result is an integer count or a fixed-point sum: the same bits whatever
+ * order the GPU adds them in.  device_pointers = 1 applies to out_sigma only (a device buffer on this context's GPU, written on
+ * dr_context_stream); the result is host memory and the call returns when it is known.  Ordered behind the frames submitted before it
+ * (dr_pipeline_submit); changes neither the accumulator, nor dr_stats or any option.  The settings are accepted or refused as by dr_render_aov;
+ * DR_ERR_INVALID for no scene, no accumulator, W / H not the accumulator's, no moments plane, divide_by < 0, a negative or NaN tolerance, or no output. */
+int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int divide_by, float tolerance, float* out_sigma, dr_error_result* result,
+                   int device_pointers);
+/* The second-moment plane, uint64 per pixel at x * H + y.  Without a plane dr_accum_moments_read writes zeros and dr_accum_moments_device_ptr gives
+ * NULL / 0 bytes; dr_accum_reproject swaps between two buffers, the pointer is the current one. */
+int dr_accum_moments_read(dr_context* c, uint64_t* out /* W*H */);
+int dr_accum_moments_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes);
+
 /* ------------------------------------------------------------------ multi-GPU group ----- */
 /* One process, one context and one host thread per GPU (the reference is single-device, K:2614-2615).  Rank r of n
  * renders the block columns bx % n == r of every frame (scene replicated); every `gather_every` frames each rank packs
@@ -495,6 +551,11 @@ int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n
  * records from the RESIDENT wide-walk array -- the walk's memory behaviour without its arithmetic.  hot_records
  * restricts the random walk to the first records of the array (0 = all of it). */
 int dr_context_probe_gather(dr_context* c, uint32_t hot_records, int iters, double* records_per_s);
+
+/* Measurement aid (tools/moments_rate.py): the two kernels that fold a frame into the accumulator, timed alone with HIP events -- `iters` launches of
+ * the plain add (acc += frame) into plain_ms[iters], then `iters` of the fused add of the second-moment plane (acc += frame, M2 += yc^2) into
+ * fused_ms[iters] (zeros without a plane).  The frame added is black, so neither the sums nor the plane change. */
+int dr_context_probe_frame_add(dr_context* c, int iters, double* plain_ms, double* fused_ms);
 
 /* Measurement aid (tools/exp_trace_rate.py): what the walk would cost as a kernel of its own.  Renders ONE frame with the counting build, which writes every ray
  * it traces into the order a per-bounce wavefront would hold them (bounce by bounce, pixels in tile order); then a TRACE-ONLY kernel walks `frames` copies of that

@@ -18,6 +18,7 @@
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
+#include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
@@ -359,9 +360,11 @@ int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int 
 // as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
 // W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
 // hist (may be NULL): the accumulator's history plane, W x H at x * H + y -- pixel p's divisor is hist[p] + divide_by.
-// Returns 0, or -1 with hk_last_error.
-int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
-               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist) {
+// m2 (may be NULL): the second-moment plane, W x H at x * H + y -- option "denoise_variance" = 1: the variance pre-pass takes the temporal variance
+// of pixels with four samples or more from it.  Returns 0, or -1 with hk_last_error.
+int hk_denoise_m2(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+                  const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist,
+                  const unsigned long long* m2) {
   if (!acc || !settings13 || !normal || !albedo || !depth || !material) { hk_err = "bad argument"; return -1; }
   RenderParams P;
   memset(&P, 0, sizeof(P));
@@ -418,7 +421,16 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
     rows(gh, [&](int y) {                                                  // colour prepare, stage 1: the variance pre-pass
       for (int x = 0; x < gw; x++) {
         const size_t i = (size_t)y * gw + x;
-        const float var = dn_variance(D, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
+        const int m = material[i];
+        float var = 0.0f;
+        bool temporal = false;
+        if (m2) {
+          const size_t px = (size_t)x * (size_t)H + (size_t)y;
+          const int32_t* a = acc + px * 3;
+          temporal = mo_denoise_variance(a[0], a[1], a[2], m2[px], (long long)dn_divisor(hist, px, divide_by), dn_albedo(albedo[3 * i], m, D.demodulate),
+                                         dn_albedo(albedo[3 * i + 1], m, D.demodulate), dn_albedo(albedo[3 * i + 2], m, D.demodulate), var);
+        }
+        if (!temporal) var = dn_variance(D, guide[i], m, gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
         pb[i] = make_float4(pa[i].x, pa[i].y, pa[i].z, var);
       }
     });
@@ -463,6 +475,11 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
   return 0;
 }
 
+int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist) {
+  return hk_denoise_m2(acc, W, H, divide_by, settings13, normal, albedo, depth, material, params, out_f32, out_rgb8, nthreads, hist, nullptr);
+}
+
 // The float camera block of a view as fill_view_params forms it (what dr_accum_reproject's definition starts from): out12 = from, llc, hor, ver;
 // den2 = den_w, den_h; grid2 = gw, gh.  Returns 0, or -1 with hk_last_error.
 int hk_camera_block(const float* settings13, int W, int H, float* out12, double* den2, int* grid2) {
@@ -478,10 +495,13 @@ int hk_camera_block(const float* settings13, int W, int H, float* out12, double*
 // dr_accum_reproject on the host: device_reproject.hpp over the pixel grid, from guides given as arrays in dr_render_aov's layout (t / material
 // gw x gh, normal gw x gh x 3) for both views -- hk_aov's or the GPU's own.  acc_from / acc_to: column-major W x H x 3; hist_from (may be NULL) /
 // hist_to: W x H at x * H + y; params: a dr_reproject_params (NULL: the defaults); counts[5]: pixels, valid, masked, offscreen, rejected.
+// m2_from / m2_to (both or neither NULL): the second-moment planes, W x H at x * H + y, carried with the sums (device_moments.hpp mo_carry).
 // Returns 0, or -1 with hk_last_error.
-int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H, int frames, const float* from_settings13, const float* to_settings13,
-                 const float* t_from, const float* normal_from, const int32_t* mat_from, const float* t_to, const float* normal_to, const int32_t* mat_to,
-                 const int32_t* params, int32_t* acc_to, int32_t* hist_to, long long* counts, int nthreads) {
+int hk_reproject_m2(const int32_t* acc_from, const int32_t* hist_from, int W, int H, int frames, const float* from_settings13, const float* to_settings13,
+                    const float* t_from, const float* normal_from, const int32_t* mat_from, const float* t_to, const float* normal_to, const int32_t* mat_to,
+                    const int32_t* params, int32_t* acc_to, int32_t* hist_to, long long* counts, int nthreads, const unsigned long long* m2_from,
+                    unsigned long long* m2_to) {
+  if ((m2_from == nullptr) != (m2_to == nullptr)) { hk_err = "bad argument"; return -1; }
   if (!acc_from || !from_settings13 || !to_settings13 || !t_from || !normal_from || !mat_from || !t_to || !normal_to || !mat_to || !acc_to || !hist_to || !counts) { hk_err = "bad argument"; return -1; }
   RenderParams Pf, Pt;
   memset(&Pf, 0, sizeof(Pf)); memset(&Pt, 0, sizeof(Pt));
@@ -504,6 +524,7 @@ int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H
   const int gw = Pt.gx * 8, gh = Pt.gy * 8;
   memset(acc_to, 0, (size_t)W * H * 3 * sizeof(int32_t));
   memset(hist_to, 0, (size_t)W * H * sizeof(int32_t));
+  if (m2_to) memset(m2_to, 0, (size_t)W * H * sizeof(unsigned long long));
   RpGuides Gt, Gf;
   Gt.t = t_to; Gt.normal = normal_to; Gt.mat = mat_to;
   Gf.t = t_from; Gf.normal = normal_from; Gf.mat = mat_from;
@@ -519,12 +540,77 @@ int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H
           part[(size_t)k * 4 + (size_t)cls]++;
           if (cls != RP_VALID) continue;
           const size_t q = (size_t)qx * (size_t)H + (size_t)qy, p = (size_t)x * (size_t)H + (size_t)y;
-          rp_carry(R, frames, acc_from + q * 3, hist_from ? hist_from[q] : 0, acc_to + p * 3, hist_to[p]);
+          const int32_t hist_q = hist_from ? hist_from[q] : 0;
+          rp_carry(R, frames, acc_from + q * 3, hist_q, acc_to + p * 3, hist_to[p]);
+          if (m2_to) m2_to[p] = mo_carry(m2_from[q], (long long)hist_q + (long long)frames, R.max_history);
         }
     });
   for (std::thread& t : th) t.join();
   counts[0] = (long long)gw * gh;
   for (int c = 0; c < 4; c++) { counts[1 + c] = 0; for (int k = 0; k < nthreads; k++) counts[1 + c] += part[(size_t)k * 4 + (size_t)c]; }
+  return 0;
+}
+
+int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H, int frames, const float* from_settings13, const float* to_settings13,
+                 const float* t_from, const float* normal_from, const int32_t* mat_from, const float* t_to, const float* normal_to, const int32_t* mat_to,
+                 const int32_t* params, int32_t* acc_to, int32_t* hist_to, long long* counts, int nthreads) {
+  return hk_reproject_m2(acc_from, hist_from, W, H, frames, from_settings13, to_settings13, t_from, normal_from, mat_from, t_to, normal_to, mat_to, params,
+                         acc_to, hist_to, counts, nthreads, nullptr, nullptr);
+}
+
+// The fused add of the second-moment plane on the host (device_moments.hpp, as kernels_moments.hip runs it): acc += frame and m2 += the frame's capped
+// luma squared, for npix pixels, in place.
+int hk_moments_add(int32_t* acc, const int32_t* frame, unsigned long long* m2, long long npix) {
+  if (!acc || !frame || !m2 || npix < 0) { hk_err = "bad argument"; return -1; }
+  for (long long p = 0; p < npix; p++) {
+    const int32_t r = frame[3 * p], g = frame[3 * p + 1], b = frame[3 * p + 2];
+    acc[3 * p] = (int32_t)((uint32_t)acc[3 * p] + (uint32_t)r);
+    acc[3 * p + 1] = (int32_t)((uint32_t)acc[3 * p + 1] + (uint32_t)g);
+    acc[3 * p + 2] = (int32_t)((uint32_t)acc[3 * p + 2] + (uint32_t)b);
+    m2[p] = mo_add(m2[p], mo_square(r, g, b));
+  }
+  return 0;
+}
+
+// dr_accum_error on the host: device_moments.hpp over the pixel grid of settings13.  acc: column-major W x H x 3; hist (may be NULL) / m2: W x H at
+// x * H + y; out_sigma (may be NULL): row-major W x H, 0 outside the grid; result (may be NULL): 19 words -- estimated, above, sum_var_q16, bins[16]
+// (pixels = grid2[0] * grid2[1], returned in grid2).  Returns 0, or -1 with hk_last_error.
+int hk_error(const int32_t* acc, const int32_t* hist, const unsigned long long* m2, int W, int H, int divide_by, float tolerance, const float* settings13,
+             float* out_sigma, unsigned long long* result, int* grid2, int nthreads) {
+  if (!acc || !m2 || !settings13 || (!out_sigma && !result)) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  if (divide_by < 0) { hk_err = "error: divide_by must be >= 0"; return -1; }
+  if (!(tolerance >= 0.0f)) { hk_err = "error: tolerance must be >= 0"; return -1; }
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  if (grid2) { grid2[0] = gw; grid2[1] = gh; }
+  if (out_sigma) memset(out_sigma, 0, (size_t)W * H * sizeof(float));
+  if (nthreads < 1) nthreads = 1;
+  std::vector<unsigned long long> part((size_t)nthreads * MO_WORDS, 0);
+  std::vector<std::thread> th;
+  for (int k = 0; k < nthreads; k++)
+    th.emplace_back([&, k] {
+      unsigned long long* cnt = part.data() + (size_t)k * MO_WORDS;
+      for (int y = k; y < gh; y += nthreads)
+        for (int x = 0; x < gw; x++) {
+          const size_t p = (size_t)x * (size_t)H + (size_t)y;
+          const int32_t* a = acc + p * 3;
+          const long long n = (long long)(hist ? hist[p] : 0) + (long long)divide_by;
+          double var = 0.0;
+          const bool est = mo_variance(a[0], a[1], a[2], m2[p], n, var);
+          const float sigma = est ? mo_sigma(var) : 0.0f;
+          if (out_sigma) out_sigma[(size_t)y * (size_t)W + (size_t)x] = sigma;
+          if (!est) continue;
+          cnt[MO_ESTIMATED]++;
+          if (sigma > tolerance) cnt[MO_ABOVE]++;
+          cnt[MO_SUM_VAR] += mo_var_q16(var);
+          cnt[MO_BIN0 + mo_bin(sigma)]++;
+        }
+    });
+  for (std::thread& t : th) t.join();
+  if (result)
+    for (int w = 0; w < MO_WORDS; w++) { result[w] = 0; for (int k = 0; k < nthreads; k++) result[w] += part[(size_t)k * MO_WORDS + (size_t)w]; }
   return 0;
 }
 

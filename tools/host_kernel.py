@@ -59,6 +59,10 @@ def lib():
         L.hk_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         L.hk_camera_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hk_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int]
+        L.hk_denoise_m2.argtypes = L.hk_denoise.argtypes + [C.c_void_p]
+        L.hk_reproject_m2.argtypes = L.hk_reproject.argtypes + [C.c_void_p, C.c_void_p]
+        L.hk_moments_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+        L.hk_error.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -116,11 +120,12 @@ class Scene:
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "normal_power_log2": 7, "sigma_depth": 1.0, "demodulate": 1, "material_stop": 1}
 
 
-def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthreads=4, hist=None, **params):
+def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthreads=4, hist=None, m2=None, **params):
     """dr_accum_denoise on the host (device_denoise.hpp): the accumulator acc (int32[W, H, 3], column-major as dr_accum_read returns it) and the
     guides as arrays shaped like dogeray_amd.Context.render_aov's (normal / albedo [gh, gw, 3], depth / material [gh, gw]) -> (f32[H, W, 3],
     uint8[H, W, 3]) in dr_accum_present's layout.  hist: the accumulator's history plane (int32[W, H], dr_accum_history_read) -- pixel p then
-    divides by hist[p] + divide_by.  params: the fields of dr_denoise_params (the rest default)."""
+    divides by hist[p] + divide_by.  m2: the second-moment plane (uint64[W, H], dr_accum_moments_read) -- option "denoise_variance" = 1: pixels with
+    four samples or more take their variance from it.  params: the fields of dr_denoise_params (the rest default)."""
     acc = np.ascontiguousarray(acc, dtype=np.int32)
     W, H = acc.shape[0], acc.shape[1]
     st = np.ascontiguousarray(settings13, dtype=np.float32)
@@ -138,8 +143,12 @@ def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthread
     if hist is not None:
         hist = np.ascontiguousarray(hist, dtype=np.int32)
         assert hist.shape == (W, H)
-    rc = lib().hk_denoise(acc.ctypes.data, W, H, int(divide_by), st.ctypes.data, *[g.ctypes.data for g in guides], raw.ctypes.data,
-                          f32.ctypes.data, rgb.ctypes.data, nthreads, hist.ctypes.data if hist is not None else None)
+    if m2 is not None:
+        m2 = np.ascontiguousarray(m2, dtype=np.uint64)
+        assert m2.shape == (W, H)
+    rc = lib().hk_denoise_m2(acc.ctypes.data, W, H, int(divide_by), st.ctypes.data, *[g.ctypes.data for g in guides], raw.ctypes.data,
+                             f32.ctypes.data, rgb.ctypes.data, nthreads, hist.ctypes.data if hist is not None else None,
+                             m2.ctypes.data if m2 is not None else None)
     if rc != 0:
         raise RuntimeError(lib().hk_last_error().decode())
     return f32, rgb
@@ -159,11 +168,12 @@ def camera_block(settings13, W, H):
 REPROJECT_DEFAULTS = {"max_history": 32, "normal_cos": 0.9, "plane_tolerance": 0.01, "material_mask": 0xFFFFFFC3, "sky": 1}
 
 
-def reproject(acc, hist, frames, from_settings13, to_settings13, guides_from, guides_to, nthreads=4, **params):
+def reproject(acc, hist, frames, from_settings13, to_settings13, guides_from, guides_to, nthreads=4, m2=None, **params):
     """dr_accum_reproject on the host (device_reproject.hpp): the accumulator acc (int32[W, H, 3] as dr_accum_read returns it), its history
     plane hist (int32[W, H] or None), the frames added since, both views' settings13 and guides (dicts with "t", "normal", "material" shaped
     like dogeray_amd.Context.render_aov's) -> (acc int32[W, H, 3], hist int32[W, H], counts dict) of the `to` view.  params: the fields of
-    dr_reproject_params (the rest default)."""
+    dr_reproject_params (the rest default).  m2: the second-moment plane (uint64[W, H]) -- it is carried as well (hk_reproject_m2) and the
+    result is (acc, hist, counts, m2 uint64[W, H])."""
     acc = np.ascontiguousarray(acc, dtype=np.int32)
     W, H = acc.shape[0], acc.shape[1]
     a, b = np.ascontiguousarray(from_settings13, dtype=np.float32), np.ascontiguousarray(to_settings13, dtype=np.float32)
@@ -188,8 +198,51 @@ def reproject(acc, hist, frames, from_settings13, to_settings13, guides_from, gu
     out_acc = np.zeros((W, H, 3), np.int32)
     out_hist = np.zeros((W, H), np.int32)
     counts = (C.c_longlong * 5)()
-    rc = lib().hk_reproject(acc.ctypes.data, hist.ctypes.data if hist is not None else None, W, H, int(frames), a.ctypes.data, b.ctypes.data,
-                            *[x.ctypes.data for x in g], raw.ctypes.data, out_acc.ctypes.data, out_hist.ctypes.data, C.cast(counts, C.c_void_p), nthreads)
+    out_m2 = None
+    if m2 is not None:
+        m2 = np.ascontiguousarray(m2, dtype=np.uint64)
+        assert m2.shape == (W, H)
+        out_m2 = np.zeros((W, H), np.uint64)
+    rc = lib().hk_reproject_m2(acc.ctypes.data, hist.ctypes.data if hist is not None else None, W, H, int(frames), a.ctypes.data, b.ctypes.data,
+                               *[x.ctypes.data for x in g], raw.ctypes.data, out_acc.ctypes.data, out_hist.ctypes.data, C.cast(counts, C.c_void_p), nthreads,
+                               m2.ctypes.data if m2 is not None else None, out_m2.ctypes.data if m2 is not None else None)
     if rc != 0:
         raise RuntimeError(lib().hk_last_error().decode())
-    return out_acc, out_hist, dict(zip(("pixels", "valid", "masked", "offscreen", "rejected"), [int(v) for v in counts]))
+    cd = dict(zip(("pixels", "valid", "masked", "offscreen", "rejected"), [int(v) for v in counts]))
+    return (out_acc, out_hist, cd) if m2 is None else (out_acc, out_hist, cd, out_m2)
+
+
+def moments_add(acc, m2, frame):
+    """The fused add of the second-moment plane on the host (device_moments.hpp): acc int32[W, H, 3] += frame and m2 uint64[W, H] += the frame's
+    capped luma x 256, squared (saturating), IN PLACE; both must be C-contiguous arrays of exactly these types."""
+    assert acc.dtype == np.int32 and m2.dtype == np.uint64 and acc.flags.c_contiguous and m2.flags.c_contiguous
+    frame = np.ascontiguousarray(frame, dtype=np.int32)
+    assert acc.shape == frame.shape and acc.shape[-1] == 3 and m2.size * 3 == acc.size
+    if lib().hk_moments_add(acc.ctypes.data, frame.ctypes.data, m2.ctypes.data, m2.size) != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    return acc, m2
+
+
+ERROR_FIELDS = ("estimated", "above", "sum_var_q16")
+
+
+def error(acc, hist, m2, settings13, divide_by, tolerance, nthreads=4):
+    """dr_accum_error on the host (device_moments.hpp): the accumulator acc (int32[W, H, 3]), its history plane hist (int32[W, H] or None) and
+    its second-moment plane m2 (uint64[W, H]) -> (sigma float32[H, W], result dict with the fields of dr_error_result)."""
+    acc = np.ascontiguousarray(acc, dtype=np.int32)
+    W, H = acc.shape[0], acc.shape[1]
+    st = np.ascontiguousarray(settings13, dtype=np.float32)
+    m2 = np.ascontiguousarray(m2, dtype=np.uint64)
+    assert m2.shape == (W, H)
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.int32)
+        assert hist.shape == (W, H)
+    sigma = np.zeros((H, W), np.float32)
+    res = np.zeros(19, np.uint64)
+    grid = np.zeros(2, np.int32)
+    rc = lib().hk_error(acc.ctypes.data, hist.ctypes.data if hist is not None else None, m2.ctypes.data, W, H, int(divide_by), float(tolerance),
+                        st.ctypes.data, sigma.ctypes.data, res.ctypes.data, grid.ctypes.data, nthreads)
+    if rc != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    d = {"pixels": int(grid[0]) * int(grid[1]), "estimated": int(res[0]), "above": int(res[1]), "sum_var_q16": int(res[2]), "bins": [int(v) for v in res[3:]]}
+    return sigma, d
