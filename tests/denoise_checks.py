@@ -120,17 +120,26 @@ def atrous(p, nz, m, gz, e, var, step):
     return (se / sw[..., None]).astype(np.float32), (sv / (sw * sw)).astype(np.float32)
 
 
-def denoise(acc, settings13, divide_by, normal, albedo, depth, material, **params):
+def denoise(acc, settings13, divide_by, normal, albedo, depth, material, hist=None, **params):
     """The restatement: acc int32[W, H, 3] (column-major, as dr_accum_read), guides as Context.render_aov returns them -> (f32[H, W, 3],
-    uint8[H, W, 3]) in dr_accum_present's layout."""
+    uint8[H, W, 3]) in dr_accum_present's layout.  hist: the accumulator's history plane (int32[W, H]) -- pixel p then divides by
+    hist[p] + divide_by, a divisor of 0 giving 0.  params: the fields of dr_denoise_params; any other name is a TypeError."""
     p = dict(DEFAULTS)
-    p.update(params)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError("unknown denoise parameter %r" % k)
+        p[k] = v
     acc = np.asarray(acc, dtype=np.int32)
     W, H = acc.shape[0], acc.shape[1]
     gw, gh = grid(settings13, W, H)
     out = np.zeros((H, W, 3), np.float32)
     with np.errstate(all="ignore"):
-        c = np.ascontiguousarray(acc[:gw, :gh].transpose(1, 0, 2)).astype(np.float32) / f32(divide_by)
+        a = np.ascontiguousarray(acc[:gw, :gh].transpose(1, 0, 2)).astype(np.float32)
+        if hist is None:
+            c = a / f32(divide_by)
+        else:
+            n = (np.asarray(hist)[:gw, :gh].T.astype(np.int64) + int(divide_by)).astype(np.float32)[..., None]
+            c = np.where(n == 0, f32(0), a / n).astype(np.float32)
         if p["iterations"] == 0:
             f = c
         else:
