@@ -84,6 +84,14 @@ class DrDenoiseParams(C.Structure):
                 ("demodulate", C.c_int), ("material_stop", C.c_int)]
 
 
+class DrUpscaleParams(C.Structure):
+    """struct dr_upscale_params (include/dogeray_amd.h dr_accum_upscale)."""
+    _fields_ = [("mode", C.c_int), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float), ("demodulate", C.c_int), ("material_stop", C.c_int)]
+
+
+UPSCALE_BLOCK, UPSCALE_GUIDED = 0, 1
+
+
 class DrReprojectParams(C.Structure):
     """struct dr_reproject_params (include/dogeray_amd.h dr_accum_reproject)."""
     _fields_ = [("max_history", C.c_int), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float), ("material_mask", C.c_uint32), ("sky", C.c_int)]
@@ -160,6 +168,8 @@ _API = [
     ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
     ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
     ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
+    ("dr_upscale_defaults", C.c_int, [C.POINTER(DrUpscaleParams)]),
+    ("dr_accum_upscale", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrUpscaleParams), C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_group_create", C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
     ("dr_group_destroy", None, [_VP]),
     ("dr_group_size", C.c_int, [_VP]),
@@ -286,6 +296,17 @@ def denoise_params(**params):
     for k, v in params.items():
         if k not in dict(DrDenoiseParams._fields_):
             raise TypeError("unknown denoise parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrDenoiseParams._fields_)))
+        setattr(p, k, v)
+    return p
+
+
+def upscale_params(**params):
+    """A DrUpscaleParams: the library's defaults (dr_upscale_defaults) with the given fields replaced."""
+    p = DrUpscaleParams()
+    _check(lib().dr_upscale_defaults(C.byref(p)))
+    for k, v in params.items():
+        if k not in dict(DrUpscaleParams._fields_):
+            raise TypeError("unknown upscale parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrUpscaleParams._fields_)))
         setattr(p, k, v)
     return p
 
@@ -682,6 +703,43 @@ class Context:
             cur.wait_stream(lib_stream)
         return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
 
+    # ---- upsampler (dr_accum_upscale)
+    def upscale(self, settings13, W, H, divide_by, out="rgb8", device=False, prefilter=None, **params):
+        """The accumulator rendered with settings13 (divisor settings13[11]) at full size (include/dogeray_amd.h dr_accum_upscale), in
+        accum_present's layout: out="rgb8" -> uint8[H, W, 3], "f32" -> float32[H, W, 3] (0..255 units, unclamped), "both" -> (rgb8, f32).
+        params: the fields of dr_upscale_params (mode = UPSCALE_GUIDED / UPSCALE_BLOCK, normal_power_log2, sigma_depth, demodulate,
+        material_stop), the rest at their defaults.  prefilter: None, True (the denoiser's defaults, demodulate as here) or a dict of
+        dr_denoise_params fields -- the a-trous filter then runs on the low grid first.  device=True: torch tensors on this context's GPU, with
+        render_aov's stream handshake."""
+        st = _f32(settings13)
+        assert st.shape == (13,)
+        if out not in ("rgb8", "f32", "both"):
+            raise ValueError("out must be 'rgb8', 'f32' or 'both', not %r" % (out,))
+        p = upscale_params(**params)
+        pre = None
+        if prefilter is not None and prefilter is not False:
+            d = {} if prefilter is True else dict(prefilter)
+            d.setdefault("demodulate", p.demodulate)
+            pre = C.byref(denoise_params(**d))
+        want_rgb, want_f32 = out in ("rgb8", "both"), out in ("f32", "both")
+        if not device:
+            rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
+            f = np.empty((H, W, 3), np.float32) if want_f32 else None
+            _check(lib().dr_accum_upscale(self._h, _p(st), W, H, int(divide_by), C.byref(p), pre, _p(f) if f is not None else None,
+                                          _p(rgb) if rgb is not None else None, 0))
+        else:
+            import torch
+            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+            rgb = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev) if want_rgb else None
+            f = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev) if want_f32 else None
+            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+            cur = torch.cuda.current_stream(dev)
+            lib_stream.wait_stream(cur)
+            _check(lib().dr_accum_upscale(self._h, _p(st), W, H, int(divide_by), C.byref(p), pre, f.data_ptr() if f is not None else None,
+                                          rgb.data_ptr() if rgb is not None else None, 1))
+            cur.wait_stream(lib_stream)
+        return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
+
     # ---- temporal reprojection (dr_accum_reproject)
     def reproject(self, from_settings13, to_settings13, W, H, frames, **params):
         """Carries the accumulator from the view it was rendered in to another one (include/dogeray_amd.h dr_accum_reproject): frames = the
@@ -951,9 +1009,15 @@ class ProgressiveRenderer:
         self._pnum = self.iter
         return counts
 
-    def image(self, divide_by, denoise=None):
+    def image(self, divide_by, denoise=None, upscale=None):
         """The displayed image: accum_present(divide_by); with denoise (True, or a dict of dr_denoise_params fields) the same image through
-        Context.denoise, guided by the AOVs of the settings the last step() rendered with."""
+        Context.denoise, guided by the AOVs of the settings the last step() rendered with.  upscale (True, or a dict of dr_upscale_params
+        fields): the last step()'s image at full size through Context.upscale -- a preview stage's td x td blocks (mode = UPSCALE_BLOCK) or
+        its guided upsample; denoise then acts as the prefilter."""
+        if upscale is not None and upscale is not False:
+            params = {} if upscale is True else dict(upscale)
+            pre = None if denoise is None or denoise is False else denoise
+            return self.ctx.upscale(self.settings13(), self.W, self.H, divide_by, prefilter=pre, **params)
         if denoise is None or denoise is False:
             return self.ctx.accum_present(divide_by)
         params = {} if denoise is True else dict(denoise)

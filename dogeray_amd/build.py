@@ -8,7 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdogeray_amd.so")
 HOST_SOURCES = ["rts_reader.cpp", "bvh_builder.cpp", "linearise.cpp", "wide_builder.cpp", "capi_host.cpp", "group.cpp", "context.cpp"]
 # one translation unit per family of kernels (kernels.hpp)
-DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip"]
+DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip",
+                  "kernels_upscale.hip"]
 # -ffp-contract=off: no FMA contraction on host or device -- the BVH build and the kernel's
 # arithmetic are specified operation by operation (DESIGN.md "arithmetic contract").
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra",
@@ -37,10 +38,14 @@ def build(force=False, verbose=False):
     hipcc = _hipcc()
     os.makedirs(os.path.join(HERE, "_build"), exist_ok=True)
     cmds = []
+    # a library newer than every source needs no objects (a tree that was copied without them is not compiled again)
+    fresh = not force and not _stale(LIB, [os.path.join(CSRC, f) for f in HOST_SOURCES + DEVICE_SOURCES] + headers + [os.path.abspath(__file__)])
     for src in HOST_SOURCES + DEVICE_SOURCES:
         sp = os.path.join(CSRC, src)
         obj = os.path.join(HERE, "_build", src + ".o")
         objs.append(obj)
+        if fresh:
+            continue
         if force or _stale(obj, [sp] + headers + [os.path.abspath(__file__)]):
             # -fno-slp-vectorize: hipcc otherwise packs adjacent scalar f32 ops into v_pk_* instructions, which
             # issue slower than the scalars they replace on gfx950 (measured: +4.6 % rays/s without them)
@@ -64,7 +69,7 @@ def build(force=False, verbose=False):
             subprocess.check_call(cmd)
         with ThreadPoolExecutor(max_workers=min(len(cmds), max(1, (os.cpu_count() or 2) // 2))) as ex:
             list(ex.map(run, cmds))
-    if force or _stale(LIB, objs):
+    if not fresh and (force or _stale(LIB, objs)):
         cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", LIB] + objs + ["-pthread", "-ldl"]
         if verbose:
             print(" ".join(cmd), flush=True)

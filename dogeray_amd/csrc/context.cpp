@@ -44,6 +44,11 @@ struct dr_context {
   float* dn_planes = nullptr; size_t dn_planes_floats = 0;
   bool dn_valid = false; float dn_key[13] = {0}; int dn_W = 0, dn_H = 0; uint64_t dn_gen = 0;
   uint8_t* dn_staging = nullptr; size_t dn_staging_bytes = 0;
+  // dr_accum_upscale: the full-resolution guides (one allocation made by the first guided call: guide 4n | scratch 4n | albedo 3n | material n |
+  // gz n floats over the full pixel grid), their key (settings13 with element 11 = 1, W, H, scene generation) and the AOV passes of the last call
+  float* up_planes = nullptr; size_t up_planes_floats = 0;
+  bool up_valid = false; float up_key[13] = {0}; int up_W = 0, up_H = 0; uint64_t up_gen = 0;
+  int up_passes = 0;
   uint64_t scene_gen = 0;                  // scene uploads so far
   // dr_accum_reproject: the second accumulator of the pair (swapped with `accum` by every reprojection), the two history planes (hist: the
   // current one, null until the first reprojection and after dr_accum_reset), the guide planes of two views (t n | normal 3n | material n
@@ -513,7 +518,7 @@ void dr_context_destroy(dr_context* c) {
   for (int k = 1; k < dr_context::PIPE_STREAMS; k++) if (c->pipe_stream[k]) (void)hipStreamSynchronize(c->pipe_stream[k]);
   if (c->acc_stream) (void)hipStreamSynchronize(c->acc_stream);
   void* bufs[] = {c->wave_log, c->packed[0], c->packed[1], c->walk, c->wide, c->pairs, c->prims, c->shade, c->tex, c->texels, c->frame, c->accum, c->present, c->counters, c->tile_counters, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start,
-                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->cert_mask,
+                  c->slot_to_orig_dev, c->aov_staging, c->dn_planes, c->dn_staging, c->up_planes, c->cert_mask,
                   c->accum2, c->hist_buf[0], c->hist_buf[1], c->rp_planes[0], c->rp_planes[1], c->rp_counts,
                   c->m2_buf[0], c->m2_buf[1], c->err_counts, c->err_staging};
   for (void* b : bufs) if (b) (void)hipFree(b);
@@ -543,6 +548,7 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   c->scene_gen++;                  // the denoiser's cached guides belong to the old scene
   c->dn_valid = false;
   c->rp_valid = false;
+  c->up_valid = false;
   DeviceImage img;
   int rc = DR_OK;
   try {
@@ -634,6 +640,7 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
       *value = (int)((1000ull * n_flagged + (unsigned)c->cert_tiles / 2) / (unsigned)c->cert_tiles);
     }
   }
+  else if (n == "upscale_aov_passes") *value = c->up_passes;                 // read-only: AOV passes the last dr_accum_upscale traced
   else if (n == "reproject_aov_passes") *value = c->rp_passes;               // read-only: AOV passes the last dr_accum_reproject traced
   else if (n == "traversal") *value = traversal_of(c);                        // the traversal launches really use
   else { set_error("unknown option " + n); return DR_ERR_INVALID; }
@@ -714,6 +721,94 @@ int aov_view(dr_context* c, const float settings13[13], int W, int H, RenderPara
   P.walk = c->walk; P.walk_bytes = (uint32_t)c->walk_bytes; P.pairs = c->pairs; P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
   P.wide = c->wide; P.wide_bytes = (uint32_t)c->wide_bytes; P.wide_pmax = c->wide_pmax; P.wide_mu = c->wide_mu;
   return DR_OK;
+}
+
+// The low side of dr_accum_denoise and dr_accum_upscale over the pixel grid of settings13 (L.gw x L.gh > 0; L.D, L.acc, L.hist, L.m2 set by the
+// caller): the planes (allocated by the first call), the cached guides (traced when the key differs; *aov_passes counts that pass), colour stage 0
+// and -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  On return L.src is the plane of the result: (e, l) after stage 0,
+// (e, var) after the last pass; L.guide, L.albedo, L.mat and L.gz are the guides.
+int denoise_low_side(dr_context* c, const float settings13[13], int W, int H, const RenderParams& P, int traversal, DnLaunch& L, bool filter, int* aov_passes) {
+  const size_t n = (size_t)L.gw * (size_t)L.gh;
+  const int gw = L.gw, gh = L.gh;
+  // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
+  const size_t need = 17 * n;
+  if (need > c->dn_planes_floats) {
+    if (c->dn_planes) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_planes); c->dn_planes = nullptr; c->dn_planes_floats = 0; }
+    c->dn_valid = false;
+    HIP_TRY(hipMalloc((void**)&c->dn_planes, need * sizeof(float)));
+    c->dn_planes_floats = need;
+  }
+  float* const guide = c->dn_planes;
+  float* const pa = guide + 4 * n;
+  float* const pb = pa + 4 * n;
+  float* const albedo = pb + 4 * n;
+  int32_t* const mat = reinterpret_cast<int32_t*>(albedo + 3 * n);
+  float* const gz = reinterpret_cast<float*>(mat + n);
+  L.albedo = albedo; L.mat = mat; L.guide = guide; L.gz = gz;
+  const bool same = c->dn_valid && c->dn_W == W && c->dn_H == H && c->dn_gen == c->scene_gen && memcmp(c->dn_key, settings13, sizeof(c->dn_key)) == 0;
+  if (!same) {
+    // the guides: launch_aov writes normal and depth into colour plane A (3n + n floats), albedo and material into their planes; the guide
+    // prepare packs (n, z) and forms gz from them
+    AovLaunch A;
+    memset(&A, 0, sizeof(A));
+    A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
+    A.focus = settings13[7];
+    A.slot_to_orig = c->slot_to_orig_dev;
+    A.normal = pa; A.depth = pa + 3 * n; A.albedo = albedo; A.material = mat;
+    launch_aov(c->stream, P, traversal, A);
+    HIP_TRY(hipGetLastError());
+    L.normal = pa; L.depth = pa + 3 * n;
+    launch_denoise_guides(c->stream, L);
+    HIP_TRY(hipGetLastError());
+    memcpy(c->dn_key, settings13, sizeof(c->dn_key));
+    c->dn_W = W; c->dn_H = H; c->dn_gen = c->scene_gen; c->dn_valid = true;
+    L.normal = nullptr; L.depth = nullptr;
+    if (aov_passes) ++*aov_passes;
+  }
+  L.dst = pa;
+  launch_denoise_colour(c->stream, L, 0);                 // acc -> (e, l) in A
+  L.src = pa; L.dst = pb;
+  if (filter) {
+    launch_denoise_colour(c->stream, L, 1);               // (e, l) -> (e, var) in B
+    L.src = pb; L.dst = pa;                               // the passes: B -> A -> B ...
+    for (int it = 0; it < L.D.iterations; it++) {
+      launch_denoise_pass(c->stream, L, 1 << it, c->denoise_tiles);
+      float* const t = const_cast<float*>(L.src);
+      L.src = L.dst; L.dst = t;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return DR_OK;
+}
+
+// Where the W x H outputs of dr_accum_denoise / dr_accum_upscale are written: the caller's device buffers, or the staging they are downloaded from
+int output_staging(dr_context* c, size_t npix, float* out_f32, uint8_t* out_rgb8, int device_pointers, float*& f32_dev, uint8_t*& rgb_dev) {
+  f32_dev = out_f32;
+  rgb_dev = out_rgb8;
+  if (device_pointers) return DR_OK;
+  const size_t bytes = (out_f32 ? npix * 3 * sizeof(float) : 0) + (out_rgb8 ? npix * 3 : 0);
+  if (bytes > c->dn_staging_bytes) {
+    if (c->dn_staging) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_staging); c->dn_staging = nullptr; c->dn_staging_bytes = 0; }
+    HIP_TRY(hipMalloc((void**)&c->dn_staging, bytes));
+    c->dn_staging_bytes = bytes;
+  }
+  f32_dev = out_f32 ? reinterpret_cast<float*>(c->dn_staging) : nullptr;
+  rgb_dev = out_rgb8 ? c->dn_staging + (out_f32 ? npix * 3 * sizeof(float) : 0) : nullptr;
+  return DR_OK;
+}
+int output_download(dr_context* c, size_t npix, float* out_f32, uint8_t* out_rgb8, const float* f32_dev, const uint8_t* rgb_dev) {
+  if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, f32_dev, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, rgb_dev, npix * 3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+
+// dr_denoise_params as dr_accum_denoise judges them: null, or why they are refused
+const char* check_denoise_params(const dr_denoise_params& p) {
+  if (p.iterations < 0 || p.iterations > DN_MAX_ITERATIONS) return "iterations must be 0 .. 10";
+  if (!(p.sigma_luminance >= 0.0f) || !(p.sigma_depth >= 0.0f)) return "sigma_luminance and sigma_depth must be >= 0";
+  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return "normal_power_log2 must be 0 .. 16";
+  return nullptr;
 }
 
 }  // namespace
@@ -799,9 +894,7 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   dr_denoise_params p;
   dr_denoise_defaults(&p);
   if (params) p = *params;
-  if (p.iterations < 0 || p.iterations > DN_MAX_ITERATIONS) { set_error("denoise: iterations must be 0 .. 10"); return DR_ERR_INVALID; }
-  if (!(p.sigma_luminance >= 0.0f) || !(p.sigma_depth >= 0.0f)) { set_error("denoise: sigma_luminance and sigma_depth must be >= 0"); return DR_ERR_INVALID; }
-  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { set_error("denoise: normal_power_log2 must be 0 .. 16"); return DR_ERR_INVALID; }
+  if (const char* why = check_denoise_params(p)) { set_error(std::string("denoise: ") + why); return DR_ERR_INVALID; }
   if (!out_f32 && !out_rgb8) { set_error("denoise: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
   { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
 
@@ -815,73 +908,124 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   L.acc = c->accum; L.hist = c->hist;
   L.m2 = c->denoise_variance ? c->m2 : nullptr;
   if (p.iterations > 0 && n > 0) {
-    // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
-    const size_t need = 17 * n;
-    if (need > c->dn_planes_floats) {
-      if (c->dn_planes) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_planes); c->dn_planes = nullptr; c->dn_planes_floats = 0; }
-      c->dn_valid = false;
-      HIP_TRY(hipMalloc((void**)&c->dn_planes, need * sizeof(float)));
-      c->dn_planes_floats = need;
-    }
-    float* const guide = c->dn_planes;
-    float* const pa = guide + 4 * n;
-    float* const pb = pa + 4 * n;
-    float* const albedo = pb + 4 * n;
-    int32_t* const mat = reinterpret_cast<int32_t*>(albedo + 3 * n);
-    float* const gz = reinterpret_cast<float*>(mat + n);
-    L.albedo = albedo; L.mat = mat; L.guide = guide; L.gz = gz;
-    const bool same = c->dn_valid && c->dn_W == W && c->dn_H == H && c->dn_gen == c->scene_gen && memcmp(c->dn_key, settings13, sizeof(c->dn_key)) == 0;
-    if (!same) {
-      // the guides: launch_aov writes normal and depth into colour plane A (3n + n floats), albedo and material into their planes; the guide
-      // prepare packs (n, z) and forms gz from them
-      AovLaunch A;
-      memset(&A, 0, sizeof(A));
-      A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
-      A.focus = settings13[7];
-      A.slot_to_orig = c->slot_to_orig_dev;
-      A.normal = pa; A.depth = pa + 3 * n; A.albedo = albedo; A.material = mat;
-      launch_aov(c->stream, P, traversal, A);
-      HIP_TRY(hipGetLastError());
-      L.normal = pa; L.depth = pa + 3 * n;
-      launch_denoise_guides(c->stream, L);
-      HIP_TRY(hipGetLastError());
-      memcpy(c->dn_key, settings13, sizeof(c->dn_key));
-      c->dn_W = W; c->dn_H = H; c->dn_gen = c->scene_gen; c->dn_valid = true;
-      L.normal = nullptr; L.depth = nullptr;
-    }
-    L.dst = pa;
-    launch_denoise_colour(c->stream, L, 0);                 // acc -> (e, l) in A
-    L.src = pa; L.dst = pb;
-    launch_denoise_colour(c->stream, L, 1);                 // (e, l) -> (e, var) in B
-    L.src = pb; L.dst = pa;                                 // the passes: B -> A -> B ...
-    for (int it = 0; it < p.iterations; it++) {
-      launch_denoise_pass(c->stream, L, 1 << it, c->denoise_tiles);
-      float* const t = const_cast<float*>(L.src);
-      L.src = L.dst; L.dst = t;
-    }
-    HIP_TRY(hipGetLastError());
+    const int rc = denoise_low_side(c, settings13, W, H, P, traversal, L, true, nullptr);
+    if (rc != DR_OK) return rc;
   }
-  // the outputs: where the caller wants them, or staged and downloaded
-  float* f32_dev = out_f32;
-  uint8_t* rgb_dev = out_rgb8;
-  if (!device_pointers) {
-    const size_t bytes = (out_f32 ? npix * 3 * sizeof(float) : 0) + (out_rgb8 ? npix * 3 : 0);
-    if (bytes > c->dn_staging_bytes) {
-      if (c->dn_staging) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dn_staging); c->dn_staging = nullptr; c->dn_staging_bytes = 0; }
-      HIP_TRY(hipMalloc((void**)&c->dn_staging, bytes));
-      c->dn_staging_bytes = bytes;
-    }
-    f32_dev = out_f32 ? reinterpret_cast<float*>(c->dn_staging) : nullptr;
-    rgb_dev = out_rgb8 ? c->dn_staging + (out_f32 ? npix * 3 * sizeof(float) : 0) : nullptr;
-  }
+  float* f32_dev;
+  uint8_t* rgb_dev;
+  { const int rc = output_staging(c, npix, out_f32, out_rgb8, device_pointers, f32_dev, rgb_dev); if (rc != DR_OK) return rc; }
   L.out_f32 = f32_dev; L.out_rgb8 = rgb_dev;
   launch_denoise_finish(c->stream, L);
   HIP_TRY(hipGetLastError());
   if (device_pointers) return DR_OK;
-  if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, f32_dev, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, rgb_dev, npix * 3, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  return output_download(c, npix, out_f32, out_rgb8, f32_dev, rgb_dev);
+}
+
+int dr_upscale_defaults(dr_upscale_params* p) {
+  if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
+  p->mode = DR_UPSCALE_GUIDED; p->normal_power_log2 = 5; p->sigma_depth = 1.0f; p->demodulate = 1; p->material_stop = 1;
   return DR_OK;
+}
+
+int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_upscale_params* params,
+                     const dr_denoise_params* prefilter, float* out_f32, uint8_t* out_rgb8, int device_pointers) {
+  if (!c || !settings13) { set_error("null argument"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  RenderParams P, PF;
+  int traversal = 0;
+  { const int rc = aov_view(c, settings13, W, H, P, traversal); if (rc != DR_OK) return rc; }
+  float full13[13];                                        // the same view at full resolution
+  memcpy(full13, settings13, sizeof(full13));
+  full13[11] = 1.0f;
+  { const int rc = aov_view(c, full13, W, H, PF, traversal); if (rc != DR_OK) return rc; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  if (W != c->accW || H != c->accH) {
+    set_error("upscale: " + std::to_string(W) + " x " + std::to_string(H) + " is not the accumulator's " + std::to_string(c->accW) + " x " + std::to_string(c->accH));
+    return DR_ERR_INVALID;
+  }
+  if (divide_by < 1) { set_error("upscale: divide_by must be >= 1"); return DR_ERR_INVALID; }
+  dr_upscale_params p;
+  dr_upscale_defaults(&p);
+  if (params) p = *params;
+  if (p.mode != DR_UPSCALE_BLOCK && p.mode != DR_UPSCALE_GUIDED) { set_error("upscale: mode must be DR_UPSCALE_BLOCK or DR_UPSCALE_GUIDED"); return DR_ERR_INVALID; }
+  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { set_error("upscale: normal_power_log2 must be 0 .. 16"); return DR_ERR_INVALID; }
+  if (!(p.sigma_depth >= 0.0f)) { set_error("upscale: sigma_depth must be >= 0"); return DR_ERR_INVALID; }
+  if (prefilter) {
+    if (p.mode == DR_UPSCALE_BLOCK) { set_error("upscale: a prefilter needs the guided mode (dr_accum_denoise filters without upscaling)"); return DR_ERR_INVALID; }
+    if (const char* why = check_denoise_params(*prefilter)) { set_error(std::string("upscale: prefilter ") + why); return DR_ERR_INVALID; }
+    if (prefilter->iterations < 1) { set_error("upscale: prefilter iterations must be >= 1"); return DR_ERR_INVALID; }
+    if ((prefilter->demodulate != 0) != (p.demodulate != 0)) { set_error("upscale: prefilter demodulate differs from the upscale parameters'"); return DR_ERR_INVALID; }
+  }
+  if (!out_f32 && !out_rgb8) { set_error("upscale: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
+  { const int jrc = join_pipeline(c); if (jrc != DR_OK) return jrc; }      // ordered behind the frames submitted before
+
+  const int gw = P.gx * 8, gh = P.gy * 8, FW = PF.gx * 8, FH = PF.gy * 8;
+  const size_t n = (size_t)gw * (size_t)gh, nf = (size_t)FW * (size_t)FH, npix = (size_t)W * (size_t)H;
+  UpLaunch U;
+  memset(&U, 0, sizeof(U));
+  U.gw = gw; U.gh = gh; U.FW = FW; U.FH = FH; U.W = W; U.H = H; U.div = n > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
+  U.U.mode = p.mode; U.U.normal_power_log2 = p.normal_power_log2; U.U.sigma_depth = p.sigma_depth;
+  U.U.demodulate = p.demodulate != 0; U.U.material_stop = p.material_stop != 0;
+  U.acc = c->accum; U.hist = c->hist;
+  c->up_passes = 0;
+  if (p.mode == DR_UPSCALE_GUIDED && n > 0) {
+    // the low side: the denoiser's planes; without a prefilter only the demodulated colour of stage 0
+    DnLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
+    L.D.demodulate = U.U.demodulate; L.D.material_stop = U.U.material_stop;
+    if (prefilter) {
+      L.D.iterations = prefilter->iterations; L.D.sigma_luminance = prefilter->sigma_luminance; L.D.normal_power_log2 = prefilter->normal_power_log2;
+      L.D.sigma_depth = prefilter->sigma_depth; L.D.material_stop = prefilter->material_stop != 0;
+    }
+    L.acc = c->accum; L.hist = c->hist;
+    L.m2 = c->denoise_variance ? c->m2 : nullptr;
+    { const int rc = denoise_low_side(c, settings13, W, H, P, traversal, L, prefilter != nullptr, &c->up_passes); if (rc != DR_OK) return rc; }
+    U.e = L.src; U.guide = L.guide; U.mat = L.mat;
+    // the full side: planes of its own, traced once per view
+    const size_t need = 13 * nf;
+    if (need > c->up_planes_floats) {
+      if (c->up_planes) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->up_planes); c->up_planes = nullptr; c->up_planes_floats = 0; }
+      c->up_valid = false;
+      HIP_TRY(hipMalloc((void**)&c->up_planes, need * sizeof(float)));
+      c->up_planes_floats = need;
+    }
+    float* const fguide = c->up_planes;
+    float* const scratch = fguide + 4 * nf;
+    float* const falbedo = scratch + 4 * nf;
+    int32_t* const fmat = reinterpret_cast<int32_t*>(falbedo + 3 * nf);
+    float* const fgz = reinterpret_cast<float*>(fmat + nf);
+    const bool same = c->up_valid && c->up_W == W && c->up_H == H && c->up_gen == c->scene_gen && memcmp(c->up_key, full13, sizeof(c->up_key)) == 0;
+    if (!same) {
+      AovLaunch A;
+      memset(&A, 0, sizeof(A));
+      A.x0 = 0; A.y0 = 0; A.w = FW; A.h = FH;
+      A.focus = full13[7];
+      A.slot_to_orig = c->slot_to_orig_dev;
+      A.normal = scratch; A.depth = scratch + 3 * nf; A.albedo = falbedo; A.material = fmat;
+      launch_aov(c->stream, PF, traversal, A);
+      HIP_TRY(hipGetLastError());
+      DnLaunch G;
+      memset(&G, 0, sizeof(G));
+      G.gw = FW; G.gh = FH; G.W = W; G.H = H;
+      G.normal = scratch; G.depth = scratch + 3 * nf; G.mat = fmat; G.guide = fguide; G.gz = fgz;
+      launch_denoise_guides(c->stream, G);
+      HIP_TRY(hipGetLastError());
+      memcpy(c->up_key, full13, sizeof(c->up_key));
+      c->up_W = W; c->up_H = H; c->up_gen = c->scene_gen; c->up_valid = true;
+      c->up_passes++;
+    }
+    U.Fguide = fguide; U.Falbedo = falbedo; U.Fmat = fmat; U.Fgz = fgz;
+  }
+  float* f32_dev;
+  uint8_t* rgb_dev;
+  { const int rc = output_staging(c, npix, out_f32, out_rgb8, device_pointers, f32_dev, rgb_dev); if (rc != DR_OK) return rc; }
+  U.out_f32 = f32_dev; U.out_rgb8 = rgb_dev;
+  launch_upscale(c->stream, U);
+  HIP_TRY(hipGetLastError());
+  if (device_pointers) return DR_OK;
+  return output_download(c, npix, out_f32, out_rgb8, f32_dev, rgb_dev);
 }
 
 int dr_reproject_defaults(dr_reproject_params* p) {

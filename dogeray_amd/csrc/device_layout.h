@@ -194,6 +194,16 @@ struct DnParams {
   int material_stop;
 };
 
+// The upsampler's parameters (dr_upscale_params, validated by dr_accum_upscale / hk_upscale; device_upscale.hpp)
+constexpr int UP_BLOCK = 0, UP_GUIDED = 1;
+struct UpParams {
+  int mode;
+  int normal_power_log2;
+  float sigma_depth;
+  int demodulate;
+  int material_stop;
+};
+
 // Temporal reprojection (dr_accum_reproject; device_reproject.hpp): the parameters (dr_reproject_params, validated by dr_accum_reproject /
 // hk_reproject), one view's float camera block as fill_view_params forms it, and the projection into the `from` camera, formed once per call
 // in double (params_host.hpp fill_reproject_proj)

@@ -112,12 +112,23 @@ bool write_denoised(dr_context* ctx, const float st[13], int W, int H, int divid
   return ends_with(path, ".ppm") ? write_ppm(path, rgb, W, H) : write_bmp(path, rgb, W, H);
 }
 
+// --preview PREFIX: a low stage of the preview ladder at full size (dr_accum_upscale) as PREFIX_<divisor>.bmp -- guided by the view's
+// full-resolution AOVs, or (--preview-block) with every low pixel filling a block as the reference shows it (K:2281-2300)
+bool write_preview(dr_context* ctx, const float st[13], int W, int H, int divide_by, bool block, const std::string& path) {
+  dr_upscale_params p;
+  dr_upscale_defaults(&p);
+  if (block) p.mode = DR_UPSCALE_BLOCK;
+  std::vector<uint8_t> rgb((size_t)W * H * 3);
+  if (dr_accum_upscale(ctx, st, W, H, divide_by, &p, nullptr, nullptr, rgb.data(), 0) != DR_OK) return false;
+  return write_bmp(path, rgb, W, H);
+}
+
 void usage() {
   fprintf(stderr,
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
           "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm] [--move-to CX,CY,CZ,LX,LY,LZ] [--move-frames N]\n"
-          "               [--until-sigma T[,PERMILLE]] [--max-frames N] [--sigma-out FILE.pfm]\n"
+          "               [--until-sigma T[,PERMILLE]] [--max-frames N] [--sigma-out FILE.pfm] [--preview PREFIX] [--preview-block]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -138,13 +149,17 @@ void usage() {
           "  --until-sigma  instead of --frames: add full-resolution frames, eight at a time, until at most PERMILLE per mille (default 10) of the pixels\n"
           "               have a standard error of the displayed mean luma above T (0..255 units; dr_accum_error, option moments) or --max-frames N\n"
           "               (default 1024) have been added; one line reports which (one context only: not with --gpus)\n"
-          "  --sigma-out  after the render, write that standard error per pixel as a one-channel .pfm (needs no --until-sigma)\n");
+          "  --sigma-out  after the render, write that standard error per pixel as a one-channel .pfm (needs no --until-sigma)\n"
+          "  --preview    write the three low stages of the preview ladder (1/8, 1/4, 1/2 resolution) at full size as PREFIX_8.bmp, PREFIX_4.bmp and\n"
+          "               PREFIX_2.bmp: the AOV-guided upsample of each stage (dr_accum_upscale, default parameters)\n"
+          "  --preview-block  with --preview: every low pixel fills a block instead, as the reference displays these stages\n");
 }
 
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string scene_path = "scene.rts", out_path, aov_prefix, denoise_path;
+  std::string scene_path = "scene.rts", out_path, aov_prefix, denoise_path, preview_prefix;
+  bool preview_block = false;
   bool move = false;
   float move_to[6] = {0, 0, 0, 0, 0, 0};
   int move_frames = 1;
@@ -188,6 +203,8 @@ int main(int argc, char** argv) {
     }
     else if (a == "--max-frames") max_frames = atoi(next());
     else if (a == "--sigma-out") sigma_path = next();
+    else if (a == "--preview") preview_prefix = next();
+    else if (a == "--preview-block") preview_block = true;
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
@@ -328,6 +345,11 @@ int main(int argc, char** argv) {
     iter += n;
     divide_by = iter - pnum;                                          // K:2287
     if (dr_accum_present(ctx, divide_by, rgb.data()) != DR_OK) die("present");
+    if (!preview_prefix.empty() && (int)st[11] > 1) {               // a low stage of the ladder, shown at full size
+      const std::string path = preview_prefix + "_" + std::to_string((int)st[11]) + ".bmp";
+      if (!write_preview(ctx, st, W, H, divide_by, preview_block, path)) { fprintf(stderr, "dogeray: cannot write the preview %s: %s\n", path.c_str(), dr_last_error()); return 1; }
+      printf("exported preview:%s\n", path.c_str());
+    }
     long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - begin).count();
     if (!quiet) {
       printf("\rTime = %lld[us]  %.2f FPS       %d samples             ", us, us > 0 ? 1e6 * n / (double)us : 0.0, divide_by * s.spp);   // K:2327

@@ -4,6 +4,7 @@
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
+//   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
 //   kernels_moments.hip       the second-moment plane: the fused frame add and the per-pixel noise estimate (option "moments", dr_accum_error)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
@@ -101,6 +102,29 @@ void launch_denoise_guides(hipStream_t stream, const DnLaunch& L);              
 void launch_denoise_colour(hipStream_t stream, const DnLaunch& L, int stage);      // 0: acc -> (e, l) in dst; 1: src (e, l) -> (e, var) in dst
 void launch_denoise_pass(hipStream_t stream, const DnLaunch& L, int step, int lattice);   // src -> dst, one a-trous iteration
 void launch_denoise_finish(hipStream_t stream, const DnLaunch& L);                 // src (or, iterations 0, acc) -> out_f32 / out_rgb8
+
+// kernels_upscale.hip: the low side is the denoiser's (DnLaunch's grid, guide, albedo, mat and a colour plane), the full side the same planes
+// over the full-resolution pixel grid FW x FH = (W / 8) * 8 x (H / 8) * 8 (pixel (X, Y) at Y * FW + X); block mode reads neither
+struct UpLaunch {
+  int gw, gh;                     // low pixel grid; the output grid is gw * div x gh * div
+  int FW, FH;                     // full-resolution pixel grid
+  int W, H;                       // accumulator (column-major) and output (row-major W x H x 3)
+  int div;                        // (int)settings13[11]
+  int divide_by;
+  UpParams U;
+  const int32_t* acc;
+  const int32_t* hist;            // the accumulator's history plane, or null
+  const float* e;                 // low colour plane, float4 per pixel: (e.r, e.g, e.b, *)
+  const float* guide;             // low guides: float4 (n, z), material
+  const int32_t* mat;
+  const float* Fguide;            // full guides: float4 (N, Z), albedo (3 per pixel), material, depth gradient
+  const float* Falbedo;
+  const int32_t* Fmat;
+  const float* Fgz;
+  float* out_f32;                 // W x H x 3 (null: not written)
+  uint8_t* out_rgb8;
+};
+void launch_upscale(hipStream_t stream, const UpLaunch& L);
 
 // kernels_reproject.hip: the guides of both views are row-major gw x gh planes as launch_aov writes them; the accumulators are column-major W x H x 3
 // ((x * H + y) * 3) and the history planes W x H (x * H + y).  Pixels outside the grid are not written (the caller clears the `to` pair).

@@ -198,6 +198,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
+ *   "upscale_aov_passes" (read only) first-hit AOV passes the last dr_accum_upscale traced: 2 with cold guide caches, 1 when only the low or only the
+ *                   full-resolution guides were cached (the same view at another divisor), 0 on a repeat and in block mode
  *   "moments"       read by dr_accum_reset: 1 gives the accumulator a second-moment plane (one uint64 per pixel, see dr_accum_error below), 0
  *                   (default) drops it; a context that never sets it allocates nothing and runs the code it ran before.  No pixel of the
  *                   accumulator changes; dr_render_accumulate then runs through the pipeline
@@ -385,6 +387,59 @@ int dr_denoise_defaults(dr_denoise_params* p);
  * divide_by < 1, iterations outside 0 .. 10, a negative sigma, normal_power_log2 outside 0 .. 16, or no output. */
 int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_denoise_params* params, float* out_f32,
                      uint8_t* out_rgb8, int device_pointers);
+
+/* ------------------------------------------------------------------ upsampler ----------- */
+/* Shows an accumulator rendered at a fraction of the resolution (settings13[11] = div > 1, the reference's preview ladder K:2169-2199) at full
+ * size.  DR_UPSCALE_BLOCK is the reference's display: every low pixel fills a div x div block (K:2281-2300).  DR_UPSCALE_GUIDED is a joint-
+ * bilateral upsample (Kopf et al. 2007) of the demodulated low-resolution colour against the first-hit AOVs of the same view traced at full
+ * resolution, with the denoiser's normal, depth and material stops; the full-resolution albedo is multiplied back, so geometric edges and
+ * texture detail are sharp although the light is not.  Only + - * /, fminf / fmaxf and comparisons in the order written here
+ * (dogeray_amd/csrc/device_upscale.hpp, no FMA contraction): the GPU is bit-identical to the host build of the same source and to the numpy
+ * restatement in the tests.  q(x), a', gz and the pair terms wn, xz are the denoiser's, above.
+ *   grids      div = (int)settings13[11] >= 1.  Low grid gw x gh: dr_render_aov's grid of settings13, low pixel q.  Output grid Gw x Gh =
+ *              gw * div x gh * div, output pixel P = (X, Y); it lies inside the full-resolution AOV grid (W / 8) * 8 x (H / 8) * 8.  Output
+ *              pixels outside Gw x Gh are 0; layout and units of out_f32 / out_rgb8 are dr_accum_denoise's
+ *   low colour c_q = (float)acc / (float)divide_by per channel, with a history plane (float)acc / (float)(hist_q + divide_by), 0 where that
+ *              divisor is 0 (the denoiser's colour)
+ *   block      the output at P is low pixel (X / div, Y / div): out_f32 = c_q; out_rgb8 = clamp(acc / divisor, 0, 255) in integers, byte for
+ *              byte what dr_accum_present writes for that pixel (div = 1: dr_accum_present's image).  No guides are traced and nothing is
+ *              allocated beyond the staging of host outputs
+ *   guides     full: N_P, Z_P, M_P, A_P = normal, depth, material, albedo of dr_render_aov for settings13 with element 11 set to 1.0f; gz_P
+ *              the denoiser's depth gradient over P's four neighbours in the full grid; A'_P = a'(A_P, M_P).  Low: n_q, z_q, m_q, a_q the same
+ *              channels for settings13 itself, a'_q; e_q = c_q / a'_q per channel
+ *   position   in integers: tx = 2 X + 1 - div, x0 = floor(tx / (2 div)) (-1 on the left edge), rx = tx - 2 div x0, fx = (float)rx /
+ *              (float)(2 div); y0, fy likewise.  bx = (1.0f - fx, fx), by = (1.0f - fy, fy)
+ *   taps       j = 0, 1 outer, i = 0, 1 inner, q = (x0 + i, y0 + j), b = bx_i * by_j.  No tap when q is outside the low grid, b == 0, exactly
+ *              one of M_P, m_q is a miss, or material_stop and M_P != m_q.  Both miss: w = b.  Otherwise
+ *              wn = fmaxf((N_P.x n_q.x + N_P.y n_q.y) + N_P.z n_q.z, 0) squared normal_power_log2 times, dz = |Z_P - z_q|,
+ *              rz = 1 / ((sigma_depth * gz_P) * (float)div + 1e-3f * Z_P), xz = dz > 0 ? dz * rz : 0, w = (b * wn) / q(xz).
+ *              sw += w, s += w * e_q per channel
+ *   output     sw > 0: f = (s / sw) * A'_P per channel.  Otherwise (no usable tap: a thin object only the full-resolution guides see) f = c of
+ *              low pixel (X / div, Y / div), the block value.  out_rgb8 = (uint8)(int)fminf(fmaxf(f, 0), 255)
+ *   prefilter  non-NULL: dr_accum_denoise's a-trous filter runs on the low grid first, with these parameters, the options "denoise_variance" and
+ *              "denoise_tiles" and the history plane as there; e_q is then the filter's e plane after its last iteration (what the denoiser's
+ *              output stage would multiply by a'_q).  The block value of a pixel without a tap stays the unfiltered c */
+enum { DR_UPSCALE_BLOCK = 0, DR_UPSCALE_GUIDED = 1 };
+typedef struct dr_upscale_params {
+  int mode;                /* default DR_UPSCALE_GUIDED */
+  int normal_power_log2;   /* 0 .. 16, default 5 (wn^32: the taps are at most one low pixel away) */
+  float sigma_depth;       /* >= 0, default 1 */
+  int demodulate;          /* default 1: upsample c / albedo, then multiply the full-resolution albedo back */
+  int material_stop;       /* default 1: no weight between pixels of different materials */
+} dr_upscale_params;
+int dr_upscale_defaults(dr_upscale_params* p);
+/* The accumulator rendered with settings13 (divided by divide_by) at full size into out_f32 (W * H * 3 floats) and / or out_rgb8 (W * H * 3
+ * bytes), either NULL (not both).  params NULL: the defaults; prefilter NULL: no filter.  device_pointers as dr_accum_denoise.  The low guides
+ * are the denoiser's cached planes (a dr_accum_denoise and a dr_accum_upscale of the same settings13 share them); the full-resolution guides
+ * live in context-owned planes of their own, allocated by the first guided call and keyed by (settings13 with element 11 = 1, W, H, scene), so
+ * the stages of a preview ladder trace them once; dr_context_upload_scene drops both, a context that never upscales allocates nothing, and
+ * option "upscale_aov_passes" reads how many AOV passes the last call traced.  Ordered behind the frames submitted before it
+ * (dr_pipeline_submit); changes neither the accumulator, nor dr_stats, the stripe or any option.  The settings are accepted or refused as by
+ * dr_render_aov; DR_ERR_INVALID for no scene, no accumulator, W / H not the accumulator's, divide_by < 1, a mode other than 0 / 1,
+ * normal_power_log2 outside 0 .. 16, a negative sigma_depth, no output, and for a prefilter in block mode (call dr_accum_denoise), with
+ * iterations < 1, with demodulate other than params' or with parameters dr_accum_denoise refuses. */
+int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, int divide_by, const dr_upscale_params* params,
+                     const dr_denoise_params* prefilter, float* out_f32, uint8_t* out_rgb8, int device_pointers);
 
 /* ------------------------------------------------------------------ temporal reprojection */
 /* Carries the accumulator across a camera move: the temporal half of SVGF (Schied et al. 2017) as a nearest-neighbour BACKWARD reprojection.

@@ -20,6 +20,7 @@
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
+#include "../dogeray_amd/csrc/device_upscale.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
 #include "../dogeray_amd/csrc/scene_host.hpp"
@@ -57,6 +58,91 @@ void render_columns(const RenderParams& P, int traversal, int first, int step, C
   }
   total = c;
 }
+// f(row) for every row, rows interleaved over the threads
+void host_rows(int nthreads, int count, const std::function<void(int)>& f) {
+  std::vector<std::thread> th;
+  for (int k = 0; k < nthreads; k++) th.emplace_back([&, k] { for (int r = k; r < count; r += nthreads) f(r); });
+  for (std::thread& t : th) t.join();
+}
+
+// The low side of hk_denoise and hk_upscale over the gw x gh pixel grid, stage by stage as kernels_denoise.hip runs it: the guide prepare, colour
+// stage 0 and -- filter -- the variance pre-pass and the D.iterations a-trous passes.  e: (e, l) after stage 0, (e, var) after the last pass.
+struct HostLow {
+  std::vector<float4> guide, e;
+  std::vector<float> gz;
+};
+void host_denoise_low(const int32_t* acc, int H, int divide_by, int gw, int gh, const DnParams& D, bool filter, const float* normal, const float* albedo,
+                      const float* depth, const int32_t* material, const int32_t* hist, const unsigned long long* m2, int nthreads, HostLow& out) {
+  const size_t n = (size_t)gw * gh;
+  auto rows = [&](int count, const std::function<void(int)>& f) { host_rows(nthreads, count, f); };
+  std::vector<float4>& guide = out.guide;
+  std::vector<float>& gz = out.gz;
+  guide.resize(n); gz.resize(n);
+  std::vector<float4> pa(n), pb(n);
+  auto mat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? DN_OUTSIDE : (int)material[(size_t)y * gw + x]; };
+  auto zat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? 0.0f : depth[(size_t)y * gw + x]; };
+  {
+    rows(gh, [&](int y) {                                                  // guide prepare
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        gz[i] = dn_gradient(zat(x, y), mat(x, y), zat(x - 1, y), mat(x - 1, y), zat(x + 1, y), mat(x + 1, y), zat(x, y - 1), mat(x, y - 1), zat(x, y + 1), mat(x, y + 1));
+        guide[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
+      }
+    });
+    rows(gh, [&](int y) {                                                  // colour prepare, stage 0
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        const size_t px = (size_t)x * (size_t)H + (size_t)y;
+        const int32_t* a = acc + px * 3;
+        const int nd = dn_divisor(hist, px, divide_by);
+        const int m = material[i];
+        const float er = dn_colour(a[0], nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
+        const float eg = dn_colour(a[1], nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
+        const float eb = dn_colour(a[2], nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
+        pa[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
+      }
+    });
+    if (!filter) { out.e.swap(pa); return; }
+    auto tap = [&](const std::vector<float4>& src, int x, int y) {
+      DnTap q;
+      q.m = mat(x, y);
+      if (q.m == DN_OUTSIDE) { q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
+      const size_t j = (size_t)y * gw + x;
+      q.c = src[j]; q.g = guide[j];
+      return q;
+    };
+    rows(gh, [&](int y) {                                                  // colour prepare, stage 1: the variance pre-pass
+      for (int x = 0; x < gw; x++) {
+        const size_t i = (size_t)y * gw + x;
+        const int m = material[i];
+        float var = 0.0f;
+        bool temporal = false;
+        if (m2) {
+          const size_t px = (size_t)x * (size_t)H + (size_t)y;
+          const int32_t* a = acc + px * 3;
+          temporal = mo_denoise_variance(a[0], a[1], a[2], m2[px], (long long)dn_divisor(hist, px, divide_by), dn_albedo(albedo[3 * i], m, D.demodulate),
+                                         dn_albedo(albedo[3 * i + 1], m, D.demodulate), dn_albedo(albedo[3 * i + 2], m, D.demodulate), var);
+        }
+        if (!temporal) var = dn_variance(D, guide[i], m, gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
+        pb[i] = make_float4(pa[i].x, pa[i].y, pa[i].z, var);
+      }
+    });
+    std::vector<float4>* src = &pb;
+    std::vector<float4>* dst = &pa;
+    for (int it = 0; it < D.iterations; it++) {
+      const int step = 1 << it;
+      rows(gh, [&](int y) {
+        for (int x = 0; x < gw; x++) {
+          const size_t i = (size_t)y * gw + x;
+          (*dst)[i] = dn_atrous(D, step, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(*src, x + step * dx, y + step * dy); });
+        }
+      });
+      std::swap(src, dst);
+    }
+    out.e.swap(*src);                                                      // the filtered (e, var)
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,77 +464,11 @@ int hk_denoise_m2(const int32_t* acc, int W, int H, int divide_by, const float* 
       D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { hk_err = "bad denoise parameters"; return -1; }
   D.demodulate = D.demodulate != 0; D.material_stop = D.material_stop != 0;
   const int gw = P.gx * 8, gh = P.gy * 8;
-  const size_t n = (size_t)gw * gh;
   if (nthreads < 1) nthreads = 1;
-  auto rows = [&](int count, const std::function<void(int)>& f) {          // f(row) for every row, rows interleaved over the threads
-    std::vector<std::thread> th;
-    for (int k = 0; k < nthreads; k++) th.emplace_back([&, k] { for (int r = k; r < count; r += nthreads) f(r); });
-    for (std::thread& t : th) t.join();
-  };
-  std::vector<float4> guide(n), pa(n), pb(n);
-  std::vector<float> gz(n);
-  auto mat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? DN_OUTSIDE : (int)material[(size_t)y * gw + x]; };
-  auto zat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? 0.0f : depth[(size_t)y * gw + x]; };
-  if (D.iterations > 0) {
-    rows(gh, [&](int y) {                                                  // guide prepare
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        gz[i] = dn_gradient(zat(x, y), mat(x, y), zat(x - 1, y), mat(x - 1, y), zat(x + 1, y), mat(x + 1, y), zat(x, y - 1), mat(x, y - 1), zat(x, y + 1), mat(x, y + 1));
-        guide[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
-      }
-    });
-    rows(gh, [&](int y) {                                                  // colour prepare, stage 0
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        const size_t px = (size_t)x * (size_t)H + (size_t)y;
-        const int32_t* a = acc + px * 3;
-        const int nd = dn_divisor(hist, px, divide_by);
-        const int m = material[i];
-        const float er = dn_colour(a[0], nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
-        const float eg = dn_colour(a[1], nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
-        const float eb = dn_colour(a[2], nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
-        pa[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
-      }
-    });
-    auto tap = [&](const std::vector<float4>& src, int x, int y) {
-      DnTap q;
-      q.m = mat(x, y);
-      if (q.m == DN_OUTSIDE) { q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
-      const size_t j = (size_t)y * gw + x;
-      q.c = src[j]; q.g = guide[j];
-      return q;
-    };
-    rows(gh, [&](int y) {                                                  // colour prepare, stage 1: the variance pre-pass
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        const int m = material[i];
-        float var = 0.0f;
-        bool temporal = false;
-        if (m2) {
-          const size_t px = (size_t)x * (size_t)H + (size_t)y;
-          const int32_t* a = acc + px * 3;
-          temporal = mo_denoise_variance(a[0], a[1], a[2], m2[px], (long long)dn_divisor(hist, px, divide_by), dn_albedo(albedo[3 * i], m, D.demodulate),
-                                         dn_albedo(albedo[3 * i + 1], m, D.demodulate), dn_albedo(albedo[3 * i + 2], m, D.demodulate), var);
-        }
-        if (!temporal) var = dn_variance(D, guide[i], m, gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
-        pb[i] = make_float4(pa[i].x, pa[i].y, pa[i].z, var);
-      }
-    });
-    std::vector<float4>* src = &pb;
-    std::vector<float4>* dst = &pa;
-    for (int it = 0; it < D.iterations; it++) {
-      const int step = 1 << it;
-      rows(gh, [&](int y) {
-        for (int x = 0; x < gw; x++) {
-          const size_t i = (size_t)y * gw + x;
-          (*dst)[i] = dn_atrous(D, step, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(*src, x + step * dx, y + step * dy); });
-        }
-      });
-      std::swap(src, dst);
-    }
-    pa.swap(*src);                                                         // pa: the filtered (e, var)
-  }
-  rows(H, [&](int y) {                                                     // finish
+  HostLow low;
+  if (D.iterations > 0) host_denoise_low(acc, H, divide_by, gw, gh, D, true, normal, albedo, depth, material, hist, m2, nthreads, low);
+  const std::vector<float4>& pa = low.e;
+  host_rows(nthreads, H, [&](int y) {                                      // finish
     for (int x = 0; x < W; x++) {
       float f[3] = {0.0f, 0.0f, 0.0f};
       if (x < gw && y < gh) {
@@ -478,6 +498,94 @@ int hk_denoise_m2(const int32_t* acc, int W, int H, int divide_by, const float* 
 int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
                const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist) {
   return hk_denoise_m2(acc, W, H, divide_by, settings13, normal, albedo, depth, material, params, out_f32, out_rgb8, nthreads, hist, nullptr);
+}
+
+// dr_accum_upscale on the host: device_upscale.hpp over the output grid of settings13, from the low guides (the grid of settings13) and the full
+// guides (settings13 with element 11 = 1) given as arrays in dr_render_aov's layout -- normal, albedo, depth, material each.  params: a
+// dr_upscale_params (NULL: the defaults); prefilter: a dr_denoise_params or NULL -- the denoiser's host passes then run on the low grid first.
+// out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3; out_notap (may be NULL): W x H bytes, 1 where a guided pixel found no usable tap.
+// hist / m2 as hk_denoise_m2.  Returns 0, or -1 with hk_last_error.
+int hk_upscale(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+               const int32_t* material, const float* fnormal, const float* falbedo, const float* fdepth, const int32_t* fmaterial, const int32_t* params,
+               const int32_t* prefilter, float* out_f32, uint8_t* out_rgb8, uint8_t* out_notap, int nthreads, const int32_t* hist,
+               const unsigned long long* m2) {
+  if (!acc || !settings13) { hk_err = "bad argument"; return -1; }
+  RenderParams P, PF;
+  memset(&P, 0, sizeof(P));
+  memset(&PF, 0, sizeof(PF));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  float full13[13];
+  memcpy(full13, settings13, sizeof(full13));
+  full13[11] = 1.0f;
+  if (const char* why = fill_view_params(full13, W, H, 0.0f, 0, 1, 0, PF)) { hk_err = why; return -1; }
+  UpParams U = {UP_GUIDED, 5, 1.0f, 1, 1};
+  if (params) {                      // dr_upscale_params: int, int, float, int, int
+    memcpy(&U.mode, params, 4); memcpy(&U.normal_power_log2, params + 1, 4); memcpy(&U.sigma_depth, params + 2, 4);
+    memcpy(&U.demodulate, params + 3, 4); memcpy(&U.material_stop, params + 4, 4);
+  }
+  if (divide_by < 1 || (U.mode != UP_BLOCK && U.mode != UP_GUIDED) || U.normal_power_log2 < 0 || U.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2 ||
+      !(U.sigma_depth >= 0.0f)) { hk_err = "bad upscale parameters"; return -1; }
+  U.demodulate = U.demodulate != 0; U.material_stop = U.material_stop != 0;
+  DnParams D = {0, 0.0f, 0, 0.0f, U.demodulate, U.material_stop};
+  if (prefilter) {
+    memcpy(&D.iterations, prefilter, 4); memcpy(&D.sigma_luminance, prefilter + 1, 4); memcpy(&D.normal_power_log2, prefilter + 2, 4);
+    memcpy(&D.sigma_depth, prefilter + 3, 4); memcpy(&D.demodulate, prefilter + 4, 4); memcpy(&D.material_stop, prefilter + 5, 4);
+    D.demodulate = D.demodulate != 0; D.material_stop = D.material_stop != 0;
+    if (U.mode == UP_BLOCK || D.iterations < 1 || D.iterations > DN_MAX_ITERATIONS || !(D.sigma_luminance >= 0.0f) || !(D.sigma_depth >= 0.0f) ||
+        D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2 || D.demodulate != U.demodulate) { hk_err = "bad upscale prefilter"; return -1; }
+  }
+  const int gw = P.gx * 8, gh = P.gy * 8, FW = PF.gx * 8, FH = PF.gy * 8, div = gw > 0 && gh > 0 ? (int)settings13[11] : 1;
+  if (nthreads < 1) nthreads = 1;
+  HostLow low;
+  std::vector<float> fgz;
+  const bool guided = U.mode == UP_GUIDED && gw > 0 && gh > 0;
+  if (guided) {
+    if (!normal || !albedo || !depth || !material || !fnormal || !falbedo || !fdepth || !fmaterial) { hk_err = "bad argument"; return -1; }
+    host_denoise_low(acc, H, divide_by, gw, gh, D, prefilter != nullptr, normal, albedo, depth, material, hist, m2, nthreads, low);
+    fgz.resize((size_t)FW * FH);
+    auto fm = [&](int x, int y) { return (x < 0 || y < 0 || x >= FW || y >= FH) ? DN_OUTSIDE : (int)fmaterial[(size_t)y * FW + x]; };
+    auto fz = [&](int x, int y) { return (x < 0 || y < 0 || x >= FW || y >= FH) ? 0.0f : fdepth[(size_t)y * FW + x]; };
+    host_rows(nthreads, FH, [&](int y) {
+      for (int x = 0; x < FW; x++)
+        fgz[(size_t)y * FW + x] = dn_gradient(fz(x, y), fm(x, y), fz(x - 1, y), fm(x - 1, y), fz(x + 1, y), fm(x + 1, y), fz(x, y - 1), fm(x, y - 1), fz(x, y + 1), fm(x, y + 1));
+    });
+  }
+  host_rows(nthreads, H, [&](int Y) {
+    for (int X = 0; X < W; X++) {
+      const size_t o = ((size_t)Y * W + X) * 3;
+      float f[3] = {0.0f, 0.0f, 0.0f};
+      uint8_t rgb[3] = {0, 0, 0};
+      bool notap = false;
+      if (X < gw * div && Y < gh * div) {
+        const int qx = X / div, qy = Y / div;
+        if (U.mode == UP_BLOCK) {
+          up_block_colour(acc, hist, H, qx, qy, divide_by, f);
+          const size_t px = (size_t)qx * (size_t)H + (size_t)qy;
+          const int nd = dn_divisor(hist, px, divide_by);
+          for (int k = 0; k < 3; k++) rgb[k] = up_present8(acc[3 * px + k], nd);
+        } else {
+          const size_t p = (size_t)Y * FW + X;
+          const int mp = fmaterial[p];
+          const float ap[3] = {dn_albedo(falbedo[3 * p], mp, U.demodulate), dn_albedo(falbedo[3 * p + 1], mp, U.demodulate), dn_albedo(falbedo[3 * p + 2], mp, U.demodulate)};
+          const bool found = up_guided(U, div, X, Y, make_float4(fnormal[3 * p], fnormal[3 * p + 1], fnormal[3 * p + 2], fdepth[p]), mp, fgz[p], ap, [&](int tx, int ty) {
+            DnTap q;
+            if (tx < 0 || ty < 0 || tx >= gw || ty >= gh) { q.m = DN_OUTSIDE; q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
+            const size_t j = (size_t)ty * gw + tx;
+            q.c = low.e[j]; q.g = low.guide[j]; q.m = material[j];
+            return q;
+          }, f);
+          if (!found) { up_block_colour(acc, hist, H, qx, qy, divide_by, f); notap = true; }
+          for (int k = 0; k < 3; k++) rgb[k] = dn_rgb8(f[k]);
+        }
+      }
+      for (int k = 0; k < 3; k++) {
+        if (out_f32) out_f32[o + k] = f[k];
+        if (out_rgb8) out_rgb8[o + k] = rgb[k];
+      }
+      if (out_notap) out_notap[(size_t)Y * W + X] = notap ? 1 : 0;
+    }
+  });
+  return 0;
 }
 
 // The float camera block of a view as fill_view_params forms it (what dr_accum_reproject's definition starts from): out12 = from, llc, hor, ver;

@@ -60,6 +60,7 @@ def lib():
         L.hk_camera_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hk_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12 + [C.c_int]
         L.hk_denoise_m2.argtypes = L.hk_denoise.argtypes + [C.c_void_p]
+        L.hk_upscale.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 14 + [C.c_int, C.c_void_p, C.c_void_p]
         L.hk_reproject_m2.argtypes = L.hk_reproject.argtypes + [C.c_void_p, C.c_void_p]
         L.hk_moments_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
         L.hk_error.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -152,6 +153,72 @@ def denoise(acc, settings13, divide_by, normal, albedo, depth, material, nthread
     if rc != 0:
         raise RuntimeError(lib().hk_last_error().decode())
     return f32, rgb
+
+
+UPSCALE_DEFAULTS = {"mode": 1, "normal_power_log2": 5, "sigma_depth": 1.0, "demodulate": 1, "material_stop": 1}
+
+
+def _denoise_raw(p):
+    raw = np.array([p["iterations"], 0, p["normal_power_log2"], 0, p["demodulate"], p["material_stop"]], dtype=np.int32)
+    raw[1] = np.array([p["sigma_luminance"]], np.float32).view(np.int32)[0]
+    raw[3] = np.array([p["sigma_depth"]], np.float32).view(np.int32)[0]
+    return raw
+
+
+def upscale(acc, settings13, divide_by, low_guides, full_guides, hist=None, m2=None, prefilter=None, nthreads=4, **params):
+    """dr_accum_upscale on the host (device_upscale.hpp): the accumulator acc (int32[W, H, 3] as dr_accum_read returns it), the guides of
+    settings13 (low_guides) and of settings13 with element 11 = 1 (full_guides) as dicts with "normal", "albedo", "depth", "material" shaped like
+    dogeray_amd.Context.render_aov's (block mode reads neither: both may be None) -> (f32[H, W, 3], uint8[H, W, 3], no-tap mask bool[H, W]) in
+    dr_accum_present's layout.  hist / m2 as denoise(); prefilter: None, or a dict of dr_denoise_params fields (the rest default) -- the
+    denoiser's host passes run on the low grid first; params: the fields of dr_upscale_params (the rest default)."""
+    acc = np.ascontiguousarray(acc, dtype=np.int32)
+    W, H = acc.shape[0], acc.shape[1]
+    st = np.ascontiguousarray(settings13, dtype=np.float32)
+    p = dict(UPSCALE_DEFAULTS)
+    for k, v in params.items():
+        if k not in p:
+            raise TypeError("unknown upscale parameter %r" % k)
+        p[k] = v
+    raw = np.array([p["mode"], p["normal_power_log2"], 0, p["demodulate"], p["material_stop"]], dtype=np.int32)
+    raw[2] = np.array([p["sigma_depth"]], np.float32).view(np.int32)[0]
+    pre = None
+    if prefilter is not None:
+        d = dict(DENOISE_DEFAULTS)
+        for k, v in dict(prefilter).items():
+            if k not in d:
+                raise TypeError("unknown denoise parameter %r" % k)
+            d[k] = v
+        pre = _denoise_raw(d)
+    keep = []
+
+    def ptrs(g, shape):
+        if g is None:
+            return [None] * 4
+        out = []
+        for k, t in (("normal", np.float32), ("albedo", np.float32), ("depth", np.float32), ("material", np.int32)):
+            a = np.ascontiguousarray(g[k], dtype=t)
+            assert a.shape[:2] == shape, "guides are not the %d x %d pixel grid" % (shape[1], shape[0])
+            keep.append(a)
+            out.append(a.ctypes.data)
+        return out
+    div = int(st[11]) if np.isfinite(st[11]) and st[11] >= 1 else 1
+    low = ptrs(low_guides, (H // div // 8 * 8, W // div // 8 * 8))
+    full = ptrs(full_guides, (H // 8 * 8, W // 8 * 8))
+    f32 = np.zeros((H, W, 3), np.float32)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    notap = np.zeros((H, W), np.uint8)
+    if hist is not None:
+        hist = np.ascontiguousarray(hist, dtype=np.int32)
+        assert hist.shape == (W, H)
+    if m2 is not None:
+        m2 = np.ascontiguousarray(m2, dtype=np.uint64)
+        assert m2.shape == (W, H)
+    rc = lib().hk_upscale(acc.ctypes.data, W, H, int(divide_by), st.ctypes.data, *low, *full, raw.ctypes.data, pre.ctypes.data if pre is not None else None,
+                          f32.ctypes.data, rgb.ctypes.data, notap.ctypes.data, nthreads, hist.ctypes.data if hist is not None else None,
+                          m2.ctypes.data if m2 is not None else None)
+    if rc != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+    return f32, rgb, notap.astype(bool)
 
 
 def camera_block(settings13, W, H):
