@@ -1,0 +1,254 @@
+// The device context (struct dr_context: resident scene, options, accumulator, pipeline state) and what the context_*.cpp files share: the error
+// macros, the owning device buffer, the guide caches' key, the launch site, and the internal functions one file defines and another calls.
+//   context.cpp            create / destroy / upload / stripe / traversal / options / statistics
+//   context_render.cpp     per-launch constants, cost feedback, grazing certificate, the launches of dr_render_frame / dr_render_accumulate*
+//   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
+//   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
+//   context_probe.cpp      measurement probes and known-answer hooks
+// Host only, no kernels: kernels.hpp declares their launchers.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "kernels.hpp"
+#include "params_host.hpp"
+#include "scene_host.hpp"
+
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess) {                                                                \
+      dr::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                    \
+      return DR_ERR_DEVICE;                                                                \
+    }                                                                                      \
+  } while (0)
+
+// a call that returns a dr_status: anything but DR_OK is the caller's result
+#define DR_TRY(expr)                                                                       \
+  do {                                                                                     \
+    const int rc_ = (expr);                                                                \
+    if (rc_ != DR_OK) return rc_;                                                          \
+  } while (0)
+
+namespace dr {
+
+// An owned device allocation of n elements (PINNED: page-locked host memory instead); reads as its pointer.  A failed allocation leaves it null
+// with n = 0.  The destructor frees: whoever destroys it has synchronised the streams that use it.
+template <class T, bool PINNED = false>
+struct DevMem {
+  T* p = nullptr;
+  size_t n = 0;
+  DevMem() = default;
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  ~DevMem() { release(); }
+  operator T*() const { return p; }
+  void release() {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr; n = 0;
+  }
+  void swap(DevMem& o) { std::swap(p, o.p); std::swap(n, o.n); }
+  // room for `need` elements, growing only; the contents do not survive growing.  `stream` is the one whose queued work may still use the
+  // allocation that is too small: it is drained before that is freed
+  int grow(size_t need, hipStream_t stream) {
+    if (p && n >= need) return DR_OK;
+    if (p) { HIP_TRY(hipStreamSynchronize(stream)); release(); }
+    const hipError_t e = PINNED ? hipHostMalloc((void**)&p, need * sizeof(T), hipHostMallocDefault) : hipMalloc((void**)&p, need * sizeof(T));
+    if (e != hipSuccess) { p = nullptr; set_error(std::string("cannot allocate ") + std::to_string(need * sizeof(T)) + " bytes: " + hipGetErrorString(e)); return DR_ERR_DEVICE; }
+    n = need;
+    return DR_OK;
+  }
+  int alloc(size_t count) { release(); return grow(count ? count : 1, nullptr); }      // a fresh allocation of at least one element
+  int upload(const std::vector<T>& src) { DR_TRY(alloc(src.size())); return put(src.data(), src.size()); }
+  int put(const T* src, size_t count) { if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice)); return DR_OK; }
+  int get(T* dst, size_t count) const { if (count) HIP_TRY(hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost)); return DR_OK; }
+};
+
+// The key of a cached set of first-hit guides: the view's settings13, the frame size and the scene upload they were traced for
+struct GuideKey {
+  bool valid = false;
+  float st[13] = {0};
+  int W = 0, H = 0;
+  uint64_t gen = 0;
+  bool matches(const float* settings13, int w, int h, uint64_t scene_gen) const {
+    return valid && W == w && H == h && gen == scene_gen && memcmp(st, settings13, sizeof(st)) == 0;
+  }
+  void store(const float* settings13, int w, int h, uint64_t scene_gen) {
+    memcpy(st, settings13, sizeof(st));
+    W = w; H = h; gen = scene_gen; valid = true;
+  }
+};
+
+// Where a render launch goes and what it may touch on the way
+struct LaunchSite {
+  hipStream_t stream;       // the launch, the tile counters' memset, the certificate mask and the feedback kernels
+  bool hold_order;          // use the stored tile order as it is, record no costs, compute no mask (a pipelined launch beside another one)
+  bool lean;                // option pipe_lean: the launch counts 0 for coop_tiles_per_wave
+};
+
+constexpr int TILE_COUNTERS = 1024;
+
+}  // namespace dr
+
+struct dr_context {
+  template <class T> using DevMem = dr::DevMem<T>;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // dr_render_accumulate_async: two batches may be in flight, each with its own pair of events
+  hipEvent_t pev0[2] = {nullptr, nullptr}, pev1[2] = {nullptr, nullptr};
+  bool pending[2] = {false, false}; uint64_t pending_frames[2] = {0, 0}, pending_samples[2] = {0, 0}; int pending_next = 0;
+  // resident scene
+  DevMem<dr::DevUnit> walk; size_t walk_bytes = 0;
+  DevMem<dr::DevUnit> wide; size_t wide_bytes = 0; int wide_depth = 0, wide_nodes = 0; float wide_pmax = 0; dr::WideMu wide_mu = {0, 0, 0}; int wide_own_bounds = 0;   // null: scene not representable (threaded walk is used)
+  int wide_tree = 2;        // structure of the wide walk's tree: 2 binned SAH with small triangles entered by their own bounds (default), 1 binned SAH over the reference's leaf boxes, 0 the reference's topology collapsed
+  DevMem<dr::DevPair> pairs;
+  DevMem<dr::DevPrim> prims;
+  DevMem<dr::DevShade> shade;
+  DevMem<dr::DevTex> tex;
+  DevMem<uint32_t> texels;
+  int n_prims = 0, n_tex = 0, tree_depth = 0;
+  std::vector<int> slot_to_orig;
+  DevMem<int32_t> slot_to_orig_dev;        // the same map on the device: uploaded by the first dr_render_aov after a scene upload
+  // dr_render_aov with host pointers: the channels are written here, then downloaded
+  DevMem<uint8_t> aov_staging;
+  // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
+  // guides' key (settings13, W, H, scene generation), and the staging of host outputs
+  DevMem<float> dn_planes;
+  dr::GuideKey dn_key;
+  DevMem<uint8_t> dn_staging;
+  // dr_accum_upscale: the full-resolution guides (one allocation made by the first guided call: guide 4n | scratch 4n | albedo 3n | material n |
+  // gz n floats over the full pixel grid), their key (settings13 with element 11 = 1, W, H, scene generation) and the AOV passes of the last call
+  DevMem<float> up_planes;
+  dr::GuideKey up_key;
+  int up_passes = 0;
+  uint64_t scene_gen = 0;                  // scene uploads so far: a guide cache of an earlier scene does not match
+  // dr_accum_reproject: the second accumulator of the pair (swapped with `accum` by every reprojection), the two history planes (hist: the
+  // current one, null until the first reprojection and after dr_accum_reset), the guide planes of two views (t n | normal 3n | material n
+  // floats each; set rp_cur holds the cached `to` view, keyed like the denoiser's guides), the class counts and the AOV passes of the last call
+  DevMem<int32_t> accum2;
+  DevMem<int32_t> hist_buf[2];
+  int32_t* hist = nullptr; int hist_cur = 0;
+  DevMem<float> rp_planes[2];
+  dr::GuideKey rp_key; int rp_cur = 0;
+  DevMem<unsigned long long> rp_counts;
+  int rp_passes = 0;
+  // the second-moment plane (option "moments", read by dr_accum_reset): m2 is the current plane (null: none), one of m2_buf -- the second one
+  // appears with the first reprojection, as for the history; the allocations outlive resets of the same size.  dr_accum_error's counts and the
+  // staging of its host output
+  int moments_opt = 0;                     // option: dr_accum_reset gives the accumulator a plane
+  int denoise_variance = 0;                // option: the denoiser's variance pre-pass takes the temporal variance from the plane (n >= 4)
+  DevMem<unsigned long long> m2_buf[2];
+  unsigned long long* m2 = nullptr; int m2_cur = 0;
+  DevMem<unsigned long long> err_counts;
+  DevMem<float> err_staging;
+  int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
+  // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
+  // computed on the launch's stream by launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload and cert_factor
+  int camera_cert = 1;                     // option: camera rays of tiles the certificate clears carry the certified margin (0: every ray the scene's)
+  int cert_factor = 40;                    // option: the certified |a^| in units of hit_tri's 1e-4 cut-off (a_star = cert_factor * 1e-4)
+  DevMem<uint32_t> cert_mask;
+  bool cert_valid = false;                 // cert_key's mask is computed (or known to be unusable: cert_ok false)
+  bool cert_ok = false;
+  float cert_key[21] = {0};
+  float cert_seen[21] = {0};               // the key of the last single-frame launch that found no mask
+  float cert_k = 1;                        // the certified margin's factor (1e-4 / a_star, rounded up)
+  int cert_tiles = 0;                      // tiles of the keyed launch
+  // frame + accumulator
+  DevMem<int32_t> frame;
+  DevMem<int32_t> accum; int accW = 0, accH = 0;
+  DevMem<uint8_t> present;
+  // multi-GPU gather: two packed copies of this context's stripe (double buffer), sized for the accumulator
+  DevMem<int32_t> packed[2];
+  DevMem<unsigned long long> counters;
+  DevMem<unsigned> tile_counters; int tile_cursor = 0; int num_cus = 256;
+  // cost feedback (persistent kernel): per-pixel cost of the last frame, per-tile cost, tile order
+  DevMem<unsigned> pixel_cost, tile_cost; DevMem<int> tile_order, region_start;
+  int order_capacity = 0;          // tiles the three buffers are sized for
+  bool order_valid = false;        // tile_order was computed for `order_key`
+  int order_age = 0;               // launches since the view (order_key) changed
+  int order_follows_camera = 1;    // a view with the same frame geometry but other settings starts from the previous view's tile order
+  int feedback_every = 8;          // ... the order is recomputed after the first two of them and then after every feedback_every-th
+  float order_key[18] = {0};       // settings13 + W, H, stripe, tile grid of the frame the order belongs to
+  int feedback = 1;
+  int stripe_mod = 1, stripe_rem = 0;
+  int traversal = DR_TRAVERSAL_WIDE;
+  int count = 0;
+  // tunables (dr_context_set_option / DOGERAY_OPTIONS; the table in context.cpp names them)
+  int kernel = DR_KERNEL_PERSISTENT;
+  int occupancy = 6;        // waves per SIMD the kernel is built and launched for (persistent: 4, 5, or 6 = six for the lean wide build and five for the others; tile kernel: 4 or 6)
+  int schedule = 0;         // persistent kernel: 0 = shade / refill below 32 walking lanes, leaf steps for 20 lanes, two steps per iteration (tuned); 1 = 32 / 8 / 1; 2 = 48 / leaves on the spot / 1
+  int xcd_regions = 1;      // persistent kernel: one tile queue per XCD (image bands), with stealing
+  int heavy_factor = 1;     // tile order: tiles costlier than this x the mean start first, the rest keep their natural order (0 = all natural, -1 = all by cost)
+  int coop_steps = 2;       // persistent kernel, drain phase: rays older than this many steps are shared with idle lanes / finished cooperatively (0 = off)
+  int coop_tiles_per_wave = 32;   // wide walk: launches with fewer tiles per wave than this run the build with the work-sharing drain
+  int coop_lanes = 8;       // ... in waves with at most this many lanes still walking
+  int split_parts = 4;      // short launches: the tiles with last frame's longest pixels are handed out in this many parts (1, 2, 4, 8), the rest of each wave helps
+  int split_waves = 12;     // ... as many of them as give this many percent of the waves a part to start with
+  int split_steps = 400;    // ... tiles whose longest pixel took at least this many node steps (multiple of 16)
+  int short_one_queue = 1;  // short launches use one tile queue instead of one per XCD
+  int coop_rounds = 2;      // work sharing: hand-over rounds per loop iteration
+  int reserve_cus = 0;      // persistent kernel: launch workgroups for this many CUs fewer than the device has (room for a gather's copy / RCCL kernels beside the rendering)
+  int wave_log_on = 0;      // persistent kernel writes begin / queue-empty / end stamps of every wave (dr_stats_wave_log)
+  DevMem<unsigned long long> wave_log; int wave_log_waves = 0;
+  int batch_frames = 32;    // persistent kernel: at most this many frames per launch in dr_render_accumulate
+  float cur_settings[13] = {0};
+  dr_stats stats;
+  // pipelined single frames (dr_pipeline_*): a second render stream, a stream that folds finished frames into the accumulator in
+  // frame order, and PIPE_DEPTH frame buffers / present buffers that rotate
+  static constexpr int PIPE_STREAMS = 4;           // render streams (stream itself is number 0); option pipe_streams uses 2 .. 4 of them
+  static constexpr int PIPE_DEPTH = PIPE_STREAMS + 1;
+  int pipe_streams = 2;     // render streams the pipeline alternates between
+  int pipe_lean = 0;        // pipelined launches run the lean build with one queue per XCD instead of the work-sharing build (their tails overlap other frames)
+  hipStream_t pipe_stream[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr}, acc_stream = nullptr;      // pipe_stream[0] = stream
+  // a slot = one GROUP of frames in flight: frames submitted one after the other (same view, seeds in arithmetic progression) share one launch -- each
+  // rendered into a buffer of its own -- and are added to the accumulator and presented one by one, in ticket order (option pipe_group; 1 = a launch per frame)
+  static constexpr int PIPE_GROUP_MAX = 16;
+  struct PipeSlot {
+    DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;         // cap_frames buffers of elems_each int32, one after the other
+    int rect[6] = {-1, 0, 0, 0, 0, 0};             // W, H, gx, gy, stripe mod, stripe rem the buffers were last rendered with (their margins are 0)
+    hipEvent_t rendered = nullptr;                 // end of the group's launch
+    hipEvent_t added[PIPE_GROUP_MAX] = {nullptr};  // frame f of the group has been added (and presented)
+    DevMem<uint8_t> rgb_dev[PIPE_GROUP_MAX]; dr::DevMem<uint8_t, true> rgb_host[PIPE_GROUP_MAX];      // frame f's present: on the device, and its pinned copy
+    int div[PIPE_GROUP_MAX] = {0};                 // divisor frame f was presented with (0: not presented)
+    bool fwaited[PIPE_GROUP_MAX] = {false};        // dr_pipeline_wait has returned for frame f
+    uint64_t first = 0; int count = 0;             // tickets [first, first + count)
+    bool drained = true;                           // the host has waited for the group's last add: its buffers may be reused at once
+  };
+  PipeSlot pipe_slot[PIPE_DEPTH];
+  uint64_t pipe_groups = 0;                        // groups launched so far (slot = group % (streams + 1), render stream = group % streams)
+  int pipe_group = 8;                              // most frames per group
+  struct PipePending { float st[13]; int W, H; float bg; uint64_t seed; int div; };
+  std::vector<PipePending> pipe_pending;           // submitted, not launched yet: tickets [pipe_next - size, pipe_next)
+  uint64_t pipe_next = 0;                          // ticket of the next frame
+  hipEvent_t pipe_last[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr};    // end of the newest launch on each render stream
+  bool pipe_last_set[PIPE_STREAMS] = {false, false, false, false};
+  hipEvent_t pipe_barrier = nullptr; bool pipe_barrier_set = false;      // end of the newest tile-order refresh: later launches read that order
+  hipEvent_t pipe_sync = nullptr;                  // orders the pipeline after earlier work on `stream`
+  bool pipe_dirty = false;                         // frames have gone through the pipeline since the last join
+  bool pipe_ready = false;                         // every stream and event of the pipeline exists (pipeline_setup)
+
+  dr::LaunchSite own_site() const { return {stream, false, false}; }      // an ordinary launch: on `stream`, with cost feedback
+  ~dr_context();            // context.cpp: drains every stream, destroys events and streams; the buffers then free themselves
+};
+
+namespace dr {
+
+// the traversal a launch really uses: the wide walk needs its structure (scenes it cannot represent walk the threaded links)
+inline int traversal_of(const dr_context* c) { return (c->traversal == DR_TRAVERSAL_WIDE && !c->wide) ? DR_TRAVERSAL_THREADED : c->traversal; }
+inline bool uses_persistent(const dr_context* c) { return c->kernel == DR_KERNEL_PERSISTENT && traversal_of(c) != DR_TRAVERSAL_ORDERED; }
+
+// context_render.cpp
+void fill_scene(const dr_context* c, RenderParams& P);      // the resident scene's buffers
+int make_params(dr_context* c, const LaunchSite& site, const float* st, int W, int H, float background, uint64_t seed, RenderParams& P, int batch_hint = 1);
+PersistentCfg persistent_cfg(const dr_context* c, const LaunchSite& site);
+void enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in);
+// context_pipeline.cpp
+int join_pipeline(dr_context* c);
+int pipeline_flush(dr_context* c);
+
+}  // namespace dr

@@ -1,0 +1,240 @@
+// Measurement probes (dr_context_probe_*) and the known-answer hooks of single device functions (dr_kat_*).
+#include "context.hpp"
+
+using namespace dr;
+
+extern "C" {
+
+int dr_context_probe_frame_add(dr_context* c, int iters, double* plain_ms, double* fused_ms) {
+  if (!c || iters < 1 || !plain_ms || !fused_ms) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->accum) { set_error("no accumulator: call dr_accum_reset(W, H) first"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
+  const size_t npix = (size_t)c->accW * c->accH, elems = npix * 3;
+  DR_TRY(c->frame.grow(elems, c->stream));
+  HIP_TRY(hipMemsetAsync(c->frame, 0, elems * sizeof(int32_t), c->stream));      // a black frame: neither the sums nor the plane change
+  for (int k = 0; k < 2 * iters; k++) {
+    const bool fused = k >= iters;
+    float ms = 0;
+    if (!fused || c->m2) {
+      HIP_TRY(hipEventRecord(c->ev0, c->stream));
+      if (fused) launch_moments_add(c->stream, c->accum, c->frame, c->m2, npix);
+      else launch_frame_add(c->stream, c->accum, c->frame, elems);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(c->ev1, c->stream));
+      HIP_TRY(hipEventSynchronize(c->ev1));
+      HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    }
+    (fused ? fused_ms : plain_ms)[k % iters] = (double)ms;
+  }
+  return DR_OK;
+}
+
+int dr_context_probe_gather(dr_context* c, uint32_t hot_records, int iters, double* records_per_s) {
+  if (!c || !records_per_s || iters < 1) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->wide) { set_error("no wide walk resident"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(c, P);
+  const unsigned total = (unsigned)(c->wide_bytes / 64);
+  const unsigned nrec = (hot_records == 0 || hot_records > total) ? total : hot_records;
+  DevMem<unsigned> out;
+  DR_TRY(out.alloc(1));
+  const int blocks = c->num_cus * 5;
+  launch_gather_probe(c->stream, P, blocks, nrec, iters / 8 + 1, out.p);      // warm-up
+  HIP_TRY(hipEventRecord(c->ev0, c->stream));
+  launch_gather_probe(c->stream, P, blocks, nrec, iters, out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev1, c->stream));
+  HIP_TRY(hipEventSynchronize(c->ev1));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  *records_per_s = (double)blocks * 256.0 * (double)iters / ((double)ms * 1e-3);
+  return DR_OK;
+}
+
+int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, int frames, int variant,
+                           double* rays_per_s, uint64_t* n_rays, uint64_t* mismatches) {
+  if (!c || !settings13 || !rays_per_s || !n_rays || !mismatches || frames < 1 || variant < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the trace probe needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(dr_accum_reset(c, W, H));
+  // 1. the rays of ONE frame, as a per-bounce wavefront would hold them: the counting build writes every ray a path starts to slot bounce * pixels + pixel (tile
+  // order); empty slots (paths that had ended) are squeezed out on the host; `frames` copies of the list make the probe's launch long enough to time
+  RenderParams Pv;
+  DR_TRY(make_params(c, c->own_site(), settings13, W, H, background, frame_seed, Pv, 1));
+  const size_t npix = (size_t)Pv.ncols * Pv.gy * 64;
+  const size_t slots = npix * (size_t)(Pv.max_depth > 0 ? Pv.max_depth : 1);
+  if (slots * (size_t)frames > 0x7fffffffull) { set_error("too many rays"); return DR_ERR_INVALID; }
+  DevMem<float> raw; DevMem<float> log; DevMem<unsigned> cursor; DevMem<unsigned> out, ref;
+  DR_TRY(raw.alloc(slots * 8));
+  HIP_TRY(hipMemset(raw.p, 0, slots * 8 * sizeof(float)));
+  const bool was_counting = c->count;
+  unsigned long long ctl[3] = {0ull, (unsigned long long)(uintptr_t)raw.p, (unsigned long long)slots};      // statistics words 40-42: rays logged, the log, its room
+  HIP_TRY(hipMemcpy(c->counters + 40, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+  c->count = true;
+  const int rc = dr_render_accumulate(c, settings13, W, H, background, frame_seed, 1000003, 1);
+  c->count = was_counting;
+  const unsigned long long off[2] = {0ull, 0ull};
+  HIP_TRY(hipMemcpy(c->counters + 41, off, sizeof(off), hipMemcpyHostToDevice));
+  if (rc != DR_OK) return rc;
+  std::vector<float> host(slots * 8), packed;
+  DR_TRY(raw.get(host.data(), host.size()));
+  packed.reserve(host.size() / 2);
+  for (size_t k = 0; k < slots; k++) {
+    const float* r = &host[k * 8];
+    if (r[4] != 0.0f || r[5] != 0.0f || r[6] != 0.0f || r[4] != r[4]) packed.insert(packed.end(), r, r + 8);      // a direction was written
+  }
+  const size_t per_frame = packed.size() / 8;
+  const unsigned n = (unsigned)(per_frame * (size_t)frames);
+  *n_rays = per_frame;
+  if (n == 0) { *rays_per_s = 0; *mismatches = 0; return DR_OK; }
+  DR_TRY(log.alloc((size_t)n * 8));
+  for (int f = 0; f < frames; f++) HIP_TRY(hipMemcpy(log.p + (size_t)f * per_frame * 8, packed.data(), per_frame * 8 * sizeof(float), hipMemcpyHostToDevice));
+  std::vector<float>().swap(host);
+  DR_TRY(cursor.alloc(1)); DR_TRY(out.alloc((size_t)n * 2)); DR_TRY(ref.alloc((size_t)n * 2));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(c, P);
+  // 2. the probe, timed (one warm-up, then the best of three)
+  float best = 1e30f;
+  for (int rep = 0; rep < 4; rep++) {
+    HIP_TRY(hipMemsetAsync(cursor.p, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    launch_trace_probe(c->stream, P, c->num_cus, variant, log.p, n, cursor.p, out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->ev1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (rep > 0 && ms < best) best = ms;
+  }
+  *rays_per_s = (double)n / ((double)best * 1e-3);
+  // 3. every result against the one-ray-per-lane walk
+  launch_trace_probe(c->stream, P, c->num_cus, 0, log.p, n, cursor.p, ref.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<unsigned> a((size_t)n * 2), b((size_t)n * 2);
+  DR_TRY(out.get(a.data(), a.size())); DR_TRY(ref.get(b.data(), b.size()));
+  uint64_t bad = 0;
+  for (size_t i = 0; i < a.size(); i++) bad += a[i] != b[i];
+  *mismatches = bad;
+  return DR_OK;
+}
+
+// ---- KAT hooks
+#define KAT_PRE(n)                                                        \
+  if (!c || (n) < 0) { set_error("bad argument"); return DR_ERR_INVALID; } \
+  HIP_TRY(hipSetDevice(c->device));                                        \
+  if ((n) == 0) return DR_OK
+
+int dr_kat_rng(dr_context* c, uint64_t seed, int n, double* out) {
+  KAT_PRE(n);
+  DevMem<double> d; DR_TRY(d.alloc((size_t)n));
+  launch_kat_rng(c->stream, seed, n, d.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return d.get(out, (size_t)n);
+}
+
+int dr_kat_aabb(dr_context* c, int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist) {
+  KAT_PRE(n);
+  DevMem<float> bo, bd, bmn, bmx, bdist; DevMem<int32_t> bhit;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bmn.alloc(m)); DR_TRY(bmx.alloc(m)); DR_TRY(bdist.alloc((size_t)n)); DR_TRY(bhit.alloc((size_t)n));
+  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bmn.put(mn, m)); DR_TRY(bmx.put(mx, m));
+  launch_kat_aabb(c->stream, n, bo.p, bd.p, bmn.p, bmx.p, bhit.p, bdist.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(bhit.get(hit, (size_t)n));
+  return bdist.get(dist, (size_t)n);
+}
+
+int dr_kat_node_planes(dr_context* c, int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt) {
+  KAT_PRE(n);
+  DevMem<uint32_t> bw;
+  DevMem<float> ba, bb, b1, b2;
+  DR_TRY(bw.alloc((size_t)n)); DR_TRY(ba.alloc((size_t)n)); DR_TRY(bb.alloc((size_t)n)); DR_TRY(b1.alloc((size_t)n * 4)); DR_TRY(b2.alloc((size_t)n * 4));
+  DR_TRY(bw.put(w, (size_t)n)); DR_TRY(ba.put(a, (size_t)n)); DR_TRY(bb.put(b, (size_t)n));
+  launch_kat_node_planes(c->stream, n, bw.p, ba.p, bb.p, b1.p, b2.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(b1.get(t_mix, (size_t)n * 4));
+  return b2.get(t_cvt, (size_t)n * 4);
+}
+
+int dr_kat_tri(dr_context* c, int n, const float* o, const float* d, const float* v0, const float* v1, const float* v2, float* t) {
+  KAT_PRE(n);
+  DevMem<float> bo, bd, b0, b1, b2, bt;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(b0.alloc(m)); DR_TRY(b1.alloc(m)); DR_TRY(b2.alloc(m)); DR_TRY(bt.alloc((size_t)n));
+  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(b0.put(v0, m)); DR_TRY(b1.put(v1, m)); DR_TRY(b2.put(v2, m));
+  launch_kat_tri(c->stream, n, bo.p, bd.p, b0.p, b1.p, b2.p, bt.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bt.get(t, (size_t)n);
+}
+
+int dr_kat_sphere(dr_context* c, int n, const float* o, const float* d, const float* centre, const float* radius, float* t) {
+  KAT_PRE(n);
+  DevMem<float> bo, bd, bc, br, bt;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bc.alloc(m)); DR_TRY(br.alloc((size_t)n)); DR_TRY(bt.alloc((size_t)n));
+  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bc.put(centre, m)); DR_TRY(br.put(radius, (size_t)n));
+  launch_kat_sphere(c->stream, n, bo.p, bd.p, bc.p, br.p, bt.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bt.get(t, (size_t)n);
+}
+
+int dr_kat_optics(dr_context* c, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* schlick) {
+  KAT_PRE(n);
+  DevMem<float> bv, bn, be, b1, b2, b3;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bv.alloc(m)); DR_TRY(bn.alloc(m)); DR_TRY(be.alloc((size_t)n)); DR_TRY(b1.alloc(m)); DR_TRY(b2.alloc(m)); DR_TRY(b3.alloc((size_t)n));
+  DR_TRY(bv.put(v, m)); DR_TRY(bn.put(nrm, m)); DR_TRY(be.put(eta, (size_t)n));
+  launch_kat_optics(c->stream, n, bv.p, bn.p, be.p, b1.p, b2.p, b3.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(b1.get(refl, m)); DR_TRY(b2.get(refr, m));
+  return b3.get(schlick, (size_t)n);
+}
+
+int dr_kat_normal(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, float* normal, float* texco) {
+  KAT_PRE(n);
+  if (!c->walk || !object_index || !o || !d || !t || !normal || !texco) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
+  std::vector<int32_t> slot_of((size_t)c->n_prims, -1), slots((size_t)n);
+  for (int sidx = 0; sidx < c->n_prims; sidx++) slot_of[(size_t)c->slot_to_orig[(size_t)sidx]] = sidx;
+  for (int i = 0; i < n; i++) {
+    if (object_index[i] < 0 || object_index[i] >= c->n_prims) { set_error("object index out of range"); return DR_ERR_INVALID; }
+    slots[(size_t)i] = slot_of[(size_t)object_index[i]];
+  }
+  DevMem<int32_t> bs; DevMem<float> bo, bd, bt, bn, bc;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bs.alloc((size_t)n)); DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bt.alloc((size_t)n)); DR_TRY(bn.alloc(m)); DR_TRY(bc.alloc(m));
+  DR_TRY(bs.put(slots.data(), (size_t)n)); DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bt.put(t, (size_t)n));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.prims = c->prims; P.shade = c->shade;
+  launch_kat_normal(c->stream, P, n, bs.p, bo.p, bd.p, bt.p, bn.p, bc.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(bn.get(normal, m));
+  return bc.get(texco, m);
+}
+
+int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits) {
+  KAT_PRE(n);
+  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+  DevMem<float> bo, bd, bt; DevMem<int32_t> bs, bv;
+  size_t m = (size_t)n * 3;
+  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bt.alloc((size_t)n)); DR_TRY(bs.alloc((size_t)n)); DR_TRY(bv.alloc((size_t)n));
+  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(c, P);
+  launch_kat_hit(c->stream, P, traversal_of(c), n, bo.p, bd.p, bt.p, bs.p, bv.p);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(bt.get(t, (size_t)n));
+  if (visits) DR_TRY(bv.get(visits, (size_t)n));
+  std::vector<int32_t> slots((size_t)n);
+  DR_TRY(bs.get(slots.data(), (size_t)n));
+  for (int i = 0; i < n; i++) idx[i] = slots[(size_t)i] >= 0 ? c->slot_to_orig[(size_t)slots[(size_t)i]] : 0;   // hit() returns index 0 on a miss (K:507)
+  return DR_OK;
+}
+
+}  // extern "C"

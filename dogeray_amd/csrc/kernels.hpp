@@ -7,7 +7,7 @@
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
 //   kernels_moments.hip       the second-moment plane: the fused frame add and the per-pixel noise estimate (option "moments", dr_accum_error)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
-// context.cpp (host only: resident scene, options, the C ABI) calls these and never sees a kernel.
+// context.cpp and the context_*.cpp files (host only: resident scene, options, the C ABI) call these and never see a kernel.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>

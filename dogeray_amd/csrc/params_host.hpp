@@ -1,6 +1,6 @@
 // settings[13] -> the per-launch constants of RenderParams that do not depend on the device: the camera block of Kernel
 // (kernel.cu K:1016-1052, identical for every pixel, so evaluated once on the host with the reference's float / double promotions),
-// the sample scale, the block grid and the stripe.  Host only; shared by context.cpp and the host build of the kernel arithmetic
+// the sample scale, the block grid and the stripe.  Host only; shared by the context_*.cpp files and the host build of the kernel arithmetic
 // (tools/host_kernel.cpp).
 #pragma once
 #include <cmath>

@@ -331,11 +331,14 @@ def test_rtsb_round_trip(dr, synth, tmp_path):
 
 
 def test_every_option_is_documented_in_the_header():
-    """Every name dr_context_set_option / dr_context_get_option accepts (csrc/context.cpp) appears, quoted, in include/dogeray_amd.h."""
+    """Every name dr_context_set_option / dr_context_get_option accepts (csrc/context.cpp: the option table, the setter's explicit cases and the
+    getter's read-only names) appears, quoted, in include/dogeray_amd.h."""
     import re
     src = open(os.path.join(ROOT, "dogeray_amd", "csrc", "context.cpp")).read()
     hdr = open(os.path.join(ROOT, "include", "dogeray_amd.h")).read()
-    names = set(re.findall(r'name == "(\w+)"', src)) | set(re.findall(r'\bn == "(\w+)"', src))
-    assert len(names) > 20
+    table = set(re.findall(r'\{"(\w+)", &dr_context::', src))
+    assert len(table) == 28
+    names = table | set(re.findall(r'name == "(\w+)"', src)) | set(re.findall(r'\bn == "(\w+)"', src))
+    assert len(names) == 36              # 28 settable, 8 read-only
     missing = sorted(n for n in names if '"%s"' % n not in hdr)
     assert not missing, missing
