@@ -24,6 +24,7 @@ TRAVERSAL_ORDERED = 1
 TRAVERSAL_WIDE = 2          # the default: 4-way tree over the reference's leaves
 KERNEL_TILE = 0
 KERNEL_PERSISTENT = 1
+MAX_REGIONS = 8             # tile queues of the persistent kernel (csrc/kernels.hpp)
 ERR_INVALID, ERR_IO, ERR_PARSE, ERR_SCENE, ERR_DEVICE, ERR_NOMEM = -1, -2, -3, -4, -5, -6      # enum dr_status
 
 
@@ -197,6 +198,8 @@ _API = [
     ("dr_kat_optics", C.c_int, [_VP, C.c_int] + [_VP] * 6),
     ("dr_kat_hit", C.c_int, [_VP, C.c_int] + [_VP] * 5),
     ("dr_kat_normal", C.c_int, [_VP, C.c_int] + [_VP] * 6),
+    ("dr_stats_tile_order", C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t), _VP, _VP]),
+    ("dr_kat_tile_feedback", C.c_int, [_VP] + [C.c_int] * 5 + [_VP] * 4),
 ]
 API_SYMBOLS = [a[0] for a in _API]
 
@@ -587,15 +590,36 @@ class Context:
         _check(lib().dr_stats_wave_log(self._h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), max_waves, C.byref(n)))
         return out[:n.value]
 
-    def pixel_cost(self, W, H):
-        """(W, H) uint32 node steps per pixel of the last frame the persistent kernel recorded (empty array: none yet)."""
-        gx, gy = (W + 7) // 8, (H + 7) // 8
+    def pixel_cost(self, W, H, div=1, raw=False):
+        """uint32 node steps per pixel of the last frame the persistent kernel recorded, over the renderer's grid of whole tiles -- gx = W // div // 8
+        block columns of gy = H // div // 8 tiles (div: the preview divisor, settings13[11]; an unstriped context): shape (gx * 8, gy * 8), or with
+        raw=True the flat gx * gy * 64 words as the feedback kernels read them (tile * 64 + lane).  An empty array: none recorded yet."""
+        gx, gy = W // div // 8, H // div // 8
         out = np.zeros(gx * gy * 64, dtype=np.uint32)
         n = C.c_size_t()
-        _check(lib().dr_stats_pixel_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint)), out.size, C.byref(n)))
-        if n.value < out.size:
-            return np.zeros((0, 0), dtype=np.uint32)
-        return out.reshape(gx, gy, 8, 8).transpose(0, 2, 1, 3).reshape(gx * 8, gy * 8)[:W, :H]
+        if out.size:
+            _check(lib().dr_stats_pixel_cost(self._h, out.ctypes.data_as(C.POINTER(C.c_uint)), out.size, C.byref(n)))
+        if n.value < out.size or out.size == 0:
+            return np.zeros(0 if raw else (0, 0), dtype=np.uint32)
+        if raw:
+            return out
+        return out.reshape(gx, gy, 8, 8).transpose(0, 2, 1, 3).reshape(gx * 8, gy * 8)
+
+    def tile_order(self):
+        """The live tile order (dr_stats_tile_order): None when no order is valid, else a dict with order int32[ntiles], region_start int32[17]
+        and the last feedback pass's ntiles, regions, heavy_factor, split_steps, split_limit."""
+        n = C.c_size_t()
+        rs = np.zeros(2 * MAX_REGIONS + 1, dtype=np.int32)
+        args = np.zeros(5, dtype=np.int32)
+        _check(lib().dr_stats_tile_order(self._h, None, 0, C.byref(n), _p(rs), _p(args)))
+        if n.value == 0:
+            return None
+        order = np.zeros(n.value, dtype=np.int32)
+        _check(lib().dr_stats_tile_order(self._h, _p(order), order.size, C.byref(n), _p(rs), _p(args)))
+        if n.value != order.size:
+            return None
+        return dict(order=order, region_start=rs, ntiles=int(args[0]), regions=int(args[1]), heavy_factor=int(args[2]), split_steps=int(args[3]),
+                    split_limit=int(args[4]))
 
     def probe_trace(self, settings13, W, H, background, frame_seed, frames=2, variant=2):
         """Trace-only probe (dr_context_probe_trace): (rays per second, rays, results differing from the one-ray-per-lane walk)."""
@@ -884,6 +908,19 @@ class Context:
         vis = np.zeros(n, dtype=np.int32) if want_visits else None
         _check(lib().dr_kat_hit(self._h, n, _p(o), _p(d), _p(t), _p(idx), _p(vis) if want_visits else None))
         return (t, idx, vis) if want_visits else (t, idx)
+
+    def kat_tile_feedback(self, pixel_cost, regions, heavy_factor, split_steps, split_limit, ntiles=None):
+        """The feedback kernels on a flat uint32 plane of ntiles * 64 pixel costs (dr_kat_tile_feedback): (tile_cost uint32[ntiles],
+        order int32[ntiles], region_start int32[17]); entries the kernels did not write are -1."""
+        pc = np.ascontiguousarray(pixel_cost, dtype=np.uint32).ravel()
+        n = pc.size // 64 if ntiles is None else int(ntiles)
+        if n >= 1 and pc.size < n * 64:
+            raise ValueError("pixel_cost holds fewer than ntiles * 64 words")
+        tc = np.zeros(max(n, 0), dtype=np.uint32)
+        order = np.zeros(max(n, 0), dtype=np.int32)
+        rs = np.zeros(2 * MAX_REGIONS + 1, dtype=np.int32)
+        _check(lib().dr_kat_tile_feedback(self._h, n, int(regions), int(heavy_factor), int(split_steps), int(split_limit), _p(pc), _p(tc), _p(order), _p(rs)))
+        return tc, order, rs
 
 
 class Group:

@@ -321,4 +321,19 @@ int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n
   return DR_OK;
 }
 
+int dr_stats_tile_order(dr_context* c, int* order, size_t capacity, size_t* n, int* region_start, int* args) {
+  if (!c || !n || !region_start || !args || (capacity > 0 && !order)) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n = 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!c->order_valid || !c->tile_order || !c->region_start) return DR_OK;
+  for (int k = 0; k < 5; k++) args[k] = c->order_args[k];
+  const size_t tiles = (size_t)c->order_args[0];
+  HIP_TRY(hipMemcpy(region_start, c->region_start, (2 * MAX_REGIONS + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  const size_t m = tiles < capacity ? tiles : capacity;
+  if (m > 0) HIP_TRY(hipMemcpy(order, c->tile_order, m * sizeof(int), hipMemcpyDeviceToHost));
+  *n = tiles;
+  return DR_OK;
+}
+
 }  // extern "C"

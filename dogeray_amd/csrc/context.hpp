@@ -174,6 +174,7 @@ struct dr_context {
   int order_follows_camera = 1;    // a view with the same frame geometry but other settings starts from the previous view's tile order
   int feedback_every = 8;          // ... the order is recomputed after the first two of them and then after every feedback_every-th
   float order_key[18] = {0};       // settings13 + W, H, stripe, tile grid of the frame the order belongs to
+  int order_args[5] = {0, 0, 0, 0, 0};      // the last launch_tile_feedback enqueued: tiles, regions, heavy_factor, split_steps, split_limit (dr_stats_tile_order)
   int feedback = 1;
   int stripe_mod = 1, stripe_rem = 0;
   int traversal = DR_TRAVERSAL_WIDE;

@@ -237,4 +237,26 @@ int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, i
   return DR_OK;
 }
 
+int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_factor, int split_steps, int split_limit, const unsigned* pixel_cost,
+                         unsigned* tile_cost, int* order, int* region_start) {
+  if (!c || !pixel_cost || !tile_cost || !order || !region_start) { set_error("null argument"); return DR_ERR_INVALID; }
+  // what make_params never launches: the order kernel relies on a 64-tile group touching at most two regions
+  if (ntiles < 1) { set_error("tile feedback: ntiles must be at least 1"); return DR_ERR_INVALID; }
+  if (regions != 1 && regions != MAX_REGIONS) { set_error("tile feedback: regions must be 1 or 8"); return DR_ERR_INVALID; }
+  if (regions == MAX_REGIONS && ntiles < 64 * MAX_REGIONS) { set_error("tile feedback: 8 regions need at least 512 tiles (regions of 64 tiles or more)"); return DR_ERR_INVALID; }
+  if (split_limit < 0) { set_error("tile feedback: split_limit must not be negative"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)ntiles, words = 2 * MAX_REGIONS + 1;
+  DevMem<unsigned> bp, bc; DevMem<int> bo, br;
+  DR_TRY(bp.alloc(n * 64)); DR_TRY(bc.alloc(n)); DR_TRY(bo.alloc(n)); DR_TRY(br.alloc(words));
+  DR_TRY(bp.put(pixel_cost, n * 64));
+  HIP_TRY(hipMemsetAsync(bo.p, 0xff, n * sizeof(int), c->stream));             // an entry the kernel does not write reads as -1
+  HIP_TRY(hipMemsetAsync(br.p, 0xff, words * sizeof(int), c->stream));
+  launch_tile_feedback(c->stream, bp.p, bc.p, bo.p, br.p, ntiles, regions, heavy_factor, split_steps, split_limit);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(bc.get(tile_cost, n)); DR_TRY(bo.get(order, n));
+  return br.get(region_start, words);
+}
+
 }  // extern "C"

@@ -138,8 +138,9 @@ void enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_
     // (the two kernels take 75 us: nothing for a launch of 32 frames, 6 % of a launch of one)
     if (pcost && !order) c->order_age = 0;
     if (pcost && (c->order_age < 2 || c->order_age % c->feedback_every == 0)) {
-      launch_tile_feedback(site.stream, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start, tiles, P.regions, c->heavy_factor, c->split_steps,
-                           c->split_parts > 1 ? (int)((long long)c->num_cus * (c->occupancy >= 5 ? 5 : 4) * 4 * c->split_waves / (100 * c->split_parts)) : 0);      // at most split_waves % of the waves start with a part of a split tile
+      const int split_limit = c->split_parts > 1 ? (int)((long long)c->num_cus * (c->occupancy >= 5 ? 5 : 4) * 4 * c->split_waves / (100 * c->split_parts)) : 0;      // at most split_waves % of the waves start with a part of a split tile
+      launch_tile_feedback(site.stream, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start, tiles, P.regions, c->heavy_factor, c->split_steps, split_limit);
+      c->order_args[0] = tiles; c->order_args[1] = P.regions; c->order_args[2] = c->heavy_factor; c->order_args[3] = c->split_steps; c->order_args[4] = split_limit;
       c->order_valid = true;
     }
     c->order_age++;

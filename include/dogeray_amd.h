@@ -599,9 +599,17 @@ int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles
  * tail goes (a single frame per launch, K:2154-2224, is mostly tail).  out: 16 * max_waves words. */
 int dr_stats_wave_log(dr_context* c, unsigned long long* out, int max_waves, int* n_waves);
 /* Node steps each pixel of the last frame cost (the persistent kernel's feedback for its tile order, option
- * "feedback"): pixel (tile, lane) at tile * 64 + lane, tile = block column * ceil(H/8) + block row,
- * lane = (x & 7) * 8 + (y & 7).  *n = words written (0: no feedback recorded yet). */
+ * "feedback"): pixel (tile, lane) at tile * 64 + lane, tile = block column * gy + block row over the frame's whole tiles
+ * (gx = W / div / 8 block columns of gy = H / div / 8 tiles, div = the preview divisor settings13[11]), lane = (x & 7) * 8 + (y & 7).
+ * *n = words written: min(capacity, 64 * the tiles the buffer has room for, which is at least gx * gy); 0: no feedback recorded yet. */
 int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n);
+/* The tile order the next persistent launch of the same view would use (test and measurement aid; waits for the context's stream):
+ * args[5] = the arguments of the last feedback pass the context enqueued -- tiles, regions (1 or 8), heavy_factor, split_steps, split_limit;
+ * *n = tiles (0: no order is valid, nothing else is written); the first min(capacity, tiles) entries of the order go to order (may be NULL
+ * with capacity 0); region_start[17]: [r], r <= regions, the first position of region r in the order; [9 + r], r < regions, how many tiles
+ * at the head of region r's part a one-frame launch hands out in split_parts parts.  The other words are not read by the kernel.
+ * DESIGN.md 4.3 "the order's contract" says what the order is. */
+int dr_stats_tile_order(dr_context* c, int* order, size_t capacity, size_t* n, int* region_start, int* args);
 /* Measurement aid (bench.py `roofline.gather`): rate at which this GPU serves divergent, dependent fetches of 64-byte
  * records from the RESIDENT wide-walk array -- the walk's memory behaviour without its arithmetic.  hot_records
  * restricts the random walk to the first records of the array (0 = all of it). */
@@ -642,6 +650,13 @@ int dr_kat_node_planes(dr_context* c, int n, const uint32_t* w, const float* a, 
 /* closest hit against the resident scene: t (-1 = miss), ORIGINAL object index and (visits may be NULL)
  * the number of boxes the chosen traversal tested for that ray */
 int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits);
+/* The two feedback kernels behind the persistent kernel's tile order, on caller data and scratch buffers (the context's own order is not
+ * touched): pixel_cost[ntiles * 64] -> tile_cost[ntiles] (the maximum of each tile's 64 words), order[ntiles] and region_start[17] as
+ * dr_stats_tile_order describes them.  order and region_start are filled with -1 before the launch: an entry the kernels did not write
+ * stays -1.  The sum of the tile costs times heavy_factor must stay below 2^64.  DR_ERR_INVALID for what no render launch asks for:
+ * ntiles < 1, regions other than 1 or 8, 8 regions of fewer than 512 tiles, split_limit < 0. */
+int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_factor, int split_steps, int split_limit,
+                         const unsigned* pixel_cost, unsigned* tile_cost, int* order, int* region_start);
 
 #ifdef __cplusplus
 }
