@@ -108,14 +108,6 @@ int output_download(dr_context* c, size_t npix, float* out_f32, uint8_t* out_rgb
   return DR_OK;
 }
 
-// dr_denoise_params as dr_accum_denoise judges them: null, or why they are refused
-const char* check_denoise_params(const dr_denoise_params& p) {
-  if (p.iterations < 0 || p.iterations > DN_MAX_ITERATIONS) return "iterations must be 0 .. 10";
-  if (!(p.sigma_luminance >= 0.0f) || !(p.sigma_depth >= 0.0f)) return "sigma_luminance and sigma_depth must be >= 0";
-  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return "normal_power_log2 must be 0 .. 16";
-  return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -195,7 +187,9 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
 
 int dr_denoise_defaults(dr_denoise_params* p) {
   if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
-  p->iterations = 5; p->sigma_luminance = 4.0f; p->normal_power_log2 = 7; p->sigma_depth = 1.0f; p->demodulate = 1; p->material_stop = 1;
+  const DnParams& D = DN_DEFAULTS;
+  p->iterations = D.iterations; p->sigma_luminance = D.sigma_luminance; p->normal_power_log2 = D.normal_power_log2;
+  p->sigma_depth = D.sigma_depth; p->demodulate = D.demodulate; p->material_stop = D.material_stop;
   return DR_OK;
 }
 
@@ -207,10 +201,8 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   DR_TRY(aov_view(c, settings13, W, H, P, traversal));
   DR_TRY(accum_matches(c, "denoise", W, H));
   if (divide_by < 1) { set_error("denoise: divide_by must be >= 1"); return DR_ERR_INVALID; }
-  dr_denoise_params p;
-  dr_denoise_defaults(&p);
-  if (params) p = *params;
-  if (const char* why = check_denoise_params(p)) { set_error(std::string("denoise: ") + why); return DR_ERR_INVALID; }
+  const DnParams D = params ? dn_params(*params) : DN_DEFAULTS;
+  if (const char* why = check_denoise_params(D)) { set_error(std::string("denoise: ") + why); return DR_ERR_INVALID; }
   if (!out_f32 && !out_rgb8) { set_error("denoise: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
@@ -219,11 +211,10 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   DnLaunch L;
   memset(&L, 0, sizeof(L));
   L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
-  L.D.iterations = p.iterations; L.D.sigma_luminance = p.sigma_luminance; L.D.normal_power_log2 = p.normal_power_log2;
-  L.D.sigma_depth = p.sigma_depth; L.D.demodulate = p.demodulate != 0; L.D.material_stop = p.material_stop != 0;
+  L.D = D;
   L.acc = c->accum; L.hist = c->hist;
   L.m2 = c->denoise_variance ? c->m2 : nullptr;
-  if (p.iterations > 0 && n > 0) DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, true, nullptr));
+  if (D.iterations > 0 && n > 0) DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, true, nullptr));
   float* f32_dev;
   uint8_t* rgb_dev;
   DR_TRY(output_staging(c, npix, out_f32, out_rgb8, device_pointers, f32_dev, rgb_dev));
@@ -236,7 +227,8 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
 
 int dr_upscale_defaults(dr_upscale_params* p) {
   if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
-  p->mode = DR_UPSCALE_GUIDED; p->normal_power_log2 = 5; p->sigma_depth = 1.0f; p->demodulate = 1; p->material_stop = 1;
+  const UpParams& U = UP_DEFAULTS;
+  p->mode = U.mode; p->normal_power_log2 = U.normal_power_log2; p->sigma_depth = U.sigma_depth; p->demodulate = U.demodulate; p->material_stop = U.material_stop;
   return DR_OK;
 }
 
@@ -252,18 +244,11 @@ int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, in
   DR_TRY(aov_view(c, full13, W, H, PF, traversal));
   DR_TRY(accum_matches(c, "upscale", W, H));
   if (divide_by < 1) { set_error("upscale: divide_by must be >= 1"); return DR_ERR_INVALID; }
-  dr_upscale_params p;
-  dr_upscale_defaults(&p);
-  if (params) p = *params;
-  if (p.mode != DR_UPSCALE_BLOCK && p.mode != DR_UPSCALE_GUIDED) { set_error("upscale: mode must be DR_UPSCALE_BLOCK or DR_UPSCALE_GUIDED"); return DR_ERR_INVALID; }
-  if (p.normal_power_log2 < 0 || p.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { set_error("upscale: normal_power_log2 must be 0 .. 16"); return DR_ERR_INVALID; }
-  if (!(p.sigma_depth >= 0.0f)) { set_error("upscale: sigma_depth must be >= 0"); return DR_ERR_INVALID; }
-  if (prefilter) {
-    if (p.mode == DR_UPSCALE_BLOCK) { set_error("upscale: a prefilter needs the guided mode (dr_accum_denoise filters without upscaling)"); return DR_ERR_INVALID; }
-    if (const char* why = check_denoise_params(*prefilter)) { set_error(std::string("upscale: prefilter ") + why); return DR_ERR_INVALID; }
-    if (prefilter->iterations < 1) { set_error("upscale: prefilter iterations must be >= 1"); return DR_ERR_INVALID; }
-    if ((prefilter->demodulate != 0) != (p.demodulate != 0)) { set_error("upscale: prefilter demodulate differs from the upscale parameters'"); return DR_ERR_INVALID; }
-  }
+  const UpParams UP = params ? up_params(*params) : UP_DEFAULTS;
+  const DnParams PRE = prefilter ? dn_params(*prefilter) : DnParams{};
+  const DnParams* const pre = prefilter ? &PRE : nullptr;
+  const std::string why = check_upscale_params(UP, pre);
+  if (!why.empty()) { set_error(why); return DR_ERR_INVALID; }
   if (!out_f32 && !out_rgb8) { set_error("upscale: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
@@ -272,23 +257,18 @@ int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, in
   UpLaunch U;
   memset(&U, 0, sizeof(U));
   U.gw = gw; U.gh = gh; U.FW = FW; U.FH = FH; U.W = W; U.H = H; U.div = n > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
-  U.U.mode = p.mode; U.U.normal_power_log2 = p.normal_power_log2; U.U.sigma_depth = p.sigma_depth;
-  U.U.demodulate = p.demodulate != 0; U.U.material_stop = p.material_stop != 0;
+  U.U = UP;
   U.acc = c->accum; U.hist = c->hist;
   c->up_passes = 0;
-  if (p.mode == DR_UPSCALE_GUIDED && n > 0) {
+  if (UP.mode == UP_GUIDED && n > 0) {
     // the low side: the denoiser's planes; without a prefilter only the demodulated colour of stage 0
     DnLaunch L;
     memset(&L, 0, sizeof(L));
     L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
-    L.D.demodulate = U.U.demodulate; L.D.material_stop = U.U.material_stop;
-    if (prefilter) {
-      L.D.iterations = prefilter->iterations; L.D.sigma_luminance = prefilter->sigma_luminance; L.D.normal_power_log2 = prefilter->normal_power_log2;
-      L.D.sigma_depth = prefilter->sigma_depth; L.D.material_stop = prefilter->material_stop != 0;
-    }
+    L.D = up_low_params(UP, pre);
     L.acc = c->accum; L.hist = c->hist;
     L.m2 = c->denoise_variance ? c->m2 : nullptr;
-    DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, prefilter != nullptr, &c->up_passes));
+    DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, pre != nullptr, &c->up_passes));
     U.e = L.src; U.guide = L.guide; U.mat = L.mat;
     // the full side: planes of its own (guide 4nf | scratch 4nf | albedo 3nf | material nf | gz nf floats), traced once per view
     if (13 * nf > c->up_planes.n) c->up_key.valid = false;
@@ -317,7 +297,8 @@ int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, in
 
 int dr_reproject_defaults(dr_reproject_params* p) {
   if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
-  p->max_history = 32; p->normal_cos = 0.9f; p->plane_tolerance = 0.01f; p->material_mask = 0xFFFFFFC3u; p->sky = 1;
+  const RpParams& R = RP_DEFAULTS;
+  p->max_history = R.max_history; p->normal_cos = R.normal_cos; p->plane_tolerance = R.plane_tolerance; p->material_mask = R.material_mask; p->sky = R.sky;
   return DR_OK;
 }
 
@@ -332,12 +313,9 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   if (c->stripe_mod != 1 || c->stripe_rem != 0) { set_error("reproject: the context renders a stripe (dr_context_set_stripe); only (1, 0) is supported"); return DR_ERR_INVALID; }
   DR_TRY(accum_matches(c, "reproject", W, H));
   if (frames < 1) { set_error("reproject: frames must be >= 1"); return DR_ERR_INVALID; }
-  dr_reproject_params p;
-  dr_reproject_defaults(&p);
-  if (params) p = *params;
   RpLaunch L;
   memset(&L, 0, sizeof(L));
-  L.R.max_history = p.max_history; L.R.normal_cos = p.normal_cos; L.R.plane_tolerance = p.plane_tolerance; L.R.material_mask = p.material_mask; L.R.sky = p.sky != 0;
+  L.R = params ? rp_params(*params) : RP_DEFAULTS;
   if (const char* why = check_reproject_params(L.R)) { set_error(why); return DR_ERR_INVALID; }
   fill_reproject_camera(Pt, L.to);
   fill_reproject_camera(Pf, L.from);

@@ -180,7 +180,7 @@ struct RenderParams {
   const uint32_t* cert_mask;      // null, or one bit per tile of this launch (local column * gy + row): set = a camera ray of the tile may graze (carries wide_mu.e)
 };
 
-// The denoiser's parameters (dr_denoise_params, validated by dr_accum_denoise / hk_denoise) and its material markers (device_denoise.hpp)
+// The denoiser's parameters (dr_denoise_params; defaults and ranges: params_host.hpp) and its material markers (device_denoise.hpp)
 constexpr int DN_MISS = -1;                    // material of a pixel whose pinhole ray hits nothing (aov_first_hit)
 constexpr int DN_OUTSIDE = -2147483647 - 1;    // material of a tap outside the pixel grid (never a real material)
 constexpr int DN_MAX_ITERATIONS = 10;
@@ -194,7 +194,7 @@ struct DnParams {
   int material_stop;
 };
 
-// The upsampler's parameters (dr_upscale_params, validated by dr_accum_upscale / hk_upscale; device_upscale.hpp)
+// The upsampler's parameters (dr_upscale_params; defaults and ranges: params_host.hpp; device_upscale.hpp)
 constexpr int UP_BLOCK = 0, UP_GUIDED = 1;
 struct UpParams {
   int mode;
@@ -204,8 +204,8 @@ struct UpParams {
   int material_stop;
 };
 
-// Temporal reprojection (dr_accum_reproject; device_reproject.hpp): the parameters (dr_reproject_params, validated by dr_accum_reproject /
-// hk_reproject), one view's float camera block as fill_view_params forms it, and the projection into the `from` camera, formed once per call
+// Temporal reprojection (dr_accum_reproject; device_reproject.hpp): the parameters (dr_reproject_params; defaults and ranges:
+// params_host.hpp), one view's float camera block as fill_view_params forms it, and the projection into the `from` camera, formed once per call
 // in double (params_host.hpp fill_reproject_proj)
 constexpr int RP_VALID = 0, RP_MASKED = 1, RP_OFFSCREEN = 2, RP_REJECTED = 3;      // the class of a grid pixel
 constexpr int RP_MAX_HISTORY = 65535;

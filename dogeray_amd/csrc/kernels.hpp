@@ -13,6 +13,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "device_launch.h"
 #include "device_layout.h"
 
 namespace dr {
@@ -77,92 +78,23 @@ struct AovLaunch {
 };
 void launch_aov(hipStream_t stream, const RenderParams& P, int traversal, const AovLaunch& A);
 
-// kernels_denoise.hip: planes of the gw x gh pixel grid, row-major (pixel (x, y) at y * gw + x), as launch_aov writes them
-struct DnLaunch {
-  int gw, gh;                     // pixel grid
-  int W, H;                       // accumulator (column-major, (x * H + y) * 3) and output (row-major W x H x 3)
-  int divide_by;
-  DnParams D;
-  const int32_t* acc;
-  const int32_t* hist;            // the accumulator's history plane (pixel (x, y) at x * H + y: its divisor is hist + divide_by), or null
-  const float* normal;            // launch_aov's normal (3 per pixel) and depth: read by the guide prepare only
-  const float* depth;
-  const float* albedo;            // launch_aov's albedo (3 per pixel)
-  const int32_t* mat;             // launch_aov's material (-1: miss)
-  const unsigned long long* m2;   // the second-moment plane (pixel (x, y) at x * H + y) when stage 1 takes the temporal variance from it (option
-                                  // "denoise_variance"), or null: the spatial estimate everywhere
-  float* guide;                   // float4 (n.x, n.y, n.z, z)
-  float* gz;                      // depth gradient
-  const float* src;               // colour planes, float4 per pixel: (e, l) or (e, var)
-  float* dst;
-  float* out_f32;                 // W x H x 3 (null: not written)
-  uint8_t* out_rgb8;
-};
+// The accumulator stages: their launch structs (DnLaunch, UpLaunch, RpLaunch, MoLaunch) are in device_launch.h, without HIP, because the per-pixel
+// bodies of the device_*.hpp headers and the host build take them too
+// kernels_denoise.hip
 void launch_denoise_guides(hipStream_t stream, const DnLaunch& L);                 // normal, depth, mat -> guide, gz
 void launch_denoise_colour(hipStream_t stream, const DnLaunch& L, int stage);      // 0: acc -> (e, l) in dst; 1: src (e, l) -> (e, var) in dst
 void launch_denoise_pass(hipStream_t stream, const DnLaunch& L, int step, int lattice);   // src -> dst, one a-trous iteration
 void launch_denoise_finish(hipStream_t stream, const DnLaunch& L);                 // src (or, iterations 0, acc) -> out_f32 / out_rgb8
 
-// kernels_upscale.hip: the low side is the denoiser's (DnLaunch's grid, guide, albedo, mat and a colour plane), the full side the same planes
-// over the full-resolution pixel grid FW x FH = (W / 8) * 8 x (H / 8) * 8 (pixel (X, Y) at Y * FW + X); block mode reads neither
-struct UpLaunch {
-  int gw, gh;                     // low pixel grid; the output grid is gw * div x gh * div
-  int FW, FH;                     // full-resolution pixel grid
-  int W, H;                       // accumulator (column-major) and output (row-major W x H x 3)
-  int div;                        // (int)settings13[11]
-  int divide_by;
-  UpParams U;
-  const int32_t* acc;
-  const int32_t* hist;            // the accumulator's history plane, or null
-  const float* e;                 // low colour plane, float4 per pixel: (e.r, e.g, e.b, *)
-  const float* guide;             // low guides: float4 (n, z), material
-  const int32_t* mat;
-  const float* Fguide;            // full guides: float4 (N, Z), albedo (3 per pixel), material, depth gradient
-  const float* Falbedo;
-  const int32_t* Fmat;
-  const float* Fgz;
-  float* out_f32;                 // W x H x 3 (null: not written)
-  uint8_t* out_rgb8;
-};
+// kernels_upscale.hip
 void launch_upscale(hipStream_t stream, const UpLaunch& L);
 
-// kernels_reproject.hip: the guides of both views are row-major gw x gh planes as launch_aov writes them; the accumulators are column-major W x H x 3
-// ((x * H + y) * 3) and the history planes W x H (x * H + y).  Pixels outside the grid are not written (the caller clears the `to` pair).
-struct RpLaunch {
-  int gw, gh;                     // pixel grid of both views
-  int W, H;
-  int frames;                     // frames the `from` accumulator holds beyond its history plane
-  RpParams R;
-  RpCamera to, from;
-  RpProj J;                       // projection into the `from` camera
-  const float* t_to; const float* normal_to; const int32_t* mat_to;
-  const float* t_from; const float* normal_from; const int32_t* mat_from;
-  const int32_t* acc_from;
-  const int32_t* hist_from;       // null: no history yet (0 everywhere)
-  int32_t* acc_to;
-  int32_t* hist_to;
-  const unsigned long long* m2_from;   // the second-moment planes (W x H at x * H + y), or both null: no plane is carried
-  unsigned long long* m2_to;
-  unsigned long long* counts;     // [4]: pixels of class RP_VALID, RP_MASKED, RP_OFFSCREEN, RP_REJECTED are added
-};
+// kernels_reproject.hip
 void launch_reproject(hipStream_t stream, const RpLaunch& L);
 
 // kernels_moments.hip
 // acc += frame and m2 += the frame's capped luma squared, in one pass (npix pixels; acc / frame column-major x 3, m2 one word per pixel)
 void launch_moments_add(hipStream_t stream, int32_t* acc, const int32_t* frame, unsigned long long* m2, size_t npix);
-// the noise estimate over the gw x gh pixel grid: sigma row-major W x H (null: not written; pixels outside the grid are not written) and the
-// counts (MO_WORDS words, device_moments.hpp: estimated, above, sum_var_q16, bins; added to; null: not counted)
-struct MoLaunch {
-  int gw, gh;
-  int W, H;
-  int divide_by;
-  float tolerance;
-  const int32_t* acc;
-  const int32_t* hist;            // null: no history plane (0 everywhere)
-  const unsigned long long* m2;
-  float* out_sigma;
-  unsigned long long* counts;
-};
 void launch_moments_error(hipStream_t stream, const MoLaunch& L);
 
 }  // namespace dr

@@ -1,5 +1,5 @@
-// The AOV-guided a-trous denoiser (dr_accum_denoise): four kernels over the pixel grid, each pixel's arithmetic one device function of
-// device_denoise.hpp.
+// The AOV-guided a-trous denoiser (dr_accum_denoise): the kernels over the pixel grid.  A kernel is its thread-to-pixel mapping and a call of
+// the stage's body in device_denoise.hpp (dn_*_pixel), which holds every pixel's arithmetic and indexing and runs unchanged in the host build.
 //   guide prepare   (n, z) packed into a float4 plane, the material plane completed, the depth gradient gz
 //   colour prepare  stage 0: the column-major accumulator -> c = acc / divide_by -> e = c / a' -> (e, l) plane
 //                   stage 1: (e, l) -> the variance pre-pass -> (e, var) plane (option "denoise_variance": the temporal variance of the second-moment
@@ -13,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include "device_denoise.hpp"
-#include "device_moments.hpp"
 #include "kernels.hpp"
 
 namespace dr {
@@ -23,17 +22,7 @@ namespace {
 __global__ __launch_bounds__(256) void dn_guide_kernel(DnLaunch L) {
   const int x = (int)(blockIdx.x * 16 + (threadIdx.x & 15)), y = (int)(blockIdx.y * 16 + (threadIdx.x >> 4));
   if (x >= L.gw || y >= L.gh) return;
-  const size_t i = (size_t)y * L.gw + x;
-  auto zm = [&](int xx, int yy, float& z) {
-    if (xx < 0 || yy < 0 || xx >= L.gw || yy >= L.gh) { z = 0.0f; return DN_OUTSIDE; }
-    const size_t j = (size_t)yy * L.gw + xx;
-    z = L.depth[j];
-    return (int)L.mat[j];
-  };
-  float zp, zl, zr, zu, zd;
-  const int mp = zm(x, y, zp), ml = zm(x - 1, y, zl), mr = zm(x + 1, y, zr), mu = zm(x, y - 1, zu), md = zm(x, y + 1, zd);
-  L.gz[i] = dn_gradient(zp, mp, zl, ml, zr, mr, zu, mu, zd, md);
-  reinterpret_cast<float4*>(L.guide)[i] = make_float4(L.normal[3 * i], L.normal[3 * i + 1], L.normal[3 * i + 2], zp);
+  dn_guide_pixel(L, x, y);
 }
 
 // consecutive threads walk a column of the accumulator (coalesced reads, as present_kernel)
@@ -41,53 +30,20 @@ __global__ __launch_bounds__(256) void dn_colour_kernel(DnLaunch L) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)L.gw * L.gh) return;
   const int x = (int)(idx / L.gh), y = (int)(idx - (long long)x * L.gh);
-  const size_t i = (size_t)y * L.gw + x;
-  const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
-  const int32_t* a = L.acc + px * 3;
-  const int n = dn_divisor(L.hist, px, L.divide_by);
-  const int m = L.mat[i];
-  const float er = dn_colour(a[0], n) / dn_albedo(L.albedo[3 * i], m, L.D.demodulate);
-  const float eg = dn_colour(a[1], n) / dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate);
-  const float eb = dn_colour(a[2], n) / dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate);
-  reinterpret_cast<float4*>(L.dst)[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
-}
-
-__device__ __forceinline__ DnTap dn_tap_global(const DnLaunch& L, int x, int y) {
-  DnTap q;
-  if (x < 0 || y < 0 || x >= L.gw || y >= L.gh) {
-    q.m = DN_OUTSIDE; q.c = make_float4(0, 0, 0, 0); q.g = q.c;
-    return q;
-  }
-  const size_t j = (size_t)y * L.gw + x;
-  q.c = reinterpret_cast<const float4*>(L.src)[j]; q.g = reinterpret_cast<const float4*>(L.guide)[j]; q.m = L.mat[j];
-  return q;
+  dn_colour_pixel(L, x, y);
 }
 
 __global__ __launch_bounds__(256) void dn_variance_kernel(DnLaunch L) {
   const int x = (int)(blockIdx.x * 16 + (threadIdx.x & 15)), y = (int)(blockIdx.y * 16 + (threadIdx.x >> 4));
   if (x >= L.gw || y >= L.gh) return;
-  const size_t i = (size_t)y * L.gw + x;
-  const float4 gp = reinterpret_cast<const float4*>(L.guide)[i];
-  const int m = L.mat[i];
-  float var = 0.0f;
-  bool temporal = false;
-  if (L.m2) {                                // option "denoise_variance": SVGF's rule, the temporal second moment once the pixel has four samples
-    const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
-    const int32_t* a = L.acc + px * 3;
-    temporal = mo_denoise_variance(a[0], a[1], a[2], L.m2[px], (long long)dn_divisor(L.hist, px, L.divide_by), dn_albedo(L.albedo[3 * i], m, L.D.demodulate),
-                                   dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate), dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate), var);
-  }
-  if (!temporal) var = dn_variance(L.D, gp, m, L.gz[i], [&](int dx, int dy) { return dn_tap_global(L, x + dx, y + dy); });
-  const float4 c = reinterpret_cast<const float4*>(L.src)[i];
-  reinterpret_cast<float4*>(L.dst)[i] = make_float4(c.x, c.y, c.z, var);
+  dn_variance_pixel(L, x, y);
 }
 
 // plain shape: one thread per pixel of a 16x16 block, every tap from the planes
 __global__ __launch_bounds__(256) void dn_pass_global_kernel(DnLaunch L, int step) {
   const int x = (int)(blockIdx.x * 16 + (threadIdx.x & 15)), y = (int)(blockIdx.y * 16 + (threadIdx.x >> 4));
   if (x >= L.gw || y >= L.gh) return;
-  const size_t i = (size_t)y * L.gw + x;
-  reinterpret_cast<float4*>(L.dst)[i] = dn_atrous(L.D, step, reinterpret_cast<const float4*>(L.guide)[i], (int)L.mat[i], L.gz[i], [&](int dx, int dy) { return dn_tap_global(L, x + step * dx, y + step * dy); });
+  dn_pass_pixel(L, step, x, y);
 }
 
 // lattice shape: workgroup (blockIdx.x, blockIdx.y) = residue class (rx, ry) = (bx % step, by % step) and lattice tile (tx, ty) = (bx / step, by / step);
@@ -124,25 +80,7 @@ __global__ __launch_bounds__(256) void dn_finish_kernel(DnLaunch L) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)L.W * L.H) return;
   const int y = (int)(idx / L.W), x = (int)(idx - (long long)y * L.W);
-  float f[3] = {0.0f, 0.0f, 0.0f};
-  if (x < L.gw && y < L.gh) {
-    const size_t i = (size_t)y * L.gw + x;
-    if (L.D.iterations == 0) {               // no filter, no demodulation: c itself
-      const size_t px = (size_t)x * (size_t)L.H + (size_t)y;
-      const int32_t* a = L.acc + px * 3;
-      const int n = dn_divisor(L.hist, px, L.divide_by);
-      f[0] = dn_colour(a[0], n); f[1] = dn_colour(a[1], n); f[2] = dn_colour(a[2], n);
-    } else {
-      const float4 e = reinterpret_cast<const float4*>(L.src)[i];
-      const int m = L.mat[i];
-      f[0] = e.x * dn_albedo(L.albedo[3 * i], m, L.D.demodulate);
-      f[1] = e.y * dn_albedo(L.albedo[3 * i + 1], m, L.D.demodulate);
-      f[2] = e.z * dn_albedo(L.albedo[3 * i + 2], m, L.D.demodulate);
-    }
-  }
-  const size_t o = (size_t)idx * 3;
-  if (L.out_f32) { L.out_f32[o] = f[0]; L.out_f32[o + 1] = f[1]; L.out_f32[o + 2] = f[2]; }
-  if (L.out_rgb8) { L.out_rgb8[o] = dn_rgb8(f[0]); L.out_rgb8[o + 1] = dn_rgb8(f[1]); L.out_rgb8[o + 2] = dn_rgb8(f[2]); }
+  dn_finish_pixel(L, x, y);
 }
 
 dim3 grid16(int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); }

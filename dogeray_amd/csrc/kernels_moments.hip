@@ -1,4 +1,6 @@
-// The second-moment plane (option "moments"; dr_accum_error): two kernels, each pixel's arithmetic the device functions of device_moments.hpp.
+// The second-moment plane (option "moments"; dr_accum_error): two kernels.  A pixel's arithmetic and indexing are the bodies of device_moments.hpp
+// (mo_add_pixel, mo_error_pixel), which run unchanged in the host build; here are the thread-to-pixel mappings, the four-pixel vector shape of the
+// add and the wave reductions of the counts.
 //   fused add   acc += frame and M2 += yc^2 in one pass over the column-major accumulator, in place of frame_add_kernel while a plane exists.
 //               A stream bound by memory: 52 bytes per pixel (12 of frame, 12 + 12 of acc, 8 + 8 of M2) against the plain add's 36.  A lane
 //               takes FOUR pixels, so that every access is a 16-byte vector access: 3 x 16 B of frame, 3 x 16 B of acc, 2 x 16 B of M2; the
@@ -37,11 +39,7 @@ __global__ __launch_bounds__(256) void moments_add_kernel(int4* __restrict__ acc
   int32_t* as = reinterpret_cast<int32_t*>(acc);
   const int32_t* fs = reinterpret_cast<const int32_t*>(frame);
   unsigned long long* ms = reinterpret_cast<unsigned long long*>(m2);
-  for (size_t p = n4 * 4 + first; p < npix; p += stride) {
-    const int32_t r = fs[3 * p], g = fs[3 * p + 1], b = fs[3 * p + 2];
-    as[3 * p] += r; as[3 * p + 1] += g; as[3 * p + 2] += b;
-    ms[p] = mo_add(ms[p], mo_square(r, g, b));
-  }
+  for (size_t p = n4 * 4 + first; p < npix; p += stride) mo_add_pixel(as, fs, ms, p);
 }
 
 // lane l of a tile is pixel (l & 7, l >> 3); the grid is whole tiles, so every lane of a launched tile has a pixel
@@ -50,13 +48,9 @@ __global__ __launch_bounds__(256) void moments_error_kernel(MoLaunch L) {
   const int tiles_x = L.gw >> 3;
   if (wave >= tiles_x * (L.gh >> 3)) return;
   const int x = (wave % tiles_x) * 8 + (lane & 7), y = (wave / tiles_x) * 8 + (lane >> 3);
-  const size_t p = (size_t)x * (size_t)L.H + (size_t)y;
-  const int32_t* a = L.acc + p * 3;
-  const long long n = (long long)(L.hist ? L.hist[p] : 0) + (long long)L.divide_by;
-  double var = 0.0;
-  const bool est = mo_variance(a[0], a[1], a[2], L.m2[p], n, var);
-  const float sigma = est ? mo_sigma(var) : 0.0f;
-  if (L.out_sigma) L.out_sigma[(size_t)y * (size_t)L.W + (size_t)x] = sigma;
+  double var;
+  float sigma;
+  const bool est = mo_error_pixel(L, x, y, var, sigma);
   if (!L.counts) return;
   const int bin = est ? mo_bin(sigma) : -1;
   unsigned long long q = est ? mo_var_q16(var) : 0ull;

@@ -1,12 +1,15 @@
 // settings[13] -> the per-launch constants of RenderParams that do not depend on the device: the camera block of Kernel
 // (kernel.cu K:1016-1052, identical for every pixel, so evaluated once on the host with the reference's float / double promotions),
-// the sample scale, the block grid and the stripe.  Host only; shared by the context_*.cpp files and the host build of the kernel arithmetic
-// (tools/host_kernel.cpp).
+// the sample scale, the block grid and the stripe; and the parameter sets of the accumulator stages (dr_denoise_params, dr_upscale_params,
+// dr_reproject_params): their defaults, their ranges and their device form, each written here and nowhere else.  Host only; shared by the
+// context_*.cpp files and the host build of the kernel arithmetic (tools/host_kernel.cpp).
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
 
+#include "../../include/dogeray_amd.h"
 #include "device_layout.h"
 
 namespace dr {
@@ -122,6 +125,41 @@ inline bool fill_reproject_proj(const RpCamera& C, RpProj& J) {
   J.LcN = dot(J.L, J.cN);
   J.hh = dot(J.hor, J.hor); J.vv = dot(J.ver, J.ver);
   return std::isfinite(J.LcN) && J.LcN != 0.0;
+}
+// The defaults of the three parameter sets, in their device form (dr_*_defaults hand them out field by field)
+constexpr DnParams DN_DEFAULTS = {5, 4.0f, 7, 1.0f, 1, 1};
+constexpr UpParams UP_DEFAULTS = {UP_GUIDED, 5, 1.0f, 1, 1};
+constexpr RpParams RP_DEFAULTS = {32, 0.9f, 0.01f, 0xFFFFFFC3u, 1};
+// The device form of a parameter set: the same fields, every flag 0 or 1
+inline DnParams dn_params(const dr_denoise_params& p) {
+  return {p.iterations, p.sigma_luminance, p.normal_power_log2, p.sigma_depth, p.demodulate != 0, p.material_stop != 0};
+}
+inline UpParams up_params(const dr_upscale_params& p) { return {p.mode, p.normal_power_log2, p.sigma_depth, p.demodulate != 0, p.material_stop != 0}; }
+inline RpParams rp_params(const dr_reproject_params& p) { return {p.max_history, p.normal_cos, p.plane_tolerance, p.material_mask, p.sky != 0}; }
+
+// dr_denoise_params' ranges; null, or what is wrong (the caller says whose parameters they are)
+inline const char* check_denoise_params(const DnParams& D) {
+  if (D.iterations < 0 || D.iterations > DN_MAX_ITERATIONS) return "iterations must be 0 .. 10";
+  if (!(D.sigma_luminance >= 0.0f) || !(D.sigma_depth >= 0.0f)) return "sigma_luminance and sigma_depth must be >= 0";
+  if (D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return "normal_power_log2 must be 0 .. 16";
+  return nullptr;
+}
+// dr_upscale_params' ranges, and a prefilter (null: none) judged against them; empty, or what is wrong
+inline std::string check_upscale_params(const UpParams& U, const DnParams* prefilter) {
+  if (U.mode != UP_BLOCK && U.mode != UP_GUIDED) return "upscale: mode must be DR_UPSCALE_BLOCK or DR_UPSCALE_GUIDED";
+  if (U.normal_power_log2 < 0 || U.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) return "upscale: normal_power_log2 must be 0 .. 16";
+  if (!(U.sigma_depth >= 0.0f)) return "upscale: sigma_depth must be >= 0";
+  if (!prefilter) return "";
+  if (U.mode == UP_BLOCK) return "upscale: a prefilter needs the guided mode (dr_accum_denoise filters without upscaling)";
+  if (const char* why = check_denoise_params(*prefilter)) return std::string("upscale: prefilter ") + why;
+  if (prefilter->iterations < 1) return "upscale: prefilter iterations must be >= 1";
+  if (prefilter->demodulate != U.demodulate) return "upscale: prefilter demodulate differs from the upscale parameters'";
+  return "";
+}
+// The denoiser's parameters on the upsampler's low side: the prefilter's (its demodulate is the upscale parameters'), or without one what colour
+// stage 0 reads of them
+inline DnParams up_low_params(const UpParams& U, const DnParams* prefilter) {
+  return prefilter ? *prefilter : DnParams{0, 0.0f, 0, 0.0f, U.demodulate, U.material_stop};
 }
 // dr_reproject_params' ranges; null, or what is wrong
 inline const char* check_reproject_params(const RpParams& R) {

@@ -4,6 +4,10 @@
 // function qualifiers vanish) together with the product's host ingest (reader, BVH builder, lineariser, wide-walk builder) into
 // tools/libhostkernel.so, and renders frames with std::threads over 8-pixel block columns, one "lane" at a time.
 //
+// The accumulator stages (hk_denoise, hk_upscale, hk_reproject, hk_moments_add, hk_error) are the product's per-pixel bodies as well
+// (device_denoise.hpp, device_upscale.hpp, device_reproject.hpp, device_moments.hpp): this file fills the launch structs of device_launch.h with
+// host pointers and loops over the pixels; no stage's arithmetic or indexing is written here.  Parameter defaults and ranges are params_host.hpp's.
+//
 // It is TEST AND BENCH INFRASTRUCTURE: tests/test_host_kernel.py compares its frames with the oracle's pixel for pixel (a check of the
 // kernel's arithmetic that needs no GPU) and bench.py reports it as cpu_baseline.kind "same-source" beside the oracle's "port".
 // It is not linked into libdogeray_amd.so, which has no CPU path (dr_context_create fails without a GPU).
@@ -64,82 +68,38 @@ void host_rows(int nthreads, int count, const std::function<void(int)>& f) {
   for (int k = 0; k < nthreads; k++) th.emplace_back([&, k] { for (int r = k; r < count; r += nthreads) f(r); });
   for (std::thread& t : th) t.join();
 }
+// f(x, y) for every pixel of a w x h grid
+template <class F>
+void host_grid(int nthreads, int w, int h, const F& f) {
+  host_rows(nthreads, h, [&](int y) { for (int x = 0; x < w; x++) f(x, y); });
+}
 
-// The low side of hk_denoise and hk_upscale over the gw x gh pixel grid, stage by stage as kernels_denoise.hip runs it: the guide prepare, colour
-// stage 0 and -- filter -- the variance pre-pass and the D.iterations a-trous passes.  e: (e, l) after stage 0, (e, var) after the last pass.
+// a parameter set handed over as words: a dr_denoise_params, dr_upscale_params or dr_reproject_params
+template <class T>
+T params_from_words(const int32_t* words) { T p; memcpy(&p, words, sizeof(T)); return p; }
+
+// The low side of hk_denoise and hk_upscale over the L.gw x L.gh pixel grid (L.D, L.acc, L.hist, L.m2 and the AOV planes L.normal, L.depth,
+// L.albedo, L.mat set by the caller), stage by stage as denoise_low_side (context_accum.cpp) launches it: the guide prepare, colour stage 0 and
+// -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  The planes live in `planes`; on return L.src is the plane of the
+// result, (e, l) after stage 0, (e, var) after the last pass, and L.guide, L.gz are the guides.
 struct HostLow {
-  std::vector<float4> guide, e;
-  std::vector<float> gz;
+  std::vector<float> guide, gz, pa, pb;      // float4 (n, z) | depth gradient | colour planes A, B (float4)
 };
-void host_denoise_low(const int32_t* acc, int H, int divide_by, int gw, int gh, const DnParams& D, bool filter, const float* normal, const float* albedo,
-                      const float* depth, const int32_t* material, const int32_t* hist, const unsigned long long* m2, int nthreads, HostLow& out) {
-  const size_t n = (size_t)gw * gh;
-  auto rows = [&](int count, const std::function<void(int)>& f) { host_rows(nthreads, count, f); };
-  std::vector<float4>& guide = out.guide;
-  std::vector<float>& gz = out.gz;
-  guide.resize(n); gz.resize(n);
-  std::vector<float4> pa(n), pb(n);
-  auto mat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? DN_OUTSIDE : (int)material[(size_t)y * gw + x]; };
-  auto zat = [&](int x, int y) { return (x < 0 || y < 0 || x >= gw || y >= gh) ? 0.0f : depth[(size_t)y * gw + x]; };
-  {
-    rows(gh, [&](int y) {                                                  // guide prepare
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        gz[i] = dn_gradient(zat(x, y), mat(x, y), zat(x - 1, y), mat(x - 1, y), zat(x + 1, y), mat(x + 1, y), zat(x, y - 1), mat(x, y - 1), zat(x, y + 1), mat(x, y + 1));
-        guide[i] = make_float4(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], depth[i]);
-      }
-    });
-    rows(gh, [&](int y) {                                                  // colour prepare, stage 0
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        const size_t px = (size_t)x * (size_t)H + (size_t)y;
-        const int32_t* a = acc + px * 3;
-        const int nd = dn_divisor(hist, px, divide_by);
-        const int m = material[i];
-        const float er = dn_colour(a[0], nd) / dn_albedo(albedo[3 * i], m, D.demodulate);
-        const float eg = dn_colour(a[1], nd) / dn_albedo(albedo[3 * i + 1], m, D.demodulate);
-        const float eb = dn_colour(a[2], nd) / dn_albedo(albedo[3 * i + 2], m, D.demodulate);
-        pa[i] = make_float4(er, eg, eb, dn_lum(er, eg, eb));
-      }
-    });
-    if (!filter) { out.e.swap(pa); return; }
-    auto tap = [&](const std::vector<float4>& src, int x, int y) {
-      DnTap q;
-      q.m = mat(x, y);
-      if (q.m == DN_OUTSIDE) { q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
-      const size_t j = (size_t)y * gw + x;
-      q.c = src[j]; q.g = guide[j];
-      return q;
-    };
-    rows(gh, [&](int y) {                                                  // colour prepare, stage 1: the variance pre-pass
-      for (int x = 0; x < gw; x++) {
-        const size_t i = (size_t)y * gw + x;
-        const int m = material[i];
-        float var = 0.0f;
-        bool temporal = false;
-        if (m2) {
-          const size_t px = (size_t)x * (size_t)H + (size_t)y;
-          const int32_t* a = acc + px * 3;
-          temporal = mo_denoise_variance(a[0], a[1], a[2], m2[px], (long long)dn_divisor(hist, px, divide_by), dn_albedo(albedo[3 * i], m, D.demodulate),
-                                         dn_albedo(albedo[3 * i + 1], m, D.demodulate), dn_albedo(albedo[3 * i + 2], m, D.demodulate), var);
-        }
-        if (!temporal) var = dn_variance(D, guide[i], m, gz[i], [&](int dx, int dy) { return tap(pa, x + dx, y + dy); });
-        pb[i] = make_float4(pa[i].x, pa[i].y, pa[i].z, var);
-      }
-    });
-    std::vector<float4>* src = &pb;
-    std::vector<float4>* dst = &pa;
-    for (int it = 0; it < D.iterations; it++) {
-      const int step = 1 << it;
-      rows(gh, [&](int y) {
-        for (int x = 0; x < gw; x++) {
-          const size_t i = (size_t)y * gw + x;
-          (*dst)[i] = dn_atrous(D, step, guide[i], (int)material[i], gz[i], [&](int dx, int dy) { return tap(*src, x + step * dx, y + step * dy); });
-        }
-      });
-      std::swap(src, dst);
-    }
-    out.e.swap(*src);                                                      // the filtered (e, var)
+void host_denoise_low(DnLaunch& L, bool filter, int nthreads, HostLow& planes) {
+  const size_t n = (size_t)L.gw * L.gh;
+  planes.guide.resize(4 * n); planes.gz.resize(n); planes.pa.resize(4 * n); planes.pb.resize(4 * n);
+  L.guide = planes.guide.data(); L.gz = planes.gz.data();
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_guide_pixel(L, x, y); });
+  L.dst = planes.pa.data();
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_colour_pixel(L, x, y); });            // acc -> (e, l) in A
+  L.src = planes.pa.data(); L.dst = planes.pb.data();
+  if (!filter) return;
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_variance_pixel(L, x, y); });          // (e, l) -> (e, var) in B
+  L.src = planes.pb.data(); L.dst = planes.pa.data();                                          // the passes: B -> A -> B ...
+  for (int it = 0; it < L.D.iterations; it++) {
+    host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_pass_pixel(L, 1 << it, x, y); });
+    float* const t = const_cast<float*>(L.src);
+    L.src = L.dst; L.dst = t;
   }
 }
 
@@ -442,7 +402,7 @@ int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int 
   return 0;
 }
 
-// dr_accum_denoise on the host: device_denoise.hpp over the pixel grid of settings13, stage by stage as kernels_denoise.hip runs it, from guides given
+// dr_accum_denoise on the host: the stage bodies of device_denoise.hpp over the pixel grid of settings13 (host_denoise_low, then the finish), from guides given
 // as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
 // W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
 // hist (may be NULL): the accumulator's history plane, W x H at x * H + y -- pixel p's divisor is hist[p] + divide_by.
@@ -455,43 +415,20 @@ int hk_denoise_m2(const int32_t* acc, int W, int H, int divide_by, const float* 
   RenderParams P;
   memset(&P, 0, sizeof(P));
   if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
-  DnParams D = {5, 4.0f, 7, 1.0f, 1, 1};
-  if (params) {                      // dr_denoise_params: int, float, int, float, int, int
-    memcpy(&D.iterations, params, 4); memcpy(&D.sigma_luminance, params + 1, 4); memcpy(&D.normal_power_log2, params + 2, 4);
-    memcpy(&D.sigma_depth, params + 3, 4); memcpy(&D.demodulate, params + 4, 4); memcpy(&D.material_stop, params + 5, 4);
-  }
-  if (divide_by < 1 || D.iterations < 0 || D.iterations > DN_MAX_ITERATIONS || !(D.sigma_luminance >= 0.0f) || !(D.sigma_depth >= 0.0f) ||
-      D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2) { hk_err = "bad denoise parameters"; return -1; }
-  D.demodulate = D.demodulate != 0; D.material_stop = D.material_stop != 0;
-  const int gw = P.gx * 8, gh = P.gy * 8;
+  const DnParams D = params ? dn_params(params_from_words<dr_denoise_params>(params)) : DN_DEFAULTS;
+  if (divide_by < 1) { hk_err = "denoise: divide_by must be >= 1"; return -1; }
+  if (const char* why = check_denoise_params(D)) { hk_err = std::string("denoise: ") + why; return -1; }
   if (nthreads < 1) nthreads = 1;
-  HostLow low;
-  if (D.iterations > 0) host_denoise_low(acc, H, divide_by, gw, gh, D, true, normal, albedo, depth, material, hist, m2, nthreads, low);
-  const std::vector<float4>& pa = low.e;
-  host_rows(nthreads, H, [&](int y) {                                      // finish
-    for (int x = 0; x < W; x++) {
-      float f[3] = {0.0f, 0.0f, 0.0f};
-      if (x < gw && y < gh) {
-        const size_t i = (size_t)y * gw + x;
-        if (D.iterations == 0) {
-          const size_t px = (size_t)x * (size_t)H + (size_t)y;
-          const int32_t* a = acc + px * 3;
-          const int nd = dn_divisor(hist, px, divide_by);
-          f[0] = dn_colour(a[0], nd); f[1] = dn_colour(a[1], nd); f[2] = dn_colour(a[2], nd);
-        } else {
-          const int m = material[i];
-          f[0] = pa[i].x * dn_albedo(albedo[3 * i], m, D.demodulate);
-          f[1] = pa[i].y * dn_albedo(albedo[3 * i + 1], m, D.demodulate);
-          f[2] = pa[i].z * dn_albedo(albedo[3 * i + 2], m, D.demodulate);
-        }
-      }
-      const size_t o = ((size_t)y * W + x) * 3;
-      for (int k = 0; k < 3; k++) {
-        if (out_f32) out_f32[o + k] = f[k];
-        if (out_rgb8) out_rgb8[o + k] = dn_rgb8(f[k]);
-      }
-    }
-  });
+  DnLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by;
+  L.D = D;
+  L.acc = acc; L.hist = hist; L.m2 = m2;
+  L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
+  HostLow planes;
+  if (D.iterations > 0) host_denoise_low(L, true, nthreads, planes);
+  L.out_f32 = out_f32; L.out_rgb8 = out_rgb8;
+  host_grid(nthreads, W, H, [&](int x, int y) { dn_finish_pixel(L, x, y); });
   return 0;
 }
 
@@ -518,72 +455,44 @@ int hk_upscale(const int32_t* acc, int W, int H, int divide_by, const float* set
   memcpy(full13, settings13, sizeof(full13));
   full13[11] = 1.0f;
   if (const char* why = fill_view_params(full13, W, H, 0.0f, 0, 1, 0, PF)) { hk_err = why; return -1; }
-  UpParams U = {UP_GUIDED, 5, 1.0f, 1, 1};
-  if (params) {                      // dr_upscale_params: int, int, float, int, int
-    memcpy(&U.mode, params, 4); memcpy(&U.normal_power_log2, params + 1, 4); memcpy(&U.sigma_depth, params + 2, 4);
-    memcpy(&U.demodulate, params + 3, 4); memcpy(&U.material_stop, params + 4, 4);
-  }
-  if (divide_by < 1 || (U.mode != UP_BLOCK && U.mode != UP_GUIDED) || U.normal_power_log2 < 0 || U.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2 ||
-      !(U.sigma_depth >= 0.0f)) { hk_err = "bad upscale parameters"; return -1; }
-  U.demodulate = U.demodulate != 0; U.material_stop = U.material_stop != 0;
-  DnParams D = {0, 0.0f, 0, 0.0f, U.demodulate, U.material_stop};
-  if (prefilter) {
-    memcpy(&D.iterations, prefilter, 4); memcpy(&D.sigma_luminance, prefilter + 1, 4); memcpy(&D.normal_power_log2, prefilter + 2, 4);
-    memcpy(&D.sigma_depth, prefilter + 3, 4); memcpy(&D.demodulate, prefilter + 4, 4); memcpy(&D.material_stop, prefilter + 5, 4);
-    D.demodulate = D.demodulate != 0; D.material_stop = D.material_stop != 0;
-    if (U.mode == UP_BLOCK || D.iterations < 1 || D.iterations > DN_MAX_ITERATIONS || !(D.sigma_luminance >= 0.0f) || !(D.sigma_depth >= 0.0f) ||
-        D.normal_power_log2 < 0 || D.normal_power_log2 > DN_MAX_NORMAL_POWER_LOG2 || D.demodulate != U.demodulate) { hk_err = "bad upscale prefilter"; return -1; }
-  }
-  const int gw = P.gx * 8, gh = P.gy * 8, FW = PF.gx * 8, FH = PF.gy * 8, div = gw > 0 && gh > 0 ? (int)settings13[11] : 1;
+  const UpParams UP = params ? up_params(params_from_words<dr_upscale_params>(params)) : UP_DEFAULTS;
+  const DnParams PRE = prefilter ? dn_params(params_from_words<dr_denoise_params>(prefilter)) : DnParams{};
+  const DnParams* const pre = prefilter ? &PRE : nullptr;
+  if (divide_by < 1) { hk_err = "upscale: divide_by must be >= 1"; return -1; }
+  hk_err = check_upscale_params(UP, pre);
+  if (!hk_err.empty()) return -1;
   if (nthreads < 1) nthreads = 1;
+  UpLaunch U;
+  memset(&U, 0, sizeof(U));
+  U.gw = P.gx * 8; U.gh = P.gy * 8; U.FW = PF.gx * 8; U.FH = PF.gy * 8; U.W = W; U.H = H;
+  U.div = U.gw > 0 && U.gh > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
+  U.U = UP;
+  U.acc = acc; U.hist = hist;
   HostLow low;
-  std::vector<float> fgz;
-  const bool guided = U.mode == UP_GUIDED && gw > 0 && gh > 0;
-  if (guided) {
+  std::vector<float> fguide, fgz;
+  if (UP.mode == UP_GUIDED && U.gw > 0 && U.gh > 0) {
     if (!normal || !albedo || !depth || !material || !fnormal || !falbedo || !fdepth || !fmaterial) { hk_err = "bad argument"; return -1; }
-    host_denoise_low(acc, H, divide_by, gw, gh, D, prefilter != nullptr, normal, albedo, depth, material, hist, m2, nthreads, low);
-    fgz.resize((size_t)FW * FH);
-    auto fm = [&](int x, int y) { return (x < 0 || y < 0 || x >= FW || y >= FH) ? DN_OUTSIDE : (int)fmaterial[(size_t)y * FW + x]; };
-    auto fz = [&](int x, int y) { return (x < 0 || y < 0 || x >= FW || y >= FH) ? 0.0f : fdepth[(size_t)y * FW + x]; };
-    host_rows(nthreads, FH, [&](int y) {
-      for (int x = 0; x < FW; x++)
-        fgz[(size_t)y * FW + x] = dn_gradient(fz(x, y), fm(x, y), fz(x - 1, y), fm(x - 1, y), fz(x + 1, y), fm(x + 1, y), fz(x, y - 1), fm(x, y - 1), fz(x, y + 1), fm(x, y + 1));
-    });
+    DnLaunch L;                                                             // the low side: the denoiser's planes
+    memset(&L, 0, sizeof(L));
+    L.gw = U.gw; L.gh = U.gh; L.W = W; L.H = H; L.divide_by = divide_by;
+    L.D = up_low_params(UP, pre);
+    L.acc = acc; L.hist = hist; L.m2 = m2;
+    L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
+    host_denoise_low(L, pre != nullptr, nthreads, low);
+    U.e = L.src; U.guide = L.guide; U.mat = L.mat;
+    DnLaunch G;                                                             // the full side: the guide prepare over the full grid
+    memset(&G, 0, sizeof(G));
+    G.gw = U.FW; G.gh = U.FH;
+    fguide.resize((size_t)4 * U.FW * U.FH); fgz.resize((size_t)U.FW * U.FH);
+    G.normal = fnormal; G.depth = fdepth; G.mat = fmaterial; G.guide = fguide.data(); G.gz = fgz.data();
+    host_grid(nthreads, G.gw, G.gh, [&](int x, int y) { dn_guide_pixel(G, x, y); });
+    U.Fguide = G.guide; U.Falbedo = falbedo; U.Fmat = fmaterial; U.Fgz = G.gz;
   }
-  host_rows(nthreads, H, [&](int Y) {
-    for (int X = 0; X < W; X++) {
-      const size_t o = ((size_t)Y * W + X) * 3;
-      float f[3] = {0.0f, 0.0f, 0.0f};
-      uint8_t rgb[3] = {0, 0, 0};
-      bool notap = false;
-      if (X < gw * div && Y < gh * div) {
-        const int qx = X / div, qy = Y / div;
-        if (U.mode == UP_BLOCK) {
-          up_block_colour(acc, hist, H, qx, qy, divide_by, f);
-          const size_t px = (size_t)qx * (size_t)H + (size_t)qy;
-          const int nd = dn_divisor(hist, px, divide_by);
-          for (int k = 0; k < 3; k++) rgb[k] = up_present8(acc[3 * px + k], nd);
-        } else {
-          const size_t p = (size_t)Y * FW + X;
-          const int mp = fmaterial[p];
-          const float ap[3] = {dn_albedo(falbedo[3 * p], mp, U.demodulate), dn_albedo(falbedo[3 * p + 1], mp, U.demodulate), dn_albedo(falbedo[3 * p + 2], mp, U.demodulate)};
-          const bool found = up_guided(U, div, X, Y, make_float4(fnormal[3 * p], fnormal[3 * p + 1], fnormal[3 * p + 2], fdepth[p]), mp, fgz[p], ap, [&](int tx, int ty) {
-            DnTap q;
-            if (tx < 0 || ty < 0 || tx >= gw || ty >= gh) { q.m = DN_OUTSIDE; q.c = make_float4(0, 0, 0, 0); q.g = q.c; return q; }
-            const size_t j = (size_t)ty * gw + tx;
-            q.c = low.e[j]; q.g = low.guide[j]; q.m = material[j];
-            return q;
-          }, f);
-          if (!found) { up_block_colour(acc, hist, H, qx, qy, divide_by, f); notap = true; }
-          for (int k = 0; k < 3; k++) rgb[k] = dn_rgb8(f[k]);
-        }
-      }
-      for (int k = 0; k < 3; k++) {
-        if (out_f32) out_f32[o + k] = f[k];
-        if (out_rgb8) out_rgb8[o + k] = rgb[k];
-      }
-      if (out_notap) out_notap[(size_t)Y * W + X] = notap ? 1 : 0;
-    }
+  U.out_f32 = out_f32; U.out_rgb8 = out_rgb8;
+  host_grid(nthreads, W, H, [&](int X, int Y) {
+    bool notap = false;
+    up_pixel(U, X, Y, &notap);
+    if (out_notap) out_notap[(size_t)Y * W + X] = notap ? 1 : 0;
   });
   return 0;
 }
@@ -617,45 +526,30 @@ int hk_reproject_m2(const int32_t* acc_from, const int32_t* hist_from, int W, in
   if (const char* why = fill_view_params(to_settings13, W, H, 0.0f, 0, 1, 0, Pt)) { hk_err = why; return -1; }
   if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { hk_err = "reproject: the two views have different divisors"; return -1; }
   if (frames < 1) { hk_err = "reproject: frames must be >= 1"; return -1; }
-  RpParams R = {32, 0.9f, 0.01f, 0xFFFFFFC3u, 1};
-  if (params) {                      // dr_reproject_params: int, float, float, uint32, int
-    memcpy(&R.max_history, params, 4); memcpy(&R.normal_cos, params + 1, 4); memcpy(&R.plane_tolerance, params + 2, 4);
-    memcpy(&R.material_mask, params + 3, 4); memcpy(&R.sky, params + 4, 4);
-  }
-  R.sky = R.sky != 0;
-  if (const char* why = check_reproject_params(R)) { hk_err = why; return -1; }
-  RpCamera to, fr;
-  RpProj J;
-  fill_reproject_camera(Pt, to);
-  fill_reproject_camera(Pf, fr);
-  if (!fill_reproject_proj(fr, J)) { hk_err = "reproject: the `from` view is degenerate"; return -1; }
-  const int gw = Pt.gx * 8, gh = Pt.gy * 8;
-  memset(acc_to, 0, (size_t)W * H * 3 * sizeof(int32_t));
+  RpLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.R = params ? rp_params(params_from_words<dr_reproject_params>(params)) : RP_DEFAULTS;
+  if (const char* why = check_reproject_params(L.R)) { hk_err = why; return -1; }
+  fill_reproject_camera(Pt, L.to);
+  fill_reproject_camera(Pf, L.from);
+  if (!fill_reproject_proj(L.from, L.J)) { hk_err = "reproject: the `from` view is degenerate"; return -1; }
+  L.gw = Pt.gx * 8; L.gh = Pt.gy * 8; L.W = W; L.H = H; L.frames = frames;
+  L.t_to = t_to; L.normal_to = normal_to; L.mat_to = mat_to;
+  L.t_from = t_from; L.normal_from = normal_from; L.mat_from = mat_from;
+  L.acc_from = acc_from; L.hist_from = hist_from; L.acc_to = acc_to; L.hist_to = hist_to;
+  L.m2_from = m2_from; L.m2_to = m2_to;
+  memset(acc_to, 0, (size_t)W * H * 3 * sizeof(int32_t));                   // (pixels outside the grid: the body writes every pixel of the grid)
   memset(hist_to, 0, (size_t)W * H * sizeof(int32_t));
   if (m2_to) memset(m2_to, 0, (size_t)W * H * sizeof(unsigned long long));
-  RpGuides Gt, Gf;
-  Gt.t = t_to; Gt.normal = normal_to; Gt.mat = mat_to;
-  Gf.t = t_from; Gf.normal = normal_from; Gf.mat = mat_from;
   if (nthreads < 1) nthreads = 1;
-  std::vector<long long> part((size_t)nthreads * 4, 0);
-  std::vector<std::thread> th;
-  for (int k = 0; k < nthreads; k++)
-    th.emplace_back([&, k] {
-      for (int y = k; y < gh; y += nthreads)
-        for (int x = 0; x < gw; x++) {
-          int qx = 0, qy = 0;
-          const int cls = rp_classify(R, to, fr, J, gw, gh, x, y, Gt, Gf, qx, qy);
-          part[(size_t)k * 4 + (size_t)cls]++;
-          if (cls != RP_VALID) continue;
-          const size_t q = (size_t)qx * (size_t)H + (size_t)qy, p = (size_t)x * (size_t)H + (size_t)y;
-          const int32_t hist_q = hist_from ? hist_from[q] : 0;
-          rp_carry(R, frames, acc_from + q * 3, hist_q, acc_to + p * 3, hist_to[p]);
-          if (m2_to) m2_to[p] = mo_carry(m2_from[q], (long long)hist_q + (long long)frames, R.max_history);
-        }
-    });
-  for (std::thread& t : th) t.join();
-  counts[0] = (long long)gw * gh;
-  for (int c = 0; c < 4; c++) { counts[1 + c] = 0; for (int k = 0; k < nthreads; k++) counts[1 + c] += part[(size_t)k * 4 + (size_t)c]; }
+  std::vector<long long> part((size_t)L.gh * 4, 0);                         // the classes of every row
+  host_rows(nthreads, L.gh, [&](int y) {
+    long long row[4] = {0, 0, 0, 0};
+    for (int x = 0; x < L.gw; x++) row[rp_pixel(L, x, y)]++;
+    memcpy(&part[(size_t)y * 4], row, sizeof(row));
+  });
+  counts[0] = (long long)L.gw * L.gh;
+  for (int c = 0; c < 4; c++) { counts[1 + c] = 0; for (int y = 0; y < L.gh; y++) counts[1 + c] += part[(size_t)y * 4 + (size_t)c]; }
   return 0;
 }
 
@@ -670,13 +564,7 @@ int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H
 // luma squared, for npix pixels, in place.
 int hk_moments_add(int32_t* acc, const int32_t* frame, unsigned long long* m2, long long npix) {
   if (!acc || !frame || !m2 || npix < 0) { hk_err = "bad argument"; return -1; }
-  for (long long p = 0; p < npix; p++) {
-    const int32_t r = frame[3 * p], g = frame[3 * p + 1], b = frame[3 * p + 2];
-    acc[3 * p] = (int32_t)((uint32_t)acc[3 * p] + (uint32_t)r);
-    acc[3 * p + 1] = (int32_t)((uint32_t)acc[3 * p + 1] + (uint32_t)g);
-    acc[3 * p + 2] = (int32_t)((uint32_t)acc[3 * p + 2] + (uint32_t)b);
-    m2[p] = mo_add(m2[p], mo_square(r, g, b));
-  }
+  for (long long p = 0; p < npix; p++) mo_add_pixel(acc, frame, m2, (size_t)p);
   return 0;
 }
 
@@ -691,34 +579,29 @@ int hk_error(const int32_t* acc, const int32_t* hist, const unsigned long long* 
   if (const char* why = fill_view_params(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
   if (divide_by < 0) { hk_err = "error: divide_by must be >= 0"; return -1; }
   if (!(tolerance >= 0.0f)) { hk_err = "error: tolerance must be >= 0"; return -1; }
-  const int gw = P.gx * 8, gh = P.gy * 8;
-  if (grid2) { grid2[0] = gw; grid2[1] = gh; }
+  MoLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by; L.tolerance = tolerance;
+  L.acc = acc; L.hist = hist; L.m2 = m2; L.out_sigma = out_sigma;
+  if (grid2) { grid2[0] = L.gw; grid2[1] = L.gh; }
   if (out_sigma) memset(out_sigma, 0, (size_t)W * H * sizeof(float));
   if (nthreads < 1) nthreads = 1;
-  std::vector<unsigned long long> part((size_t)nthreads * MO_WORDS, 0);
-  std::vector<std::thread> th;
-  for (int k = 0; k < nthreads; k++)
-    th.emplace_back([&, k] {
-      unsigned long long* cnt = part.data() + (size_t)k * MO_WORDS;
-      for (int y = k; y < gh; y += nthreads)
-        for (int x = 0; x < gw; x++) {
-          const size_t p = (size_t)x * (size_t)H + (size_t)y;
-          const int32_t* a = acc + p * 3;
-          const long long n = (long long)(hist ? hist[p] : 0) + (long long)divide_by;
-          double var = 0.0;
-          const bool est = mo_variance(a[0], a[1], a[2], m2[p], n, var);
-          const float sigma = est ? mo_sigma(var) : 0.0f;
-          if (out_sigma) out_sigma[(size_t)y * (size_t)W + (size_t)x] = sigma;
-          if (!est) continue;
-          cnt[MO_ESTIMATED]++;
-          if (sigma > tolerance) cnt[MO_ABOVE]++;
-          cnt[MO_SUM_VAR] += mo_var_q16(var);
-          cnt[MO_BIN0 + mo_bin(sigma)]++;
-        }
-    });
-  for (std::thread& t : th) t.join();
+  std::vector<unsigned long long> part((size_t)L.gh * MO_WORDS, 0);         // the counts of every row
+  host_rows(nthreads, L.gh, [&](int y) {
+    unsigned long long cnt[MO_WORDS] = {0};
+    for (int x = 0; x < L.gw; x++) {
+      double var;
+      float sigma;
+      if (!mo_error_pixel(L, x, y, var, sigma)) continue;
+      cnt[MO_ESTIMATED]++;
+      if (sigma > L.tolerance) cnt[MO_ABOVE]++;
+      cnt[MO_SUM_VAR] += mo_var_q16(var);
+      cnt[MO_BIN0 + mo_bin(sigma)]++;
+    }
+    memcpy(&part[(size_t)y * MO_WORDS], cnt, sizeof(cnt));
+  });
   if (result)
-    for (int w = 0; w < MO_WORDS; w++) { result[w] = 0; for (int k = 0; k < nthreads; k++) result[w] += part[(size_t)k * MO_WORDS + (size_t)w]; }
+    for (int w = 0; w < MO_WORDS; w++) { result[w] = 0; for (int y = 0; y < L.gh; y++) result[w] += part[(size_t)y * MO_WORDS + (size_t)w]; }
   return 0;
 }
 
