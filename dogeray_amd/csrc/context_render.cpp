@@ -79,16 +79,17 @@ void feedback_buffers(dr_context* c, const LaunchSite& site, const RenderParams&
   pcost = c->pixel_cost;
 }
 
-// The camera rays' grazing certificate of the launch's view: reuses the cached mask when the key matches, recomputes it on the site's
-// stream otherwise -- except in a pipelined launch that may run beside others reading the mask (site.hold_order): that one keeps the scene's margin.
-// Without a usable certificate P keeps cert_mask = null and wide_cert_k = 1: every ray carries the scene's margin, as before.
+// The camera rays' grazing certificate of the launch's view: reuses the cached mask and grades when the key matches, recomputes them on
+// the site's stream otherwise -- except in a pipelined launch that may run beside others reading them (site.hold_order): that one keeps the scene's margin.
+// Without a usable certificate P keeps cert_level = null and wide_cert_k = 1: every ray carries the scene's margin, as before.
 void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles) {
-  P.cert_mask = nullptr; P.wide_cert_k = 1.0f;
+  P.cert_level = nullptr;
+  for (float& k : P.wide_cert_k) k = 1.0f;
   if (!c->camera_cert || traversal_of(c) != DR_TRAVERSAL_WIDE || !c->wide || c->wide_own_bounds <= 0 || !(c->wide_mu.e > 0.0f) || tiles <= 0) return;
-  float key[21] = {0};
+  float key[22] = {0};
   memcpy(key, c->cur_settings, 13 * sizeof(float));
   key[13] = (float)P.W; key[14] = (float)P.H; key[15] = (float)P.stripe_mod; key[16] = (float)P.stripe_rem; key[17] = (float)P.ncols; key[18] = (float)P.gy;
-  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor;
+  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor; key[21] = (float)c->cert_levels;
   if (!(c->cert_valid && memcmp(c->cert_key, key, sizeof(key)) == 0)) {
     if (site.hold_order) return;
     // a single-frame launch of a view not seen before (a moving camera: every frame a new view) does not pay for the mask (0.16 ms, more than it
@@ -99,15 +100,16 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
     c->cert_valid = false;
     c->cert_ok = fill_cert_view(P, a_star, c->wide_mu.e, cv);
     if (c->cert_ok) {
-      if (c->cert_mask.grow((size_t)(tiles + 31) / 32 + 2, site.stream) != DR_OK) return;
-      launch_cert_mask(site.stream, c->prims, c->n_prims, cv, c->cert_mask, tiles);
-      c->cert_k = cert_factor_k(a_star);
+      cert_ladder(c->cert_factor, c->cert_levels != 0, cv);
+      if (c->cert_mask.grow(cert_mask_words(tiles, cv.n_levels), site.stream) != DR_OK || c->cert_level.grow(cert_level_words(tiles), site.stream) != DR_OK) return;
+      launch_cert_mask(site.stream, c->prims, c->n_prims, cv, c->cert_mask, c->cert_level, tiles);
+      for (int g = 1; g <= CERT_MAX_LEVELS; g++) c->cert_k[g] = g <= cv.n_levels ? cert_factor_k(cv.level_a[g - 1]) : 1.0f;
     }
     memcpy(c->cert_key, key, sizeof(key));
     c->cert_tiles = tiles;
     c->cert_valid = true;
   }
-  if (c->cert_ok) { P.cert_mask = c->cert_mask; P.wide_cert_k = c->cert_k; }
+  if (c->cert_ok) { P.cert_level = c->cert_level; memcpy(P.wide_cert_k, c->cert_k, sizeof(P.wide_cert_k)); }
 }
 
 }  // namespace

@@ -649,10 +649,13 @@ __device__ __forceinline__ WideRay wide_ray(V3 o, V3 d, V3 inv, float pmax, floa
 //    r_o (1 + (D + r_o) / (zmin - r_o) + Rmax (D + zmax) / (zmin (zmin - r_o))); in pixels a sample's jitter adds one, the float nu another: 1 (rect = tile columns
 //    [rect[0], rect[1]] of the LAUNCH and rows [rect[2], rect[3]]; an empty column range: none of the launch's tiles).
 // Any NaN gives 1 with every tile, or 2.  A triangle that did not enter with its own bounds (|e1| |e2| > e_own) needs nothing: 0.
-__device__ __forceinline__ int cert_leaf(const CertView& cv, const float* v0f, const float* e1f, const float* e2f, int* rect) {
+// Against a ladder (cv.level_a, ascending): *grade = the number of its steps A_T meets; all of them: 0 (the triangle constrains nobody), otherwise 1 / 2
+// as above, the tiles of rect (every tile) having grade <= *grade.  The single step a_star (fill_cert_view) is the rule above.
+__device__ __forceinline__ int cert_leaf(const CertView& cv, const float* v0f, const float* e1f, const float* e2f, int* rect, int* grade = nullptr) {
   double v0[3], e1[3], e2[3];
   for (int a = 0; a < 3; a++) { v0[a] = v0f[a]; e1[a] = e1f[a]; e2[a] = e2f[a]; }
   const double n1 = __builtin_sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), n2 = __builtin_sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+  if (grade) *grade = cv.n_levels;
   if (!(n1 * n2 <= cv.e_own)) return 0;
   double c[3], h[3], rc[3], n[3];
   double cn = 0, hn = 0;
@@ -677,7 +680,10 @@ __device__ __forceinline__ int cert_leaf(const CertView& cv, const float* v0f, c
   const double num = __builtin_fabs(rc[0] * n[0] + rc[1] * n[1] + rc[2] * n[2]) - (h[0] * __builtin_fabs(n[0]) + h[1] * __builtin_fabs(n[1]) + h[2] * __builtin_fabs(n[2])) - cv.r_o * nn;
   const double den = rcn + hn + cv.r_o;
   const double a_t = num > 0.0 ? cv.dmin * (num / den) * (1.0 - 1e-6) : 0.0;
-  if (a_t >= cv.a_star) return 0;
+  int g = 0;
+  while (g < cv.n_levels && a_t >= cv.level_a[g]) g++;
+  if (grade) *grade = g;
+  if (g == cv.n_levels) return 0;
   // ---- flagged: the tiles its box can be seen from
   const double zc = rc[0] * cv.w[0] + rc[1] * cv.w[1] + rc[2] * cv.w[2];
   const double zh = h[0] * __builtin_fabs(cv.w[0]) + h[1] * __builtin_fabs(cv.w[1]) + h[2] * __builtin_fabs(cv.w[2]);
@@ -890,12 +896,13 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
   wide_leaf_compute<COUNT>(r, o, d, inv, sg, tr, ws, stack, c);
 }
 template <bool COUNT>
-__device__ __forceinline__ Hit closest_hit_wide(WalkRsrc wide, float pmax, float mu_e, float mu_l, float mu_v, V3 o, V3 d, Ctr& c, int* __restrict__ stack /* [word * 64] */) {
+__device__ __forceinline__ Hit closest_hit_wide(WalkRsrc wide, float pmax, float mu_e, float mu_l, float mu_v, V3 o, V3 d, Ctr& c, int* __restrict__ stack /* [word * 64] */,
+                                                float cert = 1.0f /* wide_ray_margin's */) {
   Trav tr;
   trav_begin(tr);
   WideStack ws; ws.top = 0u; ws.sp = 0; ws.sb = 0;
   const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const WideRay wr = wide_ray(o, d, inv, pmax, mu_e, mu_l, mu_v);
+  const WideRay wr = wide_ray(o, d, inv, pmax, mu_e, mu_l, mu_v, cert);
   if (COUNT) c.rays++;
   while (tr.node >= 0) {
     const WideRec r = wide_fetch(wide, tr.node);
@@ -1252,7 +1259,7 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, int x, int y,
 
 // Kernel K:998-1093 for one pixel (the camera basis comes precomputed in P).
 template <bool COUNT, class Closest>
-__device__ __forceinline__ void render_pixel(const RenderParams& P, const Closest& closest, int x, int y, Ctr& c) {
+__device__ __forceinline__ void render_pixel(const RenderParams& P, const Closest& closest, int x, int y, Ctr& c, bool* camera_ray_next = nullptr /* set before every path: its first ray is a camera ray */) {
   V3 color = mk(0, 0, 0);
   for (int s = 0; (float)s < P.spp_f; ++s) {
     Xorwow rng;
@@ -1260,6 +1267,7 @@ __device__ __forceinline__ void render_pixel(const RenderParams& P, const Closes
     if (COUNT) c.samples++;
     V3 origin, dir;
     camera_ray(P, x, y, rng, origin, dir);
+    if (camera_ray_next) *camera_ray_next = true;
     color = color + trace_path<COUNT>(P, closest, origin, dir, rng, c);
   }
   store_pixel(P, x, y, color);

@@ -61,6 +61,9 @@ struct WideMu {
 // `from`; a small triangle that such a ray can be ACCEPTED on has its padded box on the ray, and the view gives a lower bound A_T of |d . (e1 x e2)| over
 // every such ray.  Triangles with A_T >= a_star certify nothing more is needed; the others set the bits of the tiles whose rays can reach their box.  A ray
 // of an unflagged tile therefore has |a^| >= a_star for every triangle it can be accepted on and carries the margin scaled by 1e-4 / a_star.
+// Graded (option cert_levels): the lemma holds for any a_star, so a triangle is measured against an ascending ladder level_a[0 .. n_levels) of them; its
+// GRADE is the number of steps A_T meets (0: none; n_levels: all, it constrains nobody) and a tile's grade is the lowest grade of the triangles its rays
+// can reach: its camera rays carry the margin of ladder step grade - 1 (grade 0: the scene's).  a_star = level_a[base]: the tile bit is "grade <= base".
 // All of it is double, filled on the host from the launch's float camera block (params_host.hpp fill_cert_view).
 struct CertView {
   double from[3];      // the camera centre (float P.from)
@@ -73,13 +76,16 @@ struct CertView {
   double eps_d;        // |d_f - d| for the float direction of a camera ray against the real one of the same (nu, nv, offset)
   double dmin;         // lower bound of |d_f| over all camera rays
   double den_w, den_h; // pixels per unit of nu / nv (P.den_w, P.den_h)
-  double a_star;       // the certified lower bound of |a^|
+  double a_star;       // the certified lower bound of |a^| (the tile bits' threshold: level_a[base])
+  double level_a[8];   // the ladder, ascending (fill_cert_view: the single step a_star; cert_ladder: the graded one)
+  int32_t n_levels, base;
   double e_own;        // triangles with |e1| |e2| above this did not enter the tree with their own bounds (WideMu e, widened)
   int32_t nx, ny;      // pixels of the rendered grid: 8 gx, 8 gy
   int32_t gy;          // tile rows (a tile's bit: local column * gy + row)
   int32_t stripe_mod, stripe_rem, ncols;      // the launch's block columns: global column = stripe_rem + local column * stripe_mod
 };
 
+constexpr int CERT_MAX_LEVELS = 7;                    // steps of the certificate's ladder at most (CertView level_a, RenderParams wide_cert_k)
 constexpr int WIDE_UNITS = 4;
 constexpr int WIDE_INDEX_BITS = 24;                   // records < 2^24 (1 GiB of them)
 constexpr int WIDE_STACK = 16;                        // stack words per lane kept in LDS (one more lives in a register)
@@ -176,8 +182,8 @@ struct RenderParams {
   uint32_t out_frame_stride;      // int32 words between the output buffers of two frames of a batch (0: one buffer for all: accumulation)
   int32_t region_start[9];        // identity order: region r owns tiles [region_start[r], region_start[r+1])
   WideMu wide_mu;                 // wide walk: the margin's scene constants (e = 0: none)
-  float wide_cert_k;              // ... the factor on it for camera rays of tiles the grazing certificate clears (>= 1e-4 / a_star; 1 without one)
-  const uint32_t* cert_mask;      // null, or one bit per tile of this launch (local column * gy + row): set = a camera ray of the tile may graze (carries wide_mu.e)
+  float wide_cert_k[CERT_MAX_LEVELS + 1];      // ... the factor on it for camera rays of a tile of grade g of the grazing certificate ([0] = 1: the scene's margin; [g] >= 1e-4 / level_a[g - 1])
+  const uint32_t* cert_level;     // null, or one byte per tile of this launch (local column * gy + row), four to a word: the tile's grade (0: a camera ray of the tile may graze)
 };
 
 // The denoiser's parameters (dr_denoise_params; defaults and ranges: params_host.hpp) and its material markers (device_denoise.hpp)

@@ -46,8 +46,11 @@ bool persistent_kernel_can_store_per_frame(const PersistentCfg& cfg);
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,
                           int heavy_factor, int split_steps, int split_limit);
 // the camera rays' grazing certificate of a view: mask = (ntiles + 31) / 32 words of tile bits (set: the tile's camera rays keep the scene's margin),
-// then the "every tile" word and the number of flagged tiles (device_core.hpp cert_leaf)
-void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, int ntiles);
+// then the "every tile" word, the number of flagged tiles and cv.n_levels scratch planes (cert_mask_words in all); level = a byte per tile, the tile's
+// grade on cv's ladder, cert_level_words words (device_core.hpp cert_leaf)
+inline size_t cert_mask_words(int ntiles, int n_levels) { return (size_t)((ntiles + 31) / 32) * (size_t)(1 + n_levels) + 2; }
+inline size_t cert_level_words(int ntiles) { return (size_t)((ntiles + 31) / 32) * 8; }
+void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, uint32_t* level, int ntiles);
 // hist: the history plane (int32 per pixel at x * H + y; the divisor of pixel p is hist[p] + div, a divisor of 0 gives 0), or null: acc / div
 void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div);
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n);      // acc += frame (pipelined single frames)

@@ -368,8 +368,10 @@ __global__ __launch_bounds__(256) void frame_add_kernel(int4* __restrict__ acc, 
 
 // ------------------------------------------------------------------ launchers
 // Per-view grazing certificate of the camera rays (option camera_cert): one thread per primitive (slot order); a small triangle whose
-// bound A_T of |d . (e1 x e2)| over the view's camera rays is below a_star sets the bits of the launch's tiles that can see its padded box
-// (device_core.hpp cert_leaf).  mask: words [0, nwords) = one bit per tile, word nwords = "every tile", word nwords + 1 = flagged tiles (cert_finish_kernel).
+// bound A_T of |d . (e1 x e2)| over the view's camera rays meets only g < n_levels steps of the view's ladder sets, in bit plane g, the bits of the
+// launch's tiles that can see its padded box (device_core.hpp cert_leaf).  mask: words [0, nwords) = one bit per tile (flagged at a_star: a bit in a
+// plane g <= cv.base), word nwords = "every tile", word nwords + 1 = flagged tiles, then the n_levels planes of nwords words each; the first
+// nwords + 2 words and the level bytes are cert_finish_kernel's.
 __global__ __launch_bounds__(256) void cert_mask_kernel(const DevPrim* __restrict__ prims, int n, CertView cv, uint32_t* __restrict__ mask, int nwords) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -377,29 +379,50 @@ __global__ __launch_bounds__(256) void cert_mask_kernel(const DevPrim* __restric
   if (p.type != 2) return;
   const float e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
   int rect[4] = {0, -1, 0, -1};
-  const int k = cert_leaf(cv, p.v0, e1, e2, rect);
+  int g = 0;
+  const int k = cert_leaf(cv, p.v0, e1, e2, rect, &g);
   if (k == 0) return;
   if (k == 2) { atomicOr(&mask[nwords], 1u); return; }
+  uint32_t* const plane = mask + nwords + 2 + (size_t)g * (size_t)nwords;
   for (int col = rect[0]; col <= rect[1]; col++) {
     const int b0 = col * cv.gy + rect[2], b1 = col * cv.gy + rect[3];      // bits [b0, b1]: one run per column
     for (int w = b0 >> 5; w <= (b1 >> 5); w++) {
       const int lo = w * 32 > b0 ? 0 : b0 - w * 32, hi = w * 32 + 31 < b1 ? 31 : b1 - w * 32;
       const uint32_t bits = (hi == 31 ? ~0u : ((1u << (hi + 1)) - 1u)) & ~((1u << lo) - 1u);
-      if ((mask[w] & bits) != bits) atomicOr(&mask[w], bits);      // (neighbouring grazing triangles flag the same tiles: most words are set already)
+      if ((plane[w] & bits) != bits) atomicOr(&plane[w], bits);      // (neighbouring grazing triangles flag the same tiles: most words are set already)
     }
   }
 }
-// one workgroup: "every tile" -> all bits; the number of flagged tiles into word nwords + 1
-__global__ __launch_bounds__(1024) void cert_finish_kernel(uint32_t* __restrict__ mask, int ntiles, int nwords) {
+// one workgroup: the planes -> the tile bits (planes 0 .. base) and a tile's grade, one byte per tile in `level` (8 words per mask word: the lowest plane
+// with its bit, n_levels without one; bytes past the last tile 0); "every tile" -> all bits and grade 0; the number of flagged tiles into word nwords + 1
+__global__ __launch_bounds__(1024) void cert_finish_kernel(uint32_t* __restrict__ mask, uint32_t* __restrict__ level, int ntiles, int nwords, int n_levels, int base) {
   __shared__ unsigned part[16];
   const bool all = mask[nwords] != 0u;
   unsigned cnt = 0;
   for (int w = threadIdx.x; w < nwords; w += 1024) {
     const int left = ntiles - w * 32;
     const uint32_t valid = left >= 32 ? ~0u : ((1u << left) - 1u);
-    uint32_t v = mask[w] & valid;
-    if (all) { v = valid; mask[w] = v; }
+    uint32_t pl[CERT_MAX_LEVELS];
+    uint32_t v = 0u;
+    for (int g = 0; g < CERT_MAX_LEVELS; g++) {
+      pl[g] = g < n_levels ? mask[nwords + 2 + (size_t)g * (size_t)nwords + w] : 0u;
+      if (g <= base) v |= pl[g];
+    }
+    v &= valid;
+    if (all) v = valid;
+    mask[w] = v;
     cnt += (unsigned)__popc(v);
+    for (int q = 0; q < 8; q++) {
+      uint32_t word = 0u;
+      for (int b = 0; b < 4; b++) {
+        const int bit = q * 4 + b;
+        unsigned grade = (unsigned)n_levels;
+        for (int g = CERT_MAX_LEVELS - 1; g >= 0; g--) if ((pl[g] >> bit) & 1u) grade = (unsigned)g;
+        if (all || !((valid >> bit) & 1u)) grade = 0u;
+        word |= grade << (8 * b);
+      }
+      level[w * 8 + q] = word;
+    }
   }
   for (int off = 32; off > 0; off >>= 1) cnt += (unsigned)__shfl_xor((int)cnt, off, 64);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
@@ -411,11 +434,11 @@ __global__ __launch_bounds__(1024) void cert_finish_kernel(uint32_t* __restrict_
   }
 }
 
-void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, int ntiles) {
+void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, uint32_t* level, int ntiles) {
   const int nwords = (ntiles + 31) / 32;
-  (void)hipMemsetAsync(mask, 0, (size_t)(nwords + 2) * sizeof(uint32_t), stream);
+  (void)hipMemsetAsync(mask, 0, cert_mask_words(ntiles, cv.n_levels) * sizeof(uint32_t), stream);
   if (n > 0) hipLaunchKernelGGL(cert_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, prims, n, cv, mask, nwords);
-  hipLaunchKernelGGL(cert_finish_kernel, dim3(1), dim3(1024), 0, stream, mask, ntiles, nwords);
+  hipLaunchKernelGGL(cert_finish_kernel, dim3(1), dim3(1024), 0, stream, mask, level, ntiles, nwords, cv.n_levels, cv.base);
 }
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,
                           int heavy_factor, int split_steps, int split_limit) {

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   // the part of the scene that band sees instead of competing for all of it -- and helps the next band
   // once its own is empty.  Region r owns positions [region_start[r], region_start[r+1]) of the order.
   int cur_tile = ntiles, cur_frame = 0;        // chunk being handed out; ntiles = none
-  bool cur_cert = false;           // lean build: the camera rays of cur_tile may carry the certified margin (its bit in P.cert_mask is clear; wave-uniform)
+  unsigned cur_cert = 0u;          // lean build: the grade of cur_tile in the view's grazing certificate (its byte of P.cert_level; 0: its camera rays keep the scene's margin; wave-uniform)
   int cur_next = 64;               // next unassigned lane-in-tile of cur_tile (64 = exhausted: fetch first)
   int cur_limit = 64;              // ... and where this wave's share of cur_tile ends (split tiles: a part of the tile)
   bool cur_split = false;
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         if (!held && tr.node == -3 && share < 0 && !(cur_tile >= ntiles && regions_left == 0)) { tr.node = -2; want_pixel = true; }
       }
       unsigned long long need = __ballot(want_pixel);
-      bool cam_cert = false;                       // lean build: this lane's pixel came from a certified tile in this phase
+      unsigned cam_cert = 0u;                      // lean build: the grade of the tile this lane's pixel came from in this phase
       while (need != 0ull) {
         if (cur_next >= cur_limit) {               // wave-uniform: fetch the next chunk (tile, frame)
           if (WIDE && COOP && held) {              // holding: no new tile, the lanes asking become helpers
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
                 tt -= nsplit * (P.split_parts - 1);
               }
               cur_tile = tile_order ? tile_order[r0 + tt] : r0 + tt;
-              if (BOUNCE_HOME) cur_cert = P.cert_mask != nullptr && ((P.cert_mask[cur_tile >> 5] >> (cur_tile & 31)) & 1u) == 0u;
+              if (BOUNCE_HOME) cur_cert = P.cert_level != nullptr ? (P.cert_level[cur_tile >> 2] >> ((cur_tile & 3) * 8)) & 0xffu : 0u;
               break;
             }
             region = region + 1 == P.regions ? 0 : region + 1;   // this band is done: help with the next one
@@ -394,9 +394,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           fresh_ray = true;
         }
       }
-      // lean build: byte 1 of stash word 1 (beside the stack pointer) says whether the lane's ray is a camera ray of a tile the view's grazing
-      // certificate clears; written with every new ray, read with the stack pointer at the restore
-      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + 1 * 64)[1] = (unsigned char)(new_path && cam_cert ? 1 : 0);
+      // lean build: byte 1 of stash word 1 (beside the stack pointer) is the certificate's grade of the lane's ray: its tile's for a camera ray, 0 for
+      // any other; written with every new ray, read with the stack pointer at the restore
+      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + 1 * 64)[1] = (unsigned char)(new_path ? cam_cert : 0u);
       if (COUNT && ray_log && fresh_ray && frame == 0) {      // measurement aid (dr_context_probe_trace): the rays the launch's first frame traces, in the
         // order a per-bounce wavefront would hold them: bounce by bounce, pixels in tile order.  Statistics words 40-42 = rays logged, the log, its room (entries)
         atomicAdd(&P.counters[40], 1ull);
@@ -420,8 +420,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         color = mk(0, 0, 0); px = -1; py = 0; pcode = 0; sample = 0; frame = 0;
         if (fresh_ray) { ws.top = 0u; ws.sp = 0; ws.sb = 0; }
         inv = mk(1.0f / path.raydir.x, 1.0f / path.raydir.y, 1.0f / path.raydir.z);      // 1/direction and the folded test's margins are
-        // (a camera ray of a tile the view's grazing certificate clears -- byte 1 of word 1 -- carries E scaled by 1e-4 / a_star: DESIGN.md 4.10)
-        const float cert = (BOUNCE_HOME && (w1 & 0xff00) != 0) ? P.wide_cert_k : 1.0f;
+        // (a camera ray of a tile of grade g in the view's grazing certificate -- byte 1 of word 1 -- carries E scaled by 1e-4 / a_star of ladder step g - 1,
+        // grade 0 by 1: DESIGN.md 4.10)
+        const float cert = BOUNCE_HOME ? P.wide_cert_k[(w1 >> 8) & CERT_MAX_LEVELS] : 1.0f;
         wr = wide_ray(path.rayo, path.raydir, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, cert);                // recomputed for every lane rather than stashed
         sg = sign_mask(inv);
       } else {

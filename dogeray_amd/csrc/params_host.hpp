@@ -99,6 +99,7 @@ inline bool fill_cert_view(const RenderParams& P, double a_star, float e_own, Ce
   cv.dmin = cv.D - cv.r_o - 1e-9 * (norm(hor) + norm(ver)) - cv.eps_d;
   cv.den_w = P.den_w; cv.den_h = P.den_h;
   cv.a_star = a_star;
+  cv.level_a[0] = a_star; cv.n_levels = 1; cv.base = 0;      // (the single step; cert_ladder sets the graded one)
   cv.e_own = (double)e_own * (1.0 + 1e-6);
   cv.nx = 8 * P.gx; cv.ny = 8 * P.gy; cv.gy = P.gy;
   cv.stripe_mod = P.stripe_mod; cv.stripe_rem = P.stripe_rem; cv.ncols = P.ncols;
@@ -167,6 +168,17 @@ inline const char* check_reproject_params(const RpParams& R) {
   if (!(R.normal_cos >= -1.0f && R.normal_cos <= 1.0f)) return "reproject: normal_cos must be -1 .. 1";
   if (!(R.plane_tolerance >= 0.0f)) return "reproject: plane_tolerance must be >= 0";
   return nullptr;
+}
+
+// The certificate's ladder for option cert_factor (CertView level_a, ascending; a_star stays level_a[base] = 1e-4 cert_factor): graded, cert_factor x
+// {1/4, 1/2, 1, 2, 4}, each step at least the 1e-4 cut-off itself (the lemma needs a_star >= 1e-4); otherwise the single step cert_factor.
+inline void cert_ladder(int cert_factor, bool graded, CertView& cv) {
+  const double mult[5] = {0.25, 0.5, 1.0, 2.0, 4.0};
+  cv.n_levels = graded ? 5 : 1; cv.base = graded ? 2 : 0;
+  for (int g = 0; g < cv.n_levels; g++) {
+    const double f = (double)cert_factor * (graded ? mult[g] : 1.0);
+    cv.level_a[g] = 1e-4 * (f > 1.0 ? f : 1.0);
+  }
 }
 
 // The factor a certified camera ray's |d|-proportional margin carries: 1e-4 / a_star, rounded up (step 2 divides by a_star instead of 1e-4)

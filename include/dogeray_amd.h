@@ -195,6 +195,10 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   lean and counting builds of the persistent kernel, for the first sample of each pixel (spp > 1: later samples keep the scene's
  *                   margin); a single-frame launch of a view not seen before computes no mask
  *   "cert_factor"   the certified |d . (e1 x e2)| in units of the 1e-4 cut-off (default 40)
+ *   "cert_levels"   1 (default): the certificate is graded.  Every tile is measured against the ladder cert_factor x {1/4, 1/2, 1, 2, 4} (10, 20, 40,
+ *                   80, 160 at the default factor; every step at least 1) and its camera rays carry the margin of the highest step it passes, the
+ *                   scene's margin when it passes none (dr_stats_cert_levels); 0 one step, cert_factor: a tile passes it or keeps the scene's
+ *                   margin.  The same bits either way
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
@@ -591,6 +595,12 @@ int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n);
  * that launch (bit t of word t / 32; tile = local block column * tile rows + row), set = the tile's camera rays keep the scene's margin.
  * *n_tiles = 0 when no certificate is in use; otherwise the tiles, and the first min(max_words, (n_tiles + 31) / 32) words are copied to out. */
 int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles);
+/* The grades of the same view's tiles (option cert_levels): one byte per tile, tile = local block column * tile rows + row.  0: the tile's camera rays
+ * keep the scene's margin; g >= 1: the tile passes the ladder's steps 0 .. g - 1 and its camera rays carry the margin of step g - 1 (with cert_levels
+ * = 1 the steps are cert_factor x {1/4, 1/2, 1, 2, 4}, grades 0 .. 5, and the tile's bit in dr_stats_cert_mask is set exactly when its grade is below
+ * 3; with cert_levels = 0 the one step is cert_factor, grades 0 and 1).  *n_tiles = 0 when no certificate is in use; otherwise the tiles, and the
+ * first min(max, n_tiles) bytes are copied to out_bytes. */
+int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tiles);
 
 /* Timeline of the last SHORT persistent-kernel launch (fewer than coop_tiles_per_wave tiles per wave: one frame, a thin stripe;
  * option "wave_log" = 1 before the launch): sixteen words per wave --

@@ -35,11 +35,15 @@ namespace {
 struct HkScene {
   dr_scene* scene = nullptr;
   DeviceImage img;
+  DeviceImage own;          // the product's default image (wide_tree = 2: small triangles with their own bounds), built when a render asks for it
+  bool has_own = false;
 };
 thread_local std::string hk_err;
 
+// plane / ktab (null: none): the grades of the view's grazing certificate, a byte per tile, and the margin's factor per grade -- the camera ray of
+// every path of a tile carries its tile's factor, as the lean build's do (kernels_render.hip; there for a pixel's first sample)
 template <bool COUNT>
-void render_columns(const RenderParams& P, int traversal, int first, int step, Ctr& total) {
+void render_columns(const RenderParams& P, int traversal, int first, int step, Ctr& total, const uint8_t* plane = nullptr, const float* ktab = nullptr) {
   std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
   Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
   const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
@@ -49,8 +53,14 @@ void render_columns(const RenderParams& P, int traversal, int first, int step, C
       for (int lane = 0; lane < 64; lane++) {                       // lane l of a tile is pixel (l >> 3, l & 7), as in the kernels
         const int x = bx * 8 + (lane >> 3), y = by * 8 + (lane & 7);
         if (traversal == DR_TRAVERSAL_WIDE && P.wide) {
-          auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_wide<COUNT>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, o, d, cc, stack.data()); };
-          render_pixel<COUNT>(P, closest, x, y, c);
+          bool camera = false;
+          const float kt = plane ? ktab[plane[(size_t)col * (size_t)P.gy + (size_t)by] & CERT_MAX_LEVELS] : 1.0f;
+          auto closest = [&](V3 o, V3 d, Ctr& cc) {
+            const float k = camera ? kt : 1.0f;
+            camera = false;
+            return closest_hit_wide<COUNT>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, o, d, cc, stack.data(), k);
+          };
+          render_pixel<COUNT>(P, closest, x, y, c, plane ? &camera : nullptr);
         } else if (traversal == DR_TRAVERSAL_ORDERED) {
           auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_ordered<COUNT>(P.pairs, P.prims, o, d, cc, stack.data()); };
           render_pixel<COUNT>(P, closest, x, y, c);
@@ -268,6 +278,98 @@ int hk_cert_check(void* hv, const float* settings13, int W, int H, double a_star
   }
   return 0;
 }
+// The graded certificate of one view (option cert_levels): the grades of its tiles as kernels_aux.hip builds them -- the same cert_leaf
+// against the ladder of cert_factor (params_host.hpp cert_ladder; graded = 0: the single step) -- and hk_cert_check's sampling check per step: a
+// camera ray that enters the padded box of a triangle of grade g must have |d . (e1 x e2)| >= the ladder's step g - 1 (g >= 1), and lie in a tile whose
+// grade is <= g (g < n_levels).  out[0..3]: rays through boxes of grade >= 1, of them below their step (must be 0), rays through boxes of grade
+// < n_levels, of them in tiles of a higher grade (must be 0); out[4] n_levels, out[5] tiles, out[6] "every tile", out[7] base; out[8 + g] tiles of
+// grade g, out[16 + g] rays through boxes of grade g (g = 0 .. 7).  plane_out (may be NULL): the grades, a byte per tile.  Returns 0, or -1.
+int hk_cert_levels(void* hv, const float* settings13, int W, int H, int cert_factor, int graded, float e_own, long long n_samples, uint64_t seed, long long* out,
+                   uint8_t* plane_out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || !out || cert_factor < 1) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 1, 1, 0, P)) { hk_err = why; return -1; }
+  CertView cv;
+  if (!fill_cert_view(P, 1e-4 * (double)cert_factor, e_own, cv)) { hk_err = "the view gives no certificate"; return -1; }
+  cert_ladder(cert_factor, graded != 0, cv);
+  const std::vector<DevPrim>& prims = h->img.prims;
+  const int tiles = P.ncols * P.gy, nl = cv.n_levels;
+  std::vector<uint8_t> plane((size_t)tiles, (uint8_t)nl);
+  std::vector<int> grade(prims.size(), nl);
+  bool every = false;
+  for (size_t i = 0; i < prims.size(); i++) {
+    const DevPrim& p = prims[i];
+    if (p.type != 2) continue;
+    const float e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
+    int rect[4] = {0, -1, 0, -1};
+    int g = nl;
+    const int k = cert_leaf(cv, p.v0, e1, e2, rect, &g);
+    if (k == 2) { every = true; g = 0; }
+    grade[i] = k == 0 ? nl : g;
+    if (k == 1)
+      for (int col = rect[0]; col <= rect[1]; col++)
+        for (int r = rect[2]; r <= rect[3]; r++) { uint8_t& b = plane[(size_t)col * cv.gy + r]; if (g < b) b = (uint8_t)g; }
+  }
+  if (every) std::fill(plane.begin(), plane.end(), (uint8_t)0);
+  if (plane_out) memcpy(plane_out, plane.data(), plane.size());
+  for (int k = 0; k < 24; k++) out[k] = 0;
+  out[4] = nl; out[5] = tiles; out[6] = every; out[7] = cv.base;
+  for (uint8_t b : plane) out[8 + b]++;
+  uint64_t st = seed * 0x9E3779B97F4A7C15ull + 1;
+  auto rnd = [&st]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return (double)(st >> 11) * 0x1p-53; };
+  std::vector<size_t> tri, low;      // own-bounds triangles; of them the ones that constrain a tile
+  for (size_t i = 0; i < prims.size(); i++) {
+    const DevPrim& p = prims[i];
+    const double n1 = std::sqrt((double)p.e1x * p.e1x + (double)p.e1y * p.e1y + (double)p.e1z * p.e1z), n2 = std::sqrt((double)p.e2x * p.e2x + (double)p.e2y * p.e2y + (double)p.e2z * p.e2z);
+    if (p.type == 2 && n1 * n2 <= cv.e_own) { tri.push_back(i); if (grade[i] < nl) low.push_back(i); }
+  }
+  if (tri.empty()) return 0;
+  for (long long s = 0; s < n_samples; s++) {
+    const bool pick_low = !low.empty() && (s & 1);
+    const size_t i = pick_low ? low[(size_t)(rnd() * (double)low.size()) % low.size()] : tri[(size_t)(rnd() * (double)tri.size()) % tri.size()];
+    const DevPrim& p = prims[i];
+    const double v0[3] = {p.v0[0], p.v0[1], p.v0[2]}, e1[3] = {p.e1x, p.e1y, p.e1z}, e2[3] = {p.e2x, p.e2y, p.e2z};
+    float mn[3], mx[3];
+    double X[3];
+    for (int a = 0; a < 3; a++) {
+      const double lo = std::min(v0[a], std::min(v0[a] + e1[a], v0[a] + e2[a])) - 0.01, hi = std::max(v0[a], std::max(v0[a] + e1[a], v0[a] + e2[a])) + 0.01;
+      mn[a] = (float)lo; mx[a] = (float)hi;
+      X[a] = lo + (hi - lo) * rnd();
+    }
+    double rel[3], z = 0;                      // the pixel X projects to through the pinhole
+    for (int a = 0; a < 3; a++) { rel[a] = X[a] - cv.from[a]; z += rel[a] * cv.w[a]; }
+    if (!(z > 0)) continue;
+    double pl[3];
+    for (int a = 0; a < 3; a++) pl[a] = cv.from[a] + rel[a] * (cv.D / z) - cv.llc[a];
+    const double nu = cv.du[0] * pl[0] + cv.du[1] * pl[1] + cv.du[2] * pl[2], nv = cv.dv[0] * pl[0] + cv.dv[1] * pl[1] + cv.dv[2] * pl[2];
+    const double fx = std::floor(nu * cv.den_w) + (double)((int)(rnd() * 3.0) - 1), fy = std::floor(nv * cv.den_h) + (double)((int)(rnd() * 3.0) - 1);
+    if (!(fx >= 0 && fy >= 0 && fx < cv.nx && fy < cv.ny)) continue;
+    const int x = (int)fx, y = (int)fy;
+    Xorwow rng;
+    rng.init(sample_seed(P, x, y, 0, (int)(rnd() * 1000.0)));
+    V3 o, d;
+    camera_ray(P, x, y, rng, o, d);
+    const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    float dist = 0;
+    if (!slab(o, inv, mn, mx, dist) || !(dist > -0.01f)) continue;
+    const int g = grade[i];
+    out[16 + g]++;
+    if (g >= 1) {
+      const double dd[3] = {d.x, d.y, d.z};
+      const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+      const double a = std::fabs(dd[0] * nx + dd[1] * ny + dd[2] * nz);
+      out[0]++;
+      if (!(a >= cv.level_a[g - 1])) out[1]++;
+    }
+    if (g < nl) {
+      out[2]++;
+      if (plane[(size_t)(x >> 3) * cv.gy + (size_t)(y >> 3)] > g) out[3]++;
+    }
+  }
+  return 0;
+}
 // the same with the certificate's factor (wide_ray_margin's last argument: 1e-4 / a_star for a certified camera ray, 1 otherwise)
 void hk_ray_margin_k(long long n, const float* o, const float* d, float e, float l, float v, float k, float* out) {
   for (long long i = 0; i < n; i++) out[i] = wide_ray_margin(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), e, l, v, k);
@@ -323,15 +425,31 @@ int hk_wide_depth(void* hv) { return ((HkScene*)hv)->img.wide.empty() ? 0 : ((Hk
 
 // One frame (dr_render_frame's arguments): int32[W * H * 3], pixel (x, y) at (x * H + y) * 3, unrendered margins 0; only the block
 // columns bx % col_mod == col_rem are rendered (a bounded sample for the bench).  counters: rays, V, L, S, T, samples (6 words).
+// level_plane (may be NULL): the grades of the view's graded certificate (hk_cert_levels' plane_out for cert_factor / graded, whole frame: col_mod 1) --
+// the frame is then rendered as the device renders it: the wide walk over the product's default tree (wide_tree = 2), the camera rays with their
+// tile's margin.
 int hk_render(void* hv, const float* settings13, int W, int H, float background, uint64_t frame_seed, int traversal, int nthreads, int col_mod, int col_rem,
-              int32_t* out, uint64_t* counters) {
+              int32_t* out, uint64_t* counters, const uint8_t* level_plane, int cert_factor, int graded) {
   HkScene* h = (HkScene*)hv;
   if (!h || !settings13 || !out || col_mod < 1 || col_rem < 0 || col_rem >= col_mod) { hk_err = "bad argument"; return -1; }
+  float ktab[CERT_MAX_LEVELS + 1];
+  for (float& k : ktab) k = 1.0f;
+  if (level_plane) {
+    if (col_mod != 1 || cert_factor < 1 || traversal != DR_TRAVERSAL_WIDE) { hk_err = "a level plane needs the whole frame, its cert_factor and the wide walk"; return -1; }
+    if (!h->has_own) {
+      if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+      h->has_own = true;
+    }
+    CertView cv;
+    cert_ladder(cert_factor, graded != 0, cv);
+    for (int g = 1; g <= cv.n_levels; g++) ktab[g] = cert_factor_k(cv.level_a[g - 1]);
+  }
   RenderParams P;
   memset(&P, 0, sizeof(P));
   if (const char* why = fill_view_params(settings13, W, H, background, frame_seed, col_mod, col_rem, P)) { hk_err = why; return -1; }
-  const DeviceImage& img = h->img;
+  const DeviceImage& img = level_plane ? h->own : h->img;
   if (P.backtex >= (int)img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
+  if (level_plane && img.wide.empty()) { hk_err = "the scene has no wide tree"; return -1; }
   P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
   P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
   P.pairs = img.pairs.data(); P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
@@ -342,7 +460,10 @@ int hk_render(void* hv, const float* settings13, int W, int H, float background,
   std::vector<Ctr> part((size_t)nthreads);
   std::vector<std::thread> th;
   for (int t = 0; t < nthreads; t++)
-    th.emplace_back([&, t] { if (counters) render_columns<true>(P, traversal, t, nthreads, part[(size_t)t]); else render_columns<false>(P, traversal, t, nthreads, part[(size_t)t]); });
+    th.emplace_back([&, t] {
+      if (counters) render_columns<true>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab);
+      else render_columns<false>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab);
+    });
   for (std::thread& t : th) t.join();
   if (counters) {
     for (int k = 0; k < 6; k++) counters[k] = 0;

@@ -54,7 +54,10 @@ def lib():
         L.hk_tri_hit.argtypes = [C.c_longlong] + [C.c_void_p] * 6
         L.hk_check_reject.restype = C.c_longlong
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
-        L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int, C.c_int]
+        L.hk_cert_levels.restype = C.c_int
+        L.hk_cert_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong, C.c_uint64, C.c_void_p, C.c_void_p]
         L.hk_aov.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 9
         L.hk_denoise.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         L.hk_camera_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -89,16 +92,39 @@ class Scene:
     def wide_depth(self):
         return int(lib().hk_wide_depth(self.h))
 
-    def render(self, settings13, W, H, background, frame_seed, traversal=2, nthreads=1, col_mod=1, col_rem=0, count=True):
-        """One frame: (int32[W, H, 3] indexed [x, y], counters dict or None)."""
+    def render(self, settings13, W, H, background, frame_seed, traversal=2, nthreads=1, col_mod=1, col_rem=0, count=True, level_plane=None, cert_factor=40,
+               graded=1):
+        """One frame: (int32[W, H, 3] indexed [x, y], counters dict or None).  level_plane: the grades of the view's grazing certificate
+        (cert_levels()[0] for the same cert_factor / graded) -- the frame is rendered over the default tree with the camera rays' certified margins."""
         st = np.ascontiguousarray(settings13, dtype=np.float32)
         out = np.zeros((W, H, 3), dtype=np.int32)
         ctr = (C.c_uint64 * 6)()
+        plane = np.ascontiguousarray(level_plane, dtype=np.uint8) if level_plane is not None else None
         rc = lib().hk_render(self.h, st.ctypes.data, W, H, float(background), int(frame_seed) & (2 ** 64 - 1), traversal, nthreads, col_mod, col_rem,
-                             out.ctypes.data, C.cast(ctr, C.c_void_p) if count else None)
+                             out.ctypes.data, C.cast(ctr, C.c_void_p) if count else None,
+                             plane.ctypes.data if plane is not None else None, int(cert_factor), int(graded))
         if rc != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return out, (dict(zip(("rays", "V", "L", "S", "T", "samples"), [int(v) for v in ctr])) if count else None)
+
+    def wide_mu(self):
+        """(own-bounds triangles, float32 (e, l, v)) of the product's default tree (hk_wide_mu)."""
+        mu = np.zeros(3, np.float32)
+        return int(lib().hk_wide_mu(self.h, mu.ctypes.data)), mu
+
+    def cert_levels(self, settings13, W, H, cert_factor=40, graded=1, e_own=1e30, n_samples=0, seed=1):
+        """The graded grazing certificate of a view on the host (hk_cert_levels): (uint8 grades, a byte per tile, and a dict of the sampling check's
+        counts), or None when the view gives no certificate."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        div = int(st[11]) if np.isfinite(st[11]) and st[11] >= 1 else 1
+        plane = np.zeros((W // div // 8) * (H // div // 8), np.uint8)
+        out = np.zeros(24, np.int64)
+        if lib().hk_cert_levels(self.h, st.ctypes.data, W, H, int(cert_factor), int(graded), C.c_float(e_own), int(n_samples), int(seed), out.ctypes.data,
+                                plane.ctypes.data) != 0:
+            return None
+        return plane, {"rays_certified": int(out[0]), "below_step": int(out[1]), "rays_constrained": int(out[2]), "tile_above": int(out[3]),
+                       "n_levels": int(out[4]), "tiles": int(out[5]), "every": int(out[6]), "base": int(out[7]),
+                       "tiles_per_grade": [int(v) for v in out[8:16]], "rays_per_grade": [int(v) for v in out[16:24]]}
 
     def aov(self, settings13, W, H, window=None, traversal=2, nthreads=4):
         """dr_render_aov on the host (device_core.hpp aov_first_hit): every channel of the window (x0, y0, w, h) of the pixel grid
