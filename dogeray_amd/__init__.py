@@ -199,6 +199,7 @@ _API = [
     ("dr_kat_optics", C.c_int, [_VP, C.c_int] + [_VP] * 6),
     ("dr_kat_hit", C.c_int, [_VP, C.c_int] + [_VP] * 5),
     ("dr_kat_normal", C.c_int, [_VP, C.c_int] + [_VP] * 6),
+    ("dr_kat_trace", C.c_int, [_VP, C.c_int, C.c_int] + [_VP] * 4),
     ("dr_stats_tile_order", C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t), _VP, _VP]),
     ("dr_kat_tile_feedback", C.c_int, [_VP] + [C.c_int] * 5 + [_VP] * 4),
 ]
@@ -919,6 +920,16 @@ class Context:
         vis = np.zeros(n, dtype=np.int32) if want_visits else None
         _check(lib().dr_kat_hit(self._h, n, _p(o), _p(d), _p(t), _p(idx), _p(vis) if want_visits else None))
         return (t, idx, vis) if want_visits else (t, idx)
+
+    def kat_trace(self, o, d, variant=0):
+        """kat_hit's rays through the lean build of the wide walk (dr_kat_trace): variant 0 one ray per lane, 1..7 the persistent trace-only kernel.
+        (t, idx) in kat_hit's convention."""
+        o, d = _f32(o), _f32(d)
+        n = o.shape[0]
+        t = np.zeros(n, dtype=np.float32)
+        idx = np.zeros(n, dtype=np.int32)
+        _check(lib().dr_kat_trace(self._h, int(variant), n, _p(o), _p(d), _p(t), _p(idx)))
+        return t, idx
 
     def kat_tile_feedback(self, pixel_cost, regions, heavy_factor, split_steps, split_limit, ntiles=None):
         """The feedback kernels on a flat uint32 plane of ntiles * 64 pixel costs (dr_kat_tile_feedback): (tile_cost uint32[ntiles],

@@ -237,6 +237,42 @@ int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, i
   return DR_OK;
 }
 
+int dr_kat_trace(dr_context* c, int variant, int n, const float* o, const float* d, float* t, int32_t* idx) {
+  KAT_PRE(n);
+  if (variant < 0 || variant > 7 || !o || !d || !t || !idx) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->wide) { set_error("the trace hook needs a resident wide tree (no scene uploaded, or the scene has none)"); return DR_ERR_INVALID; }
+  // the 8-float layout launch_trace_probe reads: origin, pad, direction, pad
+  std::vector<float> packed((size_t)n * 8, 0.0f);
+  for (int i = 0; i < n; i++) {
+    memcpy(&packed[(size_t)i * 8], o + 3 * (size_t)i, 12);
+    memcpy(&packed[(size_t)i * 8 + 4], d + 3 * (size_t)i, 12);
+  }
+  DevMem<float> rays; DevMem<unsigned> cursor, out;
+  DR_TRY(rays.alloc((size_t)n * 8)); DR_TRY(cursor.alloc(1)); DR_TRY(out.alloc((size_t)n * 2));
+  DR_TRY(rays.put(packed.data(), packed.size()));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  fill_scene(c, P);
+  HIP_TRY(hipMemsetAsync(cursor.p, 0, sizeof(unsigned), c->stream));
+  HIP_TRY(hipMemsetAsync(out.p, 0xff, (size_t)n * 2 * sizeof(unsigned), c->stream));      // a ray the kernel did not answer reads as {NaN, -1}, which no walk returns: refused below
+  launch_trace_probe(c->stream, P, c->num_cus, variant, rays.p, (unsigned)n, cursor.p, out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::vector<unsigned> res((size_t)n * 2);
+  DR_TRY(out.get(res.data(), res.size()));
+  for (int i = 0; i < n; i++) {
+    const int32_t slot = (int32_t)res[(size_t)i * 2 + 1];
+    if (slot >= c->n_prims) { set_error("the trace kernel returned a slot outside the scene"); return DR_ERR_INVALID; }
+    if (slot < 0) {      // {10000, -1}: no hit -- dr_kat_hit's miss; anything else below 0 (the fill above) is a ray the kernel never wrote
+      float none = 10000.0f;
+      if (slot != -1 || memcmp(&res[(size_t)i * 2], &none, 4) != 0) { set_error("the trace kernel left ray " + std::to_string(i) + " unanswered"); return DR_ERR_DEVICE; }
+      t[i] = -1.0f; idx[i] = 0;
+    }
+    else { memcpy(&t[i], &res[(size_t)i * 2], 4); idx[i] = c->slot_to_orig[(size_t)slot]; }
+  }
+  return DR_OK;
+}
+
 int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_factor, int split_steps, int split_limit, const unsigned* pixel_cost,
                          unsigned* tile_cost, int* order, int* region_start) {
   if (!c || !pixel_cost || !tile_cost || !order || !region_start) { set_error("null argument"); return DR_ERR_INVALID; }

@@ -463,6 +463,16 @@ __device__ __forceinline__ void parked_test(V3 o, V3 d, Trav& tr, ParkedLeaf& pk
   pk.parked = false;
 }
 
+// The leaf's side of hit()'s pruning test for a walk that is not in the reference's order.  hit() K:484 enters a box only if its entry distance is < the
+// running best t; the near-first walks enter at <=, because a leaf entered exactly at the best t may hold a TIE on t with a leaf that comes earlier in the
+// reference's order (lower slot), which hit() would have met first.  At entry == best t that is the only thing it may hold: a hit NEARER than the best from a
+// leaf that comes LATER in the reference's order is one hit() never sees -- it has the best already (or something nearer) when it reaches that box, and
+// prunes it.  Such a leaf exists only where the computed entry distance of a box exceeds the computed t of the primitive inside it, which the 0.01 of padding
+// rules out until floats step by more than that (coordinates of 2^20: tests/ray_cases.py far_mesh, long_short).  "No hit yet" is slot -1: the largest unsigned.
+__device__ __forceinline__ bool leaf_entry_admits(float dist, int slot, float best_t, int best_slot) {
+  return dist < best_t || (dist == best_t && (unsigned)slot < (unsigned)best_slot);
+}
+
 // Cooperative closest hit: all 64 lanes of a wave answer ONE query.  The wave keeps a stack of internal
 // nodes (pair records) in LDS; per round every lane pops one, tests its two child boxes against the wave's
 // best t so far, tests leaf children on the spot and pushes internal children that pass.  A ray that costs
@@ -870,7 +880,7 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
     const int slot = info & ((1 << WALK_SLOT_BITS) - 1);
     const bool cand = t > 0.0f && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot));
     if (__builtin_amdgcn_ballot_w64(cand) != 0ull) {
-      if (cand && slab_sel(o, inv, sg, mn, mx, dist) && dist <= tr.best_t) { tr.best_t = t; tr.best_slot = slot; }
+      if (cand && slab_sel(o, inv, sg, mn, mx, dist) && leaf_entry_admits(dist, slot, tr.best_t, tr.best_slot)) { tr.best_t = t; tr.best_slot = slot; }
     }
   } else
 #endif
@@ -879,7 +889,7 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
     const int info = (int)r.A.w;
     const float t = prim_hit_kind((info >> WALK_SLOT_BITS) & 3, mk(f(r.B.w), f(r.C.x), f(r.C.y)), mk(f(r.C.z), f(r.C.w), f(r.D.x)), mk(f(r.D.y), f(r.D.z), f(r.D.w)), o, d);
     const int slot = info & ((1 << WALK_SLOT_BITS) - 1);
-    if (t > 0.0f && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot))) { tr.best_t = t; tr.best_slot = slot; }
+    if (t > 0.0f && leaf_entry_admits(dist, slot, tr.best_t, tr.best_slot) && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot))) { tr.best_t = t; tr.best_slot = slot; }
   }
   wide_pop(tr, ws, stack);
   DR_MARK("leaf_end");
@@ -944,11 +954,23 @@ __device__ __forceinline__ Hit closest_hit_threaded(WalkRsrc walk, V3 o, V3 d, C
 // boxes; the far child waits on a per-lane stack in LDS (one dword per level, lane-major, so
 // a wave's pushes and pops never bank-conflict).  The tree is a median split, so its depth is
 // ceil(log2 N) <= 24 for N <= 2^24 (the host refuses deeper trees for this mode).
-
+//
+// (1) and (2) assume that a leaf's computed entry distance does not exceed the computed t of its primitive.  Where it does (coordinates of 2^20: floats step
+// by more than the 0.01 of padding) hit() decides between two leaves by its ORDER: the one it reaches later (higher slot) wins only if its box entry AND its t
+// are both < the earlier one's t (K:484, K:488).  This walk keeps m = max(entry, t) of its best leaf and decides every pair that way, whichever of the two
+// it met first; it prunes at m, not at t, so that an earlier leaf whose t lies between the best's t and the best's entry is still looked at.  With entry <= t
+// everywhere m is t and all of this is the lexicographic minimum above, bit for bit.
 template <bool COUNT>
 __device__ __forceinline__ Hit closest_hit_ordered(const DevPair* __restrict__ pairs, const DevPrim* __restrict__ prims,
                                                    V3 o, V3 d, Ctr& c, int* __restrict__ stack /* [level * 64] */) {
   Hit best; best.t = 10000000.0f; best.slot = 0x7fffffff;
+  float best_m = 10000000.0f;
+  auto offer = [&best, &best_m](float t, int slot, float entry) {
+    if (!(t > 0.0f)) return;
+    const float m = __builtin_fmaxf(entry, t);
+    const bool take = slot > best.slot ? m < best.t : !(best_m < t);      // the later of the two wins only if it is nearer in both respects
+    if (take) { best.t = t; best.slot = slot; best_m = m; }
+  };
   V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   int sp = 0;
   int cur = 0;
@@ -961,26 +983,24 @@ __device__ __forceinline__ Hit closest_hit_ordered(const DevPair* __restrict__ p
     float mn1[3] = {C.x, C.y, C.z}, mx1[3] = {D.x, D.y, D.z};
     float d0, d1;
     if (COUNT) c.V += 2;
-    bool h0 = slab(o, inv, mn0, mx0, d0) && d0 <= best.t;     // <=: a box entered exactly at the best t may hold a tie with a lower slot
-    bool h1 = slab(o, inv, mn1, mx1, d1) && d1 <= best.t;
+    bool h0 = slab(o, inv, mn0, mx0, d0) && d0 <= best_m;     // <=: a box entered exactly at the best t may hold a tie with a lower slot
+    bool h1 = slab(o, inv, mn1, mx1, d1) && d1 <= best_m;
     if (h0 && c0 < 0) {
       int slot = ~c0;
       if (COUNT) c.L++;
-      float t = prim_hit(prims, slot, o, d);
-      if (t > 0.0f && (t < best.t || (t == best.t && slot < best.slot))) { best.t = t; best.slot = slot; }
+      offer(prim_hit(prims, slot, o, d), slot, d0);
       h0 = false;
     }
     if (h1 && c1 < 0) {
-      if (d1 <= best.t) {
+      if (d1 <= best_m) {
         int slot = ~c1;
         if (COUNT) c.L++;
-        float t = prim_hit(prims, slot, o, d);
-        if (t > 0.0f && (t < best.t || (t == best.t && slot < best.slot))) { best.t = t; best.slot = slot; }
+        offer(prim_hit(prims, slot, o, d), slot, d1);
       }
       h1 = false;
     }
-    h0 = h0 && d0 <= best.t;
-    h1 = h1 && d1 <= best.t;
+    h0 = h0 && d0 <= best_m;
+    h1 = h1 && d1 <= best_m;
     if (h0 && h1) {
       bool first0 = d0 <= d1;
       int far_c = first0 ? c1 : c0;

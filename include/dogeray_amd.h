@@ -660,6 +660,13 @@ int dr_kat_node_planes(dr_context* c, int n, const uint32_t* w, const float* a, 
 /* closest hit against the resident scene: t (-1 = miss), ORIGINAL object index and (visits may be NULL)
  * the number of boxes the chosen traversal tested for that ray */
 int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits);
+/* dr_kat_hit's rays through the LEAN build of the wide walk, the one render launches time and ship (dr_kat_hit runs the counting build): the trace-only
+ * kernels of dr_context_probe_trace on caller rays -- variant 0: one ray per lane (the primitive-first leaf step behind a wave ballot); 1..7: persistent
+ * waves refilling from the ray list, planes selected by sign masks, exclusive node / leaf steps (the parameter sets listed at dr_context_probe_trace).
+ * Results in dr_kat_hit's convention: t (-1 = miss) and the ORIGINAL object index (0 on a miss).  Needs a resident wide tree (DR_ERR_INVALID for a scene
+ * that has none, whatever the traversal option says); it does not need the persistent-kernel option.  The results are preset to a pattern no walk
+ * returns, and a ray the kernel left unanswered -- anything but a hit or {10000, -1} -- is DR_ERR_DEVICE naming the ray, never a miss. */
+int dr_kat_trace(dr_context* c, int variant, int n, const float* o, const float* d, float* t, int32_t* idx);
 /* The two feedback kernels behind the persistent kernel's tile order, on caller data and scratch buffers (the context's own order is not
  * touched): pixel_cost[ntiles * 64] -> tile_cost[ntiles] (the maximum of each tile's 64 words), order[ntiles] and region_start[17] as
  * dr_stats_tile_order describes them.  order and region_start are filled with -1 before the launch: an entry the kernels did not write

@@ -197,6 +197,7 @@ def test_library_exports_every_declared_symbol(dr):
     for n in names:
         assert hasattr(L, n), "libdogeray_amd.so does not export %s" % n
     assert sorted(dr.API_SYMBOLS) == names, "python binding and header disagree"
+    assert {"dr_kat_hit", "dr_kat_trace", "dr_context_probe_trace"} <= set(names)      # the hooks tests/test_gpu_rays.py sends caller rays through
     assert dr.lib().dr_abi_version() == 2
 
 

@@ -11,6 +11,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from ray_cases import graze_pairs as _cases      # the generator of the adversarial pairs; tests/test_rays_host.py aims it at the triangles of real scenes
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
 
 
@@ -19,44 +21,6 @@ def hk():
     import host_kernel
     host_kernel.build()
     return host_kernel
-
-
-def _cases(rng, n, edge, dist, dlen, coord):
-    """n adversarial pairs: triangle edges ~edge, origin ~dist away, |d| ~dlen, coordinates ~coord"""
-    f = np.float32
-    v0 = (rng.uniform(-coord, coord, (n, 3))).astype(f)
-    e1 = (rng.normal(size=(n, 3)) * edge * rng.uniform(0.2, 1.5, (n, 1))).astype(f)
-    e2 = (rng.normal(size=(n, 3)) * edge * rng.uniform(0.2, 1.5, (n, 1))).astype(f)
-    # a third of the triangles are cells of a grid, as a height field's are: two edges along the axes (plus a little height), so that the triangle's edges
-    # lie IN the faces of its bounds and every overshoot of an edge shows
-    grid = rng.integers(0, 3, n) == 0
-    gx = np.zeros((n, 3)); gx[:, 0] = edge; gx[:, 2] = rng.normal(size=n) * edge * 0.3
-    gy = np.zeros((n, 3)); gy[:, 1] = edge; gy[:, 2] = rng.normal(size=n) * edge * 0.3
-    e1 = np.where(grid[:, None], gx, e1).astype(f); e2 = np.where(grid[:, None], gy, e2).astype(f)
-    nrm = np.cross(e1.astype(np.float64), e2.astype(np.float64))
-    area2 = np.linalg.norm(nrm, axis=1, keepdims=True) + 1e-300
-    nrm = nrm / area2
-    # a target point around the triangle's rim: barycentrics on an edge or a corner, pushed out by a little
-    u = rng.uniform(-0.3, 1.3, (n, 1)); v = rng.uniform(-0.3, 1.3, (n, 1))
-    kind = rng.integers(0, 4, (n, 1))
-    u = np.where(kind == 0, rng.uniform(-0.05, 0.05, (n, 1)), u)
-    v = np.where(kind == 1, rng.uniform(-0.05, 0.05, (n, 1)), v)
-    v = np.where(kind == 2, 1 - u + rng.uniform(-0.05, 0.05, (n, 1)), v)
-    corner = rng.integers(0, 3, (n, 1))          # kind 3: at a corner
-    u = np.where(kind == 3, (corner == 1) + rng.uniform(-0.03, 0.03, (n, 1)), u)
-    v = np.where(kind == 3, (corner == 2) + rng.uniform(-0.03, 0.03, (n, 1)), v)
-    target = v0 + u * e1 + v * e2
-    # direction: in the plane, tilted so that |a| = |d| * 2A * sin(phi) lands around the 1e-4 cut-off (or anywhere, for a third of the cases)
-    inplane = e1 * rng.normal(size=(n, 1)) + e2 * rng.normal(size=(n, 1))
-    inplane = inplane / (np.linalg.norm(inplane, axis=1, keepdims=True) + 1e-300)
-    dl = dlen * rng.uniform(0.5, 1.5, (n, 1))
-    sinphi = np.clip(1e-4 * rng.uniform(0.9, 6.0, (n, 1)) / (dl * area2), 0, 1)
-    sinphi = np.where(rng.integers(0, 3, (n, 1)) == 0, rng.uniform(0, 1, (n, 1)), sinphi) * rng.choice([-1.0, 1.0], (n, 1))
-    dirn = inplane * np.sqrt(1 - sinphi ** 2) + nrm * sinphi
-    d = (dirn * dl).astype(f)
-    t = dist * rng.uniform(0.05, 1.0, (n, 1)) / dl
-    o = (target - t * d.astype(np.float64)).astype(f)
-    return o, d, v0, e1, e2
 
 
 def _check(hk, o, d, v0, e1, e2):

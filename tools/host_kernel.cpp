@@ -420,6 +420,51 @@ void hk_scene_free(void* hv) {
   delete h;
 }
 
+// dr_kat_hit on the host: the closest hit of n caller rays (o[3n], d[3n]) by the walks of device_core.hpp -- traversal 0 closest_hit_threaded, 1
+// closest_hit_ordered, 2 closest_hit_wide<true> over the image of `tree` (1: the reference's leaf boxes; 2: the product's default, small triangles with
+// their own bounds, built on first use); a scene without a wide tree takes the threaded walk for traversal 2, as the product does.  Results in
+// dr_kat_hit's convention: t (-1: miss), the ORIGINAL object index (0 on a miss), visits (may be NULL): boxes tested.  Returns 0, or -1 with hk_last_error.
+int hk_hit(void* hv, int traversal, int tree, long long n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n < 0 || (n > 0 && (!o || !d || !t || !idx)) || traversal < 0 || traversal > 2 || (tree != 1 && tree != 2)) { hk_err = "bad argument"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
+  P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
+  P.pairs = img.pairs.data(); P.prims = img.prims.data();
+  std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
+  const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
+  for (long long i = 0; i < n; i++) {
+    const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+    Hit hit;
+    if (traversal == DR_TRAVERSAL_WIDE && P.wide) hit = closest_hit_wide<true>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, ro, rd, c, stack.data());
+    else if (traversal == DR_TRAVERSAL_ORDERED) hit = closest_hit_ordered<true>(P.pairs, P.prims, ro, rd, c, stack.data());
+    else hit = closest_hit_threaded<true>(walk, ro, rd, c);
+    t[i] = hit.t;
+    idx[i] = hit.slot >= 0 ? img.slot_to_orig[(size_t)hit.slot] : 0;      // hit() returns index 0 on a miss (K:507)
+    if (visits) visits[i] = (int32_t)c.V;
+  }
+  return 0;
+}
+// what dr_context_get_option reports for the image of `tree` (1 / 2, as hk_hit): out3 = wide_depth (0: no wide tree), wide_own_bounds, wide_nodes
+int hk_wide_info(void* hv, int tree, int* out3) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !out3 || (tree != 1 && tree != 2)) { hk_err = "bad argument"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  out3[0] = img.wide.empty() ? 0 : img.wide_depth; out3[1] = img.wide.empty() ? 0 : img.wide_own_bounds; out3[2] = img.wide.empty() ? 0 : img.wide_nodes;
+  return 0;
+}
+
 int hk_has_wide(void* hv) { return ((HkScene*)hv)->img.wide.empty() ? 0 : 1; }
 int hk_wide_depth(void* hv) { return ((HkScene*)hv)->img.wide.empty() ? 0 : ((HkScene*)hv)->img.wide_depth; }      // nodes on the longest root-to-leaf path of the wide tree
 

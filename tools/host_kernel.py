@@ -38,6 +38,10 @@ def lib():
         L.hk_scene_free.argtypes = [C.c_void_p]
         L.hk_has_wide.argtypes = [C.c_void_p]
         L.hk_wide_depth.argtypes = [C.c_void_p]
+        L.hk_hit.restype = C.c_int
+        L.hk_hit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 5
+        L.hk_wide_info.restype = C.c_int
+        L.hk_wide_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hk_check_uniform.restype = C.c_longlong
         L.hk_check_uniform.argtypes = [C.c_longlong, C.c_ulonglong]
         L.hk_ray_margin.restype = None
@@ -91,6 +95,26 @@ class Scene:
 
     def wide_depth(self):
         return int(lib().hk_wide_depth(self.h))
+
+    def hit(self, o, d, traversal=2, tree=2, want_visits=False):
+        """dr_kat_hit on the host (hk_hit): the closest hits of the rays (o, d) by the walk of `traversal` (0 threaded, 1 ordered, 2 wide) over the tree
+        of wide_tree = `tree` (1 / 2) -> (t float32[n], -1 on a miss; original object index int32[n], 0 on a miss[; boxes tested int32[n]])."""
+        o, d = np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
+        n = o.shape[0]
+        assert o.shape == (n, 3) and d.shape == (n, 3)
+        t, idx = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        vis = np.zeros(n, np.int32) if want_visits else None
+        if lib().hk_hit(self.h, int(traversal), int(tree), n, o.ctypes.data, d.ctypes.data, t.ctypes.data, idx.ctypes.data,
+                        vis.ctypes.data if want_visits else None) != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return (t, idx, vis) if want_visits else (t, idx)
+
+    def wide_info(self, tree=2):
+        """What dr_context_get_option reports for the tree of wide_tree = `tree`: a dict with wide_depth (0: no wide tree), wide_own_bounds, wide_nodes."""
+        out = np.zeros(3, np.int32)
+        if lib().hk_wide_info(self.h, int(tree), out.ctypes.data) != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return {"wide_depth": int(out[0]), "wide_own_bounds": int(out[1]), "wide_nodes": int(out[2])}
 
     def render(self, settings13, W, H, background, frame_seed, traversal=2, nthreads=1, col_mod=1, col_rem=0, count=True, level_plane=None, cert_factor=40,
                graded=1):
