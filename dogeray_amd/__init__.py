@@ -24,7 +24,7 @@ TRAVERSAL_ORDERED = 1
 TRAVERSAL_WIDE = 2          # the default: 4-way tree over the reference's leaves
 KERNEL_TILE = 0
 KERNEL_PERSISTENT = 1
-MAX_REGIONS = 8             # tile queues of the persistent kernel (csrc/kernels.hpp)
+MAX_REGIONS = 8             # tile queues of the persistent kernel (csrc/launch_plan.hpp)
 ERR_INVALID, ERR_IO, ERR_PARSE, ERR_SCENE, ERR_DEVICE, ERR_NOMEM = -1, -2, -3, -4, -5, -6      # enum dr_status
 
 

@@ -250,7 +250,7 @@ inline bool uses_persistent(const dr_context* c) { return c->kernel == DR_KERNEL
 void fill_scene(const dr_context* c, RenderParams& P);      // the resident scene's buffers
 int make_params(dr_context* c, const LaunchSite& site, const float* st, int W, int H, float background, uint64_t seed, RenderParams& P, int batch_hint = 1);
 PersistentCfg persistent_cfg(const dr_context* c, const LaunchSite& site);
-void enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in);
+int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in);
 // context_pipeline.cpp
 int join_pipeline(dr_context* c);
 int pipeline_flush(dr_context* c);

@@ -44,7 +44,7 @@ int pipeline_setup(dr_context* c) {
 
 // how many frames a group may hold right now: the option, if the launch configuration has the builds that store every frame of a batch separately
 int pipeline_group_size(const dr_context* c) {
-  if (c->pipe_group <= 1 || c->pipe_lean || !uses_persistent(c) || !persistent_kernel_can_store_per_frame(persistent_cfg(c, c->own_site()))) return 1;
+  if (c->pipe_group <= 1 || c->pipe_lean || !uses_persistent(c) || !persistent_can_store_per_frame(persistent_cfg(c, c->own_site()))) return 1;
   return c->pipe_group;
 }
 
@@ -102,7 +102,8 @@ int pipeline_flush_some(dr_context* c, int n) {
   // streams' newest launches, and the launches after it wait for the refresh); all others read the order as it is
   bool refresh = false;
   if (c->feedback && uses_persistent(c) && tiles > 0) {
-    const float geom[5] = {(float)P.W, (float)P.H, (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions, (float)P.ncols, (float)P.gy};
+    float geom[5];
+    order_geometry(P, geom);
     // (a refresh costs the overlap of two launches, 0.89 against 0.82 ms/frame when every 8th single-frame launch refreshes: four times rarer here)
     refresh = !c->order_valid || c->order_capacity < tiles || memcmp(c->order_key + 13, geom, sizeof(geom)) != 0 || c->order_age < 2 ||
               c->order_age % (4 * c->feedback_every) == 0;
@@ -115,7 +116,7 @@ int pipeline_flush_some(dr_context* c, int n) {
   if (alone)
     for (int q = 0; q < dr_context::PIPE_STREAMS; q++) if (q != si && c->pipe_last_set[q]) HIP_TRY(hipStreamWaitEvent(rs, c->pipe_last[q], 0));
   if (tiles > 0) {
-    enqueue_frame(c, site, P);
+    DR_TRY(enqueue_frame(c, site, P));
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(c->pipe_last[si], rs)); c->pipe_last_set[si] = true;

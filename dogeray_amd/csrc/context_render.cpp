@@ -30,15 +30,9 @@ int make_params(dr_context* c, const LaunchSite& site, const float* st, int W, i
   P.wave_log = c->wave_log_on ? c->wave_log.p : nullptr;
   P.coop_steps = c->coop_steps; P.coop_rounds = c->coop_rounds; P.split_parts = c->split_parts;
   P.coop_lanes = c->coop_lanes;
-  {
-    const int tiles = P.ncols * P.gy;
-    P.regions = c->xcd_regions ? MAX_REGIONS : 1;
-    if (tiles < 64 * MAX_REGIONS) P.regions = 1;                 // tiny frames: one queue
-    // a short launch (few tiles per wave: one frame, or a thin stripe of a few) ends when its slowest band ends; one queue
-    // balances better there than eight (1.88 instead of 2.00 ms for a single 1920x1080 frame of the bench scene)
-    if (c->short_one_queue && (long long)tiles * batch_hint < (long long)tiles_per_wave(c, site) * c->num_cus * 20) P.regions = 1;
-    for (int r = 0; r <= MAX_REGIONS; r++) P.region_start[r] = r <= P.regions ? (int)(((long long)tiles * r + P.regions - 1) / P.regions) : tiles;
-  }
+  const int tiles = P.ncols * P.gy;
+  P.regions = plan_regions(tiles, batch_hint, c->xcd_regions != 0, c->short_one_queue != 0, tiles_per_wave(c, site), c->num_cus);
+  for (int r = 0; r <= MAX_REGIONS; r++) P.region_start[r] = r <= P.regions ? (int)(((long long)tiles * r + P.regions - 1) / P.regions) : tiles;
   return DR_OK;
 }
 
@@ -66,8 +60,7 @@ void feedback_buffers(dr_context* c, const LaunchSite& site, const RenderParams&
   // the stored order belongs to one view: same settings, size and stripe (progressive frames)
   float key[18] = {0};
   memcpy(key, c->cur_settings, 13 * sizeof(float));
-  key[13] = (float)P.W; key[14] = (float)P.H; key[15] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;
-  key[16] = (float)P.ncols; key[17] = (float)P.gy;      // the tile grid (the preview divisor settings[11] changes it with W and H unchanged)
+  order_geometry(P, key + 13);
   if (c->order_valid && memcmp(c->order_key, key, sizeof(key)) == 0) order = c->tile_order;
   else if (c->order_valid && c->order_follows_camera && memcmp(c->order_key + 13, key + 13, 5 * sizeof(float)) == 0) {
     // same frame geometry, other camera / depth / samples (an interactive viewer moving the camera, K:2341-2500: every frame is a new
@@ -115,7 +108,7 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
 }  // namespace
 
 // enqueue one launch (P.batch frames) at `site`; no events, no sync
-void enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in) {
+int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in) {
   RenderParams P = P_in;
   const int tiles = P.ncols * P.gy;
   if (uses_persistent(c)) {
@@ -128,27 +121,31 @@ void enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_
     const int* order; unsigned* pcost;
     if (site.hold_order) {
       // a pipelined launch runs beside the previous frame's: it may read the tile order but nobody may write it (or the costs) meanwhile
-      const float geom[5] = {(float)P.W, (float)P.H, (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions, (float)P.ncols, (float)P.gy};
+      float geom[5];
+      order_geometry(P, geom);
       order = (c->order_valid && c->order_capacity >= tiles && memcmp(c->order_key + 13, geom, sizeof(geom)) == 0) ? c->tile_order.p : nullptr;
       pcost = nullptr;
     } else feedback_buffers(c, site, P, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
     cert_prepare(c, site, P, tiles);
-    c->wave_log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, order, c->region_start, pcost);
+    const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, order, c->region_start, pcost);
+    if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
+    c->wave_log_waves = log_waves;
     // next launch's order from this launch's costs (stream-ordered, no host sync).  The view does not change between the frames of
     // a progressive render, so after the first two launches of a view the order is refreshed every feedback_every-th launch only
     // (the two kernels take 75 us: nothing for a launch of 32 frames, 6 % of a launch of one)
     if (pcost && !order) c->order_age = 0;
     if (pcost && (c->order_age < 2 || c->order_age % c->feedback_every == 0)) {
-      const int split_limit = c->split_parts > 1 ? (int)((long long)c->num_cus * (c->occupancy >= 5 ? 5 : 4) * 4 * c->split_waves / (100 * c->split_parts)) : 0;      // at most split_waves % of the waves start with a part of a split tile
+      const int split_limit = plan_split_limit(c->num_cus, c->occupancy, c->split_parts, c->split_waves);
       launch_tile_feedback(site.stream, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start, tiles, P.regions, c->heavy_factor, c->split_steps, split_limit);
       c->order_args[0] = tiles; c->order_args[1] = P.regions; c->order_args[2] = c->heavy_factor; c->order_args[3] = c->split_steps; c->order_args[4] = split_limit;
       c->order_valid = true;
     }
     c->order_age++;
-    return;
+    return DR_OK;
   }
   launch_tile_kernel(site.stream, P, traversal_of(c), c->count != 0, c->occupancy);
+  return DR_OK;
 }
 
 }  // namespace dr
@@ -161,7 +158,7 @@ int launch_render(dr_context* c, const RenderParams& P) {
   int tiles = P.ncols * P.gy;
   if (tiles <= 0) return DR_OK;
   HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  enqueue_frame(c, c->own_site(), P);
+  DR_TRY(enqueue_frame(c, c->own_site(), P));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev1, c->stream));
   return DR_OK;
@@ -210,7 +207,7 @@ int accumulate_enqueue(dr_context* c, const float settings13[13], int W, int H, 
     P.batch = nframes - k < per_launch ? nframes - k : per_launch;
     P.batch_seed_stride = seed_stride;
     P.accumulate = P.batch > 1 ? 2 : 1;
-    enqueue_frame(c, c->own_site(), P);
+    DR_TRY(enqueue_frame(c, c->own_site(), P));
     launches++;
   }
   c->stats.launches += launches;

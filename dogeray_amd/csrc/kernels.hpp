@@ -15,32 +15,17 @@
 
 #include "device_launch.h"
 #include "device_layout.h"
+#include "launch_plan.hpp"
 
 namespace dr {
 
-constexpr int MAX_REGIONS = 8;           // tile queues of the persistent kernels (one per XCD)
-constexpr int WAVE_LOG_WAVES = 16384;    // waves the wave log (option wave_log) has room for
-
-// What a launch of the persistent kernel needs to know of the context's options (dr_context_set_option)
-struct PersistentCfg {
-  int traversal;             // the traversal the launch really uses (DR_TRAVERSAL_WIDE or DR_TRAVERSAL_THREADED)
-  int occupancy;             // 4, 5 or 6 waves per SIMD
-  int schedule;              // 0, 1, 2: option "schedule" (kernels_render.hip launch_persistent_occ)
-  int num_cus;
-  int coop_tiles_per_wave;
-  bool count;                // counting build
-};
-
 // kernels_render.hip
 void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal, bool count, int occupancy);
-// returns the number of waves that write the wave log (0: the launched build does not log)
+// launches the build plan_persistent (launch_plan.hpp) picks; returns the plan's log_waves, or -1: the plan names a build that is not instantiated
 int launch_persistent_kernel(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
                              const int* region_start, unsigned* pixel_cost);
 
 constexpr int COUNTER_WORDS = 48;   // 64-bit words of a context's statistics buffer: [0, 8) ray counters, [8, 16) dr_stats.diag, [16, 48) the shade / refill phase's budget (dr_stats_phase_counts)
-
-// the launch configuration has builds that store every frame of a batch into its own buffer (RenderParams::out_frame_stride != 0)
-bool persistent_kernel_can_store_per_frame(const PersistentCfg& cfg);
 
 // kernels_aux.hip
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,

@@ -1,5 +1,5 @@
 // The render kernels: the per-tile kernel (the reference's launch shape, kernel.cu K:2634-2640) and the persistent kernel (a wave is a
-// pool of 64 path slots that refill from tile queues).  Launchers at the end; context.cpp picks options, this file picks the instantiation.
+// pool of 64 path slots that refill from tile queues).  Launchers at the end; context.cpp picks options, launch_plan.hpp picks the instantiation.
 #include <hip/hip_runtime.h>
 
 #include "device_core.hpp"
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
 // COOP (wide walk): build with work sharing (lanes without a pixel take over subtrees of the rays still walking: once the queue is
 // empty, and from the start in the waves that hold a part of a split tile).  It costs registers (96 VGPRs: five waves per SIMD) and
 // code in the loop, so launches whose queue is long enough to hide their tail use the lean build (80 VGPRs and 26 KiB of LDS at
-// OCC = 6: six waves per SIMD; launch_persistent / launch_wide_lean6 pick).
+// OCC = 6: six waves per SIMD; launch_plan.hpp plan_persistent picks).
 
 // PERFRAME: every frame of the launch's batch is stored into a buffer of its own (P.out + frame * P.out_frame_stride) instead of being added into one: the
 // grouped present pipeline (dr_pipeline_*: the frames of a group share one launch and are added and shown one by one afterwards).
@@ -617,108 +617,44 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
 }
 
 // ------------------------------------------------------------------ launchers
-void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal, bool count, int occupancy) {
-  const int tiles = P.ncols * P.gy;
-  dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-#define DR_TILE(COUNT, MODE, OCC) hipLaunchKernelGGL((render_kernel<COUNT, MODE, OCC>), grid, block, 0, stream, P)
-#define DR_TILE_OCC(OCC)                                                                   \
-  do {                                                                                     \
-    if (count) {                                                                           \
-      if (traversal == DR_TRAVERSAL_ORDERED) DR_TILE(true, DR_TRAVERSAL_ORDERED, OCC);     \
-      else if (traversal == DR_TRAVERSAL_WIDE) DR_TILE(true, DR_TRAVERSAL_WIDE, OCC);      \
-      else DR_TILE(true, DR_TRAVERSAL_THREADED, OCC);                                      \
-    } else {                                                                               \
-      if (traversal == DR_TRAVERSAL_ORDERED) DR_TILE(false, DR_TRAVERSAL_ORDERED, OCC);    \
-      else if (traversal == DR_TRAVERSAL_WIDE) DR_TILE(false, DR_TRAVERSAL_WIDE, OCC);     \
-      else DR_TILE(false, DR_TRAVERSAL_THREADED, OCC);                                     \
-    }                                                                                      \
-  } while (0)
-  if (occupancy >= 6) DR_TILE_OCC(6);
-  else DR_TILE_OCC(4);
-#undef DR_TILE_OCC
-#undef DR_TILE
-}
-
+// launch_plan.hpp decides and lists the instantiations; the tables below are expanded from its lists, and a launch is one lookup
 namespace {
 
-// (COOP_PARK, COOP_UNROLL: the work-sharing build's own leaf-step threshold and steps per iteration -- short launches like fewer lanes per leaf step and more
-// steps between two looks at the queue: 32 / 12 / 4 against the lean build's 32 / 20 / 2, one frame per launch 0.915 against 0.945 ms, profiles/r4_q_short_launch_schedule.txt)
-template <int OCC, int TRAV_MIN, int PARK_MIN, int P_UNROLL = 1, int COOP_PARK = PARK_MIN, int COOP_UNROLL = P_UNROLL>
-int launch_persistent(hipStream_t stream, const RenderParams& P_in, const PersistentCfg& cfg, unsigned* counter, const int* order, const int* rstart, unsigned* pixel_cost) {
-  RenderParams P = P_in;
-  int work = P.ncols * P.gy * P.batch;
-  int blocks = cfg.num_cus * OCC;                   // OCC waves per SIMD on every CU
-  if (blocks * 4 > work) blocks = (work + 3) / 4;
-  if (P.wave_log && blocks * 4 > WAVE_LOG_WAVES) P.wave_log = nullptr;
-  int log_waves = P.wave_log ? blocks * 4 : 0;
-  dim3 grid((unsigned)blocks), block(256);
-  if (cfg.traversal == DR_TRAVERSAL_WIDE) {
-    // the cooperative drain shortens a launch's tail; with many tiles per wave the tail does not show and the leaner build is faster
-    const bool coop = P.coop_steps > 0 && (long long)work < (long long)cfg.coop_tiles_per_wave * blocks * 4;
-    if (!coop) log_waves = 0;      // only the work-sharing build writes the log
-    if (cfg.count) hipLaunchKernelGGL((render_persistent_kernel<true, OCC, TRAV_MIN, PARK_MIN, P_UNROLL, true, false>), grid, block, 0, stream, P, counter, order, rstart, pixel_cost);
-    else if (coop) hipLaunchKernelGGL((render_persistent_kernel<false, OCC, TRAV_MIN, COOP_PARK, COOP_UNROLL, true, true>), grid, block, 0, stream, P, counter, order, rstart, pixel_cost);
-    else hipLaunchKernelGGL((render_persistent_kernel<false, OCC, TRAV_MIN, PARK_MIN, P_UNROLL, true, false>), grid, block, 0, stream, P, counter, order, rstart, pixel_cost);
-    return log_waves;
-  }
-  if (cfg.count) hipLaunchKernelGGL((render_persistent_kernel<true, OCC, TRAV_MIN, PARK_MIN, P_UNROLL, false>), grid, block, 0, stream, P, counter, order, rstart, pixel_cost);
-  else hipLaunchKernelGGL((render_persistent_kernel<false, OCC, TRAV_MIN, PARK_MIN, P_UNROLL, false>), grid, block, 0, stream, P, counter, order, rstart, pixel_cost);
-  return log_waves;
-}
+struct TileEntry { bool count; int mode, occ; void (*kernel)(RenderParams); };
+#define DR_ENTRY(COUNT, MODE, OCC) {COUNT, MODE, OCC, render_kernel<COUNT, MODE, OCC>},
+const TileEntry TILE_BUILDS[] = {DR_TILE_BUILDS(DR_ENTRY)};
+#undef DR_ENTRY
 
-// Six waves per SIMD (occupancy 6): only the wide walk's lean build fits -- 80 VGPRs and 26 KiB of LDS per workgroup -- and only with the
-// default schedule; every other launch (counting build, work-sharing build of short launches, other schedules) runs five.
-bool launch_wide_lean6(hipStream_t stream, const RenderParams& P_in, const PersistentCfg& cfg, unsigned* counter, const int* order, const int* rstart, unsigned* pixel_cost, int& log_waves) {
-  if (cfg.traversal != DR_TRAVERSAL_WIDE || cfg.count || cfg.schedule != 0) return false;
-  RenderParams P = P_in;
-  const long long work = (long long)P.ncols * P.gy * P.batch;
-  if (P.coop_steps > 0 && work < (long long)cfg.coop_tiles_per_wave * cfg.num_cus * 5 * 4) return false;      // a short launch: work-sharing build
-  int blocks = cfg.num_cus * 6;
-  if ((long long)blocks * 4 > work) blocks = (int)((work + 3) / 4);
-  P.wave_log = nullptr;      // (the lean kernel does not log its waves)
-  log_waves = 0;
-  if (P.out_frame_stride) hipLaunchKernelGGL((render_persistent_kernel<false, 6, 32, 20, 2, true, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, P, counter, order, rstart, pixel_cost);
-  else hipLaunchKernelGGL((render_persistent_kernel<false, 6, 32, 20, 2, true, false>), dim3((unsigned)blocks), dim3(256), 0, stream, P, counter, order, rstart, pixel_cost);
-  return true;
-}
-
-// The instantiated schedules (option "schedule"): 0 = the tuned one -- shade / refill below 32 walking lanes, leaf steps for 20 lanes, two steps per
-// loop iteration (work-sharing build: 12 lanes, four steps) --; 1 and 2 keep the other paths of the loop alive in the tests (leaf steps for 8 lanes, one step per iteration; shade / refill
-// below 48 lanes, leaves tested on the spot).  Every other combination rounds 2 and 3 measured is in profiles/r2_*, r3_p_*.
-template <int OCC>
-int launch_persistent_occ(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* counter, const int* order, const int* rstart, unsigned* pcost) {
-  switch (cfg.schedule) {
-    case 0:  return launch_persistent<OCC, 32, 20, 2, 12, 4>(stream, P, cfg, counter, order, rstart, pcost);
-    case 1:  return launch_persistent<OCC, 32, 8, 1>(stream, P, cfg, counter, order, rstart, pcost);
-    default: return launch_persistent<OCC, 48, 0, 1>(stream, P, cfg, counter, order, rstart, pcost);
-  }
-}
+struct PersistentEntry { PersistentBuild build; void (*kernel)(RenderParams, unsigned*, const int*, const int*, unsigned*); };
+#define DR_ENTRY(COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME) \
+  {{COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME}, render_persistent_kernel<COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME>},
+const PersistentEntry PERSISTENT_BUILDS[] = {DR_PERSISTENT_BUILDS(DR_ENTRY)};
+#undef DR_ENTRY
 
 }  // namespace
 
-bool persistent_kernel_can_store_per_frame(const PersistentCfg& cfg) {
-  return cfg.traversal == DR_TRAVERSAL_WIDE && !cfg.count && cfg.schedule == 0 && cfg.occupancy >= 6;
+void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal, bool count, int occupancy) {
+  const int tiles = P.ncols * P.gy;
+  const int mode = traversal == DR_TRAVERSAL_ORDERED || traversal == DR_TRAVERSAL_WIDE ? traversal : DR_TRAVERSAL_THREADED, occ = occupancy >= 6 ? 6 : 4;
+  for (const TileEntry& e : TILE_BUILDS)
+    if (e.count == count && e.mode == mode && e.occ == occ) {
+      hipLaunchKernelGGL(e.kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, P);
+      return;
+    }
 }
 
-int launch_persistent_kernel(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
+int launch_persistent_kernel(hipStream_t stream, const RenderParams& P_in, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
                              const int* region_start, unsigned* pixel_cost) {
+  RenderParams P = P_in;
+  const PersistentPlan plan = plan_persistent(cfg, (long long)P.ncols * P.gy * P.batch, P.coop_steps, P.out_frame_stride != 0, P.wave_log != nullptr);
+  if (plan.clear_wave_log) P.wave_log = nullptr;
   const int* rstart = order ? region_start : nullptr;        // identity order: the split travels in P.region_start
-  int log_waves = 0;
-  // (a caller that sets out_frame_stride has asked persistent_kernel_can_store_per_frame for this very configuration: context.cpp pipeline_flush)
-  if (P.out_frame_stride && persistent_kernel_can_store_per_frame(cfg)) {
-    if (launch_wide_lean6(stream, P, cfg, tile_counter, order, rstart, pixel_cost, log_waves)) return log_waves;
-    // a short group: the work-sharing build, five waves per SIMD
-    const int work = P.ncols * P.gy * P.batch;
-    int blocks = cfg.num_cus * 5;
-    if (blocks * 4 > work) blocks = (work + 3) / 4;
-    RenderParams Q = P;
-    if (Q.wave_log && blocks * 4 > WAVE_LOG_WAVES) Q.wave_log = nullptr;
-    hipLaunchKernelGGL((render_persistent_kernel<false, 5, 32, 12, 4, true, true, true>), dim3((unsigned)blocks), dim3(256), 0, stream, Q, tile_counter, order, rstart, pixel_cost);
-    return Q.wave_log ? blocks * 4 : 0;
-  }
-  if (cfg.occupancy >= 6 && launch_wide_lean6(stream, P, cfg, tile_counter, order, rstart, pixel_cost, log_waves)) return log_waves;
-  if (cfg.occupancy >= 5) return launch_persistent_occ<5>(stream, P, cfg, tile_counter, order, rstart, pixel_cost);
-  return launch_persistent_occ<4>(stream, P, cfg, tile_counter, order, rstart, pixel_cost);
+  for (const PersistentEntry& e : PERSISTENT_BUILDS)
+    if (e.build == plan.build) {
+      hipLaunchKernelGGL(e.kernel, dim3((unsigned)plan.blocks), dim3(256), 0, stream, P, tile_counter, order, rstart, pixel_cost);
+      return plan.log_waves;
+    }
+  return -1;      // no such build: nothing is launched in its place
 }
 
 }  // namespace dr

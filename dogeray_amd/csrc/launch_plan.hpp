@@ -1,0 +1,130 @@
+// Which build of render_persistent_kernel a launch runs, with what grid, and the launch-size rules around it, as plain data.
+// No HIP: kernels_render.hip launches what plan_persistent returns, and the host build exports it (tests/test_launch_plan_host.py).
+// ODDITY marks behaviour nobody would write on purpose that is kept bit for bit; DESIGN.md 4.3 explains each.
+#pragma once
+#include "../../include/dogeray_amd.h"
+#include "device_layout.h"
+
+namespace dr {
+
+constexpr int MAX_REGIONS = 8;           // tile queues of the persistent kernels (one per XCD)
+constexpr int WAVE_LOG_WAVES = 16384;    // waves the wave log (option wave_log) has room for
+
+// What a launch of the persistent kernel needs to know of the context's options (dr_context_set_option)
+struct PersistentCfg {
+  int traversal;             // the traversal the launch really uses (DR_TRAVERSAL_WIDE or DR_TRAVERSAL_THREADED)
+  int occupancy;             // 4, 5 or 6 waves per SIMD
+  int schedule;              // 0, 1, 2: option "schedule" (DR_SCHEDULE_* below)
+  int num_cus;               // CUs the launch may fill (the device's less option reserve_cus)
+  int coop_tiles_per_wave;
+  bool count;                // counting build
+};
+
+struct PersistentBuild { int count, occ, trav_min, park_min, unroll, wide, coop, perframe; };      // render_persistent_kernel's template arguments
+inline bool operator==(const PersistentBuild& a, const PersistentBuild& b) {
+  return a.count == b.count && a.occ == b.occ && a.trav_min == b.trav_min && a.park_min == b.park_min && a.unroll == b.unroll && a.wide == b.wide &&
+         a.coop == b.coop && a.perframe == b.perframe;
+}
+
+// The instantiated schedules (option "schedule") as TRAV_MIN, PARK_MIN, P_UNROLL and the work-sharing build's own PARK_MIN, P_UNROLL:
+// 0 = the tuned one -- shade / refill below 32 walking lanes, leaf steps for 20 lanes, two steps per loop iteration --; 1 and 2 keep the other
+// paths of the loop alive in the tests (leaf steps for 8 lanes, one step per iteration; shade / refill below 48 lanes, leaves tested on the
+// spot).  Every other combination rounds 2 and 3 measured is in profiles/r2_*, r3_p_*.
+// (the work-sharing build's own pair: short launches like fewer lanes per leaf step and more steps between two looks at the queue: 32 / 12 / 4
+// against the lean build's 32 / 20 / 2, one frame per launch 0.915 against 0.945 ms, profiles/r4_q_short_launch_schedule.txt)
+#define DR_SCHEDULE_0 32, 20, 2, 12, 4
+#define DR_SCHEDULE_1 32, 8, 1, 8, 1
+#define DR_SCHEDULE_2 48, 0, 1, 0, 1
+struct PersistentSchedule { int trav_min, park_min, unroll, coop_park, coop_unroll; };
+constexpr PersistentSchedule PERSISTENT_SCHEDULES[3] = {{DR_SCHEDULE_0}, {DR_SCHEDULE_1}, {DR_SCHEDULE_2}};
+
+// Every instantiation that exists, X(count, occ, trav_min, park_min, unroll, wide, coop, perframe): 33.  Per occupancy 4 / 5 and schedule: wide
+// counting, wide work-sharing, wide lean, threaded counting, threaded plain (the threaded builds never read COOP: they carry the template's
+// default, true); then the six-wave lean build -- 80 VGPRs and 26 KiB of LDS per workgroup: only the wide walk's lean build fits, and only with
+// the default schedule --, its twin that stores every frame of a batch into its own buffer, and the five-wave work-sharing build that does.
+#define DR_BUILDS_OF_(X, OCC, T, P, U, CP, CU)                                                                                          \
+  X(true, OCC, T, P, U, true, false, false) X(false, OCC, T, CP, CU, true, true, false) X(false, OCC, T, P, U, true, false, false)     \
+  X(true, OCC, T, P, U, false, true, false) X(false, OCC, T, P, U, false, true, false)
+#define DR_BUILDS_OF(X, OCC, SCHEDULE) DR_BUILDS_OF_(X, OCC, SCHEDULE)
+#define DR_BUILDS_OCC(X, OCC) DR_BUILDS_OF(X, OCC, DR_SCHEDULE_0) DR_BUILDS_OF(X, OCC, DR_SCHEDULE_1) DR_BUILDS_OF(X, OCC, DR_SCHEDULE_2)
+#define DR_PERSISTENT_BUILDS(X)                                                                                                         \
+  X(false, 6, 32, 20, 2, true, false, true) X(false, 6, 32, 20, 2, true, false, false) X(false, 5, 32, 12, 4, true, true, true)        \
+  DR_BUILDS_OCC(X, 5) DR_BUILDS_OCC(X, 4)
+
+// The instantiations of the per-tile kernel, X(count, mode, occ): 12
+#define DR_TILE_BUILDS_OCC(X, OCC)                                                                                                      \
+  X(true, DR_TRAVERSAL_ORDERED, OCC) X(true, DR_TRAVERSAL_WIDE, OCC) X(true, DR_TRAVERSAL_THREADED, OCC)                                \
+  X(false, DR_TRAVERSAL_ORDERED, OCC) X(false, DR_TRAVERSAL_WIDE, OCC) X(false, DR_TRAVERSAL_THREADED, OCC)
+#define DR_TILE_BUILDS(X) DR_TILE_BUILDS_OCC(X, 6) DR_TILE_BUILDS_OCC(X, 4)
+
+struct PersistentPlan {
+  PersistentBuild build;
+  int blocks;               // workgroups of 256 threads
+  int log_waves;            // what launch_persistent_kernel returns: the waves the caller takes to have written the wave log
+  bool clear_wave_log;      // the launch passes wave_log = nullptr
+};
+
+// fewer than tiles_per_wave tiles for each of `waves` waves (the callers measure against different wave counts)
+inline bool short_launch(long long work, int tiles_per_wave, long long waves) { return work < (long long)tiles_per_wave * waves; }
+
+// the six-wave lean build fits, and with it the builds that store every frame of a batch into its own buffer (out_frame_stride != 0) exist
+inline bool persistent_can_store_per_frame(const PersistentCfg& cfg) {
+  return cfg.traversal == DR_TRAVERSAL_WIDE && !cfg.count && cfg.schedule == 0 && cfg.occupancy >= 6;
+}
+
+// work = tiles x frames of the launch; coop_steps, per_frame, wave_log_on: RenderParams' coop_steps, out_frame_stride != 0, wave_log != null
+inline PersistentPlan plan_persistent(const PersistentCfg& cfg, long long work, int coop_steps, bool per_frame, bool wave_log_on) {
+  const PersistentSchedule& s = PERSISTENT_SCHEDULES[cfg.schedule == 0 ? 0 : cfg.schedule == 1 ? 1 : 2];
+  const bool wide = cfg.traversal == DR_TRAVERSAL_WIDE, six = persistent_can_store_per_frame(cfg);
+  per_frame = per_frame && six;      // (every other configuration renders a batch into one buffer: context_pipeline.cpp asks before it sets a stride)
+  auto blocks_for = [&](int occ) {   // occ waves per SIMD on every CU, four waves per workgroup, no more waves than work
+    const int blocks = cfg.num_cus * occ;
+    return (long long)blocks * 4 > work ? (int)((work + 3) / 4) : blocks;
+  };
+  PersistentPlan p;
+  // ODDITY: too short for six waves is measured against a five-wave grid NOT clamped to the work ...
+  if (six && !(coop_steps > 0 && short_launch(work, cfg.coop_tiles_per_wave, (long long)cfg.num_cus * 5 * 4))) {
+    p.build = {false, 6, s.trav_min, s.park_min, s.unroll, true, false, per_frame};
+    p.blocks = blocks_for(6);
+    p.log_waves = 0; p.clear_wave_log = true;      // (the lean kernel does not log its waves)
+    return p;
+  }
+  const int occ = cfg.occupancy >= 5 ? 5 : 4;
+  p.blocks = blocks_for(occ);
+  p.clear_wave_log = wave_log_on && p.blocks * 4 > WAVE_LOG_WAVES;
+  p.log_waves = wave_log_on && !p.clear_wave_log ? p.blocks * 4 : 0;
+  // the cooperative drain shortens a launch's tail; with many tiles per wave the tail does not show and the leaner build is faster
+  // ODDITY: ... and here against the launch's own grid, which is; a short group of per-frame stores does not ask again
+  const bool coop = per_frame || (coop_steps > 0 && short_launch(work, cfg.coop_tiles_per_wave, (long long)p.blocks * 4));
+  // ODDITY: only the wide work-sharing build writes the log, but the threaded builds and the counting build of a short launch keep log_waves
+  if (!wide) p.build = {cfg.count, occ, s.trav_min, s.park_min, s.unroll, false, true, false};
+  else if (cfg.count) p.build = {true, occ, s.trav_min, s.park_min, s.unroll, true, false, false};
+  else if (coop) p.build = {false, occ, s.trav_min, s.coop_park, s.coop_unroll, true, true, per_frame};
+  else p.build = {false, occ, s.trav_min, s.park_min, s.unroll, true, false, false};
+  if (wide && !coop) p.log_waves = 0;
+  return p;
+}
+
+// Tile queues of a launch of `tiles` tiles (batch_hint frames of them): one per XCD, or one
+inline int plan_regions(int tiles, int batch_hint, bool xcd_regions, bool short_one_queue, int tiles_per_wave, int num_cus) {
+  int regions = xcd_regions ? MAX_REGIONS : 1;
+  if (tiles < 64 * MAX_REGIONS) regions = 1;                 // tiny frames: one queue
+  // a short launch (few tiles per wave: one frame, or a thin stripe of a few) ends when its slowest band ends; one queue
+  // balances better there than eight (1.88 instead of 2.00 ms for a single 1920x1080 frame of the bench scene)
+  // ODDITY: five waves on every CU of the device: num_cus WITHOUT option reserve_cus taken off
+  if (short_one_queue && short_launch((long long)tiles * batch_hint, tiles_per_wave, (long long)num_cus * 5 * 4)) regions = 1;
+  return regions;
+}
+
+// Tile order: at most split_waves % of the waves start with a part of a split tile.  ODDITY: the device's num_cus again, and never six waves
+inline int plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) {
+  return split_parts > 1 ? (int)((long long)num_cus * (occupancy >= 5 ? 5 : 4) * 4 * split_waves / (100 * split_parts)) : 0;
+}
+
+// The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
+inline void order_geometry(const RenderParams& P, float out[5]) {
+  out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;
+  out[3] = (float)P.ncols; out[4] = (float)P.gy;
+}
+
+}  // namespace dr

@@ -439,6 +439,65 @@ def test_wave_log_and_pixel_cost_of_a_single_frame(dr, ctx, synth):
         ctx.set_option("wave_log", 0)
 
 
+def test_wave_log_tells_which_build_a_launch_ran(dr, ctx, synth):
+    """The builds of the persistent kernel render the same frame; the wave log is what tells them apart: only the work-sharing build writes it.  A
+    128x128 frame has 256 tiles -- 64 workgroups on any device with at least 16 CUs, one queue.  The NUMBER of rows dr_stats_wave_log returns is the host's
+    plan (launch_plan.hpp; asserted equal to tools/host_kernel.py's); what the DEVICE did is read from the stamps, which come from one monotonic clock:
+      * default options, a short launch, twice: the second launch's 256 rows all begin after the first's latest end, with begin <= queue empty <= end
+        -- the work-sharing build ran and wrote exactly these rows, none is left over from an earlier launch;
+      * coop_tiles_per_wave = 0 -- how the certificate tests force the lean build: the plan reports no row;
+      * the counting build of the same short launch: the plan reports 256 rows (a known oddity) although that build does not log, so
+        the rows read back are bit for bit the second launch's -- neither the lean nor the counting launch wrote a word of them.
+    Same frame every time."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
+    import host_kernel
+    host_kernel.build()
+    ps = dr.Scene.load(os.path.join(synth["dir"], "hf_small.rts"))
+    ps.build_bvh()
+    ctx.upload(ps)
+    s = ps.settings()
+    st = dr.pack_settings13(s, 1, spp=1)
+    W, H = 128, 128
+    tpw = ctx.get_option("coop_tiles_per_wave")
+
+    def plan(tiles_per_wave, count):
+        out = []
+        for cus in (16, 256):
+            cfg = {"traversal": dr.TRAVERSAL_WIDE, "occupancy": ctx.get_option("occupancy"), "schedule": ctx.get_option("schedule"), "num_cus": cus,
+                   "coop_tiles_per_wave": tiles_per_wave, "count": count}
+            out.append(dict(zip(host_kernel.PLAN_FIELDS, host_kernel.persistent_plan(cfg, 256, ctx.get_option("coop_steps"), 0, 1))))
+        assert out[0] == out[1]
+        return out[0]
+
+    shared, lean, counting = plan(tpw, 0), plan(0, 0), plan(tpw, 1)
+    assert (shared["count"], shared["coop"], shared["occ"], shared["blocks"], shared["log_waves"]) == (0, 1, 5, 64, 256)
+    assert (lean["count"], lean["coop"], lean["occ"], lean["blocks"], lean["log_waves"]) == (0, 0, 6, 64, 0)
+    assert (counting["count"], counting["coop"], counting["occ"], counting["blocks"], counting["log_waves"]) == (1, 0, 5, 64, 256)
+    ctx.set_option("wave_log", 1)
+    try:
+        first_frame = ctx.render_frame(st, W, H, s.background, 5)
+        first = ctx.wave_log().copy()
+        a = ctx.render_frame(st, W, H, s.background, 5)
+        log = ctx.wave_log().copy()
+        assert len(first) == len(log) == shared["log_waves"]
+        begin, empty, end = log[:, 0].astype(np.int64), log[:, 1].astype(np.int64), log[:, 2].astype(np.int64)
+        assert np.all(begin <= empty) and np.all(empty <= end)
+        assert begin.min() > first[:, 2].astype(np.int64).max() > 0          # every row was written by THIS launch
+        ctx.set_option("coop_tiles_per_wave", 0)
+        b = ctx.render_frame(st, W, H, s.background, 5)
+        assert len(ctx.wave_log()) == lean["log_waves"]
+        ctx.set_option("coop_tiles_per_wave", tpw)
+        ctx.enable_counters(True)
+        c = ctx.render_frame(st, W, H, s.background, 5)
+        assert np.array_equal(ctx.wave_log(), log)                            # neither the lean nor the counting launch touched the log
+        assert np.array_equal(first_frame, a) and np.array_equal(a, b) and np.array_equal(a, c)
+    finally:
+        ctx.enable_counters(False)
+        ctx.set_option("coop_tiles_per_wave", tpw)
+        ctx.set_option("wave_log", 0)
+
+
 def test_trace_only_probe_agrees_with_the_plain_walk(dr, ctx, synth):
     """dr_context_probe_trace (measurement aid): the rays of one frame, logged by the counting build in wavefront order, walked by the trace-only kernel --
     persistent waves refilling from the ray list -- give the same (t bits, slot) as the one-ray-per-lane walk, ray for ray; the log holds every ray of the frame."""

@@ -25,6 +25,7 @@
 #include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
 #include "../dogeray_amd/csrc/device_upscale.hpp"
+#include "../dogeray_amd/csrc/launch_plan.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
 #include "../dogeray_amd/csrc/scene_host.hpp"
@@ -391,6 +392,30 @@ void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, co
     t[i] = tri_hit(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), mk(v0[3 * i], v0[3 * i + 1], v0[3 * i + 2]),
                    mk(e1[3 * i], e1[3 * i + 1], e1[3 * i + 2]), mk(e2[3 * i], e2[3 * i + 1], e2[3 * i + 2]));
 }
+
+// launch_plan.hpp on the host (tests/test_launch_plan_host.py).  cfg6: traversal, occupancy, schedule, num_cus, coop_tiles_per_wave, count;
+// out11: the build's eight template arguments (count, occ, trav_min, park_min, unroll, wide, coop, perframe), blocks, log_waves, clear_wave_log
+void hk_persistent_plan(const int* cfg6, long long work, int coop_steps, int per_frame, int wave_log_on, int* out11) {
+  const PersistentCfg cfg = {cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0};
+  const PersistentPlan p = plan_persistent(cfg, work, coop_steps, per_frame != 0, wave_log_on != 0);
+  const PersistentBuild& b = p.build;
+  const int v[11] = {b.count, b.occ, b.trav_min, b.park_min, b.unroll, b.wide, b.coop, b.perframe, p.blocks, p.log_waves, p.clear_wave_log};
+  memcpy(out11, v, sizeof(v));
+}
+int hk_persistent_can_store_per_frame(const int* cfg6) { return persistent_can_store_per_frame(PersistentCfg{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0}); }
+// the instantiations of render_persistent_kernel (DR_PERSISTENT_BUILDS), eight ints each, at most `room` of them; returns how many there are
+int hk_persistent_builds(int* out, int room) {
+#define HK_BUILD(COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME) {COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME},
+  static const int builds[][8] = {DR_PERSISTENT_BUILDS(HK_BUILD)};
+#undef HK_BUILD
+  const int n = (int)(sizeof(builds) / sizeof(builds[0]));
+  if (out && room > 0) memcpy(out, builds, sizeof(builds[0]) * (size_t)(room < n ? room : n));
+  return n;
+}
+int hk_plan_regions(int tiles, int batch_hint, int xcd_regions, int short_one_queue, int tiles_per_wave, int num_cus) {
+  return plan_regions(tiles, batch_hint, xcd_regions != 0, short_one_queue != 0, tiles_per_wave, num_cus);
+}
+int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 
 const char* hk_last_error() { return hk_err.c_str(); }
 

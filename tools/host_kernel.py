@@ -71,6 +71,12 @@ def lib():
         L.hk_reproject_m2.argtypes = L.hk_reproject.argtypes + [C.c_void_p, C.c_void_p]
         L.hk_moments_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
         L.hk_error.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.hk_persistent_plan.restype = None
+        L.hk_persistent_plan.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.hk_persistent_can_store_per_frame.argtypes = [C.POINTER(C.c_int)]
+        L.hk_persistent_builds.argtypes = [C.c_void_p, C.c_int]
+        L.hk_plan_regions.argtypes = [C.c_int] * 6
+        L.hk_plan_split_limit.argtypes = [C.c_int] * 4
         _lib = L
     return _lib
 
@@ -363,3 +369,40 @@ def error(acc, hist, m2, settings13, divide_by, tolerance, nthreads=4):
         raise RuntimeError(lib().hk_last_error().decode())
     d = {"pixels": int(grid[0]) * int(grid[1]), "estimated": int(res[0]), "above": int(res[1]), "sum_var_q16": int(res[2]), "bins": [int(v) for v in res[3:]]}
     return sigma, d
+
+
+BUILD_FIELDS = ("count", "occ", "trav_min", "park_min", "unroll", "wide", "coop", "perframe")
+PLAN_FIELDS = BUILD_FIELDS + ("blocks", "log_waves", "clear_wave_log")
+CFG_FIELDS = ("traversal", "occupancy", "schedule", "num_cus", "coop_tiles_per_wave", "count")
+
+
+def _cfg(cfg):
+    return (C.c_int * 6)(*[int(cfg[k]) for k in CFG_FIELDS])
+
+
+def persistent_plan(cfg, work, coop_steps, per_frame, wave_log_on):
+    """launch_plan.hpp plan_persistent: cfg is a dict with CFG_FIELDS -> the plan as a tuple of ints in the order of PLAN_FIELDS (the build's
+    eight template arguments first)."""
+    out = (C.c_int * 11)()
+    lib().hk_persistent_plan(_cfg(cfg), int(work), int(coop_steps), int(per_frame), int(wave_log_on), out)
+    return tuple(out)
+
+
+def persistent_can_store_per_frame(cfg):
+    return bool(lib().hk_persistent_can_store_per_frame(_cfg(cfg)))
+
+
+def persistent_builds():
+    """The instantiations of render_persistent_kernel (DR_PERSISTENT_BUILDS) as a list of tuples in the order of BUILD_FIELDS."""
+    n = lib().hk_persistent_builds(None, 0)
+    out = np.zeros((n, 8), np.int32)
+    assert lib().hk_persistent_builds(out.ctypes.data, n) == n
+    return [tuple(int(v) for v in row) for row in out]
+
+
+def plan_regions(tiles, batch_hint, xcd_regions, short_one_queue, tiles_per_wave, num_cus):
+    return int(lib().hk_plan_regions(int(tiles), int(batch_hint), int(xcd_regions), int(short_one_queue), int(tiles_per_wave), int(num_cus)))
+
+
+def plan_split_limit(num_cus, occupancy, split_parts, split_waves):
+    return int(lib().hk_plan_split_limit(int(num_cus), int(occupancy), int(split_parts), int(split_waves)))
