@@ -187,6 +187,7 @@ _API = [
     ("dr_stats_phase_counts", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int]),
     ("dr_stats_cert_mask", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_cert_levels", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
+    ("dr_stats_camera_entry", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
@@ -592,6 +593,16 @@ class Context:
         out = np.zeros(n.value, dtype=np.uint8)
         if len(out):
             _check(lib().dr_stats_cert_levels(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
+        return out
+
+    def camera_entry(self):
+        """int32 entry codes of the last certified view's tiles (dr_stats_camera_entry; wide record << 1 | is-leaf at which the tile's camera rays start,
+        0 = the root, -1 = nothing can be seen from the tile), or an empty array when no table is in use."""
+        n = C.c_int()
+        _check(lib().dr_stats_camera_entry(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int32)
+        if len(out):
+            _check(lib().dr_stats_camera_entry(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
         return out
 
     def wave_log(self, max_waves=16384):

@@ -45,6 +45,7 @@ const Option OPTIONS[] = {
     {"camera_cert", &dr_context::camera_cert, 0, 1, 0, false},
     {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, false},
     {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, false},
+    {"camera_entry", /* (as above) */ &dr_context::camera_entry, 0, 1, 0, false},
 };
 
 const Option* find_option(const std::string& name) {
@@ -71,7 +72,7 @@ int set_option(dr_context* c, const std::string& name, int v) {
       c->pipe_next = 0; c->pipe_groups = 0;
     }
   }
-  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels) {
+  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels || o->member == &dr_context::camera_entry) {
     // frames submitted before the change are launched with the setting they were submitted under
     if (!c->pipe_pending.empty()) DR_TRY(pipeline_flush(c));
     c->cert_valid = false;
@@ -179,9 +180,13 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   c->walk_bytes = img.walk.size() * sizeof(DevUnit);
   c->wide.release();
   c->wide_bytes = 0; c->wide_depth = img.wide_depth; c->wide_nodes = img.wide_nodes; c->wide_pmax = img.wide_pmax; c->wide_mu = img.wide_mu; c->wide_own_bounds = img.wide_own_bounds;
+  c->wide_leaf_rec.release(); c->wide_range.release(); c->wide_leaves = 0;
   if (!img.wide.empty()) {
     DR_TRY(c->wide.upload(img.wide));
     c->wide_bytes = img.wide.size() * sizeof(DevUnit);
+    DR_TRY(c->wide_leaf_rec.upload(img.wide_leaf_rec));
+    DR_TRY(c->wide_range.upload(img.wide_range));
+    c->wide_leaves = (int)img.wide_leaf_rec.size();
   }
   DR_TRY(c->pairs.upload(img.pairs));
   DR_TRY(c->prims.upload(img.prims));
@@ -308,6 +313,19 @@ int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tile
   HIP_TRY(hipStreamSynchronize(c->stream));
   *n_tiles = c->cert_tiles;
   if (max > 0) HIP_TRY(hipMemcpy(out_bytes, c->cert_level, (size_t)(c->cert_tiles < max ? c->cert_tiles : max), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles) {
+  if (!c || !n_tiles || max < 0 || (max > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n_tiles = 0;
+  if (!(c->camera_entry && c->cert_valid && c->entry_ok && c->cert_word && c->cert_tiles > 0)) return DR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *n_tiles = c->cert_tiles;
+  const int n = c->cert_tiles < max ? c->cert_tiles : max;
+  if (n > 0) HIP_TRY(hipMemcpy(out, c->cert_word, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int t = 0; t < n; t++) out[t] >>= ENTRY_SHIFT;      // (arithmetic: ENTRY_NONE stays -1)
   return DR_OK;
 }
 

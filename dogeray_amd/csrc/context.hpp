@@ -156,11 +156,19 @@ struct dr_context {
   DevMem<uint32_t> cert_mask;
   DevMem<uint32_t> cert_level;             // the grades, four tiles to a word
   bool cert_valid = false;                 // cert_key's mask is computed (or known to be unusable: cert_ok false)
-  bool cert_ok = false;
+  bool cert_ok = false;                    // ... and the view has a certificate
+  bool entry_ok = false;                   // ... and an entry table (option camera_entry)
   float cert_key[22] = {0};
   float cert_seen[22] = {0};               // the key of the last single-frame launch that found no mask
   float cert_k[dr::CERT_MAX_LEVELS + 1] = {1}; // the margin's factor of a tile of grade g ([0] = 1; [g] = 1e-4 / the ladder's step g - 1, rounded up)
   int cert_tiles = 0;                      // tiles of the keyed launch
+  // the camera rays' entry table of the same view, computed behind the certificate by launch_camera_entry and kept under the same
+  // key: a word per tile, entry code << 3 | grade -- what the lean and the counting build read
+  int camera_entry = 1;                    // option: a tile's camera rays start at the lowest record that holds every leaf they can reach (0: at the root)
+  DevMem<uint32_t> wide_leaf_rec, wide_range;   // the wide tree's side arrays (linearise.hpp): rank -> leaf record; record -> the ranks under it
+  int wide_leaves = 0;
+  DevMem<uint32_t> entry_mm;               // scratch: the lowest and the highest rank per tile
+  DevMem<uint32_t> cert_word;              // a word per tile: entry code << ENTRY_SHIFT | grade (RenderParams cert_level)
   // frame + accumulator
   DevMem<int32_t> frame;
   DevMem<int32_t> accum; int accW = 0, accH = 0;

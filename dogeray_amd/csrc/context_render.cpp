@@ -72,37 +72,52 @@ void feedback_buffers(dr_context* c, const LaunchSite& site, const RenderParams&
   pcost = c->pixel_cost;
 }
 
-// The camera rays' grazing certificate of the launch's view: reuses the cached mask and grades when the key matches, recomputes them on
-// the site's stream otherwise -- except in a pipelined launch that may run beside others reading them (site.hold_order): that one keeps the scene's margin.
-// Without a usable certificate P keeps cert_level = null and wide_cert_k = 1: every ray carries the scene's margin, as before.
+// The camera rays' grazing certificate of the launch's view and their entry table: reuses the cached tile words when the key matches,
+// recomputes them on the site's stream otherwise -- except in a pipelined launch that may run beside others reading them (site.hold_order): that one
+// keeps the scene's margin and the root.  The two are independent -- the certificate needs a tree with own bounds (option camera_cert), the table any
+// wide tree (option camera_entry) -- and share the view, the key and the word per tile that the kernel reads.
+// Without either P keeps cert_level = null and wide_cert_k = 1: every ray carries the scene's margin and starts at the root, as before.
 void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles) {
   P.cert_level = nullptr;
   for (float& k : P.wide_cert_k) k = 1.0f;
-  if (!c->camera_cert || traversal_of(c) != DR_TRAVERSAL_WIDE || !c->wide || c->wide_own_bounds <= 0 || !(c->wide_mu.e > 0.0f) || tiles <= 0) return;
+  const bool want_cert = c->camera_cert && c->wide_own_bounds > 0 && c->wide_mu.e > 0.0f;
+  const bool want_entry = c->camera_entry && c->wide_leaf_rec && c->wide_range && c->wide_leaves > 0;
+  if ((!want_cert && !want_entry) || traversal_of(c) != DR_TRAVERSAL_WIDE || !c->wide || tiles <= 0) return;
   float key[22] = {0};
   memcpy(key, c->cur_settings, 13 * sizeof(float));
   key[13] = (float)P.W; key[14] = (float)P.H; key[15] = (float)P.stripe_mod; key[16] = (float)P.stripe_rem; key[17] = (float)P.ncols; key[18] = (float)P.gy;
-  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor; key[21] = (float)c->cert_levels;
+  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor; key[21] = (float)(c->cert_levels + 2 * c->camera_entry + 4 * c->camera_cert);
   if (!(c->cert_valid && memcmp(c->cert_key, key, sizeof(key)) == 0)) {
     if (site.hold_order) return;
-    // a single-frame launch of a view not seen before (a moving camera: every frame a new view) does not pay for the mask (0.16 ms, more than it
-    // saves in one frame): the view's second launch, or any launch of several frames, computes it
+    // a single-frame launch of a view not seen before (a moving camera: every frame a new view) does not pay for the mask and the table (more than
+    // they save in one frame): the view's second launch, or any launch of several frames, computes them
     if (P.batch < 2 && memcmp(c->cert_seen, key, sizeof(key)) != 0) { memcpy(c->cert_seen, key, sizeof(key)); return; }
     const double a_star = 1e-4 * (double)c->cert_factor;
     CertView cv;
     c->cert_valid = false;
-    c->cert_ok = fill_cert_view(P, a_star, c->wide_mu.e, cv);
-    if (c->cert_ok) {
-      cert_ladder(c->cert_factor, c->cert_levels != 0, cv);
-      if (c->cert_mask.grow(cert_mask_words(tiles, cv.n_levels), site.stream) != DR_OK || c->cert_level.grow(cert_level_words(tiles), site.stream) != DR_OK) return;
-      launch_cert_mask(site.stream, c->prims, c->n_prims, cv, c->cert_mask, c->cert_level, tiles);
-      for (int g = 1; g <= CERT_MAX_LEVELS; g++) c->cert_k[g] = g <= cv.n_levels ? cert_factor_k(cv.level_a[g - 1]) : 1.0f;
+    c->cert_ok = c->entry_ok = false;
+    // (the table asks nothing of the view's E: a scene without own bounds passes any)
+    if (fill_cert_view(P, a_star, want_cert ? c->wide_mu.e : 1.0f, cv)) {
+      if (c->cert_level.grow(cert_level_words(tiles), site.stream) != DR_OK || c->cert_word.grow((size_t)tiles, site.stream) != DR_OK ||
+          (want_entry && c->entry_mm.grow(entry_mm_words(tiles), site.stream) != DR_OK)) return;
+      for (float& k : c->cert_k) k = 1.0f;
+      if (want_cert) {
+        cert_ladder(c->cert_factor, c->cert_levels != 0, cv);
+        if (c->cert_mask.grow(cert_mask_words(tiles, cv.n_levels), site.stream) != DR_OK) return;
+        launch_cert_mask(site.stream, c->prims, c->n_prims, cv, c->cert_mask, c->cert_level, tiles);
+        for (int g = 1; g <= CERT_MAX_LEVELS; g++) c->cert_k[g] = g <= cv.n_levels ? cert_factor_k(cv.level_a[g - 1]) : 1.0f;
+      } else {
+        (void)hipMemsetAsync(c->cert_level, 0, cert_level_words(tiles) * sizeof(uint32_t), site.stream);      // no certificate: grade 0, the scene's margin
+      }
+      // the tiles' words for the kernel: the grades, and the camera rays' entry records (no table: the root everywhere)
+      launch_camera_entry(site.stream, c->wide, c->wide_leaf_rec, c->wide_range, c->wide_leaves, cv, want_entry ? c->entry_mm.p : nullptr, c->cert_level, c->cert_word, tiles);
+      c->cert_ok = want_cert; c->entry_ok = want_entry;
     }
     memcpy(c->cert_key, key, sizeof(key));
     c->cert_tiles = tiles;
     c->cert_valid = true;
   }
-  if (c->cert_ok) { P.cert_level = c->cert_level; memcpy(P.wide_cert_k, c->cert_k, sizeof(P.wide_cert_k)); }
+  if (c->cert_ok || c->entry_ok) { P.cert_level = c->cert_word; memcpy(P.wide_cert_k, c->cert_k, sizeof(P.wide_cert_k)); }
 }
 
 }  // namespace

@@ -647,6 +647,50 @@ __device__ __forceinline__ WideRay wide_ray(V3 o, V3 d, V3 inv, float pmax, floa
   return w;
 }
 
+// The tiles a box can be seen from: the second half of cert_leaf's rule, as a function of the box alone (rc = its centre - cv.from, h = its half extents
+// with the slop in, rcn = |rc|, hn = |h|, fn = |cv.from|, cn = |centre|).  1 with rect, or 2 (every tile).  The camera rays' entry table asks it of
+// every leaf (entry_leaf below).
+// (ENTRY_MUTANT: a wrong rule on purpose, host build only -- tests/test_camera_entry_host.py shows that its cases catch each)
+#ifdef DR_HOST_BUILD
+static thread_local int entry_mutant = 0;
+#define ENTRY_MUTANT(k) (entry_mutant == (k))
+#else
+#define ENTRY_MUTANT(k) false
+#endif
+__device__ __forceinline__ int cert_box_rect(const CertView& cv, const double* rc, const double* h, double rcn, double hn, double fn, double cn, int* rect) {
+  const double zc = rc[0] * cv.w[0] + rc[1] * cv.w[1] + rc[2] * cv.w[2];
+  const double zh = h[0] * __builtin_fabs(cv.w[0]) + h[1] * __builtin_fabs(cv.w[1]) + h[2] * __builtin_fabs(cv.w[2]);
+  const double zmin = zc - zh, zmax = zc + zh;
+  if (!(zmin > 2.0 * cv.r_o + 1e-9 * (fn + cn + hn) && zmin == zmin && zmax < 1e300)) return 2;
+  double ulo = 1e300, uhi = -1e300, vlo = 1e300, vhi = -1e300;
+  for (int k = 0; k < 8; k++) {
+    double x[3];
+    for (int a = 0; a < 3; a++) x[a] = rc[a] + (((k >> a) & 1) ? h[a] : -h[a]);
+    const double z = x[0] * cv.w[0] + x[1] * cv.w[1] + x[2] * cv.w[2], s = cv.D / z;
+    double pl[3];
+    for (int a = 0; a < 3; a++) pl[a] = cv.from[a] + x[a] * s - cv.llc[a];
+    const double nu = cv.du[0] * pl[0] + cv.du[1] * pl[1] + cv.du[2] * pl[2], nv = cv.dv[0] * pl[0] + cv.dv[1] * pl[1] + cv.dv[2] * pl[2];
+    ulo = __builtin_fmin(ulo, nu); uhi = __builtin_fmax(uhi, nu); vlo = __builtin_fmin(vlo, nv); vhi = __builtin_fmax(vhi, nv);
+  }
+  const double rmax = rcn + hn;
+  double lens = cv.r_o * (1.0 + (cv.D + cv.r_o) / (zmin - cv.r_o) + rmax * (cv.D + zmax) / (zmin * (zmin - cv.r_o)));
+  if (ENTRY_MUTANT(2)) lens = 0.0;
+  const double xlo = (ulo - cv.du_n * lens) * cv.den_w, xhi = (uhi + cv.du_n * lens) * cv.den_w;
+  const double ylo = (vlo - cv.dv_n * lens) * cv.den_h, yhi = (vhi + cv.dv_n * lens) * cv.den_h;
+  if (!(xlo == xlo && xhi == xhi && ylo == ylo && yhi == yhi)) return 2;
+  auto pix = [](double f, int hi) { return f < -8.0 ? -8 : (f > (double)hi + 8.0 ? hi + 8 : (int)__builtin_floor(f)); };
+  const int px0 = pix(xlo, cv.nx) - 2, px1 = pix(xhi, cv.nx) + 1, py0 = pix(ylo, cv.ny) - 2, py1 = pix(yhi, cv.ny) + 1;
+  const int gc0 = (px0 < 0 ? 0 : px0) >> 3, gc1 = (px1 >= cv.nx ? cv.nx - 1 : px1) >> 3;
+  rect[2] = (py0 < 0 ? 0 : py0) >> 3; rect[3] = (py1 >= cv.ny ? cv.ny - 1 : py1) >> 3;
+  // global block columns [gc0, gc1] -> the launch's local columns (global = stripe_rem + local * stripe_mod)
+  const int l0 = gc0 <= cv.stripe_rem ? 0 : (gc0 - cv.stripe_rem + cv.stripe_mod - 1) / cv.stripe_mod;
+  const int l1 = gc1 < cv.stripe_rem ? -1 : (gc1 - cv.stripe_rem) / cv.stripe_mod;
+  rect[0] = l0; rect[1] = l1 < cv.ncols - 1 ? l1 : cv.ncols - 1;
+  if (px1 < 0 || py1 < 0 || px0 >= cv.nx || py0 >= cv.ny) rect[1] = rect[0] - 1;       // off the grid: no tile
+  if (ENTRY_MUTANT(1)) { rect[0]++; rect[2]++; }
+  return 1;
+}
+
 // The per-view grazing certificate of one triangle (CertView).  In double, for the triangle (v0, e1, e2) of a leaf:
 //  * its padded box is taken as a superset of the reference's (own bounds + 0.01 (1 + 1e-4) + a rounding term per axis: K:353-354 pads v1, v2, v3 in double and
 //    narrows, v0 + e1 is v1 up to one rounding of the edge), widened by what lets a float ray pass it while the real one misses (slab rounding; the float origin
@@ -694,36 +738,75 @@ __device__ __forceinline__ int cert_leaf(const CertView& cv, const float* v0f, c
   while (g < cv.n_levels && a_t >= cv.level_a[g]) g++;
   if (grade) *grade = g;
   if (g == cv.n_levels) return 0;
-  // ---- flagged: the tiles its box can be seen from
-  const double zc = rc[0] * cv.w[0] + rc[1] * cv.w[1] + rc[2] * cv.w[2];
-  const double zh = h[0] * __builtin_fabs(cv.w[0]) + h[1] * __builtin_fabs(cv.w[1]) + h[2] * __builtin_fabs(cv.w[2]);
-  const double zmin = zc - zh, zmax = zc + zh;
-  if (!(zmin > 2.0 * cv.r_o + 1e-9 * (fn + cn + hn) && zmin == zmin && zmax < 1e300)) return 2;
-  double ulo = 1e300, uhi = -1e300, vlo = 1e300, vhi = -1e300;
-  for (int k = 0; k < 8; k++) {
-    double x[3];
-    for (int a = 0; a < 3; a++) x[a] = rc[a] + (((k >> a) & 1) ? h[a] : -h[a]);
-    const double z = x[0] * cv.w[0] + x[1] * cv.w[1] + x[2] * cv.w[2], s = cv.D / z;
-    double pl[3];
-    for (int a = 0; a < 3; a++) pl[a] = cv.from[a] + x[a] * s - cv.llc[a];
-    const double nu = cv.du[0] * pl[0] + cv.du[1] * pl[1] + cv.du[2] * pl[2], nv = cv.dv[0] * pl[0] + cv.dv[1] * pl[1] + cv.dv[2] * pl[2];
-    ulo = __builtin_fmin(ulo, nu); uhi = __builtin_fmax(uhi, nu); vlo = __builtin_fmin(vlo, nv); vhi = __builtin_fmax(vhi, nv);
+  return cert_box_rect(cv, rc, h, rcn, hn, fn, cn, rect);      // flagged: the tiles its box can be seen from
+}
+
+// ---- the camera rays' entry table (option camera_entry): one record per tile at which the tile's camera rays start their walk
+// instead of the root -- the lowest record of the wide tree that has every leaf a camera ray of the tile can reach under it.  "Can reach": the leaf's
+// box, the reference's padded one of its record (units A and B) widened by cert_leaf's slop, can be seen from the tile (cert_box_rect).  Leaves are
+// numbered in depth-first order (linearise.hpp WideImage: rank), so the leaves under a record are one run of ranks and a tile only needs the lowest and
+// the highest rank that reach it.  The table while it is built, mm: word 2 t = the lowest rank of tile t, word 2 t + 1 = ~ the highest (both start at
+// all ones and only ever fall: one kind of atomic); word 2 ntiles falls to 0 when some leaf sends every tile to the root.
+// An entry code is a walk's `node` word: record << 1 | is-leaf, 0 = the root, ENTRY_NONE (-1: nothing to walk) for a tile no leaf can be seen from.
+
+// the tiles the box [mn, mx] of a leaf record can be seen from: 1 with rect, or 2 (every tile: not in front of the lens, or a NaN)
+__device__ __forceinline__ int entry_box_rect(const CertView& cv, const float* mn, const float* mx, int* rect) {
+  double c[3], h[3], rc[3];
+  double cn = 0, hn = 0, rcn = 0;
+  for (int a = 0; a < 3; a++) {
+    const double lo = mn[a], hi = mx[a];
+    c[a] = 0.5 * (lo + hi); h[a] = 0.5 * (hi - lo) + 0x1p-50 * (__builtin_fabs(lo) + __builtin_fabs(hi));      // (the sum and the difference round once each)
+    rc[a] = c[a] - cv.from[a];
+    cn += c[a] * c[a]; hn += h[a] * h[a]; rcn += rc[a] * rc[a];
   }
-  const double rmax = rcn + hn;
-  const double lens = cv.r_o * (1.0 + (cv.D + cv.r_o) / (zmin - cv.r_o) + rmax * (cv.D + zmax) / (zmin * (zmin - cv.r_o)));
-  const double xlo = (ulo - cv.du_n * lens) * cv.den_w, xhi = (uhi + cv.du_n * lens) * cv.den_w;
-  const double ylo = (vlo - cv.dv_n * lens) * cv.den_h, yhi = (vhi + cv.dv_n * lens) * cv.den_h;
-  if (!(xlo == xlo && xhi == xhi && ylo == ylo && yhi == yhi)) return 2;
-  auto pix = [](double f, int hi) { return f < -8.0 ? -8 : (f > (double)hi + 8.0 ? hi + 8 : (int)__builtin_floor(f)); };
-  const int px0 = pix(xlo, cv.nx) - 2, px1 = pix(xhi, cv.nx) + 1, py0 = pix(ylo, cv.ny) - 2, py1 = pix(yhi, cv.ny) + 1;
-  const int gc0 = (px0 < 0 ? 0 : px0) >> 3, gc1 = (px1 >= cv.nx ? cv.nx - 1 : px1) >> 3;
-  rect[2] = (py0 < 0 ? 0 : py0) >> 3; rect[3] = (py1 >= cv.ny ? cv.ny - 1 : py1) >> 3;
-  // global block columns [gc0, gc1] -> the launch's local columns (global = stripe_rem + local * stripe_mod)
-  const int l0 = gc0 <= cv.stripe_rem ? 0 : (gc0 - cv.stripe_rem + cv.stripe_mod - 1) / cv.stripe_mod;
-  const int l1 = gc1 < cv.stripe_rem ? -1 : (gc1 - cv.stripe_rem) / cv.stripe_mod;
-  rect[0] = l0; rect[1] = l1 < cv.ncols - 1 ? l1 : cv.ncols - 1;
-  if (px1 < 0 || py1 < 0 || px0 >= cv.nx || py0 >= cv.ny) rect[1] = rect[0] - 1;       // off the grid: no tile
-  return 1;
+  cn = __builtin_sqrt(cn); hn = __builtin_sqrt(hn); rcn = __builtin_sqrt(rcn);
+  const double fn = __builtin_sqrt(cv.from[0] * cv.from[0] + cv.from[1] * cv.from[1] + cv.from[2] * cv.from[2]);
+  const double slop = 0x1p-19 * (cn + hn + fn + 1.0) + cv.eps_d * (rcn + hn + cv.r_o) / cv.dmin;      // cert_leaf's
+  hn = 0;
+  for (int a = 0; a < 3; a++) { h[a] += slop; hn += h[a] * h[a]; }
+  hn = __builtin_sqrt(hn);
+  return cert_box_rect(cv, rc, h, rcn, hn, fn, cn, rect);
+}
+__device__ __forceinline__ void entry_min(uint32_t* p, uint32_t v) {
+  // read first: leaves arrive in spatial order and some hundreds of them touch a tile, nearly all of them inside what the tile has already
+#ifdef DR_HOST_BUILD
+  if (v < *p) *p = v;
+#else
+  if (v < *p) atomicMin(p, v);
+#endif
+}
+// the leaf of rank `rank` with the box [mn, mx] folded into mm
+__device__ __forceinline__ void entry_leaf(const CertView& cv, const float* mn, const float* mx, uint32_t rank, uint32_t* __restrict__ mm, int ntiles) {
+  int rect[4] = {0, -1, 0, -1};
+  if (entry_box_rect(cv, mn, mx, rect) == 2) { entry_min(&mm[2 * (size_t)ntiles], 0u); return; }
+  const uint32_t top = ENTRY_MUTANT(3) && rank > 0u ? rank - 1u : rank;
+  for (int col = rect[0]; col <= rect[1]; col++)
+    for (int r = rect[2]; r <= rect[3]; r++) {
+      const size_t t = (size_t)col * (size_t)cv.gy + (size_t)r;
+      entry_min(&mm[2 * t], rank); entry_min(&mm[2 * t + 1], ~top);
+    }
+}
+// the entry code of a tile whose leaves have the ranks [lo, ~hi_inv]: down from the root while one child holds them all.  range: two words per
+// record, the ranks of the leaves under it.  (Siblings' ranges are disjoint: at most one child holds a non-empty run.)
+__device__ __forceinline__ int entry_tile(const DevUnit* __restrict__ wide, const uint32_t* __restrict__ range, uint32_t lo, uint32_t hi_inv, bool every) {
+  if (every) return 0;
+  if (lo == 0xffffffffu) return ENTRY_NONE;
+  const uint32_t hi = ~hi_inv;
+  if (ENTRY_MUTANT(4) && lo == hi) return ENTRY_NONE;
+  uint32_t cur = 0u;
+  for (int level = 0; level < WIDE_MAX_DEPTH; level++) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(wide + (size_t)cur * WIDE_UNITS)[3];
+    const uint32_t base = w & 0xffffffu, valid = (w >> 24) & 15u, leafmask = w >> 28;
+    int next = -1;
+    for (int k = 0; k < 4; k++) {
+      const size_t ch = (size_t)base + (size_t)k;
+      if (((valid >> k) & 1u) && range[2 * ch] <= lo && hi <= range[2 * ch + 1]) next = k;
+    }
+    if (next < 0) break;
+    if ((leafmask >> next) & 1u) return (int)(((base + (uint32_t)next) << 1) | 1u);
+    cur = base + (uint32_t)next;
+  }
+  return (int)(cur << 1);
 }
 
 // The four plane bytes of a word as f16 denormals: (byte0, byte2) and (byte1, byte3), each pair in one register
@@ -907,9 +990,10 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
 }
 template <bool COUNT>
 __device__ __forceinline__ Hit closest_hit_wide(WalkRsrc wide, float pmax, float mu_e, float mu_l, float mu_v, V3 o, V3 d, Ctr& c, int* __restrict__ stack /* [word * 64] */,
-                                                float cert = 1.0f /* wide_ray_margin's */) {
+                                                float cert = 1.0f /* wide_ray_margin's */, int entry = 0 /* a camera ray's: its tile's entry code */) {
   Trav tr;
   trav_begin(tr);
+  tr.node = entry;
   WideStack ws; ws.top = 0u; ws.sp = 0; ws.sb = 0;
   const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   const WideRay wr = wide_ray(o, d, inv, pmax, mu_e, mu_l, mu_v, cert);

@@ -86,6 +86,8 @@ struct CertView {
 };
 
 constexpr int CERT_MAX_LEVELS = 7;                    // steps of the certificate's ladder at most (CertView level_a, RenderParams wide_cert_k)
+constexpr int ENTRY_NONE = -1;                        // a tile's entry code when no leaf can be seen from it (device_core.hpp entry_tile): its camera rays walk nothing
+constexpr int ENTRY_SHIFT = 3;                        // a tile's word: entry code << ENTRY_SHIFT | the certificate's grade (RenderParams cert_level; grades <= CERT_MAX_LEVELS)
 constexpr int WIDE_UNITS = 4;
 constexpr int WIDE_INDEX_BITS = 24;                   // records < 2^24 (1 GiB of them)
 constexpr int WIDE_STACK = 16;                        // stack words per lane kept in LDS (one more lives in a register)
@@ -134,6 +136,7 @@ struct DevTex {
   int32_t pad;
 };
 
+static_assert(CERT_MAX_LEVELS < (1 << ENTRY_SHIFT), "a grade fits under the entry code");
 static_assert(sizeof(DevUnit) == 16, "DevUnit");
 static_assert(sizeof(DevPair) == 64, "DevPair");
 static_assert(sizeof(DevPrim) == 48, "DevPrim");
@@ -183,7 +186,8 @@ struct RenderParams {
   int32_t region_start[9];        // identity order: region r owns tiles [region_start[r], region_start[r+1])
   WideMu wide_mu;                 // wide walk: the margin's scene constants (e = 0: none)
   float wide_cert_k[CERT_MAX_LEVELS + 1];      // ... the factor on it for camera rays of a tile of grade g of the grazing certificate ([0] = 1: the scene's margin; [g] >= 1e-4 / level_a[g - 1])
-  const uint32_t* cert_level;     // null, or one byte per tile of this launch (local column * gy + row), four to a word: the tile's grade (0: a camera ray of the tile may graze)
+  const uint32_t* cert_level;     // null, or one word per tile of this launch (local column * gy + row): the tile's grade (0: a camera ray of the tile may graze) in the low
+                                  // ENTRY_SHIFT bits, above them the entry code of its camera rays (record << 1 | is-leaf, the `node` their walk starts with; 0 the root, ENTRY_NONE)
 };
 
 // The denoiser's parameters (dr_denoise_params; defaults and ranges: params_host.hpp) and its material markers (device_denoise.hpp)

@@ -36,6 +36,12 @@ void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsign
 inline size_t cert_mask_words(int ntiles, int n_levels) { return (size_t)((ntiles + 31) / 32) * (size_t)(1 + n_levels) + 2; }
 inline size_t cert_level_words(int ntiles) { return (size_t)((ntiles + 31) / 32) * 8; }
 void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, uint32_t* level, int ntiles);
+// the camera rays' entry table of that view (option camera_entry): mm = entry_mm_words words of scratch, or null (every tile at the root); word = a word
+// per tile, its entry code << 3 | its grade from `level` (what the render kernel reads: RenderParams cert_level); leaf_rec / range: the wide tree's
+// side arrays (linearise.hpp)
+inline size_t entry_mm_words(int ntiles) { return 2 * (size_t)ntiles + 1; }
+void launch_camera_entry(hipStream_t stream, const DevUnit* wide, const uint32_t* leaf_rec, const uint32_t* range, int n_leaves, const CertView& cv,
+                         uint32_t* mm, const uint32_t* level, uint32_t* word, int ntiles);
 // hist: the history plane (int32 per pixel at x * H + y; the divisor of pixel p is hist[p] + div, a divisor of 0 gives 0), or null: acc / div
 void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div);
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n);      // acc += frame (pipelined single frames)

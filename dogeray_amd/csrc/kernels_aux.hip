@@ -434,11 +434,41 @@ __global__ __launch_bounds__(1024) void cert_finish_kernel(uint32_t* __restrict_
   }
 }
 
+// The camera rays' entry table of the same view (option camera_entry; the bodies: device_core.hpp entry_leaf, entry_tile).  One
+// thread per leaf of the wide tree, in depth-first order (leaf_rec: rank -> record): its record's box folded into the lowest and the highest rank
+// of every tile it can be seen from (mm: 2 ntiles + 1 words, all ones before).
+__global__ __launch_bounds__(256) void entry_leaf_kernel(const DevUnit* __restrict__ wide, const uint32_t* __restrict__ leaf_rec, int n, CertView cv,
+                                                         uint32_t* __restrict__ mm, int ntiles) {
+  const int rank = blockIdx.x * 256 + threadIdx.x;
+  if (rank >= n) return;
+  const DevUnit* const rec = wide + (size_t)leaf_rec[rank] * WIDE_UNITS;
+  const DevUnit A = rec[0], B = rec[1];
+  entry_leaf(cv, A.f, B.f, (uint32_t)rank, mm, ntiles);
+}
+// one thread per tile: its word for the render kernel, entry code << ENTRY_SHIFT | grade (level: cert_finish_kernel's bytes; mm null: every
+// tile starts at the root)
+__global__ __launch_bounds__(256) void entry_finish_kernel(const DevUnit* __restrict__ wide, const uint32_t* __restrict__ range, const uint32_t* __restrict__ mm,
+                                                           const uint32_t* __restrict__ level, uint32_t* __restrict__ word, int ntiles) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= ntiles) return;
+  const uint32_t grade = (level[t >> 2] >> ((t & 3) * 8)) & 0xffu;
+  const int code = mm ? entry_tile(wide, range, mm[2 * (size_t)t], mm[2 * (size_t)t + 1], mm[2 * (size_t)ntiles] == 0u) : 0;
+  word[t] = ((uint32_t)code << ENTRY_SHIFT) | grade;
+}
+
 void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, uint32_t* level, int ntiles) {
   const int nwords = (ntiles + 31) / 32;
   (void)hipMemsetAsync(mask, 0, cert_mask_words(ntiles, cv.n_levels) * sizeof(uint32_t), stream);
   if (n > 0) hipLaunchKernelGGL(cert_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, prims, n, cv, mask, nwords);
   hipLaunchKernelGGL(cert_finish_kernel, dim3(1), dim3(1024), 0, stream, mask, level, ntiles, nwords, cv.n_levels, cv.base);
+}
+void launch_camera_entry(hipStream_t stream, const DevUnit* wide, const uint32_t* leaf_rec, const uint32_t* range, int n_leaves, const CertView& cv,
+                         uint32_t* mm, const uint32_t* level, uint32_t* word, int ntiles) {
+  if (mm) {
+    (void)hipMemsetAsync(mm, 0xff, entry_mm_words(ntiles) * sizeof(uint32_t), stream);
+    if (n_leaves > 0) hipLaunchKernelGGL(entry_leaf_kernel, dim3((unsigned)((n_leaves + 255) / 256)), dim3(256), 0, stream, wide, leaf_rec, n_leaves, cv, mm, ntiles);
+  }
+  hipLaunchKernelGGL(entry_finish_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, stream, wide, range, mm, level, word, ntiles);
 }
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,
                           int heavy_factor, int split_steps, int split_limit) {

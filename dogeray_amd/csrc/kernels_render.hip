@@ -119,7 +119,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   // the part of the scene that band sees instead of competing for all of it -- and helps the next band
   // once its own is empty.  Region r owns positions [region_start[r], region_start[r+1]) of the order.
   int cur_tile = ntiles, cur_frame = 0;        // chunk being handed out; ntiles = none
-  unsigned cur_cert = 0u;          // lean build: the grade of cur_tile in the view's grazing certificate (its byte of P.cert_level; 0: its camera rays keep the scene's margin; wave-uniform)
+  unsigned cur_cert = 0u;          // lean build: cur_tile's word of P.cert_level (wave-uniform) -- in the low ENTRY_SHIFT bits its grade in the view's grazing certificate (0: its
+                                   // camera rays keep the scene's margin), above them the entry code of its camera rays (0: the root)
   int cur_next = 64;               // next unassigned lane-in-tile of cur_tile (64 = exhausted: fetch first)
   int cur_limit = 64;              // ... and where this wave's share of cur_tile ends (split tiles: a part of the tile)
   bool cur_split = false;
@@ -291,7 +292,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         if (!held && tr.node == -3 && share < 0 && !(cur_tile >= ntiles && regions_left == 0)) { tr.node = -2; want_pixel = true; }
       }
       unsigned long long need = __ballot(want_pixel);
-      unsigned cam_cert = 0u;                      // lean build: the grade of the tile this lane's pixel came from in this phase
+      unsigned cam_cert = 0u;                      // lean build: the word (entry code, grade) of the tile this lane's pixel came from in this phase
       while (need != 0ull) {
         if (cur_next >= cur_limit) {               // wave-uniform: fetch the next chunk (tile, frame)
           if (WIDE && COOP && held) {              // holding: no new tile, the lanes asking become helpers
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
                 tt -= nsplit * (P.split_parts - 1);
               }
               cur_tile = tile_order ? tile_order[r0 + tt] : r0 + tt;
-              if (BOUNCE_HOME) cur_cert = P.cert_level != nullptr ? (P.cert_level[cur_tile >> 2] >> ((cur_tile & 3) * 8)) & 0xffu : 0u;
+              if (BOUNCE_HOME) cur_cert = P.cert_level != nullptr ? P.cert_level[cur_tile] : 0u;
               break;
             }
             region = region + 1 == P.regions ? 0 : region + 1;   // this band is done: help with the next one
@@ -390,13 +391,16 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           bounce = 0;
           if (BOUNCE_HOME) st[9 * 64] = __int_as_float(0);
           trav_begin(tr);
+          // the camera rays of a tile start at the tile's entry record (no word: the root, as trav_begin left it); ENTRY_NONE: nothing of the scene can
+          // be seen from the tile -- the walk is over before it began and the next phase shades a miss
+          if (BOUNCE_HOME) tr.node = (int)cam_cert >> ENTRY_SHIFT;
           rstart = steps;
           fresh_ray = true;
         }
       }
       // lean build: byte 1 of stash word 1 (beside the stack pointer) is the certificate's grade of the lane's ray: its tile's for a camera ray, 0 for
       // any other; written with every new ray, read with the stack pointer at the restore
-      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + 1 * 64)[1] = (unsigned char)(new_path ? cam_cert : 0u);
+      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + 1 * 64)[1] = (unsigned char)(new_path ? cam_cert & ((1u << ENTRY_SHIFT) - 1u) : 0u);
       if (COUNT && ray_log && fresh_ray && frame == 0) {      // measurement aid (dr_context_probe_trace): the rays the launch's first frame traces, in the
         // order a per-bounce wavefront would hold them: bounce by bounce, pixels in tile order.  Statistics words 40-42 = rays logged, the log, its room (entries)
         atomicAdd(&P.counters[40], 1ull);

@@ -182,11 +182,13 @@ int linearise(const HostScene& sc, DeviceImage& img, int wide_tree_mode) {
     }
     WideImage w;
     img.wide.clear(); img.wide_depth = 0; img.wide_nodes = 0;
+    img.wide_leaf_rec.clear(); img.wide_range.clear();
     if (wide_tree_mode >= 0 && build_wide(sc, leaf_node_of_slot, img.prims, wide_tree_mode, 0, w)) {
       img.wide.swap(w.rec);
       img.wide_depth = w.depth;
       img.wide_nodes = w.nodes;
       img.wide_pmax = w.pmax; img.wide_mu = w.mu; img.wide_own_bounds = w.own_bounds;
+      img.wide_leaf_rec.swap(w.leaf_rec); img.wide_range.swap(w.range);
     }
   }
 

@@ -20,6 +20,8 @@ struct DeviceImage {
   float wide_pmax = 0;
   WideMu wide_mu = {0, 0, 0};      // wide_tree = 2: the margin's scene constants (device_layout.h)
   int wide_own_bounds = 0;         // ... and how many triangles entered the tree with their own bounds
+  std::vector<uint32_t> wide_leaf_rec;   // the wide tree's leaf records in depth-first order: rank -> record (WideImage)
+  std::vector<uint32_t> wide_range;      // two words per record: the ranks [first, last] of the leaves under it (a leaf: its own rank twice)
 };
 
 // wide_builder.cpp: the 4-way traversal structure over the reference's leaves (device_layout.h "wide walk")
@@ -29,7 +31,12 @@ struct WideImage {
   float pmax = 0;                  // largest |decoded plane coordinate| over all nodes
   WideMu mu = {0, 0, 0};           // tree_mode 2: constants of the rays' margin (e = 0: every leaf entered with the reference's box)
   int own_bounds = 0;              // ... number of triangles entered with their own bounds
+  // side arrays of the camera rays' entry table (the records themselves stay as they are): a leaf's rank is its place in the
+  // depth-first order of the tree, so the leaves under any record are one run of ranks
+  std::vector<uint32_t> leaf_rec;  // rank -> leaf record
+  std::vector<uint32_t> range;     // record -> [first, last] rank of the leaves under it, two words
 };
+void wide_ranks(const std::vector<DevUnit>& rec, std::vector<uint32_t>& leaf_rec, std::vector<uint32_t>& range);
 // tree_mode 2 (default): binned-SAH tree, small triangles entered with their own bounds (the rays carry a margin); 1: the same over the reference's leaf boxes;
 // 0: the reference's topology collapsed.  false = not representable.
 bool build_wide(const HostScene& sc, const std::vector<int>& leaf_node_of_slot, const std::vector<DevPrim>& prims, int tree_mode,

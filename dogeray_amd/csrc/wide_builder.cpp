@@ -264,6 +264,31 @@ bool quantise(const Box* cb, int n, float origin[3], float scale[3], uint8_t lo[
 
 }  // namespace
 
+// The leaves' ranks in depth-first order of the wide tree (children in record order) and every record's range of them, read off the records
+// themselves (linearise.hpp WideImage): what the camera rays' entry table is built from (device_core.hpp entry_leaf / entry_tile).
+void wide_ranks(const std::vector<DevUnit>& rec, std::vector<uint32_t>& leaf_rec, std::vector<uint32_t>& range) {
+  const size_t n = rec.size() / WIDE_UNITS;
+  leaf_rec.clear();
+  range.assign(2 * n, 0u);
+  if (n == 0) return;
+  struct Item { uint32_t r; int next; };      // node record, next child to descend into
+  std::vector<Item> st;
+  st.push_back({0u, 0});
+  range[0] = 0u;
+  while (!st.empty()) {
+    Item& it = st.back();
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(&rec[(size_t)it.r * WIDE_UNITS]);
+    const uint32_t base = wide_node_first_child(w), valid = wide_node_valid(w), leafmask = wide_node_leaf_mask(w);
+    if (it.next == 0) range[2 * (size_t)it.r] = (uint32_t)leaf_rec.size();
+    while (it.next < 4 && !((valid >> it.next) & 1u)) it.next++;
+    if (it.next >= 4) { range[2 * (size_t)it.r + 1] = (uint32_t)leaf_rec.size() - 1u; st.pop_back(); continue; }
+    const int k = it.next++;
+    const uint32_t ch = base + (uint32_t)k;
+    if ((leafmask >> k) & 1u) { range[2 * (size_t)ch] = range[2 * (size_t)ch + 1] = (uint32_t)leaf_rec.size(); leaf_rec.push_back(ch); }
+    else st.push_back({ch, 0});      // (invalidates `it`: nothing of it is used below)
+  }
+}
+
 bool build_wide(const HostScene& sc, const std::vector<int>& leaf_node_of_slot, const std::vector<DevPrim>& prims, int tree_mode,
                 int nthreads, WideImage& out) {
   out.rec.clear(); out.depth = 0; out.nodes = 0; out.leaves = 0;
@@ -473,7 +498,8 @@ bool build_wide(const HostScene& sc, const std::vector<int>& leaf_node_of_slot, 
   }
   if (n_leaves != N) return false;
   out.depth = depth; out.nodes = n_nodes; out.leaves = n_leaves; out.pmax = pmax;
-  return true;
+  wide_ranks(rec, out.leaf_rec, out.range);
+  return (int)out.leaf_rec.size() == N;
 }
 
 }  // namespace dr

@@ -199,6 +199,10 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   80, 160 at the default factor; every step at least 1) and its camera rays carry the margin of the highest step it passes, the
  *                   scene's margin when it passes none (dr_stats_cert_levels); 0 one step, cert_factor: a tile passes it or keeps the scene's
  *                   margin.  The same bits either way
+ *   "camera_entry"  1 (default): per view, the camera rays of a tile start their walk at the tile's entry record -- the lowest record of the wide tree
+ *                   that holds every leaf a camera ray of the tile can reach (dr_stats_camera_entry) -- instead of the root; a tile
+ *                   that sees nothing of the scene walks nothing.  0 every ray starts at the root.  The same bits either way.  Used where the
+ *                   certificate is (the lean and counting builds, a pixel's first sample), built and dropped with it, for any scene with a wide tree
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
@@ -601,6 +605,11 @@ int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles
  * 3; with cert_levels = 0 the one step is cert_factor, grades 0 and 1).  *n_tiles = 0 when no certificate is in use; otherwise the tiles, and the
  * first min(max, n_tiles) bytes are copied to out_bytes. */
 int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tiles);
+/* The entry codes of the same view's tiles (option camera_entry): one int32 per tile, tile = local block column * tile rows + row.  A code is wide
+ * record << 1 | is-leaf: the record at which the tile's camera rays start their walk; 0 the root (every tile with camera_entry = 0), -1 no leaf of the
+ * scene can be seen from the tile.  *n_tiles = 0 when no table is in use; otherwise the tiles, and the first min(max, n_tiles) codes are
+ * copied to out. */
+int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles);
 
 /* Timeline of the last SHORT persistent-kernel launch (fewer than coop_tiles_per_wave tiles per wave: one frame, a thin stripe;
  * option "wave_log" = 1 before the launch): sixteen words per wave --

@@ -44,7 +44,9 @@ thread_local std::string hk_err;
 // plane / ktab (null: none): the grades of the view's grazing certificate, a byte per tile, and the margin's factor per grade -- the camera ray of
 // every path of a tile carries its tile's factor, as the lean build's do (kernels_render.hip; there for a pixel's first sample)
 template <bool COUNT>
-void render_columns(const RenderParams& P, int traversal, int first, int step, Ctr& total, const uint8_t* plane = nullptr, const float* ktab = nullptr) {
+// eplane (null: none): the entry codes of the view's camera rays, a word per tile (hk_camera_entry) -- the camera ray of every path starts its walk there
+void render_columns(const RenderParams& P, int traversal, int first, int step, Ctr& total, const uint8_t* plane = nullptr, const float* ktab = nullptr,
+                    const int32_t* eplane = nullptr) {
   std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
   Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
   const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
@@ -56,12 +58,14 @@ void render_columns(const RenderParams& P, int traversal, int first, int step, C
         if (traversal == DR_TRAVERSAL_WIDE && P.wide) {
           bool camera = false;
           const float kt = plane ? ktab[plane[(size_t)col * (size_t)P.gy + (size_t)by] & CERT_MAX_LEVELS] : 1.0f;
+          const int entry = eplane ? eplane[(size_t)col * (size_t)P.gy + (size_t)by] : 0;
           auto closest = [&](V3 o, V3 d, Ctr& cc) {
             const float k = camera ? kt : 1.0f;
+            const int e = camera ? entry : 0;
             camera = false;
-            return closest_hit_wide<COUNT>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, o, d, cc, stack.data(), k);
+            return closest_hit_wide<COUNT>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, o, d, cc, stack.data(), k, e);
           };
-          render_pixel<COUNT>(P, closest, x, y, c, plane ? &camera : nullptr);
+          render_pixel<COUNT>(P, closest, x, y, c, plane || eplane ? &camera : nullptr);
         } else if (traversal == DR_TRAVERSAL_ORDERED) {
           auto closest = [&](V3 o, V3 d, Ctr& cc) { return closest_hit_ordered<COUNT>(P.pairs, P.prims, o, d, cc, stack.data()); };
           render_pixel<COUNT>(P, closest, x, y, c);
@@ -371,6 +375,133 @@ int hk_cert_levels(void* hv, const float* settings13, int W, int H, int cert_fac
   }
   return 0;
 }
+// The camera rays' entry table of one view (option camera_entry) over the product's default tree, as kernels_aux.hip builds it -- the same
+// entry_leaf over the leaves in depth-first order, the same entry_tile per tile -- for the block columns bx % col_mod == col_rem.  codes_out (may be NULL):
+// the entry codes, a word per tile (local column * tile rows + row).  mutant: 0, or one of device_core.hpp's ENTRY_MUTANTs (a wrong rule on purpose).
+// out[0] tiles, out[1] tiles without a leaf (ENTRY_NONE), out[2] tiles at the root, out[3] tiles at a leaf record, out[4] "every tile at the root",
+// out[5] leaves, out[8 + d] tiles whose entry lies d records below the root (d = 0 .. 17; ENTRY_NONE not counted).  Returns 0, -1 with hk_last_error,
+// or 1 when the view gives no table (fill_cert_view: a degenerate camera, a lens too wide for the focus plane) or the scene has no wide tree.
+int hk_camera_entry(void* hv, const float* settings13, int W, int H, int col_mod, int col_rem, int mutant, int32_t* codes_out, long long* out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || !out || col_mod < 1 || col_rem < 0 || col_rem >= col_mod) { hk_err = "bad argument"; return -1; }
+  if (!h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = h->own;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, 1, col_mod, col_rem, P)) { hk_err = why; return -1; }
+  CertView cv;
+  // (the table asks nothing of the certificate's a_star or of the scene's own-bounds E: any valid pair)
+  if (img.wide.empty() || !fill_cert_view(P, 40e-4, img.wide_mu.e > 0.0f ? img.wide_mu.e : 1.0f, cv)) return 1;
+  const int tiles = P.ncols * P.gy;
+  std::vector<uint32_t> mm(2 * (size_t)tiles + 1, 0xffffffffu);
+  entry_mutant = mutant;
+  for (size_t rank = 0; rank < img.wide_leaf_rec.size(); rank++) {
+    const DevUnit* rec = &img.wide[(size_t)img.wide_leaf_rec[rank] * WIDE_UNITS];
+    entry_leaf(cv, rec[0].f, rec[1].f, (uint32_t)rank, mm.data(), tiles);
+  }
+  for (int k = 0; k < 32; k++) out[k] = 0;
+  out[0] = tiles; out[4] = mm[2 * (size_t)tiles] == 0u; out[5] = (long long)img.wide_leaf_rec.size();
+  for (int t = 0; t < tiles; t++) {
+    const int code = entry_tile(img.wide.data(), img.wide_range.data(), mm[2 * (size_t)t], mm[2 * (size_t)t + 1], mm[2 * (size_t)tiles] == 0u);
+    if (codes_out) codes_out[t] = code;
+    if (code == ENTRY_NONE) { out[1]++; continue; }
+    if (code == 0) out[2]++;
+    if (code & 1) out[3]++;
+    // its depth: down from the root along the records whose ranges hold the entry's
+    const uint32_t lo = img.wide_range[2 * (size_t)(code >> 1)], hi = img.wide_range[2 * (size_t)(code >> 1) + 1];
+    uint32_t cur = 0u;
+    int d = 0;
+    while (cur != (uint32_t)(code >> 1) && d < 17) {
+      const uint32_t* w = reinterpret_cast<const uint32_t*>(&img.wide[(size_t)cur * WIDE_UNITS]);
+      uint32_t next = cur;
+      for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t ch = wide_node_first_child(w) + k;
+        if (((wide_node_valid(w) >> k) & 1u) && img.wide_range[2 * (size_t)ch] <= lo && hi <= img.wide_range[2 * (size_t)ch + 1]) next = ch;
+      }
+      if (next == cur) break;
+      cur = next; d++;
+    }
+    out[8 + d]++;
+  }
+  entry_mutant = 0;
+  return 0;
+}
+// What the table promises, by brute force: for every pixel of the stripe and `frames` frames (seeds seed + stride f) the kernel's own camera rays (camera_ray
+// with the real sample seeds, settings13's samples per pixel) against EVERY leaf of the default tree -- a leaf whose record's box the ray enters (slab(), the
+// reference's test) must lie under the entry of the ray's tile (codes: hk_camera_entry's).  out[0] rays, out[1] (ray, leaf) pairs entered, out[2] of them
+// not under the tile's entry (must be 0), out[3] pairs entered in tiles whose entry is below the root.  Returns 0, or -1.
+int hk_camera_entry_check(void* hv, const float* settings13, int W, int H, int col_mod, int col_rem, uint64_t seed, uint64_t stride, int frames, int nthreads,
+                          const int32_t* codes, long long* out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || !codes || !out || !h->has_own || h->own.wide.empty() || frames < 1) { hk_err = "bad argument (hk_camera_entry first)"; return -1; }
+  const DeviceImage& img = h->own;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, seed, col_mod, col_rem, P)) { hk_err = why; return -1; }
+  if (nthreads < 1) nthreads = 1;
+  std::vector<long long> part((size_t)nthreads * 4, 0);
+  const size_t nleaves = img.wide_leaf_rec.size();
+  host_rows(nthreads, P.ncols, [&](int col) {
+    long long* acc = &part[(size_t)(col % nthreads) * 4];
+    const int bx = P.stripe_rem + col * P.stripe_mod;
+    for (int by = 0; by < P.gy; by++) {
+      const int code = codes[(size_t)col * (size_t)P.gy + (size_t)by];
+      const uint32_t lo = code == ENTRY_NONE ? 1u : img.wide_range[2 * (size_t)(code >> 1)], hi = code == ENTRY_NONE ? 0u : img.wide_range[2 * (size_t)(code >> 1) + 1];
+      for (int lane = 0; lane < 64; lane++) {
+        const int x = bx * 8 + (lane >> 3), y = by * 8 + (lane & 7);
+        for (int f = 0; f < frames; f++)
+          for (int s = 0; (float)s < P.spp_f; s++) {
+            RenderParams Q = P;
+            Q.seed = seed + stride * (uint64_t)f;
+            Xorwow rng;
+            rng.init(sample_seed(Q, x, y, s));
+            V3 o, d;
+            camera_ray(Q, x, y, rng, o, d);
+            const V3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+            acc[0]++;
+            for (size_t rank = 0; rank < nleaves; rank++) {
+              const DevUnit* rec = &img.wide[(size_t)img.wide_leaf_rec[rank] * WIDE_UNITS];
+              float dist = 0;
+              if (!slab(o, inv, rec[0].f, rec[1].f, dist)) continue;
+              acc[1]++;
+              if (!(lo <= rank && rank <= hi)) acc[2]++;
+              if (code != 0) acc[3]++;
+            }
+          }
+      }
+    }
+  });
+  for (int k = 0; k < 4; k++) { out[k] = 0; for (int t = 0; t < nthreads; t++) out[k] += part[(size_t)t * 4 + k]; }
+  return 0;
+}
+// slab() (device_core.hpp: the reference's box test, what hk_camera_entry_check lists leaves with) on n ray / box pairs: 1 entered, 0 not
+void hk_slab(long long n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit) {
+  for (long long i = 0; i < n; i++) {
+    const V3 dd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    float dist = 0;
+    hit[i] = slab(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z), mn + 3 * i, mx + 3 * i, dist) ? 1 : 0;
+  }
+}
+// the default tree's side arrays and leaf boxes, for the tests: leaves, then per rank the record and its box (mn, mx: 6 floats); range2 (may be NULL): two words per record
+long long hk_wide_leaves(void* hv, uint32_t* leaf_rec, float* boxes, uint32_t* range2, long long room_leaves, long long room_records) {
+  HkScene* h = (HkScene*)hv;
+  if (!h) { hk_err = "bad argument"; return -1; }
+  if (!h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = h->own;
+  const long long n = (long long)img.wide_leaf_rec.size(), nrec = (long long)(img.wide.size() / WIDE_UNITS);
+  for (long long r = 0; r < n && r < room_leaves; r++) {
+    if (leaf_rec) leaf_rec[r] = img.wide_leaf_rec[(size_t)r];
+    if (boxes) { const DevUnit* rec = &img.wide[(size_t)img.wide_leaf_rec[(size_t)r] * WIDE_UNITS]; memcpy(boxes + 6 * r, rec[0].f, 12); memcpy(boxes + 6 * r + 3, rec[1].f, 12); }
+  }
+  if (range2) memcpy(range2, img.wide_range.data(), (size_t)(nrec < room_records ? nrec : room_records) * 8);
+  return n;
+}
 // the same with the certificate's factor (wide_ray_margin's last argument: 1e-4 / a_star for a certified camera ray, 1 otherwise)
 void hk_ray_margin_k(long long n, const float* o, const float* d, float e, float l, float v, float k, float* out) {
   for (long long i = 0; i < n; i++) out[i] = wide_ray_margin(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), e, l, v, k);
@@ -497,19 +628,26 @@ int hk_wide_depth(void* hv) { return ((HkScene*)hv)->img.wide.empty() ? 0 : ((Hk
 // columns bx % col_mod == col_rem are rendered (a bounded sample for the bench).  counters: rays, V, L, S, T, samples (6 words).
 // level_plane (may be NULL): the grades of the view's graded certificate (hk_cert_levels' plane_out for cert_factor / graded, whole frame: col_mod 1) --
 // the frame is then rendered as the device renders it: the wide walk over the product's default tree (wide_tree = 2), the camera rays with their
-// tile's margin.
+// tile's margin.  entry_plane (may be NULL): the entry codes of the view's camera rays for this very stripe (hk_camera_entry's codes_out): the camera rays
+// start there, over the default tree as well.
 int hk_render(void* hv, const float* settings13, int W, int H, float background, uint64_t frame_seed, int traversal, int nthreads, int col_mod, int col_rem,
-              int32_t* out, uint64_t* counters, const uint8_t* level_plane, int cert_factor, int graded) {
+              int32_t* out, uint64_t* counters, const uint8_t* level_plane, int cert_factor, int graded, const int32_t* entry_plane) {
   HkScene* h = (HkScene*)hv;
   if (!h || !settings13 || !out || col_mod < 1 || col_rem < 0 || col_rem >= col_mod) { hk_err = "bad argument"; return -1; }
   float ktab[CERT_MAX_LEVELS + 1];
   for (float& k : ktab) k = 1.0f;
   if (level_plane) {
     if (col_mod != 1 || cert_factor < 1 || traversal != DR_TRAVERSAL_WIDE) { hk_err = "a level plane needs the whole frame, its cert_factor and the wide walk"; return -1; }
+  }
+  const bool own = level_plane || entry_plane;
+  if (own) {
+    if (traversal != DR_TRAVERSAL_WIDE) { hk_err = "an entry plane needs the wide walk"; return -1; }
     if (!h->has_own) {
       if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
       h->has_own = true;
     }
+  }
+  if (level_plane) {
     CertView cv;
     cert_ladder(cert_factor, graded != 0, cv);
     for (int g = 1; g <= cv.n_levels; g++) ktab[g] = cert_factor_k(cv.level_a[g - 1]);
@@ -517,9 +655,9 @@ int hk_render(void* hv, const float* settings13, int W, int H, float background,
   RenderParams P;
   memset(&P, 0, sizeof(P));
   if (const char* why = fill_view_params(settings13, W, H, background, frame_seed, col_mod, col_rem, P)) { hk_err = why; return -1; }
-  const DeviceImage& img = level_plane ? h->own : h->img;
+  const DeviceImage& img = own ? h->own : h->img;
   if (P.backtex >= (int)img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
-  if (level_plane && img.wide.empty()) { hk_err = "the scene has no wide tree"; return -1; }
+  if (own && img.wide.empty()) { hk_err = "the scene has no wide tree"; return -1; }
   P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
   P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
   P.pairs = img.pairs.data(); P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
@@ -531,8 +669,8 @@ int hk_render(void* hv, const float* settings13, int W, int H, float background,
   std::vector<std::thread> th;
   for (int t = 0; t < nthreads; t++)
     th.emplace_back([&, t] {
-      if (counters) render_columns<true>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab);
-      else render_columns<false>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab);
+      if (counters) render_columns<true>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab, entry_plane);
+      else render_columns<false>(P, traversal, t, nthreads, part[(size_t)t], level_plane, ktab, entry_plane);
     });
   for (std::thread& t : th) t.join();
   if (counters) {

@@ -59,7 +59,15 @@ def lib():
         L.hk_check_reject.restype = C.c_longlong
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
         L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_int, C.c_int]
+                                C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.hk_camera_entry.restype = C.c_int
+        L.hk_camera_entry.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hk_camera_entry_check.restype = C.c_int
+        L.hk_camera_entry_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hk_slab.restype = None
+        L.hk_slab.argtypes = [C.c_longlong] + [C.c_void_p] * 5
+        L.hk_wide_leaves.restype = C.c_longlong
+        L.hk_wide_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong]
         L.hk_cert_levels.restype = C.c_int
         L.hk_cert_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_longlong, C.c_uint64, C.c_void_p, C.c_void_p]
         L.hk_aov.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 9
@@ -79,6 +87,14 @@ def lib():
         L.hk_plan_split_limit.argtypes = [C.c_int] * 4
         _lib = L
     return _lib
+
+
+def slab(o, d, mn, mx):
+    """device_core.hpp slab() on n ray / box pairs (hk_slab): int32[n], 1 where the ray enters the box"""
+    o, d, mn, mx = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, mn, mx))
+    hit = np.zeros(o.shape[0], np.int32)
+    lib().hk_slab(o.shape[0], o.ctypes.data, d.ctypes.data, mn.ctypes.data, mx.ctypes.data, hit.ctypes.data)
+    return hit
 
 
 class Scene:
@@ -123,19 +139,63 @@ class Scene:
         return {"wide_depth": int(out[0]), "wide_own_bounds": int(out[1]), "wide_nodes": int(out[2])}
 
     def render(self, settings13, W, H, background, frame_seed, traversal=2, nthreads=1, col_mod=1, col_rem=0, count=True, level_plane=None, cert_factor=40,
-               graded=1):
+               graded=1, entry_plane=None):
         """One frame: (int32[W, H, 3] indexed [x, y], counters dict or None).  level_plane: the grades of the view's grazing certificate
-        (cert_levels()[0] for the same cert_factor / graded) -- the frame is rendered over the default tree with the camera rays' certified margins."""
+        (cert_levels()[0] for the same cert_factor / graded) -- the frame is rendered over the default tree with the camera rays' certified margins.
+        entry_plane: the entry codes of the view's camera rays (camera_entry()[0] for the same stripe): they start their walks there."""
         st = np.ascontiguousarray(settings13, dtype=np.float32)
         out = np.zeros((W, H, 3), dtype=np.int32)
         ctr = (C.c_uint64 * 6)()
         plane = np.ascontiguousarray(level_plane, dtype=np.uint8) if level_plane is not None else None
+        eplane = np.ascontiguousarray(entry_plane, dtype=np.int32) if entry_plane is not None else None
         rc = lib().hk_render(self.h, st.ctypes.data, W, H, float(background), int(frame_seed) & (2 ** 64 - 1), traversal, nthreads, col_mod, col_rem,
                              out.ctypes.data, C.cast(ctr, C.c_void_p) if count else None,
-                             plane.ctypes.data if plane is not None else None, int(cert_factor), int(graded))
+                             plane.ctypes.data if plane is not None else None, int(cert_factor), int(graded),
+                             eplane.ctypes.data if eplane is not None else None)
         if rc != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return out, (dict(zip(("rays", "V", "L", "S", "T", "samples"), [int(v) for v in ctr])) if count else None)
+
+    def camera_entry(self, settings13, W, H, col_mod=1, col_rem=0, mutant=0):
+        """The camera rays' entry table of a view on the host (hk_camera_entry): (int32 entry codes, a word per tile of the stripe, and a dict of counts),
+        or None when the view or the scene gives no table.  mutant: one of device_core.hpp's wrong rules (1 rect narrowed, 2 no lens term, 3 highest
+        rank off by one, 4 no entry for a tile with one leaf)."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        div = int(st[11]) if np.isfinite(st[11]) and st[11] >= 1 else 1
+        gx, gy = W // div // 8, H // div // 8
+        ncols = (gx - col_rem + col_mod - 1) // col_mod if gx > col_rem else 0
+        codes = np.zeros(max(1, ncols * gy), np.int32)
+        out = np.zeros(32, np.int64)
+        rc = lib().hk_camera_entry(self.h, st.ctypes.data, W, H, int(col_mod), int(col_rem), int(mutant), codes.ctypes.data, out.ctypes.data)
+        if rc < 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        if rc != 0:
+            return None
+        assert int(out[0]) == ncols * gy
+        return codes[:ncols * gy], {"tiles": int(out[0]), "none": int(out[1]), "root": int(out[2]), "leaf": int(out[3]), "every": int(out[4]), "leaves": int(out[5]),
+                                    "depth": [int(v) for v in out[8:26]]}
+
+    def camera_entry_check(self, settings13, W, H, codes, seed, stride, frames, col_mod=1, col_rem=0, nthreads=8):
+        """hk_camera_entry_check: the kernel's camera rays of `frames` frames against every leaf, by brute force -> dict rays, entered, outside (leaves
+        entered that do not lie under their tile's entry: must be 0), entered_below_root."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        out = np.zeros(4, np.int64)
+        if lib().hk_camera_entry_check(self.h, st.ctypes.data, W, H, int(col_mod), int(col_rem), int(seed), int(stride), int(frames), int(nthreads),
+                                       codes.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return {"rays": int(out[0]), "entered": int(out[1]), "outside": int(out[2]), "entered_below_root": int(out[3])}
+
+    def wide_leaves(self):
+        """The default tree's leaves in depth-first order: (uint32 record per rank, float32 (n, 6) box per rank -- mn, mx of the record --, uint32 (records, 2)
+        rank range per record)."""
+        n = int(lib().hk_wide_leaves(self.h, None, None, None, 0, 0))
+        if n < 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        nrec = self.wide_info(2)["wide_nodes"] + n
+        rec, boxes, rng = np.zeros(n, np.uint32), np.zeros((n, 6), np.float32), np.zeros((nrec, 2), np.uint32)
+        lib().hk_wide_leaves(self.h, rec.ctypes.data, boxes.ctypes.data, rng.ctypes.data, n, nrec)
+        return rec, boxes, rng
 
     def wide_mu(self):
         """(own-bounds triangles, float32 (e, l, v)) of the product's default tree (hk_wide_mu)."""
