@@ -275,21 +275,21 @@ int dr_stats_get(dr_context* c, dr_stats* out) {
   if (!c || !out) { set_error("null argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  unsigned long long h[16];
+  unsigned long long h[STAT_PHASE];
   HIP_TRY(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
   *out = c->stats;
-  out->rays = h[0]; out->node_visits = h[1]; out->prim_tests = h[2]; out->shades = h[3]; out->texels = h[4];
-  if (c->count) out->samples = h[5];
-  out->trav_slots = h[6]; out->ray_slots = h[7];
-  for (int k = 0; k < 8; k++) out->diag[k] = h[8 + k];
+  out->rays = h[STAT_RAYS]; out->node_visits = h[STAT_NODE_VISITS]; out->prim_tests = h[STAT_PRIM_TESTS]; out->shades = h[STAT_SHADES]; out->texels = h[STAT_TEXELS];
+  if (c->count) out->samples = h[STAT_SAMPLES];
+  out->trav_slots = h[STAT_TRAV_SLOTS]; out->ray_slots = h[STAT_RAY_SLOTS];
+  for (int k = 0; k < 8; k++) out->diag[k] = h[STAT_DIAG + k];
   return DR_OK;
 }
 
 int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n) {
-  if (!c || !out || n < 0 || n > COUNTER_WORDS - 16) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c || !out || n < 0 || n > COUNTER_WORDS - STAT_PHASE) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (n > 0) HIP_TRY(hipMemcpy(out, c->counters + 16, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (n > 0) HIP_TRY(hipMemcpy(out, c->counters + STAT_PHASE, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return DR_OK;
 }
 

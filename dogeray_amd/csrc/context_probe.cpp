@@ -71,13 +71,13 @@ int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int
   DR_TRY(raw.alloc(slots * 8));
   HIP_TRY(hipMemset(raw.p, 0, slots * 8 * sizeof(float)));
   const bool was_counting = c->count;
-  unsigned long long ctl[3] = {0ull, (unsigned long long)(uintptr_t)raw.p, (unsigned long long)slots};      // statistics words 40-42: rays logged, the log, its room
-  HIP_TRY(hipMemcpy(c->counters + 40, ctl, sizeof(ctl), hipMemcpyHostToDevice));
+  unsigned long long ctl[3] = {0ull, (unsigned long long)(uintptr_t)raw.p, (unsigned long long)slots};      // STAT_LOG_RAYS, STAT_LOG_PTR, STAT_LOG_ROOM
+  HIP_TRY(hipMemcpy(c->counters + STAT_LOG_RAYS, ctl, sizeof(ctl), hipMemcpyHostToDevice));
   c->count = true;
   const int rc = dr_render_accumulate(c, settings13, W, H, background, frame_seed, 1000003, 1);
   c->count = was_counting;
   const unsigned long long off[2] = {0ull, 0ull};
-  HIP_TRY(hipMemcpy(c->counters + 41, off, sizeof(off), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->counters + STAT_LOG_PTR, off, sizeof(off), hipMemcpyHostToDevice));
   if (rc != DR_OK) return rc;
   std::vector<float> host(slots * 8), packed;
   DR_TRY(raw.get(host.data(), host.size()));

@@ -37,7 +37,7 @@ constexpr int WALK_KIND_SPHERE = 0, WALK_KIND_TRIANGLE = 1, WALK_KIND_NONE = 2; 
 // Wide walk (wide_builder.cpp): 64-byte records, a 4-way tree over the same leaves.
 //   node  {origin.xyz, index of first child | valid mask << 24 | leaf mask << 28} {lo.x, lo.y, lo.z, hi.x} {hi.y, hi.z, scale.x | scale.y << 16, scale.z} {-}
 //         each lo/hi word = one byte per child: plane = fmaf(byte, scale, origin); scale is a power of two in [2^-60, 2^36] and is stored times 2^24
-//         (the kernel reads a plane byte as the f16 denormal byte * 2^-24, device_core.hpp wide_node_test): x and y as the upper halves of their floats
+//         (the kernel reads a plane byte as the f16 denormal byte * 2^-24, device_wide.hpp wide_node_test): x and y as the upper halves of their floats
 //         (a power of two has no other bits), z as the float.  A node is its first THREE units: the kernel does not fetch the fourth (a node step costs
 //         three 16-byte loads per lane instead of four; every load instruction of a step is ~1 % of the frame, profiles/r4_o_node_three_units.txt)
 //   leaf  {min.xyz, slot | kind << 26} {max.xyz, v0.x} {v0.yz, e1.xy} {e1.z, e2.xyz}      (the walk array's leaf record)
@@ -51,13 +51,13 @@ inline uint32_t wide_node_lo(const uint32_t* w, int axis) { return w[4 + axis]; 
 inline uint32_t wide_node_hi(const uint32_t* w, int axis) { return w[7 + axis]; }
 inline uint32_t wide_node_scale24_bits(const uint32_t* w, int axis) { return axis == 0 ? w[10] << 16 : (axis == 1 ? w[10] & 0xffff0000u : w[11]); }      // bits of scale * 2^24
 // wide_tree = 2 (default): small triangles enter the tree with their OWN bounds instead of the reference's leaf box (their bounds padded by 0.01), and every ray
-// carries the position margin that makes up for it (device_core.hpp wide_ray; DESIGN.md 4.10 has the proof).  e = 0: every leaf entered with the reference's box.
+// carries the position margin that makes up for it (device_wide.hpp wide_ray; DESIGN.md 4.10 has the proof).  e = 0: every leaf entered with the reference's box.
 struct WideMu {
   float e;      // largest |e1| |e2| of the triangles that entered with their own bounds (Euclidean norms)
   float l;      // largest |e1| + |e2| of them
   float v;      // largest |v0| of them
 };
-// Per-view grazing certificate of the camera rays (option camera_cert; device_core.hpp cert_leaf).  Every camera ray starts within r_o of
+// Per-view grazing certificate of the camera rays (option camera_cert; device_cert.hpp cert_leaf).  Every camera ray starts within r_o of
 // `from`; a small triangle that such a ray can be ACCEPTED on has its padded box on the ray, and the view gives a lower bound A_T of |d . (e1 x e2)| over
 // every such ray.  Triangles with A_T >= a_star certify nothing more is needed; the others set the bits of the tiles whose rays can reach their box.  A ray
 // of an unflagged tile therefore has |a^| >= a_star for every triangle it can be accepted on and carries the margin scaled by 1e-4 / a_star.
@@ -86,7 +86,7 @@ struct CertView {
 };
 
 constexpr int CERT_MAX_LEVELS = 7;                    // steps of the certificate's ladder at most (CertView level_a, RenderParams wide_cert_k)
-constexpr int ENTRY_NONE = -1;                        // a tile's entry code when no leaf can be seen from it (device_core.hpp entry_tile): its camera rays walk nothing
+constexpr int ENTRY_NONE = -1;                        // a tile's entry code when no leaf can be seen from it (device_cert.hpp entry_tile): its camera rays walk nothing
 constexpr int ENTRY_SHIFT = 3;                        // a tile's word: entry code << ENTRY_SHIFT | the certificate's grade (RenderParams cert_level; grades <= CERT_MAX_LEVELS)
 constexpr int WIDE_UNITS = 4;
 constexpr int WIDE_INDEX_BITS = 24;                   // records < 2^24 (1 GiB of them)
@@ -158,7 +158,7 @@ struct RenderParams {
   const DevTex* tex;
   const uint32_t* texels;
   int32_t* out;                   // int32[W*H*3], pixel (x, y) at (x*H + y)*3
-  unsigned long long* counters;   // 8 words or null: rays, V, L, S, T, samples, trav_slots, ray_slots
+  unsigned long long* counters;   // the statistics buffer, COUNTER_WORDS words (kernels.hpp StatWord): the first eight are rays, V, L, S, T, samples, trav_slots, ray_slots
   unsigned long long* wave_log;   // null, or 16 words per wave of the persistent kernel: begin, queue empty, end (100 MHz ticks), loop iterations after the queue ran empty
   float from[3], llc[3], hor[3], ver[3], uu[3], vu[3];
   float lens_radius;

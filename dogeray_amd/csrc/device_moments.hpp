@@ -8,11 +8,7 @@
 // sqrt, floor and comparisons in the order written here (-ffp-contract=off): include/dogeray_amd.h has the definition this file implements,
 // operation by operation.
 #pragma once
-#ifdef DR_HOST_BUILD
-#include "host_stubs.hpp"
-#else
-#include <hip/hip_runtime.h>
-#endif
+#include "device_prims.hpp"      // the device or the host build's runtime (the one switch between them)
 #include <stdint.h>
 
 #include "device_launch.h"

@@ -8,11 +8,7 @@
 // floor and comparisons, in the order written here (-ffp-contract=off): include/dogeray_amd.h has the definition this file implements,
 // operation by operation.
 #pragma once
-#ifdef DR_HOST_BUILD
-#include "host_stubs.hpp"
-#else
-#include <hip/hip_runtime.h>
-#endif
+#include "device_prims.hpp"      // the device or the host build's runtime (the one switch between them)
 #include <stdint.h>
 
 #include "device_launch.h"
@@ -27,7 +23,7 @@ __device__ __forceinline__ double rp_dot(const D3& a, const D3& b) { return (a.x
 __device__ __forceinline__ D3 rp_d3(const double* p) { D3 r; r.x = p[0]; r.y = p[1]; r.z = p[2]; return r; }
 __device__ __forceinline__ D3 rp_f3(const float* p) { D3 r; r.x = (double)p[0]; r.y = (double)p[1]; r.z = (double)p[2]; return r; }
 
-// The pinhole direction of pixel (x, y) as aov_first_hit (device_core.hpp) forms it, in float: nu = (float)((x + 0.5) / den_w), nv likewise,
+// The pinhole direction of pixel (x, y) as aov_first_hit (device_aov.hpp) forms it, in float: nu = (float)((x + 0.5) / den_w), nv likewise,
 // d = ((llc + nu * hor) + nv * ver) - from per component; widened to double
 __device__ __forceinline__ D3 rp_dir(const RpCamera& C, int x, int y) {
   const float nu = (float)(((double)x + 0.5) / C.den_w), nv = (float)(((double)y + 0.5) / C.den_h);

@@ -25,14 +25,28 @@ void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal
 int launch_persistent_kernel(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
                              const int* region_start, unsigned* pixel_cost);
 
-constexpr int COUNTER_WORDS = 48;   // 64-bit words of a context's statistics buffer: [0, 8) ray counters, [8, 16) dr_stats.diag, [16, 48) the shade / refill phase's budget (dr_stats_phase_counts)
+// The 64-bit words of a context's statistics buffer (RenderParams counters).  The render kernels write them, context.cpp reads them
+// (dr_stats_get: words [0, STAT_PHASE); dr_stats_phase_counts: the words from STAT_PHASE on), context_probe.cpp sets the ray log's.
+enum StatWord {
+  STAT_RAYS = 0, STAT_NODE_VISITS, STAT_PRIM_TESTS, STAT_SHADES, STAT_TEXELS, STAT_SAMPLES, STAT_TRAV_SLOTS, STAT_RAY_SLOTS,      // the ray counters, in the order of Ctr
+  STAT_DIAG = 8,               // dr_stats.diag[0 .. 8): the persistent kernel's, summed over its waves
+  STAT_WAVE_CYCLES = STAT_DIAG, STAT_PHASE_CYCLES, STAT_ITERATIONS, STAT_PHASES, STAT_NODE_STEPS, STAT_LEAF_STEPS, STAT_SHADED,
+  STAT_WAVE_TICKS,             // wave lifetime in 100 MHz ticks (every build, as STAT_WAVE_CYCLES; the six between them: counting build)
+  STAT_PHASE = 16,             // the shade / refill phase's budget (counting build):
+  STAT_TURN_HIST = STAT_PHASE, // histogram of the rejection loop's turns per phase, STAT_TURN_BINS bins (the last: that many or more)
+  STAT_PB_CANDS = 32, STAT_PB_TURNS, STAT_PB_SPHERE, STAT_PB_DISK, STAT_PB_RETIRED,      // candidates drawn, turns run, sphere / disk lanes, retired lanes over phases
+  STAT_LOG_RAYS = 40, STAT_LOG_PTR, STAT_LOG_ROOM      // measurement aid (dr_context_probe_trace): rays logged, the log's address, its room in entries
+};
+constexpr int STAT_TURN_BINS = 16;
+constexpr int COUNTER_WORDS = 48;
+static_assert(STAT_TURN_HIST + STAT_TURN_BINS <= STAT_PB_CANDS && STAT_LOG_ROOM < COUNTER_WORDS, "statistics words");
 
 // kernels_aux.hip
 void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsigned* tile_cost, int* tile_order, int* region_start, int tiles, int regions,
                           int heavy_factor, int split_steps, int split_limit);
 // the camera rays' grazing certificate of a view: mask = (ntiles + 31) / 32 words of tile bits (set: the tile's camera rays keep the scene's margin),
 // then the "every tile" word, the number of flagged tiles and cv.n_levels scratch planes (cert_mask_words in all); level = a byte per tile, the tile's
-// grade on cv's ladder, cert_level_words words (device_core.hpp cert_leaf)
+// grade on cv's ladder, cert_level_words words (device_cert.hpp cert_leaf)
 inline size_t cert_mask_words(int ntiles, int n_levels) { return (size_t)((ntiles + 31) / 32) * (size_t)(1 + n_levels) + 2; }
 inline size_t cert_level_words(int ntiles) { return (size_t)((ntiles + 31) / 32) * 8; }
 void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const CertView& cv, uint32_t* mask, uint32_t* level, int ntiles);

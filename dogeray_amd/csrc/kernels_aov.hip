@@ -1,10 +1,11 @@
 // First-hit AOV buffers (dr_render_aov): one wave per 8x8 tile of the requested window, one pinhole ray per lane through the pixel centre,
-// its closest hit and what shade_prepare forms there (device_core.hpp aov_first_hit).  Camera rays of one tile are coherent, so the
+// its closest hit and what shade_prepare forms there (device_aov.hpp aov_first_hit).  Camera rays of one tile are coherent, so the
 // wave walks the tree nearly in lockstep; there is no path, no random draw and no counter.  The traversal stacks live in LDS with the layout
 // of kat_hit_kernel (word k of lane l at stack[k * 64 + l]).
 #include <hip/hip_runtime.h>
 
-#include "device_core.hpp"
+#include "device_wide.hpp"
+#include "device_aov.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 

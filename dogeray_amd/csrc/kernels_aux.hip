@@ -2,7 +2,10 @@
 // the stripe copies of the multi-GPU gather, the gather-ceiling probe and the known-answer kernels behind dr_kat_*.
 #include <hip/hip_runtime.h>
 
-#include "device_core.hpp"
+#include "device_rng.hpp"
+#include "device_wide.hpp"
+#include "device_cert.hpp"
+#include "device_surface.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -210,7 +213,7 @@ __global__ __launch_bounds__(256, OCC) void trace_probe_kernel(RenderParams P, c
   const int lane = threadIdx.x & 63;
   int* const my_stack = lds + (threadIdx.x >> 6) * (WIDE_STACK * 64) + lane;
   const WalkRsrc walk = wide_rsrc(P);
-  Trav tr; tr.node = -2; tr.best_t = 0; tr.best_slot = -1;      // -2: wants a ray; -1: done, result not written yet; -3: retired
+  Trav tr; tr.node = LANE_REFILL; tr.best_t = 0; tr.best_slot = -1;      // LANE_REFILL: wants a ray; LANE_DONE: result not written yet (device_walk.hpp)
   WideStack ws; ws.top = 0u; ws.sp = 0; ws.sb = 0;
   V3 o = mk(0, 0, 0), d = mk(0, 0, 0), inv = mk(0, 0, 0);
   WideRay wr = wide_ray_none();
@@ -220,11 +223,11 @@ __global__ __launch_bounds__(256, OCC) void trace_probe_kernel(RenderParams P, c
   unsigned chunk_next = 0, chunk_end = 0;      // this wave's share of the ray list (wave-uniform)
   bool exhausted = false;
   for (;;) {
-    const unsigned long long want = __ballot(tr.node == -1 || tr.node == -2);
+    const unsigned long long want = __ballot(tr.node == LANE_DONE || tr.node == LANE_REFILL);
     const unsigned long long walking = __ballot(tr.node >= 0);
     if (want != 0ull && ((int)__popcll(want) >= REFILL_MIN || walking == 0ull)) {
-      if (tr.node == -1) out[idx] = make_uint2(__float_as_uint(tr.best_t), (unsigned)tr.best_slot);
-      const bool mine = tr.node == -1 || tr.node == -2;
+      if (tr.node == LANE_DONE) out[idx] = make_uint2(__float_as_uint(tr.best_t), (unsigned)tr.best_slot);
+      const bool mine = tr.node == LANE_DONE || tr.node == LANE_REFILL;
       if (!exhausted) {
         const int cnt = (int)__popcll(want);
         // rays come in chunks of 128 per wave (one atomic on the shared cursor per chunk: a cursor touched at every refill is the bottleneck, 0.35 Grays/s)
@@ -243,11 +246,11 @@ __global__ __launch_bounds__(256, OCC) void trace_probe_kernel(RenderParams P, c
             inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
             wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
             trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
-          } else tr.node = my >= n ? -3 : -2;      // (-2: the chunk ran out in the middle of the wave's request: next refill)
+          } else tr.node = my >= n ? LANE_RETIRED : LANE_REFILL;      // (LANE_REFILL: the chunk ran out in the middle of the wave's request: next refill)
         }
         exhausted = chunk_next >= n;
-      } else if (mine) tr.node = -3;
-      if (__ballot(tr.node != -3) == 0ull) break;
+      } else if (mine) tr.node = LANE_RETIRED;
+      if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
     for (int u = 0; u < 2; u++) {
       const bool at_leaf = tr.node >= 0 && (tr.node & 1);
@@ -369,7 +372,7 @@ __global__ __launch_bounds__(256) void frame_add_kernel(int4* __restrict__ acc, 
 // ------------------------------------------------------------------ launchers
 // Per-view grazing certificate of the camera rays (option camera_cert): one thread per primitive (slot order); a small triangle whose
 // bound A_T of |d . (e1 x e2)| over the view's camera rays meets only g < n_levels steps of the view's ladder sets, in bit plane g, the bits of the
-// launch's tiles that can see its padded box (device_core.hpp cert_leaf).  mask: words [0, nwords) = one bit per tile (flagged at a_star: a bit in a
+// launch's tiles that can see its padded box (device_cert.hpp cert_leaf).  mask: words [0, nwords) = one bit per tile (flagged at a_star: a bit in a
 // plane g <= cv.base), word nwords = "every tile", word nwords + 1 = flagged tiles, then the n_levels planes of nwords words each; the first
 // nwords + 2 words and the level bytes are cert_finish_kernel's.
 __global__ __launch_bounds__(256) void cert_mask_kernel(const DevPrim* __restrict__ prims, int n, CertView cv, uint32_t* __restrict__ mask, int nwords) {
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(1024) void cert_finish_kernel(uint32_t* __restrict_
   }
 }
 
-// The camera rays' entry table of the same view (option camera_entry; the bodies: device_core.hpp entry_leaf, entry_tile).  One
+// The camera rays' entry table of the same view (option camera_entry; the bodies: device_cert.hpp entry_leaf, entry_tile).  One
 // thread per leaf of the wide tree, in depth-first order (leaf_rec: rank -> record): its record's box folded into the lowest and the highest rank
 // of every tile it can be seen from (mm: 2 ntiles + 1 words, all ones before).
 __global__ __launch_bounds__(256) void entry_leaf_kernel(const DevUnit* __restrict__ wide, const uint32_t* __restrict__ leaf_rec, int n, CertView cv,

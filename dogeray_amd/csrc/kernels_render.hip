@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_core.hpp"
+#include "device_coop.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
     for (int k = 0; k < 8; k++) {
       unsigned long long s = v[k];
       for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (lane == 0 && s) atomicAdd(&P.counters[k], s);
+      if (lane == 0 && s) atomicAdd(&P.counters[STAT_RAYS + k], s);
     }
   }
 }
@@ -61,8 +62,8 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
 // pixel (l >> 3, l & 7) of that tile: which lane renders a pixel does not enter its arithmetic (the RNG
 // seed is a function of x, y and the frame, K:1065), so the frame is identical to the per-tile kernel's.
 //
-// lane states (kept in `tr.node`): >= 0 walking; -1 walk finished, needs shading; -2 needs a new
-// sample or pixel; -3 retired.
+// lane states (kept in `tr.node`): >= 0 walking; LANE_DONE walk finished, needs shading; LANE_REFILL needs a new
+// sample or pixel; LANE_RETIRED (device_walk.hpp).
 // WIDE: the lanes walk the 4-way tree (wide_node_step / wide_leaf_step) instead of the threaded links.  A lane whose
 // next record is a leaf waits until PARK_MIN lanes have one (the leaf step -- exact box + triangle -- is the long
 // block, as the parked triangle test is in the threaded walk); its stack lives in the first WIDE_STACK words of
@@ -71,6 +72,34 @@ __global__ __launch_bounds__(256, OCC) void render_kernel(RenderParams P) {
 // empty, and from the start in the waves that hold a part of a split tile).  It costs registers (96 VGPRs: five waves per SIMD) and
 // code in the loop, so launches whose queue is long enough to hide their tail use the lean build (80 VGPRs and 26 KiB of LDS at
 // OCC = 6: six waves per SIMD; launch_plan.hpp plan_persistent picks).
+
+// ---- the persistent kernel's words, by name
+// A pixel's code: tile * 64 + lane-in-tile, with the sign bit set for a pixel of a split tile (its wave holds while it lives)
+constexpr int PCODE_SPLIT = (int)0x80000000, PCODE_MASK = 0x7fffffff;
+// `share` of a lane (WIDE && COOP): negative = it walks a ray of its own, alone; 0 .. 63 = it helps that lane's ray (the owner); SHARE_OWNER = its own ray has helpers
+constexpr int SHARE_ALONE = -1, SHARE_OWNER = 64;
+// The phase stash: LDS words of a lane, word k at st[k * 64], that hold what the shade / refill phase does not need while it runs and -- WIDE -- what only
+// the phase needs while the wave walks.
+//  WIDE (WIDE_STASH words per lane behind the lane's WIDE_STACK stack words; 26 KiB of LDS per workgroup with the stack: six workgroups per CU):
+//   * WS_TOP, the stack-pointer byte of WS_W1, WS_STEPS and (work-sharing build) WS_RSTART are the walk's state: stashed at the start of a phase, restored at
+//     its end.  The lean build keeps no rstart (the ray's first step is of no use to it): its word is WS_BOUNCE, where the bounce count LIVES;
+//   * the rest is needed in the phase only and LIVES here -- colour, x + 1 (0: no pixel) with y (make_params bounds the frame size), pixel code, sample, and in
+//     the upper half of WS_W1 the frame of the batch: registers only between the read after shading and the write at the end of the phase (the walk loop has
+//     eight registers more for the node step);
+//   * byte 1 of WS_W1 (lean build) is the certificate's grade of the lane's ray: its tile's for a camera ray, 0 for any other; written with every new ray, read
+//     with the stack pointer at the restore;
+//   * between phases WS_STEPS and WS_RSTART are in registers, so the work sharing's exchange has those 2 * 64 words to itself: XCH_MAX hand-overs of XCH_FIELDS
+//     words per round, field f of hand-over e at xch[f * XCH_MAX + e].
+//  Threaded walk (WAVE_LDS_DWORDS / 64 words per lane): the parked leaf, 1/direction, and -- not needed while the hit is shaded, back right after -- the pixel
+//  bookkeeping; everything is stashed at the start of a phase and restored in it.
+enum WideStashWord { WS_TOP = 0, WS_W1, WS_COLOR_X, WS_COLOR_Y, WS_COLOR_Z, WS_XY, WS_PCODE, WS_SAMPLE, WS_STEPS, WS_RSTART, WS_BOUNCE = WS_RSTART };
+constexpr int WS_W1_SP_BYTE = 0, WS_W1_GRADE_BYTE = 1, WS_W1_FRAME_HALF = 1;      // WS_W1's fields, as indices of its bytes / half-words
+constexpr int XCH_OFF = (WIDE_STACK + WS_STEPS) * 64, XCH_MAX = 16, XCH_FIELDS = 8;
+enum XchField { XCH_OX = 0, XCH_OY, XCH_OZ, XCH_DX, XCH_DY, XCH_DZ, XCH_WORD, XCH_ROOT };      // the ray, the stack word handed over, the lane whose pixel the ray belongs to
+static_assert(WS_RSTART + 1 == WIDE_STASH && XCH_MAX * XCH_FIELDS == (WIDE_STASH - WS_STEPS) * 64 && XCH_ROOT + 1 == XCH_FIELDS, "stash layout");
+enum ThreadedStashWord { TS_V0X = 0, TS_C, TS_D = TS_C + 4, TS_INFO = TS_D + 4, TS_PARKED, TS_INV_X, TS_INV_Y, TS_INV_Z, TS_COLOR_X, TS_COLOR_Y, TS_COLOR_Z, TS_PX, TS_PY,
+                         TS_PCODE, TS_FRAME, TS_SAMPLE, TS_STEPS, TS_RSTART, TS_WORDS };
+static_assert(TS_WORDS * 64 == WAVE_LDS_DWORDS, "stash layout");
 
 // PERFRAME: every frame of the launch's batch is stored into a buffer of its own (P.out + frame * P.out_frame_stride) instead of being added into one: the
 // grouped present pipeline (dr_pipeline_*: the frames of a group share one launch and are added and shown one by one afterwards).
@@ -96,11 +125,11 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   int* const my_stack = my_lds + lane;                             // WIDE: word k of this lane's stack at my_stack[k * 64]
   unsigned long long* const share_key = reinterpret_cast<unsigned long long*>(my_lds + (WIDE ? SHARE_OFF : 0));     // [64], WIDE && COOP only
   unsigned* const share_pend = reinterpret_cast<unsigned*>(my_lds + (WIDE ? SHARE_OFF : 0) + 128);                   // [64]
-  if (WIDE) {                      // the phase-only state lives in the stash (see the phase): no pixel yet
+  if (WIDE) {                      // the phase-only state lives in the stash (the layout above): no pixel yet
     int* const st0 = my_lds + WIDE_STACK * 64 + lane;
-    for (int k = 1; k < 8; k++) st0[k * 64] = 0;
+    for (int k = WS_W1; k < WS_STEPS; k++) st0[k * 64] = 0;
   }
-  int share = -1;                  // -1: this lane walks a ray of its own, alone; 0..63: it helps that lane's ray; 64: its ray has helpers
+  int share = SHARE_ALONE;
   WideStack ws; ws.top = 0u; ws.sp = 0; ws.sb = 0;
   const int ntiles = P.ncols * P.gy;
   const int nwork = ntiles * P.batch;          // queue length: every tile of every frame of the batch
@@ -131,7 +160,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   if (P.regions > 1) region = (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) % (unsigned)P.regions);   // HW_REG_XCC_ID, 4 bits
   (void)nwork;
   // per-lane path slot
-  Trav tr; tr.node = -2; tr.best_t = 0; tr.best_slot = -1;
+  Trav tr; tr.node = LANE_REFILL; tr.best_t = 0; tr.best_slot = -1;
   Path path; path.rayo = mk(0, 0, 0); path.raydir = mk(0, 0, 0); path.atten = mk(0, 0, 0);
   V3 inv = mk(0, 0, 0), color = mk(0, 0, 0);
   WideRay wr = wide_ray_none();    // WIDE: clamped 1/direction and margins of the folded node test, a function of the lane's ray
@@ -146,8 +175,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
 
   // diagnostic stamps (counting build only): wave lifetime, cycles inside the shade/refill phase
   unsigned long long t_begin = 0, t_phase = 0, n_iter = 0, n_phase = 0, n_nodestep = 0, n_leafstep = 0, n_shaded = 0;
-  float* const ray_log = COUNT ? reinterpret_cast<float*>(P.counters[41]) : nullptr;      // measurement aid (dr_context_probe_trace): statistics words 40-42 = rays logged, the log, its room
-  const unsigned long long ray_log_room = COUNT ? P.counters[42] : 0ull;
+  float* const ray_log = COUNT ? reinterpret_cast<float*>(P.counters[STAT_LOG_PTR]) : nullptr;      // measurement aid (dr_context_probe_trace)
+  const unsigned long long ray_log_room = COUNT ? P.counters[STAT_LOG_ROOM] : 0ull;
   unsigned long long pb_cands = 0, pb_turns = 0, pb_sphere = 0, pb_disk = 0, pb_retired = 0;      // ... the phase's budget (dr_stats_phase_counts)
   unsigned long long r_begin = 0;
   // wave lifetime in shader cycles and in 100 MHz ticks, every build: two clock reads per wave, written to the statistics buffer only
@@ -170,52 +199,50 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       // done takes the shared result once its last helper has reported
       // (the pending word: helpers still out in the low 8 bits; above them the node steps the helpers have spent on this pixel's rays,
       // which the owner adds to its own when it takes the result -- the cost fed back for a pixel is all the work it caused)
-      if (tr.node == -1 && share >= 0 && share < 64) {
+      if (tr.node == LANE_DONE && share >= 0 && share < SHARE_OWNER) {
         atomicMin(&share_key[share], hit_key(tr.best_t, tr.best_slot));
         atomicAdd(&share_pend[share], (((steps - rstart - (unsigned)P.coop_steps) & 0xffffu) << 8) - 1u);
-        tr.node = -3; share = -1;
+        tr.node = LANE_RETIRED; share = SHARE_ALONE;
       }
-      if (tr.node == -1 && share == 64) {
+      if (tr.node == LANE_DONE && share == SHARE_OWNER) {
         atomicMin(&share_key[lane], hit_key(tr.best_t, tr.best_slot));      // its own last improvement may be newer than the key
         if ((share_pend[lane] & 0xffu) == 0u) {
           steps += share_pend[lane] >> 8;
           const unsigned long long k = share_key[lane];
           tr.best_t = __uint_as_float((unsigned)(k >> 32)); tr.best_slot = (int)(unsigned)k;
-          share = -1;
+          share = SHARE_ALONE;
         }
       }
     }
-    const bool waits_for_helpers = WIDE && COOP && share == 64;      // (only ever true with tr.node == -1 here or while still walking)
+    const bool waits_for_helpers = WIDE && COOP && share == SHARE_OWNER;      // (only ever true with tr.node == LANE_DONE here or while still walking)
     // (a holding wave -- long pixels, helpers walking for them -- shades as soon as a ray is finished: its pixels' latency is the point)
-    if ((__popcll(walking) < TRAV_MIN || (WIDE && COOP && held)) && (walking == 0ull || __ballot((tr.node == -1 && !waits_for_helpers) || tr.node == -2) != 0ull)) {
+    if ((__popcll(walking) < TRAV_MIN || (WIDE && COOP && held)) && (walking == 0ull || __ballot((tr.node == LANE_DONE && !waits_for_helpers) || tr.node == LANE_REFILL) != 0ull)) {
       unsigned long long t0 = 0;
       DR_MARK("phase_begin");
       if (COUNT) { t0 = __builtin_readcyclecounter(); n_phase++; }
-      const bool shade_me = tr.node == -1 && !(PARK_MIN > 0 && pk.parked) && !waits_for_helpers;
+      const bool shade_me = tr.node == LANE_DONE && !(PARK_MIN > 0 && pk.parked) && !waits_for_helpers;
       if (COUNT) n_shaded += __popcll(__ballot(shade_me));
       bool fresh_ray = false;                  // this lane starts a new ray in this phase: 1/direction is recomputed after the phase
-      constexpr bool BOUNCE_HOME = WIDE && !COOP;      // lean build: the bounce count lives in stash word 9 (one register more for the walk)
+      constexpr bool BOUNCE_HOME = WIDE && !COOP;      // lean build: the bounce count lives in the stash, WS_BOUNCE (one register more for the walk)
       float* const st = reinterpret_cast<float*>(my_lds) + (WIDE ? WIDE_STACK * 64 : 0) + lane;      // slot k of this lane: st[k * 64]
       if (WIDE) {
-        // ten words (26 KiB of LDS per workgroup with the stack: six workgroups per CU).  Words 2-7 (colour, x + 1 (0: no pixel) with y -- make_params
-        // bounds the frame size --, pixel code, sample) and the frame of the batch (upper half of word 1) are needed in this phase only: they LIVE
-        // here and are registers only between the read after shading and the write at the end of the phase (the walk loop has eight registers
-        // more for the node step).  What goes in now is the walk's state: stack top, stack pointer, step counts.
-        st[0 * 64] = __uint_as_float(ws.top);
-        reinterpret_cast<unsigned char*>(st + 1 * 64)[0] = (unsigned char)ws.sp;
-        st[8 * 64] = __uint_as_float(steps);
-        if (COOP) st[9 * 64] = __uint_as_float(rstart);      // (lean build: the ray's first step is of no use to it, and word 9 is where `bounce` lives)
+        // what goes in now is the walk's state: stack top, stack pointer, step counts (the stash layout above; the phase-only words are there already)
+        st[WS_TOP * 64] = __uint_as_float(ws.top);
+        reinterpret_cast<unsigned char*>(st + WS_W1 * 64)[WS_W1_SP_BYTE] = (unsigned char)ws.sp;
+        st[WS_STEPS * 64] = __uint_as_float(steps);
+        if (COOP) st[WS_RSTART * 64] = __uint_as_float(rstart);      // (lean build: the word is WS_BOUNCE)
         asm volatile("" ::: "memory");
       } else {
-        st[0 * 64] = pk.v0x; st[1 * 64] = __uint_as_float(pk.C.x); st[2 * 64] = __uint_as_float(pk.C.y); st[3 * 64] = __uint_as_float(pk.C.z); st[4 * 64] = __uint_as_float(pk.C.w);
-        st[5 * 64] = __uint_as_float(pk.D.x); st[6 * 64] = __uint_as_float(pk.D.y); st[7 * 64] = __uint_as_float(pk.D.z); st[8 * 64] = __uint_as_float(pk.D.w);
-        st[9 * 64] = __int_as_float(pk.info); st[10 * 64] = pk.parked ? 1.0f : 0.0f;
-        st[11 * 64] = inv.x; st[12 * 64] = inv.y; st[13 * 64] = inv.z;
+        st[TS_V0X * 64] = pk.v0x;
+        st[(TS_C + 0) * 64] = __uint_as_float(pk.C.x); st[(TS_C + 1) * 64] = __uint_as_float(pk.C.y); st[(TS_C + 2) * 64] = __uint_as_float(pk.C.z); st[(TS_C + 3) * 64] = __uint_as_float(pk.C.w);
+        st[(TS_D + 0) * 64] = __uint_as_float(pk.D.x); st[(TS_D + 1) * 64] = __uint_as_float(pk.D.y); st[(TS_D + 2) * 64] = __uint_as_float(pk.D.z); st[(TS_D + 3) * 64] = __uint_as_float(pk.D.w);
+        st[TS_INFO * 64] = __int_as_float(pk.info); st[TS_PARKED * 64] = pk.parked ? 1.0f : 0.0f;
+        st[TS_INV_X * 64] = inv.x; st[TS_INV_Y * 64] = inv.y; st[TS_INV_Z * 64] = inv.z;
         // pixel bookkeeping: not needed while the hit is shaded, back right after
-        st[14 * 64] = color.x; st[15 * 64] = color.y; st[16 * 64] = color.z;
-        st[17 * 64] = __int_as_float(px); st[18 * 64] = __int_as_float(py); st[19 * 64] = __int_as_float(pcode);
-        st[20 * 64] = __int_as_float(frame); st[21 * 64] = __int_as_float(sample);
-        st[22 * 64] = __uint_as_float(steps); st[23 * 64] = __uint_as_float(rstart);
+        st[TS_COLOR_X * 64] = color.x; st[TS_COLOR_Y * 64] = color.y; st[TS_COLOR_Z * 64] = color.z;
+        st[TS_PX * 64] = __int_as_float(px); st[TS_PY * 64] = __int_as_float(py); st[TS_PCODE * 64] = __int_as_float(pcode);
+        st[TS_FRAME * 64] = __int_as_float(frame); st[TS_SAMPLE * 64] = __int_as_float(sample);
+        st[TS_STEPS * 64] = __uint_as_float(steps); st[TS_RSTART * 64] = __uint_as_float(rstart);
         asm volatile("" ::: "memory");           // the values must really travel through LDS (no forwarding in registers)
       }
       // ---- shade the lanes whose walk has finished
@@ -223,7 +250,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       bool ended = false;
       V3 radiance = mk(0, 0, 0);
       // (the hit is shaded in two parts around the phase's ONE rejection loop, which serves the lanes that scatter -- a point in the unit
-      // sphere -- and, further down, the lanes that start a path -- a point in the unit disk: device_core.hpp rand_points_merged.  A path that ends
+      // sphere -- and, further down, the lanes that start a path -- a point in the unit disk: device_rng.hpp rand_points_merged.  A path that ends
       // here, at an emissive surface or at the depth limit, draws nothing more: its generator is re-seeded with its next pixel.)
       ShadeCtx sc; sc.hitpoint = sc.N = sc.ocolor = mk(0, 0, 0); sc.add_x = sc.rough = sc.ir = sc.r5 = 0.0f; sc.mat = -1; sc.front = false;
       bool scatter_me = false;
@@ -231,11 +258,11 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         if (tr.best_slot >= 0 && tr.best_t > 0.0f) {
           if (!shade_prepare<COUNT>(P, path, tr.best_t, tr.best_slot, rng, c, sc, radiance)) ended = true;
           else {
-            if (BOUNCE_HOME) bounce = __float_as_int(st[9 * 64]);
+            if (BOUNCE_HOME) bounce = __float_as_int(st[WS_BOUNCE * 64]);
             bounce++;
             if (bounce >= P.max_depth) ended = true;        // depth exhausted: black (K:981)
             else scatter_me = true;
-            if (BOUNCE_HOME) st[9 * 64] = __int_as_float(bounce);
+            if (BOUNCE_HOME) st[WS_BOUNCE * 64] = __int_as_float(bounce);
           }
         } else {
           radiance = shade_miss<COUNT>(P, path, c);
@@ -245,24 +272,24 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       DR_MARK("phase_unstash");
       if (WIDE) {
         asm volatile("" ::: "memory");
-        color = mk(st[2 * 64], st[3 * 64], st[4 * 64]);
-        { const int xy = __float_as_int(st[5 * 64]); px = (int)((unsigned)xy >> 16) - 1; py = xy & 0xffff; }
-        pcode = __float_as_int(st[6 * 64]);
-        frame = (int)((unsigned)__float_as_int(st[1 * 64]) >> 16); sample = __float_as_int(st[7 * 64]);
-        steps = __float_as_uint(st[8 * 64]);
-        if (COOP) rstart = __float_as_uint(st[9 * 64]);
+        color = mk(st[WS_COLOR_X * 64], st[WS_COLOR_Y * 64], st[WS_COLOR_Z * 64]);
+        { const int xy = __float_as_int(st[WS_XY * 64]); px = (int)((unsigned)xy >> 16) - 1; py = xy & 0xffff; }
+        pcode = __float_as_int(st[WS_PCODE * 64]);
+        frame = (int)((unsigned)__float_as_int(st[WS_W1 * 64]) >> (16 * WS_W1_FRAME_HALF)); sample = __float_as_int(st[WS_SAMPLE * 64]);
+        steps = __float_as_uint(st[WS_STEPS * 64]);
+        if (COOP) rstart = __float_as_uint(st[WS_RSTART * 64]);
       } else {
         asm volatile("" ::: "memory");
-        color = mk(st[14 * 64], st[15 * 64], st[16 * 64]);
-        px = __float_as_int(st[17 * 64]); py = __float_as_int(st[18 * 64]); pcode = __float_as_int(st[19 * 64]);
-        frame = __float_as_int(st[20 * 64]); sample = __float_as_int(st[21 * 64]);
-        steps = __float_as_uint(st[22 * 64]); rstart = __float_as_uint(st[23 * 64]);
+        color = mk(st[TS_COLOR_X * 64], st[TS_COLOR_Y * 64], st[TS_COLOR_Z * 64]);
+        px = __float_as_int(st[TS_PX * 64]); py = __float_as_int(st[TS_PY * 64]); pcode = __float_as_int(st[TS_PCODE * 64]);
+        frame = __float_as_int(st[TS_FRAME * 64]); sample = __float_as_int(st[TS_SAMPLE * 64]);
+        steps = __float_as_uint(st[TS_STEPS * 64]); rstart = __float_as_uint(st[TS_RSTART * 64]);
       }
       if (shade_me) {
         if (ended) {
           color = color + radiance;
           sample++;
-          tr.node = -2;
+          tr.node = LANE_REFILL;
         } else {
           trav_begin(tr);
           rstart = steps;
@@ -272,13 +299,13 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       }
       // ---- lanes between paths: next sample of the same pixel, or store and take a new pixel
       bool want_pixel = false;
-      if (tr.node == -2) {
+      if (tr.node == LANE_REFILL) {
         if (px >= 0 && (float)sample < P.spp_f && !degenerate) {
           // same pixel, next sample (K:1059)
         } else {
           if (px >= 0) {
             store_pixel(P, px, py, color, PERFRAME ? (size_t)frame * (size_t)P.out_frame_stride : (size_t)0);
-            if (pixel_cost) pixel_cost[pcode & 0x7fffffff] = steps;
+            if (pixel_cost) pixel_cost[pcode & PCODE_MASK] = steps;
           }
           px = -1;
           want_pixel = true;
@@ -289,14 +316,16 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         // their own pixels end, are helpers that take over subtrees of the long pixels' rays (the work-sharing block below); once
         // the pixels are done the lanes go back to fetching.
         held = __ballot(px >= 0 && pcode < 0) != 0ull;
-        if (!held && tr.node == -3 && share < 0 && !(cur_tile >= ntiles && regions_left == 0)) { tr.node = -2; want_pixel = true; }
+        if (!held && tr.node == LANE_RETIRED && share < 0 && !(cur_tile >= ntiles && regions_left == 0)) { tr.node = LANE_REFILL; want_pixel = true; }
       }
       unsigned long long need = __ballot(want_pixel);
       unsigned cam_cert = 0u;                      // lean build: the word (entry code, grade) of the tile this lane's pixel came from in this phase
       while (need != 0ull) {
+        // (the fetch below stays written out in the refill loop: moved into an always-inline lambda, the same statements compile to a different kernel --
+        // most of the file's assembly changes; like the wide steps further down, not to be restructured without a GPU to measure on)
         if (cur_next >= cur_limit) {               // wave-uniform: fetch the next chunk (tile, frame)
           if (WIDE && COOP && held) {              // holding: no new tile, the lanes asking become helpers
-            if (want_pixel) { tr.node = -3; want_pixel = false; }
+            if (want_pixel) { tr.node = LANE_RETIRED; want_pixel = false; }
             break;
           }
           cur_tile = ntiles;
@@ -330,7 +359,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           }
         }
         if (cur_tile >= ntiles) {                  // frame exhausted: retire the lanes still asking
-          if (want_pixel) { tr.node = -3; want_pixel = false; }
+          if (want_pixel) { tr.node = LANE_RETIRED; want_pixel = false; }
           if (WAVE_LOG && r_empty == 0ull) r_empty = __builtin_amdgcn_s_memrealtime();
           break;
         }
@@ -341,7 +370,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           const int col = cur_tile / P.gy, by = cur_tile - col * P.gy;
           px = (P.stripe_rem + col * P.stripe_mod) * 8 + (l >> 3);
           py = by * 8 + (l & 7);
-          pcode = (cur_tile * 64 + l) | (cur_split ? (int)0x80000000 : 0);      // sign bit: pixel of a split tile (its wave holds while it lives)
+          pcode = (cur_tile * 64 + l) | (cur_split ? PCODE_SPLIT : 0);
           frame = cur_frame;
           steps = 0;
           sample = 0;
@@ -357,7 +386,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       DR_MARK("phase_camera");
       bool new_path = false;
       float cam_nu = 0.0f, cam_nv = 0.0f;
-      if (tr.node == -2 && px >= 0) {
+      if (tr.node == LANE_REFILL && px >= 0) {
         if (degenerate) {
           sample = 0x7fffffff;                     // nothing to trace: the pixel is stored as 0 next round
           if (COUNT) c.samples++;
@@ -380,8 +409,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           unsigned long long lane_turns = my_turns;
           for (int off = 32; off > 0; off >>= 1) lane_turns += __shfl_xor(lane_turns, off, 64);
           const unsigned n_sphere = (unsigned)__popcll(__ballot(draw_kind == 3)), n_disk = (unsigned)__popcll(__ballot(draw_kind == 2));
-          const unsigned n_retired = (unsigned)__popcll(__ballot(tr.node == -3));
-          if (lane == 0) atomicAdd(&P.counters[16 + (wave_turns < 15u ? wave_turns : 15u)], 1ull);      // histogram of turns per phase (the sums below leave with the wave)
+          const unsigned n_retired = (unsigned)__popcll(__ballot(tr.node == LANE_RETIRED));
+          if (lane == 0) atomicAdd(&P.counters[STAT_TURN_HIST + (wave_turns < (unsigned)(STAT_TURN_BINS - 1) ? wave_turns : (unsigned)(STAT_TURN_BINS - 1))], 1ull);      // histogram of turns per phase (the sums below leave with the wave)
           pb_cands += lane_turns; pb_turns += wave_turns; pb_sphere += n_sphere; pb_disk += n_disk; pb_retired += n_retired;
         }
         if (scatter_me) shade_scatter(path, sc, pt, rng);
@@ -389,7 +418,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           camera_finish(P, cam_nu, cam_nv, pt, path.rayo, path.raydir);
           path.atten = splat(1.0f);
           bounce = 0;
-          if (BOUNCE_HOME) st[9 * 64] = __int_as_float(0);
+          if (BOUNCE_HOME) st[WS_BOUNCE * 64] = __int_as_float(0);
           trav_begin(tr);
           // the camera rays of a tile start at the tile's entry record (no word: the root, as trav_begin left it); ENTRY_NONE: nothing of the scene can
           // be seen from the tile -- the walk is over before it began and the next phase shades a miss
@@ -398,13 +427,12 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           fresh_ray = true;
         }
       }
-      // lean build: byte 1 of stash word 1 (beside the stack pointer) is the certificate's grade of the lane's ray: its tile's for a camera ray, 0 for
-      // any other; written with every new ray, read with the stack pointer at the restore
-      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + 1 * 64)[1] = (unsigned char)(new_path ? cam_cert & ((1u << ENTRY_SHIFT) - 1u) : 0u);
+      // lean build: the certificate's grade of the lane's ray (the stash layout above)
+      if (BOUNCE_HOME && fresh_ray) reinterpret_cast<unsigned char*>(st + WS_W1 * 64)[WS_W1_GRADE_BYTE] = (unsigned char)(new_path ? cam_cert & ((1u << ENTRY_SHIFT) - 1u) : 0u);
       if (COUNT && ray_log && fresh_ray && frame == 0) {      // measurement aid (dr_context_probe_trace): the rays the launch's first frame traces, in the
-        // order a per-bounce wavefront would hold them: bounce by bounce, pixels in tile order.  Statistics words 40-42 = rays logged, the log, its room (entries)
-        atomicAdd(&P.counters[40], 1ull);
-        const unsigned long long k = (unsigned long long)bounce * (unsigned long long)(ntiles * 64) + (unsigned long long)(pcode & 0x7fffffff);
+        // order a per-bounce wavefront would hold them: bounce by bounce, pixels in tile order
+        atomicAdd(&P.counters[STAT_LOG_RAYS], 1ull);
+        const unsigned long long k = (unsigned long long)bounce * (unsigned long long)(ntiles * 64) + (unsigned long long)(pcode & PCODE_MASK);
         if (k < ray_log_room) {
           float* const r = ray_log + k * 8;
           r[0] = path.rayo.x; r[1] = path.rayo.y; r[2] = path.rayo.z; r[3] = 0.0f; r[4] = path.raydir.x; r[5] = path.raydir.y; r[6] = path.raydir.z; r[7] = 0.0f;
@@ -413,33 +441,34 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       DR_MARK("phase_restore");
       if (WIDE) {
         asm volatile("" ::: "memory");
-        const int w1 = __float_as_int(st[1 * 64]);
-        ws.top = __float_as_uint(st[0 * 64]); ws.sp = w1 & 0xff;
+        const int w1 = __float_as_int(st[WS_W1 * 64]);
+        ws.top = __float_as_uint(st[WS_TOP * 64]); ws.sp = (w1 >> (8 * WS_W1_SP_BYTE)) & 0xff;
         // the phase-only state goes home (the values in registers are dead from here to the next phase)
-        st[2 * 64] = color.x; st[3 * 64] = color.y; st[4 * 64] = color.z;
-        st[5 * 64] = __int_as_float(((px + 1) << 16) | py); st[6 * 64] = __int_as_float(pcode);
-        st[7 * 64] = __int_as_float(sample);
-        reinterpret_cast<unsigned short*>(st + 1 * 64)[1] = (unsigned short)frame;
+        st[WS_COLOR_X * 64] = color.x; st[WS_COLOR_Y * 64] = color.y; st[WS_COLOR_Z * 64] = color.z;
+        st[WS_XY * 64] = __int_as_float(((px + 1) << 16) | py); st[WS_PCODE * 64] = __int_as_float(pcode);
+        st[WS_SAMPLE * 64] = __int_as_float(sample);
+        reinterpret_cast<unsigned short*>(st + WS_W1 * 64)[WS_W1_FRAME_HALF] = (unsigned short)frame;
         asm volatile("" ::: "memory");
         color = mk(0, 0, 0); px = -1; py = 0; pcode = 0; sample = 0; frame = 0;
         if (fresh_ray) { ws.top = 0u; ws.sp = 0; ws.sb = 0; }
         inv = mk(1.0f / path.raydir.x, 1.0f / path.raydir.y, 1.0f / path.raydir.z);      // 1/direction and the folded test's margins are
-        // (a camera ray of a tile of grade g in the view's grazing certificate -- byte 1 of word 1 -- carries E scaled by 1e-4 / a_star of ladder step g - 1,
+        // (a camera ray of a tile of grade g in the view's grazing certificate -- the grade byte of WS_W1 -- carries E scaled by 1e-4 / a_star of ladder step g - 1,
         // grade 0 by 1: DESIGN.md 4.10)
-        const float cert = BOUNCE_HOME ? P.wide_cert_k[(w1 >> 8) & CERT_MAX_LEVELS] : 1.0f;
+        const float cert = BOUNCE_HOME ? P.wide_cert_k[(w1 >> (8 * WS_W1_GRADE_BYTE)) & CERT_MAX_LEVELS] : 1.0f;
         wr = wide_ray(path.rayo, path.raydir, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, cert);                // recomputed for every lane rather than stashed
         sg = sign_mask(inv);
       } else {
         asm volatile("" ::: "memory");
-        pk.v0x = st[0 * 64]; pk.C = u32x4{__float_as_uint(st[1 * 64]), __float_as_uint(st[2 * 64]), __float_as_uint(st[3 * 64]), __float_as_uint(st[4 * 64])};
-        pk.D = u32x4{__float_as_uint(st[5 * 64]), __float_as_uint(st[6 * 64]), __float_as_uint(st[7 * 64]), __float_as_uint(st[8 * 64])};
-        pk.info = __float_as_int(st[9 * 64]); pk.parked = st[10 * 64] != 0.0f;
-        inv = mk(st[11 * 64], st[12 * 64], st[13 * 64]);
+        pk.v0x = st[TS_V0X * 64];
+        pk.C = u32x4{__float_as_uint(st[(TS_C + 0) * 64]), __float_as_uint(st[(TS_C + 1) * 64]), __float_as_uint(st[(TS_C + 2) * 64]), __float_as_uint(st[(TS_C + 3) * 64])};
+        pk.D = u32x4{__float_as_uint(st[(TS_D + 0) * 64]), __float_as_uint(st[(TS_D + 1) * 64]), __float_as_uint(st[(TS_D + 2) * 64]), __float_as_uint(st[(TS_D + 3) * 64])};
+        pk.info = __float_as_int(st[TS_INFO * 64]); pk.parked = st[TS_PARKED * 64] != 0.0f;
+        inv = mk(st[TS_INV_X * 64], st[TS_INV_Y * 64], st[TS_INV_Z * 64]);
         if (fresh_ray) inv = mk(1.0f / path.raydir.x, 1.0f / path.raydir.y, 1.0f / path.raydir.z);
       }
       if (COUNT) t_phase += __builtin_readcyclecounter() - t0;
       DR_MARK("phase_end");
-      if (__ballot(tr.node != -3) == 0ull) break;
+      if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
     if (WIDE && COOP && !COUNT && P.coop_steps > 0 && (cur_tile >= ntiles || held)) {
       // ---- draining (the queue is empty), or holding (pixels of a split tile, see the refill above): lanes without a pixel take over subtrees of the rays that still walk.  A walking lane
@@ -450,39 +479,37 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       // of dependent steps is spread over the idle lanes at the cost of one hand-over per piece -- every leaf is still
       // tested by exactly one lane, with the reference's box and arithmetic, against a bound no smaller than the final t.
       for (int round = 0; round < P.coop_rounds; round++) {      // (a lane that has just taken a word over may hand part of it on in the next round)
-      const unsigned long long idle = __ballot(tr.node == -3);
+      const unsigned long long idle = __ballot(tr.node == LANE_RETIRED);
       const bool can_give = tr.node >= 0 && (ws.sp > ws.sb || ws.top != 0u) && (int)(steps - rstart) >= P.coop_steps;
       const unsigned long long givers = __ballot(can_give);
       const int n_idle = (int)__popcll(idle), n_give = (int)__popcll(givers);
-      // (with the phase-only state at home in stash words 1-7, the exchange has words 8-9 of the stash -- the step counts, in registers
-      // between phases -- to itself: 128 words = 16 hand-overs of 8 words per round)
-      constexpr int XCH_MAX = 16;
+      // (the exchange: XCH_MAX hand-overs per round in the stash's step-count words -- the stash layout above)
       const int n_most = n_idle < n_give ? n_idle : n_give;
       const int n = n_most < XCH_MAX ? n_most : XCH_MAX;
       if (n == 0) break;
       {
-        int* const xch = my_lds + (WIDE_STACK + 8) * 64;      // field f of hand-over e at xch[f * XCH_MAX + e]
+        int* const xch = my_lds + XCH_OFF;      // field f of hand-over e at xch[f * XCH_MAX + e]
         const int rank_g = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(givers >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)givers, 0u));
         const int rank_i = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
         if (can_give && rank_g < n) {
-          const int root = share >= 0 && share < 64 ? share : lane;               // the lane whose pixel this ray belongs to
-          if (share < 0) { share_key[lane] = hit_key(tr.best_t, tr.best_slot); share_pend[lane] = 0u; share = 64; }
+          const int root = share >= 0 && share < SHARE_OWNER ? share : lane;               // the lane whose pixel this ray belongs to
+          if (share < 0) { share_key[lane] = hit_key(tr.best_t, tr.best_slot); share_pend[lane] = 0u; share = SHARE_OWNER; }
           atomicAdd(&share_pend[root], 1u);
           unsigned word;
           if (ws.sp > ws.sb) { word = (unsigned)my_stack[ws.sb * 64]; ws.sb++; }
           else { word = ws.top; ws.top = 0u; }
-          xch[rank_g + 0 * XCH_MAX] = __float_as_int(path.rayo.x); xch[rank_g + 1 * XCH_MAX] = __float_as_int(path.rayo.y); xch[rank_g + 2 * XCH_MAX] = __float_as_int(path.rayo.z);
-          xch[rank_g + 3 * XCH_MAX] = __float_as_int(path.raydir.x); xch[rank_g + 4 * XCH_MAX] = __float_as_int(path.raydir.y); xch[rank_g + 5 * XCH_MAX] = __float_as_int(path.raydir.z);
-          xch[rank_g + 6 * XCH_MAX] = (int)word; xch[rank_g + 7 * XCH_MAX] = root;
+          xch[rank_g + XCH_OX * XCH_MAX] = __float_as_int(path.rayo.x); xch[rank_g + XCH_OY * XCH_MAX] = __float_as_int(path.rayo.y); xch[rank_g + XCH_OZ * XCH_MAX] = __float_as_int(path.rayo.z);
+          xch[rank_g + XCH_DX * XCH_MAX] = __float_as_int(path.raydir.x); xch[rank_g + XCH_DY * XCH_MAX] = __float_as_int(path.raydir.y); xch[rank_g + XCH_DZ * XCH_MAX] = __float_as_int(path.raydir.z);
+          xch[rank_g + XCH_WORD * XCH_MAX] = (int)word; xch[rank_g + XCH_ROOT * XCH_MAX] = root;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (tr.node == -3 && rank_i < n) {
-          path.rayo = mk(__int_as_float(xch[rank_i + 0 * XCH_MAX]), __int_as_float(xch[rank_i + 1 * XCH_MAX]), __int_as_float(xch[rank_i + 2 * XCH_MAX]));
-          path.raydir = mk(__int_as_float(xch[rank_i + 3 * XCH_MAX]), __int_as_float(xch[rank_i + 4 * XCH_MAX]), __int_as_float(xch[rank_i + 5 * XCH_MAX]));
-          ws.top = (unsigned)xch[rank_i + 6 * XCH_MAX]; ws.sp = 0; ws.sb = 0;
-          share = xch[rank_i + 7 * XCH_MAX];
+        if (tr.node == LANE_RETIRED && rank_i < n) {
+          path.rayo = mk(__int_as_float(xch[rank_i + XCH_OX * XCH_MAX]), __int_as_float(xch[rank_i + XCH_OY * XCH_MAX]), __int_as_float(xch[rank_i + XCH_OZ * XCH_MAX]));
+          path.raydir = mk(__int_as_float(xch[rank_i + XCH_DX * XCH_MAX]), __int_as_float(xch[rank_i + XCH_DY * XCH_MAX]), __int_as_float(xch[rank_i + XCH_DZ * XCH_MAX]));
+          ws.top = (unsigned)xch[rank_i + XCH_WORD * XCH_MAX]; ws.sp = 0; ws.sb = 0;
+          share = xch[rank_i + XCH_ROOT * XCH_MAX];
           inv = mk(1.0f / path.raydir.x, 1.0f / path.raydir.y, 1.0f / path.raydir.z);
           wr = wide_ray(path.rayo, path.raydir, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v);
           sg = sign_mask(inv);
@@ -496,7 +523,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       }
       // lanes of a shared ray: publish an improvement, take over a better bound
       if (tr.node >= 0 && share >= 0) {
-        const int root = share < 64 ? share : lane;
+        const int root = share < SHARE_OWNER ? share : lane;
         const unsigned long long mine = hit_key(tr.best_t, tr.best_slot), k = share_key[root];
         if (mine < k) atomicMin(&share_key[root], mine);
         else if (k < mine) { tr.best_t = __uint_as_float((unsigned)(k >> 32)); tr.best_slot = (int)(unsigned)k; }
@@ -515,7 +542,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         Hit r;
         const bool done = coop_closest_hit(P.pairs, P.prims, uo, ud, ui, bcast(tr.best_t), __builtin_amdgcn_readlane(tr.best_slot, L), my_lds, r);
         if (lane == L) {
-          if (done) { tr.best_t = r.t; tr.best_slot = r.slot; tr.node = -1; }
+          if (done) { tr.best_t = r.t; tr.best_slot = r.slot; tr.node = LANE_DONE; }
           else rstart = 0x80000000u;              // stack overflow: never ask again for this ray ((int)(steps - rstart) is negative from now on)
         }
       }
@@ -590,32 +617,32 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   }
   if (lane == 0) {
     const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
-    atomicAdd(&P.counters[8], __builtin_readcyclecounter() - t_begin);
-    atomicAdd(&P.counters[15], r_end - r_begin);      // 100 MHz ticks: wave cycles / this = shader clock / 100 MHz
+    atomicAdd(&P.counters[STAT_WAVE_CYCLES], __builtin_readcyclecounter() - t_begin);
+    atomicAdd(&P.counters[STAT_WAVE_TICKS], r_end - r_begin);      // 100 MHz ticks: wave cycles / this = shader clock / 100 MHz
     if (WAVE_LOG && P.wave_log) {
       unsigned long long* const w = P.wave_log + (size_t)wave_id * 16;
       w[0] = r_begin; w[1] = r_empty; w[2] = r_end; w[3] = n_after;
     }
   }
   if (COUNT && lane == 0) {
-    atomicAdd(&P.counters[9], t_phase);
-    atomicAdd(&P.counters[10], n_iter);
-    atomicAdd(&P.counters[11], n_phase);
-    atomicAdd(&P.counters[12], n_nodestep);
-    atomicAdd(&P.counters[13], n_leafstep);
-    atomicAdd(&P.counters[14], n_shaded);
-    atomicAdd(&P.counters[32], pb_cands);        // candidates drawn by all lanes
-    atomicAdd(&P.counters[33], pb_turns);        // turns the waves ran
-    atomicAdd(&P.counters[34], pb_sphere);       // lanes that drew a point in the sphere (scatter)
-    atomicAdd(&P.counters[35], pb_disk);         // lanes that drew a point in the disk (new path)
-    atomicAdd(&P.counters[36], pb_retired);      // retired lanes summed over phases
+    atomicAdd(&P.counters[STAT_PHASE_CYCLES], t_phase);
+    atomicAdd(&P.counters[STAT_ITERATIONS], n_iter);
+    atomicAdd(&P.counters[STAT_PHASES], n_phase);
+    atomicAdd(&P.counters[STAT_NODE_STEPS], n_nodestep);
+    atomicAdd(&P.counters[STAT_LEAF_STEPS], n_leafstep);
+    atomicAdd(&P.counters[STAT_SHADED], n_shaded);
+    atomicAdd(&P.counters[STAT_PB_CANDS], pb_cands);        // candidates drawn by all lanes
+    atomicAdd(&P.counters[STAT_PB_TURNS], pb_turns);        // turns the waves ran
+    atomicAdd(&P.counters[STAT_PB_SPHERE], pb_sphere);       // lanes that drew a point in the sphere (scatter)
+    atomicAdd(&P.counters[STAT_PB_DISK], pb_disk);         // lanes that drew a point in the disk (new path)
+    atomicAdd(&P.counters[STAT_PB_RETIRED], pb_retired);      // retired lanes summed over phases
   }
   if (COUNT) {
     unsigned v[8] = {c.rays, c.V, c.L, c.S, c.T, c.samples, c.trav_slots, c.ray_slots};
     for (int k = 0; k < 8; k++) {
       unsigned long long s = v[k];
       for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (lane == 0 && s) atomicAdd(&P.counters[k], s);
+      if (lane == 0 && s) atomicAdd(&P.counters[STAT_RAYS + k], s);
     }
   }
 }

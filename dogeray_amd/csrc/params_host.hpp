@@ -68,7 +68,7 @@ inline const char* fill_view_params(const float* st, int W, int H, float backgro
   return nullptr;
 }
 
-// The camera rays' grazing certificate of a view (CertView, device_layout.h; device_core.hpp cert_leaf): from the launch's float camera block, in double.
+// The camera rays' grazing certificate of a view (CertView, device_layout.h; device_cert.hpp cert_leaf): from the launch's float camera block, in double.
 // a_star: the certified |a^| (>= 1e-4); e_own: the scene's WideMu e.  Returns false when the view gives nothing to certify with (no own-bounds tree,
 // degenerate camera, non-finite values): its camera rays then keep the scene's margin.
 inline bool fill_cert_view(const RenderParams& P, double a_star, float e_own, CertView& cv) {

@@ -265,7 +265,7 @@ bool quantise(const Box* cb, int n, float origin[3], float scale[3], uint8_t lo[
 }  // namespace
 
 // The leaves' ranks in depth-first order of the wide tree (children in record order) and every record's range of them, read off the records
-// themselves (linearise.hpp WideImage): what the camera rays' entry table is built from (device_core.hpp entry_leaf / entry_tile).
+// themselves (linearise.hpp WideImage): what the camera rays' entry table is built from (device_cert.hpp entry_leaf / entry_tile).
 void wide_ranks(const std::vector<DevUnit>& rec, std::vector<uint32_t>& leaf_rec, std::vector<uint32_t>& range) {
   const size_t n = rec.size() / WIDE_UNITS;
   leaf_rec.clear();
@@ -302,7 +302,7 @@ bool build_wide(const HostScene& sc, const std::vector<int>& leaf_node_of_slot, 
   }
   // ---- 0. the boxes the tree is built over and culls with.  tree_mode 2: a small triangle enters with its OWN bounds (the record's v0, v0 + e1, v0 + e2,
   // rounded outward) instead of the reference's leaf box, which is those bounds padded by 0.01 (K:353-354) -- 2.9 times the footprint of a 0.028-wide triangle --;
-  // the rays make up for it with a margin that is a multiple of E = max |e1| |e2| over these triangles (device_core.hpp wide_ray_margin).
+  // the rays make up for it with a margin that is a multiple of E = max |e1| |e2| over these triangles (device_wide.hpp wide_ray_margin).
   // "Small": |e1| |e2| at or below a cut chosen per scene (below); the tree keeps the reference's boxes altogether unless at least half of the leaves qualify.
   // Other primitives keep the reference's box.
   std::vector<Box> cull(leaf);
@@ -468,7 +468,7 @@ bool build_wide(const HostScene& sc, const std::vector<int>& leaf_node_of_slot, 
     uint32_t s24[3];
     for (int a = 0; a < 3; a++) {
       words[a] = fbits(origin[a]);
-      s24[a] = fbits(ldexpf(scale[a], 24));      // the record holds scale * 2^24 (device_core.hpp wide_node_test)
+      s24[a] = fbits(ldexpf(scale[a], 24));      // the record holds scale * 2^24 (device_wide.hpp wide_node_test)
       if (s24[a] & 0xffffu) return false;        // (a power of two: nothing below the upper half)
     }
     words[3] = (uint32_t)base | (((1u << w.n) - 1u) << 24) | (leafmask << 28);

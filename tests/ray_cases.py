@@ -1,4 +1,4 @@
-"""Seeded scenes and classes of adversarial rays for the closest-hit walks (device_core.hpp closest_hit_threaded, closest_hit_ordered,
+"""Seeded scenes and classes of adversarial rays for the closest-hit walks (device_walk.hpp closest_hit_threaded, closest_hit_ordered,
 closest_hit_wide and the lean build's wide_leaf_compute<false> / SignMask / persistent refill), and the table of (scene, class) pairs shared by
 tests/test_rays_host.py (no GPU: every pair through the host build of the walks, hk_hit, against the oracle's hit(), and the proof -- on the oracle
 and the inputs alone -- that every class reaches the edge it is named for) and tests/test_gpu_rays.py (the same pairs through dr_kat_hit and

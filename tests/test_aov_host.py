@@ -1,4 +1,4 @@
-"""First-hit AOV buffers without a GPU: the host build of the device function (tools/host_kernel.cpp hk_aov = device_core.hpp aov_first_hit
+"""First-hit AOV buffers without a GPU: the host build of the device function (tools/host_kernel.cpp hk_aov = device_aov.hpp aov_first_hit
 compiled for the CPU) against the oracle and numpy restatements, the C layout of dr_aov_buffers, the PFM helpers."""
 import ctypes
 import os

@@ -2,7 +2,7 @@
  * the lemma with a certificate: a ray with |a^| >= A for its triangle keeps every accepted hit inside the own bounds widened by the margin whose
    |d|-proportional part is scaled by 1e-4 / A (the adversarial sampler of test_margin_lemma.py, |d| from 1 to 30);
  * the per-view mask is conservative: camera rays built by camera_prepare / camera_finish through random points of padded boxes have |a^| >= a_star
-   when the box's triangle is certified, and land in a flagged tile when it is not (device_core.hpp cert_leaf, tools/host_kernel.cpp hk_cert_check)."""
+   when the box's triangle is certified, and land in a flagged tile when it is not (device_cert.hpp cert_leaf, tools/host_kernel.cpp hk_cert_check)."""
 import ctypes as C
 import os
 import sys

@@ -220,7 +220,7 @@ def test_a_nan_vertex_gives_no_table_or_a_sound_one(dr, tmp_path):
         assert hs.camera_entry_check(st, 64, 40, table[0], SEED, STRIDE, FRAMES)["outside"] == 0
 
 
-# the wrong rules (device_core.hpp ENTRY_MUTANT) and the case that catches each
+# the wrong rules (device_cert.hpp ENTRY_MUTANT) and the case that catches each
 def _caught(hs, st, W, H, mutant, frames=FRAMES):
     table = hs.camera_entry(st, W, H, mutant=mutant)
     assert table is not None

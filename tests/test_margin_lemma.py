@@ -1,5 +1,5 @@
 """The lemma behind wide_tree = 2: whenever hit_tri, in floats, accepts a hit at t_f, the EXACT point o + t_f d lies inside the triangle's own
-bounds widened by the ray's margin (device_core.hpp wide_ray_margin with the triangle's own |e1| |e2|, |e1| + |e2|, |v0| as the scene constants -- the least the
+bounds widened by the ray's margin (device_wide.hpp wide_ray_margin with the triangle's own |e1| |e2|, |e1| + |e2|, |v0| as the scene constants -- the least the
 scene's constants can be) -- so the tree over those bounds, every box test loosened by the margin, reaches every leaf whose hit the reference accepts.
 The kernel's own tri_hit and wide_ray_margin (compiled for the host) on adversarial pairs: rays that graze the triangle just above hit_tri's |a| >= 1e-4 cut-off,
 aimed at its edges and corners from far away; the worst cases are re-checked in exact rational arithmetic."""

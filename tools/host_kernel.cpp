@@ -122,7 +122,7 @@ void host_denoise_low(DnLaunch& L, bool filter, int nthreads, HostLow& planes) {
 
 extern "C" {
 
-// The restated uniform draws of device_core.hpp (Xorwow::uniform_double, uniform_pm1, outside_unit) against the plain expressions of
+// The restated uniform draws of device_rng.hpp (Xorwow::uniform_double, uniform_pm1, outside_unit) against the plain expressions of
 // curand_uniform_double (CUDA 11.2 curand_kernel.h) and of kernel.cu K:640-648: n random generator outputs plus the corners; returns mismatches.
 long long hk_check_uniform(long long n, unsigned long long seed) {
   long long bad = 0;
@@ -155,7 +155,7 @@ long long hk_check_uniform(long long n, unsigned long long seed) {
   return bad;
 }
 
-// The merged rejection loop (device_core.hpp rand_points_merged: candidates classified from 32 bits, the accepted one converted exactly from the
+// The merged rejection loop (device_rng.hpp rand_points_merged: candidates classified from 32 bits, the accepted one converted exactly from the
 // generator's state) against rand_in_unit_sphere / rand_in_unit_disk on n generator states: the same point, bit for bit, and the same state afterwards.
 // Returns mismatches; *max_d2_gap (optional) = the largest |d2~ - d2| seen over all candidates, to set beside the bound of the proof (2^-17).
 long long hk_check_reject(long long n, unsigned long long seed, double* max_d2_gap) {
@@ -187,11 +187,11 @@ long long hk_check_reject(long long n, unsigned long long seed, double* max_d2_g
   return bad;
 }
 
-// device_core.hpp wide_ray_margin, for the test of its lemma (tests/test_margin_lemma.py): the position margin of n rays for the scene constants (e, l, v)
+// device_wide.hpp wide_ray_margin, for the test of its lemma (tests/test_margin_lemma.py): the position margin of n rays for the scene constants (e, l, v)
 void hk_ray_margin(long long n, const float* o, const float* d, float e, float l, float v, float* out) {
   for (long long i = 0; i < n; i++) out[i] = wide_ray_margin(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), e, l, v);
 }
-// The camera rays' grazing certificate (device_core.hpp cert_leaf) of the scene's triangles for one view, as kernels_aux.hip
+// The camera rays' grazing certificate (device_cert.hpp cert_leaf) of the scene's triangles for one view, as kernels_aux.hip
 // cert_mask_kernel builds it, and a check of what it promises against the kernel's own camera rays (camera_ray: camera_prepare, the lens disk,
 // camera_finish).  n_samples times: a triangle, a random point X of its padded box (own bounds + 0.01), the pixel X projects to (+-1), a random
 // sample seed; a ray that enters that box (slab(), entry > -0.01, as K:484-488) must have |d . (e1 x e2)| >= a_star if the triangle is certified,
@@ -377,7 +377,7 @@ int hk_cert_levels(void* hv, const float* settings13, int W, int H, int cert_fac
 }
 // The camera rays' entry table of one view (option camera_entry) over the product's default tree, as kernels_aux.hip builds it -- the same
 // entry_leaf over the leaves in depth-first order, the same entry_tile per tile -- for the block columns bx % col_mod == col_rem.  codes_out (may be NULL):
-// the entry codes, a word per tile (local column * tile rows + row).  mutant: 0, or one of device_core.hpp's ENTRY_MUTANTs (a wrong rule on purpose).
+// the entry codes, a word per tile (local column * tile rows + row).  mutant: 0, or one of device_cert.hpp's ENTRY_MUTANTs (a wrong rule on purpose).
 // out[0] tiles, out[1] tiles without a leaf (ENTRY_NONE), out[2] tiles at the root, out[3] tiles at a leaf record, out[4] "every tile at the root",
 // out[5] leaves, out[8 + d] tiles whose entry lies d records below the root (d = 0 .. 17; ENTRY_NONE not counted).  Returns 0, -1 with hk_last_error,
 // or 1 when the view gives no table (fill_cert_view: a degenerate camera, a lens too wide for the focus plane) or the scene has no wide tree.
@@ -477,7 +477,7 @@ int hk_camera_entry_check(void* hv, const float* settings13, int W, int H, int c
   for (int k = 0; k < 4; k++) { out[k] = 0; for (int t = 0; t < nthreads; t++) out[k] += part[(size_t)t * 4 + k]; }
   return 0;
 }
-// slab() (device_core.hpp: the reference's box test, what hk_camera_entry_check lists leaves with) on n ray / box pairs: 1 entered, 0 not
+// slab() (device_intersect.hpp: the reference's box test, what hk_camera_entry_check lists leaves with) on n ray / box pairs: 1 entered, 0 not
 void hk_slab(long long n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit) {
   for (long long i = 0; i < n; i++) {
     const V3 dd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
@@ -517,7 +517,7 @@ int hk_wide_mu(void* hv, float* out3) {
   out3[0] = img.wide_mu.e; out3[1] = img.wide_mu.l; out3[2] = img.wide_mu.v;
   return img.wide_own_bounds;
 }
-// hit_tri (device_core.hpp tri_hit) on n ray / triangle pairs: t or -1
+// hit_tri (device_intersect.hpp tri_hit) on n ray / triangle pairs: t or -1
 void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* t) {
   for (long long i = 0; i < n; i++)
     t[i] = tri_hit(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), mk(v0[3 * i], v0[3 * i + 1], v0[3 * i + 2]),
@@ -680,7 +680,7 @@ int hk_render(void* hv, const float* settings13, int W, int H, float background,
   return 0;
 }
 
-// dr_render_aov on the host: device_core.hpp aov_first_hit for every pixel of the window (x0, y0, w, h) of the pixel grid, with the given traversal;
+// dr_render_aov on the host: device_aov.hpp aov_first_hit for every pixel of the window (x0, y0, w, h) of the pixel grid, with the given traversal;
 // the channels (null: not written) in dr_render_aov's layout.  Returns 0, or -1 with hk_last_error.
 int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int w, int h, int traversal, int nthreads, float* t, float* distance,
            float* depth, int32_t* object, int32_t* material, float* normal, float* uv, float* albedo, float* dir) {

@@ -15,7 +15,7 @@ _lib = None
 
 
 def build(force=False):
-    deps = _SOURCES + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))] + [os.path.join(_HERE, "host_kernel", "host_stubs.hpp")]
+    deps = _SOURCES + [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".hpp"))] + [os.path.join(_HERE, "host_kernel", f) for f in ("host_stubs.hpp", "host_prims.hpp")]
     if not force and os.path.exists(_SO) and all(os.path.getmtime(d) <= os.path.getmtime(_SO) for d in deps):
         return _SO
     cxx = "/opt/rocm/lib/llvm/bin/clang++"          # ext_vector_type (u32x4) is a clang extension
@@ -90,7 +90,7 @@ def lib():
 
 
 def slab(o, d, mn, mx):
-    """device_core.hpp slab() on n ray / box pairs (hk_slab): int32[n], 1 where the ray enters the box"""
+    """device_intersect.hpp slab() on n ray / box pairs (hk_slab): int32[n], 1 where the ray enters the box"""
     o, d, mn, mx = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, mn, mx))
     hit = np.zeros(o.shape[0], np.int32)
     lib().hk_slab(o.shape[0], o.ctypes.data, d.ctypes.data, mn.ctypes.data, mx.ctypes.data, hit.ctypes.data)
@@ -158,7 +158,7 @@ class Scene:
 
     def camera_entry(self, settings13, W, H, col_mod=1, col_rem=0, mutant=0):
         """The camera rays' entry table of a view on the host (hk_camera_entry): (int32 entry codes, a word per tile of the stripe, and a dict of counts),
-        or None when the view or the scene gives no table.  mutant: one of device_core.hpp's wrong rules (1 rect narrowed, 2 no lens term, 3 highest
+        or None when the view or the scene gives no table.  mutant: one of device_cert.hpp's wrong rules (1 rect narrowed, 2 no lens term, 3 highest
         rank off by one, 4 no entry for a tile with one leaf)."""
         st = np.ascontiguousarray(settings13, dtype=np.float32)
         div = int(st[11]) if np.isfinite(st[11]) and st[11] >= 1 else 1
@@ -217,7 +217,7 @@ class Scene:
                        "tiles_per_grade": [int(v) for v in out[8:16]], "rays_per_grade": [int(v) for v in out[16:24]]}
 
     def aov(self, settings13, W, H, window=None, traversal=2, nthreads=4):
-        """dr_render_aov on the host (device_core.hpp aov_first_hit): every channel of the window (x0, y0, w, h) of the pixel grid
+        """dr_render_aov on the host (device_aov.hpp aov_first_hit): every channel of the window (x0, y0, w, h) of the pixel grid
         (None: all of it) as a dict of arrays shaped like dogeray_amd.Context.render_aov's."""
         st = np.ascontiguousarray(settings13, dtype=np.float32)
         if window is None:

@@ -1,5 +1,5 @@
 // What dogeray_amd/csrc/device_core.hpp needs of <hip/hip_runtime.h> when it is compiled for the HOST (-DDR_HOST_BUILD, clang++ -x c++):
-// the function qualifiers, float4, the bit casts and an atomicAdd.  Test / bench infrastructure (tools/host_kernel.cpp); the product
+// the function qualifiers, float4, the bit casts and an atomicAdd (host_prims.hpp beside this file: the project's own primitives).  Test / bench infrastructure (tools/host_kernel.cpp); the product
 // library never sees this file and has no CPU path.
 #pragma once
 #include <cmath>

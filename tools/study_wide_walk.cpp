@@ -1,4 +1,4 @@
-// Host emulation of the wide walk (device_core.hpp wide_* functions, same arithmetic and stack discipline) against the
+// Host emulation of the wide walk (device_wide.hpp wide_* functions, same arithmetic and stack discipline) against the
 // threaded reference-order walk, on camera rays + two diffuse bounces: checks that hits are identical and prints visits per ray,
 // build time and tree statistics.  The folded node test is the kernel's own source (device_core.hpp compiled for the host, as in
 // tools/host_kernel.cpp), checked at every node against the plain decode-and-slab test it must cover.  Build from the repo root:
@@ -6,7 +6,7 @@
 //       dogeray_amd/csrc/linearise.cpp dogeray_amd/csrc/wide_builder.cpp dogeray_amd/csrc/rts_reader.cpp \
 //       dogeray_amd/csrc/bvh_builder.cpp dogeray_amd/csrc/capi_host.cpp -pthread && /tmp/widewalk scene.rts 20000 [tree_mode] [cert_factor]
 // cert_factor > 0 (with tree_mode 2): the camera rays are the kernel's own (camera_ray through a random pixel, lens and jitter included) and, in tiles the
-// view's grazing certificate clears (device_core.hpp cert_leaf with a_star = cert_factor * 1e-4), carry the certified margin.
+// view's grazing certificate clears (device_cert.hpp cert_leaf with a_star = cert_factor * 1e-4), carry the certified margin.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
