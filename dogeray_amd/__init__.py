@@ -188,6 +188,7 @@ _API = [
     ("dr_stats_cert_mask", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_cert_levels", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_camera_entry", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
+    ("dr_stats_sky_tiles", C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
@@ -604,6 +605,13 @@ class Context:
         if len(out):
             _check(lib().dr_stats_camera_entry(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
         return out
+
+    def sky_tiles(self):
+        """(sky tiles, geometry tiles) of the last launch (dr_stats_sky_tiles): the tiles sky_tiles_kernel rendered and the tiles left to the
+        persistent kernel; (0, 0) when the launch was not split (option "sky_tiles")."""
+        n_sky, n_geometry = C.c_int(), C.c_int()
+        _check(lib().dr_stats_sky_tiles(self._h, C.byref(n_sky), C.byref(n_geometry)))
+        return n_sky.value, n_geometry.value
 
     def wave_log(self, max_waves=16384):
         """(n, 16) uint64: begin, queue-empty, end stamps (100 MHz ticks) and iterations after the queue was empty, per wave of the

@@ -46,6 +46,7 @@ const Option OPTIONS[] = {
     {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, false},
     {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, false},
     {"camera_entry", /* (as above) */ &dr_context::camera_entry, 0, 1, 0, false},
+    {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 1, 0, false},
 };
 
 const Option* find_option(const std::string& name) {
@@ -72,7 +73,8 @@ int set_option(dr_context* c, const std::string& name, int v) {
       c->pipe_next = 0; c->pipe_groups = 0;
     }
   }
-  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels || o->member == &dr_context::camera_entry) {
+  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels || o->member == &dr_context::camera_entry ||
+           o->member == &dr_context::sky_tiles) {
     // frames submitted before the change are launched with the setting they were submitted under
     if (!c->pipe_pending.empty()) DR_TRY(pipeline_flush(c));
     c->cert_valid = false;
@@ -326,6 +328,18 @@ int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles) {
   const int n = c->cert_tiles < max ? c->cert_tiles : max;
   if (n > 0) HIP_TRY(hipMemcpy(out, c->cert_word, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (int t = 0; t < n; t++) out[t] >>= ENTRY_SHIFT;      // (arithmetic: ENTRY_NONE stays -1)
+  return DR_OK;
+}
+
+int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry) {
+  if (!c || !n_sky || !n_geometry) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n_sky = 0; *n_geometry = 0;
+  if (!c->sky_split_last || !c->sky_counts) return DR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  unsigned h[2] = {0, 0};
+  HIP_TRY(hipMemcpy(h, c->sky_counts, sizeof(h), hipMemcpyDeviceToHost));
+  *n_sky = (int)h[0]; *n_geometry = (int)h[1];
   return DR_OK;
 }
 

@@ -169,6 +169,17 @@ struct dr_context {
   int wide_leaves = 0;
   DevMem<uint32_t> entry_mm;               // scratch: the lowest and the highest rank per tile
   DevMem<uint32_t> cert_word;              // a word per tile: entry code << ENTRY_SHIFT | grade (RenderParams cert_level)
+  // sky tiles: a lean launch with an entry table hands the tiles of code ENTRY_NONE to sky_tiles_kernel and the rest of its order to the
+  // persistent kernel (context_render.cpp enqueue_frame).  The split is made on the launch's stream and kept while the words and the order it was
+  // made from are the same (sky_key: cert_gen, order in use, order_gen, tiles, regions -- sky_split_kernel takes 0.53 % of a 32-frame launch of the bench
+  // view, profiles/sky_tiles_ab.txt); tile_order / region_start above stay whole
+  int sky_tiles = 1;                       // option: 0 every tile goes through the persistent kernel
+  DevMem<int> launch_order, launch_region_start, sky_list;
+  DevMem<unsigned> sky_counts;             // [0] sky tiles, [1] geometry tiles of the last split
+  bool sky_split_last = false;             // the last launch was split (dr_stats_sky_tiles)
+  uint64_t cert_gen = 0;                   // computations of the tiles' words so far (cert_prepare)
+  uint64_t order_gen = 0;                  // computations of tile_order so far (launch_tile_feedback)
+  uint64_t sky_key[5] = {0, 0, 0, 0, 0}; bool sky_key_valid = false;      // what the launch's own pair and sky_list were split from
   // frame + accumulator
   DevMem<int32_t> frame;
   DevMem<int32_t> accum; int accW = 0, accH = 0;

@@ -96,6 +96,7 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
     CertView cv;
     c->cert_valid = false;
     c->cert_ok = c->entry_ok = false;
+    c->cert_gen++;
     // (the table asks nothing of the view's E: a scene without own bounds passes any)
     if (fill_cert_view(P, a_star, want_cert ? c->wide_mu.e : 1.0f, cv)) {
       if (c->cert_level.grow(cert_level_words(tiles), site.stream) != DR_OK || c->cert_word.grow((size_t)tiles, site.stream) != DR_OK ||
@@ -118,6 +119,32 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
     c->cert_valid = true;
   }
   if (c->cert_ok || c->entry_ok) { P.cert_level = c->cert_word; memcpy(P.wide_cert_k, c->cert_k, sizeof(P.wide_cert_k)); }
+}
+
+// Sky tiles (option sky_tiles): when the launch runs the lean build over a view with an entry table, the tiles no leaf can be seen from
+// are rendered by sky_tiles_kernel, in front of the persistent kernel on the same stream, and order / region_start become the launch's own pair
+// that holds the other tiles only (kept from launch to launch while the tiles' words and the order are the same).  The plan is still made from every tile (the number of geometry tiles stays on the device).  A pipelined launch
+// beside others is not split, nor one on another stream than the context's (the launch's own pair is one per context).
+bool sky_split(dr_context* c, const LaunchSite& site, const RenderParams& P, int tiles, const int*& order, const int*& region_start, unsigned* pcost) {
+  if (!c->sky_tiles || !c->entry_ok || !P.cert_level || site.hold_order || site.stream != c->stream || P.out_frame_stride != 0) return false;
+  if (P.max_depth <= 0 || !(P.spp_f > 0.0f)) return false;
+  if (!plan_sky_split(plan_persistent(persistent_cfg(c, site), (long long)tiles * P.batch, P.coop_steps, false, P.wave_log != nullptr))) return false;
+  // the split of the same words and the same order is the same arrays: made once, on this stream, and reused by the launches behind it (every launch
+  // that splits runs on this stream, so none reads the arrays while they are rewritten)
+  const uint64_t key[5] = {c->cert_gen, order ? 1u : 0u, order ? c->order_gen : 0u, (uint64_t)tiles, (uint64_t)P.regions};
+  const bool room = c->launch_order.n >= (size_t)tiles && c->sky_list.n >= (size_t)tiles && c->launch_region_start.p && c->sky_counts.p;
+  if (!(room && c->sky_key_valid && memcmp(c->sky_key, key, sizeof(key)) == 0)) {
+    c->sky_key_valid = false;
+    if (c->launch_order.grow((size_t)tiles, site.stream) != DR_OK || c->sky_list.grow((size_t)tiles, site.stream) != DR_OK ||
+        c->launch_region_start.grow(2 * MAX_REGIONS + 1, site.stream) != DR_OK || c->sky_counts.grow(2, site.stream) != DR_OK)
+      return false;
+    launch_sky_split(site.stream, order, region_start, P.region_start, P.cert_level, tiles, P.regions, c->launch_order, c->launch_region_start, c->sky_list, c->sky_counts);
+    memcpy(c->sky_key, key, sizeof(key));
+    c->sky_key_valid = true;
+  }
+  launch_sky_tiles(site.stream, P, c->sky_list, c->sky_counts, pcost);
+  order = c->launch_order; region_start = c->launch_region_start;
+  return true;
 }
 
 }  // namespace
@@ -143,7 +170,9 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
     } else feedback_buffers(c, site, P, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
     cert_prepare(c, site, P, tiles);
-    const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, order, c->region_start, pcost);
+    const int* launch_order = order; const int* launch_rstart = c->region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
+    c->sky_split_last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost);
+    const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, launch_order, launch_rstart, pcost);
     if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
     c->wave_log_waves = log_waves;
     // next launch's order from this launch's costs (stream-ordered, no host sync).  The view does not change between the frames of
@@ -153,12 +182,14 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
     if (pcost && (c->order_age < 2 || c->order_age % c->feedback_every == 0)) {
       const int split_limit = plan_split_limit(c->num_cus, c->occupancy, c->split_parts, c->split_waves);
       launch_tile_feedback(site.stream, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start, tiles, P.regions, c->heavy_factor, c->split_steps, split_limit);
+      c->order_gen++;
       c->order_args[0] = tiles; c->order_args[1] = P.regions; c->order_args[2] = c->heavy_factor; c->order_args[3] = c->split_steps; c->order_args[4] = split_limit;
       c->order_valid = true;
     }
     c->order_age++;
     return DR_OK;
   }
+  c->sky_split_last = false;
   launch_tile_kernel(site.stream, P, traversal_of(c), c->count != 0, c->occupancy);
   return DR_OK;
 }

@@ -1,0 +1,51 @@
+// Tiles that see nothing of the scene (entry code ENTRY_NONE in the view's entry table): every path of their pixels misses, so a frame
+// of such a pixel is spp camera rays and spp backgrounds -- no walk, no path pool.  sky_pixel is that frame, written with the functions the render
+// kernels run (render_pixel with a `closest` that always misses); sky_split_plain is the partition of a launch's tile order into the geometry tiles
+// the persistent kernel keeps and the sky tiles, as plain C++ (kernels_aux.hip sky_split_kernel computes the same arrays with one workgroup; the
+// host build exports this one, tests/test_sky_tiles_host.py).
+#pragma once
+#include "device_shade.hpp"
+#include "launch_plan.hpp"
+
+namespace dr {
+
+// a tile's word (entry code << ENTRY_SHIFT | grade, RenderParams cert_level) says that no leaf can be seen from the tile
+__host__ __device__ __forceinline__ bool sky_word(uint32_t word) { return ((int)word >> ENTRY_SHIFT) == ENTRY_NONE; }
+
+// What store_pixel adds for pixel (x, y) and frame `frame` of the launch when every sample's path misses (max_depth > 0: the first ray of a path
+// is always shaded)
+__device__ __forceinline__ void sky_pixel(const RenderParams& P, int x, int y, int frame, int& r, int& g, int& b) {
+  V3 color = mk(0, 0, 0);
+  Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int s = 0; (float)s < P.spp_f; ++s) {
+    Xorwow rng;
+    rng.init(sample_seed(P, x, y, s, frame));
+    Path path; path.atten = splat(1.0f);
+    camera_ray(P, x, y, rng, path.rayo, path.raydir);
+    color = color + shade_miss<false>(P, path, c);
+  }
+  r = f2i(color.x * 255 * P.scale); g = f2i(color.y * 255 * P.scale); b = f2i(color.z * 255 * P.scale);
+}
+
+// The split of a launch's order: order (null: the identity) and region_start in the persistent kernel's format (region r owns positions
+// [region_start[r], region_start[r + 1]) of the order, region_start[regions] = tiles); word = a word per tile.
+//   launch_order          the tiles that are not sky, in the order they had (a stable partition: every region keeps its heavy-first, then natural order)
+//   launch_region_start   2 * MAX_REGIONS + 1 ints: the starts of the compacted regions, [regions] = the geometry tiles; the split counts
+//                         [MAX_REGIONS + 1 + r] = 0
+//   sky_list              the sky tiles, ascending
+// Returns the number of sky tiles.
+inline int sky_split_plain(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order,
+                           int* launch_region_start, int* sky_list) {
+  int n_geometry = 0, n_sky = 0, r = 0;
+  for (int k = 0; k < 2 * MAX_REGIONS + 1; k++) launch_region_start[k] = 0;
+  for (int i = 0; i < tiles; i++) {
+    while (r <= regions && region_start[r] <= i) launch_region_start[r++] = n_geometry;
+    const int t = order ? order[i] : i;
+    if (!sky_word(word[t])) launch_order[n_geometry++] = t;
+    if (sky_word(word[i])) sky_list[n_sky++] = i;
+  }
+  while (r <= regions) launch_region_start[r++] = n_geometry;
+  return n_sky;
+}
+
+}  // namespace dr

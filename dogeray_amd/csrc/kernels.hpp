@@ -1,6 +1,6 @@
 // Launchers of the device code, one translation unit per family of kernels:
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
-//   kernels_aux.hip           tile-order feedback, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
+//   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
@@ -56,6 +56,13 @@ void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const Cer
 inline size_t entry_mm_words(int ntiles) { return 2 * (size_t)ntiles + 1; }
 void launch_camera_entry(hipStream_t stream, const DevUnit* wide, const uint32_t* leaf_rec, const uint32_t* range, int n_leaves, const CertView& cv,
                          uint32_t* mm, const uint32_t* level, uint32_t* word, int ntiles);
+// sky tiles (option sky_tiles; device_sky.hpp sky_split_plain describes the arrays): the split of a launch's order -- order / region_start as the
+// persistent kernel would take them (order null: the identity, regions from own_region_start, MAX_REGIONS + 1 ints on the host), word = the tiles' words --
+// into launch_order / launch_region_start for the persistent kernel and sky_list with counts ([0] sky tiles, [1] geometry tiles) for launch_sky_tiles,
+// which renders P.batch frames of the listed tiles (one wave per tile; pixel_cost non-null: their costs, 0)
+void launch_sky_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint32_t* word, int tiles, int regions,
+                      int* launch_order, int* launch_region_start, int* sky_list, unsigned* counts);
+void launch_sky_tiles(hipStream_t stream, const RenderParams& P, const int* sky_list, const unsigned* counts, unsigned* pixel_cost);
 // hist: the history plane (int32 per pixel at x * H + y; the divisor of pixel p is hist[p] + div, a divisor of 0 gives 0), or null: acc / div
 void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div);
 void launch_frame_add(hipStream_t stream, int32_t* acc, const int32_t* frame, size_t n);      // acc += frame (pipelined single frames)

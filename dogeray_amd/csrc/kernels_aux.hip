@@ -6,6 +6,7 @@
 #include "device_wide.hpp"
 #include "device_cert.hpp"
 #include "device_surface.hpp"
+#include "device_sky.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -155,6 +156,98 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const unsigned* __rest
     }
     placed0 += (unsigned)__popcll(b0); placed1 += (unsigned)__popcll(b1);
   });
+}
+
+// ---- sky tiles (option sky_tiles): the tiles of a lean launch whose entry code is ENTRY_NONE leave the persistent kernel's queue
+// One workgroup splits the launch's order (device_sky.hpp sky_split_plain says what comes out): wave w owns a contiguous range of the order's positions
+// -- and, for the sky list, of the tile numbering -- and walks it 64 at a time, twice: counting, then placing through ballots and prefix counts, as
+// tile_order_kernel places its light tiles.  own: the region starts of the identity order (order null).  counts: [0] sky tiles, [1] geometry tiles.
+struct SkyRegions { int start[MAX_REGIONS + 1]; };
+__global__ __launch_bounds__(1024) void sky_split_kernel(const int* __restrict__ order, const int* __restrict__ region_start, SkyRegions own,
+                                                          const uint32_t* __restrict__ word, int ntiles, int regions, int* __restrict__ launch_order,
+                                                          int* __restrict__ launch_region_start, int* __restrict__ sky_list, unsigned* __restrict__ counts) {
+  constexpr int WAVES = 16, GROUPS = 8;
+  __shared__ int rs[MAX_REGIONS + 1];
+  __shared__ unsigned geo_cnt[WAVES], sky_cnt[WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (tid <= MAX_REGIONS) {
+    int v = ntiles;
+    if (tid <= regions) {
+      if (order) v = region_start[tid];
+      else {
+#pragma unroll
+        for (int k = 0; k <= MAX_REGIONS; k++) if (tid == k) v = own.start[k];
+      }
+    }
+    rs[tid] = v;
+  }
+  if (tid > regions && tid < 2 * MAX_REGIONS + 1) launch_region_start[tid] = 0;      // (the split counts among them: a lean launch hands out no tile in parts)
+  __syncthreads();
+  const int per = ((ntiles + WAVES - 1) / WAVES + 63) & ~63;
+  const int w0 = w * per < ntiles ? w * per : ntiles, w1 = w0 + per < ntiles ? w0 + per : ntiles;
+  auto mbcnt = [](unsigned long long m) { return (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
+  // body(i, t, geometry, sky): position i of the order holds tile t, which is (not) kept; tile i is a sky tile
+  auto for_range = [&](auto&& body) {
+    for (int g0 = w0; g0 < w1; g0 += 64 * GROUPS) {
+      int t[GROUPS]; uint32_t wt[GROUPS], wi[GROUPS];
+#pragma unroll
+      for (int k = 0; k < GROUPS; k++) { const int i = g0 + 64 * k + lane; t[k] = i < w1 ? (order ? order[i] : i) : -1; }
+#pragma unroll
+      for (int k = 0; k < GROUPS; k++) {
+        const int i = g0 + 64 * k + lane;
+        wi[k] = i < w1 ? word[i] : 0u;
+        wt[k] = (unsigned)t[k] < (unsigned)ntiles ? word[t[k]] : 0u;
+      }
+#pragma unroll
+      for (int k = 0; k < GROUPS; k++) {
+        const int i = g0 + 64 * k + lane;
+        if (g0 + 64 * k < w1) body(i, t[k], i < w1 && !sky_word(wt[k]), i < w1 && sky_word(wi[k]));
+      }
+    }
+  };
+  {
+    unsigned ng = 0, ns = 0;
+    for_range([&](int, int, bool geometry, bool sky) { ng += (unsigned)__popcll(__ballot(geometry)); ns += (unsigned)__popcll(__ballot(sky)); });
+    if (lane == 0) { geo_cnt[w] = ng; sky_cnt[w] = ns; }
+  }
+  __syncthreads();
+  unsigned gbase = 0, sbase = 0, gtotal = 0, stotal = 0;
+  for (int k = 0; k < WAVES; k++) {
+    if (k < w) { gbase += geo_cnt[k]; sbase += sky_cnt[k]; }
+    gtotal += geo_cnt[k]; stotal += sky_cnt[k];
+  }
+  for_range([&](int i, int t, bool geometry, bool sky) {
+    const unsigned long long bg = __ballot(geometry), bs = __ballot(sky);
+    const unsigned p = gbase + mbcnt(bg);                    // geometry tiles in front of position i
+    if (i < w1)
+      for (int r = 0; r <= regions; r++) if (i == rs[r]) launch_region_start[r] = (int)p;
+    if (geometry) launch_order[p] = t;
+    if (sky) sky_list[sbase + mbcnt(bs)] = i;
+    gbase += (unsigned)__popcll(bg); sbase += (unsigned)__popcll(bs);
+  });
+  if (tid <= regions && rs[tid] >= ntiles) launch_region_start[tid] = (int)gtotal;      // (the end, and regions that start there)
+  if (tid == 0) { counts[0] = stotal; counts[1] = gtotal; }
+}
+// One wave per sky tile, lane l on pixel (l >> 3, l & 7) of it as in the render kernels: the launch's frames of the pixel summed in registers
+// (device_sky.hpp sky_pixel) and written once; the cost the persistent kernel records for such a pixel is 0 node steps.
+__global__ __launch_bounds__(256) void sky_tiles_kernel(RenderParams P, const int* __restrict__ sky_list, const unsigned* __restrict__ counts,
+                                                         unsigned* __restrict__ pixel_cost) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= (int)counts[0]) return;
+  const int tile = sky_list[i];
+  const int col = tile / P.gy, by = tile - col * P.gy;
+  const int x = (P.stripe_rem + col * P.stripe_mod) * 8 + (lane >> 3), y = by * 8 + (lane & 7);
+  int r = 0, g = 0, b = 0;
+  for (int frame = 0; frame < P.batch; frame++) {
+    int fr, fg, fb;
+    sky_pixel(P, x, y, frame, fr, fg, fb);
+    r += fr; g += fg; b += fb;
+  }
+  int32_t* px = P.out + ((size_t)x * (size_t)P.H + (size_t)y) * 3;
+  if (P.accumulate == 2) { atomicAdd(px + 0, r); atomicAdd(px + 1, g); atomicAdd(px + 2, b); }
+  else if (P.accumulate) { px[0] += r; px[1] += g; px[2] += b; }
+  else { px[0] = r; px[1] = g; px[2] = b; }
+  if (pixel_cost) pixel_cost[(size_t)tile * 64 + lane] = 0u;
 }
 
 // clamp(acc / divide_by, 0, 255) into row-major RGB8 (draw loop K:2281-2287)
@@ -477,6 +570,17 @@ void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsign
                           int heavy_factor, int split_steps, int split_limit) {
   hipLaunchKernelGGL(tile_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, pixel_cost, tile_cost, tiles);
   hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, tile_cost, tile_order, region_start, tiles, regions, heavy_factor, split_steps, split_limit);
+}
+void launch_sky_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint32_t* word, int tiles, int regions,
+                      int* launch_order, int* launch_region_start, int* sky_list, unsigned* counts) {
+  SkyRegions own;
+  for (int r = 0; r <= MAX_REGIONS; r++) own.start[r] = own_region_start[r];
+  hipLaunchKernelGGL(sky_split_kernel, dim3(1), dim3(1024), 0, stream, order, order ? region_start : nullptr, own, word, tiles, regions, launch_order,
+                     launch_region_start, sky_list, counts);
+}
+void launch_sky_tiles(hipStream_t stream, const RenderParams& P, const int* sky_list, const unsigned* counts, unsigned* pixel_cost) {
+  const int tiles = P.ncols * P.gy;
+  hipLaunchKernelGGL(sky_tiles_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, P, sky_list, counts, pixel_cost);
 }
 void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div) {
   const int n = W * H;

@@ -105,6 +105,11 @@ inline PersistentPlan plan_persistent(const PersistentCfg& cfg, long long work, 
   return p;
 }
 
+// Option sky_tiles: a launch may leave its sky tiles (entry code ENTRY_NONE) to a kernel of their own only in the lean build of the wide walk that adds
+// a batch into one buffer -- the counting build keeps every pixel (its counters are the bench's metric), the work-sharing build and the per-frame
+// stores are not split
+inline bool plan_sky_split(const PersistentPlan& p) { return p.build.wide && !p.build.count && !p.build.coop && !p.build.perframe; }
+
 // Tile queues of a launch of `tiles` tiles (batch_hint frames of them): one per XCD, or one
 inline int plan_regions(int tiles, int batch_hint, bool xcd_regions, bool short_one_queue, int tiles_per_wave, int num_cus) {
   int regions = xcd_regions ? MAX_REGIONS : 1;

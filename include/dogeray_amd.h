@@ -203,6 +203,10 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   that holds every leaf a camera ray of the tile can reach (dr_stats_camera_entry) -- instead of the root; a tile
  *                   that sees nothing of the scene walks nothing.  0 every ray starts at the root.  The same bits either way.  Used where the
  *                   certificate is (the lean and counting builds, a pixel's first sample), built and dropped with it, for any scene with a wide tree
+ *   "sky_tiles"     1 (default): a launch of the lean build over a view with an entry table renders the tiles no leaf can be seen from (entry code -1)
+ *                   in a kernel of their own -- one wave per tile, the launch's frames summed in registers, no walk and no path pool -- and hands the
+ *                   persistent kernel the other tiles only (dr_stats_sky_tiles); 0 every tile goes through the persistent kernel.
+ *                   The same bits either way.  Not used by the counting and work-sharing builds nor by pipelined launches
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)
@@ -610,6 +614,9 @@ int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tile
  * scene can be seen from the tile.  *n_tiles = 0 when no table is in use; otherwise the tiles, and the first min(max, n_tiles) codes are
  * copied to out. */
 int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles);
+/* The last launch's split (option sky_tiles): *n_sky = the tiles rendered by the sky kernel (entry code -1), *n_geometry = the tiles left to the
+ * persistent kernel; both 0 when the launch was not split. */
+int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry);
 
 /* Timeline of the last SHORT persistent-kernel launch (fewer than coop_tiles_per_wave tiles per wave: one frame, a thin stripe;
  * option "wave_log" = 1 before the launch): sixteen words per wave --

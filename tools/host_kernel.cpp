@@ -24,6 +24,7 @@
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
+#include "../dogeray_amd/csrc/device_sky.hpp"
 #include "../dogeray_amd/csrc/device_upscale.hpp"
 #include "../dogeray_amd/csrc/launch_plan.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
@@ -545,6 +546,39 @@ int hk_persistent_builds(int* out, int room) {
 }
 int hk_plan_regions(int tiles, int batch_hint, int xcd_regions, int short_one_queue, int tiles_per_wave, int num_cus) {
   return plan_regions(tiles, batch_hint, xcd_regions != 0, short_one_queue != 0, tiles_per_wave, num_cus);
+}
+// launch_plan.hpp plan_sky_split of the plan hk_persistent_plan returns for the same arguments
+int hk_plan_sky_split(const int* cfg6, long long work, int coop_steps, int per_frame, int wave_log_on) {
+  const PersistentCfg cfg = {cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0};
+  return plan_sky_split(plan_persistent(cfg, work, coop_steps, per_frame != 0, wave_log_on != 0)) ? 1 : 0;
+}
+// device_sky.hpp sky_split_plain: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of sky tiles
+int hk_sky_split(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order, int* launch_region_start, int* sky_list) {
+  return sky_split_plain(order, region_start, word, tiles, regions, launch_order, launch_region_start, sky_list);
+}
+// device_sky.hpp sky_pixel summed over `frames` frames of a launch (seed, stride: dr_render_accumulate's) for n pixels (xs, ys): out[3 * n].
+// Returns 0, or -1 with hk_last_error.
+int hk_sky_pixel(void* hv, const float* settings13, int W, int H, float background, uint64_t seed, uint64_t stride, int frames, int n, const int* xs, const int* ys,
+                 int32_t* out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || n < 0 || (n > 0 && (!xs || !ys || !out))) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, background, seed, 1, 0, P)) { hk_err = why; return -1; }
+  const DeviceImage& img = h->img;
+  if (P.backtex >= (int)img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
+  P.tex = img.tex.data(); P.texels = img.texels.data();
+  P.batch = frames; P.batch_seed_stride = stride;
+  for (int i = 0; i < n; i++) {
+    int r = 0, g = 0, b = 0;
+    for (int f = 0; f < frames; f++) {
+      int fr, fg, fb;
+      sky_pixel(P, xs[i], ys[i], f, fr, fg, fb);
+      r += fr; g += fg; b += fb;
+    }
+    out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
+  }
+  return 0;
 }
 int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 

@@ -85,6 +85,9 @@ def lib():
         L.hk_persistent_builds.argtypes = [C.c_void_p, C.c_int]
         L.hk_plan_regions.argtypes = [C.c_int] * 6
         L.hk_plan_split_limit.argtypes = [C.c_int] * 4
+        L.hk_plan_sky_split.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.c_int, C.c_int]
+        L.hk_sky_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hk_sky_pixel.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -185,6 +188,17 @@ class Scene:
                                        codes.ctypes.data, out.ctypes.data) != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return {"rays": int(out[0]), "entered": int(out[1]), "outside": int(out[2]), "entered_below_root": int(out[3])}
+
+    def sky_pixel(self, settings13, W, H, background, seed, stride, frames, xs, ys):
+        """device_sky.hpp sky_pixel for the pixels (xs, ys), summed over `frames` frames of a launch with dr_render_accumulate's seed and stride
+        (hk_sky_pixel): int32[n, 3], what those frames add to the accumulator when every path of the pixels misses."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        xs, ys = np.ascontiguousarray(xs, dtype=np.int32), np.ascontiguousarray(ys, dtype=np.int32)
+        out = np.zeros((len(xs), 3), np.int32)
+        if lib().hk_sky_pixel(self.h, st.ctypes.data, W, H, float(background), int(seed) & (2 ** 64 - 1), int(stride) & (2 ** 64 - 1), int(frames), len(xs),
+                              xs.ctypes.data, ys.ctypes.data, out.ctypes.data) != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return out
 
     def wide_leaves(self):
         """The default tree's leaves in depth-first order: (uint32 record per rank, float32 (n, 6) box per rank -- mn, mx of the record --, uint32 (records, 2)
@@ -458,6 +472,24 @@ def persistent_builds():
     out = np.zeros((n, 8), np.int32)
     assert lib().hk_persistent_builds(out.ctypes.data, n) == n
     return [tuple(int(v) for v in row) for row in out]
+
+
+def plan_sky_split(cfg, work, coop_steps, per_frame, wave_log_on):
+    """launch_plan.hpp plan_sky_split of persistent_plan's plan for the same arguments: may the launch leave its sky tiles to sky_tiles_kernel"""
+    return bool(lib().hk_plan_sky_split(_cfg(cfg), int(work), int(coop_steps), int(per_frame), int(wave_log_on)))
+
+
+def sky_split(order, region_start, word, regions):
+    """device_sky.hpp sky_split_plain (hk_sky_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], word uint32[tiles]
+    -> (launch_order int32[geometry tiles], launch_region_start int32[17], sky_list int32[sky tiles])."""
+    word = np.ascontiguousarray(word, dtype=np.uint32)
+    tiles = len(word)
+    rs = np.ascontiguousarray(region_start, dtype=np.int32)
+    o = np.ascontiguousarray(order, dtype=np.int32) if order is not None else None
+    lo, lrs, sky = np.zeros(max(1, tiles), np.int32), np.zeros(17, np.int32), np.zeros(max(1, tiles), np.int32)
+    n = lib().hk_sky_split(o.ctypes.data if o is not None else None, rs.ctypes.data, word.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data,
+                           sky.ctypes.data)
+    return lo[:tiles - n], lrs, sky[:n]
 
 
 def plan_regions(tiles, batch_hint, xcd_regions, short_one_queue, tiles_per_wave, num_cus):
