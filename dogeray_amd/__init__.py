@@ -79,6 +79,23 @@ AOV_CHANNELS = {"t": (np.float32, 1), "distance": (np.float32, 1), "depth": (np.
 ALL = tuple(AOV_CHANNELS)
 
 
+class DrRayBuffers(C.Structure):
+    """struct dr_ray_buffers (include/dogeray_amd.h dr_trace_rays): origin, dir (3 floats per ray), tmax (one, or NULL)."""
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("tmax", C.c_void_p)]
+
+
+class DrHitBuffers(C.Structure):
+    """struct dr_hit_buffers: one pointer per channel of dr_trace_rays (NULL: not computed)."""
+    _fields_ = [("t", C.c_void_p), ("object", C.c_void_p), ("material", C.c_void_p), ("distance", C.c_void_p), ("normal", C.c_void_p),
+                ("uv", C.c_void_p), ("albedo", C.c_void_p), ("occluded", C.c_void_p)]
+
+
+# the channels of Context.trace: name -> (dtype, components per ray); "occluded" is what any_hit=True returns
+TRACE_CHANNELS = {"t": (np.float32, 1), "object": (np.int32, 1), "material": (np.int32, 1), "distance": (np.float32, 1), "normal": (np.float32, 3),
+                  "uv": (np.float32, 2), "albedo": (np.float32, 3)}
+TRACE_CLOSEST, TRACE_ANY = 0, 1
+
+
 class DrDenoiseParams(C.Structure):
     """struct dr_denoise_params (include/dogeray_amd.h dr_accum_denoise)."""
     _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float),
@@ -167,6 +184,7 @@ _API = [
     ("dr_accum_unpack_stripes", C.c_int, [_VP, _VP, C.c_uint64, C.c_int, C.c_int, _VP]),
     ("dr_accum_reserve_pack", C.c_int, [_VP, C.c_int]),
     ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
+    ("dr_trace_rays", C.c_int, [_VP, C.c_int, C.c_int64, C.POINTER(DrRayBuffers), C.POINTER(DrHitBuffers), C.c_int]),
     ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
     ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_upscale_defaults", C.c_int, [C.POINTER(DrUpscaleParams)]),
@@ -184,6 +202,7 @@ _API = [
     ("dr_stats_reset", C.c_int, [_VP]),
     ("dr_stats_get", C.c_int, [_VP, C.POINTER(DrStats)]),
     ("dr_context_probe_trace", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dr_context_probe_rays", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, _VP, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("dr_stats_phase_counts", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int]),
     ("dr_stats_cert_mask", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_cert_levels", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
@@ -659,6 +678,18 @@ class Context:
         _check(lib().dr_context_probe_trace(self._h, _p(st), W, H, float(background), int(frame_seed) & (2 ** 64 - 1), int(frames), int(variant), C.byref(r), C.byref(n), C.byref(bad)))
         return r.value, int(n.value), int(bad.value)
 
+    def probe_rays(self, settings13, W, H, background, frame_seed):
+        """The rays the trace-only probe walks (dr_context_probe_rays): one frame's rays in wavefront order -> (o float32[n, 3], d float32[n, 3])."""
+        st = _f32(settings13)
+        n = C.c_uint64()
+        room = 2 * W * H              # one logging frame in the usual case; a frame with more rays than that is logged again with room for all
+        while True:
+            o, d = np.zeros((room, 3), np.float32), np.zeros((room, 3), np.float32)
+            _check(lib().dr_context_probe_rays(self._h, _p(st), W, H, float(background), int(frame_seed) & (2 ** 64 - 1), _p(o), _p(d), room, C.byref(n)))
+            if n.value <= room:
+                return o[:n.value].copy(), d[:n.value].copy()
+            room = n.value
+
     def probe_gather(self, hot_records=0, iters=2000):
         """Records/s of divergent, dependent 64-byte fetches from the resident wide array (bench.py roofline.gather)."""
         v = C.c_double()
@@ -706,6 +737,72 @@ class Context:
         cur = torch.cuda.current_stream(dev)
         lib_stream.wait_stream(cur)
         _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 1))
+        cur.wait_stream(lib_stream)
+        return out
+
+    # ---- ray queries (dr_trace_rays)
+    def trace(self, o, d, tmax=None, channels=("t", "object"), any_hit=False):
+        """Closest hit or occlusion of the caller's rays (include/dogeray_amd.h dr_trace_rays): o, d [n, 3] float32 (d as traced, not normalised),
+        tmax [n] or None (every ray 10000) -> a dict channel -> array [n] (t, distance: float32; object, material: int32, -1 on a miss) or [n, k]
+        (normal, albedo: 3; uv: 2); any_hit=True -> {"occluded": int32[n]}, 1 where anything is hit at t <= tmax.  numpy inputs take the host
+        path and return numpy arrays.  torch tensors on this context's GPU (float32, contiguous) take the device path and return torch tensors,
+        written on the library's stream, which waits for torch's current stream first; torch's current stream waits for it afterwards.  Mixed or
+        wrongly shaped inputs raise before anything is launched."""
+        channels = ("occluded",) if any_hit else tuple(channels)
+        for k in channels:
+            if k != "occluded" and k not in TRACE_CHANNELS:
+                raise ValueError("unknown trace channel %r (known: %s)" % (k, ", ".join(TRACE_CHANNELS)))
+        if not any_hit and "occluded" in channels:
+            raise ValueError("channel 'occluded' is what any_hit=True returns")
+        if not channels:
+            raise ValueError("no channel asked for")
+        spec = lambda k: (np.int32, 1) if k == "occluded" else TRACE_CHANNELS[k]
+        given = [a for a in (o, d, tmax) if a is not None]
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
+        rays, hits = DrRayBuffers(), DrHitBuffers()
+        mode = TRACE_ANY if any_hit else TRACE_CLOSEST
+        if not any(is_torch):
+            o, d = _f32(o), _f32(d)
+            n = o.shape[0] if o.ndim == 2 else -1
+            if o.shape != (n, 3) or d.shape != (n, 3):
+                raise ValueError("o and d must both be [n, 3]")
+            if tmax is not None:
+                tmax = _f32(tmax)
+                if tmax.shape != (n,):
+                    raise ValueError("tmax must be [n]")
+            out = {k: np.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=spec(k)[0]) for k in channels}
+            rays.origin, rays.dir, rays.tmax = o.ctypes.data, d.ctypes.data, (tmax.ctypes.data if tmax is not None else None)
+            for k, a in out.items():
+                setattr(hits, k, a.ctypes.data)
+            _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), 0))
+            return out
+        if not all(is_torch):
+            raise TypeError("o, d and tmax must all be numpy arrays or all torch tensors")
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        for name, a in (("o", o), ("d", d), ("tmax", tmax)):
+            if a is None:
+                continue
+            if a.device != dev:
+                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
+            if a.dtype != torch.float32:
+                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n = o.shape[0] if o.dim() == 2 else -1
+        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
+            raise ValueError("o and d must both be [n, 3]")
+        if tmax is not None and tuple(tmax.shape) != (n,):
+            raise ValueError("tmax must be [n]")
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=tdt[spec(k)[0]], device=dev) for k in channels}
+        rays.origin, rays.dir, rays.tmax = o.data_ptr(), d.data_ptr(), (tmax.data_ptr() if tmax is not None else None)
+        for k, a in out.items():
+            setattr(hits, k, a.data_ptr())
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), 1))
         cur.wait_stream(lib_stream)
         return out
 

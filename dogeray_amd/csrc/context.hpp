@@ -4,6 +4,7 @@
 //   context_render.cpp     per-launch constants, cost feedback, grazing certificate, the launches of dr_render_frame / dr_render_accumulate*
 //   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
+//   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
 //   context_probe.cpp      measurement probes and known-answer hooks
 // Host only, no kernels: kernels.hpp declares their launchers.
 #pragma once
@@ -116,6 +117,12 @@ struct dr_context {
   DevMem<int32_t> slot_to_orig_dev;        // the same map on the device: uploaded by the first dr_render_aov after a scene upload
   // dr_render_aov with host pointers: the channels are written here, then downloaded
   DevMem<uint8_t> aov_staging;
+  // dr_trace_rays: the per-ray {t, slot} words between the trace kernel and the surface pass, the persistent kernel's cursor, and the staging of host
+  // rays and results -- all made by the first call that needs them (a context that never traces allocates nothing)
+  DevMem<uint32_t> trace_hit;
+  DevMem<unsigned> trace_cursor;
+  DevMem<uint8_t> trace_staging;
+  int trace_kernel = 0;                    // option (private, for the tests): 0 plan_trace decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
   // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
   // guides' key (settings13, W, H, scene generation), and the staging of host outputs
   DevMem<float> dn_planes;

@@ -54,20 +54,17 @@ int dr_context_probe_gather(dr_context* c, uint32_t hot_records, int iters, doub
   return DR_OK;
 }
 
-int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, int frames, int variant,
-                           double* rays_per_s, uint64_t* n_rays, uint64_t* mismatches) {
-  if (!c || !settings13 || !rays_per_s || !n_rays || !mismatches || frames < 1 || variant < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
-  if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the trace probe needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+// The rays of ONE frame, as a per-bounce wavefront would hold them: the counting build writes every ray a path starts to slot bounce * pixels + pixel (tile
+// order); empty slots (paths that had ended) are squeezed out on the host.  packed: 8 floats per ray -- origin, pad, direction, pad.  Resets the accumulator.
+static int log_frame_rays(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, size_t max_rays, std::vector<float>& packed) {
   HIP_TRY(hipSetDevice(c->device));
   DR_TRY(dr_accum_reset(c, W, H));
-  // 1. the rays of ONE frame, as a per-bounce wavefront would hold them: the counting build writes every ray a path starts to slot bounce * pixels + pixel (tile
-  // order); empty slots (paths that had ended) are squeezed out on the host; `frames` copies of the list make the probe's launch long enough to time
   RenderParams Pv;
   DR_TRY(make_params(c, c->own_site(), settings13, W, H, background, frame_seed, Pv, 1));
   const size_t npix = (size_t)Pv.ncols * Pv.gy * 64;
   const size_t slots = npix * (size_t)(Pv.max_depth > 0 ? Pv.max_depth : 1);
-  if (slots * (size_t)frames > 0x7fffffffull) { set_error("too many rays"); return DR_ERR_INVALID; }
-  DevMem<float> raw; DevMem<float> log; DevMem<unsigned> cursor; DevMem<unsigned> out, ref;
+  if (slots > max_rays) { set_error("too many rays"); return DR_ERR_INVALID; }
+  DevMem<float> raw;
   DR_TRY(raw.alloc(slots * 8));
   HIP_TRY(hipMemset(raw.p, 0, slots * 8 * sizeof(float)));
   const bool was_counting = c->count;
@@ -79,20 +76,31 @@ int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int
   const unsigned long long off[2] = {0ull, 0ull};
   HIP_TRY(hipMemcpy(c->counters + STAT_LOG_PTR, off, sizeof(off), hipMemcpyHostToDevice));
   if (rc != DR_OK) return rc;
-  std::vector<float> host(slots * 8), packed;
+  std::vector<float> host(slots * 8);
   DR_TRY(raw.get(host.data(), host.size()));
+  packed.clear();
   packed.reserve(host.size() / 2);
   for (size_t k = 0; k < slots; k++) {
     const float* r = &host[k * 8];
     if (r[4] != 0.0f || r[5] != 0.0f || r[6] != 0.0f || r[4] != r[4]) packed.insert(packed.end(), r, r + 8);      // a direction was written
   }
+  return DR_OK;
+}
+
+int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, int frames, int variant,
+                           double* rays_per_s, uint64_t* n_rays, uint64_t* mismatches) {
+  if (!c || !settings13 || !rays_per_s || !n_rays || !mismatches || frames < 1 || variant < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the trace probe needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+  // 1. the rays of one frame in wavefront order (log_frame_rays); `frames` copies of the list make the probe's launch long enough to time
+  std::vector<float> packed;
+  DR_TRY(log_frame_rays(c, settings13, W, H, background, frame_seed, 0x7fffffffull / (size_t)frames, packed));
+  DevMem<float> log; DevMem<unsigned> cursor; DevMem<unsigned> out, ref;
   const size_t per_frame = packed.size() / 8;
   const unsigned n = (unsigned)(per_frame * (size_t)frames);
   *n_rays = per_frame;
   if (n == 0) { *rays_per_s = 0; *mismatches = 0; return DR_OK; }
   DR_TRY(log.alloc((size_t)n * 8));
   for (int f = 0; f < frames; f++) HIP_TRY(hipMemcpy(log.p + (size_t)f * per_frame * 8, packed.data(), per_frame * 8 * sizeof(float), hipMemcpyHostToDevice));
-  std::vector<float>().swap(host);
   DR_TRY(cursor.alloc(1)); DR_TRY(out.alloc((size_t)n * 2)); DR_TRY(ref.alloc((size_t)n * 2));
   RenderParams P;
   memset(&P, 0, sizeof(P));
@@ -120,6 +128,18 @@ int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int
   uint64_t bad = 0;
   for (size_t i = 0; i < a.size(); i++) bad += a[i] != b[i];
   *mismatches = bad;
+  return DR_OK;
+}
+
+int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, float* origin, float* dir,
+                          uint64_t capacity, uint64_t* n_rays) {
+  if (!c || !settings13 || !n_rays || (capacity > 0 && (!origin || !dir))) { set_error("bad argument"); return DR_ERR_INVALID; }
+  if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the ray log needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+  std::vector<float> packed;
+  DR_TRY(log_frame_rays(c, settings13, W, H, background, frame_seed, 0x7fffffffull, packed));
+  const size_t n = packed.size() / 8;
+  *n_rays = n;
+  for (size_t i = 0; i < n && i < capacity; i++) { memcpy(origin + 3 * i, &packed[8 * i], 12); memcpy(dir + 3 * i, &packed[8 * i + 4], 12); }
   return DR_OK;
 }
 

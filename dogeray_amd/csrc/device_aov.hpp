@@ -59,4 +59,41 @@ __device__ __forceinline__ AovHit aov_first_hit(const RenderParams& P, const Clo
   return a;
 }
 
+// The same for a caller's ray (dr_trace_rays): what shade_prepare forms at the hit (t, slot) of the ray (o, d), with the meaning, the miss values and the
+// arithmetic of aov_first_hit's fields of the same name; the origin is the ray's own, not the camera.  depth is a pinhole's: +inf here.  A sibling of
+// aov_first_hit, which stays as it is (the AOV kernel's code does not move).
+__device__ __forceinline__ AovHit ray_surface(const RenderParams& P, V3 o, V3 d, float t, int slot) {
+  AovHit a;
+  a.dir = d;
+  a.t = t;
+  const float inf = __builtin_inff();
+  a.slot = -1; a.distance = inf; a.depth = inf; a.mat = -1;
+  a.normal = mk(0, 0, 0); a.u = 0; a.v = 0; a.albedo = mk(0, 0, 0);
+  if (!(t > 0.0f) || slot < 0) { a.t = -1.0f; return a; }
+  a.slot = slot;
+  a.distance = t * length(d);
+  const V3 hitpoint = o + splat(t) * d;                           // K:806
+  const float4* pp = reinterpret_cast<const float4*>(P.prims + slot);
+  const float4* sp = reinterpret_cast<const float4*>(P.shade + slot);
+  const float4 pA = pp[0], pB = pp[1], pC = pp[2];
+  const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3], s4 = sp[4], s5 = sp[5], s6 = sp[6];
+  V3 texco;
+  V3 N = surface_normal(pA, pB, pC, s0, s1, s2, s3, s4, s6, o, d, hitpoint, texco);
+  a.normal = dot(d, N) < 0 ? N : N * splat(-1.0f);
+  a.u = texco.x; a.v = texco.y;
+  const V3 col = mk(s4.z, s4.w, s5.x);
+  a.mat = __float_as_int(s5.w);
+  const int texnum = __float_as_int(s6.x), flags = __float_as_int(s6.z);
+  a.albedo = col;
+  Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (texnum >= 0) {
+    a.albedo = rgb_of(tex_fetch<false>(P.tex, P.texels, texnum, texco.x, -texco.y + 1, c));
+  } else if (flags & 2) {                                         // checker K:776-784
+    const float u2 = __builtin_floorf(texco.x * 10), v2 = __builtin_floorf(texco.y * 10);
+    const float yes = u2 + v2;
+    a.albedo = (__builtin_fmodf(yes, 2.0f) == 0) ? splat(0.8f) : col;
+  }
+  return a;
+}
+
 }  // namespace dr

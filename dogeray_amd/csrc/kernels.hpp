@@ -2,6 +2,7 @@
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
 //   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
+//   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
@@ -92,6 +93,22 @@ struct AovLaunch {
   float* normal; float* uv; float* albedo; float* dir;
 };
 void launch_aov(hipStream_t stream, const RenderParams& P, int traversal, const AovLaunch& A);
+
+// kernels_trace.hip: n caller rays (origin / dir 3 floats per ray, tmax one or null: every ray 10000) and what to write per ray (null: not written).
+// The trace kernel writes t (-1: miss), object (slot_to_orig of the slot, -1: miss), occluded (1 / 0) and hit -- {t bits, slot}, miss {-1, -1}: what
+// the surface pass reads --; launch_trace_surface maps (origin, dir, hit) to distance, material, normal, uv, albedo (dr_render_aov's channels)
+struct TraceLaunch {
+  const float* origin; const float* dir; const float* tmax;
+  unsigned n;
+  const int32_t* slot_to_orig;
+  float* t; int32_t* object; int32_t* occluded;
+  uint32_t* hit;                  // two words per ray
+  unsigned* cursor;               // persistent kernel: the ray list's cursor, zeroed on the launch's stream by the caller
+  float* distance; int32_t* material; float* normal; float* uv; float* albedo;
+};
+// any: DR_TRACE_ANY; plan: plan_trace's (launch_plan.hpp).  n > 0.
+void launch_trace(hipStream_t stream, const RenderParams& P, const TracePlan& plan, bool any, const TraceLaunch& T);
+void launch_trace_surface(hipStream_t stream, const RenderParams& P, const TraceLaunch& T);
 
 // The accumulator stages: their launch structs (DnLaunch, UpLaunch, RpLaunch, MoLaunch) are in device_launch.h, without HIP, because the per-pixel
 // bodies of the device_*.hpp headers and the host build take them too

@@ -126,6 +126,37 @@ inline int plan_split_limit(int num_cus, int occupancy, int split_parts, int spl
   return split_parts > 1 ? (int)((long long)num_cus * (occupancy >= 5 ? 5 : 4) * 4 * split_waves / (100 * split_parts)) : 0;
 }
 
+// ---- dr_trace_rays (kernels_trace.hip): which kernel walks a list of caller rays, and with what grid
+// The persistent kernel's parameters are those of the trace-only probe's best variant (profiles/r4_j_trace_only_probe.txt, variant 2: six waves per
+// SIMD, refill once 8 lanes are free, leaf steps for 20 lanes: 5.65 Grays/s against 4.91 for one ray per lane); it exists for the wide walk only.
+// TRACE_PERSISTENT_MIN_RAYS is the measured cross-over (profiles/trace_rays_rate.txt, part c, a frame's rays of the bench scene in wavefront order):
+// one ray per lane is faster up to 16.8 M rays (x 0.63 at 262 144, x 0.83 at 4.2 M, x 0.98 at 16.8 M), the persistent kernel from 49.3 M on
+// (x 1.07, x 1.09 at 65.7 M; any-hit the same within 0.02); 2^25 lies between the two, near their geometric mean.  A grid of one-ray-per-lane
+// workgroups refills itself, workgroup by workgroup; the persistent waves' refill rounds pay only once the list is long enough for its tail to matter.
+enum { TRACE_KERNEL_PLAIN = 0, TRACE_KERNEL_PERSISTENT = 1 };
+enum { TRACE_FORCE_NONE = 0, TRACE_FORCE_PLAIN = 1, TRACE_FORCE_PERSISTENT = 2 };      // option "trace_kernel"
+constexpr int TRACE_OCC = 6, TRACE_REFILL_MIN = 8, TRACE_PARK = 20;
+constexpr int TRACE_CHUNK = 128;                          // rays a wave takes from the list per atomic
+constexpr long long TRACE_PERSISTENT_MIN_RAYS = 1 << 25;
+struct TracePlan {
+  int kernel;               // TRACE_KERNEL_*
+  int traversal;            // the walk really used: a scene without a wide tree walks the threaded links
+  int blocks;               // workgroups of 256 threads
+};
+// n > 0 rays; traversal: the context's; force: option "trace_kernel" (the persistent kernel cannot be forced where it does not exist)
+inline TracePlan plan_trace(long long n, int traversal, bool has_wide, int num_cus, int force) {
+  TracePlan p;
+  p.traversal = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
+  const bool can = p.traversal == DR_TRAVERSAL_WIDE;
+  const bool persistent = can && (force == TRACE_FORCE_PERSISTENT || (force != TRACE_FORCE_PLAIN && n >= TRACE_PERSISTENT_MIN_RAYS));
+  p.kernel = persistent ? TRACE_KERNEL_PERSISTENT : TRACE_KERNEL_PLAIN;
+  if (persistent) {       // no more waves than chunks
+    const long long full = (long long)num_cus * TRACE_OCC, need = (n + 4 * TRACE_CHUNK - 1) / (4 * TRACE_CHUNK);
+    p.blocks = (int)(need < full ? need : full);
+  } else p.blocks = (int)((n + 255) / 256);
+  return p;
+}
+
 // The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
 inline void order_geometry(const RenderParams& P, float out[5]) {
   out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;

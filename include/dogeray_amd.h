@@ -217,6 +217,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   accumulator changes; dr_render_accumulate then runs through the pipeline
  *   "denoise_variance" 1: while the accumulator has a second-moment plane, dr_accum_denoise's variance pre-pass takes the temporal variance of pixels
  *                   with four samples or more from it (SVGF's rule; see dr_accum_error below); 0 (default): the spatial estimate everywhere, the bits as before
+ *   "trace_kernel"  (private, for the tests) which kernel dr_trace_rays runs: 0 (default) the launch plan decides by the ray count, 1 the one-ray-per-lane
+ *                   kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -347,6 +349,46 @@ typedef struct dr_aov_buffers {
  * upload copies the slot -> object map to the device. */
 int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
                   int device_pointers);
+
+/* ------------------------------------------------------------------ ray queries --------- */
+/* Closest hit and occlusion on the CALLER's rays -- line of sight, ambient occlusion, baking, picking along arbitrary rays, a tensor of rays in a
+ * learning loop, shadow rays: what rtcIntersect / rtcOccluded are elsewhere.  Rays are three arrays; ray i is origin[3i..], dir[3i..], tmax[i].
+ *
+ * DR_TRACE_CLOSEST.  The answer for ray i is hit()'s own answer (K:468-512) on the resident scene if its t <= min(tmax_i, 10000), else a miss -- for
+ * every ray, without exception.  A hit at exactly t == tmax_i is kept; a NaN tmax, or one <= 0, is a miss.  The channels (NULL: not computed) have the
+ * meaning, the miss values and the bit patterns of dr_render_aov's channels of the same name -- t -1, object -1, material -1, distance +inf, normal /
+ * uv / albedo 0 -- with the ray's own origin in place of the camera.
+ *   tmax decides at the end of the walk; it does not prune the walk.  hit() with its running best started at (tmax, no slot) would skip every box
+ *   entered behind tmax, and that is the same answer only while no leaf's computed box entry exceeds the computed t of the primitive inside it.  It
+ *   does at coordinates around 2^20 and for a few accepted hits of grazing rays and sliver triangles (a few rays in a thousand of the adversarial
+ *   classes of tests/ray_cases.py): there the pruned walk reports a miss in front of a hit at t <= tmax_i.  This call does not.
+ * DR_TRACE_ANY.  occluded[i] = 1 exactly when the closest-hit query above would return a hit, else 0; the walk stops as soon as that is known (it
+ * holds a primitive at t <= tmax_i), and which primitive that was is not exposed: every channel other than `occluded` must be NULL (DR_ERR_INVALID
+ * otherwise).  In closest mode a non-NULL `occluded` is DR_ERR_INVALID.
+ *
+ * device_pointers = 0: host buffers, the call returns when they are filled; 1: every pointer is device memory on this context's GPU, the work is
+ * queued on dr_context_stream and the call returns at once (dr_render_aov's convention).  Ordered behind the frames submitted before it; changes
+ * neither the accumulator, nor dr_stats, the stripe or any option.  Works with every traversal (dr_context_set_traversal; a scene without a wide
+ * tree walks the threaded links).  DR_ERR_INVALID: no scene, n < 0 or n >= 2^31, a null origin or dir, no output channel, a mode other than the
+ * two.  n == 0 is DR_OK and launches nothing.  The per-ray scratch the call needs belongs to the context, grows on demand and goes with
+ * dr_context_destroy; a context that never traces allocates nothing. */
+enum { DR_TRACE_CLOSEST = 0, DR_TRACE_ANY = 1 };
+typedef struct dr_ray_buffers {
+  const float* origin;   /* n * 3 */
+  const float* dir;      /* n * 3, as traced: not normalised, t is in units of |dir| like hit()'s */
+  const float* tmax;     /* n, or NULL: every ray hit()'s own cap (10000) */
+} dr_ray_buffers;
+typedef struct dr_hit_buffers {   /* NULL: not computed */
+  float* t;
+  int32_t* object;
+  int32_t* material;
+  float* distance;
+  float* normal;         /* n * 3 */
+  float* uv;             /* n * 2 */
+  float* albedo;         /* n * 3 */
+  int32_t* occluded;     /* DR_TRACE_ANY only: 1 / 0 */
+} dr_hit_buffers;
+int dr_trace_rays(dr_context* c, int mode, int64_t n, const dr_ray_buffers* rays, const dr_hit_buffers* hits, int device_pointers);
 
 /* ------------------------------------------------------------------ denoiser ------------ */
 /* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by
@@ -653,6 +695,11 @@ int dr_context_probe_frame_add(dr_context* c, int iters, double* plain_ms, doubl
  * timed (best of three).  *n_rays = rays of the frame; *mismatches = results that differ from the one-ray-per-lane walk (t bits or slot). */
 int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, int frames, int variant,
                            double* rays_per_s, uint64_t* n_rays, uint64_t* mismatches);
+/* Measurement aid: the rays that probe walks -- one frame's rays in wavefront order (bounce by bounce, pixels in tile order), as the counting build logs
+ * them -- for a caller who wants to send them through dr_trace_rays (tools/trace_rate.py).  origin / dir: room for `capacity` rays of 3 floats each;
+ * *n_rays: the rays of the frame (call with capacity 0 to size the buffers).  Resets the accumulator to W x H, as the probe does. */
+int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, float* origin, float* dir,
+                          uint64_t capacity, uint64_t* n_rays);
 
 /* ------------------------------------------------------------------ known-answer hooks -- */
 /* Run single device functions on caller data (host pointers), for parity tests. */

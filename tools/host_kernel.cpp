@@ -21,6 +21,7 @@
 
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
+#include "../dogeray_amd/csrc/device_trace.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
@@ -642,6 +643,80 @@ int hk_hit(void* hv, int traversal, int tree, long long n, const float* o, const
   }
   return 0;
 }
+// dr_trace_rays on the host: the walks of device_trace.hpp (trace_threaded, trace_ordered, trace_wide through trace_ray) on n caller rays, traversal and
+// tree as hk_hit's (a scene without a wide tree takes the threaded walk for traversal 2).  mode 0 (DR_TRACE_CLOSEST): t (-1: miss), idx -- the ORIGINAL
+// object index, -1 on a miss: dr_trace_rays' `object` --, slot (may be NULL): the hit's slot for hk_ray_surface; mode 1 (DR_TRACE_ANY): occluded 1 / 0.
+// tmax NULL: every ray 10000.  visits (may be NULL): boxes tested per ray (the counting build's V).  Returns 0, or -1 with hk_last_error.
+int hk_trace(void* hv, int traversal, int tree, int mode, long long n, const float* o, const float* d, const float* tmax, float* t, int32_t* idx,
+             int32_t* occluded, int32_t* slot, int32_t* visits) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n < 0 || traversal < 0 || traversal > 2 || (tree != 1 && tree != 2) || (mode != DR_TRACE_CLOSEST && mode != DR_TRACE_ANY) ||
+      (n > 0 && (!o || !d || (mode == DR_TRACE_CLOSEST ? (!t || !idx) : !occluded)))) { hk_err = "bad argument"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
+  P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
+  P.pairs = img.pairs.data(); P.prims = img.prims.data();
+  std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
+  const int walk = plan_trace(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, TRACE_FORCE_PLAIN).traversal;
+  for (long long i = 0; i < n; i++) {
+    const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    const float cap = tmax ? tmax[i] : 10000.0f;
+    Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+    Hit hit;
+    if (mode == DR_TRACE_ANY) {
+      if (walk == DR_TRAVERSAL_WIDE) hit = trace_ray<DR_TRAVERSAL_WIDE, true, true>(P, ro, rd, cap, c, stack.data());
+      else if (walk == DR_TRAVERSAL_ORDERED) hit = trace_ray<DR_TRAVERSAL_ORDERED, true, true>(P, ro, rd, cap, c, stack.data());
+      else hit = trace_ray<DR_TRAVERSAL_THREADED, true, true>(P, ro, rd, cap, c, stack.data());
+      occluded[i] = hit.slot >= 0 ? 1 : 0;
+    } else {
+      if (walk == DR_TRAVERSAL_WIDE) hit = trace_ray<DR_TRAVERSAL_WIDE, true, false>(P, ro, rd, cap, c, stack.data());
+      else if (walk == DR_TRAVERSAL_ORDERED) hit = trace_ray<DR_TRAVERSAL_ORDERED, true, false>(P, ro, rd, cap, c, stack.data());
+      else hit = trace_ray<DR_TRAVERSAL_THREADED, true, false>(P, ro, rd, cap, c, stack.data());
+      t[i] = hit.t;
+      idx[i] = hit.slot >= 0 ? img.slot_to_orig[(size_t)hit.slot] : -1;
+      if (slot) slot[i] = hit.slot;
+    }
+    if (visits) visits[i] = (int32_t)c.V;
+  }
+  return 0;
+}
+// dr_trace_rays' surface pass on the host: device_aov.hpp ray_surface on n rays and their hits (t, slot: hk_trace's, of the same tree); the channels
+// (null: not written) as dr_trace_rays writes them.  Returns 0, or -1 with hk_last_error.
+int hk_ray_surface(void* hv, int tree, long long n, const float* o, const float* d, const float* t, const int32_t* slot, int32_t* material, float* distance,
+                   float* normal, float* uv, float* albedo) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n < 0 || (tree != 1 && tree != 2) || (n > 0 && (!o || !d || !t || !slot))) { hk_err = "bad argument"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
+  for (long long i = 0; i < n; i++) {
+    if (slot[i] >= (int32_t)img.prims.size()) { hk_err = "slot outside the scene"; return -1; }
+    const AovHit a = ray_surface(P, mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), t[i], slot[i]);
+    if (material) material[i] = a.mat;
+    if (distance) distance[i] = a.distance;
+    if (normal) { normal[3 * i] = a.normal.x; normal[3 * i + 1] = a.normal.y; normal[3 * i + 2] = a.normal.z; }
+    if (uv) { uv[2 * i] = a.u; uv[2 * i + 1] = a.v; }
+    if (albedo) { albedo[3 * i] = a.albedo.x; albedo[3 * i + 1] = a.albedo.y; albedo[3 * i + 2] = a.albedo.z; }
+  }
+  return 0;
+}
+// launch_plan.hpp plan_trace: out3 = kernel (TRACE_KERNEL_*), the traversal really walked, workgroups
+void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
+  const TracePlan p = plan_trace(n, traversal, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
+}
+long long hk_trace_persistent_min_rays() { return TRACE_PERSISTENT_MIN_RAYS; }
 // what dr_context_get_option reports for the image of `tree` (1 / 2, as hk_hit): out3 = wide_depth (0: no wide tree), wide_own_bounds, wide_nodes
 int hk_wide_info(void* hv, int tree, int* out3) {
   HkScene* h = (HkScene*)hv;

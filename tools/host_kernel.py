@@ -40,6 +40,13 @@ def lib():
         L.hk_wide_depth.argtypes = [C.c_void_p]
         L.hk_hit.restype = C.c_int
         L.hk_hit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 5
+        L.hk_trace.restype = C.c_int
+        L.hk_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 8
+        L.hk_ray_surface.restype = C.c_int
+        L.hk_ray_surface.argtypes = [C.c_void_p, C.c_int, C.c_longlong] + [C.c_void_p] * 9
+        L.hk_trace_plan.restype = None
+        L.hk_trace_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hk_trace_persistent_min_rays.restype = C.c_longlong
         L.hk_wide_info.restype = C.c_int
         L.hk_wide_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hk_check_uniform.restype = C.c_longlong
@@ -133,6 +140,36 @@ class Scene:
                         vis.ctypes.data if want_visits else None) != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return (t, idx, vis) if want_visits else (t, idx)
+
+    def trace(self, o, d, tmax=None, traversal=2, tree=2, any_hit=False, channels=("t", "object"), want_visits=False):
+        """dr_trace_rays on the host (hk_trace, hk_ray_surface): the rays (o, d[, tmax]) by the walks of device_trace.hpp -> a dict of arrays as
+        dogeray_amd.Context.trace returns it ({"occluded"} for any_hit); want_visits adds "visits", the boxes tested per ray."""
+        o, d = np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
+        n = o.shape[0]
+        assert o.shape == (n, 3) and d.shape == (n, 3)
+        if tmax is not None:
+            tmax = np.ascontiguousarray(tmax, dtype=np.float32)
+            assert tmax.shape == (n,)
+        t, idx, slot, occ = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        vis = np.zeros(n, np.int32)
+        if lib().hk_trace(self.h, int(traversal), int(tree), 1 if any_hit else 0, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data if tmax is not None else None,
+                          t.ctypes.data, idx.ctypes.data, occ.ctypes.data, slot.ctypes.data, vis.ctypes.data) != 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        if any_hit:
+            out = {"occluded": occ}
+        else:
+            out = {}
+            sizes = {"material": (np.int32, 1), "distance": (np.float32, 1), "normal": (np.float32, 3), "uv": (np.float32, 2), "albedo": (np.float32, 3)}
+            extra = {k: np.zeros((n, sizes[k][1]) if sizes[k][1] > 1 else n, sizes[k][0]) for k in channels if k in sizes}
+            if extra:
+                if lib().hk_ray_surface(self.h, int(tree), n, o.ctypes.data, d.ctypes.data, t.ctypes.data, slot.ctypes.data,
+                                        *[extra[k].ctypes.data if k in extra else None for k in ("material", "distance", "normal", "uv", "albedo")]) != 0:
+                    raise RuntimeError(lib().hk_last_error().decode())
+            for k in channels:
+                out[k] = t if k == "t" else idx if k == "object" else extra[k]
+        if want_visits:
+            out["visits"] = vis
+        return out
 
     def wide_info(self, tree=2):
         """What dr_context_get_option reports for the tree of wide_tree = `tree`: a dict with wide_depth (0: no wide tree), wide_own_bounds, wide_nodes."""
@@ -472,6 +509,20 @@ def persistent_builds():
     out = np.zeros((n, 8), np.int32)
     assert lib().hk_persistent_builds(out.ctypes.data, n) == n
     return [tuple(int(v) for v in row) for row in out]
+
+
+TRACE_PLAN_FIELDS = ("kernel", "traversal", "blocks")
+
+
+def trace_plan(n, traversal, has_wide, num_cus=256, force=0):
+    """launch_plan.hpp plan_trace -> (kernel: 0 one ray per lane / 1 persistent, the traversal really walked, workgroups)"""
+    out = (C.c_int * 3)()
+    lib().hk_trace_plan(int(n), int(traversal), int(bool(has_wide)), int(num_cus), int(force), out)
+    return tuple(out)
+
+
+def trace_persistent_min_rays():
+    return int(lib().hk_trace_persistent_min_rays())
 
 
 def plan_sky_split(cfg, work, coop_steps, per_frame, wave_log_on):

@@ -1,0 +1,55 @@
+// The host build of dr_trace_rays (tools/host_kernel.cpp hk_trace, hk_ray_surface) under AddressSanitizer + UBSan, as a stand-alone program: random and
+// degenerate rays with adversarial tmax values through every walk, both modes, both trees of every scene file given.  Build and run from the repo root:
+//   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -mfma -pthread -DDR_HOST_BUILD=1 -I tools/host_kernel \
+//     -o /tmp/trace_asan tools/trace_sanitize_driver.cpp tools/host_kernel.cpp dogeray_amd/csrc/{rts_reader,bvh_builder,linearise,wide_builder,capi_host}.cpp
+//   /tmp/trace_asan tests/golden/textures tests/golden/scenes/*.rts
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+extern "C" {
+void* hk_scene_load(const char* rts_path, const char* texdir);
+void hk_scene_free(void* h);
+const char* hk_last_error();
+int hk_trace(void* hv, int traversal, int tree, int mode, long long n, const float* o, const float* d, const float* tmax, float* t, int32_t* idx,
+             int32_t* occluded, int32_t* slot, int32_t* visits);
+int hk_ray_surface(void* hv, int tree, long long n, const float* o, const float* d, const float* t, const int32_t* slot, int32_t* material, float* distance,
+                   float* normal, float* uv, float* albedo);
+}
+
+int main(int argc, char** argv) {
+  if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }
+  const long long n = 3000;
+  uint64_t s = 88172645463325252ull;
+  auto rnd = [&s]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (float)((double)(s >> 11) * 0x1p-53); };
+  const float special[] = {0.0f, -0.0f, 1.0f, -1.0f, 1e-30f, 1e30f, std::numeric_limits<float>::infinity(), -std::numeric_limits<float>::infinity(), std::nanf("")};
+  int bad = 0;
+  for (int a = 2; a < argc; a++) {
+    void* h = hk_scene_load(argv[a], argv[1]);
+    if (!h) { printf("%s: not loaded (%s)\n", argv[a], hk_last_error()); continue; }
+    std::vector<float> o(3 * n), d(3 * n), tmax(n), t(n), dist(n), nrm(3 * n), uv(2 * n), alb(3 * n);
+    std::vector<int32_t> idx(n), occ(n), slot(n), vis(n), mat(n);
+    for (long long i = 0; i < 3 * n; i++) {
+      o[i] = (rnd() - 0.5f) * 20.0f; d[i] = rnd() - 0.5f;
+      if (rnd() < 0.02f) o[i] = special[(int)(rnd() * 9) % 9];
+      if (rnd() < 0.05f) d[i] = special[(int)(rnd() * 9) % 9];
+    }
+    for (long long i = 0; i < n; i++) tmax[i] = rnd() < 0.1f ? special[(int)(rnd() * 9) % 9] : rnd() * 30.0f;
+    for (int tree = 1; tree <= 2; tree++)
+      for (int traversal = 0; traversal <= 2; traversal++)
+        for (int capped = 0; capped < 2; capped++) {
+          const float* cap = capped ? tmax.data() : nullptr;
+          if (hk_trace(h, traversal, tree, 0, n, o.data(), d.data(), cap, t.data(), idx.data(), nullptr, slot.data(), vis.data()) != 0 ||
+              hk_trace(h, traversal, tree, 1, n, o.data(), d.data(), cap, nullptr, nullptr, occ.data(), nullptr, vis.data()) != 0 ||
+              hk_ray_surface(h, tree, n, o.data(), d.data(), t.data(), slot.data(), mat.data(), dist.data(), nrm.data(), uv.data(), alb.data()) != 0) {
+            printf("%s: %s\n", argv[a], hk_last_error()); bad++; continue;
+          }
+          for (long long i = 0; i < n; i++) if ((occ[i] != 0) != (t[i] > 0.0f)) { printf("%s: ray %lld: occluded %d, closest t %g\n", argv[a], i, occ[i], t[i]); bad++; break; }
+        }
+    hk_scene_free(h);
+    printf("%s: ok\n", argv[a]);
+  }
+  return bad ? 1 : 0;
+}
