@@ -626,8 +626,8 @@ class Context:
         return out
 
     def sky_tiles(self):
-        """(sky tiles, geometry tiles) of the last launch (dr_stats_sky_tiles): the tiles sky_tiles_kernel rendered and the tiles left to the
-        persistent kernel; (0, 0) when the launch was not split (option "sky_tiles")."""
+        """(sky tiles, geometry tiles) of the last launch (dr_stats_sky_tiles): the tiles rendered without a walk (by sky_tiles_kernel, or by the persistent kernel's
+        retiring waves: option "sky_tiles" 1 / 2) and the tiles left to the persistent kernel's queues; (0, 0) when the launch was not split (option "sky_tiles")."""
         n_sky, n_geometry = C.c_int(), C.c_int()
         _check(lib().dr_stats_sky_tiles(self._h, C.byref(n_sky), C.byref(n_geometry)))
         return n_sky.value, n_geometry.value

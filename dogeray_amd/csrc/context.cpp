@@ -46,7 +46,7 @@ const Option OPTIONS[] = {
     {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, false},
     {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, false},
     {"camera_entry", /* (as above) */ &dr_context::camera_entry, 0, 1, 0, false},
-    {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 1, 0, false},
+    {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 2, 0, false},
     {"trace_kernel", /* (as above) */ &dr_context::trace_kernel, 0, 2, 0, false},
 };
 

@@ -92,6 +92,7 @@ struct LaunchSite {
 };
 
 constexpr int TILE_COUNTERS = 1024;
+constexpr int LAUNCH_COUNTERS = MAX_REGIONS + 1;      // a launch's block of them: a cursor per tile queue, then the sky units' cursor (option sky_tiles = 2)
 
 }  // namespace dr
 
@@ -180,7 +181,7 @@ struct dr_context {
   // persistent kernel (context_render.cpp enqueue_frame).  The split is made on the launch's stream and kept while the words and the order it was
   // made from are the same (sky_key: cert_gen, order in use, order_gen, tiles, regions -- sky_split_kernel takes 0.53 % of a 32-frame launch of the bench
   // view, profiles/sky_tiles_ab.txt); tile_order / region_start above stay whole
-  int sky_tiles = 1;                       // option: 0 every tile goes through the persistent kernel
+  int sky_tiles = 2;                       // option: 0 every tile goes through the persistent kernel; 1 sky_tiles_kernel in front of it; 2 its retiring waves
   DevMem<int> launch_order, launch_region_start, sky_list;
   DevMem<unsigned> sky_counts;             // [0] sky tiles, [1] geometry tiles of the last split
   bool sky_split_last = false;             // the last launch was split (dr_stats_sky_tiles)

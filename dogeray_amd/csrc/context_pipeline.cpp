@@ -112,7 +112,7 @@ int pipeline_flush_some(dr_context* c, int n) {
   if (c->pipe_barrier_set) HIP_TRY(hipStreamWaitEvent(rs, c->pipe_barrier, 0));
   // the tile counters are cleared (on this launch's stream) when the cursor wraps: like a refresh, that launch runs alone -- nobody may
   // still count on the old values, and nobody may start on the new ones before they are cleared
-  const bool alone = refresh || c->tile_cursor + MAX_REGIONS > TILE_COUNTERS;
+  const bool alone = refresh || c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS;
   if (alone)
     for (int q = 0; q < dr_context::PIPE_STREAMS; q++) if (q != si && c->pipe_last_set[q]) HIP_TRY(hipStreamWaitEvent(rs, c->pipe_last[q], 0));
   if (tiles > 0) {

@@ -125,7 +125,10 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
 // are rendered by sky_tiles_kernel, in front of the persistent kernel on the same stream, and order / region_start become the launch's own pair
 // that holds the other tiles only (kept from launch to launch while the tiles' words and the order are the same).  The plan is still made from every tile (the number of geometry tiles stays on the device).  A pipelined launch
 // beside others is not split, nor one on another stream than the context's (the launch's own pair is one per context).
-bool sky_split(dr_context* c, const LaunchSite& site, const RenderParams& P, int tiles, const int*& order, const int*& region_start, unsigned* pcost) {
+// sky_tiles = 2: no kernel in front -- the list, the counts and the launch's unit cursor (`cursor`: zero when the launch starts) travel in P and the
+// persistent kernel's waves render the sky tiles when they retire, a unit of SKY_CHUNK frames at a time.  Only a launch that adds atomically
+// (P.accumulate == 2) may cut a tile's batch into several units; every other launch is of one frame, one unit per tile.
+bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles, const int*& order, const int*& region_start, unsigned* pcost, unsigned* cursor) {
   if (!c->sky_tiles || !c->entry_ok || !P.cert_level || site.hold_order || site.stream != c->stream || P.out_frame_stride != 0) return false;
   if (P.max_depth <= 0 || !(P.spp_f > 0.0f)) return false;
   if (!plan_sky_split(plan_persistent(persistent_cfg(c, site), (long long)tiles * P.batch, P.coop_steps, false, P.wave_log != nullptr))) return false;
@@ -142,7 +145,10 @@ bool sky_split(dr_context* c, const LaunchSite& site, const RenderParams& P, int
     memcpy(c->sky_key, key, sizeof(key));
     c->sky_key_valid = true;
   }
-  launch_sky_tiles(site.stream, P, c->sky_list, c->sky_counts, pcost);
+  if (c->sky_tiles == 2) {
+    P.sky_list = c->sky_list; P.sky_counts = c->sky_counts; P.sky_cursor = cursor;
+    P.sky_chunk = sky_chunk_frames(P.batch, P.accumulate == 2 ? SKY_CHUNK : 0);
+  } else launch_sky_tiles(site.stream, P, c->sky_list, c->sky_counts, pcost);
   order = c->launch_order; region_start = c->launch_region_start;
   return true;
 }
@@ -154,12 +160,12 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
   RenderParams P = P_in;
   const int tiles = P.ncols * P.gy;
   if (uses_persistent(c)) {
-    if (c->tile_cursor + MAX_REGIONS > TILE_COUNTERS) {
+    if (c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS) {
       (void)hipMemsetAsync(c->tile_counters, 0, TILE_COUNTERS * sizeof(unsigned), site.stream);
       c->tile_cursor = 0;
     }
-    unsigned* counter = c->tile_counters + c->tile_cursor;      // one counter per region
-    c->tile_cursor += MAX_REGIONS;
+    unsigned* counter = c->tile_counters + c->tile_cursor;      // one counter per region, and the sky units' cursor behind them
+    c->tile_cursor += LAUNCH_COUNTERS;
     const int* order; unsigned* pcost;
     if (site.hold_order) {
       // a pipelined launch runs beside the previous frame's: it may read the tile order but nobody may write it (or the costs) meanwhile
@@ -171,7 +177,7 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
     if (!c->wave_log_on) P.wave_log = nullptr;
     cert_prepare(c, site, P, tiles);
     const int* launch_order = order; const int* launch_rstart = c->region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
-    c->sky_split_last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost);
+    c->sky_split_last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
     const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, launch_order, launch_rstart, pcost);
     if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
     c->wave_log_waves = log_waves;

@@ -188,6 +188,12 @@ struct RenderParams {
   float wide_cert_k[CERT_MAX_LEVELS + 1];      // ... the factor on it for camera rays of a tile of grade g of the grazing certificate ([0] = 1: the scene's margin; [g] >= 1e-4 / level_a[g - 1])
   const uint32_t* cert_level;     // null, or one word per tile of this launch (local column * gy + row): the tile's grade (0: a camera ray of the tile may graze) in the low
                                   // ENTRY_SHIFT bits, above them the entry code of its camera rays (record << 1 | is-leaf, the `node` their walk starts with; 0 the root, ENTRY_NONE)
+  // option sky_tiles = 2 (lean build only; null: the launch's waves render no sky tile): the split's sky tiles and counts ([0] sky tiles), the unit
+  // cursor (0 when the launch starts) and the frames per unit (launch_plan.hpp sky_unit)
+  const int* sky_list;
+  const unsigned* sky_counts;
+  unsigned* sky_cursor;
+  int32_t sky_chunk;
 };
 
 // The denoiser's parameters (dr_denoise_params; defaults and ranges: params_host.hpp) and its material markers (device_denoise.hpp)

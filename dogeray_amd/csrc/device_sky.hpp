@@ -27,6 +27,26 @@ __device__ __forceinline__ void sky_pixel(const RenderParams& P, int x, int y, i
   r = f2i(color.x * 255 * P.scale); g = f2i(color.y * 255 * P.scale); b = f2i(color.z * 255 * P.scale);
 }
 
+// `count` frames from frame `first` of the launch for lane `lane` of sky tile `tile` -- pixel (lane >> 3, lane & 7) of it, as in the render kernels --
+// summed in registers and written once per channel as P.accumulate says (several units of one tile: the atomic add); the cost the persistent kernel
+// records for such a pixel, 0 node steps, is stored by the unit that starts at frame 0.  The one body of sky_tiles_kernel (kernels_aux.hip: the whole
+// batch) and of the lean build's retiring waves (kernels_render.hip: a unit of launch_plan.hpp sky_unit); which wave runs it enters no arithmetic.
+__device__ __forceinline__ void sky_tile_frames(const RenderParams& P, int tile, int lane, int first, int count, unsigned* pixel_cost) {
+  const int col = tile / P.gy, by = tile - col * P.gy;
+  const int x = (P.stripe_rem + col * P.stripe_mod) * 8 + (lane >> 3), y = by * 8 + (lane & 7);
+  int r = 0, g = 0, b = 0;
+  for (int frame = first; frame < first + count; frame++) {
+    int fr, fg, fb;
+    sky_pixel(P, x, y, frame, fr, fg, fb);
+    r += fr; g += fg; b += fb;
+  }
+  int32_t* px = P.out + ((size_t)x * (size_t)P.H + (size_t)y) * 3;
+  if (P.accumulate == 2) { atomicAdd(px + 0, r); atomicAdd(px + 1, g); atomicAdd(px + 2, b); }
+  else if (P.accumulate) { px[0] += r; px[1] += g; px[2] += b; }
+  else { px[0] = r; px[1] = g; px[2] = b; }
+  if (pixel_cost && first == 0) pixel_cost[(size_t)tile * 64 + lane] = 0u;
+}
+
 // The split of a launch's order: order (null: the identity) and region_start in the persistent kernel's format (region r owns positions
 // [region_start[r], region_start[r + 1]) of the order, region_start[regions] = tiles); word = a word per tile.
 //   launch_order          the tiles that are not sky, in the order they had (a stable partition: every region keeps its heavy-first, then natural order)

@@ -228,26 +228,13 @@ __global__ __launch_bounds__(1024) void sky_split_kernel(const int* __restrict__
   if (tid <= regions && rs[tid] >= ntiles) launch_region_start[tid] = (int)gtotal;      // (the end, and regions that start there)
   if (tid == 0) { counts[0] = stotal; counts[1] = gtotal; }
 }
-// One wave per sky tile, lane l on pixel (l >> 3, l & 7) of it as in the render kernels: the launch's frames of the pixel summed in registers
-// (device_sky.hpp sky_pixel) and written once; the cost the persistent kernel records for such a pixel is 0 node steps.
+// One wave per sky tile and the launch's whole batch (device_sky.hpp sky_tile_frames: the body it shares with the lean build's retiring waves, option
+// sky_tiles = 2).
 __global__ __launch_bounds__(256) void sky_tiles_kernel(RenderParams P, const int* __restrict__ sky_list, const unsigned* __restrict__ counts,
                                                          unsigned* __restrict__ pixel_cost) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= (int)counts[0]) return;
-  const int tile = sky_list[i];
-  const int col = tile / P.gy, by = tile - col * P.gy;
-  const int x = (P.stripe_rem + col * P.stripe_mod) * 8 + (lane >> 3), y = by * 8 + (lane & 7);
-  int r = 0, g = 0, b = 0;
-  for (int frame = 0; frame < P.batch; frame++) {
-    int fr, fg, fb;
-    sky_pixel(P, x, y, frame, fr, fg, fb);
-    r += fr; g += fg; b += fb;
-  }
-  int32_t* px = P.out + ((size_t)x * (size_t)P.H + (size_t)y) * 3;
-  if (P.accumulate == 2) { atomicAdd(px + 0, r); atomicAdd(px + 1, g); atomicAdd(px + 2, b); }
-  else if (P.accumulate) { px[0] += r; px[1] += g; px[2] += b; }
-  else { px[0] = r; px[1] = g; px[2] = b; }
-  if (pixel_cost) pixel_cost[(size_t)tile * 64 + lane] = 0u;
+  sky_tile_frames(P, sky_list[i], lane, 0, P.batch, pixel_cost);
 }
 
 // clamp(acc / divide_by, 0, 255) into row-major RGB8 (draw loop K:2281-2287)

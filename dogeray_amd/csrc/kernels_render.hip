@@ -4,6 +4,7 @@
 
 #include "device_core.hpp"
 #include "device_coop.hpp"
+#include "device_sky.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -101,6 +102,27 @@ enum ThreadedStashWord { TS_V0X = 0, TS_C, TS_D = TS_C + 4, TS_INFO = TS_D + 4, 
                          TS_PCODE, TS_FRAME, TS_SAMPLE, TS_STEPS, TS_RSTART, TS_WORDS };
 static_assert(TS_WORDS * 64 == WAVE_LDS_DWORDS, "stash layout");
 
+// The launch's sky units, taken from its cursor until none is left (option sky_tiles = 2; the end of render_persistent_kernel).  A function of its own
+// that reads the launch's constants from the kernel's argument block: inlined -- against P, or against a copy read afresh -- the block changes the
+// register allocation of the whole kernel and the launch's bulk runs 4.6 % slower (profiles/sky_inline_ab.txt).
+typedef const __attribute__((address_space(4))) RenderParams* ArgBlock;
+__device__ __attribute__((noinline)) void sky_units_run(ArgBlock args, int lane, unsigned* pixel_cost) {
+#if defined(__HIP_DEVICE_COMPILE__)      // (the host pass has no copy out of the argument block's address space, and no use for the body)
+  if (args->sky_list == nullptr) return;
+  const RenderParams S = *args;
+  const unsigned n_units = sky_units(S.sky_counts[0], S.batch, S.sky_chunk);
+  __builtin_amdgcn_s_setprio(0);      // below the waves that still walk (the top of the kernel)
+  for (;;) {
+    unsigned u = 0;
+    if (lane == 0) u = atomicAdd(S.sky_cursor, 1u);
+    u = (unsigned)__builtin_amdgcn_readfirstlane((int)u);
+    if (u >= n_units) break;
+    const SkyUnit su = sky_unit(u, S.batch, S.sky_chunk);
+    sky_tile_frames(S, S.sky_list[su.index], lane, su.first, su.count, pixel_cost);
+  }
+#endif
+}
+
 // PERFRAME: every frame of the launch's batch is stored into a buffer of its own (P.out + frame * P.out_frame_stride) instead of being added into one: the
 // grouped present pipeline (dr_pipeline_*: the frames of a group share one launch and are added and shown one by one afterwards).
 template <bool COUNT, int OCC, int TRAV_MIN, int PARK_MIN, int P_UNROLL, bool WIDE, bool COOP = true, bool PERFRAME = false>
@@ -109,6 +131,10 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
                                                                      unsigned* __restrict__ pixel_cost) {
   const int lane = threadIdx.x & 63;
   const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6);
+  // a launch whose retiring waves render its sky tiles (sky_units_run, at the end): the waves walk at priority 1 and drop to 0 for the sky units.  The
+  // launch lasts as long as its slowest wave, and a SIMD's issue slots go to the higher priority first: at equal priority the sky units beside a
+  // straggler slow it down and the launch gains nothing (profiles/sky_inline_ab.txt).  (wave-uniform: a kernel argument)
+  if (WIDE && !COOP && !COUNT && !PERFRAME && P.sky_list != nullptr) __builtin_amdgcn_s_setprio(1);
   // LDS per wave (threaded walk: 6 KiB; wide walk: 6.5 KiB, 7.25 with work sharing), used for two things that never overlap in time
   // within a wave:
   //  * during the shade/refill phase, the state that phase does not need (threaded walk: the parked leaf, 1/direction; and while a
@@ -614,6 +640,12 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         steps++;
       }
     }
+  }
+  if (WIDE && !COOP && !COUNT && !PERFRAME) {
+    // ---- sky tiles (option sky_tiles = 2): every lane has retired -- the queues are empty and this wave's last pixel is stored --, but the
+    // launch lasts until its slowest wave's last pixel.  The wave renders the launch's sky tiles in that time, a unit (launch_plan.hpp sky_unit: a sky tile
+    // and a chunk of the batch's frames) at a time from a cursor; no walk, no stash: the body of sky_tiles_kernel on all 64 lanes.
+    sky_units_run((ArgBlock)__builtin_amdgcn_kernarg_segment_ptr(), lane, pixel_cost);      // P is the kernel's first argument
   }
   if (lane == 0) {
     const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();

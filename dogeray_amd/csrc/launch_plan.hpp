@@ -110,6 +110,24 @@ inline PersistentPlan plan_persistent(const PersistentCfg& cfg, long long work, 
 // stores are not split
 inline bool plan_sky_split(const PersistentPlan& p) { return p.build.wide && !p.build.count && !p.build.coop && !p.build.perframe; }
 
+// Option sky_tiles = 2: the lean build's waves render the sky tiles themselves once all their lanes have retired (kernels_render.hip), a unit at a time
+// from a cursor.  A unit is a position in sky_list and a chunk of consecutive frames of the launch's batch: unit u is chunk u % chunks of list entry
+// u / chunks, chunks = ceil(batch / chunk frames), the last chunk the shorter one.  `chunk` = frames per unit, 0 (or more than the batch): the whole
+// batch, one unit per sky tile.  (constexpr: the kernel and the host build call the same functions.)
+#ifndef DR_SKY_CHUNK
+#define DR_SKY_CHUNK 0
+#endif
+constexpr int SKY_CHUNK = DR_SKY_CHUNK;
+struct SkyUnit { int index, first, count; };      // position in sky_list, first frame of the batch, frames
+constexpr int sky_chunk_frames(int batch, int chunk) { return chunk > 0 && chunk < batch ? chunk : (batch > 0 ? batch : 1); }
+constexpr int sky_chunks(int batch, int chunk) { return batch > 0 ? (batch + sky_chunk_frames(batch, chunk) - 1) / sky_chunk_frames(batch, chunk) : 0; }
+constexpr unsigned sky_units(unsigned n_sky, int batch, int chunk) { return n_sky * (unsigned)sky_chunks(batch, chunk); }
+constexpr SkyUnit sky_unit(unsigned u, int batch, int chunk) {
+  const unsigned chunks = (unsigned)sky_chunks(batch, chunk), index = u / chunks;
+  const int frames = sky_chunk_frames(batch, chunk), first = (int)(u - index * chunks) * frames;
+  return SkyUnit{(int)index, first, batch - first < frames ? batch - first : frames};
+}
+
 // Tile queues of a launch of `tiles` tiles (batch_hint frames of them): one per XCD, or one
 inline int plan_regions(int tiles, int batch_hint, bool xcd_regions, bool short_one_queue, int tiles_per_wave, int num_cus) {
   int regions = xcd_regions ? MAX_REGIONS : 1;

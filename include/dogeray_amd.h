@@ -203,10 +203,12 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   that holds every leaf a camera ray of the tile can reach (dr_stats_camera_entry) -- instead of the root; a tile
  *                   that sees nothing of the scene walks nothing.  0 every ray starts at the root.  The same bits either way.  Used where the
  *                   certificate is (the lean and counting builds, a pixel's first sample), built and dropped with it, for any scene with a wide tree
- *   "sky_tiles"     1 (default): a launch of the lean build over a view with an entry table renders the tiles no leaf can be seen from (entry code -1)
- *                   in a kernel of their own -- one wave per tile, the launch's frames summed in registers, no walk and no path pool -- and hands the
- *                   persistent kernel the other tiles only (dr_stats_sky_tiles); 0 every tile goes through the persistent kernel.
- *                   The same bits either way.  Not used by the counting and work-sharing builds nor by pipelined launches
+ *   "sky_tiles"     a launch of the lean build over a view with an entry table takes the tiles no leaf can be seen from (entry code -1) out of the
+ *                   persistent kernel's queues (dr_stats_sky_tiles) and renders them without a walk or a path pool, a wave per tile
+ *                   with the frames summed in registers: 2 (default) in the persistent kernel's own waves once all their lanes have retired, in
+ *                   the time the launch waits for its slowest wave; 1 in a kernel of their own in front of the persistent kernel; 0 every tile
+ *                   goes through the persistent kernel's queues.  The same bits with every value.  Not used by the counting and work-sharing
+ *                   builds nor by pipelined launches
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)

@@ -581,6 +581,37 @@ int hk_sky_pixel(void* hv, const float* settings13, int W, int H, float backgrou
   }
   return 0;
 }
+// launch_plan.hpp's sky units (option sky_tiles = 2): how many a launch of `batch` frames with n_sky sky tiles has, and unit u as (position in sky_list,
+// first frame, frames)
+unsigned hk_sky_units(unsigned n_sky, int batch, int chunk) { return sky_units(n_sky, batch, chunk); }
+void hk_sky_unit(unsigned u, int batch, int chunk, int* out3) {
+  const SkyUnit s = sky_unit(u, batch, chunk);
+  out3[0] = s.index; out3[1] = s.first; out3[2] = s.count;
+}
+// device_sky.hpp sky_tile_frames, the body the sky kernel and the persistent kernel's retiring waves share, over every unit of a launch of `batch` frames
+// (seed, stride: dr_render_accumulate's) whose sky list is sky_list[n_sky], all 64 lanes of each, units in the order `perm` gives (null: ascending): added
+// into acc (int32[W * H * 3], P.accumulate = 2) and, cost non-null, the cost words (unsigned[tiles * 64]) written.  Returns the units run, or -1.
+long long hk_sky_units_render(void* hv, const float* settings13, int W, int H, float background, uint64_t seed, uint64_t stride, int batch, int chunk, int n_sky,
+                              const int* sky_list, const unsigned* perm, int32_t* acc, unsigned* cost) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || batch < 1 || n_sky < 0 || !acc || (n_sky > 0 && !sky_list)) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, background, seed, 1, 0, P)) { hk_err = why; return -1; }
+  const DeviceImage& img = h->img;
+  if (P.backtex >= (int)img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
+  P.tex = img.tex.data(); P.texels = img.texels.data();
+  P.batch = batch; P.batch_seed_stride = stride;
+  P.out = acc; P.accumulate = 2;
+  P.sky_chunk = sky_chunk_frames(batch, chunk);
+  const unsigned n_units = sky_units((unsigned)n_sky, batch, P.sky_chunk);
+  for (unsigned k = 0; k < n_units; k++) {
+    const SkyUnit s = sky_unit(perm ? perm[k] : k, batch, P.sky_chunk);
+    if (s.index < 0 || s.index >= n_sky || sky_list[s.index] < 0 || sky_list[s.index] >= P.ncols * P.gy) { hk_err = "unit outside the list"; return -1; }
+    for (int lane = 0; lane < 64; lane++) sky_tile_frames(P, sky_list[s.index], lane, s.first, s.count, cost);
+  }
+  return (long long)n_units;
+}
 int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 
 const char* hk_last_error() { return hk_err.c_str(); }

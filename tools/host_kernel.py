@@ -95,6 +95,13 @@ def lib():
         L.hk_plan_sky_split.argtypes = [C.POINTER(C.c_int), C.c_longlong, C.c_int, C.c_int, C.c_int]
         L.hk_sky_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hk_sky_pixel.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hk_sky_units.restype = C.c_uint
+        L.hk_sky_units.argtypes = [C.c_uint, C.c_int, C.c_int]
+        L.hk_sky_unit.restype = None
+        L.hk_sky_unit.argtypes = [C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.hk_sky_units_render.restype = C.c_longlong
+        L.hk_sky_units_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -236,6 +243,20 @@ class Scene:
                               xs.ctypes.data, ys.ctypes.data, out.ctypes.data) != 0:
             raise RuntimeError(lib().hk_last_error().decode())
         return out
+
+    def sky_units_render(self, settings13, W, H, background, seed, stride, batch, chunk, sky_list, perm=None, cost=None):
+        """device_sky.hpp sky_tile_frames over every unit of a launch of `batch` frames whose sky tiles are sky_list (hk_sky_units_render), the units in
+        the order perm gives: (int32[W, H, 3] what the units add to an accumulator of zeros, units run).  cost: uint32[tiles * 64], written in place."""
+        st = np.ascontiguousarray(settings13, dtype=np.float32)
+        sl = np.ascontiguousarray(sky_list, dtype=np.int32)
+        pm = np.ascontiguousarray(perm, dtype=np.uint32) if perm is not None else None
+        acc = np.zeros((W, H, 3), np.int32)
+        n = lib().hk_sky_units_render(self.h, st.ctypes.data, W, H, float(background), int(seed) & (2 ** 64 - 1), int(stride) & (2 ** 64 - 1), int(batch),
+                                      int(chunk), len(sl), sl.ctypes.data, pm.ctypes.data if pm is not None else None, acc.ctypes.data,
+                                      cost.ctypes.data if cost is not None else None)
+        if n < 0:
+            raise RuntimeError(lib().hk_last_error().decode())
+        return acc, int(n)
 
     def wide_leaves(self):
         """The default tree's leaves in depth-first order: (uint32 record per rank, float32 (n, 6) box per rank -- mn, mx of the record --, uint32 (records, 2)
@@ -541,6 +562,18 @@ def sky_split(order, region_start, word, regions):
     n = lib().hk_sky_split(o.ctypes.data if o is not None else None, rs.ctypes.data, word.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data,
                            sky.ctypes.data)
     return lo[:tiles - n], lrs, sky[:n]
+
+
+def sky_units(n_sky, batch, chunk):
+    """launch_plan.hpp sky_units: the units (sky tile, chunk of frames) of a launch of `batch` frames with n_sky sky tiles; chunk 0 = the whole batch"""
+    return int(lib().hk_sky_units(int(n_sky), int(batch), int(chunk)))
+
+
+def sky_unit(u, batch, chunk):
+    """launch_plan.hpp sky_unit: unit u as (position in sky_list, first frame, frames)"""
+    out = (C.c_int * 3)()
+    lib().hk_sky_unit(int(u), int(batch), int(chunk), out)
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def plan_regions(tiles, batch_hint, xcd_regions, short_one_queue, tiles_per_wave, num_cus):
