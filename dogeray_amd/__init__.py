@@ -512,7 +512,8 @@ class Context:
                                                 int(seed_stride) & (2 ** 64 - 1), nframes))
 
     def pipeline_submit(self, settings13, W, H, background, frame_seed, present_divide_by=0):
-        """Queues one frame of the pipelined present loop (dr_pipeline_submit); returns its ticket."""
+        """Queues one frame of the pipelined present loop (dr_pipeline_submit); returns its ticket.  The frame is rendered with the scene, stripe,
+        traversal and options of this moment: upload, set_stripe, set_traversal, enable_counters and set_option apply to frames submitted after them."""
         st = _f32(settings13)
         t = C.c_uint64(0)
         _check(lib().dr_pipeline_submit(self._h, _p(st), W, H, float(background), int(frame_seed) & (2 ** 64 - 1), int(present_divide_by), C.byref(t)))
@@ -520,7 +521,10 @@ class Context:
 
     def pipeline_wait(self, ticket, want_image=False, in_place=False):
         """Waits for a submitted frame; with want_image the RGB8 image [H, W, 3] of exactly the frames up to that ticket (in_place: a
-        read-only view of the library's pinned download buffer, valid until pipe_streams + 1 more GROUPS of frames have been launched)."""
+        read-only view of the library's pinned download buffer, valid until the next call that may launch a group of frames -- pipeline_submit, or
+        any call ordered behind frames that are still held).  Every ticket handed out stays waitable until it has been waited for, however many
+        groups have been launched since; the image of a presented frame is kept until then (at most 32 of them beyond the frames in flight:
+        pipeline_submit raises ERR_INVALID rather than drop one).  A frame submitted without a present raises ERR_INVALID with want_image."""
         if not want_image:
             _check(lib().dr_pipeline_wait(self._h, int(ticket), None))
             return None

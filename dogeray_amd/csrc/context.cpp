@@ -55,11 +55,20 @@ const Option* find_option(const std::string& name) {
   return nullptr;
 }
 
+// One rule for whatever changes the state a launch reads (an option, the stripe, the traversal, the counters switch): frames submitted before the change
+// are launched with the state they were submitted under -- the frames still held go first.  (Nothing is held while a context is being created.)
+int flush_held(dr_context* c) {
+  if (c->pipe_pending.empty()) return DR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  return pipeline_flush(c);
+}
+
 int set_option(dr_context* c, const std::string& name, int v) {
   const Option* o = find_option(name);
   if (!o) { set_error("unknown option '" + name + "'"); return DR_ERR_INVALID; }
   if (o->lo == ANY) v = v != 0;
   else if (v < o->lo || v > o->hi || (o->only && !(o->only >> v & 1u))) { set_error("value not supported for option '" + name + "'"); return DR_ERR_INVALID; }
+  DR_TRY(flush_held(c));
   if (name == "split_steps") v &= ~15;
   else if (name == "wave_log") {
     if (v && !c->wave_log) {
@@ -70,16 +79,13 @@ int set_option(dr_context* c, const std::string& name, int v) {
   else if (name == "pipe_streams") {
     if (v != c->pipe_streams) {               // slots and streams are numbered by ticket: drain, then start again from ticket 0
       if (hipSetDevice(c->device) != hipSuccess || join_pipeline(c) != DR_OK || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("pipe_streams: cannot drain the pipeline"); return DR_ERR_DEVICE; }
-      for (int k = 0; k < dr_context::PIPE_DEPTH; k++) { c->pipe_slot[k].drained = true; c->pipe_slot[k].count = 0; }
+      for (int k = 0; k < dr_context::PIPE_DEPTH; k++) { c->pipe_slot[k].drained = true; c->pipe_slot[k].count = 0; c->pipe_slot[k].unwaited = 0; }
+      c->pipe_parked.clear();                 // (images kept for tickets of the old numbering)
       c->pipe_next = 0; c->pipe_groups = 0;
     }
   }
   else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels || o->member == &dr_context::camera_entry ||
-           o->member == &dr_context::sky_tiles) {
-    // frames submitted before the change are launched with the setting they were submitted under
-    if (!c->pipe_pending.empty()) DR_TRY(pipeline_flush(c));
-    c->cert_valid = false;
-  }
+           o->member == &dr_context::sky_tiles) c->cert_valid = false;
   c->*(o->member) = v;
   if (o->reorders) c->order_valid = false;
   return DR_OK;
@@ -169,6 +175,10 @@ void dr_context_destroy(dr_context* c) { delete c; }
 int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   if (!c || !s) { set_error("null argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  // frames submitted before the upload are rendered from the scene that is resident now: they are launched, and everything queued has finished,
+  // before a buffer of that scene is freed
+  DR_TRY(join_pipeline(c));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   c->scene_gen++;                  // the cached guides of the denoiser, the upscaler and the reprojector belong to the old scene
   DeviceImage img;
   int rc = DR_OK;
@@ -208,6 +218,7 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
 
 int dr_context_set_stripe(dr_context* c, int mod, int rem) {
   if (!c || mod < 1 || rem < 0 || rem >= mod) { set_error("stripe: need mod >= 1 and 0 <= rem < mod"); return DR_ERR_INVALID; }
+  DR_TRY(flush_held(c));
   c->stripe_mod = mod; c->stripe_rem = rem;
   return DR_OK;
 }
@@ -249,6 +260,7 @@ int dr_context_set_traversal(dr_context* c, int mode) {
     set_error("ordered traversal supports at most 2^24 primitives");
     return DR_ERR_SCENE;
   }
+  DR_TRY(flush_held(c));
   c->traversal = mode;
   return DR_OK;
 }
@@ -261,6 +273,7 @@ int dr_context_stream(dr_context* c, void** hip_stream) {
 
 int dr_stats_enable_counters(dr_context* c, int on) {
   if (!c) { set_error("null context"); return DR_ERR_INVALID; }
+  DR_TRY(flush_held(c));
   c->count = on != 0;
   return DR_OK;
 }
@@ -268,6 +281,7 @@ int dr_stats_enable_counters(dr_context* c, int on) {
 int dr_stats_reset(dr_context* c) {
   if (!c) { set_error("null context"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // frames submitted before the reset are counted before it
   HIP_TRY(hipMemsetAsync(c->counters, 0, COUNTER_WORDS * sizeof(unsigned long long), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   memset(&c->stats, 0, sizeof(c->stats));
@@ -277,6 +291,7 @@ int dr_stats_reset(dr_context* c) {
 int dr_stats_get(dr_context* c, dr_stats* out) {
   if (!c || !out) { set_error("null argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   unsigned long long h[STAT_PHASE];
   HIP_TRY(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
@@ -291,6 +306,7 @@ int dr_stats_get(dr_context* c, dr_stats* out) {
 int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n) {
   if (!c || !out || n < 0 || n > COUNTER_WORDS - STAT_PHASE) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (n > 0) HIP_TRY(hipMemcpy(out, c->counters + STAT_PHASE, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return DR_OK;
@@ -299,8 +315,9 @@ int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n) {
 int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles) {
   if (!c || !n_tiles || max_words < 0 || (max_words > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
+  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int words = (c->cert_tiles + 31) / 32;
   *n_tiles = c->cert_tiles;
@@ -311,8 +328,9 @@ int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles
 int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tiles) {
   if (!c || !n_tiles || max < 0 || (max > 0 && !out_bytes)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_level && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
+  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_level && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   *n_tiles = c->cert_tiles;
   if (max > 0) HIP_TRY(hipMemcpy(out_bytes, c->cert_level, (size_t)(c->cert_tiles < max ? c->cert_tiles : max), hipMemcpyDeviceToHost));
@@ -322,8 +340,9 @@ int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tile
 int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles) {
   if (!c || !n_tiles || max < 0 || (max > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  if (!(c->camera_entry && c->cert_valid && c->entry_ok && c->cert_word && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
+  if (!(c->camera_entry && c->cert_valid && c->entry_ok && c->cert_word && c->cert_tiles > 0)) return DR_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   *n_tiles = c->cert_tiles;
   const int n = c->cert_tiles < max ? c->cert_tiles : max;
@@ -335,8 +354,9 @@ int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles) {
 int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry) {
   if (!c || !n_sky || !n_geometry) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_sky = 0; *n_geometry = 0;
-  if (!c->sky_split_last || !c->sky_counts) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
+  if (!c->sky_split_last || !c->sky_counts) return DR_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   unsigned h[2] = {0, 0};
   HIP_TRY(hipMemcpy(h, c->sky_counts, sizeof(h), hipMemcpyDeviceToHost));
@@ -348,6 +368,7 @@ int dr_stats_wave_log(dr_context* c, unsigned long long* out, int max_waves, int
   if (!c || !out || !n_waves || max_waves < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wave_log) { set_error("wave log is off (option wave_log)"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const int n = c->wave_log_waves < max_waves ? c->wave_log_waves : max_waves;
   if (n > 0) HIP_TRY(hipMemcpy(out, c->wave_log, (size_t)n * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -358,6 +379,7 @@ int dr_stats_wave_log(dr_context* c, unsigned long long* out, int max_waves, int
 int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n) {
   if (!c || !out || !n) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const size_t have = c->pixel_cost ? (size_t)c->order_capacity * 64 : 0;      // pixel (tile, lane-in-tile) at tile * 64 + lane, tile = block column * gy + block row
   const size_t m = have < capacity ? have : capacity;
@@ -370,6 +392,7 @@ int dr_stats_tile_order(dr_context* c, int* order, size_t capacity, size_t* n, i
   if (!c || !n || !region_start || !args || (capacity > 0 && !order)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n = 0;
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (!c->order_valid || !c->tile_order || !c->region_start) return DR_OK;
   for (int k = 0; k < 5; k++) args[k] = c->order_args[k];

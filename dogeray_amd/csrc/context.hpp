@@ -12,6 +12,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -247,6 +248,7 @@ struct dr_context {
     DevMem<uint8_t> rgb_dev[PIPE_GROUP_MAX]; dr::DevMem<uint8_t, true> rgb_host[PIPE_GROUP_MAX];      // frame f's present: on the device, and its pinned copy
     int div[PIPE_GROUP_MAX] = {0};                 // divisor frame f was presented with (0: not presented)
     bool fwaited[PIPE_GROUP_MAX] = {false};        // dr_pipeline_wait has returned for frame f
+    int unwaited = 0;                              // frames of the group that were presented and have not been waited for: their images are owed
     uint64_t first = 0; int count = 0;             // tickets [first, first + count)
     bool drained = true;                           // the host has waited for the group's last add: its buffers may be reused at once
   };
@@ -256,6 +258,12 @@ struct dr_context {
   struct PipePending { float st[13]; int W, H; float bg; uint64_t seed; int div; };
   std::vector<PipePending> pipe_pending;           // submitted, not launched yet: tickets [pipe_next - size, pipe_next)
   uint64_t pipe_next = 0;                          // ticket of the next frame
+  // a ticket stays waitable until it has been waited for: when a slot is reused, the pinned images of its frames that were presented and not yet
+  // waited for move here (swapped, not copied; their adds have run).  An entry goes at the first launch after its wait; dr_pipeline_submit refuses
+  // a frame whose launch could leave more than PIPE_PARKED_MAX images owed
+  static constexpr int PIPE_PARKED_MAX = 2 * PIPE_GROUP_MAX;
+  struct PipeParked { dr::DevMem<uint8_t, true> rgb; bool waited = false; };
+  std::map<uint64_t, PipeParked> pipe_parked;      // by ticket
   hipEvent_t pipe_last[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr};    // end of the newest launch on each render stream
   bool pipe_last_set[PIPE_STREAMS] = {false, false, false, false};
   hipEvent_t pipe_barrier = nullptr; bool pipe_barrier_set = false;      // end of the newest tile-order refresh: later launches read that order

@@ -390,6 +390,7 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
 int dr_accum_reserve_pack(dr_context* c, int slot) {
   if (!c || !c->accum || (slot != 0 && slot != 1)) { set_error("pack: no accumulator, or slot not 0/1"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   const int gx = c->accW / 8;
   const size_t run = (size_t)8 * (size_t)c->accH * 3;                 // int32 per block column
   // sized for the largest stripe of this partition (rank 0's), so that every rank's buffer can take part in one
@@ -419,6 +420,7 @@ int dr_accum_pack_stripe(dr_context* c, int slot, void** dev_ptr, uint64_t* byte
 int dr_accum_unpack_stripes(dr_context* c, const void* packed_dev, uint64_t rank_stride_bytes, int world, int first_rank, void* hip_stream) {
   if (!c || !c->accum || !packed_dev || world < 1 || first_rank < 0 || first_rank > world || (rank_stride_bytes & 15ull)) { set_error("unpack: bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // the frames submitted before are added before the stripes are written over the sums (a stream of the caller's is ordered by the caller)
   hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
   const int gx = c->accW / 8;
   const size_t run = (size_t)8 * (size_t)c->accH * 3;
@@ -456,6 +458,8 @@ int dr_accum_history_read(dr_context* c, int32_t* out) {
 
 int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
   if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // as dr_accum_device_ptr
   *dev_ptr = c->hist;
   if (bytes) *bytes = c->hist ? (uint64_t)c->accW * c->accH * sizeof(int32_t) : 0;
   return DR_OK;
@@ -474,6 +478,8 @@ int dr_accum_moments_read(dr_context* c, uint64_t* out) {
 
 int dr_accum_moments_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
   if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // as dr_accum_device_ptr
   *dev_ptr = c->m2;
   if (bytes) *bytes = c->m2 ? (uint64_t)c->accW * c->accH * sizeof(uint64_t) : 0;
   return DR_OK;
@@ -538,6 +544,9 @@ int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8) {
 
 int dr_accum_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
   if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  // the caller orders its own work on dr_context_stream(): the frames submitted before are launched, and that stream waits for their adds
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
   *dev_ptr = c->accum;
   if (bytes) *bytes = (uint64_t)c->accW * c->accH * 3 * sizeof(int32_t);
   return DR_OK;

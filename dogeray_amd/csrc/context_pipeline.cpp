@@ -55,8 +55,33 @@ dr_context::PipeSlot* pipeline_slot_of(dr_context* c, uint64_t ticket) {
   return nullptr;
 }
 
+// A slot is about to be reused and the host has waited for its last add: the images of its frames that were presented and have not been waited for
+// are still owed to the caller.  They move to the context's store (the pinned buffers are swapped, not copied); the slot, which then holds no ticket,
+// allocates new ones.
+void pipeline_park(dr_context* c, dr_context::PipeSlot& sl) {
+  for (int f = 0; f < sl.count; f++)
+    if (sl.div[f] != 0 && !sl.fwaited[f]) {
+      dr_context::PipeParked& e = c->pipe_parked[sl.first + (uint64_t)f];
+      e.rgb.swap(sl.rgb_host[f]);
+      e.waited = false;
+    }
+  sl.unwaited = 0; sl.count = 0;
+}
+
+// images owed to the caller that would be in the store after the next `launches` launches: those in it now and not waited for, and those of the slots
+// these launches reuse
+int pipeline_owed_after(const dr_context* c, int launches) {
+  int owed = 0;
+  for (const auto& kv : c->pipe_parked) owed += kv.second.waited ? 0 : 1;
+  const uint64_t depth = (uint64_t)c->pipe_streams + 1;
+  for (int k = 0; k < launches && k < (int)depth; k++) owed += c->pipe_slot[(c->pipe_groups + (uint64_t)k) % depth].unwaited;
+  return owed;
+}
+
 // launches the first n pending frames as one group
 int pipeline_flush_some(dr_context* c, int n) {
+  if (!c->pipe_parked.empty())                // images that have been waited for were the caller's until now
+    for (auto it = c->pipe_parked.begin(); it != c->pipe_parked.end();) it = it->second.waited ? c->pipe_parked.erase(it) : std::next(it);
   const dr_context::PipePending first = c->pipe_pending[0];
   const uint64_t stride = n > 1 ? c->pipe_pending[1].seed - first.seed : 0;
   const uint64_t first_ticket = c->pipe_next - (uint64_t)c->pipe_pending.size();
@@ -76,9 +101,10 @@ int pipeline_flush_some(dr_context* c, int n) {
     HIP_TRY(hipStreamWaitEvent(c->acc_stream, c->pipe_sync, 0));
     c->pipe_dirty = true;
   }
-  // the slot's previous group: its present buffers go back to the caller first, and its adds must have run
+  // the slot's previous group: its adds must have run, and the presents nobody has waited for yet stay waitable
   if (!sl.drained && sl.count > 0) { HIP_TRY(hipEventSynchronize(sl.added[sl.count - 1])); sl.drained = true; }
   if (sl.count > 0) HIP_TRY(hipStreamWaitEvent(rs, sl.added[sl.count - 1], 0));
+  if (sl.unwaited > 0) pipeline_park(c, sl);
   if (sl.elems_each != elems || sl.cap_frames < n || !sl.frames) {
     const int cap = n > c->pipe_group ? n : c->pipe_group;
     sl.cap_frames = 0;
@@ -124,6 +150,7 @@ int pipeline_flush_some(dr_context* c, int n) {
   HIP_TRY(hipEventRecord(sl.rendered, rs));
   // fold into the accumulator, in ticket order (K:2213-2218), and make the image of exactly the frames so far (K:2287)
   HIP_TRY(hipStreamWaitEvent(c->acc_stream, sl.rendered, 0));
+  sl.unwaited = 0;
   for (int f = 0; f < n; f++) {
     if (c->m2) launch_moments_add(c->acc_stream, c->accum, sl.frames + (size_t)f * elems, c->m2, (size_t)W * H);      // acc += frame; M2 += yc^2
     else launch_frame_add(c->acc_stream, c->accum, sl.frames + (size_t)f * elems, elems);
@@ -136,6 +163,7 @@ int pipeline_flush_some(dr_context* c, int n) {
       launch_present(c->acc_stream, c->accum, c->hist, sl.rgb_dev[f], W, H, div);
       HIP_TRY(hipMemcpyAsync(sl.rgb_host[f], sl.rgb_dev[f], bytes, hipMemcpyDeviceToHost, c->acc_stream));
       sl.div[f] = div;
+      sl.unwaited++;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sl.added[f], c->acc_stream));
@@ -153,8 +181,9 @@ int pipeline_flush_some(dr_context* c, int n) {
 
 namespace dr {
 
-// launches the frames submitted since the last launch: as ONE group if the launch configuration (still) has the builds that store every frame of a batch
-// separately -- an option may have changed since the frames were submitted --, else one by one
+// launches the frames submitted since the last launch, as ONE group.  Whatever changes the state a launch reads -- the scene, the stripe, the traversal,
+// the counters switch, an option -- calls this before it changes it, so the frames run with the state they were submitted under and the configuration
+// still has the builds that store every frame of a batch separately.  Were it not so, they would be launched one by one (a defence: no caller gets there)
 int pipeline_flush(dr_context* c) {
   while (!c->pipe_pending.empty()) {
     const int all = (int)c->pipe_pending.size();
@@ -180,13 +209,21 @@ int dr_pipeline_submit(dr_context* c, const float settings13[13], int W, int H, 
     DR_TRY(make_params(c, c->own_site(), settings13, W, H, background, frame_seed, probe, 1));
   }
   // a group holds frames of ONE view whose seeds are in arithmetic progression (what a progressive render submits): anything else starts a new group
+  bool closes = false;
   if (!c->pipe_pending.empty()) {
     const dr_context::PipePending& p0 = c->pipe_pending[0];
     const dr_context::PipePending& pl = c->pipe_pending.back();
     const bool same_view = memcmp(p0.st, settings13, 13 * sizeof(float)) == 0 && p0.W == W && p0.H == H && p0.bg == background;
     const bool in_step = c->pipe_pending.size() == 1 || frame_seed - pl.seed == c->pipe_pending[1].seed - p0.seed;
-    if (!same_view || !in_step) DR_TRY(pipeline_flush(c));
+    closes = !same_view || !in_step;
   }
+  // every ticket handed out stays waitable: the launch of the group this frame closes and the launch of its own group each reuse a slot, and the
+  // presents of those slots that nobody has waited for go to the store.  A frame that could overfill it is refused, never an image dropped
+  if (pipeline_owed_after(c, closes ? 2 : 1) > dr_context::PIPE_PARKED_MAX) {
+    set_error("pipeline: too many presented frames have not been waited for: call dr_pipeline_wait for the oldest tickets first");
+    return DR_ERR_INVALID;
+  }
+  if (closes) DR_TRY(pipeline_flush(c));
   dr_context::PipePending p;
   memcpy(p.st, settings13, sizeof(p.st)); p.W = W; p.H = H; p.bg = background; p.seed = frame_seed; p.div = present_divide_by;
   c->pipe_pending.push_back(p);
@@ -201,23 +238,41 @@ int dr_pipeline_wait(dr_context* c, uint64_t ticket, uint8_t* out_rgb8) {
   if (!c || !c->pipe_ready) { set_error("pipeline: nothing submitted"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   if (ticket < c->pipe_next && ticket + c->pipe_pending.size() >= c->pipe_next) DR_TRY(pipeline_flush(c));      // submitted, its group not launched yet: it is now
-  dr_context::PipeSlot* sl = pipeline_slot_of(c, ticket);
-  if (!sl) { set_error("pipeline: ticket not in flight (the pipeline keeps pipe_streams + 1 groups of frames)"); return DR_ERR_INVALID; }
-  const int f = (int)(ticket - sl->first);
-  HIP_TRY(hipEventSynchronize(sl->added[f]));
-  sl->fwaited[f] = true;
-  if (f == sl->count - 1) sl->drained = true;
-  if (out_rgb8) {
-    if (!sl->div[f]) { set_error("pipeline: that frame was submitted without a present"); return DR_ERR_INVALID; }
-    memcpy(out_rgb8, sl->rgb_host[f], (size_t)c->accW * c->accH * 3);
+  const size_t bytes = (size_t)c->accW * c->accH * 3;
+  if (dr_context::PipeSlot* sl = pipeline_slot_of(c, ticket)) {
+    const int f = (int)(ticket - sl->first);
+    HIP_TRY(hipEventSynchronize(sl->added[f]));
+    if (!sl->fwaited[f] && sl->div[f]) sl->unwaited--;
+    sl->fwaited[f] = true;
+    if (f == sl->count - 1) sl->drained = true;
+    if (out_rgb8) {
+      if (!sl->div[f]) { set_error("pipeline: that frame was submitted without a present"); return DR_ERR_INVALID; }
+      memcpy(out_rgb8, sl->rgb_host[f], bytes);
+    }
+    return DR_OK;
   }
+  // its slot has been reused: the frame has been added (the launch that took the slot waited for that), and its image, if it is still owed, was kept
+  auto parked = c->pipe_parked.find(ticket);
+  if (parked != c->pipe_parked.end()) {
+    parked->second.waited = true;
+    if (out_rgb8) memcpy(out_rgb8, parked->second.rgb, bytes < parked->second.rgb.n ? bytes : parked->second.rgb.n);
+    return DR_OK;
+  }
+  if (ticket >= c->pipe_next - c->pipe_pending.size()) { set_error("pipeline: no such ticket (dr_pipeline_submit has not handed it out)"); return DR_ERR_INVALID; }
+  if (out_rgb8) { set_error("pipeline: that frame was submitted without a present (or its image was handed out by an earlier wait and has been released)"); return DR_ERR_INVALID; }
   return DR_OK;
 }
 
 int dr_pipeline_image(dr_context* c, uint64_t ticket, const uint8_t** rgb8) {
   if (!c || !c->pipe_ready || !rgb8) { set_error("pipeline: nothing submitted, or null argument"); return DR_ERR_INVALID; }
   dr_context::PipeSlot* sl = pipeline_slot_of(c, ticket);
-  if (!sl) { set_error("pipeline: ticket not in flight (the pipeline keeps pipe_streams + 1 groups of frames)"); return DR_ERR_INVALID; }
+  if (!sl) {
+    auto parked = c->pipe_parked.find(ticket);
+    if (parked == c->pipe_parked.end()) { set_error("pipeline: no image of that ticket (not handed out, submitted without a present, or released after its wait)"); return DR_ERR_INVALID; }
+    if (!parked->second.waited) { set_error("pipeline: dr_pipeline_wait(ticket) comes first"); return DR_ERR_INVALID; }
+    *rgb8 = parked->second.rgb;
+    return DR_OK;
+  }
   const int f = (int)(ticket - sl->first);
   if (!sl->fwaited[f]) { set_error("pipeline: dr_pipeline_wait(ticket) comes first"); return DR_ERR_INVALID; }
   if (!sl->div[f]) { set_error("pipeline: that frame was submitted without a present"); return DR_ERR_INVALID; }

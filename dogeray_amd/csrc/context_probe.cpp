@@ -34,6 +34,7 @@ int dr_context_probe_gather(dr_context* c, uint32_t hot_records, int iters, doub
   if (!c || !records_per_s || iters < 1) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wide) { set_error("no wide walk resident"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // timed behind the frames submitted before, not beside them
   RenderParams P;
   memset(&P, 0, sizeof(P));
   fill_scene(c, P);
@@ -91,6 +92,8 @@ int dr_context_probe_trace(dr_context* c, const float settings13[13], int W, int
                            double* rays_per_s, uint64_t* n_rays, uint64_t* mismatches) {
   if (!c || !settings13 || !rays_per_s || !n_rays || !mismatches || frames < 1 || variant < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the trace probe needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
   // 1. the rays of one frame in wavefront order (log_frame_rays); `frames` copies of the list make the probe's launch long enough to time
   std::vector<float> packed;
   DR_TRY(log_frame_rays(c, settings13, W, H, background, frame_seed, 0x7fffffffull / (size_t)frames, packed));
@@ -135,6 +138,8 @@ int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int 
                           uint64_t capacity, uint64_t* n_rays) {
   if (!c || !settings13 || !n_rays || (capacity > 0 && (!origin || !dir))) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wide || traversal_of(c) != DR_TRAVERSAL_WIDE || !uses_persistent(c)) { set_error("the ray log needs the wide walk and the persistent kernel"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
   std::vector<float> packed;
   DR_TRY(log_frame_rays(c, settings13, W, H, background, frame_seed, 0x7fffffffull, packed));
   const size_t n = packed.size() / 8;

@@ -269,15 +269,24 @@ int dr_context_synchronize(dr_context* c);
  *                        The frame's group is launched when it is full, when a frame that does not continue it is submitted, or when it is waited for.
  *   dr_pipeline_wait     blocks until that frame has been added (and presented); out_rgb8 may be NULL.  A caller that keeps two groups' worth of
  *                        frames in flight gets the batched rate; one that waits for every frame before it submits the next gets groups of one
- *                        (the rate of round 3's pipeline).  Tickets of the newest pipe_streams + 1 groups can be waited for.
+ *                        (the rate of round 3's pipeline).
  *   dr_render_accumulate_pipelined   nframes frames, no presents: dr_render_accumulate's result through the pipeline.
- * Any other call on the context is ordered behind the frames submitted before it (their groups are launched first). */
+ * Every ticket handed out stays waitable until it has been waited for, however many groups have been launched since: the image of a frame that was
+ * presented is kept until dr_pipeline_wait(ticket) has returned and the next group is launched after that; a frame without a present whose buffers
+ * have been reused has finished, and dr_pipeline_wait(ticket, NULL) returns DR_OK for it.  At most 32 images are kept for frames whose buffers have
+ * been reused: dr_pipeline_submit returns DR_ERR_INVALID ("... call dr_pipeline_wait for the oldest tickets first") for a frame that could take
+ * them beyond that -- it refuses, it never drops an image.  A ticket that was never handed out is DR_ERR_INVALID.  Setting "pipe_streams" to another
+ * value drains the pipeline and starts again from ticket 0; earlier tickets are gone.
+ * A frame is launched with the state it was submitted under: a scene upload, dr_context_set_stripe, dr_context_set_traversal,
+ * dr_stats_enable_counters and dr_context_set_option first launch the frames still held, and apply to frames submitted AFTER them.  Any other call
+ * on the context -- the dr_stats_* readers, dr_accum_device_ptr and its kin, and the probes among them -- is ordered behind the frames submitted
+ * before it (their groups are launched first, and the context's stream waits for them). */
 int dr_pipeline_submit(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed,
                        int present_divide_by, uint64_t* ticket);
 int dr_pipeline_wait(dr_context* c, uint64_t ticket, uint8_t* out_rgb8);
 /* the presented image of a ticket that has been waited for, in place: a pointer into the library's pinned download buffer (W * H * 3 bytes, row-major
- * RGB8), valid until pipe_streams + 1 more frames have been submitted -- for a caller that uploads it to a texture anyway (K:2243-2275) and would
- * rather not copy 6 MB per frame twice */
+ * RGB8), valid until the next call that may launch a group (dr_pipeline_submit, and any call ordered behind held frames): the launch may reuse or release
+ * it -- for a caller that uploads it to a texture anyway (K:2243-2275) and would rather not copy 6 MB per frame twice */
 int dr_pipeline_image(dr_context* c, uint64_t ticket, const uint8_t** rgb8);
 int dr_render_accumulate_pipelined(dr_context* c, const float settings13[13], int W, int H, float background,
                                    uint64_t frame_seed, uint64_t seed_stride, int nframes);
