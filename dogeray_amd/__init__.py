@@ -221,6 +221,13 @@ _API = [
     ("dr_kat_hit", C.c_int, [_VP, C.c_int] + [_VP] * 5),
     ("dr_kat_normal", C.c_int, [_VP, C.c_int] + [_VP] * 6),
     ("dr_kat_trace", C.c_int, [_VP, C.c_int, C.c_int] + [_VP] * 4),
+    ("dr_kat_sample", C.c_int, [_VP, C.c_int] + [_VP] * 7),
+    ("dr_kat_outside", C.c_int, [_VP, C.c_int, _VP, _VP]),
+    ("dr_kat_tex", C.c_int, [_VP, C.c_int] + [_VP] * 4),
+    ("dr_kat_bounce", C.c_int, [_VP, C.c_int] + [_VP] * 12),
+    ("dr_kat_miss", C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int, C.c_float, _VP]),
+    ("dr_kat_camera", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int] + [_VP] * 6),
+    ("dr_kat_store", C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP]),
     ("dr_stats_tile_order", C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t), _VP, _VP]),
     ("dr_kat_tile_feedback", C.c_int, [_VP] + [C.c_int] * 5 + [_VP] * 4),
 ]
@@ -1050,6 +1057,59 @@ class Context:
         idx = np.zeros(n, dtype=np.int32)
         _check(lib().dr_kat_trace(self._h, int(variant), n, _p(o), _p(d), _p(t), _p(idx)))
         return t, idx
+
+    # the shading step: where a hook returns "both forms" the arrays have a leading axis of 2 -- [0] the plain functions, [1] what the persistent kernel runs
+    def kat_sample(self, seed, warm, kind):
+        """dr_kat_sample: (point float32[2, n, 3], next uint32[2, n, 2]) -- rand_in_unit_sphere / rand_in_unit_disk, and rand_points_merged"""
+        seed, warm, kind = np.ascontiguousarray(seed, np.uint64), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(kind, np.int32)
+        n = seed.shape[0]
+        pt, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
+        _check(lib().dr_kat_sample(self._h, n, _p(seed), _p(warm), _p(kind), _p(pt[0]), _p(nx[0]), _p(pt[1]), _p(nx[1])))
+        return pt, nx
+
+    def kat_outside(self, d2):
+        d2 = _f32(d2)
+        out = np.zeros(d2.shape[0], np.int32)
+        _check(lib().dr_kat_outside(self._h, d2.shape[0], _p(d2), _p(out)))
+        return out
+
+    def kat_tex(self, tex, u, v):
+        tex, u, v = np.ascontiguousarray(tex, np.int32), _f32(u), _f32(v)
+        out = np.zeros(tex.shape[0], np.uint32)
+        _check(lib().dr_kat_tex(self._h, tex.shape[0], _p(tex), _p(u), _p(v), _p(out)))
+        return out
+
+    def kat_bounce(self, obj_index, o, d, t, atten, seed, warm):
+        """dr_kat_bounce: (alive int32[2, n], origin, direction, attenuation float32[2, n, 3], next uint32[2, n, 2]) -- shade_hit, and the split"""
+        idx, warm, seed = np.ascontiguousarray(obj_index, np.int32), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(seed, np.uint64)
+        o, d, t, atten = _f32(o), _f32(d), _f32(t), _f32(atten)
+        n = idx.shape[0]
+        alive, nx = np.zeros((2, n), np.int32), np.zeros((2, n, 2), np.uint32)
+        o2, d2, a2 = (np.zeros((2, n, 3), np.float32) for _ in range(3))
+        _check(lib().dr_kat_bounce(self._h, n, _p(idx), _p(o), _p(d), _p(t), _p(atten), _p(seed), _p(warm), _p(alive), _p(o2), _p(d2), _p(a2), _p(nx)))
+        return alive, o2, d2, a2, nx
+
+    def kat_miss(self, d, atten, backtex, background):
+        d, atten = _f32(d), _f32(atten)
+        out = np.zeros((d.shape[0], 3), np.float32)
+        _check(lib().dr_kat_miss(self._h, d.shape[0], _p(d), _p(atten), int(backtex), float(background), _p(out)))
+        return out
+
+    def kat_camera(self, settings13, W, H, frame_seed, stride, x, y, sample):
+        """dr_kat_camera: (origin, dir float32[2, n, 3], next uint32[2, n, 2]) -- camera_ray, and the split"""
+        st = _f32(settings13)
+        x, y, sample = (np.ascontiguousarray(a, np.int32) for a in (x, y, sample))
+        n = x.shape[0]
+        o, d, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
+        _check(lib().dr_kat_camera(self._h, _p(st), int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF, n, _p(x), _p(y), _p(sample),
+                                   _p(o), _p(d), _p(nx)))
+        return o, d, nx
+
+    def kat_store(self, color, spp):
+        color = _f32(color)
+        out = np.zeros((color.shape[0], 3), np.int32)
+        _check(lib().dr_kat_store(self._h, color.shape[0], _p(color), int(spp), _p(out)))
+        return out
 
     def kat_tile_feedback(self, pixel_cost, regions, heavy_factor, split_steps, split_limit, ntiles=None):
         """The feedback kernels on a flat uint32 plane of ntiles * 64 pixel costs (dr_kat_tile_feedback): (tile_cost uint32[ntiles],

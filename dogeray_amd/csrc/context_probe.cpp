@@ -242,6 +242,142 @@ int dr_kat_normal(dr_context* c, int n, const int32_t* object_index, const float
   return bc.get(texco, m);
 }
 
+// ---- the shading step (kernels_kat_shade.hip; device_kat_shade.hpp says what each element writes)
+int dr_kat_sample(dr_context* c, int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point_plain, uint32_t* next_plain,
+                  float* point_merged, uint32_t* next_merged) {
+  KAT_PRE(n);
+  if (!seed || !warm || !kind || !point_plain || !next_plain || !point_merged || !next_merged) { set_error("null argument"); return DR_ERR_INVALID; }
+  for (int i = 0; i < n; i++)
+    if (warm[i] < 0 || warm[i] > 4096 || (kind[i] != 0 && kind[i] != 2 && kind[i] != 3)) { set_error("warm must be 0 .. 4096, kind 0, 2 or 3"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  DevMem<uint64_t> bs; DevMem<int32_t> bw, bk; DevMem<float> p1, p2; DevMem<uint32_t> n1, n2;
+  DR_TRY(bs.alloc(m)); DR_TRY(bw.alloc(m)); DR_TRY(bk.alloc(m)); DR_TRY(p1.alloc(3 * m)); DR_TRY(p2.alloc(3 * m)); DR_TRY(n1.alloc(2 * m)); DR_TRY(n2.alloc(2 * m));
+  DR_TRY(bs.put(seed, m)); DR_TRY(bw.put(warm, m)); DR_TRY(bk.put(kind, m));
+  launch_kat_sample(c->stream, n, bs.p, bw.p, bk.p, p1.p, n1.p, p2.p, n2.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(p1.get(point_plain, 3 * m)); DR_TRY(n1.get(next_plain, 2 * m)); DR_TRY(p2.get(point_merged, 3 * m));
+  return n2.get(next_merged, 2 * m);
+}
+
+int dr_kat_outside(dr_context* c, int n, const float* d2, int32_t* out) {
+  KAT_PRE(n);
+  if (!d2 || !out) { set_error("null argument"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  DevMem<float> bd; DevMem<int32_t> bo;
+  DR_TRY(bd.alloc((size_t)n)); DR_TRY(bo.alloc((size_t)n));
+  DR_TRY(bd.put(d2, (size_t)n));
+  launch_kat_outside(c->stream, n, bd.p, bo.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bo.get(out, (size_t)n);
+}
+
+int dr_kat_tex(dr_context* c, int n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba) {
+  KAT_PRE(n);
+  if (!c->walk || !tex || !u || !v || !rgba) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
+  for (int i = 0; i < n; i++)
+    if (tex[i] < 0 || tex[i] >= c->n_tex) { set_error("texture index out of range"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  DevMem<int32_t> bt; DevMem<float> bu, bv; DevMem<uint32_t> bo;
+  DR_TRY(bt.alloc((size_t)n)); DR_TRY(bu.alloc((size_t)n)); DR_TRY(bv.alloc((size_t)n)); DR_TRY(bo.alloc((size_t)n));
+  DR_TRY(bt.put(tex, (size_t)n)); DR_TRY(bu.put(u, (size_t)n)); DR_TRY(bv.put(v, (size_t)n));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.tex = c->tex; P.texels = c->texels;
+  launch_kat_tex(c->stream, P, n, bt.p, bu.p, bv.p, bo.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bo.get(rgba, (size_t)n);
+}
+
+int dr_kat_bounce(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, const float* atten,
+                  const uint64_t* seed, const int32_t* warm, int32_t* alive, float* o_out, float* d_out, float* atten_out, uint32_t* next) {
+  KAT_PRE(n);
+  if (!c->walk || !object_index || !o || !d || !t || !atten || !seed || !warm || !alive || !o_out || !d_out || !atten_out || !next) {
+    set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID;
+  }
+  std::vector<int32_t> slot_of((size_t)c->n_prims, -1), slots((size_t)n);
+  for (int sidx = 0; sidx < c->n_prims; sidx++) slot_of[(size_t)c->slot_to_orig[(size_t)sidx]] = sidx;
+  for (int i = 0; i < n; i++) {
+    if (object_index[i] < 0 || object_index[i] >= c->n_prims) { set_error("object index out of range"); return DR_ERR_INVALID; }
+    if (warm[i] < 0 || warm[i] > 4096) { set_error("warm must be 0 .. 4096"); return DR_ERR_INVALID; }
+    slots[(size_t)i] = slot_of[(size_t)object_index[i]];
+  }
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  DevMem<int32_t> bs, bw, ba; DevMem<float> bo, bd, bt, bat, o2, d2, a2; DevMem<uint64_t> bseed; DevMem<uint32_t> nx;
+  DR_TRY(bs.alloc(m)); DR_TRY(bw.alloc(m)); DR_TRY(bo.alloc(3 * m)); DR_TRY(bd.alloc(3 * m)); DR_TRY(bt.alloc(m)); DR_TRY(bat.alloc(3 * m)); DR_TRY(bseed.alloc(m));
+  DR_TRY(ba.alloc(2 * m)); DR_TRY(o2.alloc(6 * m)); DR_TRY(d2.alloc(6 * m)); DR_TRY(a2.alloc(6 * m)); DR_TRY(nx.alloc(4 * m));
+  DR_TRY(bs.put(slots.data(), m)); DR_TRY(bw.put(warm, m)); DR_TRY(bo.put(o, 3 * m)); DR_TRY(bd.put(d, 3 * m)); DR_TRY(bt.put(t, m)); DR_TRY(bat.put(atten, 3 * m));
+  DR_TRY(bseed.put(seed, m));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
+  launch_kat_bounce(c->stream, P, n, bs.p, bo.p, bd.p, bt.p, bat.p, bseed.p, bw.p, ba.p, o2.p, d2.p, a2.p, nx.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(ba.get(alive, 2 * m)); DR_TRY(o2.get(o_out, 6 * m)); DR_TRY(d2.get(d_out, 6 * m)); DR_TRY(a2.get(atten_out, 6 * m));
+  return nx.get(next, 4 * m);
+}
+
+int dr_kat_miss(dr_context* c, int n, const float* d, const float* atten, int backtex, float background, float* rgb) {
+  KAT_PRE(n);
+  if (!c->walk || !d || !atten || !rgb) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
+  if (backtex >= c->n_tex) { set_error("backtex refers to a texture that is not loaded"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n * 3;
+  DevMem<float> bd, ba, bo;
+  DR_TRY(bd.alloc(m)); DR_TRY(ba.alloc(m)); DR_TRY(bo.alloc(m));
+  DR_TRY(bd.put(d, m)); DR_TRY(ba.put(atten, m));
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.tex = c->tex; P.texels = c->texels; P.backtex = backtex; P.bgint = background;
+  launch_kat_miss(c->stream, P, n, bd.p, ba.p, bo.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bo.get(rgb, m);
+}
+
+int dr_kat_camera(dr_context* c, const float settings13[13], int W, int H, uint64_t frame_seed, uint32_t seed_stride, int n, const int32_t* x,
+                  const int32_t* y, const int32_t* sample, float* origin, float* dir, uint32_t* next) {
+  KAT_PRE(n);
+  if (!settings13 || !x || !y || !sample || !origin || !dir || !next) { set_error("null argument"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  RenderParams P;
+  DR_TRY(make_params(c, c->own_site(), settings13, W, H, 0.0f, frame_seed, P, 1));      // the view as a render launch fills it
+  P.seed_stride = seed_stride;                                                          // (a launch's is 8 * its block columns)
+  const size_t m = (size_t)n;
+  DevMem<int32_t> bx, by, bs; DevMem<float> bo, bd; DevMem<uint32_t> nx;
+  DR_TRY(bx.alloc(m)); DR_TRY(by.alloc(m)); DR_TRY(bs.alloc(m)); DR_TRY(bo.alloc(6 * m)); DR_TRY(bd.alloc(6 * m)); DR_TRY(nx.alloc(4 * m));
+  DR_TRY(bx.put(x, m)); DR_TRY(by.put(y, m)); DR_TRY(bs.put(sample, m));
+  launch_kat_camera(c->stream, P, n, bx.p, by.p, bs.p, bo.p, bd.p, nx.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(bo.get(origin, 6 * m)); DR_TRY(bd.get(dir, 6 * m));
+  return nx.get(next, 4 * m);
+}
+
+int dr_kat_store(dr_context* c, int n, const float* color, int spp, int32_t* out) {
+  KAT_PRE(n);
+  if (!color || !out || spp < 1) { set_error("null argument, or spp < 1"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
+  const float st[13] = {0, 0, 2, 0, 0, 0, 0, 1, 45, 1, (float)spp, 1, -1};      // any view: the store reads its sample scale alone
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(st, 8, 8, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
+  const size_t m = (size_t)n * 3;
+  DevMem<float> bc; DevMem<int32_t> bo;
+  DR_TRY(bc.alloc(m)); DR_TRY(bo.alloc(m));
+  DR_TRY(bc.put(color, m));
+  P.W = n; P.H = 1; P.out = bo.p; P.accumulate = 0;                            // colour i is pixel (i, 0) of an n x 1 frame
+  launch_kat_store(c->stream, P, n, bc.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return bo.get(out, m);
+}
+
 int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits) {
   KAT_PRE(n);
   if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }

@@ -1,6 +1,7 @@
 // Launchers of the device code, one translation unit per family of kernels:
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
 //   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
+//   kernels_kat_shade.hip     known-answer kernels of the shading step: samplers, texel fetch, one bounce, background, camera ray, store
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
@@ -81,6 +82,19 @@ void launch_kat_sphere(hipStream_t stream, int n, const float* o, const float* d
 void launch_kat_optics(hipStream_t stream, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* sch);
 void launch_kat_normal(hipStream_t stream, const RenderParams& P, int n, const int32_t* slot, const float* o, const float* d, const float* t, float* nrm, float* texco);
 void launch_kat_hit(hipStream_t stream, const RenderParams& P, int traversal, int n, const float* o, const float* d, float* t, int32_t* slot, int32_t* visits);
+
+// kernels_kat_shade.hip: the shading step's known-answer kernels (device_kat_shade.hpp says what each writes; "2": both forms, form f of element i at f * n + i)
+void launch_kat_sample(hipStream_t stream, int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* p_plain, uint32_t* n_plain,
+                       float* p_merged, uint32_t* n_merged);
+void launch_kat_outside(hipStream_t stream, int n, const float* d2, int32_t* out);
+void launch_kat_tex(hipStream_t stream, const RenderParams& P, int n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba);
+void launch_kat_bounce(hipStream_t stream, const RenderParams& P, int n, const int32_t* slot, const float* o, const float* d, const float* t,
+                       const float* atten, const uint64_t* seed, const int32_t* warm, int32_t* alive2, float* o2, float* d2, float* atten2,
+                       uint32_t* next2);
+void launch_kat_miss(hipStream_t stream, const RenderParams& P, int n, const float* d, const float* atten, float* rgb);
+void launch_kat_camera(hipStream_t stream, const RenderParams& P, int n, const int32_t* x, const int32_t* y, const int32_t* s, float* origin2,
+                       float* dir2, uint32_t* next2);
+void launch_kat_store(hipStream_t stream, const RenderParams& P, int n, const float* color);      // into P.out, pixel (i, 0) of an n x 1 frame
 
 // kernels_aov.hip: the window (x0, y0, w, h) of the pixel grid and the channels to write (null: not written), each a row-major w x h plane
 // (pixel (x, y) at (y - y0) * w + (x - x0); normal / albedo / dir 3 floats per pixel, uv 2)

@@ -727,6 +727,38 @@ int dr_kat_optics(dr_context* c, int n, const float* v, const float* nrm, const 
  * the normalised, not yet flipped normal and the interpolated texture coordinate (z = 0), 3 floats each */
 int dr_kat_normal(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t,
                   float* normal, float* texco);
+/* The shading step, function by function (device_rng.hpp, device_surface.hpp, device_shade.hpp), one element per GPU lane.  Where the render kernels
+ * have two forms of a step, a hook runs BOTH on copies of the same generator state and returns both: the results of form 0 (the plain functions) for
+ * the n elements, then those of form 1 (what the persistent kernel runs).  A generator is Xorwow::init(seed[i]) followed by warm[i] (0 .. 4096) calls
+ * of next(); `next` holds the two outputs that follow what the step drew, which proves how many draws it consumed.
+ *
+ * dr_kat_sample: kind[i] 3 = a point in the unit sphere, 2 = in the unit disk, 0 = nothing (point 0).  point_plain / next_plain: rand_in_unit_sphere /
+ * rand_in_unit_disk; point_merged / next_merged: rand_points_merged with the lane's kind -- the 64 lanes of a wave run ONE loop, so the order of the
+ * elements decides which kinds share a loop.  Points 3 floats, next 2 words per element. */
+int dr_kat_sample(dr_context* c, int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point_plain,
+                  uint32_t* next_plain, float* point_merged, uint32_t* next_merged);
+/* outside_unit on a squared length: out[i] = 1 where the rejection loops reject */
+int dr_kat_outside(dr_context* c, int n, const float* d2, int32_t* out);
+/* tex_fetch of texture tex[i] of the resident scene at (u[i], v[i]): the texel word r | g << 8 | b << 16 */
+int dr_kat_tex(dr_context* c, int n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba);
+/* One bounce of the ray (o, d) with attenuation atten on object object_index[i] (index in the .rts file) of the resident scene at a GIVEN distance t[i]
+ * -- no traversal, as dr_kat_normal.  Form 0: shade_hit; form 1: shade_prepare, the point of rand_points_merged (kind 3 for the materials that draw
+ * one, else 0), shade_scatter.  Per form and element: alive (1: the path continues; 0: it ended at an emissive surface or an unknown material -- the
+ * ray is returned as it came and atten_out holds the radiance), the ray and attenuation afterwards, next.  alive[2 n], o_out / d_out / atten_out
+ * [2 n * 3], next[2 n * 2]. */
+int dr_kat_bounce(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, const float* atten,
+                  const uint64_t* seed, const int32_t* warm, int32_t* alive, float* o_out, float* d_out, float* atten_out, uint32_t* next);
+/* shade_miss: the background of a ray of direction d and attenuation atten that hit nothing (backtex: a texture of the resident scene, -1 = the sky
+ * gradient; background: its intensity): rgb[n * 3] */
+int dr_kat_miss(dr_context* c, int n, const float* d, const float* atten, int backtex, float background, float* rgb);
+/* The camera ray of sample sample[i] of pixel (x[i], y[i]) of the view (settings13, W, H) as a render launch fills it, the generator seeded with
+ * sample_seed for frame_seed -- frame_seed + sample * 0x9E3779B97F4A7C15 + (uint32)(x + y * seed_stride); a launch's seed_stride is 8 * its block
+ * columns.  Form 0: camera_ray; form 1: camera_prepare, the point of rand_points_merged (kind 2), camera_finish.  origin / dir [2 n * 3],
+ * next[2 n * 2].  Needs an uploaded scene, as every render launch. */
+int dr_kat_camera(dr_context* c, const float settings13[13], int W, int H, uint64_t frame_seed, uint32_t seed_stride, int n, const int32_t* x,
+                  const int32_t* y, const int32_t* sample, float* origin, float* dir, uint32_t* next);
+/* store_pixel (not accumulating) of a pixel's summed colour for spp samples: out[n * 3] */
+int dr_kat_store(dr_context* c, int n, const float* color, int spp, int32_t* out);
 /* The plane arithmetic of the wide walk's node test (device_wide.hpp wide_node_test): for word w[i] (four plane bytes) t_mix[4 i + k] =
  * fma(byte_k read as the f16 denormal byte * 2^-24 inside v_fma_mix_f32, a[i] * 2^24, b[i]) and t_cvt[4 i + k] = fma((float)byte_k, a[i], b[i]):
  * the two must agree bit for bit (a[i] * 2^24 must not overflow) -- the check that the instruction keeps f16 denormals */

@@ -705,93 +705,115 @@ inline void tex_fetch(const Texture& t, float u, float v, uint8_t out[4], Counte
   out[0] = p[0]; out[1] = p[1]; out[2] = p[2]; out[3] = p[3];
 }
 
-// raycolor K:787-982
+// raycolor K:787-982, split at its seams into the functions it calls itself (bounce: the "t > 0" branch of one iteration, K:806-944; miss: the
+// background, K:951-976), so that the known-answer entry points below (orc_kat_bounce, orc_kat_miss) run the code that renders.
+enum Branch {          // the path one bounce took
+  BR_DIFFUSE = 0, BR_DIFFUSE_NORMALISED = 1, BR_MIRROR = 2, BR_METAL = 3, BR_GLOSSY_METAL = 4, BR_GLOSSY_DIFFUSE = 5,
+  BR_GLASS_CANNOT_REFRACT = 6, BR_GLASS_SCHLICK = 7, BR_GLASS_REFRACT = 8, BR_EMISSIVE = 9
+};
+// One bounce on object g at distance t: rayo / raydir / atten updated.  BR_EMISSIVE (emissive and every unknown material): the path ends and atten
+// holds its radiance (K:941-944).
+int bounce(const Scene& s, int g, float t, V3& rayo, V3& raydir, V3& atten, Xorwow& rng, Counters& c) {
+  V3 texco = v3(0, 0, 0);                       // C6
+  c.S++;
+  V3 hitpoint = rayo + splat(t) * raydir;
+  V3 N = getnormal(s, g, rayo, hitpoint, raydir, texco);
+  bool front = dot(raydir, N) < 0;             // K:235, 819
+  N = front ? N : N * splat(-1);
+  const Obj& b = s.objs[(size_t)g];
+  V3 ocolor = b.col;
+  float rough = b.addional.y;
+  if (b.texnum >= 0) {                         // K:829-833
+    uint8_t C[4]; tex_fetch(s.tex[(size_t)b.texnum], texco.x, -texco.y + 1, C, c);
+    ocolor = v3(float(C[0]) / 255, float(C[1]) / 255, float(C[2]) / 255);
+  } else if (b.tex) {
+    ocolor = checker(texco, splat((float)0.8), b.col);
+  }
+  if (b.rtexnum >= 0) {                        // K:840-844
+    uint8_t C[4]; tex_fetch(s.tex[(size_t)b.rtexnum], texco.x, -texco.y + 1, C, c);
+    rough = float(C[0]) / 255 / 2;
+  }
+  if (b.mat == 0) {                            // diffuse K:848-866
+    V3 target = hitpoint + N;
+    const bool plain = b.addional.x == 0;
+    if (plain) target = target + rand_in_unit_sphere(rng);
+    else target = target + normalized(rand_in_unit_sphere(rng));
+    atten = atten * ocolor;
+    rayo = hitpoint;
+    raydir = normalized(target - hitpoint);
+    return plain ? BR_DIFFUSE : BR_DIFFUSE_NORMALISED;
+  } else if (b.mat == 2) {                     // mirror K:867-874
+    atten = atten * ocolor;
+    rayo = hitpoint;
+    raydir = reflect(normalized(raydir), N);
+    return BR_MIRROR;
+  } else if (b.mat == 3) {                     // metal K:875-883
+    V3 refl = reflect(normalized(raydir), N);
+    atten = atten * ocolor;
+    rayo = hitpoint;
+    raydir = refl + splat(rough) * rand_in_unit_sphere(rng);
+    return BR_METAL;
+  } else if (b.mat == 5) {                     // glossy K:884-912
+    float r = randy(rng);
+    if (r > 0.8) {
+      V3 refl = reflect(normalized(raydir), N);
+      atten = atten * ocolor;
+      rayo = hitpoint;
+      raydir = refl + splat(rough) * rand_in_unit_sphere(rng);
+      return BR_GLOSSY_METAL;
+    } else {
+      V3 target = hitpoint + N;
+      target = target + rand_in_unit_sphere(rng);
+      atten = atten * ocolor;
+      rayo = hitpoint;
+      raydir = normalized(target - hitpoint);
+      return BR_GLOSSY_DIFFUSE;
+    }
+  } else if (b.mat == 4) {                     // glass K:914-939
+    float ir = b.addional.y;
+    float ratio = front ? (float)(1.0 / (double)ir) : ir;
+    float cos_theta = (float)fmin((double)dot(normalized(raydir) * splat(-1), N), 1.0);   // C3
+    float sin_theta = (float)sqrt(1.0 - (double)(cos_theta * cos_theta));
+    bool cannot = (ratio * sin_theta) > 1.0;
+    V3 out;
+    int br = BR_GLASS_REFRACT;
+    if (cannot) br = BR_GLASS_CANNOT_REFRACT;                           // (|| short-circuits: no draw)
+    else if (reflectance(cos_theta, ratio) > randy(rng)) br = BR_GLASS_SCHLICK;
+    if (br != BR_GLASS_REFRACT) out = reflect(normalized(raydir), N);
+    else out = refract(normalized(raydir), N, ratio);
+    atten = atten * ocolor;
+    rayo = hitpoint;
+    raydir = out;
+    return br;
+  }
+  atten = ocolor * atten;                      // emissive K:941-944
+  return BR_EMISSIVE;
+}
+// The background of a ray that hit nothing, K:951-976
+V3 miss(const Scene& s, V3 raydir, V3 atten, int backtex, float bgint, Counters& c) {
+  if (backtex > -1) {                          // env map K:953-966
+    V3 u = normalized(raydir);
+    float m = (float)(2. * sqrt(sqd((double)u.x) + sqd((double)u.y) + sqd((double)u.z + 1.)));
+    V3 tt = u / splat(m) + splat(.5f);
+    tt.y = -tt.y;
+    uint8_t C[4]; tex_fetch(s.tex[(size_t)backtex], tt.x, -tt.y + 1, C, c);
+    V3 col = v3(float(C[0]) / 255, float(C[1]) / 255, float(C[2]) / 255);
+    return atten * col * splat(bgint);
+  }
+  V3 u = normalized(raydir);                   // sky K:971-974
+  float t2 = (float)(0.5 * ((double)u.y + 1.0));
+  float omt = (float)(1.0 - (double)t2);
+  V3 sky = splat(omt) * v3(1.0f, 1.0f, 1.0f) + splat(t2) * v3((float)0.5, (float)0.7, (float)1.0);
+  return atten * sky * splat(bgint);
+}
 V3 raycolor(const Scene& s, V3 origin, V3 dir, int max_depth, int backtex, float bgint, Xorwow& rng, Counters& c) {
   V3 raydir = dir, rayo = origin, atten = splat(1.0f);
   for (int i = 0; i < max_depth; i++) {
-    V3 texco = v3(0, 0, 0);                       // C6
     HitRec h = hit(s, rayo, raydir, c);
-    int g = h.idx;
-    float t = h.t;
-    if (t > 0.0) {
-      c.S++;
-      V3 hitpoint = rayo + splat(t) * raydir;
-      V3 N = getnormal(s, g, rayo, hitpoint, raydir, texco);
-      bool front = dot(raydir, N) < 0;             // K:235, 819
-      N = front ? N : N * splat(-1);
-      const Obj& b = s.objs[(size_t)g];
-      V3 ocolor = b.col;
-      float rough = b.addional.y;
-      if (b.texnum >= 0) {                         // K:829-833
-        uint8_t C[4]; tex_fetch(s.tex[(size_t)b.texnum], texco.x, -texco.y + 1, C, c);
-        ocolor = v3(float(C[0]) / 255, float(C[1]) / 255, float(C[2]) / 255);
-      } else if (b.tex) {
-        ocolor = checker(texco, splat((float)0.8), b.col);
-      }
-      if (b.rtexnum >= 0) {                        // K:840-844
-        uint8_t C[4]; tex_fetch(s.tex[(size_t)b.rtexnum], texco.x, -texco.y + 1, C, c);
-        rough = float(C[0]) / 255 / 2;
-      }
-      if (b.mat == 0) {                            // diffuse K:848-866
-        V3 target = hitpoint + N;
-        if (b.addional.x == 0) target = target + rand_in_unit_sphere(rng);
-        else target = target + normalized(rand_in_unit_sphere(rng));
-        atten = atten * ocolor;
-        rayo = hitpoint;
-        raydir = normalized(target - hitpoint);
-      } else if (b.mat == 2) {                     // mirror K:867-874
-        atten = atten * ocolor;
-        rayo = hitpoint;
-        raydir = reflect(normalized(raydir), N);
-      } else if (b.mat == 3) {                     // metal K:875-883
-        V3 refl = reflect(normalized(raydir), N);
-        atten = atten * ocolor;
-        rayo = hitpoint;
-        raydir = refl + splat(rough) * rand_in_unit_sphere(rng);
-      } else if (b.mat == 5) {                     // glossy K:884-912
-        float r = randy(rng);
-        if (r > 0.8) {
-          V3 refl = reflect(normalized(raydir), N);
-          atten = atten * ocolor;
-          rayo = hitpoint;
-          raydir = refl + splat(rough) * rand_in_unit_sphere(rng);
-        } else {
-          V3 target = hitpoint + N;
-          target = target + rand_in_unit_sphere(rng);
-          atten = atten * ocolor;
-          rayo = hitpoint;
-          raydir = normalized(target - hitpoint);
-        }
-      } else if (b.mat == 4) {                     // glass K:914-939
-        float ir = b.addional.y;
-        float ratio = front ? (float)(1.0 / (double)ir) : ir;
-        float cos_theta = (float)fmin((double)dot(normalized(raydir) * splat(-1), N), 1.0);   // C3
-        float sin_theta = (float)sqrt(1.0 - (double)(cos_theta * cos_theta));
-        bool cannot = (ratio * sin_theta) > 1.0;
-        V3 out;
-        if (cannot || reflectance(cos_theta, ratio) > randy(rng)) out = reflect(normalized(raydir), N);
-        else out = refract(normalized(raydir), N, ratio);
-        atten = atten * ocolor;
-        rayo = hitpoint;
-        raydir = out;
-      } else {                                     // emissive K:941-944
-        return ocolor * atten;
-      }
+    if (h.t > 0.0) {
+      if (bounce(s, h.idx, h.t, rayo, raydir, atten, rng, c) == BR_EMISSIVE) return atten;
     } else {
-      if (backtex > -1) {                          // env map K:953-966
-        V3 u = normalized(raydir);
-        float m = (float)(2. * sqrt(sqd((double)u.x) + sqd((double)u.y) + sqd((double)u.z + 1.)));
-        V3 tt = u / splat(m) + splat(.5f);
-        tt.y = -tt.y;
-        uint8_t C[4]; tex_fetch(s.tex[(size_t)backtex], tt.x, -tt.y + 1, C, c);
-        V3 col = v3(float(C[0]) / 255, float(C[1]) / 255, float(C[2]) / 255);
-        return atten * col * splat(bgint);
-      }
-      V3 u = normalized(raydir);                   // sky K:971-974
-      float t2 = (float)(0.5 * ((double)u.y + 1.0));
-      float omt = (float)(1.0 - (double)t2);
-      V3 sky = splat(omt) * v3(1.0f, 1.0f, 1.0f) + splat(t2) * v3((float)0.5, (float)0.7, (float)1.0);
-      return atten * sky * splat(bgint);
+      return miss(s, raydir, atten, backtex, bgint, c);
     }
   }
   return v3(0, 0, 0);                              // K:981
@@ -804,13 +826,10 @@ struct RenderArgs {    // settings[13] K:2581 + W,H + backgroundintensity + fram
   uint64_t frame_seed;
 };
 
-// Kernel K:998-1093 for one pixel
-void pixel(const Scene& s, const RenderArgs& a, int x, int y, unsigned stride, int32_t* out, Counters& c, uint32_t* visits = nullptr) {
-  const uint64_t v_before = c.V;
-  const float* st = a.settings;
-  int W = a.W, H = a.H;
-  size_t w = (size_t)x * H + y;                    // K:1006
-  out[3*w] = out[3*w+1] = out[3*w+2] = 0;
+// Kernel K:998-1093 for one pixel, split the same way: the camera block (K:1016-1052), the camera ray of one sample (K:1065-1073) and the store (K:1081-1085)
+struct Camera { V3 from, uu, vu, horizontal, vertical, llc; float lens_radius; };
+Camera camera_of(const float* st, int W, int H) {
+  Camera cam;
   float aspect = float(W / st[11]) / float(H / st[11]);            // K:1016
   float fov = (float)((double)st[8] * M_PI / 180);                 // K:1020
   float vh = (float)(2.0 * (double)tanf(fov / 2));                 // K:1023, C10
@@ -819,28 +838,49 @@ void pixel(const Scene& s, const RenderArgs& a, int x, int y, unsigned stride, i
   float focus = st[7];
   V3 vup = v3(0, 1, 0);
   V3 wu = normalized(from - at);
-  V3 uu = normalized(cross(vup, wu));
-  V3 vu = cross(wu, uu);
-  V3 horizontal = splat(focus) * splat(vw) * uu;                   // K:1047
-  V3 vertical = splat(focus) * splat(vh) * vu;
-  V3 llc = from - horizontal / splat(2) - vertical / splat(2) - splat(focus) * wu;
-  float lens_radius = st[6] / 2;
+  cam.from = from;
+  cam.uu = normalized(cross(vup, wu));
+  cam.vu = cross(wu, cam.uu);
+  cam.horizontal = splat(focus) * splat(vw) * cam.uu;              // K:1047
+  cam.vertical = splat(focus) * splat(vh) * cam.vu;
+  cam.llc = from - cam.horizontal / splat(2) - cam.vertical / splat(2) - splat(focus) * wu;
+  cam.lens_radius = st[6] / 2;
+  return cam;
+}
+inline uint64_t sample_seed(uint64_t frame_seed, int sidx, int x, int y, unsigned stride) {   // K:1065, C8
+  return frame_seed + (uint64_t)sidx * SPP_SEED_STRIDE + (uint64_t)((unsigned)x + (unsigned)y * stride);
+}
+void camera_ray(const Camera& cam, const float* st, int W, int H, int x, int y, Xorwow& rng, V3& origin, V3& dir) {
+  float nu = (float)(((double)float(x) + rng.uniform_double()) / (double)float(W / st[11]));   // K:1067
+  float nv = (float)(((double)float(y) + rng.uniform_double()) / (double)float(H / st[11]));
+  V3 rd = splat(cam.lens_radius) * rand_in_unit_disk(rng);
+  V3 offset = cam.uu * splat(rd.x) + cam.vu * splat(rd.y);
+  dir = cam.llc + splat(nu) * cam.horizontal + splat(nv) * cam.vertical - cam.from - offset;
+  origin = cam.from + offset;
+}
+void store(V3 color, float spp, int32_t* out3) {
+  float scale = (float)(1.0 / (double)spp);                         // K:1081
+  out3[0] = f2i(color.x * 255 * scale);
+  out3[1] = f2i(color.y * 255 * scale);
+  out3[2] = f2i(color.z * 255 * scale);
+}
+void pixel(const Scene& s, const RenderArgs& a, int x, int y, unsigned stride, int32_t* out, Counters& c, uint32_t* visits = nullptr) {
+  const uint64_t v_before = c.V;
+  const float* st = a.settings;
+  int W = a.W, H = a.H;
+  size_t w = (size_t)x * H + y;                    // K:1006
+  out[3*w] = out[3*w+1] = out[3*w+2] = 0;
+  const Camera cam = camera_of(st, W, H);
   V3 color = v3(0, 0, 0);
   for (int sidx = 0; sidx < st[10]; ++sidx) {                       // K:1059
     Xorwow rng;
-    rng.init(a.frame_seed + (uint64_t)sidx * SPP_SEED_STRIDE + (uint64_t)((unsigned)x + (unsigned)y * stride));  // K:1065, C8
+    rng.init(sample_seed(a.frame_seed, sidx, x, y, stride));
     c.samples++;
-    float nu = (float)(((double)float(x) + rng.uniform_double()) / (double)float(W / st[11]));   // K:1067
-    float nv = (float)(((double)float(y) + rng.uniform_double()) / (double)float(H / st[11]));
-    V3 rd = splat(lens_radius) * rand_in_unit_disk(rng);
-    V3 offset = uu * splat(rd.x) + vu * splat(rd.y);
-    V3 dir = llc + splat(nu) * horizontal + splat(nv) * vertical - from - offset;
-    color = color + raycolor(s, from + offset, dir, f2i(st[9]), f2i(st[12]), a.bgint, rng, c);
+    V3 origin, dir;
+    camera_ray(cam, st, W, H, x, y, rng, origin, dir);
+    color = color + raycolor(s, origin, dir, f2i(st[9]), f2i(st[12]), a.bgint, rng, c);
   }
-  float scale = (float)(1.0 / (double)st[10]);                      // K:1081
-  out[3*w]   = f2i(color.x * 255 * scale);
-  out[3*w+1] = f2i(color.y * 255 * scale);
-  out[3*w+2] = f2i(color.z * 255 * scale);
+  store(color, st[10], out + 3 * w);
   if (visits) visits[w] = (uint32_t)(c.V - v_before);   // node visits spent on this pixel (load-balance studies)
 }
 
@@ -1039,6 +1079,83 @@ void orc_kat_optics(int n, const float* v, const float* nrm, const float* eta, f
     refr[3*i] = r2.x; refr[3*i+1] = r2.y; refr[3*i+2] = r2.z;
     schlick[i] = reflectance(a.x, eta[i]);
   }
+}
+
+// ---- the shading step, function by function (tests/test_shade_host.py, tests/test_gpu_shade.py)
+// Xorwow::init(seed[i]), warm[i] calls of next(), then rand_in_unit_sphere (kind 3), rand_in_unit_disk (kind 2) or nothing (kind 0): point[3n] (zero for
+// kind 0) and next[2n], the generator's two following outputs -- they prove how many draws were consumed
+void orc_kat_sample(int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point, uint32_t* next) {
+  for (int i = 0; i < n; i++) {
+    Xorwow r; r.init(seed[i]);
+    for (int k = 0; k < warm[i]; k++) r.next();
+    V3 p = v3(0, 0, 0);
+    if (kind[i] == 3) p = rand_in_unit_sphere(r);
+    else if (kind[i] == 2) p = rand_in_unit_disk(r);
+    point[3 * i] = p.x; point[3 * i + 1] = p.y; point[3 * i + 2] = p.z;
+    next[2 * i] = r.next(); next[2 * i + 1] = r.next();
+  }
+}
+// the rejection test of K:645 / K:992 on a given squared length: pow(length, 2.0f) >= 1 with length = sqrtf(d2) (C1)
+void orc_kat_outside(int n, const float* d2, int32_t* out) {
+  for (int i = 0; i < n; i++) {
+    const volatile float l = sqrtf(d2[i]);
+    out[i] = sqf(l) >= 1;
+  }
+}
+// texel (r | g << 8 | b << 16 | a << 24) of texture tex[i] at (u[i], v[i]); returns -1 for a texture that is not loaded
+int orc_kat_tex(void* h, int n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba) {
+  const Scene& s = *(Scene*)h; Counters c;
+  for (int i = 0; i < n; i++) {
+    if (tex[i] < 0 || tex[i] >= (int)s.tex.size()) { g_err = "texture out of range"; return -1; }
+    uint8_t C4[4]; tex_fetch(s.tex[(size_t)tex[i]], u[i], v[i], C4, c);
+    rgba[i] = (uint32_t)C4[0] | (uint32_t)C4[1] << 8 | (uint32_t)C4[2] << 16 | (uint32_t)C4[3] << 24;
+  }
+  return 0;
+}
+// bounce() on object obj[i] at a given t[i] (no traversal, as orc_kat_normal), the generator seeded and warmed as orc_kat_sample's: branch[n] (enum
+// Branch), the ray and the attenuation afterwards (BR_EMISSIVE: the ray unchanged, atten the radiance) and the generator's two following outputs
+int orc_kat_bounce(void* h, int n, const int32_t* obj, const float* o, const float* d, const float* t, const float* atten, const uint64_t* seed,
+                   const int32_t* warm, int32_t* branch, float* o2, float* d2, float* atten2, uint32_t* next) {
+  const Scene& s = *(Scene*)h; Counters c;
+  for (int i = 0; i < n; i++) {
+    if (obj[i] < 0 || obj[i] >= s.nanum - 1) { g_err = "object out of range"; return -1; }
+    Xorwow r; r.init(seed[i]);
+    for (int k = 0; k < warm[i]; k++) r.next();
+    V3 ro = v3(o[3*i], o[3*i+1], o[3*i+2]), rd = v3(d[3*i], d[3*i+1], d[3*i+2]), at = v3(atten[3*i], atten[3*i+1], atten[3*i+2]);
+    branch[i] = bounce(s, obj[i], t[i], ro, rd, at, r, c);
+    o2[3*i] = ro.x; o2[3*i+1] = ro.y; o2[3*i+2] = ro.z;
+    d2[3*i] = rd.x; d2[3*i+1] = rd.y; d2[3*i+2] = rd.z;
+    atten2[3*i] = at.x; atten2[3*i+1] = at.y; atten2[3*i+2] = at.z;
+    next[2 * i] = r.next(); next[2 * i + 1] = r.next();
+  }
+  return 0;
+}
+int orc_kat_miss(void* h, int n, const float* d, const float* atten, int backtex, float bgint, float* rgb) {
+  const Scene& s = *(Scene*)h; Counters c;
+  if (backtex >= (int)s.tex.size()) { g_err = "backtex out of range"; return -1; }
+  for (int i = 0; i < n; i++) {
+    V3 r = miss(s, v3(d[3*i], d[3*i+1], d[3*i+2]), v3(atten[3*i], atten[3*i+1], atten[3*i+2]), backtex, bgint, c);
+    rgb[3*i] = r.x; rgb[3*i+1] = r.y; rgb[3*i+2] = r.z;
+  }
+  return 0;
+}
+// the camera ray of sample[i] of pixel (x[i], y[i]) as pixel() forms it: the generator seeded with sample_seed(frame_seed, sample, x, y, stride), then
+// camera_ray -- origin[3n], dir[3n] and the generator's two following outputs
+void orc_kat_camera(const float* settings13, int W, int H, uint64_t frame_seed, unsigned stride, int n, const int32_t* x, const int32_t* y,
+                    const int32_t* sample, float* origin, float* dir, uint32_t* next) {
+  const Camera cam = camera_of(settings13, W, H);
+  for (int i = 0; i < n; i++) {
+    Xorwow r; r.init(sample_seed(frame_seed, sample[i], x[i], y[i], stride));
+    V3 ro, rd;
+    camera_ray(cam, settings13, W, H, x[i], y[i], r, ro, rd);
+    origin[3*i] = ro.x; origin[3*i+1] = ro.y; origin[3*i+2] = ro.z;
+    dir[3*i] = rd.x; dir[3*i+1] = rd.y; dir[3*i+2] = rd.z;
+    next[2 * i] = r.next(); next[2 * i + 1] = r.next();
+  }
+}
+// store() of a pixel's summed colour for spp samples: int32[3n]
+void orc_kat_store(int n, const float* color, int spp, int32_t* out) {
+  for (int i = 0; i < n; i++) store(v3(color[3*i], color[3*i+1], color[3*i+2]), (float)spp, out + 3 * i);
 }
 
 }  // extern "C"

@@ -85,6 +85,14 @@ def lib(variant=""):
     L.orc_kat_hit.argtypes = [vp, C.c_int] + [C.c_void_p] * 4
     L.orc_kat_normal.argtypes = [vp, C.c_int] + [C.c_void_p] * 6
     L.orc_kat_optics.argtypes = [C.c_int] + [C.c_void_p] * 6
+    L.orc_kat_sample.argtypes = [C.c_int] + [C.c_void_p] * 5
+    L.orc_kat_outside.argtypes = [C.c_int] + [C.c_void_p] * 2
+    L.orc_kat_tex.argtypes = [vp, C.c_int] + [C.c_void_p] * 4
+    L.orc_kat_bounce.argtypes = [vp, C.c_int] + [C.c_void_p] * 12
+    L.orc_kat_miss.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+    L.orc_kat_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint, C.c_int] + [C.c_void_p] * 6
+    L.orc_kat_camera.restype = None
+    L.orc_kat_store.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     _libs[name] = L
     return L
 
@@ -190,6 +198,83 @@ class Scene:
         idx = np.zeros(n, dtype=np.int32)
         self.L.orc_kat_hit(self.h, n, _p(o), _p(d), _p(t), _p(idx))
         return t, idx
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise RuntimeError(self.L.orc_last_error().decode())
+
+    def kat_tex(self, tex, u, v):
+        """tex_fetch: the texel (r | g << 8 | b << 16 | a << 24) of texture tex[i] at (u[i], v[i])"""
+        tex, u, v = _i32(tex), _f32(u), _f32(v)
+        out = np.zeros(tex.shape[0], dtype=np.uint32)
+        self._ok(self.L.orc_kat_tex(self.h, tex.shape[0], _p(tex), _p(u), _p(v), _p(out)))
+        return out
+
+    def kat_bounce(self, obj_index, o, d, t, atten, seed, warm):
+        """One bounce (raycolor's t > 0 branch) on objects obj_index at given t: (branch int32[n] -- BRANCHES --, origin, direction, attenuation
+        afterwards [n, 3], the generator's two following outputs uint32[n, 2])."""
+        idx, o, d, t, atten, seed, warm = _i32(obj_index), _f32(o), _f32(d), _f32(t), _f32(atten), _u64(seed), _i32(warm)
+        n = idx.shape[0]
+        br, nx = np.zeros(n, np.int32), np.zeros((n, 2), np.uint32)
+        o2, d2, a2 = (np.zeros((n, 3), np.float32) for _ in range(3))
+        self._ok(self.L.orc_kat_bounce(self.h, n, _p(idx), _p(o), _p(d), _p(t), _p(atten), _p(seed), _p(warm), _p(br), _p(o2), _p(d2), _p(a2), _p(nx)))
+        return br, o2, d2, a2, nx
+
+    def kat_miss(self, d, atten, backtex, bgint):
+        """The background of rays that hit nothing: rgb float32[n, 3]"""
+        d, atten = _f32(d), _f32(atten)
+        out = np.zeros((d.shape[0], 3), np.float32)
+        self._ok(self.L.orc_kat_miss(self.h, d.shape[0], _p(d), _p(atten), int(backtex), float(bgint), _p(out)))
+        return out
+
+
+# orc_kat_bounce's branch values
+BRANCHES = ("diffuse", "diffuse, normalised point", "mirror", "metal", "glossy as metal", "glossy as diffuse", "glass: cannot refract",
+            "glass: reflects by Schlick", "glass: refracts", "emissive / unknown material")
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def kat_sample(seed, warm, kind):
+    """Xorwow::init(seed), warm calls of next(), then a point in the unit sphere (kind 3), the unit disk (kind 2) or nothing (0):
+    (point float32[n, 3], the generator's two following outputs uint32[n, 2])"""
+    seed, warm, kind = _u64(seed), _i32(warm), _i32(kind)
+    n = seed.shape[0]
+    pt, nx = np.zeros((n, 3), np.float32), np.zeros((n, 2), np.uint32)
+    lib().orc_kat_sample(n, _p(seed), _p(warm), _p(kind), _p(pt), _p(nx))
+    return pt, nx
+
+
+def kat_outside(d2):
+    """the rejection test on a squared length: l = sqrtf(d2); l * l >= 1 -> int32[n]"""
+    d2 = _f32(d2)
+    out = np.zeros(d2.shape[0], np.int32)
+    lib().orc_kat_outside(d2.shape[0], _p(d2), _p(out))
+    return out
+
+
+def kat_camera(settings13, W, H, frame_seed, stride, x, y, sample):
+    """The camera rays of samples `sample` of pixels (x, y) for the seeds frame_seed + sample * stride64 + (x + y * stride):
+    (origin, dir float32[n, 3], the generator's two following outputs uint32[n, 2])"""
+    st, x, y, sample = _f32(settings13), _i32(x), _i32(y), _i32(sample)
+    n = x.shape[0]
+    o, d, nx = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.uint32)
+    lib().orc_kat_camera(_p(st), int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF, n, _p(x), _p(y), _p(sample), _p(o), _p(d), _p(nx))
+    return o, d, nx
+
+
+def kat_store(color, spp):
+    """A pixel's summed colour -> the int32[n, 3] it stores for spp samples"""
+    color = _f32(color)
+    out = np.zeros((color.shape[0], 3), np.int32)
+    lib().orc_kat_store(color.shape[0], _p(color), int(spp), _p(out))
+    return out
 
 
 def settings13(s, divisor, spp=None, depth=None):

@@ -22,6 +22,7 @@
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
 #include "../dogeray_amd/csrc/device_trace.hpp"
+#include "../dogeray_amd/csrc/device_kat_shade.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
@@ -615,6 +616,79 @@ long long hk_sky_units_render(void* hv, const float* settings13, int W, int H, f
 int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 
 const char* hk_last_error() { return hk_err.c_str(); }
+
+// ---- dr_kat_sample .. dr_kat_store on the host: the same per-element bodies (device_kat_shade.hpp) in a loop, the same arguments and layouts
+// (include/dogeray_amd.h), the scene's records out of the image of wide_tree = 1.  Each returns 0, or -1 with hk_last_error.
+int hk_kat_sample(long long n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point_plain, uint32_t* next_plain, float* point_merged,
+                  uint32_t* next_merged) {
+  for (long long i = 0; i < n; i++) {
+    if (warm[i] < 0 || warm[i] > 4096 || (kind[i] != 0 && kind[i] != 2 && kind[i] != 3)) { hk_err = "warm must be 0 .. 4096, kind 0, 2 or 3"; return -1; }
+    kat_sample_lane((int)i, seed, warm, kind, point_plain, next_plain, point_merged, next_merged);
+  }
+  return 0;
+}
+int hk_kat_outside(long long n, const float* d2, int32_t* out) {
+  for (long long i = 0; i < n; i++) kat_outside_lane((int)i, d2, out);
+  return 0;
+}
+int hk_kat_tex(void* hv, long long n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba) {
+  HkScene* h = (HkScene*)hv;
+  if (!h) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.tex = h->img.tex.data(); P.texels = h->img.texels.data();
+  for (long long i = 0; i < n; i++) {
+    if (tex[i] < 0 || tex[i] >= (int)h->img.tex.size()) { hk_err = "texture index out of range"; return -1; }
+    kat_tex_lane(P, (int)i, tex, u, v, rgba);
+  }
+  return 0;
+}
+int hk_kat_bounce(void* hv, long long n, const int32_t* object_index, const float* o, const float* d, const float* t, const float* atten, const uint64_t* seed,
+                  const int32_t* warm, int32_t* alive, float* o_out, float* d_out, float* atten_out, uint32_t* next) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n > 0x7fffffff) { hk_err = "bad argument"; return -1; }
+  const DeviceImage& img = h->img;
+  const int n_prims = (int)img.slot_to_orig.size();
+  std::vector<int32_t> slot_of((size_t)n_prims, -1), slots((size_t)n);
+  for (int s = 0; s < n_prims; s++) slot_of[(size_t)img.slot_to_orig[(size_t)s]] = s;
+  for (long long i = 0; i < n; i++) {
+    if (object_index[i] < 0 || object_index[i] >= n_prims || warm[i] < 0 || warm[i] > 4096) { hk_err = "object index or warm out of range"; return -1; }
+    slots[(size_t)i] = slot_of[(size_t)object_index[i]];
+  }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
+  for (long long i = 0; i < n; i++) kat_bounce_lane(P, (int)i, slots.data(), o, d, t, atten, seed, warm, alive, o_out, d_out, atten_out, next, (int)n);
+  return 0;
+}
+int hk_kat_miss(void* hv, long long n, const float* d, const float* atten, int backtex, float background, float* rgb) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || backtex >= (int)h->img.tex.size()) { hk_err = "bad argument, or backtex refers to a texture that is not loaded"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.tex = h->img.tex.data(); P.texels = h->img.texels.data(); P.backtex = backtex; P.bgint = background;
+  for (long long i = 0; i < n; i++) kat_miss_lane(P, (int)i, d, atten, rgb);
+  return 0;
+}
+int hk_kat_camera(const float* settings13, int W, int H, uint64_t frame_seed, uint32_t seed_stride, long long n, const int32_t* x, const int32_t* y,
+                  const int32_t* sample, float* origin, float* dir, uint32_t* next) {
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(settings13, W, H, 0.0f, frame_seed, 1, 0, P)) { hk_err = why; return -1; }      // (what make_params fills the view with)
+  P.seed_stride = seed_stride;
+  for (long long i = 0; i < n; i++) kat_camera_lane(P, (int)i, x, y, sample, origin, dir, next, (int)n);
+  return 0;
+}
+int hk_kat_store(long long n, const float* color, int spp, int32_t* out) {
+  if (spp < 1) { hk_err = "spp < 1"; return -1; }
+  const float st[13] = {0, 0, 2, 0, 0, 0, 0, 1, 45, 1, (float)spp, 1, -1};
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(st, 8, 8, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  P.W = (int)n; P.H = 1; P.out = out; P.accumulate = 0;
+  for (long long i = 0; i < n; i++) kat_store_lane(P, (int)i, color);
+  return 0;
+}
 
 void* hk_scene_load(const char* rts_path, const char* texdir) {
   HkScene* h = new HkScene();

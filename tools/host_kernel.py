@@ -102,8 +102,55 @@ def lib():
         L.hk_sky_units_render.restype = C.c_longlong
         L.hk_sky_units_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
+        L.hk_kat_sample.argtypes = [C.c_longlong] + [C.c_void_p] * 7
+        L.hk_kat_outside.argtypes = [C.c_longlong, C.c_void_p, C.c_void_p]
+        L.hk_kat_tex.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4
+        L.hk_kat_bounce.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 12
+        L.hk_kat_miss.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
+        L.hk_kat_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_longlong] + [C.c_void_p] * 6
+        L.hk_kat_store.argtypes = [C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
+
+
+def _ok(rc):
+    if rc != 0:
+        raise RuntimeError(lib().hk_last_error().decode())
+
+
+# dr_kat_sample, dr_kat_outside, dr_kat_camera, dr_kat_store on the host (hk_kat_*): the same arguments and results as dogeray_amd.Context.kat_* --
+# where a hook returns both forms the arrays have a leading axis of 2, [0] the plain functions, [1] what the persistent kernel runs.  The hooks that
+# read a scene (kat_tex, kat_bounce, kat_miss) are methods of Scene.
+def kat_sample(seed, warm, kind):
+    seed, warm, kind = np.ascontiguousarray(seed, np.uint64), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(kind, np.int32)
+    n = seed.shape[0]
+    pt, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
+    _ok(lib().hk_kat_sample(n, seed.ctypes.data, warm.ctypes.data, kind.ctypes.data, pt[0].ctypes.data, nx[0].ctypes.data, pt[1].ctypes.data, nx[1].ctypes.data))
+    return pt, nx
+
+
+def kat_outside(d2):
+    d2 = np.ascontiguousarray(d2, np.float32)
+    out = np.zeros(d2.shape[0], np.int32)
+    _ok(lib().hk_kat_outside(d2.shape[0], d2.ctypes.data, out.ctypes.data))
+    return out
+
+
+def kat_camera(settings13, W, H, frame_seed, stride, x, y, sample):
+    st = np.ascontiguousarray(settings13, np.float32)
+    x, y, sample = (np.ascontiguousarray(a, np.int32) for a in (x, y, sample))
+    n = x.shape[0]
+    o, d, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
+    _ok(lib().hk_kat_camera(st.ctypes.data, int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF, n, x.ctypes.data, y.ctypes.data,
+                            sample.ctypes.data, o.ctypes.data, d.ctypes.data, nx.ctypes.data))
+    return o, d, nx
+
+
+def kat_store(color, spp):
+    color = np.ascontiguousarray(color, np.float32)
+    out = np.zeros((color.shape[0], 3), np.int32)
+    _ok(lib().hk_kat_store(color.shape[0], color.ctypes.data, int(spp), out.ctypes.data))
+    return out
 
 
 def slab(o, d, mn, mx):
@@ -176,6 +223,28 @@ class Scene:
                 out[k] = t if k == "t" else idx if k == "object" else extra[k]
         if want_visits:
             out["visits"] = vis
+        return out
+
+    def kat_tex(self, tex, u, v):
+        tex, u, v = np.ascontiguousarray(tex, np.int32), np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32)
+        out = np.zeros(tex.shape[0], np.uint32)
+        _ok(lib().hk_kat_tex(self.h, tex.shape[0], tex.ctypes.data, u.ctypes.data, v.ctypes.data, out.ctypes.data))
+        return out
+
+    def kat_bounce(self, obj_index, o, d, t, atten, seed, warm):
+        idx, warm, seed = np.ascontiguousarray(obj_index, np.int32), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(seed, np.uint64)
+        o, d, t, atten = (np.ascontiguousarray(a, np.float32) for a in (o, d, t, atten))
+        n = idx.shape[0]
+        alive, nx = np.zeros((2, n), np.int32), np.zeros((2, n, 2), np.uint32)
+        o2, d2, a2 = (np.zeros((2, n, 3), np.float32) for _ in range(3))
+        _ok(lib().hk_kat_bounce(self.h, n, idx.ctypes.data, o.ctypes.data, d.ctypes.data, t.ctypes.data, atten.ctypes.data, seed.ctypes.data, warm.ctypes.data,
+                                alive.ctypes.data, o2.ctypes.data, d2.ctypes.data, a2.ctypes.data, nx.ctypes.data))
+        return alive, o2, d2, a2, nx
+
+    def kat_miss(self, d, atten, backtex, background):
+        d, atten = np.ascontiguousarray(d, np.float32), np.ascontiguousarray(atten, np.float32)
+        out = np.zeros((d.shape[0], 3), np.float32)
+        _ok(lib().hk_kat_miss(self.h, d.shape[0], d.ctypes.data, atten.ctypes.data, int(backtex), float(background), out.ctypes.data))
         return out
 
     def wide_info(self, tree=2):
