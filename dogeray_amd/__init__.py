@@ -96,6 +96,25 @@ TRACE_CHANNELS = {"t": (np.float32, 1), "object": (np.int32, 1), "material": (np
 TRACE_CLOSEST, TRACE_ANY = 0, 1
 
 
+class DrRadianceParams(C.Structure):
+    """struct dr_radiance_params (include/dogeray_amd.h dr_trace_radiance)."""
+    _fields_ = [("spp", C.c_int), ("max_depth", C.c_int), ("background", C.c_float), ("backtex", C.c_int), ("seed", C.c_uint64)]
+
+
+class DrRadianceRays(C.Structure):
+    """struct dr_radiance_rays: origin, dir (3 floats per ray), seed (uint64 per ray, or NULL), skip (int32 per ray, or NULL)."""
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("seed", C.c_void_p), ("skip", C.c_void_p)]
+
+
+class DrRadianceOut(C.Structure):
+    """struct dr_radiance_out: radiance (3 floats per ray), bounces (int32 per ray); NULL: not computed."""
+    _fields_ = [("radiance", C.c_void_p), ("bounces", C.c_void_p)]
+
+
+# the channels of Context.radiance: name -> (dtype, components per ray)
+RADIANCE_CHANNELS = {"radiance": (np.float32, 3), "bounces": (np.int32, 1)}
+
+
 class DrDenoiseParams(C.Structure):
     """struct dr_denoise_params (include/dogeray_amd.h dr_accum_denoise)."""
     _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float),
@@ -185,6 +204,8 @@ _API = [
     ("dr_accum_reserve_pack", C.c_int, [_VP, C.c_int]),
     ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
     ("dr_trace_rays", C.c_int, [_VP, C.c_int, C.c_int64, C.POINTER(DrRayBuffers), C.POINTER(DrHitBuffers), C.c_int]),
+    ("dr_radiance_defaults", C.c_int, [C.POINTER(DrRadianceParams)]),
+    ("dr_trace_radiance", C.c_int, [_VP, C.c_int64, C.POINTER(DrRadianceRays), C.POINTER(DrRadianceParams), C.POINTER(DrRadianceOut), C.c_int]),
     ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
     ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_upscale_defaults", C.c_int, [C.POINTER(DrUpscaleParams)]),
@@ -814,6 +835,75 @@ class Context:
         cur = torch.cuda.current_stream(dev)
         lib_stream.wait_stream(cur)
         _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), 1))
+        cur.wait_stream(lib_stream)
+        return out
+
+    # ---- radiance queries (dr_trace_radiance)
+    def radiance(self, o, d, spp=1, max_depth=10, background=1.0, backtex=-1, seed=0, seeds=None, skip=None, channels=("radiance",)):
+        """The light along the caller's rays (include/dogeray_amd.h dr_trace_radiance): o, d [n, 3] float32 (d as traced, not normalised), spp
+        samples of raycolor each with depth max_depth; seeds uint64 [n] or None (ray i: seed + i), skip int32 [n] or None: generator outputs
+        discarded after seeding -> a dict: "radiance" float32 [n, 3], the SUM of the samples (divide by spp for the mean), "bounces" int32 [n],
+        the closest-hit queries of all samples.  numpy inputs take the host path and return numpy arrays; torch tensors on this context's GPU
+        (o, d float32, seeds int64 holding the 64 bits, skip int32; contiguous) take the device path and return torch tensors -- Context.trace's
+        convention.  Mixed or wrongly shaped inputs raise before anything is launched."""
+        channels = tuple(channels)
+        for k in channels:
+            if k not in RADIANCE_CHANNELS:
+                raise ValueError("unknown radiance channel %r (known: %s)" % (k, ", ".join(RADIANCE_CHANNELS)))
+        if not channels:
+            raise ValueError("no channel asked for")
+        params = DrRadianceParams()
+        _check(lib().dr_radiance_defaults(C.byref(params)))
+        params.spp, params.max_depth, params.background, params.backtex = int(spp), int(max_depth), float(background), int(backtex)
+        params.seed = int(seed) & (2 ** 64 - 1)
+        given = [a for a in (o, d, seeds, skip) if a is not None]
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
+        rays, outs = DrRadianceRays(), DrRadianceOut()
+        shape = lambda n, k: (n, 3) if RADIANCE_CHANNELS[k][1] > 1 else (n,)
+        if not any(is_torch):
+            o, d = _f32(o), _f32(d)
+            n = o.shape[0] if o.ndim == 2 else -1
+            if o.shape != (n, 3) or d.shape != (n, 3):
+                raise ValueError("o and d must both be [n, 3]")
+            seeds = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+            skip = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
+            if (seeds is not None and seeds.shape != (n,)) or (skip is not None and skip.shape != (n,)):
+                raise ValueError("seeds and skip must be [n]")
+            out = {k: np.empty(shape(n, k), dtype=RADIANCE_CHANNELS[k][0]) for k in channels}
+            rays.origin, rays.dir = o.ctypes.data, d.ctypes.data
+            rays.seed, rays.skip = (seeds.ctypes.data if seeds is not None else None), (skip.ctypes.data if skip is not None else None)
+            for k, a in out.items():
+                setattr(outs, k, a.ctypes.data)
+            _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 0))
+            return out
+        if not all(is_torch):
+            raise TypeError("o, d, seeds and skip must all be numpy arrays or all torch tensors")
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        for name, a, dt in (("o", o, torch.float32), ("d", d, torch.float32), ("seeds", seeds, torch.int64), ("skip", skip, torch.int32)):
+            if a is None:
+                continue
+            if a.device != dev:
+                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
+            if a.dtype != dt:
+                raise TypeError("%s must be %s, not %s" % (name, dt, a.dtype))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n = o.shape[0] if o.dim() == 2 else -1
+        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
+            raise ValueError("o and d must both be [n, 3]")
+        if (seeds is not None and tuple(seeds.shape) != (n,)) or (skip is not None and tuple(skip.shape) != (n,)):
+            raise ValueError("seeds and skip must be [n]")
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty(shape(n, k), dtype=tdt[RADIANCE_CHANNELS[k][0]], device=dev) for k in channels}
+        rays.origin, rays.dir = o.data_ptr(), d.data_ptr()
+        rays.seed, rays.skip = (seeds.data_ptr() if seeds is not None else None), (skip.data_ptr() if skip is not None else None)
+        for k, a in out.items():
+            setattr(outs, k, a.data_ptr())
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 1))
         cur.wait_stream(lib_stream)
         return out
 

@@ -5,6 +5,7 @@
 //   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
+//   context_radiance.cpp   radiance queries on caller rays (dr_trace_radiance)
 //   context_probe.cpp      measurement probes and known-answer hooks
 // Host only, no kernels: kernels.hpp declares their launchers.
 #pragma once
@@ -125,6 +126,10 @@ struct dr_context {
   DevMem<unsigned> trace_cursor;
   DevMem<uint8_t> trace_staging;
   int trace_kernel = 0;                    // option (private, for the tests): 0 plan_trace decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
+  // dr_trace_radiance: the staging of host rays and results and the persistent kernel's cursor, made by the first call that needs them
+  DevMem<uint8_t> radiance_staging;
+  DevMem<unsigned> radiance_cursor;
+  int radiance_kernel = 0;                 // option (private, for the tests): 0 plan_radiance decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
   // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
   // guides' key (settings13, W, H, scene generation), and the staging of host outputs
   DevMem<float> dn_planes;

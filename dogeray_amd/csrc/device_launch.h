@@ -1,5 +1,5 @@
 // What one launch of an accumulator stage needs: the grids, the parameters and the planes of the denoiser, the upsampler, the temporal
-// reprojection and the noise estimate.  No HIP in here: kernels.hpp hands these structs to the launchers with device pointers in them, and the
+// reprojection and the noise estimate -- and what a launch of dr_trace_radiance needs.  No HIP in here: kernels.hpp hands these structs to the launchers with device pointers in them, and the
 // host build (tools/host_kernel.cpp) fills the same structs with host pointers; the per-pixel bodies of device_denoise.hpp, device_upscale.hpp,
 // device_reproject.hpp and device_moments.hpp take them and run on either.
 #pragma once
@@ -86,6 +86,21 @@ struct MoLaunch {
   const unsigned long long* m2;
   float* out_sigma;
   unsigned long long* counts;
+};
+
+// kernels_radiance.hip (dr_trace_radiance): n caller rays (origin / dir 3 floats per ray), their seeds (null: base_seed + i) and the generator outputs
+// to discard after seeding (null: none), spp samples each; radiance (3 floats per ray: the samples' float sum) and bounces (closest-hit queries of all
+// samples), null: not written.  max_depth, the background and backtex travel in RenderParams, where trace_path reads them.
+struct RadianceLaunch {
+  const float* origin; const float* dir;
+  const uint64_t* seed;
+  const int32_t* skip;
+  unsigned n;
+  int spp;
+  uint64_t base_seed;
+  float* radiance;
+  int32_t* bounces;
+  unsigned* cursor;               // persistent kernel: the ray list's cursor, zeroed on the launch's stream by the caller
 };
 
 }  // namespace dr

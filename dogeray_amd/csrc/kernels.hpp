@@ -4,6 +4,7 @@
 //   kernels_kat_shade.hip     known-answer kernels of the shading step: samplers, texel fetch, one bounce, background, camera ray, store
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
+//   kernels_radiance.hip      path-traced radiance along caller rays (dr_trace_radiance)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
@@ -123,6 +124,10 @@ struct TraceLaunch {
 // any: DR_TRACE_ANY; plan: plan_trace's (launch_plan.hpp).  n > 0.
 void launch_trace(hipStream_t stream, const RenderParams& P, const TracePlan& plan, bool any, const TraceLaunch& T);
 void launch_trace_surface(hipStream_t stream, const RenderParams& P, const TraceLaunch& T);
+
+// kernels_radiance.hip: R (RadianceLaunch, device_launch.h) by the kernel of plan (plan_radiance's, launch_plan.hpp); P: the scene, max_depth, bgint,
+// backtex.  n > 0; the persistent kernel's cursor zeroed on `stream` by the caller.
+void launch_radiance(hipStream_t stream, const RenderParams& P, const RadiancePlan& plan, const RadianceLaunch& R);
 
 // The accumulator stages: their launch structs (DnLaunch, UpLaunch, RpLaunch, MoLaunch) are in device_launch.h, without HIP, because the per-pixel
 // bodies of the device_*.hpp headers and the host build take them too

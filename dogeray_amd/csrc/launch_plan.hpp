@@ -175,6 +175,37 @@ inline TracePlan plan_trace(long long n, int traversal, bool has_wide, int num_c
   return p;
 }
 
+// ---- dr_trace_radiance (kernels_radiance.hip): which kernel path-traces a list of caller rays, and with what grid.  As plan_trace: the persistent
+// kernel exists for the wide walk only, and cannot be forced where it does not exist.  Its chunk is half the trace kernel's: a ray here is a whole
+// path (spp samples of up to max_depth walks), so a wave's last chunk weighs more than the atomics saved.
+// RADIANCE_PERSISTENT_MIN_RAYS is the measured cross-over (profiles/radiance_rate.txt, parts b and d; bench scene, spp 1, depth 10; one ray per lane
+// against persistent): camera rays x 0.61 at 2^16, x 0.93 at 2^20, x 1.01 at 2^22, x 1.10 at 2^24; rays that start on the surfaces x 0.89, x 0.99,
+// x 1.51 (2.70 -> 1.79 ms), x 1.84 (8.32 -> 4.51 ms).  The phase at 32 waiting lanes (the render kernel's TRAV_MIN) rather than the trace kernel's 8:
+// a phase here shades, and 2^24 camera rays took 5.66 ms against 6.30 at 8.
+enum { RADIANCE_KERNEL_PLAIN = 0, RADIANCE_KERNEL_PERSISTENT = 1 };
+enum { RADIANCE_FORCE_NONE = 0, RADIANCE_FORCE_PLAIN = 1, RADIANCE_FORCE_PERSISTENT = 2 };      // option "radiance_kernel"
+constexpr int RADIANCE_OCC = 5, RADIANCE_REFILL_MIN = 32, RADIANCE_PARK = 20;
+constexpr int RADIANCE_CHUNK = 64;                        // rays a wave takes from the list per atomic
+constexpr long long RADIANCE_PERSISTENT_MIN_RAYS = 1 << 22;
+struct RadiancePlan {
+  int kernel;               // RADIANCE_KERNEL_*
+  int traversal;            // the walk really used: a scene without a wide tree walks the threaded links
+  int blocks;               // workgroups of 256 threads
+};
+// n > 0 rays; traversal: the context's; force: option "radiance_kernel"
+inline RadiancePlan plan_radiance(long long n, int traversal, bool has_wide, int num_cus, int force) {
+  RadiancePlan p;
+  p.traversal = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
+  const bool can = p.traversal == DR_TRAVERSAL_WIDE;
+  const bool persistent = can && (force == RADIANCE_FORCE_PERSISTENT || (force != RADIANCE_FORCE_PLAIN && n >= RADIANCE_PERSISTENT_MIN_RAYS));
+  p.kernel = persistent ? RADIANCE_KERNEL_PERSISTENT : RADIANCE_KERNEL_PLAIN;
+  if (persistent) {       // no more waves than chunks
+    const long long full = (long long)num_cus * RADIANCE_OCC, need = (n + 4 * RADIANCE_CHUNK - 1) / (4 * RADIANCE_CHUNK);
+    p.blocks = (int)(need < full ? need : full);
+  } else p.blocks = (int)((n + 255) / 256);
+  return p;
+}
+
 // The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
 inline void order_geometry(const RenderParams& P, float out[5]) {
   out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;

@@ -221,6 +221,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   with four samples or more from it (SVGF's rule; see dr_accum_error below); 0 (default): the spatial estimate everywhere, the bits as before
  *   "trace_kernel"  (private, for the tests) which kernel dr_trace_rays runs: 0 (default) the launch plan decides by the ray count, 1 the one-ray-per-lane
  *                   kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
+ *   "radiance_kernel" (private, for the tests) which kernel dr_trace_radiance runs: 0 (default) the launch plan decides by the ray count, 1 the
+ *                   one-ray-per-lane kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -400,6 +402,51 @@ typedef struct dr_hit_buffers {   /* NULL: not computed */
   int32_t* occluded;     /* DR_TRACE_ANY only: 1 / 0 */
 } dr_hit_buffers;
 int dr_trace_rays(dr_context* c, int mode, int64_t n, const dr_ray_buffers* rays, const dr_hit_buffers* hits, int device_pointers);
+
+/* ------------------------------------------------------------------ radiance queries ---- */
+/* The LIGHT along the caller's rays: raycolor (K:787-982) on ray i = (origin[3i..], dir[3i..]) instead of a camera ray -- a lightmap or an irradiance
+ * probe, a reflection probe or a 360-degree panorama (tools/panorama.py), a fisheye or orthographic view, the radiance target of a batch of training
+ * rays.  The materials' scatter, the texel fetch, the background and the generator are the renderer's own, bit for bit.
+ *
+ * Sample s (0 <= s < spp) of ray i runs
+ *   Xorwow::init(S_i + s * 0x9E3779B97F4A7C15), S_i = rays->seed ? seed[i] : params->seed + (uint64_t)i, both sums wrapping (curand_init(seed, 0, 0),
+ *     K:1065, with the caller's word where Kernel has the pixel's);
+ *   then skip[i] calls of next(), their outputs discarded (curand(), K:644) -- so that a caller who drew a camera ray of its own from the same
+ *     generator continues where that left off;
+ *   then raycolor from (origin_i, dir_i) with attenuation 1, depth params->max_depth (settings13[9]'s meaning), bgint params->background and
+ *     backtex params->backtex (settings13[12]'s meaning: -1 the sky gradient K:971-974, else the environment texture K:953-966).
+ * radiance[i] = the float sum of the samples' results in sample order, starting from 0: Kernel's color = color + raycolor(...) (K:1076).  The sum is
+ * NOT divided by spp and NOT quantised (K:1081-1085 does both for a pixel): the caller divides, and the bits stay defined.
+ * bounces[i] = the closest-hit queries (hit(), K:801) of all samples of ray i.
+ *
+ * device_pointers = 0: host buffers, the call returns when they are filled; 1: every pointer is device memory on this context's GPU, the work is
+ * queued on dr_context_stream and the call returns at once (dr_trace_rays' convention).  Ordered behind the frames submitted before it; changes
+ * neither the accumulator, nor dr_stats, the stripe or any option.  Works with every traversal (a scene without a wide tree walks the threaded
+ * links); every walk starts at the root with the margin of a scattered ray -- the rays are the caller's, so there is no camera certificate and no
+ * entry table.  DR_ERR_INVALID: no scene, n < 0 or n >= 2^31, a null origin or dir, no output, spp < 1, max_depth < 1, a backtex that
+ * dr_render_frame would refuse for the resident scene (a texture that is not loaded), and -- host pointers -- a negative skip.  With device pointers
+ * the skips are not read by the host: a negative skip discards nothing, as 0.  n == 0 is DR_OK and launches nothing.  The scratch the call needs
+ * belongs to the context, grows on demand and goes with dr_context_destroy; a context that never calls this allocates nothing. */
+typedef struct dr_radiance_params {
+  int      spp;         /* samples per ray, >= 1 */
+  int      max_depth;   /* raycolor's depth (settings13[9]'s meaning), >= 1 */
+  float    background;  /* bgint, as dr_render_frame's `background` */
+  int      backtex;     /* settings13[12]'s meaning: -1 the sky gradient, else a texture */
+  uint64_t seed;        /* base seed */
+} dr_radiance_params;
+int dr_radiance_defaults(dr_radiance_params* p);   /* 1, 10, 1.0f, -1, 0 */
+typedef struct dr_radiance_rays {
+  const float*    origin;  /* n * 3 */
+  const float*    dir;     /* n * 3, as traced, not normalised */
+  const uint64_t* seed;    /* n, or NULL: params->seed + i */
+  const int32_t*  skip;    /* n, or NULL: generator outputs discarded after seeding, >= 0 */
+} dr_radiance_rays;
+typedef struct dr_radiance_out {   /* NULL: not computed; at least one non-NULL */
+  float*   radiance;   /* n * 3 */
+  int32_t* bounces;    /* n: closest-hit queries made, summed over the samples */
+} dr_radiance_out;
+int dr_trace_radiance(dr_context* c, int64_t n, const dr_radiance_rays* rays, const dr_radiance_params* params, const dr_radiance_out* out,
+                      int device_pointers);
 
 /* ------------------------------------------------------------------ denoiser ------------ */
 /* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by

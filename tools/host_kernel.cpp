@@ -25,6 +25,7 @@
 #include "../dogeray_amd/csrc/device_kat_shade.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
+#include "../dogeray_amd/csrc/device_radiance.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
 #include "../dogeray_amd/csrc/device_sky.hpp"
 #include "../dogeray_amd/csrc/device_upscale.hpp"
@@ -822,6 +823,60 @@ void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int fo
   out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
 }
 long long hk_trace_persistent_min_rays() { return TRACE_PERSISTENT_MIN_RAYS; }
+// dr_trace_radiance on the host: device_radiance.hpp radiance_ray on n caller rays over the walks of device_core.hpp, traversal and tree as hk_hit's
+// (a scene without a wide tree takes the threaded walk for traversal 2).  seed / skip NULL as in dr_radiance_rays; radiance (3n) / bounces (n): NULL not
+// written, one of them at least.  The refusals are dr_trace_radiance's.  Returns 0, or -1 with hk_last_error.
+int hk_radiance(void* hv, int traversal, int tree, long long n, const float* o, const float* d, const uint64_t* seed, const int32_t* skip, int spp,
+                int max_depth, float background, int backtex, uint64_t base_seed, float* radiance, int32_t* bounces) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || traversal < 0 || traversal > 2 || (tree != 1 && tree != 2)) { hk_err = "bad argument"; return -1; }
+  if (n < 0 || n >= (long long)1 << 31) { hk_err = "radiance: the ray count must be in [0, 2^31)"; return -1; }
+  if (!o || !d) { hk_err = "radiance: null origin or dir"; return -1; }
+  if (!radiance && !bounces) { hk_err = "radiance: no output"; return -1; }
+  if (spp < 1 || max_depth < 1) { hk_err = "radiance: spp and max_depth must be >= 1"; return -1; }
+  if (backtex >= (int)h->img.tex.size()) { hk_err = "backtex refers to a texture that is not loaded"; return -1; }
+  if (skip) for (long long i = 0; i < n; i++) if (skip[i] < 0) { hk_err = "radiance: a skip is negative"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
+  P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
+  P.pairs = img.pairs.data(); P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
+  P.max_depth = max_depth; P.bgint = background; P.backtex = backtex;
+  RadianceLaunch R;
+  memset(&R, 0, sizeof(R));
+  R.origin = o; R.dir = d; R.seed = seed; R.skip = skip; R.n = (unsigned)n; R.spp = spp; R.base_seed = base_seed; R.radiance = radiance; R.bounces = bounces;
+  std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
+  const int mode = plan_radiance(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, RADIANCE_FORCE_PLAIN).traversal;
+  const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
+  for (long long i = 0; i < n; i++) {
+    if (mode == DR_TRAVERSAL_WIDE) {
+      auto closest = [&](V3 ro, V3 rd, Ctr& cc) { return closest_hit_wide<false>(wide, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, ro, rd, cc, stack.data()); };
+      radiance_ray(P, R, (unsigned)i, closest);
+    } else if (mode == DR_TRAVERSAL_ORDERED) {
+      auto closest = [&](V3 ro, V3 rd, Ctr& cc) { return closest_hit_ordered<false>(P.pairs, P.prims, ro, rd, cc, stack.data()); };
+      radiance_ray(P, R, (unsigned)i, closest);
+    } else {
+      auto closest = [&](V3 ro, V3 rd, Ctr& cc) { return closest_hit_threaded<false>(walk, ro, rd, cc); };
+      radiance_ray(P, R, (unsigned)i, closest);
+    }
+  }
+  return 0;
+}
+// launch_plan.hpp plan_radiance: out3 = kernel (RADIANCE_KERNEL_*), the traversal really walked, workgroups
+void hk_radiance_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
+  const RadiancePlan p = plan_radiance(n, traversal, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
+}
+long long hk_radiance_persistent_min_rays() { return RADIANCE_PERSISTENT_MIN_RAYS; }
+int hk_radiance_chunk() { return RADIANCE_CHUNK; }
+int hk_radiance_occ() { return RADIANCE_OCC; }
+int hk_radiance_refill_min() { return RADIANCE_REFILL_MIN; }
+int hk_radiance_park() { return RADIANCE_PARK; }
 // what dr_context_get_option reports for the image of `tree` (1 / 2, as hk_hit): out3 = wide_depth (0: no wide tree), wide_own_bounds, wide_nodes
 int hk_wide_info(void* hv, int tree, int* out3) {
   HkScene* h = (HkScene*)hv;

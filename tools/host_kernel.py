@@ -47,6 +47,11 @@ def lib():
         L.hk_trace_plan.restype = None
         L.hk_trace_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.hk_trace_persistent_min_rays.restype = C.c_longlong
+        L.hk_radiance.restype = C.c_int
+        L.hk_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.hk_radiance_plan.restype = None
+        L.hk_radiance_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hk_radiance_persistent_min_rays.restype = C.c_longlong
         L.hk_wide_info.restype = C.c_int
         L.hk_wide_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.hk_check_uniform.restype = C.c_longlong
@@ -223,6 +228,23 @@ class Scene:
                 out[k] = t if k == "t" else idx if k == "object" else extra[k]
         if want_visits:
             out["visits"] = vis
+        return out
+
+    def radiance(self, o, d, spp=1, max_depth=10, background=1.0, backtex=-1, seed=0, seeds=None, skip=None, traversal=2, tree=2,
+                 channels=("radiance", "bounces")):
+        """dr_trace_radiance on the host (hk_radiance: device_radiance.hpp radiance_ray over the host walks): the arguments and the dict of
+        dogeray_amd.Context.radiance, by the walk of `traversal` over the tree of wide_tree = `tree`."""
+        o, d = np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
+        n = o.shape[0]
+        assert o.shape == (n, 3) and d.shape == (n, 3)
+        seeds = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
+        skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
+        assert (seeds is None or seeds.shape == (n,)) and (skip is None or skip.shape == (n,))
+        out = {k: np.zeros((n, 3), np.float32) if k == "radiance" else np.zeros(n, np.int32) for k in channels}
+        _ok(lib().hk_radiance(self.h, int(traversal), int(tree), n, o.ctypes.data, d.ctypes.data, seeds.ctypes.data if seeds is not None else None,
+                              skip.ctypes.data if skip is not None else None, int(spp), int(max_depth), float(background), int(backtex),
+                              int(seed) & (2 ** 64 - 1), out["radiance"].ctypes.data if "radiance" in out else None,
+                              out["bounces"].ctypes.data if "bounces" in out else None))
         return out
 
     def kat_tex(self, tex, u, v):
@@ -613,6 +635,33 @@ def trace_plan(n, traversal, has_wide, num_cus=256, force=0):
 
 def trace_persistent_min_rays():
     return int(lib().hk_trace_persistent_min_rays())
+
+
+def radiance_plan(n, traversal, has_wide, num_cus=256, force=0):
+    """launch_plan.hpp plan_radiance -> (kernel: 0 one ray per lane / 1 persistent, the traversal really walked, workgroups)"""
+    out = (C.c_int * 3)()
+    lib().hk_radiance_plan(int(n), int(traversal), int(bool(has_wide)), int(num_cus), int(force), out)
+    return tuple(out)
+
+
+def radiance_persistent_min_rays():
+    return int(lib().hk_radiance_persistent_min_rays())
+
+
+def radiance_chunk():
+    return int(lib().hk_radiance_chunk())
+
+
+def radiance_occ():
+    return int(lib().hk_radiance_occ())
+
+
+def radiance_refill_min():
+    return int(lib().hk_radiance_refill_min())
+
+
+def radiance_park():
+    return int(lib().hk_radiance_park())
 
 
 def plan_sky_split(cfg, work, coop_steps, per_frame, wave_log_on):
