@@ -70,6 +70,27 @@ __device__ __forceinline__ float tri_hit(V3 ro, V3 rd, V3 v0, V3 e1, V3 e2) {
   float t = f * dot(e2, q);
   return t > EPS ? t : -1.0f;
 }
+// The same test, which also hands out the barycentrics u, v as it forms them: they mean something only when the result is > 0 (a test that returns
+// early leaves them as they were: no select on the way out).  They are the ux, uy that surface_normal (device_surface.hpp) forms from the same ray and
+// the same v0, e1, e2, bit for bit: h, a, f, s, q here are its pvec, det, invDet, tvec, qvec, and a product of two floats does not depend on the order of
+// its factors (tests/test_hit_inputs_host.py compares the words).
+__device__ __forceinline__ float tri_hit(V3 ro, V3 rd, V3 v0, V3 e1, V3 e2, float& u_out, float& v_out) {
+  const float EPS = 0.0001f;
+  V3 h = cross(rd, e2);
+  float a = dot(e1, h);
+  if (a > -EPS && a < EPS) return -1.0f;
+  float f = 1.0f / a;
+  V3 s = ro - v0;
+  float u = f * dot(s, h);
+  u_out = u;
+  if (u < 0.0f || u > 1.0f) return -1.0f;
+  V3 q = cross(s, e1);
+  float v = f * dot(rd, q);
+  v_out = v;
+  if (v < 0.0f || u + v > 1.0f) return -1.0f;
+  float t = f * dot(e2, q);
+  return t > EPS ? t : -1.0f;
+}
 
 // hit_sphere K:316-333
 __device__ __forceinline__ float sphere_hit(V3 c, float radius, V3 o, V3 d) {
@@ -98,6 +119,15 @@ __device__ __forceinline__ float prim_hit_kind(int kind, V3 v0, V3 e1, V3 e2, V3
   float dist = -1.0f;
   if (kind == WALK_KIND_TRIANGLE) dist = tri_hit(o, d, v0, e1, e2);
   else if (kind == WALK_KIND_SPHERE) dist = sphere_hit(v0, e1.x, o, d);
+  if (dist < 10000.0f && dist > -0.0f) return dist;          // K:449
+  return -1.0f;
+}
+// ... with a triangle's barycentrics handed out (tri_hit above).  A sphere has none: it writes zeros, which nobody reads, so that the caller's words have
+// a value on every path that can return t > 0 and may stay without one on the others.
+__device__ __forceinline__ float prim_hit_kind(int kind, V3 v0, V3 e1, V3 e2, V3 o, V3 d, float& u_out, float& v_out) {
+  float dist = -1.0f;
+  if (kind == WALK_KIND_TRIANGLE) dist = tri_hit(o, d, v0, e1, e2, u_out, v_out);
+  else if (kind == WALK_KIND_SPHERE) { dist = sphere_hit(v0, e1.x, o, d); u_out = v_out = 0.0f; }
   if (dist < 10000.0f && dist > -0.0f) return dist;          // K:449
   return -1.0f;
 }

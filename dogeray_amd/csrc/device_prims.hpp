@@ -34,6 +34,20 @@ __device__ __forceinline__ bool first_active_lane() { return __lane_id() == (uns
 #define DR_PIN(s) asm volatile("; " s)      // a comment in the assembly that the compiler moves nothing across (the host: nothing)
 // the leaf step of the wide walk may test the primitive before the box, the wave deciding together (device_wide.hpp wide_leaf_compute); the host keeps the reference's order
 constexpr bool LEAF_PRIM_FIRST = true;
+// What the lean persistent build hands its shade / refill phase about a hit (kernels_render.hip; measured in profiles/hit_inputs_ab.txt;
+// the macros serve the variant libraries of tools/exp_variant.sh):
+//  HIT_UV_CARRIED: the barycentrics u, v of the accepted triangle hit travel from the leaf step to the phase in two stash words, and the phase
+//                  (device_shade.hpp shade_prepare_hit) takes them as given instead of forming them again from the primitive record;
+//  HIT_FETCH_LAZY: the phase takes a hit's type from its shade record and loads the primitive record (with HIT_UV_CARRIED) and the texture coordinates
+//                  only in a wave where some lane reads them.
+#ifndef DR_HIT_UV_CARRIED
+#define DR_HIT_UV_CARRIED 1
+#endif
+#ifndef DR_HIT_FETCH_LAZY
+#define DR_HIT_FETCH_LAZY 1
+#endif
+constexpr bool HIT_UV_CARRIED = DR_HIT_UV_CARRIED != 0;
+constexpr bool HIT_FETCH_LAZY = DR_HIT_FETCH_LAZY != 0;
 
 // ---- 128-bit loads through a buffer descriptor (device_walk.hpp ld_unit has the reason)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -16,18 +16,12 @@ struct Path { V3 rayo, raydir, atten; };
 struct ShadeCtx { V3 hitpoint, N, ocolor; float add_x, rough, ir, r5; int mat; bool front; };
 __device__ __forceinline__ bool shade_needs_sphere(const ShadeCtx& sc) { return sc.mat == 0 || sc.mat == 3 || sc.mat == 5; }
 
-// Returns false when the path ends at an emissive surface, with `emitted` as its radiance (K:941-944); true: sc is filled
+// What shade_prepare does with the unflipped normal N and the texture coordinate of a hit (s4 .. s6: the material's units of the shade record):
+// returns false when the path ends at an emissive surface, with `emitted` as its radiance (K:941-944); true: sc is filled
 template <bool COUNT>
-__device__ __forceinline__ bool shade_prepare(const RenderParams& P, const Path& path, float t, int slot, Xorwow& rng, Ctr& c, ShadeCtx& sc, V3& emitted) {
-  const V3 rayo = path.rayo, raydir = path.raydir;
-  if (COUNT) c.S++;
-  V3 hitpoint = rayo + splat(t) * raydir;
-  const float4* pp = reinterpret_cast<const float4*>(P.prims + slot);
-  const float4* sp = reinterpret_cast<const float4*>(P.shade + slot);
-  float4 pA = pp[0], pB = pp[1], pC = pp[2];
-  float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3], s4 = sp[4], s5 = sp[5], s6 = sp[6];
-  V3 texco;
-  V3 N = surface_normal(pA, pB, pC, s0, s1, s2, s3, s4, s6, rayo, raydir, hitpoint, texco);
+__device__ __forceinline__ bool shade_material(const RenderParams& P, const Path& path, V3 hitpoint, V3 N, V3 texco, float4 s4, float4 s5, float4 s6, Xorwow& rng, Ctr& c,
+                                               ShadeCtx& sc, V3& emitted) {
+  const V3 raydir = path.raydir;
   bool front = dot(raydir, N) < 0;
   N = front ? N : N * splat(-1.0f);
   // ---- material inputs K:826-844
@@ -55,6 +49,60 @@ __device__ __forceinline__ bool shade_prepare(const RenderParams& P, const Path&
   if (mat == 5) sc.r5 = randy(rng);
   sc.hitpoint = hitpoint; sc.N = N; sc.ocolor = ocolor; sc.add_x = add_x; sc.rough = rough; sc.ir = s5.z; sc.mat = mat; sc.front = front;      // ir: b[g].addional.y itself, not the textured roughness (K:917)
   return true;
+}
+
+// Returns false when the path ends at an emissive surface, with `emitted` as its radiance (K:941-944); true: sc is filled
+template <bool COUNT>
+__device__ __forceinline__ bool shade_prepare(const RenderParams& P, const Path& path, float t, int slot, Xorwow& rng, Ctr& c, ShadeCtx& sc, V3& emitted) {
+  const V3 rayo = path.rayo, raydir = path.raydir;
+  if (COUNT) c.S++;
+  V3 hitpoint = rayo + splat(t) * raydir;
+  const float4* pp = reinterpret_cast<const float4*>(P.prims + slot);
+  const float4* sp = reinterpret_cast<const float4*>(P.shade + slot);
+  float4 pA = pp[0], pB = pp[1], pC = pp[2];
+  float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3], s4 = sp[4], s5 = sp[5], s6 = sp[6];
+  V3 texco;
+  V3 N = surface_normal(pA, pB, pC, s0, s1, s2, s3, s4, s6, rayo, raydir, hitpoint, texco);
+  return shade_material<COUNT>(P, path, hitpoint, N, texco, s4, s5, s6, rng, c, sc, emitted);
+}
+
+// shade_prepare for a hit of the lean persistent build (kernels_render.hip; device_prims.hpp HIT_UV_CARRIED, HIT_FETCH_LAZY), which may know more than
+// the records and fetch less of them.  The same arithmetic on the same words: tests/test_hit_inputs_host.py, tests/test_gpu_hit_inputs.py.
+//  CARRIED: (hit_u, hit_v) are the barycentrics of the tri_hit that accepted this hit, taken as given (otherwise tri_barycentrics forms them again);
+//  LAZY: the hit's type is the shade record's copy (linearise.cpp writes the object's type into both records); the primitive record is loaded only in a
+//        wave where a lane reads it -- without CARRIED every lane does; with it a sphere, a type that is never hit and a triangle whose face normal is the
+//        -20 sentinel -- and t1, t2 (sp[3]) only where a lane has a texture, a roughness texture or the checker flag: texco has no other reader.  The lazy
+//        loads are a second round trip, for the waves that take the branch.
+// texco_out (the host's test hook, tools/host_kernel.cpp hk_hit_inputs): where texco goes besides
+template <bool CARRIED, bool LAZY>
+__device__ __forceinline__ bool shade_prepare_hit(const RenderParams& P, const Path& path, float t, int slot, float hit_u, float hit_v, Xorwow& rng, Ctr& c, ShadeCtx& sc,
+                                                  V3& emitted, V3* texco_out = nullptr) {
+  const V3 rayo = path.rayo, raydir = path.raydir;
+  V3 hitpoint = rayo + splat(t) * raydir;
+  const float4* pp = reinterpret_cast<const float4*>(P.prims + slot);
+  const float4* sp = reinterpret_cast<const float4*>(P.shade + slot);
+  float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s4 = sp[4], s5 = sp[5], s6 = sp[6];
+  const int type = LAZY ? __float_as_int(s6.w) : __float_as_int(pp[2].y);
+  // ---- the primitive record: the barycentrics (unless carried) and prim_normal
+  float ux = hit_u, uy = hit_v;
+  V3 Ng = mk(0, 0, 0);
+  const bool reads_prim = !(CARRIED && LAZY) || type != 2 || s0.z == -20;
+  if (DR_WAVE_ANY(reads_prim)) {
+    if (reads_prim) {
+      const float4 pA = pp[0], pB = pp[1], pC = pp[2];
+      if (!CARRIED && type == 2) tri_barycentrics(pA, pB, pC, rayo, raydir, ux, uy);
+      Ng = prim_normal(type, pA, pB, pC, hitpoint);
+    }
+  }
+  // ---- the texture coordinate (0 for a sphere, K:703-773; 0 where no lane of the wave reads it)
+  V3 texco = mk(0, 0, 0);
+  const bool reads_texco = !LAZY || __float_as_int(s6.x) >= 0 || __float_as_int(s6.y) >= 0 || (__float_as_int(s6.z) & 2) != 0;
+  if (DR_WAVE_ANY(reads_texco)) {
+    if (type == 2 && reads_texco) texco = texco_of(ux, uy, sp[3], s4);
+  }
+  V3 N = shade_normal(type, Ng, ux, uy, s0, s1, s2, s6);
+  if (texco_out) *texco_out = texco;
+  return shade_material<false>(P, path, hitpoint, N, texco, s4, s5, s6, rng, c, sc, emitted);
 }
 
 // the scatter of one bounce (rs: the point in the unit sphere, for the materials that draw one): rayo / raydir / atten updated

@@ -94,5 +94,49 @@ __device__ __forceinline__ V3 surface_normal(float4 pA, float4 pB, float4 pC, fl
   }
   return N;
 }
+// surface_normal in the pieces the lean persistent build puts together (device_shade.hpp shade_prepare_hit), which may know a hit's barycentrics already
+// and looks at the primitive record only where a lane reads it.  The arithmetic is the block's above, operation by operation.
+//  prim_normal: what the block takes from the primitive record apart from the barycentrics -- a sphere's normal, cross(e1, e2) of a triangle (used when the
+//  file's face normal is the -20 sentinel), the normalised offset of any other type;
+__device__ __forceinline__ V3 prim_normal(int type, float4 pA, float4 pB, float4 pC, V3 hitpoint) {
+  if (type == 0) return (hitpoint - mk(pA.x, pA.y, pA.z)) / splat(pA.w);
+  if (type == 2) return cross(mk(pA.w, pB.x, pB.y), mk(pB.z, pB.w, pC.x));
+  return normalized(hitpoint - mk(pA.x, pA.y, pA.z));
+}
+//  tri_barycentrics: ux, uy of a triangle from the ray's origin (K:728-745) -- bit for bit the u, v of the tri_hit that accepted the hit;
+__device__ __forceinline__ void tri_barycentrics(float4 pA, float4 pB, float4 pC, V3 rayo, V3 raydir, float& ux, float& uy) {
+  V3 v0 = mk(pA.x, pA.y, pA.z), v0v1 = mk(pA.w, pB.x, pB.y), v0v2 = mk(pB.z, pB.w, pC.x);
+  V3 pvec = cross(raydir, v0v2);
+  float det = dot(v0v1, pvec);
+  float invDet = 1 / det;
+  V3 tvec = rayo - v0;
+  ux = dot(tvec, pvec) * invDet;
+  V3 qvec = cross(tvec, v0v1);
+  uy = dot(raydir, qvec) * invDet;
+}
+//  texco_of: the interpolated texture coordinate (s3: t1, t2; s4.xy: t3);
+__device__ __forceinline__ V3 texco_of(float ux, float uy, float4 s3, float4 s4) {
+  float uz = 1 - ux - uy;
+  V3 texco = mk(0, 0, 0);
+  texco.x = uz * s3.x + ux * s3.z + uy * s4.x;
+  texco.y = uz * s3.y + ux * s3.w + uy * s4.y;
+  return texco;
+}
+//  shade_normal: the unflipped normal from prim_normal's Ng, a triangle's barycentrics and the normals of the shade record.
+__device__ __forceinline__ V3 shade_normal(int type, V3 Ng, float ux, float uy, float4 s0, float4 s1, float4 s2, float4 s6) {
+  if (type != 2) return Ng;
+  V3 N = Ng;
+  float uz = 1 - ux - uy;
+  V3 fn = mk(s0.x, s0.y, s0.z);
+  if (fn.z != -20) {
+    N = fn;
+    int flags = __float_as_int(s6.z);
+    if (s1.y != -20 && (flags & 1)) {     // n1.z
+      V3 n1 = mk(s0.w, s1.x, s1.y), n2 = mk(s1.z, s1.w, s2.x), n3 = mk(s2.y, s2.z, s2.w);
+      N = splat(uz) * n1 + splat(ux) * n2 + splat(uy) * n3;
+    }
+  }
+  return normalized(N);
+}
 
 }  // namespace dr

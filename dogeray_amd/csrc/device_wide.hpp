@@ -219,6 +219,32 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
   DR_MARK("leaf_end");
 }
 
+// The primitive-first leaf step above for the lean persistent build with HIT_UV_CARRIED (kernels_render.hip): the lane that accepts the candidate -- every
+// acceptance, ties included -- leaves the barycentrics tri_hit formed in its two stash words u_word, v_word, so that they are those of the best hit when
+// the walk ends (a sphere leaves what is there: nobody reads them for one).  The two LDS writes sit in the candidate branch, which 5 % of the lanes take.
+// A function of its own so that every other caller of wide_leaf_compute compiles as before.
+template <class Sign>
+__device__ __forceinline__ void wide_leaf_compute_uv(const WideRec& r, V3 o, V3 d, V3 inv, const Sign& sg, Trav& tr, WideStack& ws, const int* __restrict__ stack,
+                                                     float* u_word, float* v_word) {
+  auto f = [](unsigned v) { return __uint_as_float(v); };
+  DR_MARK("leaf_begin");
+  float mn[3] = {f(r.A.x), f(r.A.y), f(r.A.z)}, mx[3] = {f(r.B.x), f(r.B.y), f(r.B.z)};
+  float dist;
+  const int info = (int)r.A.w;
+  float hit_u, hit_v;      // written by every test that can return t > 0, read by a lane that accepts; no value on the other paths: no select, no copy
+  const float t = prim_hit_kind((info >> WALK_SLOT_BITS) & 3, mk(f(r.B.w), f(r.C.x), f(r.C.y)), mk(f(r.C.z), f(r.C.w), f(r.D.x)), mk(f(r.D.y), f(r.D.z), f(r.D.w)), o, d, hit_u, hit_v);
+  const int slot = info & ((1 << WALK_SLOT_BITS) - 1);
+  const bool cand = t > 0.0f && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot));
+  if (DR_WAVE_ANY(cand)) {
+    if (cand && slab_sel(o, inv, sg, mn, mx, dist) && leaf_entry_admits(dist, slot, tr.best_t, tr.best_slot)) {
+      tr.best_t = t; tr.best_slot = slot;
+      *u_word = hit_u; *v_word = hit_v;
+    }
+  }
+  wide_pop(tr, ws, stack);
+  DR_MARK("leaf_end");
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void wide_node_compute(const WideRec& r, V3 inv, const WideRay& wr, Trav& tr, WideStack& ws, int* __restrict__ stack, Ctr& c) {
   SignCmp sg; sg.inv = inv;

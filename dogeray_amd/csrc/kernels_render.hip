@@ -90,7 +90,12 @@ constexpr int SHARE_ALONE = -1, SHARE_OWNER = 64;
 //   * byte 1 of WS_W1 (lean build) is the certificate's grade of the lane's ray: its tile's for a camera ray, 0 for any other; written with every new ray, read
 //     with the stack pointer at the restore;
 //   * between phases WS_STEPS and WS_RSTART are in registers, so the work sharing's exchange has those 2 * 64 words to itself: XCH_MAX hand-overs of XCH_FIELDS
-//     words per round, field f of hand-over e at xch[f * XCH_MAX + e].
+//     words per round, field f of hand-over e at xch[f * XCH_MAX + e];
+//   * between phases WS_TOP and WS_STEPS of the lean build (HIT_UV_CARRIED) carry the barycentrics u, v of the lane's best hit: the leaf step writes them
+//     with every hit it accepts (device_wide.hpp wide_leaf_compute_uv), the phase reads them before it stashes the stack top and the step count there and puts
+//     them back for the lanes that go on walking: v after shading, when the step count is a register again, u at the restore (in between it waits in
+//     WS_COLOR_X, whose value is a register for that time).  Only a lane that shades a triangle hit
+//     looks at them, so a new ray clears nothing.
 //  Threaded walk (WAVE_LDS_DWORDS / 64 words per lane): the parked leaf, 1/direction, and -- not needed while the hit is shaded, back right after -- the pixel
 //  bookkeeping; everything is stashed at the start of a phase and restored in it.
 enum WideStashWord { WS_TOP = 0, WS_W1, WS_COLOR_X, WS_COLOR_Y, WS_COLOR_Z, WS_XY, WS_PCODE, WS_SAMPLE, WS_STEPS, WS_RSTART, WS_BOUNCE = WS_RSTART };
@@ -149,6 +154,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   __shared__ __attribute__((aligned(16))) int wave_lds[4 * REGION];
   int* const my_lds = wave_lds + (threadIdx.x >> 6) * REGION;
   int* const my_stack = my_lds + lane;                             // WIDE: word k of this lane's stack at my_stack[k * 64]
+  // the lean build's forms of the hit's inputs (device_prims.hpp): u, v carried in WS_TOP / WS_STEPS (the stash layout above), the lazy fetches of shade_prepare
+  constexpr bool UV_CARRIED = HIT_UV_CARRIED && WIDE && !COOP && !COUNT, FETCH_LAZY = HIT_FETCH_LAZY && WIDE && !COOP && !COUNT;
+  float* const uv_words = reinterpret_cast<float*>(my_stack) + WIDE_STACK * 64;      // this lane's stash, as the leaf step sees it (UV_CARRIED only)
   unsigned long long* const share_key = reinterpret_cast<unsigned long long*>(my_lds + (WIDE ? SHARE_OFF : 0));     // [64], WIDE && COOP only
   unsigned* const share_pend = reinterpret_cast<unsigned*>(my_lds + (WIDE ? SHARE_OFF : 0) + 128);                   // [64]
   if (WIDE) {                      // the phase-only state lives in the stash (the layout above): no pixel yet
@@ -251,6 +259,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       bool fresh_ray = false;                  // this lane starts a new ray in this phase: 1/direction is recomputed after the phase
       constexpr bool BOUNCE_HOME = WIDE && !COOP;      // lean build: the bounce count lives in the stash, WS_BOUNCE (one register more for the walk)
       float* const st = reinterpret_cast<float*>(my_lds) + (WIDE ? WIDE_STACK * 64 : 0) + lane;      // slot k of this lane: st[k * 64]
+      // lean build, HIT_UV_CARRIED: the barycentrics of the lane's best hit, left by the leaf step in the two words that the walk's state goes into next
+      // (read by the lanes that shade a triangle hit only: a new ray clears nothing)
+      const float hit_u = UV_CARRIED ? st[WS_TOP * 64] : 0.0f, hit_v = UV_CARRIED ? st[WS_STEPS * 64] : 0.0f;
       if (WIDE) {
         // what goes in now is the walk's state: stack top, stack pointer, step counts (the stash layout above; the phase-only words are there already)
         st[WS_TOP * 64] = __uint_as_float(ws.top);
@@ -282,7 +293,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       bool scatter_me = false;
       if (shade_me) {
         if (tr.best_slot >= 0 && tr.best_t > 0.0f) {
-          if (!shade_prepare<COUNT>(P, path, tr.best_t, tr.best_slot, rng, c, sc, radiance)) ended = true;
+          if (UV_CARRIED || FETCH_LAZY ? !shade_prepare_hit<UV_CARRIED, FETCH_LAZY>(P, path, tr.best_t, tr.best_slot, hit_u, hit_v, rng, c, sc, radiance)
+                                       : !shade_prepare<COUNT>(P, path, tr.best_t, tr.best_slot, rng, c, sc, radiance)) ended = true;
           else {
             if (BOUNCE_HOME) bounce = __float_as_int(st[WS_BOUNCE * 64]);
             bounce++;
@@ -303,6 +315,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         pcode = __float_as_int(st[WS_PCODE * 64]);
         frame = (int)((unsigned)__float_as_int(st[WS_W1 * 64]) >> (16 * WS_W1_FRAME_HALF)); sample = __float_as_int(st[WS_SAMPLE * 64]);
         steps = __float_as_uint(st[WS_STEPS * 64]);
+        // (a lane that is still walking keeps its best hit's u, v through the phase: v goes back now that its word is read; u waits in the colour's first word,
+        // which is a register from here to the restore, and goes back there -- neither is a register through the rest of the phase)
+        if (UV_CARRIED) { st[WS_STEPS * 64] = hit_v; st[WS_COLOR_X * 64] = hit_u; }
         if (COOP) rstart = __float_as_uint(st[WS_RSTART * 64]);
       } else {
         asm volatile("" ::: "memory");
@@ -469,6 +484,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         asm volatile("" ::: "memory");
         const int w1 = __float_as_int(st[WS_W1 * 64]);
         ws.top = __float_as_uint(st[WS_TOP * 64]); ws.sp = (w1 >> (8 * WS_W1_SP_BYTE)) & 0xff;
+        if (UV_CARRIED) st[WS_TOP * 64] = st[WS_COLOR_X * 64];
         // the phase-only state goes home (the values in registers are dead from here to the next phase)
         st[WS_COLOR_X * 64] = color.x; st[WS_COLOR_Y * 64] = color.y; st[WS_COLOR_Z * 64] = color.z;
         st[WS_XY * 64] = __int_as_float(((px + 1) << 16) | py); st[WS_PCODE * 64] = __int_as_float(pcode);
@@ -596,7 +612,10 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       if (tr.node >= 0 && (at_leaf ? do_leaves : do_nodes)) {
         if (COUNT) { if (first_active_lane()) c.trav_slots += 64; }
         const WideRec r = wide_fetch(walk, tr.node);
-        if (at_leaf) wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
+        if (at_leaf) {
+          if (UV_CARRIED) wide_leaf_compute_uv(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
+          else wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
+        }
         else wide_node_compute<COUNT>(r, wr, sg, tr, ws, my_stack, c);
         steps++;
       }
@@ -610,7 +629,10 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         if (tr.node >= 0 && (at_leaf2 ? do_leaves2 : do_nodes2)) {
           if (COUNT) { if (first_active_lane()) c.trav_slots += 64; }
           const WideRec r = wide_fetch(walk, tr.node);
-          if (at_leaf2) wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
+          if (at_leaf2) {
+            if (UV_CARRIED) wide_leaf_compute_uv(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
+            else wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
+          }
           else wide_node_compute<COUNT>(r, wr, sg, tr, ws, my_stack, c);
           steps++;
         }

@@ -528,6 +528,67 @@ void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, co
                    mk(e1[3 * i], e1[3 * i + 1], e1[3 * i + 2]), mk(e2[3 * i], e2[3 * i + 1], e2[3 * i + 2]));
 }
 
+// tri_hit's form that hands out the barycentrics (device_intersect.hpp): t or -1, and uv[2 i], uv[2 i + 1] as the test left them (0 where it never formed them)
+void hk_tri_hit_uv(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* t, float* uv) {
+  for (long long i = 0; i < n; i++) {
+    float u = 0.0f, v = 0.0f;
+    t[i] = tri_hit(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), mk(v0[3 * i], v0[3 * i + 1], v0[3 * i + 2]),
+                   mk(e1[3 * i], e1[3 * i + 1], e1[3 * i + 2]), mk(e2[3 * i], e2[3 * i + 1], e2[3 * i + 2]), u, v);
+    uv[2 * i] = u; uv[2 * i + 1] = v;
+  }
+}
+// tri_barycentrics (device_surface.hpp: the barycentrics as surface_normal forms them, from the ray's origin) on n ray / triangle pairs
+void hk_tri_barycentrics(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* uv) {
+  for (long long i = 0; i < n; i++) {
+    const float4 pA = make_float4(v0[3 * i], v0[3 * i + 1], v0[3 * i + 2], e1[3 * i]), pB = make_float4(e1[3 * i + 1], e1[3 * i + 2], e2[3 * i], e2[3 * i + 1]),
+                 pC = make_float4(e2[3 * i + 2], 0.0f, 0.0f, 0.0f);
+    tri_barycentrics(pA, pB, pC, ld3(o + 3 * i), ld3(d + 3 * i), uv[2 * i], uv[2 * i + 1]);
+  }
+}
+// What the shade phase forms at n given hits before any draw of a point, one way per call (tests/test_hit_inputs_host.py): form 0 shade_prepare<false>
+// (texco: surface_normal's on the same records), form 1 shade_prepare_hit<carried, lazy> (device_shade.hpp: the lean persistent build's).  Hit i: the ray
+// (o, d), t, the barycentrics uv (read by the carried forms only), record i of prims (DevPrim) and of shade (DevShade), a generator seeded with seed[i].
+// Out: alive (0: the path ended at an emissive surface, `emitted` holds its radiance and sc is untouched), texco[2], sc[16] -- the words of ShadeCtx:
+// hitpoint, N, ocolor, add_x, rough, ir, r5, mat, front, 0 --, emitted[3], next[2]: the generator's two following outputs.  Returns 0, or -1 with hk_last_error.
+int hk_hit_inputs(long long n, int form, int carried, int lazy, const float* o, const float* d, const float* t, const float* uv, const void* prims, const void* shade,
+                  int ntex, const void* tex, const uint32_t* texels, const uint64_t* seed, int32_t* alive, float* texco, uint32_t* sc_words, float* emitted, uint32_t* next) {
+  if (n < 0 || n > 0x7fffffff || (form != 0 && form != 1)) { hk_err = "bad argument"; return -1; }
+  const DevShade* sh = (const DevShade*)shade;
+  for (long long i = 0; i < n; i++)
+    if (sh[i].texnum >= ntex || sh[i].rtexnum >= ntex) { hk_err = "a shade record names a texture that is not given"; return -1; }
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.prims = (const DevPrim*)prims; P.shade = sh; P.tex = (const DevTex*)tex; P.texels = texels;
+  for (long long i = 0; i < n; i++) {
+    Path path; path.rayo = ld3(o + 3 * i); path.raydir = ld3(d + 3 * i); path.atten = mk(0.5f, 0.75f, 1.0f);
+    Xorwow rng; rng.init(seed[i]);
+    Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+    ShadeCtx sc; memset(&sc, 0, sizeof(sc));
+    V3 em = mk(0, 0, 0), tc = mk(0, 0, 0);
+    bool on;
+    if (form == 0) {
+      const float4* pp = reinterpret_cast<const float4*>(P.prims + i);
+      const float4* sp = reinterpret_cast<const float4*>(P.shade + i);
+      surface_normal(pp[0], pp[1], pp[2], sp[0], sp[1], sp[2], sp[3], sp[4], sp[6], path.rayo, path.raydir, path.rayo + splat(t[i]) * path.raydir, tc);
+      on = shade_prepare<false>(P, path, t[i], (int)i, rng, c, sc, em);
+    } else {
+      const float hu = uv[2 * i], hv = uv[2 * i + 1];
+      if (carried && lazy) on = shade_prepare_hit<true, true>(P, path, t[i], (int)i, hu, hv, rng, c, sc, em, &tc);
+      else if (carried) on = shade_prepare_hit<true, false>(P, path, t[i], (int)i, hu, hv, rng, c, sc, em, &tc);
+      else if (lazy) on = shade_prepare_hit<false, true>(P, path, t[i], (int)i, hu, hv, rng, c, sc, em, &tc);
+      else on = shade_prepare_hit<false, false>(P, path, t[i], (int)i, hu, hv, rng, c, sc, em, &tc);
+    }
+    alive[i] = on ? 1 : 0;
+    texco[2 * i] = tc.x; texco[2 * i + 1] = tc.y;
+    const float f[13] = {sc.hitpoint.x, sc.hitpoint.y, sc.hitpoint.z, sc.N.x, sc.N.y, sc.N.z, sc.ocolor.x, sc.ocolor.y, sc.ocolor.z, sc.add_x, sc.rough, sc.ir, sc.r5};
+    memcpy(sc_words + 16 * i, f, sizeof(f));
+    sc_words[16 * i + 13] = (uint32_t)sc.mat; sc_words[16 * i + 14] = sc.front ? 1u : 0u; sc_words[16 * i + 15] = 0u;
+    emitted[3 * i] = em.x; emitted[3 * i + 1] = em.y; emitted[3 * i + 2] = em.z;
+    next[2 * i] = rng.next(); next[2 * i + 1] = rng.next();
+  }
+  return 0;
+}
+
 // launch_plan.hpp on the host (tests/test_launch_plan_host.py).  cfg6: traversal, occupancy, schedule, num_cus, coop_tiles_per_wave, count;
 // out11: the build's eight template arguments (count, occ, trav_min, park_min, unroll, wide, coop, perframe), blocks, log_waves, clear_wave_log
 void hk_persistent_plan(const int* cfg6, long long work, int coop_steps, int per_frame, int wave_log_on, int* out11) {

@@ -68,6 +68,11 @@ def lib():
         L.hk_cert_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_float, C.c_longlong, C.c_uint64, C.c_void_p, C.c_void_p]
         L.hk_tri_hit.restype = None
         L.hk_tri_hit.argtypes = [C.c_longlong] + [C.c_void_p] * 6
+        L.hk_tri_hit_uv.restype = None
+        L.hk_tri_hit_uv.argtypes = [C.c_longlong] + [C.c_void_p] * 7
+        L.hk_tri_barycentrics.restype = None
+        L.hk_tri_barycentrics.argtypes = [C.c_longlong] + [C.c_void_p] * 6
+        L.hk_hit_inputs.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 8
         L.hk_check_reject.restype = C.c_longlong
         L.hk_check_reject.argtypes = [C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)]
         L.hk_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -164,6 +169,44 @@ def slab(o, d, mn, mx):
     hit = np.zeros(o.shape[0], np.int32)
     lib().hk_slab(o.shape[0], o.ctypes.data, d.ctypes.data, mn.ctypes.data, mx.ctypes.data, hit.ctypes.data)
     return hit
+
+
+def tri_hit_uv(o, d, v0, e1, e2):
+    """device_intersect.hpp tri_hit in both forms on n ray / triangle pairs -> (t of the plain form, t and uv float32[n, 2] of the form that hands out
+    the barycentrics)"""
+    o, d, v0, e1, e2 = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, v0, e1, e2))
+    n = o.shape[0]
+    t0, t1, uv = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros((n, 2), np.float32)
+    lib().hk_tri_hit(n, o.ctypes.data, d.ctypes.data, v0.ctypes.data, e1.ctypes.data, e2.ctypes.data, t0.ctypes.data)
+    lib().hk_tri_hit_uv(n, o.ctypes.data, d.ctypes.data, v0.ctypes.data, e1.ctypes.data, e2.ctypes.data, t1.ctypes.data, uv.ctypes.data)
+    return t0, t1, uv
+
+
+def tri_barycentrics(o, d, v0, e1, e2):
+    """device_surface.hpp tri_barycentrics on n ray / triangle pairs -> float32[n, 2]: ux, uy as surface_normal forms them"""
+    o, d, v0, e1, e2 = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, v0, e1, e2))
+    uv = np.zeros((o.shape[0], 2), np.float32)
+    lib().hk_tri_barycentrics(o.shape[0], o.ctypes.data, d.ctypes.data, v0.ctypes.data, e1.ctypes.data, e2.ctypes.data, uv.ctypes.data)
+    return uv
+
+
+def hit_inputs(o, d, t, uv, prims, shade, seed, form=0, carried=False, lazy=False, tex=None, texels=None):
+    """hk_hit_inputs: what the shade phase forms at n hits.  prims uint32[n, 12] (DevPrim words), shade uint32[n, 32] (DevShade words), tex int32[k, 4]
+    (DevTex words) with texels uint32[...]; form 0 = shade_prepare, form 1 = shade_prepare_hit<carried, lazy> -> dict of alive int32[n],
+    texco float32[n, 2], sc uint32[n, 16] (the words of ShadeCtx), emitted float32[n, 3], next uint32[n, 2]."""
+    o, d, t, uv = (np.ascontiguousarray(a, dtype=np.float32) for a in (o, d, t, uv))
+    prims, shade = np.ascontiguousarray(prims, dtype=np.uint32), np.ascontiguousarray(shade, dtype=np.uint32)
+    seed = np.ascontiguousarray(seed, dtype=np.uint64)
+    n = o.shape[0]
+    assert prims.shape == (n, 12) and shade.shape == (n, 32) and uv.shape == (n, 2) and t.shape == (n,) and seed.shape == (n,)
+    tex = np.ascontiguousarray(tex if tex is not None else np.zeros((1, 4)), dtype=np.int32)
+    texels = np.ascontiguousarray(texels if texels is not None else np.zeros(1), dtype=np.uint32)
+    out = {"alive": np.zeros(n, np.int32), "texco": np.zeros((n, 2), np.float32), "sc": np.zeros((n, 16), np.uint32), "emitted": np.zeros((n, 3), np.float32),
+           "next": np.zeros((n, 2), np.uint32)}
+    _ok(lib().hk_hit_inputs(n, int(form), int(bool(carried)), int(bool(lazy)), o.ctypes.data, d.ctypes.data, t.ctypes.data, uv.ctypes.data, prims.ctypes.data,
+                            shade.ctypes.data, int(tex.shape[0]) if texels.size > 1 else 0, tex.ctypes.data, texels.ctypes.data, seed.ctypes.data,
+                            out["alive"].ctypes.data, out["texco"].ctypes.data, out["sc"].ctypes.data, out["emitted"].ctypes.data, out["next"].ctypes.data))
+    return out
 
 
 class Scene:

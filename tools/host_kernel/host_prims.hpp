@@ -18,6 +18,7 @@ __device__ __forceinline__ uint32_t xorwow_combine(uint32_t t, uint32_t v4) { re
 __device__ __forceinline__ bool first_active_lane() { return true; }
 #define DR_PIN(s) do {} while (0)
 constexpr bool LEAF_PRIM_FIRST = false;      // the reference's order: the box, then the primitive (L counts primitives tested behind a passed box)
+constexpr bool HIT_UV_CARRIED = false, HIT_FETCH_LAZY = false;      // the host's walks and renders keep the plain shade path; hk_hit_inputs names the forms itself
 
 // ---- 128-bit loads through a buffer descriptor
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
