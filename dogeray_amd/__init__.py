@@ -115,6 +115,22 @@ class DrRadianceOut(C.Structure):
 RADIANCE_CHANNELS = {"radiance": (np.float32, 3), "bounces": (np.int32, 1)}
 
 
+class DrPointBuffers(C.Structure):
+    """struct dr_point_buffers (include/dogeray_amd.h dr_query_nearest): point (3 floats per query), rmax (one, or NULL)."""
+    _fields_ = [("point", C.c_void_p), ("rmax", C.c_void_p)]
+
+
+class DrNearestBuffers(C.Structure):
+    """struct dr_nearest_buffers: one pointer per channel of dr_query_nearest (NULL: not computed)."""
+    _fields_ = [("distance", C.c_void_p), ("d2", C.c_void_p), ("object", C.c_void_p), ("material", C.c_void_p), ("point", C.c_void_p),
+                ("uv", C.c_void_p)]
+
+
+# the channels of Context.nearest: name -> (dtype, components per query)
+NEAREST_CHANNELS = {"distance": (np.float32, 1), "d2": (np.float32, 1), "object": (np.int32, 1), "material": (np.int32, 1), "point": (np.float32, 3),
+                    "uv": (np.float32, 2)}
+
+
 class DrDenoiseParams(C.Structure):
     """struct dr_denoise_params (include/dogeray_amd.h dr_accum_denoise)."""
     _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float),
@@ -206,6 +222,7 @@ _API = [
     ("dr_trace_rays", C.c_int, [_VP, C.c_int, C.c_int64, C.POINTER(DrRayBuffers), C.POINTER(DrHitBuffers), C.c_int]),
     ("dr_radiance_defaults", C.c_int, [C.POINTER(DrRadianceParams)]),
     ("dr_trace_radiance", C.c_int, [_VP, C.c_int64, C.POINTER(DrRadianceRays), C.POINTER(DrRadianceParams), C.POINTER(DrRadianceOut), C.c_int]),
+    ("dr_query_nearest", C.c_int, [_VP, C.c_int64, C.POINTER(DrPointBuffers), C.POINTER(DrNearestBuffers), C.c_int]),
     ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
     ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_upscale_defaults", C.c_int, [C.POINTER(DrUpscaleParams)]),
@@ -904,6 +921,68 @@ class Context:
         cur = torch.cuda.current_stream(dev)
         lib_stream.wait_stream(cur)
         _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 1))
+        cur.wait_stream(lib_stream)
+        return out
+
+    # ---- point queries (dr_query_nearest)
+    def nearest(self, p, rmax=None, channels=("distance", "object")):
+        """The nearest surface point of the resident scene to each point (include/dogeray_amd.h dr_query_nearest): p [n, 3] float32, rmax [n] or
+        None (unbounded) -> a dict channel -> array [n] (distance, d2: float32; object, material: int32, -1 on a miss) or [n, k] (point: 3;
+        uv: 2).  numpy inputs take the host path and return numpy arrays.  torch tensors on this context's GPU (float32, contiguous) take the
+        device path and return torch tensors, written on the library's stream, which waits for torch's current stream first; torch's current
+        stream waits for it afterwards.  Mixed or wrongly shaped inputs raise before anything is launched."""
+        channels = tuple(channels)
+        for k in channels:
+            if k not in NEAREST_CHANNELS:
+                raise ValueError("unknown nearest channel %r (known: %s)" % (k, ", ".join(NEAREST_CHANNELS)))
+        if not channels:
+            raise ValueError("no channel asked for")
+        spec = lambda k: NEAREST_CHANNELS[k]
+        given = [a for a in (p, rmax) if a is not None]
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
+        pts, outs = DrPointBuffers(), DrNearestBuffers()
+        if not any(is_torch):
+            p = _f32(p)
+            n = p.shape[0] if p.ndim == 2 else -1
+            if p.shape != (n, 3):
+                raise ValueError("p must be [n, 3]")
+            if rmax is not None:
+                rmax = _f32(rmax)
+                if rmax.shape != (n,):
+                    raise ValueError("rmax must be [n]")
+            out = {k: np.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=spec(k)[0]) for k in channels}
+            pts.point, pts.rmax = p.ctypes.data, (rmax.ctypes.data if rmax is not None else None)
+            for k, a in out.items():
+                setattr(outs, k, a.ctypes.data)
+            _check(lib().dr_query_nearest(self._h, n, C.byref(pts), C.byref(outs), 0))
+            return out
+        if not all(is_torch):
+            raise TypeError("p and rmax must both be numpy arrays or both torch tensors")
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        for name, a in (("p", p), ("rmax", rmax)):
+            if a is None:
+                continue
+            if a.device != dev:
+                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
+            if a.dtype != torch.float32:
+                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n = p.shape[0] if p.dim() == 2 else -1
+        if tuple(p.shape) != (n, 3):
+            raise ValueError("p must be [n, 3]")
+        if rmax is not None and tuple(rmax.shape) != (n,):
+            raise ValueError("rmax must be [n]")
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=tdt[spec(k)[0]], device=dev) for k in channels}
+        pts.point, pts.rmax = p.data_ptr(), (rmax.data_ptr() if rmax is not None else None)
+        for k, a in out.items():
+            setattr(outs, k, a.data_ptr())
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        _check(lib().dr_query_nearest(self._h, n, C.byref(pts), C.byref(outs), 1))
         cur.wait_stream(lib_stream)
         return out
 

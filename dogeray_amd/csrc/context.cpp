@@ -194,6 +194,7 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   c->walk_bytes = img.walk.size() * sizeof(DevUnit);
   c->wide.release();
   c->wide_bytes = 0; c->wide_depth = img.wide_depth; c->wide_nodes = img.wide_nodes; c->wide_pmax = img.wide_pmax; c->wide_mu = img.wide_mu; c->wide_own_bounds = img.wide_own_bounds;
+  c->near_lmax = img.near_lmax;
   c->wide_leaf_rec.release(); c->wide_range.release(); c->wide_leaves = 0;
   if (!img.wide.empty()) {
     DR_TRY(c->wide.upload(img.wide));

@@ -6,6 +6,7 @@
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
 //   context_radiance.cpp   radiance queries on caller rays (dr_trace_radiance)
+//   context_nearest.cpp    nearest-surface point queries (dr_query_nearest)
 //   context_probe.cpp      measurement probes and known-answer hooks
 // Host only, no kernels: kernels.hpp declares their launchers.
 #pragma once
@@ -130,6 +131,11 @@ struct dr_context {
   DevMem<uint8_t> radiance_staging;
   DevMem<unsigned> radiance_cursor;
   int radiance_kernel = 0;                 // option (private, for the tests): 0 plan_radiance decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
+  // dr_query_nearest: the scene's largest |e1| + |e2| / radius (the pruning slack's constant, device_nearest.hpp), the per-query {d2 bits, slot}
+  // words between the walk kernel and the finishing pass, and the staging of host points and results, made by the first call that needs them
+  float near_lmax = 0;
+  DevMem<uint32_t> nearest_key;
+  DevMem<uint8_t> nearest_staging;
   // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
   // guides' key (settings13, W, H, scene generation), and the staging of host outputs
   DevMem<float> dn_planes;

@@ -1,5 +1,5 @@
 // What one launch of an accumulator stage needs: the grids, the parameters and the planes of the denoiser, the upsampler, the temporal
-// reprojection and the noise estimate -- and what a launch of dr_trace_radiance needs.  No HIP in here: kernels.hpp hands these structs to the launchers with device pointers in them, and the
+// reprojection and the noise estimate -- and what a launch of dr_trace_radiance or dr_query_nearest needs.  No HIP in here: kernels.hpp hands these structs to the launchers with device pointers in them, and the
 // host build (tools/host_kernel.cpp) fills the same structs with host pointers; the per-pixel bodies of device_denoise.hpp, device_upscale.hpp,
 // device_reproject.hpp and device_moments.hpp take them and run on either.
 #pragma once
@@ -101,6 +101,19 @@ struct RadianceLaunch {
   float* radiance;
   int32_t* bounces;
   unsigned* cursor;               // persistent kernel: the ray list's cursor, zeroed on the launch's stream by the caller
+};
+
+// kernels_nearest.hip (dr_query_nearest): n query points (3 floats each), their search radii (null: unbounded) and the scene's largest
+// |e1| + |e2| / radius (the pruning slack's constant).  The walk kernel writes key -- {d2 bits, slot} per query, a miss {0, -1}: what
+// the finishing pass reads --, d2, distance and object; the finishing pass material, qpoint (3 per query) and uv (2).  Null: not written (key: always).
+struct NearestLaunch {
+  const float* point; const float* rmax;
+  unsigned n;
+  float lmax;
+  const int32_t* slot_to_orig;    // slot -> object index of the file (read when `object` is written)
+  uint32_t* key;
+  float* distance; float* d2; int32_t* object;
+  int32_t* material; float* qpoint; float* uv;
 };
 
 }  // namespace dr

@@ -5,6 +5,7 @@
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
 //   kernels_radiance.hip      path-traced radiance along caller rays (dr_trace_radiance)
+//   kernels_nearest.hip       nearest-surface point queries (dr_query_nearest)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
@@ -128,6 +129,11 @@ void launch_trace_surface(hipStream_t stream, const RenderParams& P, const Trace
 // kernels_radiance.hip: R (RadianceLaunch, device_launch.h) by the kernel of plan (plan_radiance's, launch_plan.hpp); P: the scene, max_depth, bgint,
 // backtex.  n > 0; the persistent kernel's cursor zeroed on `stream` by the caller.
 void launch_radiance(hipStream_t stream, const RenderParams& P, const RadiancePlan& plan, const RadianceLaunch& R);
+
+// kernels_nearest.hip: N (NearestLaunch, device_launch.h) by the walk of plan (plan_nearest's, launch_plan.hpp): the walk kernel writes N.key, d2,
+// distance, object; the finishing pass reads N.key and writes material, qpoint, uv.  n > 0.
+void launch_nearest(hipStream_t stream, const RenderParams& P, const NearestPlan& plan, const NearestLaunch& N);
+void launch_nearest_finish(hipStream_t stream, const RenderParams& P, const NearestPlan& plan, const NearestLaunch& N);
 
 // The accumulator stages: their launch structs (DnLaunch, UpLaunch, RpLaunch, MoLaunch) are in device_launch.h, without HIP, because the per-pixel
 // bodies of the device_*.hpp headers and the host build take them too

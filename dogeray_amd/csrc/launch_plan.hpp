@@ -206,6 +206,18 @@ inline RadiancePlan plan_radiance(long long n, int traversal, bool has_wide, int
   return p;
 }
 
+// ---- dr_query_nearest (kernels_nearest.hip): one query per lane, workgroups of 256; the 4-way records where the scene has them, else the threaded links
+struct NearestPlan {
+  bool wide;
+  int blocks;
+};
+inline NearestPlan plan_nearest(long long n, bool has_wide) {      // n > 0 queries
+  NearestPlan p;
+  p.wide = has_wide;
+  p.blocks = (int)((n + 255) / 256);
+  return p;
+}
+
 // The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
 inline void order_geometry(const RenderParams& P, float out[5]) {
   out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;

@@ -1,4 +1,5 @@
 // Host scene -> device image (see device_layout.h for the why of each array).
+#include <cmath>
 #include <cstring>
 
 #include "linearise.hpp"
@@ -128,6 +129,19 @@ int linearise(const HostScene& sc, DeviceImage& img, int wide_tree_mode) {
     s.flags = (o.smooth ? 1 : 0) | (o.tex ? 2 : 0);
     s.type = o.type;
     s.orig = oi;
+  }
+
+  {      // the point queries' scene constant (device_nearest.hpp): in double, rounded up; a NaN edge belongs to a primitive that never answers
+    double lmax = 0;
+    for (const DevPrim& p : img.prims) {
+      double l = -1;
+      if (p.type == 2) l = std::sqrt((double)p.e1x * p.e1x + (double)p.e1y * p.e1y + (double)p.e1z * p.e1z) + std::sqrt((double)p.e2x * p.e2x + (double)p.e2y * p.e2y + (double)p.e2z * p.e2z);
+      else if (p.type == 0) l = std::fabs((double)p.e1x);
+      if (l > lmax) lmax = l;
+    }
+    float f = (float)lmax;
+    if ((double)f < lmax) f = nextafterf(f, INFINITY);
+    img.near_lmax = f;
   }
 
   // the walk array: records in pre-order, links carry the target's leaf flag

@@ -20,6 +20,7 @@ struct DeviceImage {
   float wide_pmax = 0;
   WideMu wide_mu = {0, 0, 0};      // wide_tree = 2: the margin's scene constants (device_layout.h)
   int wide_own_bounds = 0;         // ... and how many triangles entered the tree with their own bounds
+  float near_lmax = 0;             // largest |e1| + |e2| of the triangles and |radius| of the spheres, rounded up (dr_query_nearest's pruning slack, device_nearest.hpp)
   std::vector<uint32_t> wide_leaf_rec;   // the wide tree's leaf records in depth-first order: rank -> record (WideImage)
   std::vector<uint32_t> wide_range;      // two words per record: the ranks [first, last] of the leaves under it (a leaf: its own rank twice)
 };

@@ -448,6 +448,42 @@ typedef struct dr_radiance_out {   /* NULL: not computed; at least one non-NULL 
 int dr_trace_radiance(dr_context* c, int64_t n, const dr_radiance_rays* rays, const dr_radiance_params* params, const dr_radiance_out* out,
                       int device_pointers);
 
+/* ------------------------------------------------------------------ point queries ------- */
+/* How far is a point from the resident scene, and where is the nearest surface point -- unsigned distance fields, snapping probes off walls, collision
+ * radii, sphere-tracing grids: what rtcPointQuery, Open3D's compute_closest_points and trimesh's nearest are elsewhere.  Query i is point[3i..] and
+ * rmax[i].
+ *
+ * Per primitive, nearest_prim (dogeray_amd/csrc/device_nearest.hpp) gives the squared distance d2, the nearest point and its barycentrics (u, v):
+ * a triangle v0 + u e1 + v e2 with the point translated to the origin first, a sphere | |p - c| - r |; degenerate triangles answer as the segment or
+ * point they are, objects of other types and spheres of negative radius never answer.  The answer of a query is the minimum of (bits of d2, leaf
+ * order) over all primitives -- a tie goes to the primitive the renderer's own traversal reaches first -- and it is a hit when d2 <= rmax * rmax
+ * rounded to float.  rmax NULL or +inf: unbounded.  A NaN or negative rmax, or a point with a non-finite component: a miss, nothing is walked.
+ * No traversal, tree (option wide_tree) or fallback changes a bit of it: the walks prune with a proven slack.
+ *   distance  sqrtf(d2), -1 on a miss          d2      the key's float, 0 on a miss
+ *   object    index in the scene file, -1      material the object's mat, -1
+ *   point     the nearest surface point, 0     uv      its barycentrics (a sphere: 0, 0), 0
+ * sqrtf(d2) is within 32 * 2^-24 * (d + 2 Lmax) of the true distance d, Lmax the scene's largest |e1| + |e2| or radius, for points and scenes
+ * below 2^30.  Unsigned: which side of a surface the point is on is not answered.
+ *
+ * device_pointers = 0: host buffers, the call returns when they are filled; 1: every pointer is device memory on this context's GPU, the work is
+ * queued on dr_context_stream and the call returns at once (dr_trace_rays' convention).  Ordered behind the frames submitted before it; changes
+ * neither the accumulator, nor dr_stats, the stripe or any option.  A scene with a wide tree is walked through it whatever the traversal option
+ * says; one without walks the threaded links.  DR_ERR_INVALID: no scene, n < 0 or n >= 2^31, a null `point`, no output channel.  n == 0 is DR_OK
+ * and launches nothing.  The scratch the call needs belongs to the context, grows on demand and goes with dr_context_destroy. */
+typedef struct dr_point_buffers {
+  const float* point;    /* n * 3 */
+  const float* rmax;     /* n, or NULL: unbounded */
+} dr_point_buffers;
+typedef struct dr_nearest_buffers {   /* NULL: not computed; at least one non-NULL */
+  float* distance;
+  float* d2;
+  int32_t* object;
+  int32_t* material;
+  float* point;          /* n * 3 */
+  float* uv;             /* n * 2 */
+} dr_nearest_buffers;
+int dr_query_nearest(dr_context* c, int64_t n, const dr_point_buffers* pts, const dr_nearest_buffers* out, int device_pointers);
+
 /* ------------------------------------------------------------------ denoiser ------------ */
 /* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by
  * the first-hit AOVs of the same settings13 (dr_render_aov).  No temporal reprojection here: the accumulator is the temporal mean already

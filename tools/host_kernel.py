@@ -49,6 +49,16 @@ def lib():
         L.hk_trace_persistent_min_rays.restype = C.c_longlong
         L.hk_radiance.restype = C.c_int
         L.hk_radiance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.hk_nearest.restype = C.c_int
+        L.hk_nearest.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 9 + [C.c_int]
+        L.hk_nearest_brute.restype = C.c_int
+        L.hk_nearest_brute.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 8 + [C.c_int]
+        L.hk_nearest_prim.restype = None
+        L.hk_nearest_prim.argtypes = [C.c_longlong] + [C.c_void_p] * 8
+        L.hk_nearest_prims.restype = C.c_longlong
+        L.hk_nearest_prims.argtypes = [C.c_void_p] * 8
+        L.hk_nearest_records.restype = C.c_longlong
+        L.hk_nearest_records.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.hk_radiance_plan.restype = None
         L.hk_radiance_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.hk_radiance_persistent_min_rays.restype = C.c_longlong
@@ -209,6 +219,39 @@ def hit_inputs(o, d, t, uv, prims, shade, seed, form=0, carried=False, lazy=Fals
     return out
 
 
+NEAREST_CHANNELS = ("distance", "d2", "object", "material", "point", "uv")      # in the order of dr_nearest_buffers
+
+
+def _nearest_in(p, rmax):
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    n = p.shape[0]
+    assert p.shape == (n, 3)
+    if rmax is not None:
+        rmax = np.ascontiguousarray(rmax, dtype=np.float32)
+        assert rmax.shape == (n,)
+    return p, rmax, n
+
+
+def _nearest_out(n, channels):
+    shape = {"distance": (n,), "d2": (n,), "object": (n,), "material": (n,), "point": (n, 3), "uv": (n, 2)}
+    return {k: np.zeros(shape[k], np.int32 if k in ("object", "material") else np.float32) for k in channels}
+
+
+def nearest_k():
+    """the k of the accuracy bound k u (d + 2 Lmax) of nearest_prim (device_nearest.hpp NEAREST_K)"""
+    return int(lib().hk_nearest_k())
+
+
+def nearest_prim(kind, a, b, c, p):
+    """nearest_prim (device_nearest.hpp) pair by pair -> (d2 [n], q [n, 3], uv [n, 2])"""
+    kind = np.ascontiguousarray(kind, np.int32)
+    a, b, c, p = (np.ascontiguousarray(x, np.float32) for x in (a, b, c, p))
+    n = len(kind)
+    d2, q, uv = np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float32)
+    lib().hk_nearest_prim(n, kind.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data, p.ctypes.data, d2.ctypes.data, q.ctypes.data, uv.ctypes.data)
+    return d2, q, uv
+
+
 class Scene:
     def __init__(self, rts_path, texdir=""):
         self.h = lib().hk_scene_load(os.fsencode(rts_path), os.fsencode(texdir or ""))
@@ -289,6 +332,40 @@ class Scene:
                               int(seed) & (2 ** 64 - 1), out["radiance"].ctypes.data if "radiance" in out else None,
                               out["bounces"].ctypes.data if "bounces" in out else None))
         return out
+
+    def nearest(self, p, rmax=None, walk=2, tree=2, channels=NEAREST_CHANNELS, want_visits=False, nthreads=1):
+        """dr_query_nearest on the host (hk_nearest): the points p[, rmax] by the walks of device_nearest.hpp -- walk 2 the 4-way records of the tree of
+        wide_tree = `tree`, 0 the threaded links -> a dict of arrays as dogeray_amd.Context.nearest returns it; want_visits adds "visits", the records
+        visited per query."""
+        p, rmax, n = _nearest_in(p, rmax)
+        out = _nearest_out(n, channels)
+        vis = np.zeros(n, np.int32)
+        _ok(lib().hk_nearest(self.h, int(walk), int(tree), n, p.ctypes.data, rmax.ctypes.data if rmax is not None else None,
+                             *[out[k].ctypes.data if k in out else None for k in NEAREST_CHANNELS], vis.ctypes.data, int(nthreads)))
+        if want_visits:
+            out["visits"] = vis
+        return out
+
+    def nearest_brute(self, p, rmax=None, channels=NEAREST_CHANNELS, nthreads=1):
+        """the same answer by its definition (hk_nearest_brute): the key-minimum of nearest_prim over every primitive, no tree"""
+        p, rmax, n = _nearest_in(p, rmax)
+        out = _nearest_out(n, channels)
+        _ok(lib().hk_nearest_brute(self.h, n, p.ctypes.data, rmax.ctypes.data if rmax is not None else None,
+                                   *[out[k].ctypes.data if k in out else None for k in NEAREST_CHANNELS], int(nthreads)))
+        return out
+
+    def nearest_prims(self):
+        """the primitive records in slot order: dict kind (0 sphere, 1 triangle, 2 none), a, b, c [n, 3], orig, material, and lmax (the pruning slack's scene constant)"""
+        n = int(lib().hk_nearest_prims(self.h, *([None] * 7)))
+        kind, orig, mat = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        a, b, c = (np.zeros((n, 3), np.float32) for _ in range(3))
+        lmax = np.zeros(1, np.float32)
+        lib().hk_nearest_prims(self.h, kind.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data, orig.ctypes.data, mat.ctypes.data, lmax.ctypes.data)
+        return {"kind": kind, "a": a, "b": b, "c": c, "orig": orig, "material": mat, "lmax": float(lmax[0])}
+
+    def nearest_records(self, walk=2, tree=2):
+        """records of the walk Scene.nearest takes"""
+        return int(lib().hk_nearest_records(self.h, int(walk), int(tree)))
 
     def kat_tex(self, tex, u, v):
         tex, u, v = np.ascontiguousarray(tex, np.int32), np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32)
