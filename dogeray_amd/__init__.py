@@ -131,6 +131,26 @@ NEAREST_CHANNELS = {"distance": (np.float32, 1), "d2": (np.float32, 1), "object"
                     "uv": (np.float32, 2)}
 
 
+class DrAllHitsParams(C.Structure):
+    """struct dr_allhits_params (include/dogeray_amd.h dr_trace_all_hits)."""
+    _fields_ = [("max_hits", C.c_int), ("kind_mask", C.c_int)]
+
+
+class DrAllHitsBuffers(C.Structure):
+    """struct dr_allhits_buffers: one pointer per channel of dr_trace_all_hits (NULL: not computed)."""
+    _fields_ = [("count", C.c_void_p), ("t", C.c_void_p), ("object", C.c_void_p), ("material", C.c_void_p), ("distance", C.c_void_p),
+                ("normal", C.c_void_p), ("uv", C.c_void_p), ("albedo", C.c_void_p)]
+
+
+# the channels of Context.trace_all: name -> (dtype, components per listed hit; 0: one value per ray)
+ALLHITS_CHANNELS = {"count": (np.int32, 0), "t": (np.float32, 1), "object": (np.int32, 1), "material": (np.int32, 1), "distance": (np.float32, 1),
+                    "normal": (np.float32, 3), "uv": (np.float32, 2), "albedo": (np.float32, 3)}
+ALLHITS_MAX = 8                                   # DR_ALLHITS_MAX
+ALLHITS_KINDS = {"triangle": 1, "sphere": 2}      # DR_ALLHITS_TRIANGLES, DR_ALLHITS_SPHERES
+# Context.contains: three fixed directions, none along an axis, no two orthogonal (pairwise dot products 11, -1, 5)
+CONTAINS_DIRECTIONS = ((1.0, 2.0, 3.0), (3.0, 1.0, 2.0), (2.0, -3.0, 1.0))
+
+
 class DrDenoiseParams(C.Structure):
     """struct dr_denoise_params (include/dogeray_amd.h dr_accum_denoise)."""
     _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("normal_power_log2", C.c_int), ("sigma_depth", C.c_float),
@@ -223,6 +243,8 @@ _API = [
     ("dr_radiance_defaults", C.c_int, [C.POINTER(DrRadianceParams)]),
     ("dr_trace_radiance", C.c_int, [_VP, C.c_int64, C.POINTER(DrRadianceRays), C.POINTER(DrRadianceParams), C.POINTER(DrRadianceOut), C.c_int]),
     ("dr_query_nearest", C.c_int, [_VP, C.c_int64, C.POINTER(DrPointBuffers), C.POINTER(DrNearestBuffers), C.c_int]),
+    ("dr_allhits_defaults", C.c_int, [C.POINTER(DrAllHitsParams)]),
+    ("dr_trace_all_hits", C.c_int, [_VP, C.c_int64, C.POINTER(DrRayBuffers), C.POINTER(DrAllHitsParams), C.POINTER(DrAllHitsBuffers), C.c_int]),
     ("dr_denoise_defaults", C.c_int, [C.POINTER(DrDenoiseParams)]),
     ("dr_accum_denoise", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrDenoiseParams), _VP, _VP, C.c_int]),
     ("dr_upscale_defaults", C.c_int, [C.POINTER(DrUpscaleParams)]),
@@ -924,8 +946,132 @@ class Context:
         cur.wait_stream(lib_stream)
         return out
 
+    # ---- all hits (dr_trace_all_hits)
+    def trace_all(self, o, d, tmax=None, max_hits=4, kinds=("triangle", "sphere"), channels=("count", "t", "object")):
+        """Every crossing of the caller's rays, the first max_hits in order (include/dogeray_amd.h dr_trace_all_hits): o, d [n, 3] float32 (d as
+        traced, not normalised), tmax [n] or None (every ray 10000), K = max_hits in 0 .. ALLHITS_MAX, kinds: which primitives count -> a dict
+        channel -> array: count int32 [n], the size of the whole set; t, distance float32 and object, material int32 [n, K]; normal, albedo
+        [n, K, 3], uv [n, K, 2]; unused entries are t / object / material -1 and zeros.  max_hits=0 returns the count only.  numpy inputs take the
+        host path and return numpy arrays; torch tensors on this context's GPU (float32, contiguous) take the device path and return torch
+        tensors -- Context.trace's convention, stream hand-over included.  Bad arguments raise before anything is launched."""
+        channels = tuple(channels)
+        for k in channels:
+            if k not in ALLHITS_CHANNELS:
+                raise ValueError("unknown all-hits channel %r (known: %s)" % (k, ", ".join(ALLHITS_CHANNELS)))
+        if not channels:
+            raise ValueError("no channel asked for")
+        K = int(max_hits)
+        if K < 0 or K > ALLHITS_MAX:
+            raise ValueError("max_hits must be in 0 .. %d" % ALLHITS_MAX)
+        if K == 0 and channels != ("count",):
+            raise ValueError("max_hits=0 returns the channel 'count' only")
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        for k in kinds:
+            if k not in ALLHITS_KINDS:
+                raise ValueError("unknown kind %r (known: %s)" % (k, ", ".join(ALLHITS_KINDS)))
+        if not kinds:
+            raise ValueError("no kind asked for")
+        params = DrAllHitsParams()
+        _check(lib().dr_allhits_defaults(C.byref(params)))
+        params.max_hits, params.kind_mask = K, sum(ALLHITS_KINDS[k] for k in set(kinds))
+        shape = lambda n, k: (n,) if ALLHITS_CHANNELS[k][1] == 0 else ((n, K) if ALLHITS_CHANNELS[k][1] == 1 else (n, K, ALLHITS_CHANNELS[k][1]))
+        given = [a for a in (o, d, tmax) if a is not None]
+        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
+        rays, outs = DrRayBuffers(), DrAllHitsBuffers()
+        if not any(is_torch):
+            o, d = _f32(o), _f32(d)
+            n = o.shape[0] if o.ndim == 2 else -1
+            if o.shape != (n, 3) or d.shape != (n, 3):
+                raise ValueError("o and d must both be [n, 3]")
+            if tmax is not None:
+                tmax = _f32(tmax)
+                if tmax.shape != (n,):
+                    raise ValueError("tmax must be [n]")
+            out = {k: np.empty(shape(n, k), dtype=ALLHITS_CHANNELS[k][0]) for k in channels}
+            rays.origin, rays.dir, rays.tmax = o.ctypes.data, d.ctypes.data, (tmax.ctypes.data if tmax is not None else None)
+            for k, a in out.items():
+                setattr(outs, k, a.ctypes.data)
+            _check(lib().dr_trace_all_hits(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 0))
+            return out
+        if not all(is_torch):
+            raise TypeError("o, d and tmax must all be numpy arrays or all torch tensors")
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        for name, a in (("o", o), ("d", d), ("tmax", tmax)):
+            if a is None:
+                continue
+            if a.device != dev:
+                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
+            if a.dtype != torch.float32:
+                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n = o.shape[0] if o.dim() == 2 else -1
+        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
+            raise ValueError("o and d must both be [n, 3]")
+        if tmax is not None and tuple(tmax.shape) != (n,):
+            raise ValueError("tmax must be [n]")
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty(shape(n, k), dtype=tdt[ALLHITS_CHANNELS[k][0]], device=dev) for k in channels}
+        rays.origin, rays.dir, rays.tmax = o.data_ptr(), d.data_ptr(), (tmax.data_ptr() if tmax is not None else None)
+        for k, a in out.items():
+            setattr(outs, k, a.data_ptr())
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        _check(lib().dr_trace_all_hits(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 1))
+        cur.wait_stream(lib_stream)
+        return out
+
+    def contains(self, points, directions=None):
+        """Which points lie inside the resident scene's CLOSED triangle meshes: bool [n] for points [n, 3] (numpy in, numpy out; torch tensors on
+        this context's GPU in, a torch tensor out).  Along each of three directions (CONTAINS_DIRECTIONS, or the caller's three: not along an
+        axis of the mesh, no two orthogonal) the parity of the number of triangles the ray from the point crosses (trace_all, triangles only,
+        max_hits=0) says inside (odd) or outside (even), and the majority of the three decides.  Three directions vote because a ray through an
+        edge or a vertex that two triangles share may count 0 or 2 crossings there instead of 1.  Meant for watertight meshes: an open mesh has
+        no inside, spheres are not solids for this test (hit_sphere reports an entry only), and a triangle too small or too edge-on for
+        hit_tri's |a| >= 1e-4 at these direction lengths is not counted.  Points closer to the surface than about 1e-2 of its size may fall
+        either way."""
+        dirs = CONTAINS_DIRECTIONS if directions is None else tuple(tuple(float(x) for x in v) for v in directions)
+        if len(dirs) != 3 or any(len(v) != 3 for v in dirs):
+            raise ValueError("directions must be three 3-vectors")
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            if points.dim() != 2 or points.shape[1] != 3:
+                raise ValueError("points must be [n, 3]")
+            votes = None
+            for v in dirs:
+                d = torch.tensor(v, dtype=torch.float32, device=points.device).expand(points.shape[0], 3).contiguous()
+                odd = self.trace_all(points, d, max_hits=0, kinds=("triangle",), channels=("count",))["count"] & 1
+                votes = odd if votes is None else votes + odd
+            return votes >= 2
+        points = _f32(points)
+        if points.ndim != 2 or points.shape[1] != 3:
+            raise ValueError("points must be [n, 3]")
+        votes = np.zeros(points.shape[0], np.int32)
+        for v in dirs:
+            d = np.ascontiguousarray(np.broadcast_to(np.array(v, np.float32), points.shape))
+            votes += self.trace_all(points, d, max_hits=0, kinds=("triangle",), channels=("count",))["count"] & 1
+        return votes >= 2
+
     # ---- point queries (dr_query_nearest)
-    def nearest(self, p, rmax=None, channels=("distance", "object")):
+    def nearest(self, p, rmax=None, channels=("distance", "object"), signed=False):
+        """The nearest surface point of the resident scene to each point (dr_query_nearest; arguments, channels and paths: _nearest_unsigned
+        below).  signed=True negates `distance` where Context.contains says the point lies inside a closed triangle mesh: the crossing parity that
+        dr_query_nearest itself leaves out.  Only hits change sign (a miss stays -1, so ask with rmax=None when both can occur); every other
+        channel, and the default signed=False, are the unsigned answer bit for bit."""
+        out = self._nearest_unsigned(p, rmax, channels)
+        if signed and "distance" in out:
+            inside = self.contains(p)
+            dist = out["distance"]
+            if type(dist).__module__.split(".")[0] == "torch":
+                import torch
+                out["distance"] = torch.where(inside & (dist > 0), -dist, dist)
+            else:
+                out["distance"] = np.where(inside & (dist > 0), -dist, dist).astype(np.float32)
+        return out
+
+    def _nearest_unsigned(self, p, rmax=None, channels=("distance", "object")):
         """The nearest surface point of the resident scene to each point (include/dogeray_amd.h dr_query_nearest): p [n, 3] float32, rmax [n] or
         None (unbounded) -> a dict channel -> array [n] (distance, d2: float32; object, material: int32, -1 on a miss) or [n, k] (point: 3;
         uv: 2).  numpy inputs take the host path and return numpy arrays.  torch tensors on this context's GPU (float32, contiguous) take the

@@ -49,6 +49,7 @@ const Option OPTIONS[] = {
     {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 2, 0, false},
     {"trace_kernel", /* (as above) */ &dr_context::trace_kernel, 0, 2, 0, false},
     {"radiance_kernel", /* (as above) */ &dr_context::radiance_kernel, 0, 2, 0, false},
+    {"allhits_kernel", /* (as above) */ &dr_context::allhits_kernel, 0, 2, 0, false},
 };
 
 const Option* find_option(const std::string& name) {

@@ -7,6 +7,7 @@
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
 //   context_radiance.cpp   radiance queries on caller rays (dr_trace_radiance)
 //   context_nearest.cpp    nearest-surface point queries (dr_query_nearest)
+//   context_allhits.cpp    every crossing of a caller ray (dr_trace_all_hits)
 //   context_probe.cpp      measurement probes and known-answer hooks
 // Host only, no kernels: kernels.hpp declares their launchers.
 #pragma once
@@ -136,6 +137,12 @@ struct dr_context {
   float near_lmax = 0;
   DevMem<uint32_t> nearest_key;
   DevMem<uint8_t> nearest_staging;
+  // dr_trace_all_hits: the per-entry {t bits, slot} words between the walk kernel and the surface pass, the persistent kernel's cursor and the staging
+  // of host rays and results, made by the first call that needs them
+  DevMem<uint32_t> allhits_hit;
+  DevMem<unsigned> allhits_cursor;
+  DevMem<uint8_t> allhits_staging;
+  int allhits_kernel = 0;                  // option (private, for the tests): 0 plan_allhits decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
   // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
   // guides' key (settings13, W, H, scene generation), and the staging of host outputs
   DevMem<float> dn_planes;

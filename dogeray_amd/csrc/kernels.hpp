@@ -6,6 +6,7 @@
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
 //   kernels_radiance.hip      path-traced radiance along caller rays (dr_trace_radiance)
 //   kernels_nearest.hip       nearest-surface point queries (dr_query_nearest)
+//   kernels_allhits.hip       every crossing of a caller ray, the first K sorted (dr_trace_all_hits)
 //   kernels_denoise.hip       the AOV-guided a-trous denoiser of the accumulator (dr_accum_denoise)
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
@@ -125,6 +126,23 @@ struct TraceLaunch {
 // any: DR_TRACE_ANY; plan: plan_trace's (launch_plan.hpp).  n > 0.
 void launch_trace(hipStream_t stream, const RenderParams& P, const TracePlan& plan, bool any, const TraceLaunch& T);
 void launch_trace_surface(hipStream_t stream, const RenderParams& P, const TraceLaunch& T);
+
+// kernels_allhits.hip (dr_trace_all_hits): n caller rays as TraceLaunch's, the list length K = max_hits (0 .. DR_ALLHITS_MAX) and the kinds that count.
+// The walk kernel writes count (n), t and object (n * K; unused entries -1) and hit -- {t bits, slot} per entry, unused {-1, -1}: what the surface
+// pass reads --; launch_allhits_surface, one thread per entry, maps (origin, dir, hit) to distance, material, normal, uv, albedo.  Null: not written.
+struct AllHitsLaunch {
+  const float* origin; const float* dir; const float* tmax;
+  unsigned n;
+  int K, kind_mask;
+  const int32_t* slot_to_orig;
+  int32_t* count; float* t; int32_t* object;
+  uint32_t* hit;                  // two words per entry
+  unsigned* cursor;               // persistent kernel: the ray list's cursor, zeroed on the launch's stream by the caller
+  float* distance; int32_t* material; float* normal; float* uv; float* albedo;
+};
+// plan: plan_allhits' (launch_plan.hpp).  n > 0; the surface pass needs K > 0.
+void launch_allhits(hipStream_t stream, const RenderParams& P, const AllHitsPlan& plan, const AllHitsLaunch& A);
+void launch_allhits_surface(hipStream_t stream, const RenderParams& P, const AllHitsLaunch& A);
 
 // kernels_radiance.hip: R (RadianceLaunch, device_launch.h) by the kernel of plan (plan_radiance's, launch_plan.hpp); P: the scene, max_depth, bgint,
 // backtex.  n > 0; the persistent kernel's cursor zeroed on `stream` by the caller.

@@ -218,6 +218,35 @@ inline NearestPlan plan_nearest(long long n, bool has_wide) {      // n > 0 quer
   return p;
 }
 
+// ---- dr_trace_all_hits (kernels_allhits.hip): which kernel walks a list of caller rays for all their crossings, and with what grid.  A scene with a
+// wide tree is walked through it whatever the traversal option says (plan_nearest's rule); the persistent kernel exists for that walk only and cannot be
+// forced where it does not exist.  Its parameters are the trace kernel's, but five waves per SIMD: a workgroup holds 32 KiB of LDS, the lanes' stacks
+// and their lists.  ALLHITS_PERSISTENT_MIN_RAYS is the measured cross-over (profiles/allhits_rate.txt, part c; a frame's rays of the bench scene in
+// wavefront order, K = 4): one ray per lane is faster up to 3.3 M rays (x 0.51 at 262 144, x 0.69 at 1.0 M, x 0.86 at 3.3 M), the persistent kernel
+// from 13.1 M on (x 1.22, x 1.40 at 52.5 M; the count alone x 1.34, x 1.58); 2^23 lies between the two, near their geometric mean.
+enum { ALLHITS_KERNEL_PLAIN = 0, ALLHITS_KERNEL_PERSISTENT = 1 };
+enum { ALLHITS_FORCE_NONE = 0, ALLHITS_FORCE_PLAIN = 1, ALLHITS_FORCE_PERSISTENT = 2 };      // option "allhits_kernel"
+constexpr int ALLHITS_OCC = 5, ALLHITS_REFILL_MIN = 8, ALLHITS_PARK = 20;
+constexpr int ALLHITS_CHUNK = 128;                        // rays a wave takes from the list per atomic
+constexpr long long ALLHITS_PERSISTENT_MIN_RAYS = 1 << 23;
+struct AllHitsPlan {
+  int kernel;               // ALLHITS_KERNEL_*
+  bool wide;                // the 4-way records, else the threaded links
+  int blocks;               // workgroups of 256 threads
+};
+// n > 0 rays; force: option "allhits_kernel"
+inline AllHitsPlan plan_allhits(long long n, bool has_wide, int num_cus, int force) {
+  AllHitsPlan p;
+  p.wide = has_wide;
+  const bool persistent = has_wide && (force == ALLHITS_FORCE_PERSISTENT || (force != ALLHITS_FORCE_PLAIN && n >= ALLHITS_PERSISTENT_MIN_RAYS));
+  p.kernel = persistent ? ALLHITS_KERNEL_PERSISTENT : ALLHITS_KERNEL_PLAIN;
+  if (persistent) {       // no more waves than chunks
+    const long long full = (long long)num_cus * ALLHITS_OCC, need = (n + 4 * ALLHITS_CHUNK - 1) / (4 * ALLHITS_CHUNK);
+    p.blocks = (int)(need < full ? need : full);
+  } else p.blocks = (int)((n + 255) / 256);
+  return p;
+}
+
 // The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
 inline void order_geometry(const RenderParams& P, float out[5]) {
   out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;

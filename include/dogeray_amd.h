@@ -223,6 +223,8 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
  *   "radiance_kernel" (private, for the tests) which kernel dr_trace_radiance runs: 0 (default) the launch plan decides by the ray count, 1 the
  *                   one-ray-per-lane kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
+ *   "allhits_kernel" (private, for the tests) which kernel dr_trace_all_hits runs: 0 (default) the launch plan decides by the ray count, 1 the
+ *                   one-ray-per-lane kernel, 2 the persistent kernel wherever it exists (a scene with a wide tree).  The same bits either way
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -483,6 +485,52 @@ typedef struct dr_nearest_buffers {   /* NULL: not computed; at least one non-NU
   float* uv;             /* n * 2 */
 } dr_nearest_buffers;
 int dr_query_nearest(dr_context* c, int64_t n, const dr_point_buffers* pts, const dr_nearest_buffers* out, int device_pointers);
+
+/* ------------------------------------------------------------------ all hits ------------ */
+/* EVERY surface a caller ray goes through, not only the first -- thickness and entry / exit pairs, x-ray and transparency compositing, crossing counts
+ * that decide inside or outside, the multi-hit lists of acoustic or RF propagation: what an RTC_FILTER that never accepts collects elsewhere.  Rays are
+ * dr_trace_rays' three arrays; cap_i = min(tmax_i, 10000), tmax NULL: 10000; a NaN or non-positive tmax_i gives count 0 and nothing is walked.
+ *
+ * The primitive at leaf-order slot s is CROSSED by ray (o, d, cap) when all of these hold: its kind is in kind_mask; slab(o, 1 / d, box) passes on the
+ * box stored in its leaf record -- the reference's padded box, in both trees --; t = prim_hit_kind(...) satisfies 0 < t <= cap.  That is hit()'s own
+ * acceptance rule (K:484-488) without its running best.  The answer of a ray is the SET of crossed slots ordered by (bits of t, slot) ascending: each
+ * slot at most once, every tie on t present, lower slot first.  The definition uses no tree, and no traversal, tree (option wide_tree), kernel or
+ * fallback changes a bit of it: the walks prune nothing by t (DESIGN.md 4.19 has the reachability argument; no class of rays is excepted).
+ *   count     int32 n          the size of the whole set, also when it exceeds max_hits
+ *   t         float n * K      the K = max_hits smallest, in order; -1 in unused entries
+ *   object    int32 n * K      index in the scene file, -1           material  int32 n * K   the object's mat, -1
+ *   distance  float n * K      t * |dir|, 0                          normal / uv / albedo    n * K * 3 / 2 / 3 as dr_trace_rays', 0
+ * The first entry is NOT by definition dr_trace_rays' closest hit: hit()'s answer depends on the order in which boxes are entered for the rare accepted
+ * hits whose float t lies in front of their own padded box, so the first entry's t is <= the closest hit's t whenever both report a hit, and equal
+ * on well-conditioned rays.
+ *
+ * max_hits 0 .. DR_ALLHITS_MAX; 0 returns the count only, and every pointer other than `count` must be NULL then.  A caller who needs more than
+ * DR_ALLHITS_MAX entries pages with a larger origin offset of their own.  kind_mask: DR_ALLHITS_TRIANGLES | DR_ALLHITS_SPHERES (default both; at least one).
+ * A sphere answers with hit_sphere's one root (its entry), as everywhere in this library.
+ *
+ * device_pointers, the stream, the ordering behind submitted frames and the side effects (none) are dr_trace_rays'.  A scene with a wide tree is
+ * walked through it whatever the traversal option says; one without walks the threaded links.  DR_ERR_INVALID: no scene, n < 0 or n >= 2^31, a null
+ * origin or dir, no output channel, max_hits or kind_mask out of range, a K-shaped channel with max_hits 0.  n == 0 is DR_OK and launches nothing.
+ * params NULL: the defaults. */
+#define DR_ALLHITS_MAX 8
+enum { DR_ALLHITS_TRIANGLES = 1, DR_ALLHITS_SPHERES = 2 };
+typedef struct dr_allhits_params {
+  int max_hits;          /* K: listed hits per ray, default 4 */
+  int kind_mask;         /* default DR_ALLHITS_TRIANGLES | DR_ALLHITS_SPHERES */
+} dr_allhits_params;
+typedef struct dr_allhits_buffers {   /* NULL: not computed; at least one non-NULL */
+  int32_t* count;        /* n */
+  float* t;              /* n * K */
+  int32_t* object;       /* n * K */
+  int32_t* material;     /* n * K */
+  float* distance;       /* n * K */
+  float* normal;         /* n * K * 3 */
+  float* uv;             /* n * K * 2 */
+  float* albedo;         /* n * K * 3 */
+} dr_allhits_buffers;
+int dr_allhits_defaults(dr_allhits_params* params);
+int dr_trace_all_hits(dr_context* c, int64_t n, const dr_ray_buffers* rays, const dr_allhits_params* params, const dr_allhits_buffers* out,
+                      int device_pointers);
 
 /* ------------------------------------------------------------------ denoiser ------------ */
 /* An edge-avoiding a-trous wavelet filter over the accumulator (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017), guided by

@@ -11,6 +11,7 @@
 // It is TEST AND BENCH INFRASTRUCTURE: tests/test_host_kernel.py compares its frames with the oracle's pixel for pixel (a check of the
 // kernel's arithmetic that needs no GPU) and bench.py reports it as cpu_baseline.kind "same-source" beside the oracle's "port".
 // It is not linked into libdogeray_amd.so, which has no CPU path (dr_context_create fails without a GPU).
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -22,6 +23,7 @@
 #define DR_HOST_BUILD 1
 #include "../dogeray_amd/csrc/device_core.hpp"
 #include "../dogeray_amd/csrc/device_trace.hpp"
+#include "../dogeray_amd/csrc/device_allhits.hpp"
 #include "../dogeray_amd/csrc/device_kat_shade.hpp"
 #include "../dogeray_amd/csrc/device_denoise.hpp"
 #include "../dogeray_amd/csrc/device_moments.hpp"
@@ -1041,6 +1043,125 @@ long long hk_nearest_records(void* hv, int walk, int tree) {
   if (walk == 2 && !img.wide.empty()) return (long long)(img.wide.size() / WIDE_UNITS);
   return (long long)(2 * img.prims.size() - 1);
 }
+// dr_trace_all_hits on the host: the per-ray bodies of device_allhits.hpp (allhits_wide or allhits_threaded, allhits_store, allhits_surface) on n caller
+// rays with list length max_hits and kind_mask.  walk 2: the 4-way records of the image of `tree` (1 / 2, as hk_hit's), 0: the threaded links; a scene
+// without a wide tree takes the threaded walk for walk 2, as the product does.  zero_margin (a switch for tests/test_allhits_host.py): the wide node
+// step runs with the ray's margins forced to zero -- fl(o * inv) on both sides --, which the reachability argument does not cover.  The channels as
+// dr_trace_all_hits writes them (NULL: not written); visits (may be NULL): records visited per ray.  Returns 0, or -1 with hk_last_error.
+int hk_allhits(void* hv, int walk, int tree, long long n, const float* o, const float* d, const float* tmax, int max_hits, int kind_mask, int zero_margin,
+               int32_t* count, float* t, int32_t* object, int32_t* material, float* distance, float* normal, float* uv, float* albedo, int32_t* visits, int nthreads) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n < 0 || n >= (long long)1 << 31 || (walk != 0 && walk != 2) || (tree != 1 && tree != 2) || (n > 0 && (!o || !d)) || nthreads < 1 || max_hits < 0 ||
+      max_hits > ALLHITS_MAX || kind_mask <= 0 || kind_mask > 3) { hk_err = "bad argument"; return -1; }
+  if (max_hits == 0 && (t || object || material || distance || normal || uv || albedo)) { hk_err = "max_hits 0 returns the count only"; return -1; }
+  if (tree == 2 && !h->has_own) {
+    if (linearise(h->scene->host, h->own, 2) != DR_OK) { hk_err = "scene could not be linearised"; return -1; }
+    h->has_own = true;
+  }
+  const DeviceImage& img = tree == 2 ? h->own : h->img;
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
+  P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
+  P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
+  const bool wide = plan_allhits(n > 0 ? n : 1, walk == 2 && P.wide != nullptr, 1, ALLHITS_FORCE_PLAIN).wide;
+  const int K = max_hits;
+  const bool surface = material || distance || normal || uv || albedo;
+  std::vector<uint32_t> hit(surface ? 2 * (size_t)n * (size_t)K : 0);
+  const AllHitsSurface S = {distance, material, normal, uv, albedo};
+  host_rows(nthreads, nthreads, [&](int k) {
+    std::vector<int> stack((size_t)WIDE_STACK * 64);
+    std::vector<unsigned> list((size_t)ALLHITS_LIST_WORDS * 64);
+    for (long long i = k; i < n; i += nthreads) {
+      const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+      const float tm = tmax ? tmax[i] : 10000.0f;
+      Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
+      int cnt = 0;
+      if (wide && zero_margin) {
+        const float cap = trace_cap(tm);
+        if (cap > 0.0f) {
+          const V3 inv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+          WideRay wr = wide_ray(ro, rd, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v);
+          wr.on = wr.of = mk(ro.x * wr.inv.x, ro.y * wr.inv.y, ro.z * wr.inv.z);
+          allhits_wide<true>(wide_rsrc(P), wr, ro, rd, inv, cap, kind_mask, K, cnt, list.data(), c, stack.data());
+        }
+      } else if (wide) cnt = allhits_ray<true, true>(P, ro, rd, tm, kind_mask, K, list.data(), c, stack.data());
+      else cnt = allhits_ray<false, true>(P, ro, rd, tm, kind_mask, K, list.data(), c, stack.data());
+      allhits_store((size_t)i, cnt, K, list.data(), img.slot_to_orig.data(), count, t, object, surface ? hit.data() : nullptr);
+      if (surface) for (int e = 0; e < K; e++) allhits_surface(P, o, d, hit.data(), K, (size_t)i * (size_t)K + (size_t)e, S);
+      if (visits) visits[i] = (int32_t)c.V;
+    }
+  });
+  return 0;
+}
+// The answer of dr_trace_all_hits by its definition, with no walk: every leaf record of the pre-order array in storage order (a record's successor is
+// known from the record before it: an inner node's hit link, a leaf's next-is-leaf bit), slab() on the record's box, prim_hit_kind on its primitive,
+// 0 < t <= cap, the kind mask; the crossings sorted by (bits of t, slot).  count, t, object as hk_allhits'.  The yardstick of tests/test_allhits_host.py.
+int hk_allhits_brute(void* hv, long long n, const float* o, const float* d, const float* tmax, int max_hits, int kind_mask, int32_t* count, float* t, int32_t* object,
+                     int nthreads) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || n < 0 || (n > 0 && (!o || !d)) || nthreads < 1 || max_hits < 0 || kind_mask <= 0 || kind_mask > 3) { hk_err = "bad argument"; return -1; }
+  const DeviceImage& img = h->img;
+  const std::vector<DevUnit>& w = img.walk;
+  auto word = [&w](size_t unit, int k) { int32_t v; memcpy(&v, &w[unit].f[k], 4); return v; };
+  std::vector<size_t> leaves;
+  {
+    size_t u = 0;
+    bool leaf = false;      // (the root of a scene of two objects or more is an inner node)
+    while (u + (leaf ? WALK_UNITS_LEAF : WALK_UNITS_INTERNAL) <= w.size()) {
+      if (leaf) {
+        leaves.push_back(u);
+        const int info = word(u, 3);
+        if ((info >> 29) & 1) break;
+        leaf = (info >> 28) & 1; u += WALK_UNITS_LEAF;
+      } else {
+        const int link = word(u, 3);
+        if (link < 0) break;
+        leaf = link & 1; u += WALK_UNITS_INTERNAL;
+      }
+    }
+  }
+  if (leaves.size() != img.prims.size()) { hk_err = "the walk array's leaves do not match the primitives"; return -1; }
+  const int K = max_hits;
+  host_rows(nthreads, nthreads, [&](int k) {
+    std::vector<unsigned long long> keys;
+    for (long long i = k; i < n; i += nthreads) {
+      const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+      const float tm = tmax ? tmax[i] : 10000.0f;
+      const float cap = tm > 0.0f ? fminf(tm, 10000.0f) : 0.0f;
+      keys.clear();
+      if (cap > 0.0f) {
+        const V3 inv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
+        for (const size_t u : leaves) {
+          const float mn[3] = {w[u].f[0], w[u].f[1], w[u].f[2]}, mx[3] = {w[u + 1].f[0], w[u + 1].f[1], w[u + 1].f[2]};
+          const int info = word(u, 3), kind = (info >> WALK_SLOT_BITS) & 3, slot = info & ((1 << WALK_SLOT_BITS) - 1);
+          if (!((kind == WALK_KIND_TRIANGLE && (kind_mask & 1)) || (kind == WALK_KIND_SPHERE && (kind_mask & 2)))) continue;
+          float dist;
+          if (!slab(ro, inv, mn, mx, dist)) continue;
+          const float th = prim_hit_kind(kind, mk(w[u + 1].f[3], w[u + 2].f[0], w[u + 2].f[1]), mk(w[u + 2].f[2], w[u + 2].f[3], w[u + 3].f[0]),
+                                         mk(w[u + 3].f[1], w[u + 3].f[2], w[u + 3].f[3]), ro, rd);
+          if (th > 0.0f && th <= cap) keys.push_back(hit_key(th, slot));
+        }
+        std::sort(keys.begin(), keys.end());
+      }
+      if (count) count[i] = (int32_t)keys.size();
+      for (int e = 0; e < K; e++) {
+        const bool have = (size_t)e < keys.size();
+        if (t) t[i * K + e] = have ? __uint_as_float((uint32_t)(keys[(size_t)e] >> 32)) : -1.0f;
+        if (object) object[i * K + e] = have ? img.slot_to_orig[(size_t)(uint32_t)keys[(size_t)e]] : -1;
+      }
+    }
+  });
+  return 0;
+}
+int hk_allhits_max() { return ALLHITS_MAX; }
+int hk_allhits_chunk() { return ALLHITS_CHUNK; }
+// launch_plan.hpp plan_allhits: out3 = kernel (ALLHITS_KERNEL_*), wide (1 / 0), workgroups
+void hk_allhits_plan(long long n, int has_wide, int num_cus, int force, int* out3) {
+  const AllHitsPlan p = plan_allhits(n, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.wide ? 1 : 0; out3[2] = p.blocks;
+}
+long long hk_allhits_persistent_min_rays() { return ALLHITS_PERSISTENT_MIN_RAYS; }
 // launch_plan.hpp plan_radiance: out3 = kernel (RADIANCE_KERNEL_*), the traversal really walked, workgroups
 void hk_radiance_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
   const RadiancePlan p = plan_radiance(n, traversal, has_wide != 0, num_cus, force);

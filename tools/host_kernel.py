@@ -59,6 +59,13 @@ def lib():
         L.hk_nearest_prims.argtypes = [C.c_void_p] * 8
         L.hk_nearest_records.restype = C.c_longlong
         L.hk_nearest_records.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.hk_allhits.restype = C.c_int
+        L.hk_allhits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 9 + [C.c_int]
+        L.hk_allhits_brute.restype = C.c_int
+        L.hk_allhits_brute.argtypes = [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int]
+        L.hk_allhits_plan.restype = None
+        L.hk_allhits_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hk_allhits_persistent_min_rays.restype = C.c_longlong
         L.hk_radiance_plan.restype = None
         L.hk_radiance_plan.argtypes = [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.hk_radiance_persistent_min_rays.restype = C.c_longlong
@@ -237,6 +244,48 @@ def _nearest_out(n, channels):
     return {k: np.zeros(shape[k], np.int32 if k in ("object", "material") else np.float32) for k in channels}
 
 
+ALLHITS_CHANNELS = ("count", "t", "object", "material", "distance", "normal", "uv", "albedo")      # in the order of dr_allhits_buffers
+_ALLHITS_SPEC = {"count": (np.int32, 0), "t": (np.float32, 1), "object": (np.int32, 1), "material": (np.int32, 1), "distance": (np.float32, 1),
+                 "normal": (np.float32, 3), "uv": (np.float32, 2), "albedo": (np.float32, 3)}
+
+
+def _allhits_in(o, d, tmax):
+    o, d = np.ascontiguousarray(o, dtype=np.float32), np.ascontiguousarray(d, dtype=np.float32)
+    n = o.shape[0]
+    assert o.shape == (n, 3) and d.shape == (n, 3)
+    if tmax is not None:
+        tmax = np.ascontiguousarray(tmax, dtype=np.float32)
+        assert tmax.shape == (n,)
+    return o, d, tmax, n
+
+
+def _allhits_out(n, K, channels):
+    K = max(K, 0)      # (a K out of range is refused by the library)
+    shape = lambda c: (n,) if c == 0 else ((n, K) if c == 1 else (n, K, c))
+    return {k: np.zeros(shape(_ALLHITS_SPEC[k][1]), _ALLHITS_SPEC[k][0]) for k in channels}
+
+
+def allhits_max():
+    """DR_ALLHITS_MAX as the device code sees it"""
+    return int(lib().hk_allhits_max())
+
+
+def allhits_chunk():
+    """rays a wave of the persistent kernel takes from the list per atomic (launch_plan.hpp ALLHITS_CHUNK)"""
+    return int(lib().hk_allhits_chunk())
+
+
+def allhits_plan(n, has_wide, num_cus=256, force=0):
+    """launch_plan.hpp plan_allhits -> (kernel: 0 one ray per lane / 1 persistent, wide 1 / 0, workgroups)"""
+    out = (C.c_int * 3)()
+    lib().hk_allhits_plan(int(n), int(bool(has_wide)), int(num_cus), int(force), out)
+    return tuple(out)
+
+
+def allhits_persistent_min_rays():
+    return int(lib().hk_allhits_persistent_min_rays())
+
+
 def nearest_k():
     """the k of the accuracy bound k u (d + 2 Lmax) of nearest_prim (device_nearest.hpp NEAREST_K)"""
     return int(lib().hk_nearest_k())
@@ -366,6 +415,29 @@ class Scene:
     def nearest_records(self, walk=2, tree=2):
         """records of the walk Scene.nearest takes"""
         return int(lib().hk_nearest_records(self.h, int(walk), int(tree)))
+
+    def allhits(self, o, d, tmax=None, max_hits=4, kind_mask=3, walk=2, tree=2, channels=("count", "t", "object"), zero_margin=False, want_visits=False,
+                nthreads=1):
+        """dr_trace_all_hits on the host (hk_allhits): the rays (o, d[, tmax]) by the walks of device_allhits.hpp -- walk 2 the 4-way records of the tree
+        of wide_tree = `tree`, 0 the threaded links -> a dict of arrays as dogeray_amd.Context.trace_all returns it; zero_margin forces the wide node
+        step's margins to zero (the switch of tests/test_allhits_host.py); want_visits adds "visits", the records visited per ray."""
+        o, d, tmax, n = _allhits_in(o, d, tmax)
+        out = _allhits_out(n, int(max_hits), channels)
+        vis = np.zeros(n, np.int32)
+        _ok(lib().hk_allhits(self.h, int(walk), int(tree), n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data if tmax is not None else None, int(max_hits),
+                             int(kind_mask), int(bool(zero_margin)), *[out[k].ctypes.data if k in out else None for k in ALLHITS_CHANNELS], vis.ctypes.data,
+                             int(nthreads)))
+        if want_visits:
+            out["visits"] = vis
+        return out
+
+    def allhits_brute(self, o, d, tmax=None, max_hits=4, kind_mask=3, nthreads=1):
+        """the same answer by its definition (hk_allhits_brute): a loop over every leaf record, no walk -> {"count", "t", "object"}"""
+        o, d, tmax, n = _allhits_in(o, d, tmax)
+        out = _allhits_out(n, int(max_hits), ("count", "t", "object"))
+        _ok(lib().hk_allhits_brute(self.h, n, o.ctypes.data, d.ctypes.data, tmax.ctypes.data if tmax is not None else None, int(max_hits), int(kind_mask),
+                                   out["count"].ctypes.data, out["t"].ctypes.data, out["object"].ctypes.data, int(nthreads)))
+        return out
 
     def kat_tex(self, tex, u, v):
         tex, u, v = np.ascontiguousarray(tex, np.int32), np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32)
