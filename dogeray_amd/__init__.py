@@ -811,6 +811,65 @@ class Context:
         cur.wait_stream(lib_stream)
         return out
 
+    # ---- queries on the caller's lists (trace, radiance, trace_all, nearest): what they share
+    def _list_query(self, inputs, out_spec, call):
+        """The marshalling of a query on n caller items.  inputs: (name, array, shape tail, numpy dtype, torch dtype's name as the messages
+        print it) each, an item's array [n] + tail; the arrays with the first one's tail are required and give n, the others may be None.
+        out_spec: channel -> (numpy dtype, shape tail).  numpy arrays (or anything numpy converts) take the host path, torch tensors on this
+        context's GPU (of the dtype named, contiguous) the device path: the library's stream waits for torch's current stream first, torch's
+        current stream for it afterwards.  Every check is made before anything is launched.  call(ins, outs, n, device_pointers) makes the C
+        call: ins name -> address or None, outs channel -> address.  Returns the dict channel -> array."""
+        names = [i[0] for i in inputs]
+        groups = []      # consecutive inputs of one tail are judged together: [o, d], [tmax]
+        for i in inputs:
+            if not groups or groups[-1][0][2] != i[2]:
+                groups.append([])
+            groups[-1].append(i)
+        is_torch = [type(i[1]).__module__.split(".")[0] == "torch" for i in inputs if i[1] is not None]
+
+        def shapes_of(group, arrays, n):
+            if n is None:
+                n = arrays[0].shape[0] if arrays[0].ndim == 2 else -1
+            tail = tuple(group[0][2])
+            if any(a is not None and tuple(a.shape) != (n,) + tail for a in arrays):      # (the wording is each method's own, kept)
+                raise ValueError("%s must %sbe [n%s]" % (" and ".join(g[0] for g in group), "both " if len(group) > 1 and tail else "",
+                                                         "".join(", %d" % t for t in tail)))
+            return n
+
+        if not any(is_torch):
+            n, arr = None, {}
+            for group in groups:
+                for name, a, tail, npdt, _ in group:
+                    arr[name] = np.ascontiguousarray(a, dtype=npdt) if a is not None or n is None else None
+                n = shapes_of(group, [arr[g[0]] for g in group], n)
+            out = {k: np.empty((n,) + tuple(tail), dtype=dt) for k, (dt, tail) in out_spec.items()}
+            call({k: (a.ctypes.data if a is not None else None) for k, a in arr.items()}, {k: a.ctypes.data for k, a in out.items()}, n, 0)
+            return out
+        if not all(is_torch):
+            raise TypeError("%s and %s must %s be numpy arrays or %s torch tensors" % ((", ".join(names[:-1]), names[-1]) + (("both",) * 2 if len(names) == 2 else ("all",) * 2)))
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        for name, a, _, _, tname in inputs:
+            if a is None:
+                continue
+            if a.device != dev:
+                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
+            if a.dtype != getattr(torch, tname.split(".")[-1]):
+                raise TypeError("%s must be %s, not %s" % (name, tname, a.dtype))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        n = None
+        for group in groups:
+            n = shapes_of(group, [g[1] for g in group], n)
+        tdt = {np.float32: torch.float32, np.int32: torch.int32}
+        out = {k: torch.empty((n,) + tuple(tail), dtype=tdt[dt], device=dev) for k, (dt, tail) in out_spec.items()}
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        call({name: (a.data_ptr() if a is not None else None) for name, a, _, _, _ in inputs}, {k: a.data_ptr() for k, a in out.items()}, n, 1)
+        cur.wait_stream(lib_stream)
+        return out
+
     # ---- ray queries (dr_trace_rays)
     def trace(self, o, d, tmax=None, channels=("t", "object"), any_hit=False):
         """Closest hit or occlusion of the caller's rays (include/dogeray_amd.h dr_trace_rays): o, d [n, 3] float32 (d as traced, not normalised),
@@ -828,54 +887,16 @@ class Context:
         if not channels:
             raise ValueError("no channel asked for")
         spec = lambda k: (np.int32, 1) if k == "occluded" else TRACE_CHANNELS[k]
-        given = [a for a in (o, d, tmax) if a is not None]
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
-        rays, hits = DrRayBuffers(), DrHitBuffers()
         mode = TRACE_ANY if any_hit else TRACE_CLOSEST
-        if not any(is_torch):
-            o, d = _f32(o), _f32(d)
-            n = o.shape[0] if o.ndim == 2 else -1
-            if o.shape != (n, 3) or d.shape != (n, 3):
-                raise ValueError("o and d must both be [n, 3]")
-            if tmax is not None:
-                tmax = _f32(tmax)
-                if tmax.shape != (n,):
-                    raise ValueError("tmax must be [n]")
-            out = {k: np.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=spec(k)[0]) for k in channels}
-            rays.origin, rays.dir, rays.tmax = o.ctypes.data, d.ctypes.data, (tmax.ctypes.data if tmax is not None else None)
-            for k, a in out.items():
-                setattr(hits, k, a.ctypes.data)
-            _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), 0))
-            return out
-        if not all(is_torch):
-            raise TypeError("o, d and tmax must all be numpy arrays or all torch tensors")
-        import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-        for name, a in (("o", o), ("d", d), ("tmax", tmax)):
-            if a is None:
-                continue
-            if a.device != dev:
-                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
-            if a.dtype != torch.float32:
-                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        n = o.shape[0] if o.dim() == 2 else -1
-        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
-            raise ValueError("o and d must both be [n, 3]")
-        if tmax is not None and tuple(tmax.shape) != (n,):
-            raise ValueError("tmax must be [n]")
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=tdt[spec(k)[0]], device=dev) for k in channels}
-        rays.origin, rays.dir, rays.tmax = o.data_ptr(), d.data_ptr(), (tmax.data_ptr() if tmax is not None else None)
-        for k, a in out.items():
-            setattr(hits, k, a.data_ptr())
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), 1))
-        cur.wait_stream(lib_stream)
-        return out
+
+        def call(ins, outs, n, device_pointers):
+            rays, hits = DrRayBuffers(), DrHitBuffers()
+            rays.origin, rays.dir, rays.tmax = ins["o"], ins["d"], ins["tmax"]
+            for k, ptr in outs.items():
+                setattr(hits, k, ptr)
+            _check(lib().dr_trace_rays(self._h, mode, n, C.byref(rays), C.byref(hits), device_pointers))
+        return self._list_query([("o", o, (3,), np.float32, "float32"), ("d", d, (3,), np.float32, "float32"), ("tmax", tmax, (), np.float32, "float32")],
+                                {k: (spec(k)[0], (spec(k)[1],) if spec(k)[1] > 1 else ()) for k in channels}, call)
 
     # ---- radiance queries (dr_trace_radiance)
     def radiance(self, o, d, spp=1, max_depth=10, background=1.0, backtex=-1, seed=0, seeds=None, skip=None, channels=("radiance",)):
@@ -895,56 +916,16 @@ class Context:
         _check(lib().dr_radiance_defaults(C.byref(params)))
         params.spp, params.max_depth, params.background, params.backtex = int(spp), int(max_depth), float(background), int(backtex)
         params.seed = int(seed) & (2 ** 64 - 1)
-        given = [a for a in (o, d, seeds, skip) if a is not None]
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
-        rays, outs = DrRadianceRays(), DrRadianceOut()
-        shape = lambda n, k: (n, 3) if RADIANCE_CHANNELS[k][1] > 1 else (n,)
-        if not any(is_torch):
-            o, d = _f32(o), _f32(d)
-            n = o.shape[0] if o.ndim == 2 else -1
-            if o.shape != (n, 3) or d.shape != (n, 3):
-                raise ValueError("o and d must both be [n, 3]")
-            seeds = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-            skip = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
-            if (seeds is not None and seeds.shape != (n,)) or (skip is not None and skip.shape != (n,)):
-                raise ValueError("seeds and skip must be [n]")
-            out = {k: np.empty(shape(n, k), dtype=RADIANCE_CHANNELS[k][0]) for k in channels}
-            rays.origin, rays.dir = o.ctypes.data, d.ctypes.data
-            rays.seed, rays.skip = (seeds.ctypes.data if seeds is not None else None), (skip.ctypes.data if skip is not None else None)
-            for k, a in out.items():
-                setattr(outs, k, a.ctypes.data)
-            _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 0))
-            return out
-        if not all(is_torch):
-            raise TypeError("o, d, seeds and skip must all be numpy arrays or all torch tensors")
-        import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-        for name, a, dt in (("o", o, torch.float32), ("d", d, torch.float32), ("seeds", seeds, torch.int64), ("skip", skip, torch.int32)):
-            if a is None:
-                continue
-            if a.device != dev:
-                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
-            if a.dtype != dt:
-                raise TypeError("%s must be %s, not %s" % (name, dt, a.dtype))
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        n = o.shape[0] if o.dim() == 2 else -1
-        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
-            raise ValueError("o and d must both be [n, 3]")
-        if (seeds is not None and tuple(seeds.shape) != (n,)) or (skip is not None and tuple(skip.shape) != (n,)):
-            raise ValueError("seeds and skip must be [n]")
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty(shape(n, k), dtype=tdt[RADIANCE_CHANNELS[k][0]], device=dev) for k in channels}
-        rays.origin, rays.dir = o.data_ptr(), d.data_ptr()
-        rays.seed, rays.skip = (seeds.data_ptr() if seeds is not None else None), (skip.data_ptr() if skip is not None else None)
-        for k, a in out.items():
-            setattr(outs, k, a.data_ptr())
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 1))
-        cur.wait_stream(lib_stream)
-        return out
+
+        def call(ins, outs, n, device_pointers):
+            rays, res = DrRadianceRays(), DrRadianceOut()
+            rays.origin, rays.dir, rays.seed, rays.skip = ins["o"], ins["d"], ins["seeds"], ins["skip"]
+            for k, ptr in outs.items():
+                setattr(res, k, ptr)
+            _check(lib().dr_trace_radiance(self._h, n, C.byref(rays), C.byref(params), C.byref(res), device_pointers))
+        return self._list_query([("o", o, (3,), np.float32, "torch.float32"), ("d", d, (3,), np.float32, "torch.float32"),
+                                 ("seeds", seeds, (), np.uint64, "torch.int64"), ("skip", skip, (), np.int32, "torch.int32")],
+                                {k: (RADIANCE_CHANNELS[k][0], (3,) if RADIANCE_CHANNELS[k][1] > 1 else ()) for k in channels}, call)
 
     # ---- all hits (dr_trace_all_hits)
     def trace_all(self, o, d, tmax=None, max_hits=4, kinds=("triangle", "sphere"), channels=("count", "t", "object")):
@@ -974,54 +955,16 @@ class Context:
         params = DrAllHitsParams()
         _check(lib().dr_allhits_defaults(C.byref(params)))
         params.max_hits, params.kind_mask = K, sum(ALLHITS_KINDS[k] for k in set(kinds))
-        shape = lambda n, k: (n,) if ALLHITS_CHANNELS[k][1] == 0 else ((n, K) if ALLHITS_CHANNELS[k][1] == 1 else (n, K, ALLHITS_CHANNELS[k][1]))
-        given = [a for a in (o, d, tmax) if a is not None]
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
-        rays, outs = DrRayBuffers(), DrAllHitsBuffers()
-        if not any(is_torch):
-            o, d = _f32(o), _f32(d)
-            n = o.shape[0] if o.ndim == 2 else -1
-            if o.shape != (n, 3) or d.shape != (n, 3):
-                raise ValueError("o and d must both be [n, 3]")
-            if tmax is not None:
-                tmax = _f32(tmax)
-                if tmax.shape != (n,):
-                    raise ValueError("tmax must be [n]")
-            out = {k: np.empty(shape(n, k), dtype=ALLHITS_CHANNELS[k][0]) for k in channels}
-            rays.origin, rays.dir, rays.tmax = o.ctypes.data, d.ctypes.data, (tmax.ctypes.data if tmax is not None else None)
-            for k, a in out.items():
-                setattr(outs, k, a.ctypes.data)
-            _check(lib().dr_trace_all_hits(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 0))
-            return out
-        if not all(is_torch):
-            raise TypeError("o, d and tmax must all be numpy arrays or all torch tensors")
-        import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-        for name, a in (("o", o), ("d", d), ("tmax", tmax)):
-            if a is None:
-                continue
-            if a.device != dev:
-                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
-            if a.dtype != torch.float32:
-                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        n = o.shape[0] if o.dim() == 2 else -1
-        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
-            raise ValueError("o and d must both be [n, 3]")
-        if tmax is not None and tuple(tmax.shape) != (n,):
-            raise ValueError("tmax must be [n]")
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty(shape(n, k), dtype=tdt[ALLHITS_CHANNELS[k][0]], device=dev) for k in channels}
-        rays.origin, rays.dir, rays.tmax = o.data_ptr(), d.data_ptr(), (tmax.data_ptr() if tmax is not None else None)
-        for k, a in out.items():
-            setattr(outs, k, a.data_ptr())
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        _check(lib().dr_trace_all_hits(self._h, n, C.byref(rays), C.byref(params), C.byref(outs), 1))
-        cur.wait_stream(lib_stream)
-        return out
+        tail = lambda k: () if ALLHITS_CHANNELS[k][1] == 0 else ((K,) if ALLHITS_CHANNELS[k][1] == 1 else (K, ALLHITS_CHANNELS[k][1]))
+
+        def call(ins, outs, n, device_pointers):
+            rays, res = DrRayBuffers(), DrAllHitsBuffers()
+            rays.origin, rays.dir, rays.tmax = ins["o"], ins["d"], ins["tmax"]
+            for k, ptr in outs.items():
+                setattr(res, k, ptr)
+            _check(lib().dr_trace_all_hits(self._h, n, C.byref(rays), C.byref(params), C.byref(res), device_pointers))
+        return self._list_query([("o", o, (3,), np.float32, "float32"), ("d", d, (3,), np.float32, "float32"), ("tmax", tmax, (), np.float32, "float32")],
+                                {k: (ALLHITS_CHANNELS[k][0], tail(k)) for k in channels}, call)
 
     def contains(self, points, directions=None):
         """Which points lie inside the resident scene's CLOSED triangle meshes: bool [n] for points [n, 3] (numpy in, numpy out; torch tensors on
@@ -1083,54 +1026,15 @@ class Context:
                 raise ValueError("unknown nearest channel %r (known: %s)" % (k, ", ".join(NEAREST_CHANNELS)))
         if not channels:
             raise ValueError("no channel asked for")
-        spec = lambda k: NEAREST_CHANNELS[k]
-        given = [a for a in (p, rmax) if a is not None]
-        is_torch = [type(a).__module__.split(".")[0] == "torch" for a in given]
-        pts, outs = DrPointBuffers(), DrNearestBuffers()
-        if not any(is_torch):
-            p = _f32(p)
-            n = p.shape[0] if p.ndim == 2 else -1
-            if p.shape != (n, 3):
-                raise ValueError("p must be [n, 3]")
-            if rmax is not None:
-                rmax = _f32(rmax)
-                if rmax.shape != (n,):
-                    raise ValueError("rmax must be [n]")
-            out = {k: np.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=spec(k)[0]) for k in channels}
-            pts.point, pts.rmax = p.ctypes.data, (rmax.ctypes.data if rmax is not None else None)
-            for k, a in out.items():
-                setattr(outs, k, a.ctypes.data)
-            _check(lib().dr_query_nearest(self._h, n, C.byref(pts), C.byref(outs), 0))
-            return out
-        if not all(is_torch):
-            raise TypeError("p and rmax must both be numpy arrays or both torch tensors")
-        import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-        for name, a in (("p", p), ("rmax", rmax)):
-            if a is None:
-                continue
-            if a.device != dev:
-                raise ValueError("%s is on %s, not on this context's %s" % (name, a.device, dev))
-            if a.dtype != torch.float32:
-                raise TypeError("%s must be float32, not %s" % (name, a.dtype))
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        n = p.shape[0] if p.dim() == 2 else -1
-        if tuple(p.shape) != (n, 3):
-            raise ValueError("p must be [n, 3]")
-        if rmax is not None and tuple(rmax.shape) != (n,):
-            raise ValueError("rmax must be [n]")
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty((n, spec(k)[1]) if spec(k)[1] > 1 else (n,), dtype=tdt[spec(k)[0]], device=dev) for k in channels}
-        pts.point, pts.rmax = p.data_ptr(), (rmax.data_ptr() if rmax is not None else None)
-        for k, a in out.items():
-            setattr(outs, k, a.data_ptr())
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        _check(lib().dr_query_nearest(self._h, n, C.byref(pts), C.byref(outs), 1))
-        cur.wait_stream(lib_stream)
-        return out
+
+        def call(ins, outs, n, device_pointers):
+            pts, res = DrPointBuffers(), DrNearestBuffers()
+            pts.point, pts.rmax = ins["p"], ins["rmax"]
+            for k, ptr in outs.items():
+                setattr(res, k, ptr)
+            _check(lib().dr_query_nearest(self._h, n, C.byref(pts), C.byref(res), device_pointers))
+        return self._list_query([("p", p, (3,), np.float32, "float32"), ("rmax", rmax, (), np.float32, "float32")],
+                                {k: (NEAREST_CHANNELS[k][0], (NEAREST_CHANNELS[k][1],) if NEAREST_CHANNELS[k][1] > 1 else ()) for k in channels}, call)
 
     def pick(self, settings13, W, H, x, y):
         """Every channel of pixel (x, y) of the grid: t, distance, depth (float), object, material (int; -1 on a miss), normal, albedo,

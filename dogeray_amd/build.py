@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdogeray_amd.so")
 HOST_SOURCES = ["rts_reader.cpp", "bvh_builder.cpp", "linearise.cpp", "wide_builder.cpp", "capi_host.cpp", "group.cpp", "context.cpp", "context_render.cpp",
-                "context_pipeline.cpp", "context_accum.cpp", "context_trace.cpp", "context_radiance.cpp", "context_nearest.cpp", "context_allhits.cpp",
+                "context_pipeline.cpp", "context_accum.cpp", "context_query.cpp", "context_trace.cpp", "context_radiance.cpp", "context_nearest.cpp", "context_allhits.cpp",
                 "context_probe.cpp"]
 # one translation unit per family of kernels (kernels.hpp)
 DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip",

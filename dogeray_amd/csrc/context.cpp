@@ -212,7 +212,7 @@ int dr_context_upload_scene(dr_context* c, const dr_scene* s) {
   c->n_prims = (int)img.prims.size();
   c->n_tex = (int)img.tex.size();
   c->slot_to_orig = img.slot_to_orig;
-  c->slot_to_orig_dev.release();   // the old scene's map (dr_render_aov uploads the new one when it first needs it)
+  c->slot_to_orig_dev.release();   // the old scene's map (ensure_slot_to_orig uploads the new one when a call first needs it)
   int depth = 0;
   while (((size_t)1 << depth) < img.prims.size()) depth++;
   c->tree_depth = depth;

@@ -4,6 +4,7 @@
 //   context_render.cpp     per-launch constants, cost feedback, grazing certificate, the launches of dr_render_frame / dr_render_accumulate*
 //   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
+//   context_query.cpp      what the queries on caller lists share: staging in and out, scratch, cursor, the object map's upload
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
 //   context_radiance.cpp   radiance queries on caller rays (dr_trace_radiance)
 //   context_nearest.cpp    nearest-surface point queries (dr_query_nearest)
@@ -119,30 +120,20 @@ struct dr_context {
   DevMem<uint32_t> texels;
   int n_prims = 0, n_tex = 0, tree_depth = 0;
   std::vector<int> slot_to_orig;
-  DevMem<int32_t> slot_to_orig_dev;        // the same map on the device: uploaded by the first dr_render_aov after a scene upload
+  DevMem<int32_t> slot_to_orig_dev;        // the same map on the device: uploaded by the first call that reads it after a scene upload (ensure_slot_to_orig)
   // dr_render_aov with host pointers: the channels are written here, then downloaded
   DevMem<uint8_t> aov_staging;
-  // dr_trace_rays: the per-ray {t, slot} words between the trace kernel and the surface pass, the persistent kernel's cursor, and the staging of host
-  // rays and results -- all made by the first call that needs them (a context that never traces allocates nothing)
-  DevMem<uint32_t> trace_hit;
-  DevMem<unsigned> trace_cursor;
-  DevMem<uint8_t> trace_staging;
-  int trace_kernel = 0;                    // option (private, for the tests): 0 plan_trace decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
-  // dr_trace_radiance: the staging of host rays and results and the persistent kernel's cursor, made by the first call that needs them
-  DevMem<uint8_t> radiance_staging;
-  DevMem<unsigned> radiance_cursor;
-  int radiance_kernel = 0;                 // option (private, for the tests): 0 plan_radiance decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
-  // dr_query_nearest: the scene's largest |e1| + |e2| / radius (the pruning slack's constant, device_nearest.hpp), the per-query {d2 bits, slot}
-  // words between the walk kernel and the finishing pass, and the staging of host points and results, made by the first call that needs them
-  float near_lmax = 0;
-  DevMem<uint32_t> nearest_key;
-  DevMem<uint8_t> nearest_staging;
-  // dr_trace_all_hits: the per-entry {t bits, slot} words between the walk kernel and the surface pass, the persistent kernel's cursor and the staging
-  // of host rays and results, made by the first call that needs them
-  DevMem<uint32_t> allhits_hit;
-  DevMem<unsigned> allhits_cursor;
-  DevMem<uint8_t> allhits_staging;
-  int allhits_kernel = 0;                  // option (private, for the tests): 0 plan_allhits decides, 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
+  // the queries on caller lists (dr_trace_rays, dr_trace_radiance, dr_query_nearest, dr_trace_all_hits; context_query.cpp): the staging of host inputs
+  // and results, the two words per entry between a walk kernel and its surface / finishing pass ({t or d2 bits, slot}), and the persistent kernels'
+  // cursor -- each made by the first call that needs it (a context that never queries allocates nothing).  One of each serves every query: they are
+  // used on `stream` only, one call's work queued behind the other's, and DevMem::grow drains `stream` before it frees what is too small, so no
+  // kernel of an earlier device-pointer call still reads what a later call replaces
+  DevMem<uint8_t> query_staging;
+  DevMem<uint32_t> query_scratch;
+  DevMem<unsigned> query_cursor;
+  // options (private, for the tests): 0 the plan decides (launch_plan.hpp), 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
+  int trace_kernel = 0, radiance_kernel = 0, allhits_kernel = 0;
+  float near_lmax = 0;                     // dr_query_nearest: the scene's largest |e1| + |e2| / radius (the pruning slack's constant, device_nearest.hpp)
   // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
   // guides' key (settings13, W, H, scene generation), and the staging of host outputs
   DevMem<float> dn_planes;
@@ -307,5 +298,19 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
 // context_pipeline.cpp
 int join_pipeline(dr_context* c);
 int pipeline_flush(dr_context* c);
+// context_query.cpp: a list of n caller items through the device and back
+struct QueryIn { const void* p; int words; };                 // a caller's input array (null: not given) and its 4-byte words per item
+struct QueryOut { void* p; int words; bool per_item; };       // a channel (null: not wanted), its 4-byte words per entry; per_item: one entry per item whatever K
+constexpr int QUERY_MAX_IN = 4, QUERY_MAX_OUT = 8;
+struct QueryIo {
+  const void* in[QUERY_MAX_IN];            // where the kernels read input k (null: not given) ...
+  void* out[QUERY_MAX_OUT];                // ... and write channel k (null: not wanted): the caller's memory, or staging
+  size_t out_bytes[QUERY_MAX_OUT];
+};
+int ensure_slot_to_orig(dr_context* c);
+int query_begin(dr_context* c, size_t n, size_t K, const QueryIn* in, int n_in, const QueryOut* out, int n_out, bool device_pointers, QueryIo& io);
+int query_scratch(dr_context* c, size_t entries, uint32_t*& words);
+int query_cursor(dr_context* c, unsigned*& cursor);
+int query_end(dr_context* c, const QueryOut* out, int n_out, bool device_pointers, const QueryIo& io);
 
 }  // namespace dr

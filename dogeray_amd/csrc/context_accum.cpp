@@ -149,11 +149,7 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
     return DR_ERR_INVALID;
   }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
-  if (!c->slot_to_orig_dev) {
-    DR_TRY(c->slot_to_orig_dev.alloc(c->slot_to_orig.size()));
-    if (!c->slot_to_orig.empty())
-      HIP_TRY(hipMemcpyAsync(c->slot_to_orig_dev, c->slot_to_orig.data(), c->slot_to_orig.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  }
+  DR_TRY(ensure_slot_to_orig(c));
   AovLaunch A;
   A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
   A.focus = settings13[7];

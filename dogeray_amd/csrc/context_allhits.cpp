@@ -1,4 +1,5 @@
-// Every crossing of a caller ray (dr_trace_all_hits): the arguments judged, the context's scratch, the launches of kernels_allhits.hip.
+// Every crossing of a caller ray (dr_trace_all_hits): the arguments judged, the plan, the launches of kernels_allhits.hip.  The list's way in and out:
+// context_query.cpp.
 #include "context.hpp"
 
 using namespace dr;
@@ -21,68 +22,42 @@ int dr_trace_all_hits(dr_context* c, int64_t n, const dr_ray_buffers* rays, cons
   if (prm.max_hits < 0 || prm.max_hits > DR_ALLHITS_MAX) { set_error("all hits: max_hits must be in [0, " + std::to_string(DR_ALLHITS_MAX) + "]"); return DR_ERR_INVALID; }
   if (prm.kind_mask <= 0 || prm.kind_mask > (DR_ALLHITS_TRIANGLES | DR_ALLHITS_SPHERES)) { set_error("all hits: kind_mask names no kind, or an unknown one"); return DR_ERR_INVALID; }
   const int K = prm.max_hits;
-  // channel k: where the caller wants it and its words per entry (count: per ray; count, t, object: the walk kernel's; the others: the surface pass's)
-  void* const want[8] = {out->count, out->t, out->object, out->material, out->distance, out->normal, out->uv, out->albedo};
-  const int words[8] = {1, 1, 1, 1, 1, 3, 2, 3};
+  // count: per ray, the others per entry; count, t, object: the walk kernel's; the others: the surface pass's
+  const QueryIn in[3] = {{rays->origin, 3}, {rays->dir, 3}, {rays->tmax, 1}};
+  const QueryOut ch[8] = {{out->count, 1, true}, {out->t, 1, false}, {out->object, 1, false}, {out->material, 1, false}, {out->distance, 1, false},
+                          {out->normal, 3, false}, {out->uv, 2, false}, {out->albedo, 3, false}};
   bool some = false, listed = false, surface = false;
-  for (int k = 0; k < 8; k++) { some = some || want[k]; listed = listed || (k >= 1 && want[k]); surface = surface || (k >= 3 && want[k]); }
+  for (int k = 0; k < 8; k++) { some = some || ch[k].p; listed = listed || (k >= 1 && ch[k].p); surface = surface || (k >= 3 && ch[k].p); }
   if (!some) { set_error("all hits: no output channel"); return DR_ERR_INVALID; }
   if (K == 0 && listed) { set_error("all hits: max_hits 0 returns `count` only"); return DR_ERR_INVALID; }
   if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
   if (n == 0) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
-  if (out->object && !c->slot_to_orig_dev) {
-    DR_TRY(c->slot_to_orig_dev.alloc(c->slot_to_orig.size()));
-    if (!c->slot_to_orig.empty())
-      HIP_TRY(hipMemcpyAsync(c->slot_to_orig_dev, c->slot_to_orig.data(), c->slot_to_orig.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  }
+  if (out->object) DR_TRY(ensure_slot_to_orig(c));
   const AllHitsPlan plan = plan_allhits(n, c->wide != nullptr, c->num_cus, c->allhits_kernel);
-  const size_t rays_n = (size_t)n;
-  auto entries = [rays_n, K](int k) { return k == 0 ? rays_n : rays_n * (size_t)K; };
-  if (surface) DR_TRY(c->allhits_hit.grow(2 * rays_n * (size_t)K, c->stream));
-  if (plan.kernel == ALLHITS_KERNEL_PERSISTENT && !c->allhits_cursor) DR_TRY(c->allhits_cursor.alloc(1));
+  QueryIo io;
+  DR_TRY(query_begin(c, (size_t)n, (size_t)K, in, 3, ch, 8, device_pointers != 0, io));
   AllHitsLaunch A;
   memset(&A, 0, sizeof(A));
   A.n = (unsigned)n;
   A.K = K; A.kind_mask = prm.kind_mask;
   A.slot_to_orig = c->slot_to_orig_dev;
-  A.hit = surface ? c->allhits_hit.p : nullptr;
-  A.cursor = c->allhits_cursor;
-  void* dev[8] = {nullptr};
-  if (device_pointers) {
-    A.origin = rays->origin; A.dir = rays->dir; A.tmax = rays->tmax;
-    for (int k = 0; k < 8; k++) dev[k] = want[k];
-  } else {
-    // staging: origin 3n | dir 3n | tmax n floats, then the wanted channels
-    size_t bytes = rays_n * 7 * sizeof(float);
-    for (int k = 0; k < 8; k++) if (want[k]) bytes += entries(k) * (size_t)words[k] * 4;
-    DR_TRY(c->allhits_staging.grow(bytes, c->stream));
-    float* const in = reinterpret_cast<float*>(c->allhits_staging.p);
-    HIP_TRY(hipMemcpyAsync(in, rays->origin, rays_n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + 3 * rays_n, rays->dir, rays_n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (rays->tmax) HIP_TRY(hipMemcpyAsync(in + 6 * rays_n, rays->tmax, rays_n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    A.origin = in; A.dir = in + 3 * rays_n; A.tmax = rays->tmax ? in + 6 * rays_n : nullptr;
-    size_t off = rays_n * 7 * sizeof(float);
-    for (int k = 0; k < 8; k++) if (want[k]) { dev[k] = c->allhits_staging + off; off += entries(k) * (size_t)words[k] * 4; }
-  }
-  A.count = (int32_t*)dev[0]; A.t = (float*)dev[1]; A.object = (int32_t*)dev[2];
-  A.material = (int32_t*)dev[3]; A.distance = (float*)dev[4]; A.normal = (float*)dev[5]; A.uv = (float*)dev[6]; A.albedo = (float*)dev[7];
+  A.origin = (const float*)io.in[0]; A.dir = (const float*)io.in[1]; A.tmax = (const float*)io.in[2];
+  A.count = (int32_t*)io.out[0]; A.t = (float*)io.out[1]; A.object = (int32_t*)io.out[2];
+  A.material = (int32_t*)io.out[3]; A.distance = (float*)io.out[4]; A.normal = (float*)io.out[5]; A.uv = (float*)io.out[6]; A.albedo = (float*)io.out[7];
+  if (surface) DR_TRY(query_scratch(c, (size_t)n * (size_t)K, A.hit));
+  if (plan.kernel == QUERY_KERNEL_PERSISTENT) DR_TRY(query_cursor(c, A.cursor));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   fill_scene(c, P);
-  if (plan.kernel == ALLHITS_KERNEL_PERSISTENT) HIP_TRY(hipMemsetAsync(c->allhits_cursor, 0, sizeof(unsigned), c->stream));      // a stale cursor would drop rays
   launch_allhits(c->stream, P, plan, A);
   HIP_TRY(hipGetLastError());
   if (surface) {
     launch_allhits_surface(c->stream, P, A);
     HIP_TRY(hipGetLastError());
   }
-  if (device_pointers) return DR_OK;
-  for (int k = 0; k < 8; k++)
-    if (want[k]) HIP_TRY(hipMemcpyAsync(want[k], dev[k], entries(k) * (size_t)words[k] * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
+  return query_end(c, ch, 8, device_pointers != 0, io);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_allhits.hpp"
+#include "device_list.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -28,9 +29,8 @@ __global__ __launch_bounds__(256) void allhits_plain_kernel(RenderParams P, AllH
   allhits_flush(A, i, count, list);
 }
 
-// The persistent kernel, in the shape of trace_persistent_kernel (kernels_trace.hip): a wave's lanes are a pool of ray slots that refill from the ray list
-// -- chunks of ALLHITS_CHUNK rays per wave and atomic --, node steps and leaf steps exclusive, a leaf step once PARK lanes stand at a leaf.  A lane's list
-// is flushed at the refill that gives it its next ray.
+// The persistent kernel (the wave loop: device_list.hpp; parameters: launch_plan.hpp): lanes refill from the ray list once REFILL_MIN of them want a ray or
+// nobody walks.  A lane's list is flushed at the refill that gives it its next ray.
 template <int OCC, int REFILL_MIN, int PARK>
 __global__ __launch_bounds__(256, OCC) void allhits_persistent_kernel(RenderParams P, AllHitsLaunch A) {
   __shared__ int lds[4 * WIDE_STACK * 64];
@@ -50,53 +50,32 @@ __global__ __launch_bounds__(256, OCC) void allhits_persistent_kernel(RenderPara
   unsigned idx = 0;
   float cap = 0;
   int count = 0;
-  unsigned chunk_next = 0, chunk_end = 0;      // this wave's share of the ray list (wave-uniform)
-  bool exhausted = false;
+  ListFeed feed;
   for (;;) {
     const unsigned long long want = __ballot(tr.node == LANE_DONE || tr.node == LANE_REFILL);
     const unsigned long long walking = __ballot(tr.node >= 0);
     if (want != 0ull && ((int)__popcll(want) >= REFILL_MIN || walking == 0ull)) {
       if (tr.node == LANE_DONE) allhits_flush(A, idx, count, my_list);
       const bool mine = tr.node == LANE_DONE || tr.node == LANE_REFILL;
-      if (!exhausted) {
-        const int cnt = (int)__popcll(want);
-        if (chunk_next + (unsigned)cnt > chunk_end && chunk_next >= chunk_end) {
-          unsigned b = 0;
-          if (lane == 0) b = atomicAdd(A.cursor, (unsigned)ALLHITS_CHUNK);
-          chunk_next = (unsigned)__builtin_amdgcn_readfirstlane((int)b); chunk_end = chunk_next + (unsigned)ALLHITS_CHUNK;
-        }
-        const unsigned base = chunk_next;
-        const unsigned my = base + (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(want >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)want, 0u));
-        chunk_next = base + (unsigned)cnt < chunk_end ? base + (unsigned)cnt : chunk_end;
-        if (mine) {
-          if (my < n && my < chunk_end) {
-            idx = my;
-            o = ld3(A.origin + 3 * (size_t)my); d = ld3(A.dir + 3 * (size_t)my);
-            cap = trace_cap(A.tmax ? A.tmax[my] : 10000.0f);
-            inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-            wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
-            trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
-            count = 0;
-            if (!(cap > 0.0f)) tr.node = LANE_DONE;      // a tmax that admits nothing: count 0, written at the next refill
-          } else tr.node = my >= n ? LANE_RETIRED : LANE_REFILL;      // (LANE_REFILL: the chunk ran out in the middle of the wave's request: next refill)
-        }
-        exhausted = chunk_next >= n;
-      } else if (mine) tr.node = LANE_RETIRED;
+      const ListItem it = feed.take<ALLHITS_CHUNK>(want, A.cursor, n);
+      if (mine) {
+        if (it.ok) {
+          idx = it.index;
+          o = ld3(A.origin + 3 * (size_t)idx); d = ld3(A.dir + 3 * (size_t)idx);
+          cap = trace_cap(A.tmax ? A.tmax[idx] : 10000.0f);
+          inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+          wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
+          trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
+          count = 0;
+          if (!(cap > 0.0f)) tr.node = LANE_DONE;      // a tmax that admits nothing: count 0, written at the next refill
+        } else tr.node = it.state;
+      }
       if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
-    for (int u = 0; u < 2; u++) {
-      const bool at_leaf = tr.node >= 0 && (tr.node & 1);
-      const unsigned long long leaves = __ballot(at_leaf), nodes = __ballot(tr.node >= 0 && !(tr.node & 1));
-      const bool do_leaves = leaves != 0ull && ((int)__popcll(leaves) >= PARK || nodes == 0ull || exhausted);
-      const bool do_nodes = !do_leaves || exhausted;
-      if (tr.node >= 0 && (at_leaf ? do_leaves : do_nodes)) {
-        const WideRec r = wide_fetch(walk, tr.node);
-        if (at_leaf) {
-          allhits_wide_leaf(r, o, d, inv, sg, cap, kind_mask, K, count, my_list);
-          wide_pop(tr, ws, my_stack);
-        } else wide_node_compute<false>(r, wr, sg, tr, ws, my_stack, c);
-      }
-    }
+    list_walk_round<PARK>(walk, wr, sg, feed.exhausted, tr, ws, my_stack, c, [&](const WideRec& r) {
+      allhits_wide_leaf(r, o, d, inv, sg, cap, kind_mask, K, count, my_list);
+      wide_pop(tr, ws, my_stack);
+    });
   }
 }
 
@@ -110,7 +89,7 @@ __global__ __launch_bounds__(256) void allhits_surface_kernel(RenderParams P, Al
 
 void launch_allhits(hipStream_t stream, const RenderParams& P, const AllHitsPlan& plan, const AllHitsLaunch& A) {
   const dim3 grid((unsigned)plan.blocks), block(256);
-  if (plan.kernel == ALLHITS_KERNEL_PERSISTENT) {      // (A.cursor: zeroed on this stream by the caller)
+  if (plan.kernel == QUERY_KERNEL_PERSISTENT) {      // (A.cursor: zeroed on this stream by the caller)
     hipLaunchKernelGGL((allhits_persistent_kernel<ALLHITS_OCC, ALLHITS_REFILL_MIN, ALLHITS_PARK>), grid, block, 0, stream, P, A);
   }
   else if (plan.wide) hipLaunchKernelGGL((allhits_plain_kernel<true>), grid, block, 0, stream, P, A);

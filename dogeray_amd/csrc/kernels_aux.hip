@@ -4,6 +4,7 @@
 
 #include "device_rng.hpp"
 #include "device_wide.hpp"
+#include "device_list.hpp"
 #include "device_cert.hpp"
 #include "device_surface.hpp"
 #include "device_sky.hpp"
@@ -300,49 +301,27 @@ __global__ __launch_bounds__(256, OCC) void trace_probe_kernel(RenderParams P, c
   SignMask sg = sign_mask(inv);
   Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned idx = 0;
-  unsigned chunk_next = 0, chunk_end = 0;      // this wave's share of the ray list (wave-uniform)
-  bool exhausted = false;
+  ListFeed feed;
   for (;;) {
     const unsigned long long want = __ballot(tr.node == LANE_DONE || tr.node == LANE_REFILL);
     const unsigned long long walking = __ballot(tr.node >= 0);
     if (want != 0ull && ((int)__popcll(want) >= REFILL_MIN || walking == 0ull)) {
       if (tr.node == LANE_DONE) out[idx] = make_uint2(__float_as_uint(tr.best_t), (unsigned)tr.best_slot);
       const bool mine = tr.node == LANE_DONE || tr.node == LANE_REFILL;
-      if (!exhausted) {
-        const int cnt = (int)__popcll(want);
-        // rays come in chunks of 128 per wave (one atomic on the shared cursor per chunk: a cursor touched at every refill is the bottleneck, 0.35 Grays/s)
-        if (chunk_next + (unsigned)cnt > chunk_end && chunk_next >= chunk_end) {
-          unsigned b = 0;
-          if (lane == 0) b = atomicAdd(cursor, 128u);
-          chunk_next = (unsigned)__builtin_amdgcn_readfirstlane((int)b); chunk_end = chunk_next + 128u;
-        }
-        const unsigned base = chunk_next;
-        const unsigned my = base + (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(want >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)want, 0u));
-        chunk_next = base + (unsigned)cnt < chunk_end ? base + (unsigned)cnt : chunk_end;
-        if (mine) {
-          if (my < n && my < chunk_end) {
-            const float4 a = rays[2 * (size_t)my], b = rays[2 * (size_t)my + 1];
-            idx = my; o = mk(a.x, a.y, a.z); d = mk(b.x, b.y, b.z);
-            inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-            wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
-            trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
-          } else tr.node = my >= n ? LANE_RETIRED : LANE_REFILL;      // (LANE_REFILL: the chunk ran out in the middle of the wave's request: next refill)
-        }
-        exhausted = chunk_next >= n;
-      } else if (mine) tr.node = LANE_RETIRED;
+      const ListItem it = feed.take<128u>(want, cursor, n);
+      if (mine) {
+        if (it.ok) {
+          const float4 a = rays[2 * (size_t)it.index], b = rays[2 * (size_t)it.index + 1];
+          idx = it.index; o = mk(a.x, a.y, a.z); d = mk(b.x, b.y, b.z);
+          inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+          wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
+          trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
+        } else tr.node = it.state;
+      }
       if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
-    for (int u = 0; u < 2; u++) {
-      const bool at_leaf = tr.node >= 0 && (tr.node & 1);
-      const unsigned long long leaves = __ballot(at_leaf), nodes = __ballot(tr.node >= 0 && !(tr.node & 1));
-      const bool do_leaves = leaves != 0ull && ((int)__popcll(leaves) >= PARK || nodes == 0ull || exhausted);
-      const bool do_nodes = !do_leaves || exhausted;
-      if (tr.node >= 0 && (at_leaf ? do_leaves : do_nodes)) {
-        const WideRec r = wide_fetch(walk, tr.node);
-        if (at_leaf) wide_leaf_compute<false>(r, o, d, inv, sg, tr, ws, my_stack, c);
-        else wide_node_compute<false>(r, wr, sg, tr, ws, my_stack, c);
-      }
-    }
+    list_walk_round<PARK>(walk, wr, sg, feed.exhausted, tr, ws, my_stack, c,
+                          [&](const WideRec& r) { wide_leaf_compute<false>(r, o, d, inv, sg, tr, ws, my_stack, c); });
   }
 }
 // the same rays, one per lane, each wave waiting for its slowest (the reference the probe's results are checked against)

@@ -5,6 +5,7 @@
 
 #include "device_core.hpp"
 #include "device_radiance.hpp"
+#include "device_list.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -34,12 +35,11 @@ __global__ __launch_bounds__(256) void radiance_plain_kernel(RenderParams P, Rad
   }
 }
 
-// The persistent kernel, modelled on trace_persistent_kernel (kernels_trace.hip): a wave's lanes are a pool of PATH slots.  A lane keeps its path
+// The persistent kernel (the wave loop: device_list.hpp; parameters: launch_plan.hpp): a wave's lanes are a pool of PATH slots.  A lane keeps its path
 // across bounces and the spp samples of its ray one after another -- so a ray's samples are summed in sample order, on one lane --, and takes a
-// new ray from the list (chunks of RADIANCE_CHUNK rays per wave and atomic) only when the last sample's path has ended: emissive hit, miss, or depth
-// exhausted.  Node steps and leaf steps are exclusive, a leaf step once PARK lanes stand at a leaf.  Once REFILL_MIN lanes have finished their walk or
-// want a ray (or nobody walks) the phase runs: the finished lanes shade -- shade_hit / shade_miss as trace_path calls them, each lane its own draws
-// --, then the lanes without a ray refill.
+// new ray from the list only when the last sample's path has ended: emissive hit, miss, or depth exhausted.  Once REFILL_MIN lanes have finished their
+// walk or want a ray (or nobody walks) the phase runs: the finished lanes shade -- shade_hit / shade_miss as trace_path calls them, each lane its own
+// draws --, then the lanes without a ray refill.
 // Lane states (tr.node): >= 0 walking; LANE_DONE walk finished, to be shaded; LANE_REFILL wants a ray; LANE_RETIRED.  Every state reaches
 // LANE_RETIRED: a walk ends (the walks of trace_persistent_kernel); a LANE_DONE lane leaves the phase walking again with depth + 1 <= max_depth or
 // with sample + 1 <= spp, or as LANE_REFILL; a LANE_REFILL lane leaves it with a ray, retired (the list is used up), or -- its wave's chunk ran
@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256, OCC) void radiance_persistent_kernel(RenderPar
   Xorwow rng; rng.init(0);
   unsigned idx = 0;
   int sample = 0, depth = 0, bounces = 0;      // of ray idx: the sample under way, its closest-hit queries so far, those of all samples
-  unsigned chunk_next = 0, chunk_end = 0;      // this wave's share of the ray list (wave-uniform)
-  bool exhausted = false;
+  ListFeed feed;
   for (;;) {
     const unsigned long long want = __ballot(tr.node == LANE_DONE || tr.node == LANE_REFILL);
     const unsigned long long walking = __ballot(tr.node >= 0);
@@ -87,22 +86,11 @@ __global__ __launch_bounds__(256, OCC) void radiance_persistent_kernel(RenderPar
       const bool mine = tr.node == LANE_REFILL;
       const unsigned long long asking = __ballot(mine);
       if (asking != 0ull) {
-        if (!exhausted) {
-          const int cnt = (int)__popcll(asking);
-          if (chunk_next >= chunk_end) {
-            unsigned b = 0;
-            if (lane == 0) b = atomicAdd(R.cursor, (unsigned)RADIANCE_CHUNK);
-            chunk_next = (unsigned)__builtin_amdgcn_readfirstlane((int)b); chunk_end = chunk_next + (unsigned)RADIANCE_CHUNK;
-          }
-          const unsigned base = chunk_next;
-          const unsigned my = base + (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(asking >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)asking, 0u));
-          chunk_next = base + (unsigned)cnt < chunk_end ? base + (unsigned)cnt : chunk_end;
-          if (mine) {
-            if (my < n && my < chunk_end) { idx = my; sample = 0; bounces = 0; sum = mk(0, 0, 0); begin = true; }
-            else tr.node = my >= n ? LANE_RETIRED : LANE_REFILL;      // (LANE_REFILL: the chunk ran out in the middle of the wave's request: next phase)
-          }
-          exhausted = chunk_next >= n;
-        } else if (mine) tr.node = LANE_RETIRED;
+        const ListItem it = feed.take<RADIANCE_CHUNK>(asking, R.cursor, n);
+        if (mine) {
+          if (it.ok) { idx = it.index; sample = 0; bounces = 0; sum = mk(0, 0, 0); begin = true; }
+          else tr.node = it.state;
+        }
       }
       if (begin) {
         radiance_begin(R, idx, sample, rng);
@@ -117,23 +105,14 @@ __global__ __launch_bounds__(256, OCC) void radiance_persistent_kernel(RenderPar
       }
       if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
-    for (int u = 0; u < 2; u++) {
-      const bool at_leaf = tr.node >= 0 && (tr.node & 1);
-      const unsigned long long leaves = __ballot(at_leaf), nodes = __ballot(tr.node >= 0 && !(tr.node & 1));
-      const bool do_leaves = leaves != 0ull && ((int)__popcll(leaves) >= PARK || nodes == 0ull || exhausted);
-      const bool do_nodes = !do_leaves || exhausted;
-      if (tr.node >= 0 && (at_leaf ? do_leaves : do_nodes)) {
-        const WideRec r = wide_fetch(walk, tr.node);
-        if (at_leaf) wide_leaf_compute<false>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
-        else wide_node_compute<false>(r, wr, sg, tr, ws, my_stack, c);
-      }
-    }
+    list_walk_round<PARK>(walk, wr, sg, feed.exhausted, tr, ws, my_stack, c,
+                          [&](const WideRec& r) { wide_leaf_compute<false>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c); });
   }
 }
 
 void launch_radiance(hipStream_t stream, const RenderParams& P, const RadiancePlan& plan, const RadianceLaunch& R) {
   const dim3 grid((unsigned)plan.blocks), block(256);
-  if (plan.kernel == RADIANCE_KERNEL_PERSISTENT) {      // (R.cursor: zeroed on this stream by the caller)
+  if (plan.kernel == QUERY_KERNEL_PERSISTENT) {      // (R.cursor: zeroed on this stream by the caller)
     hipLaunchKernelGGL((radiance_persistent_kernel<RADIANCE_OCC, RADIANCE_REFILL_MIN, RADIANCE_PARK>), grid, block, 0, stream, P, R);
   }
   else if (plan.traversal == DR_TRAVERSAL_WIDE) hipLaunchKernelGGL((radiance_plain_kernel<DR_TRAVERSAL_WIDE>), grid, block, 0, stream, P, R);

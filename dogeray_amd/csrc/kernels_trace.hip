@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_trace.hpp"
+#include "device_list.hpp"
 #include "device_aov.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
@@ -19,8 +20,8 @@ __device__ __forceinline__ void trace_store(const TraceLaunch& T, unsigned i, Hi
   if (T.hit) { T.hit[2 * (size_t)i] = __float_as_uint(h.t); T.hit[2 * (size_t)i + 1] = (unsigned)h.slot; }
 }
 
-// The persistent kernel, modelled on trace_probe_kernel (kernels_aux.hip; parameters: launch_plan.hpp): a wave's lanes are a pool of ray slots that refill
-// from the ray list -- chunks of TRACE_CHUNK rays per wave and atomic --, node steps and leaf steps exclusive, a leaf step once PARK lanes stand at a leaf.
+// The persistent kernel (the wave loop: device_list.hpp; parameters: launch_plan.hpp): lanes refill from the ray list once REFILL_MIN of them want a ray or
+// nobody walks; a finished lane's result is written at the refill that gives it its next ray.
 // ANY: a lane whose ray holds a primitive at t <= its cap is LANE_DONE at once and takes the next ray at the next refill.
 template <bool ANY, int OCC, int REFILL_MIN, int PARK>
 __global__ __launch_bounds__(256, OCC) void trace_persistent_kernel(RenderParams P, TraceLaunch T) {
@@ -37,52 +38,31 @@ __global__ __launch_bounds__(256, OCC) void trace_persistent_kernel(RenderParams
   Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned idx = 0;
   float cap = 0;
-  unsigned chunk_next = 0, chunk_end = 0;      // this wave's share of the ray list (wave-uniform)
-  bool exhausted = false;
+  ListFeed feed;
   for (;;) {
     const unsigned long long want = __ballot(tr.node == LANE_DONE || tr.node == LANE_REFILL);
     const unsigned long long walking = __ballot(tr.node >= 0);
     if (want != 0ull && ((int)__popcll(want) >= REFILL_MIN || walking == 0ull)) {
       if (tr.node == LANE_DONE) trace_store(T, idx, trace_result(tr.best_t, tr.best_slot, cap));
       const bool mine = tr.node == LANE_DONE || tr.node == LANE_REFILL;
-      if (!exhausted) {
-        const int cnt = (int)__popcll(want);
-        if (chunk_next + (unsigned)cnt > chunk_end && chunk_next >= chunk_end) {
-          unsigned b = 0;
-          if (lane == 0) b = atomicAdd(T.cursor, (unsigned)TRACE_CHUNK);
-          chunk_next = (unsigned)__builtin_amdgcn_readfirstlane((int)b); chunk_end = chunk_next + (unsigned)TRACE_CHUNK;
-        }
-        const unsigned base = chunk_next;
-        const unsigned my = base + (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(want >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)want, 0u));
-        chunk_next = base + (unsigned)cnt < chunk_end ? base + (unsigned)cnt : chunk_end;
-        if (mine) {
-          if (my < n && my < chunk_end) {
-            idx = my;
-            o = ld3(T.origin + 3 * (size_t)my); d = ld3(T.dir + 3 * (size_t)my);
-            cap = trace_cap(T.tmax ? T.tmax[my] : 10000.0f);
-            inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-            wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
-            trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
-            if (!(cap > 0.0f)) tr.node = LANE_DONE;      // a tmax that admits nothing: a miss, written at the next refill
-          } else tr.node = my >= n ? LANE_RETIRED : LANE_REFILL;      // (LANE_REFILL: the chunk ran out in the middle of the wave's request: next refill)
-        }
-        exhausted = chunk_next >= n;
-      } else if (mine) tr.node = LANE_RETIRED;
+      const ListItem it = feed.take<TRACE_CHUNK>(want, T.cursor, n);
+      if (mine) {
+        if (it.ok) {
+          idx = it.index;
+          o = ld3(T.origin + 3 * (size_t)idx); d = ld3(T.dir + 3 * (size_t)idx);
+          cap = trace_cap(T.tmax ? T.tmax[idx] : 10000.0f);
+          inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+          wr = wide_ray(o, d, inv, P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v); sg = sign_mask(inv);
+          trav_begin(tr); ws.top = 0u; ws.sp = 0; ws.sb = 0;
+          if (!(cap > 0.0f)) tr.node = LANE_DONE;      // a tmax that admits nothing: a miss, written at the next refill
+        } else tr.node = it.state;
+      }
       if (__ballot(tr.node != LANE_RETIRED) == 0ull) break;
     }
-    for (int u = 0; u < 2; u++) {
-      const bool at_leaf = tr.node >= 0 && (tr.node & 1);
-      const unsigned long long leaves = __ballot(at_leaf), nodes = __ballot(tr.node >= 0 && !(tr.node & 1));
-      const bool do_leaves = leaves != 0ull && ((int)__popcll(leaves) >= PARK || nodes == 0ull || exhausted);
-      const bool do_nodes = !do_leaves || exhausted;
-      if (tr.node >= 0 && (at_leaf ? do_leaves : do_nodes)) {
-        const WideRec r = wide_fetch(walk, tr.node);
-        if (at_leaf) {
-          wide_leaf_compute<false>(r, o, d, inv, sg, tr, ws, my_stack, c);
-          if (ANY && tr.best_slot >= 0 && tr.best_t <= cap) tr.node = LANE_DONE;
-        } else wide_node_compute<false>(r, wr, sg, tr, ws, my_stack, c);
-      }
-    }
+    list_walk_round<PARK>(walk, wr, sg, feed.exhausted, tr, ws, my_stack, c, [&](const WideRec& r) {
+      wide_leaf_compute<false>(r, o, d, inv, sg, tr, ws, my_stack, c);
+      if (ANY && tr.best_slot >= 0 && tr.best_t <= cap) tr.node = LANE_DONE;
+    });
   }
 }
 
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(256) void trace_surface_kernel(RenderParams P, Trac
 template <bool ANY>
 static void launch_trace_mode(hipStream_t stream, const RenderParams& P, const TracePlan& plan, const TraceLaunch& T) {
   const dim3 grid((unsigned)plan.blocks), block(256);
-  if (plan.kernel == TRACE_KERNEL_PERSISTENT) {      // (T.cursor: zeroed on this stream by the caller)
+  if (plan.kernel == QUERY_KERNEL_PERSISTENT) {      // (T.cursor: zeroed on this stream by the caller)
     hipLaunchKernelGGL((trace_persistent_kernel<ANY, TRACE_OCC, TRACE_REFILL_MIN, TRACE_PARK>), grid, block, 0, stream, P, T);
   }
   else if (plan.traversal == DR_TRAVERSAL_WIDE) hipLaunchKernelGGL((trace_plain_rays_kernel<DR_TRAVERSAL_WIDE, ANY>), grid, block, 0, stream, P, T);

@@ -144,6 +144,20 @@ inline int plan_split_limit(int num_cus, int occupancy, int split_parts, int spl
   return split_parts > 1 ? (int)((long long)num_cus * (occupancy >= 5 ? 5 : 4) * 4 * split_waves / (100 * split_parts)) : 0;
 }
 
+// ---- the queries on caller lists: one ray per lane in workgroups of 256, or -- where the query has one -- a persistent kernel whose waves take chunks
+// of the list (device_list.hpp).  plan_ray_list decides for n > 0 rays: can_persist: the persistent kernel exists for this scene and traversal (it cannot
+// be forced where it does not); force: the query's private option; min_rays: its measured cross-over; occ, chunk: the persistent kernel's waves per SIMD
+// and rays per chunk -- no more waves than chunks.  The per-query constants and what they were measured on stay with each query below.
+enum { QUERY_KERNEL_PLAIN = 0, QUERY_KERNEL_PERSISTENT = 1 };
+enum { QUERY_FORCE_NONE = 0, QUERY_FORCE_PLAIN = 1, QUERY_FORCE_PERSISTENT = 2 };      // options "trace_kernel", "radiance_kernel", "allhits_kernel"
+struct RayListPlan { int kernel, blocks; };      // QUERY_KERNEL_*, workgroups of 256 threads
+inline RayListPlan plan_ray_list(long long n, bool can_persist, int force, long long min_rays, int occ, int chunk, int num_cus) {
+  const bool persistent = can_persist && (force == QUERY_FORCE_PERSISTENT || (force != QUERY_FORCE_PLAIN && n >= min_rays));
+  if (!persistent) return {QUERY_KERNEL_PLAIN, (int)((n + 255) / 256)};
+  const long long full = (long long)num_cus * occ, need = (n + 4 * chunk - 1) / (4 * chunk);
+  return {QUERY_KERNEL_PERSISTENT, (int)(need < full ? need : full)};
+}
+
 // ---- dr_trace_rays (kernels_trace.hip): which kernel walks a list of caller rays, and with what grid
 // The persistent kernel's parameters are those of the trace-only probe's best variant (profiles/r4_j_trace_only_probe.txt, variant 2: six waves per
 // SIMD, refill once 8 lanes are free, leaf steps for 20 lanes: 5.65 Grays/s against 4.91 for one ray per lane); it exists for the wide walk only.
@@ -151,28 +165,19 @@ inline int plan_split_limit(int num_cus, int occupancy, int split_parts, int spl
 // one ray per lane is faster up to 16.8 M rays (x 0.63 at 262 144, x 0.83 at 4.2 M, x 0.98 at 16.8 M), the persistent kernel from 49.3 M on
 // (x 1.07, x 1.09 at 65.7 M; any-hit the same within 0.02); 2^25 lies between the two, near their geometric mean.  A grid of one-ray-per-lane
 // workgroups refills itself, workgroup by workgroup; the persistent waves' refill rounds pay only once the list is long enough for its tail to matter.
-enum { TRACE_KERNEL_PLAIN = 0, TRACE_KERNEL_PERSISTENT = 1 };
-enum { TRACE_FORCE_NONE = 0, TRACE_FORCE_PLAIN = 1, TRACE_FORCE_PERSISTENT = 2 };      // option "trace_kernel"
 constexpr int TRACE_OCC = 6, TRACE_REFILL_MIN = 8, TRACE_PARK = 20;
 constexpr int TRACE_CHUNK = 128;                          // rays a wave takes from the list per atomic
 constexpr long long TRACE_PERSISTENT_MIN_RAYS = 1 << 25;
 struct TracePlan {
-  int kernel;               // TRACE_KERNEL_*
+  int kernel;               // QUERY_KERNEL_*
   int traversal;            // the walk really used: a scene without a wide tree walks the threaded links
   int blocks;               // workgroups of 256 threads
 };
 // n > 0 rays; traversal: the context's; force: option "trace_kernel" (the persistent kernel cannot be forced where it does not exist)
 inline TracePlan plan_trace(long long n, int traversal, bool has_wide, int num_cus, int force) {
-  TracePlan p;
-  p.traversal = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
-  const bool can = p.traversal == DR_TRAVERSAL_WIDE;
-  const bool persistent = can && (force == TRACE_FORCE_PERSISTENT || (force != TRACE_FORCE_PLAIN && n >= TRACE_PERSISTENT_MIN_RAYS));
-  p.kernel = persistent ? TRACE_KERNEL_PERSISTENT : TRACE_KERNEL_PLAIN;
-  if (persistent) {       // no more waves than chunks
-    const long long full = (long long)num_cus * TRACE_OCC, need = (n + 4 * TRACE_CHUNK - 1) / (4 * TRACE_CHUNK);
-    p.blocks = (int)(need < full ? need : full);
-  } else p.blocks = (int)((n + 255) / 256);
-  return p;
+  const int walk = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
+  const RayListPlan l = plan_ray_list(n, walk == DR_TRAVERSAL_WIDE, force, TRACE_PERSISTENT_MIN_RAYS, TRACE_OCC, TRACE_CHUNK, num_cus);
+  return {l.kernel, walk, l.blocks};
 }
 
 // ---- dr_trace_radiance (kernels_radiance.hip): which kernel path-traces a list of caller rays, and with what grid.  As plan_trace: the persistent
@@ -182,28 +187,19 @@ inline TracePlan plan_trace(long long n, int traversal, bool has_wide, int num_c
 // against persistent): camera rays x 0.61 at 2^16, x 0.93 at 2^20, x 1.01 at 2^22, x 1.10 at 2^24; rays that start on the surfaces x 0.89, x 0.99,
 // x 1.51 (2.70 -> 1.79 ms), x 1.84 (8.32 -> 4.51 ms).  The phase at 32 waiting lanes (the render kernel's TRAV_MIN) rather than the trace kernel's 8:
 // a phase here shades, and 2^24 camera rays took 5.66 ms against 6.30 at 8.
-enum { RADIANCE_KERNEL_PLAIN = 0, RADIANCE_KERNEL_PERSISTENT = 1 };
-enum { RADIANCE_FORCE_NONE = 0, RADIANCE_FORCE_PLAIN = 1, RADIANCE_FORCE_PERSISTENT = 2 };      // option "radiance_kernel"
 constexpr int RADIANCE_OCC = 5, RADIANCE_REFILL_MIN = 32, RADIANCE_PARK = 20;
 constexpr int RADIANCE_CHUNK = 64;                        // rays a wave takes from the list per atomic
 constexpr long long RADIANCE_PERSISTENT_MIN_RAYS = 1 << 22;
 struct RadiancePlan {
-  int kernel;               // RADIANCE_KERNEL_*
+  int kernel;               // QUERY_KERNEL_*
   int traversal;            // the walk really used: a scene without a wide tree walks the threaded links
   int blocks;               // workgroups of 256 threads
 };
 // n > 0 rays; traversal: the context's; force: option "radiance_kernel"
 inline RadiancePlan plan_radiance(long long n, int traversal, bool has_wide, int num_cus, int force) {
-  RadiancePlan p;
-  p.traversal = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
-  const bool can = p.traversal == DR_TRAVERSAL_WIDE;
-  const bool persistent = can && (force == RADIANCE_FORCE_PERSISTENT || (force != RADIANCE_FORCE_PLAIN && n >= RADIANCE_PERSISTENT_MIN_RAYS));
-  p.kernel = persistent ? RADIANCE_KERNEL_PERSISTENT : RADIANCE_KERNEL_PLAIN;
-  if (persistent) {       // no more waves than chunks
-    const long long full = (long long)num_cus * RADIANCE_OCC, need = (n + 4 * RADIANCE_CHUNK - 1) / (4 * RADIANCE_CHUNK);
-    p.blocks = (int)(need < full ? need : full);
-  } else p.blocks = (int)((n + 255) / 256);
-  return p;
+  const int walk = (traversal == DR_TRAVERSAL_WIDE && !has_wide) ? DR_TRAVERSAL_THREADED : traversal;
+  const RayListPlan l = plan_ray_list(n, walk == DR_TRAVERSAL_WIDE, force, RADIANCE_PERSISTENT_MIN_RAYS, RADIANCE_OCC, RADIANCE_CHUNK, num_cus);
+  return {l.kernel, walk, l.blocks};
 }
 
 // ---- dr_query_nearest (kernels_nearest.hip): one query per lane, workgroups of 256; the 4-way records where the scene has them, else the threaded links
@@ -224,27 +220,18 @@ inline NearestPlan plan_nearest(long long n, bool has_wide) {      // n > 0 quer
 // and their lists.  ALLHITS_PERSISTENT_MIN_RAYS is the measured cross-over (profiles/allhits_rate.txt, part c; a frame's rays of the bench scene in
 // wavefront order, K = 4): one ray per lane is faster up to 3.3 M rays (x 0.51 at 262 144, x 0.69 at 1.0 M, x 0.86 at 3.3 M), the persistent kernel
 // from 13.1 M on (x 1.22, x 1.40 at 52.5 M; the count alone x 1.34, x 1.58); 2^23 lies between the two, near their geometric mean.
-enum { ALLHITS_KERNEL_PLAIN = 0, ALLHITS_KERNEL_PERSISTENT = 1 };
-enum { ALLHITS_FORCE_NONE = 0, ALLHITS_FORCE_PLAIN = 1, ALLHITS_FORCE_PERSISTENT = 2 };      // option "allhits_kernel"
 constexpr int ALLHITS_OCC = 5, ALLHITS_REFILL_MIN = 8, ALLHITS_PARK = 20;
 constexpr int ALLHITS_CHUNK = 128;                        // rays a wave takes from the list per atomic
 constexpr long long ALLHITS_PERSISTENT_MIN_RAYS = 1 << 23;
 struct AllHitsPlan {
-  int kernel;               // ALLHITS_KERNEL_*
+  int kernel;               // QUERY_KERNEL_*
   bool wide;                // the 4-way records, else the threaded links
   int blocks;               // workgroups of 256 threads
 };
 // n > 0 rays; force: option "allhits_kernel"
 inline AllHitsPlan plan_allhits(long long n, bool has_wide, int num_cus, int force) {
-  AllHitsPlan p;
-  p.wide = has_wide;
-  const bool persistent = has_wide && (force == ALLHITS_FORCE_PERSISTENT || (force != ALLHITS_FORCE_PLAIN && n >= ALLHITS_PERSISTENT_MIN_RAYS));
-  p.kernel = persistent ? ALLHITS_KERNEL_PERSISTENT : ALLHITS_KERNEL_PLAIN;
-  if (persistent) {       // no more waves than chunks
-    const long long full = (long long)num_cus * ALLHITS_OCC, need = (n + 4 * ALLHITS_CHUNK - 1) / (4 * ALLHITS_CHUNK);
-    p.blocks = (int)(need < full ? need : full);
-  } else p.blocks = (int)((n + 255) / 256);
-  return p;
+  const RayListPlan l = plan_ray_list(n, has_wide, force, ALLHITS_PERSISTENT_MIN_RAYS, ALLHITS_OCC, ALLHITS_CHUNK, num_cus);
+  return {l.kernel, has_wide, l.blocks};
 }
 
 // The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)

@@ -344,3 +344,23 @@ def test_errors_raise_before_a_launch(dr, ctx, tmp_path_factory):
         assert e.value.code == dr.ERR_INVALID
     finally:
         fresh.close()
+
+
+def test_bad_tensors_raise_with_the_messages_they_always_had(dr, ctx):
+    """Context.trace_all through the shared marshaller (dogeray_amd._list_query): exception type and message, before anything is launched"""
+    import torch
+    dev = torch.device("cuda", 0)
+    o = np.zeros((4, 3), F)
+    to = torch.from_numpy(o).to(dev)
+    cases = [
+        (TypeError, "o, d and tmax must all be numpy arrays or all torch tensors", lambda: ctx.trace_all(to, o)),
+        (ValueError, "d is on cpu, not on this context's cuda:0", lambda: ctx.trace_all(to, to.cpu())),
+        (TypeError, "d must be float32, not torch.float64", lambda: ctx.trace_all(to, to.double())),
+        (ValueError, "o must be contiguous", lambda: ctx.trace_all(to.t().contiguous().t(), to)),
+        (ValueError, "o and d must both be [n, 3]", lambda: ctx.trace_all(to[:, :2].contiguous(), to)),
+        (ValueError, "tmax must be [n]", lambda: ctx.trace_all(to, to, torch.ones(3, device=dev))),
+    ]
+    for kind, message, call in cases:
+        with pytest.raises(kind) as e:
+            call()
+        assert type(e.value) is kind and str(e.value) == message

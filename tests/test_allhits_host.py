@@ -235,3 +235,17 @@ def test_the_plan_and_the_refusals(hk, tmp_path_factory):
         with pytest.raises(RuntimeError):
             hs.allhits(o, d, **bad)
     assert hs.allhits(o[:0], d[:0])["t"].shape == (0, 4)
+
+
+def test_context_trace_all_judges_numpy_shapes_without_a_gpu():
+    """Context.trace_all's shape checks (the shared marshaller, dogeray_amd._list_query) raise before a launch: type and message as ever"""
+    import dogeray_amd as dr
+    ctx = dr.Context.__new__(dr.Context)      # no device behind it: nothing below may reach one
+    o = np.zeros((4, 3), np.float32)
+    for bad in ((o, o[:3]), (o[:, :2], o), (o.reshape(-1), o.reshape(-1))):
+        with pytest.raises(ValueError) as e:
+            ctx.trace_all(*bad)
+        assert str(e.value) == "o and d must both be [n, 3]"
+    with pytest.raises(ValueError) as e:
+        ctx.trace_all(o, o, np.zeros(3, np.float32))
+    assert str(e.value) == "tmax must be [n]"

@@ -265,3 +265,24 @@ def test_refusals(dr, hk, ctx, tmp_path_factory):
         ctx.nearest(torch.zeros((3, 4), dtype=torch.float32, device=dev).t())      # [4, 3], not contiguous
     got = ctx.nearest(tp)
     assert np.array_equal(bits(got["distance"].cpu().numpy()), bits(want["distance"])) and np.array_equal(got["object"].cpu().numpy(), want["object"])
+
+
+def test_bad_tensors_raise_with_the_messages_they_always_had(dr, ctx):
+    """Context.nearest through the shared marshaller (dogeray_amd._list_query): exception type and message, before anything is launched"""
+    import torch
+    dev = torch.device("cuda", 0)
+    p = np.zeros((4, 3), F)
+    tp = torch.from_numpy(p).to(dev)
+    cases = [
+        (TypeError, "p and rmax must both be numpy arrays or both torch tensors", lambda: ctx.nearest(tp, np.ones(4, F))),
+        (ValueError, "p is on cpu, not on this context's cuda:0", lambda: ctx.nearest(torch.from_numpy(p))),
+        (TypeError, "p must be float32, not torch.float64", lambda: ctx.nearest(tp.double())),
+        (TypeError, "rmax must be float32, not torch.float64", lambda: ctx.nearest(tp, torch.ones(4, dtype=torch.float64, device=dev))),
+        (ValueError, "p must be contiguous", lambda: ctx.nearest(torch.zeros((3, 4), dtype=torch.float32, device=dev).t())),
+        (ValueError, "p must be [n, 3]", lambda: ctx.nearest(tp[:, :2].contiguous())),
+        (ValueError, "rmax must be [n]", lambda: ctx.nearest(tp, torch.ones(3, device=dev))),
+    ]
+    for kind, message, call in cases:
+        with pytest.raises(kind) as e:
+            call()
+        assert type(e.value) is kind and str(e.value) == message

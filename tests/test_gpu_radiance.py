@@ -353,3 +353,26 @@ def test_refusals(dr, ctx, shading):
     with pytest.raises(TypeError):
         ctx.radiance(to, td, skip=torch.zeros(4, dtype=torch.int64, device=dev))
     restore(dr, ctx)
+
+
+def test_bad_tensors_raise_with_the_messages_they_always_had(dr, ctx):
+    """Context.radiance through the shared marshaller (dogeray_amd._list_query): exception type and message, before anything is launched"""
+    import torch
+    dev = torch.device("cuda", 0)
+    o = np.zeros((4, 3), np.float32)
+    to = torch.from_numpy(o).to(dev)
+    cases = [
+        (TypeError, "o, d, seeds and skip must all be numpy arrays or all torch tensors", lambda: ctx.radiance(to, o)),
+        (TypeError, "o, d, seeds and skip must all be numpy arrays or all torch tensors", lambda: ctx.radiance(to, to, skip=np.zeros(4, np.int32))),
+        (ValueError, "d is on cpu, not on this context's cuda:0", lambda: ctx.radiance(to, torch.from_numpy(o))),
+        (TypeError, "d must be torch.float32, not torch.float64", lambda: ctx.radiance(to, to.double())),
+        (TypeError, "seeds must be torch.int64, not torch.int32", lambda: ctx.radiance(to, to, seeds=torch.zeros(4, dtype=torch.int32, device=dev))),
+        (TypeError, "skip must be torch.int32, not torch.int64", lambda: ctx.radiance(to, to, skip=torch.zeros(4, dtype=torch.int64, device=dev))),
+        (ValueError, "d must be contiguous", lambda: ctx.radiance(to, to.t().contiguous().t())),
+        (ValueError, "o and d must both be [n, 3]", lambda: ctx.radiance(to, to[:3])),
+        (ValueError, "seeds and skip must be [n]", lambda: ctx.radiance(to, to, seeds=torch.zeros(3, dtype=torch.int64, device=dev))),
+    ]
+    for kind, message, call in cases:
+        with pytest.raises(kind) as e:
+            call()
+        assert type(e.value) is kind and str(e.value) == message

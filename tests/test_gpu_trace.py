@@ -368,3 +368,26 @@ def test_probe_rays_are_the_rays_the_probe_walks(dr, ctx, synth):
     assert (d != 0).any(axis=1).all() and np.isfinite(o).all() and np.isfinite(d).all()
     t = ctx.trace(o, d)["t"]
     assert (t > 0).any() and (t < 0).any()
+
+
+def test_bad_tensors_raise_with_the_messages_they_always_had(dr, ctx):
+    """Context.trace through the shared marshaller (dogeray_amd._list_query): exception type and message, before anything is launched"""
+    import torch
+    dev = torch.device("cuda", 0)
+    o = np.zeros((4, 3), np.float32)
+    to = torch.from_numpy(o).to(dev)
+    cases = [
+        (TypeError, "o, d and tmax must all be numpy arrays or all torch tensors", lambda: ctx.trace(to, o)),
+        (TypeError, "o, d and tmax must all be numpy arrays or all torch tensors", lambda: ctx.trace(o, o, tmax=torch.ones(4, device=dev))),
+        (ValueError, "d is on cpu, not on this context's cuda:0", lambda: ctx.trace(to, torch.from_numpy(o))),
+        (TypeError, "d must be float32, not torch.float64", lambda: ctx.trace(to, to.double())),
+        (TypeError, "tmax must be float32, not torch.int32", lambda: ctx.trace(to, to, tmax=torch.ones(4, dtype=torch.int32, device=dev))),
+        (ValueError, "d must be contiguous", lambda: ctx.trace(to, to.t().contiguous().t())),
+        (ValueError, "o and d must both be [n, 3]", lambda: ctx.trace(to, to[:3])),
+        (ValueError, "o and d must both be [n, 3]", lambda: ctx.trace(to.reshape(-1), to.reshape(-1))),
+        (ValueError, "tmax must be [n]", lambda: ctx.trace(to, to, tmax=torch.ones(3, device=dev))),
+    ]
+    for kind, message, call in cases:
+        with pytest.raises(kind) as e:
+            call()
+        assert type(e.value) is kind and str(e.value) == message

@@ -211,3 +211,18 @@ def test_rmax_contract(stem, tmp_path_factory):
                 out = sc.nearest(p, rmax, walk=walk, tree=tree, nthreads=4)
                 bad = differing(out, ref, n)
                 assert len(bad) == 0, "rmax %s, walk %d tree %d: %s" % (name, walk, tree, describe(p, out, ref, bad))
+
+
+def test_context_nearest_judges_numpy_shapes_without_a_gpu():
+    """Context.nearest's shape checks (the shared marshaller, dogeray_amd._list_query) raise before the library is called: type and message as ever"""
+    import dogeray_amd as dr
+    ctx = dr.Context.__new__(dr.Context)      # no device behind it: nothing below may reach one
+    p = np.zeros((4, 3), np.float32)
+    for bad in (p[:, :2], p.reshape(-1), None):
+        with pytest.raises(ValueError) as e:
+            ctx.nearest(bad)
+        assert str(e.value) == "p must be [n, 3]"
+    for rmax in (np.ones(3, np.float32), np.ones((4, 1), np.float32)):
+        with pytest.raises(ValueError) as e:
+            ctx.nearest(p, rmax=rmax)
+        assert str(e.value) == "rmax must be [n]"

@@ -146,3 +146,18 @@ def test_plan_table(hk):
         assert hk.radiance_plan(n, traversal, has_wide, CUS, force) == (kernel, walked, blocks), (n, traversal, has_wide, force)
     for cus in (1, 64, 256, 304):
         assert hk.radiance_plan(2 ** 31 - 1, WIDE, True, cus, 0) == (PERSISTENT, WIDE, cus * occ)
+
+
+def test_context_radiance_judges_numpy_shapes_without_a_gpu():
+    """Context.radiance's shape checks (the shared marshaller, dogeray_amd._list_query) raise before a launch: type and message as ever"""
+    import dogeray_amd as dr
+    ctx = dr.Context.__new__(dr.Context)      # no device behind it: nothing below may reach one
+    o = np.zeros((4, 3), np.float32)
+    for bad in ((o, o[:3]), (o[:, :2], o), (o.reshape(-1), o.reshape(-1))):
+        with pytest.raises(ValueError) as e:
+            ctx.radiance(*bad)
+        assert str(e.value) == "o and d must both be [n, 3]"
+    for kw in (dict(seeds=np.zeros(3, np.uint64)), dict(skip=np.zeros(5, np.int32)), dict(seeds=np.zeros(4, np.uint64), skip=np.zeros((4, 1), np.int32))):
+        with pytest.raises(ValueError) as e:
+            ctx.radiance(o, o, **kw)
+        assert str(e.value) == "seeds and skip must be [n]"

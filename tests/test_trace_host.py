@@ -162,3 +162,18 @@ def test_surface_pass_reproduces_the_aov_channels(hk, orc, tmp_path, name):
             same = np.array_equal(ck.bits(out[k]), ck.bits(want)) if want.dtype == np.float32 else np.array_equal(out[k], want)
             assert same, "%s channel %s traversal %d" % (name, k, traversal)
     assert (a["t"] > 0).any()
+
+
+def test_context_trace_judges_numpy_shapes_without_a_gpu():
+    """Context.trace's shape checks (the shared marshaller, dogeray_amd._list_query) raise before the library is called: type and message as ever"""
+    import dogeray_amd as dr
+    ctx = dr.Context.__new__(dr.Context)      # no device behind it: nothing below may reach one
+    o = np.zeros((4, 3), np.float32)
+    for bad in ((o, o[:3]), (o[:, :2], o), (o.reshape(-1), o.reshape(-1)), (None, o)):
+        with pytest.raises(ValueError) as e:
+            ctx.trace(*bad)
+        assert str(e.value) == "o and d must both be [n, 3]"
+    for kw in (dict(tmax=np.ones(3, np.float32)), dict(tmax=np.ones((4, 1), np.float32))):
+        with pytest.raises(ValueError) as e:
+            ctx.trace(o, o, **kw)
+        assert str(e.value) == "tmax must be [n]"

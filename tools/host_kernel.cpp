@@ -833,7 +833,7 @@ int hk_trace(void* hv, int traversal, int tree, int mode, long long n, const flo
   P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
   P.pairs = img.pairs.data(); P.prims = img.prims.data();
   std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
-  const int walk = plan_trace(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, TRACE_FORCE_PLAIN).traversal;
+  const int walk = plan_trace(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, QUERY_FORCE_PLAIN).traversal;
   for (long long i = 0; i < n; i++) {
     const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     const float cap = tmax ? tmax[i] : 10000.0f;
@@ -881,7 +881,7 @@ int hk_ray_surface(void* hv, int tree, long long n, const float* o, const float*
   }
   return 0;
 }
-// launch_plan.hpp plan_trace: out3 = kernel (TRACE_KERNEL_*), the traversal really walked, workgroups
+// launch_plan.hpp plan_trace: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
 void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
   const TracePlan p = plan_trace(n, traversal, has_wide != 0, num_cus, force);
   out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
@@ -915,7 +915,7 @@ int hk_radiance(void* hv, int traversal, int tree, long long n, const float* o, 
   memset(&R, 0, sizeof(R));
   R.origin = o; R.dir = d; R.seed = seed; R.skip = skip; R.n = (unsigned)n; R.spp = spp; R.base_seed = base_seed; R.radiance = radiance; R.bounces = bounces;
   std::vector<int> stack((size_t)WIDE_STACK * 64 > (size_t)ORDERED_STACK * 64 ? (size_t)WIDE_STACK * 64 : (size_t)ORDERED_STACK * 64);
-  const int mode = plan_radiance(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, RADIANCE_FORCE_PLAIN).traversal;
+  const int mode = plan_radiance(n > 0 ? n : 1, traversal, P.wide != nullptr, 1, QUERY_FORCE_PLAIN).traversal;
   const WalkRsrc walk = walk_rsrc(P), wide = wide_rsrc(P);
   for (long long i = 0; i < n; i++) {
     if (mode == DR_TRAVERSAL_WIDE) {
@@ -1064,7 +1064,7 @@ int hk_allhits(void* hv, int walk, int tree, long long n, const float* o, const 
   P.walk = img.walk.data(); P.walk_bytes = (uint32_t)(img.walk.size() * sizeof(DevUnit));
   P.wide = img.wide.empty() ? nullptr : img.wide.data(); P.wide_bytes = (uint32_t)(img.wide.size() * sizeof(DevUnit)); P.wide_pmax = img.wide_pmax; P.wide_mu = img.wide_mu;
   P.prims = img.prims.data(); P.shade = img.shade.data(); P.tex = img.tex.data(); P.texels = img.texels.data();
-  const bool wide = plan_allhits(n > 0 ? n : 1, walk == 2 && P.wide != nullptr, 1, ALLHITS_FORCE_PLAIN).wide;
+  const bool wide = plan_allhits(n > 0 ? n : 1, walk == 2 && P.wide != nullptr, 1, QUERY_FORCE_PLAIN).wide;
   const int K = max_hits;
   const bool surface = material || distance || normal || uv || albedo;
   std::vector<uint32_t> hit(surface ? 2 * (size_t)n * (size_t)K : 0);
@@ -1156,13 +1156,13 @@ int hk_allhits_brute(void* hv, long long n, const float* o, const float* d, cons
 }
 int hk_allhits_max() { return ALLHITS_MAX; }
 int hk_allhits_chunk() { return ALLHITS_CHUNK; }
-// launch_plan.hpp plan_allhits: out3 = kernel (ALLHITS_KERNEL_*), wide (1 / 0), workgroups
+// launch_plan.hpp plan_allhits: out3 = kernel (QUERY_KERNEL_*), wide (1 / 0), workgroups
 void hk_allhits_plan(long long n, int has_wide, int num_cus, int force, int* out3) {
   const AllHitsPlan p = plan_allhits(n, has_wide != 0, num_cus, force);
   out3[0] = p.kernel; out3[1] = p.wide ? 1 : 0; out3[2] = p.blocks;
 }
 long long hk_allhits_persistent_min_rays() { return ALLHITS_PERSISTENT_MIN_RAYS; }
-// launch_plan.hpp plan_radiance: out3 = kernel (RADIANCE_KERNEL_*), the traversal really walked, workgroups
+// launch_plan.hpp plan_radiance: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
 void hk_radiance_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
   const RadiancePlan p = plan_radiance(n, traversal, has_wide != 0, num_cus, force);
   out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
