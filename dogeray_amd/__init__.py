@@ -332,6 +332,51 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+# ---- known-answer hooks (dr_kat_*, and their host mirrors tools/host_kernel.py hk_kat_*): n items in, n items out.
+# hook -> (inputs: (name, dtype, shape tail) each, an item's array [n] + tail; outputs: (dtype, shape) each, "n" standing for n, in the order
+# the wrapper returns them).  Where a hook returns both forms of a step the output has a leading axis of 2.
+_U32, _I32, _U64, _F32 = np.uint32, np.int32, np.uint64, np.float32
+KAT_HOOKS = {
+    "rng": ((), ((np.float64, ("n",)),)),
+    "aabb": ((("o", _F32, (3,)), ("d", _F32, (3,)), ("mn", _F32, (3,)), ("mx", _F32, (3,))), ((_I32, ("n",)), (_F32, ("n",)))),
+    "tri": ((("o", _F32, (3,)), ("d", _F32, (3,)), ("v0", _F32, (3,)), ("v1", _F32, (3,)), ("v2", _F32, (3,))), ((_F32, ("n",)),)),
+    "node_planes": ((("w", _U32, ()), ("a", _F32, ()), ("b", _F32, ())), ((_F32, ("n", 4)), (_F32, ("n", 4)))),
+    "sphere": ((("o", _F32, (3,)), ("d", _F32, (3,)), ("c", _F32, (3,)), ("r", _F32, ())), ((_F32, ("n",)),)),
+    "optics": ((("v", _F32, (3,)), ("nrm", _F32, (3,)), ("eta", _F32, ())), ((_F32, ("n", 3)), (_F32, ("n", 3)), (_F32, ("n",)))),
+    "normal": ((("obj_index", _I32, ()), ("o", _F32, (3,)), ("d", _F32, (3,)), ("t", _F32, ())), ((_F32, ("n", 3)), (_F32, ("n", 3)))),
+    "hit": ((("o", _F32, (3,)), ("d", _F32, (3,))), ((_F32, ("n",)), (_I32, ("n",)), (_I32, ("n",)))),
+    "trace": ((("o", _F32, (3,)), ("d", _F32, (3,))), ((_F32, ("n",)), (_I32, ("n",)))),
+    "sample": ((("seed", _U64, ()), ("warm", _I32, ()), ("kind", _I32, ())), ((_F32, (2, "n", 3)), (_U32, (2, "n", 2)))),
+    "outside": ((("d2", _F32, ()),), ((_I32, ("n",)),)),
+    "tex": ((("tex", _I32, ()), ("u", _F32, ()), ("v", _F32, ())), ((_U32, ("n",)),)),
+    "bounce": ((("obj_index", _I32, ()), ("o", _F32, (3,)), ("d", _F32, (3,)), ("t", _F32, ()), ("atten", _F32, (3,)), ("seed", _U64, ()), ("warm", _I32, ())),
+               ((_I32, (2, "n")), (_F32, (2, "n", 3)), (_F32, (2, "n", 3)), (_F32, (2, "n", 3)), (_U32, (2, "n", 2)))),
+    "miss": ((("d", _F32, (3,)), ("atten", _F32, (3,))), ((_F32, ("n", 3)),)),
+    "camera": ((("x", _I32, ()), ("y", _I32, ()), ("sample", _I32, ())), ((_F32, (2, "n", 3)), (_F32, (2, "n", 3)), (_U32, (2, "n", 2)))),
+    "store": ((("color", _F32, (3,)),), ((_I32, ("n", 3)),)),
+    "tile_feedback": ((("pixel_cost", _U32, (64,)),), ((_U32, ("n",)), (_I32, ("n",)), (_I32, (2 * MAX_REGIONS + 1,)))),
+}
+
+
+def kat_marshal(hook, arrays, call, n=None):
+    """The marshalling of a known-answer hook (KAT_HOOKS[hook]): converts `arrays` to the inputs' dtypes, takes n from the first one, raises
+    ValueError unless every input is [n] + its tail (leading dimension n, n * prod(tail) elements), allocates the outputs zeroed and calls
+    call(n, input pointers, output arrays), which makes the library call and raises on its status.  Returns the outputs as a tuple.  A hook
+    that has its own rule for the count (kat_rng, kat_tile_feedback) passes n: the inputs are then only converted, and the outputs hold
+    max(n, 0) items.  Everything before `call` touches no library."""
+    ins_spec, outs_spec = KAT_HOOKS[hook]
+    assert len(arrays) == len(ins_spec)
+    ins = [np.ascontiguousarray(a, dtype=dt) for a, (_, dt, _) in zip(arrays, ins_spec)]
+    if n is None:
+        n = ins[0].shape[0]
+        for a, (name, _, tail) in zip(ins, ins_spec):
+            if a.shape[0] != n or a.size != n * int(np.prod(tail, dtype=np.int64)):
+                raise ValueError("kat_%s: %s must be [%s]" % (hook, name, ", ".join(["n"] + [str(k) for k in tail])))
+    outs = tuple(np.zeros(tuple(max(n, 0) if k == "n" else k for k in shape), dtype=dt) for dt, shape in outs_spec)
+    call(n, [_p(a) for a in ins], outs)
+    return outs
+
+
 def device_count():
     return lib().dr_device_count()
 
@@ -1203,145 +1248,83 @@ class Context:
                 break
         return frames, result
 
-    # ---- known-answer hooks (tests)
+    # ---- known-answer hooks (tests): shapes and dtypes in KAT_HOOKS, the marshalling in kat_marshal
+    def _kat(self, hook, arrays, head=(), mid=(), outs=lambda out: [_p(a) for a in out], n=None):
+        """kat_marshal calling dr_kat_<hook>(context, *head, n, inputs, *mid, outs(output arrays))"""
+        def call(n, ins, out):
+            _check(getattr(lib(), "dr_kat_" + hook)(self._h, *head, n, *ins, *mid, *outs(out)))
+        return kat_marshal(hook, arrays, call, n)
+
     def kat_rng(self, seed, n):
-        out = np.zeros(n, dtype=np.float64)
-        _check(lib().dr_kat_rng(self._h, seed, n, _p(out)))
-        return out
+        return self._kat("rng", (), head=(seed,), n=n)[0]
 
     def kat_aabb(self, o, d, mn, mx):
-        o, d, mn, mx = map(_f32, (o, d, mn, mx))
-        n = o.shape[0]
-        hit = np.zeros(n, dtype=np.int32)
-        dist = np.zeros(n, dtype=np.float32)
-        _check(lib().dr_kat_aabb(self._h, n, _p(o), _p(d), _p(mn), _p(mx), _p(hit), _p(dist)))
-        return hit, dist
+        return self._kat("aabb", (o, d, mn, mx))
 
     def kat_tri(self, o, d, v0, v1, v2):
-        o, d, v0, v1, v2 = map(_f32, (o, d, v0, v1, v2))
-        n = o.shape[0]
-        t = np.zeros(n, dtype=np.float32)
-        _check(lib().dr_kat_tri(self._h, n, _p(o), _p(d), _p(v0), _p(v1), _p(v2), _p(t)))
-        return t
+        return self._kat("tri", (o, d, v0, v1, v2))[0]
 
     def kat_node_planes(self, w, a, b):
         """(t_mix, t_cvt), 4 per word: the node test's plane arithmetic through v_fma_mix_f32 / through a conversion and an fma"""
-        w = np.ascontiguousarray(w, np.uint32); a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
-        n = len(w)
-        t1 = np.empty(n * 4, np.float32); t2 = np.empty(n * 4, np.float32)
-        _check(lib().dr_kat_node_planes(self._h, n, _p(w), _p(a), _p(b), _p(t1), _p(t2)))
-        return t1, t2
+        t1, t2 = self._kat("node_planes", (w, a, b))
+        return t1.reshape(-1), t2.reshape(-1)
 
     def kat_sphere(self, o, d, c, r):
-        o, d, c, r = map(_f32, (o, d, c, r))
-        n = o.shape[0]
-        t = np.zeros(n, dtype=np.float32)
-        _check(lib().dr_kat_sphere(self._h, n, _p(o), _p(d), _p(c), _p(r), _p(t)))
-        return t
+        return self._kat("sphere", (o, d, c, r))[0]
 
     def kat_optics(self, v, nrm, eta):
-        v, nrm, eta = map(_f32, (v, nrm, eta))
-        n = v.shape[0]
-        refl = np.zeros((n, 3), dtype=np.float32)
-        refr = np.zeros((n, 3), dtype=np.float32)
-        sch = np.zeros(n, dtype=np.float32)
-        _check(lib().dr_kat_optics(self._h, n, _p(v), _p(nrm), _p(eta), _p(refl), _p(refr), _p(sch)))
-        return refl, refr, sch
+        return self._kat("optics", (v, nrm, eta))
 
     def kat_normal(self, obj_index, o, d, t):
         """getnormal K:703-773: (normal[n, 3] before the facing flip, texco[n, 3]) for hits of rays (o, d) at t on objects obj_index."""
-        idx = np.ascontiguousarray(obj_index, dtype=np.int32)
-        o, d, t = _f32(o), _f32(d), _f32(t)
-        n = idx.shape[0]
-        nrm = np.zeros((n, 3), dtype=np.float32)
-        tc = np.zeros((n, 3), dtype=np.float32)
-        _check(lib().dr_kat_normal(self._h, n, _p(idx), _p(o), _p(d), _p(t), _p(nrm), _p(tc)))
-        return nrm, tc
+        return self._kat("normal", (obj_index, o, d, t))
 
     def kat_hit(self, o, d, want_visits=False):
-        o, d = _f32(o), _f32(d)
-        n = o.shape[0]
-        t = np.zeros(n, dtype=np.float32)
-        idx = np.zeros(n, dtype=np.int32)
-        vis = np.zeros(n, dtype=np.int32) if want_visits else None
-        _check(lib().dr_kat_hit(self._h, n, _p(o), _p(d), _p(t), _p(idx), _p(vis) if want_visits else None))
-        return (t, idx, vis) if want_visits else (t, idx)
+        out = self._kat("hit", (o, d), outs=lambda out: [_p(out[0]), _p(out[1]), _p(out[2]) if want_visits else None])
+        return out if want_visits else out[:2]
 
     def kat_trace(self, o, d, variant=0):
         """kat_hit's rays through the lean build of the wide walk (dr_kat_trace): variant 0 one ray per lane, 1..7 the persistent trace-only kernel.
         (t, idx) in kat_hit's convention."""
-        o, d = _f32(o), _f32(d)
-        n = o.shape[0]
-        t = np.zeros(n, dtype=np.float32)
-        idx = np.zeros(n, dtype=np.int32)
-        _check(lib().dr_kat_trace(self._h, int(variant), n, _p(o), _p(d), _p(t), _p(idx)))
-        return t, idx
+        return self._kat("trace", (o, d), head=(int(variant),))
 
     # the shading step: where a hook returns "both forms" the arrays have a leading axis of 2 -- [0] the plain functions, [1] what the persistent kernel runs
     def kat_sample(self, seed, warm, kind):
         """dr_kat_sample: (point float32[2, n, 3], next uint32[2, n, 2]) -- rand_in_unit_sphere / rand_in_unit_disk, and rand_points_merged"""
-        seed, warm, kind = np.ascontiguousarray(seed, np.uint64), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(kind, np.int32)
-        n = seed.shape[0]
-        pt, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
-        _check(lib().dr_kat_sample(self._h, n, _p(seed), _p(warm), _p(kind), _p(pt[0]), _p(nx[0]), _p(pt[1]), _p(nx[1])))
-        return pt, nx
+        return self._kat("sample", (seed, warm, kind), outs=lambda out: [_p(out[0][0]), _p(out[1][0]), _p(out[0][1]), _p(out[1][1])])
 
     def kat_outside(self, d2):
-        d2 = _f32(d2)
-        out = np.zeros(d2.shape[0], np.int32)
-        _check(lib().dr_kat_outside(self._h, d2.shape[0], _p(d2), _p(out)))
-        return out
+        return self._kat("outside", (d2,))[0]
 
     def kat_tex(self, tex, u, v):
-        tex, u, v = np.ascontiguousarray(tex, np.int32), _f32(u), _f32(v)
-        out = np.zeros(tex.shape[0], np.uint32)
-        _check(lib().dr_kat_tex(self._h, tex.shape[0], _p(tex), _p(u), _p(v), _p(out)))
-        return out
+        return self._kat("tex", (tex, u, v))[0]
 
     def kat_bounce(self, obj_index, o, d, t, atten, seed, warm):
         """dr_kat_bounce: (alive int32[2, n], origin, direction, attenuation float32[2, n, 3], next uint32[2, n, 2]) -- shade_hit, and the split"""
-        idx, warm, seed = np.ascontiguousarray(obj_index, np.int32), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(seed, np.uint64)
-        o, d, t, atten = _f32(o), _f32(d), _f32(t), _f32(atten)
-        n = idx.shape[0]
-        alive, nx = np.zeros((2, n), np.int32), np.zeros((2, n, 2), np.uint32)
-        o2, d2, a2 = (np.zeros((2, n, 3), np.float32) for _ in range(3))
-        _check(lib().dr_kat_bounce(self._h, n, _p(idx), _p(o), _p(d), _p(t), _p(atten), _p(seed), _p(warm), _p(alive), _p(o2), _p(d2), _p(a2), _p(nx)))
-        return alive, o2, d2, a2, nx
+        return self._kat("bounce", (obj_index, o, d, t, atten, seed, warm))
 
     def kat_miss(self, d, atten, backtex, background):
-        d, atten = _f32(d), _f32(atten)
-        out = np.zeros((d.shape[0], 3), np.float32)
-        _check(lib().dr_kat_miss(self._h, d.shape[0], _p(d), _p(atten), int(backtex), float(background), _p(out)))
-        return out
+        return self._kat("miss", (d, atten), mid=(int(backtex), float(background)))[0]
 
     def kat_camera(self, settings13, W, H, frame_seed, stride, x, y, sample):
         """dr_kat_camera: (origin, dir float32[2, n, 3], next uint32[2, n, 2]) -- camera_ray, and the split"""
         st = _f32(settings13)
-        x, y, sample = (np.ascontiguousarray(a, np.int32) for a in (x, y, sample))
-        n = x.shape[0]
-        o, d, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
-        _check(lib().dr_kat_camera(self._h, _p(st), int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF, n, _p(x), _p(y), _p(sample),
-                                   _p(o), _p(d), _p(nx)))
-        return o, d, nx
+        return self._kat("camera", (x, y, sample), head=(_p(st), int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF))
 
     def kat_store(self, color, spp):
-        color = _f32(color)
-        out = np.zeros((color.shape[0], 3), np.int32)
-        _check(lib().dr_kat_store(self._h, color.shape[0], _p(color), int(spp), _p(out)))
-        return out
+        return self._kat("store", (color,), mid=(int(spp),))[0]
 
     def kat_tile_feedback(self, pixel_cost, regions, heavy_factor, split_steps, split_limit, ntiles=None):
         """The feedback kernels on a flat uint32 plane of ntiles * 64 pixel costs (dr_kat_tile_feedback): (tile_cost uint32[ntiles],
         order int32[ntiles], region_start int32[17]); entries the kernels did not write are -1."""
-        pc = np.ascontiguousarray(pixel_cost, dtype=np.uint32).ravel()
-        n = pc.size // 64 if ntiles is None else int(ntiles)
-        if n >= 1 and pc.size < n * 64:
+        words = int(np.size(pixel_cost))
+        n = words // 64 if ntiles is None else int(ntiles)
+        if n >= 1 and words < n * 64:
             raise ValueError("pixel_cost holds fewer than ntiles * 64 words")
-        tc = np.zeros(max(n, 0), dtype=np.uint32)
-        order = np.zeros(max(n, 0), dtype=np.int32)
-        rs = np.zeros(2 * MAX_REGIONS + 1, dtype=np.int32)
-        _check(lib().dr_kat_tile_feedback(self._h, n, int(regions), int(heavy_factor), int(split_steps), int(split_limit), _p(pc), _p(tc), _p(order), _p(rs)))
-        return tc, order, rs
+
+        def call(n, ins, out):
+            _check(lib().dr_kat_tile_feedback(self._h, n, int(regions), int(heavy_factor), int(split_steps), int(split_limit), *ins, *[_p(a) for a in out]))
+        return kat_marshal("tile_feedback", (pixel_cost,), call, n)
 
 
 class Group:

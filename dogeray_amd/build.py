@@ -12,7 +12,7 @@ HOST_SOURCES = ["rts_reader.cpp", "bvh_builder.cpp", "linearise.cpp", "wide_buil
 # one translation unit per family of kernels (kernels.hpp)
 DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip",
                   "kernels_upscale.hip", "kernels_trace.hip", "kernels_radiance.hip", "kernels_nearest.hip", "kernels_allhits.hip",
-                  "kernels_kat_shade.hip"]
+                  "kernels_kat.hip"]
 # -ffp-contract=off: no FMA contraction on host or device -- the BVH build and the kernel's
 # arithmetic are specified operation by operation (DESIGN.md "arithmetic contract").
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra",

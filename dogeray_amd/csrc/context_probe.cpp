@@ -1,4 +1,8 @@
 // Measurement probes (dr_context_probe_*) and the known-answer hooks of single device functions (dr_kat_*).
+#include <deque>
+#include <initializer_list>
+#include <utility>
+
 #include "context.hpp"
 
 using namespace dr;
@@ -148,279 +152,247 @@ int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int 
   return DR_OK;
 }
 
-// ---- KAT hooks
-#define KAT_PRE(n)                                                        \
-  if (!c || (n) < 0) { set_error("bad argument"); return DR_ERR_INVALID; } \
-  HIP_TRY(hipSetDevice(c->device));                                        \
-  if ((n) == 0) return DR_OK
+}  // extern "C"
 
-int dr_kat_rng(dr_context* c, uint64_t seed, int n, double* out) {
-  KAT_PRE(n);
-  DevMem<double> d; DR_TRY(d.alloc((size_t)n));
-  launch_kat_rng(c->stream, seed, n, d.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return d.get(out, (size_t)n);
-}
+// ---- known-answer hooks: n items in, one small kernel, n items out (the common contract: include/dogeray_amd.h "known-answer hooks")
+namespace {
 
-int dr_kat_aabb(dr_context* c, int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist) {
-  KAT_PRE(n);
-  DevMem<float> bo, bd, bmn, bmx, bdist; DevMem<int32_t> bhit;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bmn.alloc(m)); DR_TRY(bmx.alloc(m)); DR_TRY(bdist.alloc((size_t)n)); DR_TRY(bhit.alloc((size_t)n));
-  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bmn.put(mn, m)); DR_TRY(bmx.put(mx, m));
-  launch_kat_aabb(c->stream, n, bo.p, bd.p, bmn.p, bmx.p, bhit.p, bdist.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(bhit.get(hit, (size_t)n));
-  return bdist.get(dist, (size_t)n);
-}
+// The staging of one hook call: device copies of the caller's inputs, device buffers for its outputs, the launch and the way back.  A failed step is
+// remembered and makes every later one a no-op, the launch included.  The buffers live until the call returns.
+struct KatStage {
+  // !c or n < 0: "bad argument"; then the device; n == 0 is DR_OK before any pointer is looked at (KAT_BEGIN returns it); a null pointer among
+  // `required`: "null argument"; needs_scene without one: "no scene uploaded"
+  int begin(dr_context* ctx, long long n, std::initializer_list<const void*> required, bool needs_scene) {
+    if (!ctx || n < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return DR_OK;
+    for (const void* p : required)
+      if (!p) { set_error("null argument"); return DR_ERR_INVALID; }
+    if (needs_scene && !ctx->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
+    c = ctx;
+    return DR_OK;
+  }
+  // a device copy of host[0 .. count)
+  template <class T> T* in(const T* host, size_t count) { return static_cast<T*>(stage(host, nullptr, count * sizeof(T), -1)); }
+  // a device buffer of count elements that finish() copies to host (null: it stays on the device); preset_byte >= 0: every byte set to it on the stream
+  template <class T> T* out(T* host, size_t count, int preset_byte = -1) { return static_cast<T*>(stage(nullptr, host, count * sizeof(T), preset_byte)); }
+  // launch(args...) unless a staging step failed -- the in() and out() calls among args have run by now --, then: the launch's error, the stream
+  // drained, the outputs in the caller's arrays
+  template <class Launch, class... Args> int finish(Launch launch, Args&&... args) {
+    DR_TRY(rc);
+    launch(std::forward<Args>(args)...);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const Buf& b : bufs)
+      if (b.host) HIP_TRY(hipMemcpy(b.host, b.dev.p, b.bytes, hipMemcpyDeviceToHost));
+    return DR_OK;
+  }
 
-int dr_kat_node_planes(dr_context* c, int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt) {
-  KAT_PRE(n);
-  DevMem<uint32_t> bw;
-  DevMem<float> ba, bb, b1, b2;
-  DR_TRY(bw.alloc((size_t)n)); DR_TRY(ba.alloc((size_t)n)); DR_TRY(bb.alloc((size_t)n)); DR_TRY(b1.alloc((size_t)n * 4)); DR_TRY(b2.alloc((size_t)n * 4));
-  DR_TRY(bw.put(w, (size_t)n)); DR_TRY(ba.put(a, (size_t)n)); DR_TRY(bb.put(b, (size_t)n));
-  launch_kat_node_planes(c->stream, n, bw.p, ba.p, bb.p, b1.p, b2.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(b1.get(t_mix, (size_t)n * 4));
-  return b2.get(t_cvt, (size_t)n * 4);
-}
+ private:
+  struct Buf { DevMem<unsigned char> dev; void* host = nullptr; size_t bytes = 0; };      // (an allocation each: 256-byte aligned, whatever the element)
+  void* stage(const void* src, void* dst, size_t bytes, int preset_byte) {
+    if (rc == DR_OK) rc = stage_step(src, dst, bytes, preset_byte);
+    return rc == DR_OK ? bufs.back().dev.p : nullptr;
+  }
+  int stage_step(const void* src, void* dst, size_t bytes, int preset_byte) {
+    bufs.emplace_back();
+    Buf& b = bufs.back();
+    b.host = dst; b.bytes = bytes;
+    DR_TRY(b.dev.alloc(bytes));
+    if (src) HIP_TRY(hipMemcpy(b.dev.p, src, bytes, hipMemcpyHostToDevice));
+    if (preset_byte >= 0) HIP_TRY(hipMemsetAsync(b.dev.p, preset_byte, bytes, c->stream));
+    return DR_OK;
+  }
+  dr_context* c = nullptr;
+  std::deque<Buf> bufs;
+  int rc = DR_OK;
+};
 
-int dr_kat_tri(dr_context* c, int n, const float* o, const float* d, const float* v0, const float* v1, const float* v2, float* t) {
-  KAT_PRE(n);
-  DevMem<float> bo, bd, b0, b1, b2, bt;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(b0.alloc(m)); DR_TRY(b1.alloc(m)); DR_TRY(b2.alloc(m)); DR_TRY(bt.alloc((size_t)n));
-  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(b0.put(v0, m)); DR_TRY(b1.put(v1, m)); DR_TRY(b2.put(v2, m));
-  launch_kat_tri(c->stream, n, bo.p, bd.p, b0.p, b1.p, b2.p, bt.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bt.get(t, (size_t)n);
-}
+#define KAT_BEGIN(k, c, n, needs_scene, ...) \
+  KatStage k;                                \
+  if (const int rc_ = k.begin(c, n, {__VA_ARGS__}, needs_scene); rc_ != DR_OK || (n) == 0) return rc_
 
-int dr_kat_sphere(dr_context* c, int n, const float* o, const float* d, const float* centre, const float* radius, float* t) {
-  KAT_PRE(n);
-  DevMem<float> bo, bd, bc, br, bt;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bc.alloc(m)); DR_TRY(br.alloc((size_t)n)); DR_TRY(bt.alloc((size_t)n));
-  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bc.put(centre, m)); DR_TRY(br.put(radius, (size_t)n));
-  launch_kat_sphere(c->stream, n, bo.p, bd.p, bc.p, br.p, bt.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bt.get(t, (size_t)n);
-}
-
-int dr_kat_optics(dr_context* c, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* schlick) {
-  KAT_PRE(n);
-  DevMem<float> bv, bn, be, b1, b2, b3;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bv.alloc(m)); DR_TRY(bn.alloc(m)); DR_TRY(be.alloc((size_t)n)); DR_TRY(b1.alloc(m)); DR_TRY(b2.alloc(m)); DR_TRY(b3.alloc((size_t)n));
-  DR_TRY(bv.put(v, m)); DR_TRY(bn.put(nrm, m)); DR_TRY(be.put(eta, (size_t)n));
-  launch_kat_optics(c->stream, n, bv.p, bn.p, be.p, b1.p, b2.p, b3.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(b1.get(refl, m)); DR_TRY(b2.get(refr, m));
-  return b3.get(schlick, (size_t)n);
-}
-
-int dr_kat_normal(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, float* normal, float* texco) {
-  KAT_PRE(n);
-  if (!c->walk || !object_index || !o || !d || !t || !normal || !texco) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
-  std::vector<int32_t> slot_of((size_t)c->n_prims, -1), slots((size_t)n);
+// slots[i] = the slot of the resident scene that holds object object_index[i] of the file (the inverse of slot_to_orig)
+int kat_slots(const dr_context* c, const int32_t* object_index, int n, std::vector<int32_t>& slots) {
+  std::vector<int32_t> slot_of((size_t)c->n_prims, -1);
   for (int sidx = 0; sidx < c->n_prims; sidx++) slot_of[(size_t)c->slot_to_orig[(size_t)sidx]] = sidx;
+  slots.resize((size_t)n);
   for (int i = 0; i < n; i++) {
     if (object_index[i] < 0 || object_index[i] >= c->n_prims) { set_error("object index out of range"); return DR_ERR_INVALID; }
     slots[(size_t)i] = slot_of[(size_t)object_index[i]];
   }
-  DevMem<int32_t> bs; DevMem<float> bo, bd, bt, bn, bc;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bs.alloc((size_t)n)); DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bt.alloc((size_t)n)); DR_TRY(bn.alloc(m)); DR_TRY(bc.alloc(m));
-  DR_TRY(bs.put(slots.data(), (size_t)n)); DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m)); DR_TRY(bt.put(t, (size_t)n));
+  return DR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dr_kat_rng(dr_context* c, uint64_t seed, int n, double* out) {
+  KAT_BEGIN(k, c, n, false, out);
+  DR_TRY(join_pipeline(c));
+  return k.finish(launch_kat_rng, c->stream, seed, n, k.out(out, (size_t)n));
+}
+
+int dr_kat_aabb(dr_context* c, int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist) {
+  KAT_BEGIN(k, c, n, false, o, d, mn, mx, hit, dist);
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_aabb, c->stream, n, k.in(o, 3 * m), k.in(d, 3 * m), k.in(mn, 3 * m), k.in(mx, 3 * m), k.out(hit, m), k.out(dist, m));
+}
+
+int dr_kat_node_planes(dr_context* c, int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt) {
+  KAT_BEGIN(k, c, n, false, w, a, b, t_mix, t_cvt);
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_node_planes, c->stream, n, k.in(w, m), k.in(a, m), k.in(b, m), k.out(t_mix, 4 * m), k.out(t_cvt, 4 * m));
+}
+
+int dr_kat_tri(dr_context* c, int n, const float* o, const float* d, const float* v0, const float* v1, const float* v2, float* t) {
+  KAT_BEGIN(k, c, n, false, o, d, v0, v1, v2, t);
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_tri, c->stream, n, k.in(o, 3 * m), k.in(d, 3 * m), k.in(v0, 3 * m), k.in(v1, 3 * m), k.in(v2, 3 * m), k.out(t, m));
+}
+
+int dr_kat_sphere(dr_context* c, int n, const float* o, const float* d, const float* centre, const float* radius, float* t) {
+  KAT_BEGIN(k, c, n, false, o, d, centre, radius, t);
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_sphere, c->stream, n, k.in(o, 3 * m), k.in(d, 3 * m), k.in(centre, 3 * m), k.in(radius, m), k.out(t, m));
+}
+
+int dr_kat_optics(dr_context* c, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* schlick) {
+  KAT_BEGIN(k, c, n, false, v, nrm, eta, refl, refr, schlick);
+  DR_TRY(join_pipeline(c));
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_optics, c->stream, n, k.in(v, 3 * m), k.in(nrm, 3 * m), k.in(eta, m), k.out(refl, 3 * m), k.out(refr, 3 * m), k.out(schlick, m));
+}
+
+int dr_kat_normal(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, float* normal, float* texco) {
+  KAT_BEGIN(k, c, n, true, object_index, o, d, t, normal, texco);
+  std::vector<int32_t> slots;
+  DR_TRY(kat_slots(c, object_index, n, slots));
+  DR_TRY(join_pipeline(c));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   P.prims = c->prims; P.shade = c->shade;
-  launch_kat_normal(c->stream, P, n, bs.p, bo.p, bd.p, bt.p, bn.p, bc.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(bn.get(normal, m));
-  return bc.get(texco, m);
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_normal, c->stream, P, n, k.in(slots.data(), m), k.in(o, 3 * m), k.in(d, 3 * m), k.in(t, m), k.out(normal, 3 * m), k.out(texco, 3 * m));
 }
 
-// ---- the shading step (kernels_kat_shade.hip; device_kat_shade.hpp says what each element writes)
+// ---- the shading step (device_kat_shade.hpp says what each element writes)
 int dr_kat_sample(dr_context* c, int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point_plain, uint32_t* next_plain,
                   float* point_merged, uint32_t* next_merged) {
-  KAT_PRE(n);
-  if (!seed || !warm || !kind || !point_plain || !next_plain || !point_merged || !next_merged) { set_error("null argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, false, seed, warm, kind, point_plain, next_plain, point_merged, next_merged);
   for (int i = 0; i < n; i++)
     if (warm[i] < 0 || warm[i] > 4096 || (kind[i] != 0 && kind[i] != 2 && kind[i] != 3)) { set_error("warm must be 0 .. 4096, kind 0, 2 or 3"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));
   const size_t m = (size_t)n;
-  DevMem<uint64_t> bs; DevMem<int32_t> bw, bk; DevMem<float> p1, p2; DevMem<uint32_t> n1, n2;
-  DR_TRY(bs.alloc(m)); DR_TRY(bw.alloc(m)); DR_TRY(bk.alloc(m)); DR_TRY(p1.alloc(3 * m)); DR_TRY(p2.alloc(3 * m)); DR_TRY(n1.alloc(2 * m)); DR_TRY(n2.alloc(2 * m));
-  DR_TRY(bs.put(seed, m)); DR_TRY(bw.put(warm, m)); DR_TRY(bk.put(kind, m));
-  launch_kat_sample(c->stream, n, bs.p, bw.p, bk.p, p1.p, n1.p, p2.p, n2.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(p1.get(point_plain, 3 * m)); DR_TRY(n1.get(next_plain, 2 * m)); DR_TRY(p2.get(point_merged, 3 * m));
-  return n2.get(next_merged, 2 * m);
+  return k.finish(launch_kat_sample, c->stream, n, k.in(seed, m), k.in(warm, m), k.in(kind, m), k.out(point_plain, 3 * m), k.out(next_plain, 2 * m),
+                  k.out(point_merged, 3 * m), k.out(next_merged, 2 * m));
 }
 
 int dr_kat_outside(dr_context* c, int n, const float* d2, int32_t* out) {
-  KAT_PRE(n);
-  if (!d2 || !out) { set_error("null argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, false, d2, out);
   DR_TRY(join_pipeline(c));
-  DevMem<float> bd; DevMem<int32_t> bo;
-  DR_TRY(bd.alloc((size_t)n)); DR_TRY(bo.alloc((size_t)n));
-  DR_TRY(bd.put(d2, (size_t)n));
-  launch_kat_outside(c->stream, n, bd.p, bo.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bo.get(out, (size_t)n);
+  return k.finish(launch_kat_outside, c->stream, n, k.in(d2, (size_t)n), k.out(out, (size_t)n));
 }
 
 int dr_kat_tex(dr_context* c, int n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba) {
-  KAT_PRE(n);
-  if (!c->walk || !tex || !u || !v || !rgba) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, true, tex, u, v, rgba);
   for (int i = 0; i < n; i++)
     if (tex[i] < 0 || tex[i] >= c->n_tex) { set_error("texture index out of range"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));
-  DevMem<int32_t> bt; DevMem<float> bu, bv; DevMem<uint32_t> bo;
-  DR_TRY(bt.alloc((size_t)n)); DR_TRY(bu.alloc((size_t)n)); DR_TRY(bv.alloc((size_t)n)); DR_TRY(bo.alloc((size_t)n));
-  DR_TRY(bt.put(tex, (size_t)n)); DR_TRY(bu.put(u, (size_t)n)); DR_TRY(bv.put(v, (size_t)n));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   P.tex = c->tex; P.texels = c->texels;
-  launch_kat_tex(c->stream, P, n, bt.p, bu.p, bv.p, bo.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bo.get(rgba, (size_t)n);
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_tex, c->stream, P, n, k.in(tex, m), k.in(u, m), k.in(v, m), k.out(rgba, m));
 }
 
 int dr_kat_bounce(dr_context* c, int n, const int32_t* object_index, const float* o, const float* d, const float* t, const float* atten,
                   const uint64_t* seed, const int32_t* warm, int32_t* alive, float* o_out, float* d_out, float* atten_out, uint32_t* next) {
-  KAT_PRE(n);
-  if (!c->walk || !object_index || !o || !d || !t || !atten || !seed || !warm || !alive || !o_out || !d_out || !atten_out || !next) {
-    set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID;
-  }
-  std::vector<int32_t> slot_of((size_t)c->n_prims, -1), slots((size_t)n);
-  for (int sidx = 0; sidx < c->n_prims; sidx++) slot_of[(size_t)c->slot_to_orig[(size_t)sidx]] = sidx;
-  for (int i = 0; i < n; i++) {
-    if (object_index[i] < 0 || object_index[i] >= c->n_prims) { set_error("object index out of range"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, true, object_index, o, d, t, atten, seed, warm, alive, o_out, d_out, atten_out, next);
+  std::vector<int32_t> slots;
+  DR_TRY(kat_slots(c, object_index, n, slots));
+  for (int i = 0; i < n; i++)
     if (warm[i] < 0 || warm[i] > 4096) { set_error("warm must be 0 .. 4096"); return DR_ERR_INVALID; }
-    slots[(size_t)i] = slot_of[(size_t)object_index[i]];
-  }
   DR_TRY(join_pipeline(c));
-  const size_t m = (size_t)n;
-  DevMem<int32_t> bs, bw, ba; DevMem<float> bo, bd, bt, bat, o2, d2, a2; DevMem<uint64_t> bseed; DevMem<uint32_t> nx;
-  DR_TRY(bs.alloc(m)); DR_TRY(bw.alloc(m)); DR_TRY(bo.alloc(3 * m)); DR_TRY(bd.alloc(3 * m)); DR_TRY(bt.alloc(m)); DR_TRY(bat.alloc(3 * m)); DR_TRY(bseed.alloc(m));
-  DR_TRY(ba.alloc(2 * m)); DR_TRY(o2.alloc(6 * m)); DR_TRY(d2.alloc(6 * m)); DR_TRY(a2.alloc(6 * m)); DR_TRY(nx.alloc(4 * m));
-  DR_TRY(bs.put(slots.data(), m)); DR_TRY(bw.put(warm, m)); DR_TRY(bo.put(o, 3 * m)); DR_TRY(bd.put(d, 3 * m)); DR_TRY(bt.put(t, m)); DR_TRY(bat.put(atten, 3 * m));
-  DR_TRY(bseed.put(seed, m));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   P.prims = c->prims; P.shade = c->shade; P.tex = c->tex; P.texels = c->texels;
-  launch_kat_bounce(c->stream, P, n, bs.p, bo.p, bd.p, bt.p, bat.p, bseed.p, bw.p, ba.p, o2.p, d2.p, a2.p, nx.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(ba.get(alive, 2 * m)); DR_TRY(o2.get(o_out, 6 * m)); DR_TRY(d2.get(d_out, 6 * m)); DR_TRY(a2.get(atten_out, 6 * m));
-  return nx.get(next, 4 * m);
+  const size_t m = (size_t)n;
+  return k.finish(launch_kat_bounce, c->stream, P, n, k.in(slots.data(), m), k.in(o, 3 * m), k.in(d, 3 * m), k.in(t, m), k.in(atten, 3 * m), k.in(seed, m),
+                  k.in(warm, m), k.out(alive, 2 * m), k.out(o_out, 6 * m), k.out(d_out, 6 * m), k.out(atten_out, 6 * m), k.out(next, 4 * m));
 }
 
 int dr_kat_miss(dr_context* c, int n, const float* d, const float* atten, int backtex, float background, float* rgb) {
-  KAT_PRE(n);
-  if (!c->walk || !d || !atten || !rgb) { set_error("no scene uploaded, or null argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, true, d, atten, rgb);
   if (backtex >= c->n_tex) { set_error("backtex refers to a texture that is not loaded"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));
-  const size_t m = (size_t)n * 3;
-  DevMem<float> bd, ba, bo;
-  DR_TRY(bd.alloc(m)); DR_TRY(ba.alloc(m)); DR_TRY(bo.alloc(m));
-  DR_TRY(bd.put(d, m)); DR_TRY(ba.put(atten, m));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   P.tex = c->tex; P.texels = c->texels; P.backtex = backtex; P.bgint = background;
-  launch_kat_miss(c->stream, P, n, bd.p, ba.p, bo.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bo.get(rgb, m);
+  const size_t m = (size_t)n * 3;
+  return k.finish(launch_kat_miss, c->stream, P, n, k.in(d, m), k.in(atten, m), k.out(rgb, m));
 }
 
 int dr_kat_camera(dr_context* c, const float settings13[13], int W, int H, uint64_t frame_seed, uint32_t seed_stride, int n, const int32_t* x,
                   const int32_t* y, const int32_t* sample, float* origin, float* dir, uint32_t* next) {
-  KAT_PRE(n);
-  if (!settings13 || !x || !y || !sample || !origin || !dir || !next) { set_error("null argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, false, settings13, x, y, sample, origin, dir, next);
   DR_TRY(join_pipeline(c));
   RenderParams P;
   DR_TRY(make_params(c, c->own_site(), settings13, W, H, 0.0f, frame_seed, P, 1));      // the view as a render launch fills it
   P.seed_stride = seed_stride;                                                          // (a launch's is 8 * its block columns)
   const size_t m = (size_t)n;
-  DevMem<int32_t> bx, by, bs; DevMem<float> bo, bd; DevMem<uint32_t> nx;
-  DR_TRY(bx.alloc(m)); DR_TRY(by.alloc(m)); DR_TRY(bs.alloc(m)); DR_TRY(bo.alloc(6 * m)); DR_TRY(bd.alloc(6 * m)); DR_TRY(nx.alloc(4 * m));
-  DR_TRY(bx.put(x, m)); DR_TRY(by.put(y, m)); DR_TRY(bs.put(sample, m));
-  launch_kat_camera(c->stream, P, n, bx.p, by.p, bs.p, bo.p, bd.p, nx.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(bo.get(origin, 6 * m)); DR_TRY(bd.get(dir, 6 * m));
-  return nx.get(next, 4 * m);
+  return k.finish(launch_kat_camera, c->stream, P, n, k.in(x, m), k.in(y, m), k.in(sample, m), k.out(origin, 6 * m), k.out(dir, 6 * m), k.out(next, 4 * m));
 }
 
 int dr_kat_store(dr_context* c, int n, const float* color, int spp, int32_t* out) {
-  KAT_PRE(n);
-  if (!color || !out || spp < 1) { set_error("null argument, or spp < 1"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, false, color, out);
+  if (spp < 1) { set_error("null argument, or spp < 1"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));
   const float st[13] = {0, 0, 2, 0, 0, 0, 0, 1, 45, 1, (float)spp, 1, -1};      // any view: the store reads its sample scale alone
   RenderParams P;
   memset(&P, 0, sizeof(P));
   if (const char* why = fill_view_params(st, 8, 8, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
   const size_t m = (size_t)n * 3;
-  DevMem<float> bc; DevMem<int32_t> bo;
-  DR_TRY(bc.alloc(m)); DR_TRY(bo.alloc(m));
-  DR_TRY(bc.put(color, m));
-  P.W = n; P.H = 1; P.out = bo.p; P.accumulate = 0;                            // colour i is pixel (i, 0) of an n x 1 frame
-  launch_kat_store(c->stream, P, n, bc.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return bo.get(out, m);
+  P.W = n; P.H = 1; P.out = k.out(out, m); P.accumulate = 0;                   // colour i is pixel (i, 0) of an n x 1 frame
+  return k.finish(launch_kat_store, c->stream, P, n, k.in(color, m));
 }
 
 int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits) {
-  KAT_PRE(n);
-  if (!c->walk) { set_error("no scene uploaded"); return DR_ERR_INVALID; }
-  DevMem<float> bo, bd, bt; DevMem<int32_t> bs, bv;
-  size_t m = (size_t)n * 3;
-  DR_TRY(bo.alloc(m)); DR_TRY(bd.alloc(m)); DR_TRY(bt.alloc((size_t)n)); DR_TRY(bs.alloc((size_t)n)); DR_TRY(bv.alloc((size_t)n));
-  DR_TRY(bo.put(o, m)); DR_TRY(bd.put(d, m));
+  KAT_BEGIN(k, c, n, true, o, d, t, idx);
+  DR_TRY(join_pipeline(c));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   fill_scene(c, P);
-  launch_kat_hit(c->stream, P, traversal_of(c), n, bo.p, bd.p, bt.p, bs.p, bv.p);
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(bt.get(t, (size_t)n));
-  if (visits) DR_TRY(bv.get(visits, (size_t)n));
-  std::vector<int32_t> slots((size_t)n);
-  DR_TRY(bs.get(slots.data(), (size_t)n));
+  const size_t m = (size_t)n;
+  std::vector<int32_t> slots(m);
+  DR_TRY(k.finish(launch_kat_hit, c->stream, P, traversal_of(c), n, k.in(o, 3 * m), k.in(d, 3 * m), k.out(t, m), k.out(slots.data(), m),
+                  k.out(visits, m)));      // (the kernel counts whether or not the caller asks: visits may be null)
   for (int i = 0; i < n; i++) idx[i] = slots[(size_t)i] >= 0 ? c->slot_to_orig[(size_t)slots[(size_t)i]] : 0;   // hit() returns index 0 on a miss (K:507)
   return DR_OK;
 }
 
 int dr_kat_trace(dr_context* c, int variant, int n, const float* o, const float* d, float* t, int32_t* idx) {
-  KAT_PRE(n);
-  if (variant < 0 || variant > 7 || !o || !d || !t || !idx) { set_error("bad argument"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, n, false, o, d, t, idx);
+  if (variant < 0 || variant > 7) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wide) { set_error("the trace hook needs a resident wide tree (no scene uploaded, or the scene has none)"); return DR_ERR_INVALID; }
+  DR_TRY(join_pipeline(c));
   // the 8-float layout launch_trace_probe reads: origin, pad, direction, pad
   std::vector<float> packed((size_t)n * 8, 0.0f);
   for (int i = 0; i < n; i++) {
     memcpy(&packed[(size_t)i * 8], o + 3 * (size_t)i, 12);
     memcpy(&packed[(size_t)i * 8 + 4], d + 3 * (size_t)i, 12);
   }
-  DevMem<float> rays; DevMem<unsigned> cursor, out;
-  DR_TRY(rays.alloc((size_t)n * 8)); DR_TRY(cursor.alloc(1)); DR_TRY(out.alloc((size_t)n * 2));
-  DR_TRY(rays.put(packed.data(), packed.size()));
   RenderParams P;
   memset(&P, 0, sizeof(P));
   fill_scene(c, P);
-  HIP_TRY(hipMemsetAsync(cursor.p, 0, sizeof(unsigned), c->stream));
-  HIP_TRY(hipMemsetAsync(out.p, 0xff, (size_t)n * 2 * sizeof(unsigned), c->stream));      // a ray the kernel did not answer reads as {NaN, -1}, which no walk returns: refused below
-  launch_trace_probe(c->stream, P, c->num_cus, variant, rays.p, (unsigned)n, cursor.p, out.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  std::vector<unsigned> res((size_t)n * 2);
-  DR_TRY(out.get(res.data(), res.size()));
+  std::vector<unsigned> res((size_t)n * 2);      // preset: a ray the kernel did not answer reads as {NaN, -1}, which no walk returns: refused below
+  DR_TRY(k.finish(launch_trace_probe, c->stream, P, c->num_cus, variant, k.in(packed.data(), packed.size()), (unsigned)n, k.out<unsigned>(nullptr, 1, 0),
+                  k.out(res.data(), res.size(), 0xff)));
   for (int i = 0; i < n; i++) {
     const int32_t slot = (int32_t)res[(size_t)i * 2 + 1];
     if (slot >= c->n_prims) { set_error("the trace kernel returned a slot outside the scene"); return DR_ERR_INVALID; }
@@ -436,24 +408,16 @@ int dr_kat_trace(dr_context* c, int variant, int n, const float* o, const float*
 
 int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_factor, int split_steps, int split_limit, const unsigned* pixel_cost,
                          unsigned* tile_cost, int* order, int* region_start) {
-  if (!c || !pixel_cost || !tile_cost || !order || !region_start) { set_error("null argument"); return DR_ERR_INVALID; }
   // what make_params never launches: the order kernel relies on a 64-tile group touching at most two regions
   if (ntiles < 1) { set_error("tile feedback: ntiles must be at least 1"); return DR_ERR_INVALID; }
   if (regions != 1 && regions != MAX_REGIONS) { set_error("tile feedback: regions must be 1 or 8"); return DR_ERR_INVALID; }
   if (regions == MAX_REGIONS && ntiles < 64 * MAX_REGIONS) { set_error("tile feedback: 8 regions need at least 512 tiles (regions of 64 tiles or more)"); return DR_ERR_INVALID; }
   if (split_limit < 0) { set_error("tile feedback: split_limit must not be negative"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)ntiles, words = 2 * MAX_REGIONS + 1;
-  DevMem<unsigned> bp, bc; DevMem<int> bo, br;
-  DR_TRY(bp.alloc(n * 64)); DR_TRY(bc.alloc(n)); DR_TRY(bo.alloc(n)); DR_TRY(br.alloc(words));
-  DR_TRY(bp.put(pixel_cost, n * 64));
-  HIP_TRY(hipMemsetAsync(bo.p, 0xff, n * sizeof(int), c->stream));             // an entry the kernel does not write reads as -1
-  HIP_TRY(hipMemsetAsync(br.p, 0xff, words * sizeof(int), c->stream));
-  launch_tile_feedback(c->stream, bp.p, bc.p, bo.p, br.p, ntiles, regions, heavy_factor, split_steps, split_limit);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  DR_TRY(bc.get(tile_cost, n)); DR_TRY(bo.get(order, n));
-  return br.get(region_start, words);
+  KAT_BEGIN(k, c, ntiles, false, pixel_cost, tile_cost, order, region_start);
+  DR_TRY(join_pipeline(c));
+  const size_t n = (size_t)ntiles;      // order and region_start preset: an entry the kernels do not write reads as -1
+  return k.finish(launch_tile_feedback, c->stream, k.in(pixel_cost, n * 64), k.out(tile_cost, n), k.out(order, n, 0xff),
+                  k.out(region_start, (size_t)(2 * MAX_REGIONS + 1), 0xff), ntiles, regions, heavy_factor, split_steps, split_limit);
 }
 
 }  // extern "C"

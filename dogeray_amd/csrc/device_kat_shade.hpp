@@ -1,6 +1,6 @@
 // The known-answer hooks of the shading step (dr_kat_sample, dr_kat_outside, dr_kat_tex, dr_kat_bounce, dr_kat_miss, dr_kat_camera, dr_kat_store), one
 // element per lane: each body calls the product's functions of device_rng.hpp, device_surface.hpp and device_shade.hpp unchanged and writes what they
-// return.  kernels_kat_shade.hip runs them on the device, tools/host_kernel.cpp (hk_kat_*) in a loop on the host.  No render kernel includes this file.
+// return.  kernels_kat.hip runs them on the device, tools/host_kernel.cpp (hk_kat_*) in a loop on the host.  No render kernel includes this file.
 #pragma once
 #include "device_shade.hpp"
 

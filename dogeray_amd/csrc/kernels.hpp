@@ -1,7 +1,7 @@
 // Launchers of the device code, one translation unit per family of kernels:
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
-//   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, known-answer kernels
-//   kernels_kat_shade.hip     known-answer kernels of the shading step: samplers, texel fetch, one bounce, background, camera ray, store
+//   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, trace-only probe
+//   kernels_kat.hip           known-answer kernels behind dr_kat_*: generator, intersections, optics, normal, closest hit; the shading step
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
 //   kernels_radiance.hip      path-traced radiance along caller rays (dr_trace_radiance)
@@ -77,6 +77,8 @@ void launch_gather_probe(hipStream_t stream, const RenderParams& P, int blocks, 
 // trace-only probe (dr_context_probe_trace): variant 0 = one ray per lane, waves wait for their slowest; 1.. = persistent waves refilling from the ray list
 // (occupancy / lanes that must be free before a refill / lanes at a leaf before a leaf step: 6/1/20, 6/8/20, 6/16/20, 8/8/20, 8/8/28, 6/8/28, 8/4/32)
 void launch_trace_probe(hipStream_t stream, const RenderParams& P, int num_cus, int variant, const float* rays, unsigned n, unsigned* cursor, unsigned* out);
+
+// kernels_kat.hip: one element per lane
 void launch_kat_rng(hipStream_t stream, uint64_t seed, int n, double* out);
 void launch_kat_aabb(hipStream_t stream, int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist);
 void launch_kat_node_planes(hipStream_t stream, int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt);
@@ -85,8 +87,7 @@ void launch_kat_sphere(hipStream_t stream, int n, const float* o, const float* d
 void launch_kat_optics(hipStream_t stream, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* sch);
 void launch_kat_normal(hipStream_t stream, const RenderParams& P, int n, const int32_t* slot, const float* o, const float* d, const float* t, float* nrm, float* texco);
 void launch_kat_hit(hipStream_t stream, const RenderParams& P, int traversal, int n, const float* o, const float* d, float* t, int32_t* slot, int32_t* visits);
-
-// kernels_kat_shade.hip: the shading step's known-answer kernels (device_kat_shade.hpp says what each writes; "2": both forms, form f of element i at f * n + i)
+// the shading step's (device_kat_shade.hpp says what each writes; "2": both forms, form f of element i at f * n + i)
 void launch_kat_sample(hipStream_t stream, int n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* p_plain, uint32_t* n_plain,
                        float* p_merged, uint32_t* n_merged);
 void launch_kat_outside(hipStream_t stream, int n, const float* d2, int32_t* out);

@@ -1,5 +1,5 @@
 // Everything on the device that is not a render kernel: tile-order feedback of the persistent kernels, the display divide,
-// the stripe copies of the multi-GPU gather, the gather-ceiling probe and the known-answer kernels behind dr_kat_*.
+// the stripe copies of the multi-GPU gather, the gather-ceiling probe and the trace-only probe.
 #include <hip/hip_runtime.h>
 
 #include "device_rng.hpp"
@@ -336,85 +336,6 @@ __global__ __launch_bounds__(256) void trace_plain_kernel(RenderParams P, const 
   out[i] = h.slot < 0 ? make_uint2(__float_as_uint(10000.0f), 0xffffffffu) : make_uint2(__float_as_uint(h.t), (unsigned)h.slot);
 }
 
-// ---- known-answer kernels
-__global__ void kat_rng_kernel(uint64_t seed, int n, double* out) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    Xorwow r; r.init(seed);
-    for (int i = 0; i < n; i++) out[i] = r.uniform_double();
-  }
-}
-__global__ void kat_aabb_kernel(int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  V3 dd = ld3(d + 3 * i);
-  V3 inv = mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z);
-  float t;
-  bool h = slab(ld3(o + 3 * i), inv, mn + 3 * i, mx + 3 * i, t);
-  hit[i] = h; dist[i] = h ? t : 0;
-}
-__global__ void kat_node_planes_kernel(int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const PlanePairs p = plane_pairs(w[i]);
-  const float a24 = a[i] * 0x1p24f;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    t_mix[4 * i + k] = plane_t(p, k, a24, b[i]);                                                         // the kernel's instruction (v_fma_mix_f32 on the f16 denormal)
-    t_cvt[4 * i + k] = __builtin_fmaf((float)((w[i] >> (8 * k)) & 255u), a[i], b[i]);                    // conversion + fma
-  }
-}
-__global__ void kat_tri_kernel(int n, const float* o, const float* d, const float* v0, const float* v1, const float* v2, float* t) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  V3 a = ld3(v0 + 3 * i);
-  t[i] = tri_hit(ld3(o + 3 * i), ld3(d + 3 * i), a, ld3(v1 + 3 * i) - a, ld3(v2 + 3 * i) - a);
-}
-__global__ void kat_sphere_kernel(int n, const float* o, const float* d, const float* c, const float* r, float* t) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  t[i] = sphere_hit(ld3(c + 3 * i), r[i], ld3(o + 3 * i), ld3(d + 3 * i));
-}
-__global__ void kat_optics_kernel(int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* sch) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  V3 a = ld3(v + 3 * i), b = ld3(nrm + 3 * i);
-  V3 r1 = reflect(a, b), r2 = refract(a, b, eta[i]);
-  refl[3 * i] = r1.x; refl[3 * i + 1] = r1.y; refl[3 * i + 2] = r1.z;
-  refr[3 * i] = r2.x; refr[3 * i + 1] = r2.y; refr[3 * i + 2] = r2.z;
-  sch[i] = reflectance(a.x, eta[i]);
-}
-__global__ void kat_normal_kernel(RenderParams P, int n, const int32_t* slot, const float* o, const float* d, const float* t, float* nrm, float* texco) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4* pp = reinterpret_cast<const float4*>(P.prims + slot[i]);
-  const float4* sp = reinterpret_cast<const float4*>(P.shade + slot[i]);
-  const V3 ro = ld3(o + 3 * i), rd = ld3(d + 3 * i);
-  const V3 hitpoint = ro + splat(t[i]) * rd;                           // K:806
-  V3 tc;
-  const V3 N = surface_normal(pp[0], pp[1], pp[2], sp[0], sp[1], sp[2], sp[3], sp[4], sp[6], ro, rd, hitpoint, tc);
-  nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
-  texco[3 * i] = tc.x; texco[3 * i + 1] = tc.y; texco[3 * i + 2] = tc.z;
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void kat_hit_kernel(RenderParams P, int n, const float* o, const float* d, float* t, int32_t* slot, int32_t* visits) {
-  __shared__ int lds_stack[MODE == DR_TRAVERSAL_ORDERED ? ORDERED_STACK * 256 : (MODE == DR_TRAVERSAL_WIDE ? WIDE_STACK * 256 : 1)];
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Ctr c = {0, 0, 0, 0, 0, 0, 0, 0};
-  Hit h;
-  if (MODE == DR_TRAVERSAL_ORDERED) {
-    int* stack = lds_stack + (threadIdx.x >> 6) * (ORDERED_STACK * 64) + (threadIdx.x & 63);
-    h = closest_hit_ordered<true>(P.pairs, P.prims, ld3(o + 3 * i), ld3(d + 3 * i), c, stack);
-  } else if (MODE == DR_TRAVERSAL_WIDE) {
-    int* stack = lds_stack + (threadIdx.x >> 6) * (WIDE_STACK * 64) + (threadIdx.x & 63);
-    h = closest_hit_wide<true>(wide_rsrc(P), P.wide_pmax, P.wide_mu.e, P.wide_mu.l, P.wide_mu.v, ld3(o + 3 * i), ld3(d + 3 * i), c, stack);
-  } else {
-    h = closest_hit_threaded<true>(walk_rsrc(P), ld3(o + 3 * i), ld3(d + 3 * i), c);
-  }
-  t[i] = h.t; slot[i] = h.slot;
-  if (visits) visits[i] = (int32_t)c.V;
-}
-
 // acc += frame, 16 bytes per lane (pipelined single frames: every frame renders into a buffer of its own and is folded into
 // the accumulator in frame order, K:2213-2218)
 __global__ __launch_bounds__(256) void frame_add_kernel(int4* __restrict__ acc, const int4* __restrict__ frame, size_t n4, size_t n) {
@@ -579,31 +500,6 @@ void launch_trace_probe(hipStream_t stream, const RenderParams& P, int num_cus, 
     case 6: hipLaunchKernelGGL((trace_probe_kernel<6, 8, 28>), dim3((unsigned)(num_cus * 6)), dim3(256), 0, stream, P, r4, n, cursor, o2); break;
     default: hipLaunchKernelGGL((trace_probe_kernel<8, 4, 32>), dim3((unsigned)(num_cus * 8)), dim3(256), 0, stream, P, r4, n, cursor, o2); break;
   }
-}
-void launch_kat_rng(hipStream_t stream, uint64_t seed, int n, double* out) { hipLaunchKernelGGL(kat_rng_kernel, dim3(1), dim3(64), 0, stream, seed, n, out); }
-void launch_kat_aabb(hipStream_t stream, int n, const float* o, const float* d, const float* mn, const float* mx, int32_t* hit, float* dist) {
-  hipLaunchKernelGGL(kat_aabb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, o, d, mn, mx, hit, dist);
-}
-void launch_kat_node_planes(hipStream_t stream, int n, const uint32_t* w, const float* a, const float* b, float* t_mix, float* t_cvt) {
-  hipLaunchKernelGGL(kat_node_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, w, a, b, t_mix, t_cvt);
-}
-void launch_kat_tri(hipStream_t stream, int n, const float* o, const float* d, const float* v0, const float* v1, const float* v2, float* t) {
-  hipLaunchKernelGGL(kat_tri_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, o, d, v0, v1, v2, t);
-}
-void launch_kat_sphere(hipStream_t stream, int n, const float* o, const float* d, const float* c, const float* r, float* t) {
-  hipLaunchKernelGGL(kat_sphere_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, o, d, c, r, t);
-}
-void launch_kat_optics(hipStream_t stream, int n, const float* v, const float* nrm, const float* eta, float* refl, float* refr, float* sch) {
-  hipLaunchKernelGGL(kat_optics_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, v, nrm, eta, refl, refr, sch);
-}
-void launch_kat_normal(hipStream_t stream, const RenderParams& P, int n, const int32_t* slot, const float* o, const float* d, const float* t, float* nrm, float* texco) {
-  hipLaunchKernelGGL(kat_normal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, P, n, slot, o, d, t, nrm, texco);
-}
-void launch_kat_hit(hipStream_t stream, const RenderParams& P, int traversal, int n, const float* o, const float* d, float* t, int32_t* slot, int32_t* visits) {
-  dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (traversal == DR_TRAVERSAL_WIDE) hipLaunchKernelGGL((kat_hit_kernel<DR_TRAVERSAL_WIDE>), grid, block, 0, stream, P, n, o, d, t, slot, visits);
-  else if (traversal == DR_TRAVERSAL_ORDERED) hipLaunchKernelGGL((kat_hit_kernel<DR_TRAVERSAL_ORDERED>), grid, block, 0, stream, P, n, o, d, t, slot, visits);
-  else hipLaunchKernelGGL((kat_hit_kernel<DR_TRAVERSAL_THREADED>), grid, block, 0, stream, P, n, o, d, t, slot, visits);
 }
 
 }  // namespace dr

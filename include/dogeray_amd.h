@@ -844,7 +844,13 @@ int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int 
                           uint64_t capacity, uint64_t* n_rays);
 
 /* ------------------------------------------------------------------ known-answer hooks -- */
-/* Run single device functions on caller data (host pointers), for parity tests. */
+/* Run single device functions on caller data (host pointers), for parity tests.  The contract of every hook: n items in, n items out, one item per
+ * GPU lane; arrays hold n (or the stated multiple of n) elements.  A null context or n < 0 is DR_ERR_INVALID; n == 0 is DR_OK and touches no
+ * pointer; otherwise a null pointer is DR_ERR_INVALID ("null argument") -- only dr_kat_hit's visits may be null -- and a hook that reads the resident
+ * scene without one is DR_ERR_INVALID ("no scene uploaded").  Values are judged next (each hook says which), and nothing reaches the device before
+ * every check has passed.  The call is ordered behind the frames submitted before it (dr_pipeline_submit), runs on the context's stream and returns
+ * after the results are in the caller's arrays; a launch error is DR_ERR_DEVICE.  (dr_kat_tile_feedback counts tiles: its refusals come first, and
+ * it has no empty call.) */
 int dr_kat_rng(dr_context* c, uint64_t seed, int n, double* out);
 int dr_kat_aabb(dr_context* c, int n, const float* o, const float* d, const float* mn, const float* mx,
                 int32_t* hit, float* dist);

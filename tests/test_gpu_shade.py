@@ -1,4 +1,4 @@
-"""The shading step on the GPU, function by function: Context.kat_* (kernels_kat_shade.hip: the per-element bodies of device_kat_shade.hpp over
+"""The shading step on the GPU, function by function: Context.kat_* (kernels_kat.hip: the per-element bodies of device_kat_shade.hpp over
 device_rng.hpp, device_surface.hpp and device_shade.hpp, one element per lane) against the oracle's functions of the same steps on every case of
 tests/shade_cases.py, bit for bit -- the cases tests/test_shade_host.py runs through the host build.  Where a hook has two forms (the plain functions
 and what the persistent kernel runs: rand_points_merged, shade_prepare / shade_scatter, camera_prepare / camera_finish) both must equal the oracle.

@@ -16,16 +16,6 @@ EXEMPT = {
     "dr_context_destroy": "the destructor drains every stream; frames still held are dropped with the context",
     "dr_context_stream": "hands out the stream handle, touches no device state",
     "dr_context_get_option": "reads host members; takes a const context",
-    "dr_kat_rng": "known-answer hook of one device function: own buffers only",
-    "dr_kat_aabb": "known-answer hook of one device function: own buffers only",
-    "dr_kat_node_planes": "known-answer hook of one device function: own buffers only",
-    "dr_kat_tri": "known-answer hook of one device function: own buffers only",
-    "dr_kat_sphere": "known-answer hook of one device function: own buffers only",
-    "dr_kat_optics": "known-answer hook of one device function: own buffers only",
-    "dr_kat_tile_feedback": "known-answer hook of the feedback kernels: own buffers only",
-    "dr_kat_normal": "reads only the resident scene (an upload launches held frames first)",
-    "dr_kat_hit": "reads only the resident scene (an upload launches held frames first)",
-    "dr_kat_trace": "reads only the resident scene (an upload launches held frames first)",
 }
 
 DEFINITION = re.compile(r"^(?:static\s+|inline\s+)*[A-Za-z_][\w:<>\s\*&]*?\b([A-Za-z_]\w*)\((.*)$")

@@ -3,11 +3,15 @@
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+from dogeray_amd import kat_marshal      # noqa: E402  (the known-answer hooks' table and marshaller; loads no library)
 _SO = os.path.join(_HERE, "libhostkernel.so")
 _CSRC = os.path.join(_ROOT, "dogeray_amd", "csrc")
 _SOURCES = [os.path.join(_HERE, "host_kernel.cpp")] + [os.path.join(_CSRC, f) for f in ("rts_reader.cpp", "bvh_builder.cpp", "linearise.cpp", "wide_builder.cpp", "capi_host.cpp")]
@@ -145,39 +149,31 @@ def _ok(rc):
         raise RuntimeError(lib().hk_last_error().decode())
 
 
-# dr_kat_sample, dr_kat_outside, dr_kat_camera, dr_kat_store on the host (hk_kat_*): the same arguments and results as dogeray_amd.Context.kat_* --
-# where a hook returns both forms the arrays have a leading axis of 2, [0] the plain functions, [1] what the persistent kernel runs.  The hooks that
-# read a scene (kat_tex, kat_bounce, kat_miss) are methods of Scene.
+# dr_kat_sample, dr_kat_outside, dr_kat_camera, dr_kat_store on the host (hk_kat_*): the arguments, checks and results of dogeray_amd.Context.kat_*, by
+# the same table and marshaller (dogeray_amd.KAT_HOOKS, kat_marshal) -- where a hook returns both forms the arrays have a leading axis of 2, [0] the
+# plain functions, [1] what the persistent kernel runs.  The hooks that read a scene (kat_tex, kat_bounce, kat_miss) are methods of Scene.
+def _kat(hook, arrays, head=(), mid=(), outs=lambda out: [a.ctypes.data for a in out]):
+    """kat_marshal calling hk_kat_<hook>(*head, n, inputs, *mid, outs(output arrays))"""
+    def call(n, ins, out):
+        _ok(getattr(lib(), "hk_kat_" + hook)(*head, n, *ins, *mid, *outs(out)))
+    return kat_marshal(hook, arrays, call)
+
+
 def kat_sample(seed, warm, kind):
-    seed, warm, kind = np.ascontiguousarray(seed, np.uint64), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(kind, np.int32)
-    n = seed.shape[0]
-    pt, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
-    _ok(lib().hk_kat_sample(n, seed.ctypes.data, warm.ctypes.data, kind.ctypes.data, pt[0].ctypes.data, nx[0].ctypes.data, pt[1].ctypes.data, nx[1].ctypes.data))
-    return pt, nx
+    return _kat("sample", (seed, warm, kind), outs=lambda out: [out[0][0].ctypes.data, out[1][0].ctypes.data, out[0][1].ctypes.data, out[1][1].ctypes.data])
 
 
 def kat_outside(d2):
-    d2 = np.ascontiguousarray(d2, np.float32)
-    out = np.zeros(d2.shape[0], np.int32)
-    _ok(lib().hk_kat_outside(d2.shape[0], d2.ctypes.data, out.ctypes.data))
-    return out
+    return _kat("outside", (d2,))[0]
 
 
 def kat_camera(settings13, W, H, frame_seed, stride, x, y, sample):
-    st = np.ascontiguousarray(settings13, np.float32)
-    x, y, sample = (np.ascontiguousarray(a, np.int32) for a in (x, y, sample))
-    n = x.shape[0]
-    o, d, nx = np.zeros((2, n, 3), np.float32), np.zeros((2, n, 3), np.float32), np.zeros((2, n, 2), np.uint32)
-    _ok(lib().hk_kat_camera(st.ctypes.data, int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF, n, x.ctypes.data, y.ctypes.data,
-                            sample.ctypes.data, o.ctypes.data, d.ctypes.data, nx.ctypes.data))
-    return o, d, nx
+    st = np.array(settings13, dtype=np.float32, order="C")
+    return _kat("camera", (x, y, sample), head=(st.ctypes.data, int(W), int(H), int(frame_seed) & (2 ** 64 - 1), int(stride) & 0xFFFFFFFF))
 
 
 def kat_store(color, spp):
-    color = np.ascontiguousarray(color, np.float32)
-    out = np.zeros((color.shape[0], 3), np.int32)
-    _ok(lib().hk_kat_store(color.shape[0], color.ctypes.data, int(spp), out.ctypes.data))
-    return out
+    return _kat("store", (color,), mid=(int(spp),))[0]
 
 
 def slab(o, d, mn, mx):
@@ -440,26 +436,13 @@ class Scene:
         return out
 
     def kat_tex(self, tex, u, v):
-        tex, u, v = np.ascontiguousarray(tex, np.int32), np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32)
-        out = np.zeros(tex.shape[0], np.uint32)
-        _ok(lib().hk_kat_tex(self.h, tex.shape[0], tex.ctypes.data, u.ctypes.data, v.ctypes.data, out.ctypes.data))
-        return out
+        return _kat("tex", (tex, u, v), head=(self.h,))[0]
 
     def kat_bounce(self, obj_index, o, d, t, atten, seed, warm):
-        idx, warm, seed = np.ascontiguousarray(obj_index, np.int32), np.ascontiguousarray(warm, np.int32), np.ascontiguousarray(seed, np.uint64)
-        o, d, t, atten = (np.ascontiguousarray(a, np.float32) for a in (o, d, t, atten))
-        n = idx.shape[0]
-        alive, nx = np.zeros((2, n), np.int32), np.zeros((2, n, 2), np.uint32)
-        o2, d2, a2 = (np.zeros((2, n, 3), np.float32) for _ in range(3))
-        _ok(lib().hk_kat_bounce(self.h, n, idx.ctypes.data, o.ctypes.data, d.ctypes.data, t.ctypes.data, atten.ctypes.data, seed.ctypes.data, warm.ctypes.data,
-                                alive.ctypes.data, o2.ctypes.data, d2.ctypes.data, a2.ctypes.data, nx.ctypes.data))
-        return alive, o2, d2, a2, nx
+        return _kat("bounce", (obj_index, o, d, t, atten, seed, warm), head=(self.h,))
 
     def kat_miss(self, d, atten, backtex, background):
-        d, atten = np.ascontiguousarray(d, np.float32), np.ascontiguousarray(atten, np.float32)
-        out = np.zeros((d.shape[0], 3), np.float32)
-        _ok(lib().hk_kat_miss(self.h, d.shape[0], d.ctypes.data, atten.ctypes.data, int(backtex), float(background), out.ctypes.data))
-        return out
+        return _kat("miss", (d, atten), head=(self.h,), mid=(int(backtex), float(background)))[0]
 
     def wide_info(self, tree=2):
         """What dr_context_get_option reports for the tree of wide_tree = `tree`: a dict with wide_depth (0: no wide tree), wide_own_bounds, wide_nodes."""
