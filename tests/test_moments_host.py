@@ -1,5 +1,5 @@
 """The second-moment plane without a GPU: the host build of its device functions (tools/host_kernel.cpp hk_moments_add / hk_error /
-hk_reproject_m2 / hk_denoise_m2 = device_moments.hpp compiled for the CPU) against the numpy restatement (tests/moments_checks.py), bit for
+hk_reproject / hk_denoise = device_moments.hpp compiled for the CPU) against the numpy restatement (tests/moments_checks.py), bit for
 bit, on frames rendered by the host build of the render kernel and on synthetic frames that reach the cap and the saturation; the carry across
 a reprojection, the denoiser's temporal variance, the C layout of dr_error_result and the surface (symbols, options, the CLI's help)."""
 import ctypes

@@ -11,16 +11,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void* hk_scene_load(const char* rts_path, const char* texdir);
-void hk_scene_free(void* h);
-const char* hk_last_error();
-int hk_allhits_max();
-int hk_allhits(void* hv, int walk, int tree, long long n, const float* o, const float* d, const float* tmax, int max_hits, int kind_mask, int zero_margin,
-               int32_t* count, float* t, int32_t* object, int32_t* material, float* distance, float* normal, float* uv, float* albedo, int32_t* visits, int nthreads);
-int hk_allhits_brute(void* hv, long long n, const float* o, const float* d, const float* tmax, int max_hits, int kind_mask, int32_t* count, float* t, int32_t* object,
-                     int nthreads);
-}
+#include "host_kernel/hk_api.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }

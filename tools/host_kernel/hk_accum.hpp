@@ -1,0 +1,215 @@
+// The accumulator stages on the host (hk_denoise, hk_upscale, hk_reproject, hk_moments_add, hk_error): the launch structs of device_launch.h filled with
+// host pointers and a loop over the pixels; no stage's arithmetic or indexing is written here.  Parameter defaults and ranges are params_host.hpp's.
+// Part of host_kernel.cpp.
+namespace {
+// a parameter set handed over as words: a dr_denoise_params, dr_upscale_params or dr_reproject_params
+template <class T>
+T params_from_words(const int32_t* words) { T p; memcpy(&p, words, sizeof(T)); return p; }
+
+// The low side of hk_denoise and hk_upscale over the L.gw x L.gh pixel grid (L.D, L.acc, L.hist, L.m2 and the AOV planes L.normal, L.depth,
+// L.albedo, L.mat set by the caller), stage by stage as denoise_low_side (context_accum.cpp) launches it: the guide prepare, colour stage 0 and
+// -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  The planes live in `planes`; on return L.src is the plane of the
+// result, (e, l) after stage 0, (e, var) after the last pass, and L.guide, L.gz are the guides.
+// the launch of the low side on the gw x gh grid: the denoiser's parameters, the accumulator's planes and the guides in dr_render_aov's layout
+DnLaunch host_low_launch(int gw, int gh, int W, int H, int divide_by, const DnParams& D, const int32_t* acc, const int32_t* hist, const unsigned long long* m2,
+                         const float* normal, const float* albedo, const float* depth, const int32_t* material) {
+  DnLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by; L.D = D;
+  L.acc = acc; L.hist = hist; L.m2 = m2;
+  L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
+  return L;
+}
+struct HostLow {
+  std::vector<float> guide, gz, pa, pb;      // float4 (n, z) | depth gradient | colour planes A, B (float4)
+};
+void host_denoise_low(DnLaunch& L, bool filter, int nthreads, HostLow& planes) {
+  const size_t n = (size_t)L.gw * L.gh;
+  planes.guide.resize(4 * n); planes.gz.resize(n); planes.pa.resize(4 * n); planes.pb.resize(4 * n);
+  L.guide = planes.guide.data(); L.gz = planes.gz.data();
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_guide_pixel(L, x, y); });
+  L.dst = planes.pa.data();
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_colour_pixel(L, x, y); });            // acc -> (e, l) in A
+  L.src = planes.pa.data(); L.dst = planes.pb.data();
+  if (!filter) return;
+  host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_variance_pixel(L, x, y); });          // (e, l) -> (e, var) in B
+  L.src = planes.pb.data(); L.dst = planes.pa.data();                                          // the passes: B -> A -> B ...
+  for (int it = 0; it < L.D.iterations; it++) {
+    host_grid(nthreads, L.gw, L.gh, [&](int x, int y) { dn_pass_pixel(L, 1 << it, x, y); });
+    float* const t = const_cast<float*>(L.src);
+    L.src = L.dst; L.dst = t;
+  }
+}
+}  // namespace
+extern "C" {
+// dr_accum_denoise on the host: the stage bodies of device_denoise.hpp over the pixel grid of settings13 (host_denoise_low, then the finish), from guides given
+// as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
+// W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
+// hist (may be NULL): the accumulator's history plane, W x H at x * H + y -- pixel p's divisor is hist[p] + divide_by.
+// m2 (may be NULL): the second-moment plane, W x H at x * H + y -- option "denoise_variance" = 1: the variance pre-pass takes the temporal variance
+// of pixels with four samples or more from it.  Returns 0, or -1 with hk_last_error.
+int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+               const int32_t* material, const int32_t* params, float* out_f32, uint8_t* out_rgb8, int nthreads, const int32_t* hist,
+               const unsigned long long* m2) {
+  if (!acc || !settings13 || !normal || !albedo || !depth || !material) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  const DnParams D = params ? dn_params(params_from_words<dr_denoise_params>(params)) : DN_DEFAULTS;
+  if (divide_by < 1) { hk_err = "denoise: divide_by must be >= 1"; return -1; }
+  if (const char* why = check_denoise_params(D)) { hk_err = std::string("denoise: ") + why; return -1; }
+  DnLaunch L = host_low_launch(P.gx * 8, P.gy * 8, W, H, divide_by, D, acc, hist, m2, normal, albedo, depth, material);
+  HostLow planes;
+  if (D.iterations > 0) host_denoise_low(L, true, nthreads, planes);
+  L.out_f32 = out_f32; L.out_rgb8 = out_rgb8;
+  host_grid(nthreads, W, H, [&](int x, int y) { dn_finish_pixel(L, x, y); });
+  return 0;
+}
+
+// dr_accum_upscale on the host: device_upscale.hpp over the output grid of settings13, from the low guides (the grid of settings13) and the full
+// guides (settings13 with element 11 = 1) given as arrays in dr_render_aov's layout -- normal, albedo, depth, material each.  params: a
+// dr_upscale_params (NULL: the defaults); prefilter: a dr_denoise_params or NULL -- the denoiser's host passes then run on the low grid first.
+// out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3; out_notap (may be NULL): W x H bytes, 1 where a guided pixel found no usable tap.
+// hist / m2 as hk_denoise.  Returns 0, or -1 with hk_last_error.
+int hk_upscale(const int32_t* acc, int W, int H, int divide_by, const float* settings13, const float* normal, const float* albedo, const float* depth,
+               const int32_t* material, const float* fnormal, const float* falbedo, const float* fdepth, const int32_t* fmaterial, const int32_t* params,
+               const int32_t* prefilter, float* out_f32, uint8_t* out_rgb8, uint8_t* out_notap, int nthreads, const int32_t* hist,
+               const unsigned long long* m2) {
+  if (!acc || !settings13) { hk_err = "bad argument"; return -1; }
+  RenderParams P, PF;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  float full13[13];
+  memcpy(full13, settings13, sizeof(full13));
+  full13[11] = 1.0f;
+  if (const char* why = host_view(full13, W, H, 0.0f, 0, 1, 0, PF)) { hk_err = why; return -1; }
+  const UpParams UP = params ? up_params(params_from_words<dr_upscale_params>(params)) : UP_DEFAULTS;
+  const DnParams PRE = prefilter ? dn_params(params_from_words<dr_denoise_params>(prefilter)) : DnParams{};
+  const DnParams* const pre = prefilter ? &PRE : nullptr;
+  if (divide_by < 1) { hk_err = "upscale: divide_by must be >= 1"; return -1; }
+  hk_err = check_upscale_params(UP, pre);
+  if (!hk_err.empty()) return -1;
+  UpLaunch U;
+  memset(&U, 0, sizeof(U));
+  U.gw = P.gx * 8; U.gh = P.gy * 8; U.FW = PF.gx * 8; U.FH = PF.gy * 8; U.W = W; U.H = H;
+  U.div = U.gw > 0 && U.gh > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
+  U.U = UP;
+  U.acc = acc; U.hist = hist;
+  HostLow low;
+  std::vector<float> fguide, fgz;
+  if (UP.mode == UP_GUIDED && U.gw > 0 && U.gh > 0) {
+    if (!normal || !albedo || !depth || !material || !fnormal || !falbedo || !fdepth || !fmaterial) { hk_err = "bad argument"; return -1; }
+    DnLaunch L = host_low_launch(U.gw, U.gh, W, H, divide_by, up_low_params(UP, pre), acc, hist, m2, normal, albedo, depth, material);      // the denoiser's planes
+    host_denoise_low(L, pre != nullptr, nthreads, low);
+    U.e = L.src; U.guide = L.guide; U.mat = L.mat;
+    DnLaunch G;                                                             // the full side: the guide prepare over the full grid
+    memset(&G, 0, sizeof(G));
+    G.gw = U.FW; G.gh = U.FH;
+    fguide.resize((size_t)4 * U.FW * U.FH); fgz.resize((size_t)U.FW * U.FH);
+    G.normal = fnormal; G.depth = fdepth; G.mat = fmaterial; G.guide = fguide.data(); G.gz = fgz.data();
+    host_grid(nthreads, G.gw, G.gh, [&](int x, int y) { dn_guide_pixel(G, x, y); });
+    U.Fguide = G.guide; U.Falbedo = falbedo; U.Fmat = fmaterial; U.Fgz = G.gz;
+  }
+  U.out_f32 = out_f32; U.out_rgb8 = out_rgb8;
+  host_grid(nthreads, W, H, [&](int X, int Y) {
+    bool notap = false;
+    up_pixel(U, X, Y, &notap);
+    if (out_notap) out_notap[(size_t)Y * W + X] = notap ? 1 : 0;
+  });
+  return 0;
+}
+
+// The float camera block of a view as fill_view_params forms it (what dr_accum_reproject's definition starts from): out12 = from, llc, hor, ver;
+// den2 = den_w, den_h; grid2 = gw, gh.  Returns 0, or -1 with hk_last_error.
+int hk_camera_block(const float* settings13, int W, int H, float* out12, double* den2, int* grid2) {
+  RenderParams P;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  memcpy(out12, P.from, 12); memcpy(out12 + 3, P.llc, 12); memcpy(out12 + 6, P.hor, 12); memcpy(out12 + 9, P.ver, 12);
+  den2[0] = P.den_w; den2[1] = P.den_h;
+  grid2[0] = P.gx * 8; grid2[1] = P.gy * 8;
+  return 0;
+}
+
+// dr_accum_reproject on the host: device_reproject.hpp over the pixel grid, from guides given as arrays in dr_render_aov's layout (t / material
+// gw x gh, normal gw x gh x 3) for both views -- hk_aov's or the GPU's own.  acc_from / acc_to: column-major W x H x 3; hist_from (may be NULL) /
+// hist_to: W x H at x * H + y; params: a dr_reproject_params (NULL: the defaults); counts[5]: pixels, valid, masked, offscreen, rejected.
+// m2_from / m2_to (both or neither NULL): the second-moment planes, W x H at x * H + y, carried with the sums (device_moments.hpp mo_carry).
+// Returns 0, or -1 with hk_last_error.
+int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H, int frames, const float* from_settings13, const float* to_settings13,
+                 const float* t_from, const float* normal_from, const int32_t* mat_from, const float* t_to, const float* normal_to, const int32_t* mat_to,
+                 const int32_t* params, int32_t* acc_to, int32_t* hist_to, long long* counts, int nthreads, const unsigned long long* m2_from,
+                 unsigned long long* m2_to) {
+  if ((m2_from == nullptr) != (m2_to == nullptr)) { hk_err = "bad argument"; return -1; }
+  if (!acc_from || !from_settings13 || !to_settings13 || !t_from || !normal_from || !mat_from || !t_to || !normal_to || !mat_to || !acc_to || !hist_to || !counts) { hk_err = "bad argument"; return -1; }
+  RenderParams Pf, Pt;
+  if (const char* why = host_view(from_settings13, W, H, 0.0f, 0, 1, 0, Pf)) { hk_err = why; return -1; }
+  if (const char* why = host_view(to_settings13, W, H, 0.0f, 0, 1, 0, Pt)) { hk_err = why; return -1; }
+  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { hk_err = "reproject: the two views have different divisors"; return -1; }
+  if (frames < 1) { hk_err = "reproject: frames must be >= 1"; return -1; }
+  RpLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.R = params ? rp_params(params_from_words<dr_reproject_params>(params)) : RP_DEFAULTS;
+  if (const char* why = check_reproject_params(L.R)) { hk_err = why; return -1; }
+  fill_reproject_camera(Pt, L.to);
+  fill_reproject_camera(Pf, L.from);
+  if (!fill_reproject_proj(L.from, L.J)) { hk_err = "reproject: the `from` view is degenerate"; return -1; }
+  L.gw = Pt.gx * 8; L.gh = Pt.gy * 8; L.W = W; L.H = H; L.frames = frames;
+  L.t_to = t_to; L.normal_to = normal_to; L.mat_to = mat_to;
+  L.t_from = t_from; L.normal_from = normal_from; L.mat_from = mat_from;
+  L.acc_from = acc_from; L.hist_from = hist_from; L.acc_to = acc_to; L.hist_to = hist_to;
+  L.m2_from = m2_from; L.m2_to = m2_to;
+  memset(acc_to, 0, (size_t)W * H * 3 * sizeof(int32_t));                   // (pixels outside the grid: the body writes every pixel of the grid)
+  memset(hist_to, 0, (size_t)W * H * sizeof(int32_t));
+  if (m2_to) memset(m2_to, 0, (size_t)W * H * sizeof(unsigned long long));
+  std::vector<long long> part((size_t)L.gh * 4, 0);                         // the classes of every row
+  host_rows(nthreads, L.gh, [&](int y) {
+    long long row[4] = {0, 0, 0, 0};
+    for (int x = 0; x < L.gw; x++) row[rp_pixel(L, x, y)]++;
+    memcpy(&part[(size_t)y * 4], row, sizeof(row));
+  });
+  counts[0] = (long long)L.gw * L.gh;
+  for (int c = 0; c < 4; c++) { counts[1 + c] = 0; for (int y = 0; y < L.gh; y++) counts[1 + c] += part[(size_t)y * 4 + (size_t)c]; }
+  return 0;
+}
+
+// The fused add of the second-moment plane on the host (device_moments.hpp, as kernels_moments.hip runs it): acc += frame and m2 += the frame's capped
+// luma squared, for npix pixels, in place.
+int hk_moments_add(int32_t* acc, const int32_t* frame, unsigned long long* m2, long long npix) {
+  if (!acc || !frame || !m2 || npix < 0) { hk_err = "bad argument"; return -1; }
+  for (long long p = 0; p < npix; p++) mo_add_pixel(acc, frame, m2, (size_t)p);
+  return 0;
+}
+
+// dr_accum_error on the host: device_moments.hpp over the pixel grid of settings13.  acc: column-major W x H x 3; hist (may be NULL) / m2: W x H at
+// x * H + y; out_sigma (may be NULL): row-major W x H, 0 outside the grid; result (may be NULL): 19 words -- estimated, above, sum_var_q16, bins[16]
+// (pixels = grid2[0] * grid2[1], returned in grid2).  Returns 0, or -1 with hk_last_error.
+int hk_error(const int32_t* acc, const int32_t* hist, const unsigned long long* m2, int W, int H, int divide_by, float tolerance, const float* settings13,
+             float* out_sigma, unsigned long long* result, int* grid2, int nthreads) {
+  if (!acc || !m2 || !settings13 || (!out_sigma && !result)) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  if (divide_by < 0) { hk_err = "error: divide_by must be >= 0"; return -1; }
+  if (!(tolerance >= 0.0f)) { hk_err = "error: tolerance must be >= 0"; return -1; }
+  MoLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by; L.tolerance = tolerance;
+  L.acc = acc; L.hist = hist; L.m2 = m2; L.out_sigma = out_sigma;
+  if (grid2) { grid2[0] = L.gw; grid2[1] = L.gh; }
+  if (out_sigma) memset(out_sigma, 0, (size_t)W * H * sizeof(float));
+  std::vector<unsigned long long> part((size_t)L.gh * MO_WORDS, 0);         // the counts of every row
+  host_rows(nthreads, L.gh, [&](int y) {
+    unsigned long long cnt[MO_WORDS] = {0};
+    for (int x = 0; x < L.gw; x++) {
+      double var;
+      float sigma;
+      if (!mo_error_pixel(L, x, y, var, sigma)) continue;
+      cnt[MO_ESTIMATED]++;
+      if (sigma > L.tolerance) cnt[MO_ABOVE]++;
+      cnt[MO_SUM_VAR] += mo_var_q16(var);
+      cnt[MO_BIN0 + mo_bin(sigma)]++;
+    }
+    memcpy(&part[(size_t)y * MO_WORDS], cnt, sizeof(cnt));
+  });
+  if (result)
+    for (int w = 0; w < MO_WORDS; w++) { result[w] = 0; for (int y = 0; y < L.gh; y++) result[w] += part[(size_t)y * MO_WORDS + (size_t)w]; }
+  return 0;
+}
+}  // extern "C"

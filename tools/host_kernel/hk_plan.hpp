@@ -1,0 +1,109 @@
+// launch_plan.hpp on the host -- the persistent kernel's plan and builds, the regions, the query kernels' plans and constants -- and device_sky.hpp: the
+// sky split and the sky tiles' pixels and units.  Part of host_kernel.cpp.
+extern "C" {
+// launch_plan.hpp on the host (tests/test_launch_plan_host.py).  cfg6: traversal, occupancy, schedule, num_cus, coop_tiles_per_wave, count;
+// out11: the build's eight template arguments (count, occ, trav_min, park_min, unroll, wide, coop, perframe), blocks, log_waves, clear_wave_log
+void hk_persistent_plan(const int* cfg6, long long work, int coop_steps, int per_frame, int wave_log_on, int* out11) {
+  const PersistentCfg cfg = {cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0};
+  const PersistentPlan p = plan_persistent(cfg, work, coop_steps, per_frame != 0, wave_log_on != 0);
+  const PersistentBuild& b = p.build;
+  const int v[11] = {b.count, b.occ, b.trav_min, b.park_min, b.unroll, b.wide, b.coop, b.perframe, p.blocks, p.log_waves, p.clear_wave_log};
+  memcpy(out11, v, sizeof(v));
+}
+int hk_persistent_can_store_per_frame(const int* cfg6) { return persistent_can_store_per_frame(PersistentCfg{cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0}); }
+// the instantiations of render_persistent_kernel (DR_PERSISTENT_BUILDS), eight ints each, at most `room` of them; returns how many there are
+int hk_persistent_builds(int* out, int room) {
+#define HK_BUILD(COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME) {COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME},
+  static const int builds[][8] = {DR_PERSISTENT_BUILDS(HK_BUILD)};
+#undef HK_BUILD
+  const int n = (int)(sizeof(builds) / sizeof(builds[0]));
+  if (out && room > 0) memcpy(out, builds, sizeof(builds[0]) * (size_t)(room < n ? room : n));
+  return n;
+}
+int hk_plan_regions(int tiles, int batch_hint, int xcd_regions, int short_one_queue, int tiles_per_wave, int num_cus) {
+  return plan_regions(tiles, batch_hint, xcd_regions != 0, short_one_queue != 0, tiles_per_wave, num_cus);
+}
+// launch_plan.hpp plan_sky_split of the plan hk_persistent_plan returns for the same arguments
+int hk_plan_sky_split(const int* cfg6, long long work, int coop_steps, int per_frame, int wave_log_on) {
+  const PersistentCfg cfg = {cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0};
+  return plan_sky_split(plan_persistent(cfg, work, coop_steps, per_frame != 0, wave_log_on != 0)) ? 1 : 0;
+}
+// device_sky.hpp sky_split_plain: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of sky tiles
+int hk_sky_split(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order, int* launch_region_start, int* sky_list) {
+  return sky_split_plain(order, region_start, word, tiles, regions, launch_order, launch_region_start, sky_list);
+}
+int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
+// launch_plan.hpp plan_trace: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
+void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
+  const TracePlan p = plan_trace(n, traversal, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
+}
+long long hk_trace_persistent_min_rays() { return TRACE_PERSISTENT_MIN_RAYS; }
+int hk_allhits_max() { return ALLHITS_MAX; }
+int hk_allhits_chunk() { return ALLHITS_CHUNK; }
+// launch_plan.hpp plan_allhits: out3 = kernel (QUERY_KERNEL_*), wide (1 / 0), workgroups
+void hk_allhits_plan(long long n, int has_wide, int num_cus, int force, int* out3) {
+  const AllHitsPlan p = plan_allhits(n, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.wide ? 1 : 0; out3[2] = p.blocks;
+}
+long long hk_allhits_persistent_min_rays() { return ALLHITS_PERSISTENT_MIN_RAYS; }
+// launch_plan.hpp plan_radiance: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
+void hk_radiance_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
+  const RadiancePlan p = plan_radiance(n, traversal, has_wide != 0, num_cus, force);
+  out3[0] = p.kernel; out3[1] = p.traversal; out3[2] = p.blocks;
+}
+long long hk_radiance_persistent_min_rays() { return RADIANCE_PERSISTENT_MIN_RAYS; }
+int hk_radiance_chunk() { return RADIANCE_CHUNK; }
+int hk_radiance_occ() { return RADIANCE_OCC; }
+int hk_radiance_refill_min() { return RADIANCE_REFILL_MIN; }
+int hk_radiance_park() { return RADIANCE_PARK; }
+// device_sky.hpp sky_pixel summed over `frames` frames of a launch (seed, stride: dr_render_accumulate's) for n pixels (xs, ys): out[3 * n].
+// Returns 0, or -1 with hk_last_error.
+int hk_sky_pixel(void* hv, const float* settings13, int W, int H, float background, uint64_t seed, uint64_t stride, int frames, int n, const int* xs, const int* ys,
+                 int32_t* out) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || n < 0 || (n > 0 && (!xs || !ys || !out))) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(h->img, settings13, W, H, background, seed, 1, 0, P)) { hk_err = why; return -1; }
+  fill_image(h->img, P);
+  P.batch = frames; P.batch_seed_stride = stride;
+  for (int i = 0; i < n; i++) {
+    int r = 0, g = 0, b = 0;
+    for (int f = 0; f < frames; f++) {
+      int fr, fg, fb;
+      sky_pixel(P, xs[i], ys[i], f, fr, fg, fb);
+      r += fr; g += fg; b += fb;
+    }
+    out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
+  }
+  return 0;
+}
+// launch_plan.hpp's sky units (option sky_tiles = 2): how many a launch of `batch` frames with n_sky sky tiles has, and unit u as (position in sky_list,
+// first frame, frames)
+unsigned hk_sky_units(unsigned n_sky, int batch, int chunk) { return sky_units(n_sky, batch, chunk); }
+void hk_sky_unit(unsigned u, int batch, int chunk, int* out3) {
+  const SkyUnit s = sky_unit(u, batch, chunk);
+  out3[0] = s.index; out3[1] = s.first; out3[2] = s.count;
+}
+// device_sky.hpp sky_tile_frames, the body the sky kernel and the persistent kernel's retiring waves share, over every unit of a launch of `batch` frames
+// (seed, stride: dr_render_accumulate's) whose sky list is sky_list[n_sky], all 64 lanes of each, units in the order `perm` gives (null: ascending): added
+// into acc (int32[W * H * 3], P.accumulate = 2) and, cost non-null, the cost words (unsigned[tiles * 64]) written.  Returns the units run, or -1.
+long long hk_sky_units_render(void* hv, const float* settings13, int W, int H, float background, uint64_t seed, uint64_t stride, int batch, int chunk, int n_sky,
+                              const int* sky_list, const unsigned* perm, int32_t* acc, unsigned* cost) {
+  HkScene* h = (HkScene*)hv;
+  if (!h || !settings13 || batch < 1 || n_sky < 0 || !acc || (n_sky > 0 && !sky_list)) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(h->img, settings13, W, H, background, seed, 1, 0, P)) { hk_err = why; return -1; }
+  fill_image(h->img, P);
+  P.batch = batch; P.batch_seed_stride = stride;
+  P.out = acc; P.accumulate = 2;
+  P.sky_chunk = sky_chunk_frames(batch, chunk);
+  const unsigned n_units = sky_units((unsigned)n_sky, batch, P.sky_chunk);
+  for (unsigned k = 0; k < n_units; k++) {
+    const SkyUnit s = sky_unit(perm ? perm[k] : k, batch, P.sky_chunk);
+    if (s.index < 0 || s.index >= n_sky || sky_list[s.index] < 0 || sky_list[s.index] >= P.ncols * P.gy) { hk_err = "unit outside the list"; return -1; }
+    for (int lane = 0; lane < 64; lane++) sky_tile_frames(P, sky_list[s.index], lane, s.first, s.count, cost);
+  }
+  return (long long)n_units;
+}
+}  // extern "C"

@@ -11,15 +11,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void* hk_scene_load(const char* rts_path, const char* texdir);
-void hk_scene_free(void* h);
-const char* hk_last_error();
-int hk_nearest(void* hv, int walk, int tree, long long n, const float* p, const float* rmax, float* distance, float* d2, int32_t* object, int32_t* material,
-               float* point, float* uv, int32_t* visits, int nthreads);
-int hk_nearest_brute(void* hv, long long n, const float* p, const float* rmax, float* distance, float* d2, int32_t* object, int32_t* material, float* point,
-                     float* uv, int nthreads);
-}
+#include "host_kernel/hk_api.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }

@@ -10,13 +10,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void* hk_scene_load(const char* rts_path, const char* texdir);
-void hk_scene_free(void* h);
-const char* hk_last_error();
-int hk_radiance(void* hv, int traversal, int tree, long long n, const float* o, const float* d, const uint64_t* seed, const int32_t* skip, int spp,
-                int max_depth, float background, int backtex, uint64_t base_seed, float* radiance, int32_t* bounces);
-}
+#include "host_kernel/hk_api.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }

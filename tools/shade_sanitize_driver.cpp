@@ -10,21 +10,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void* hk_scene_load(const char* rts_path, const char* texdir);
-void hk_scene_free(void* h);
-const char* hk_last_error();
-int hk_kat_sample(long long n, const uint64_t* seed, const int32_t* warm, const int32_t* kind, float* point_plain, uint32_t* next_plain, float* point_merged,
-                  uint32_t* next_merged);
-int hk_kat_outside(long long n, const float* d2, int32_t* out);
-int hk_kat_tex(void* hv, long long n, const int32_t* tex, const float* u, const float* v, uint32_t* rgba);
-int hk_kat_bounce(void* hv, long long n, const int32_t* object_index, const float* o, const float* d, const float* t, const float* atten, const uint64_t* seed,
-                  const int32_t* warm, int32_t* alive, float* o_out, float* d_out, float* atten_out, uint32_t* next);
-int hk_kat_miss(void* hv, long long n, const float* d, const float* atten, int backtex, float background, float* rgb);
-int hk_kat_camera(const float* settings13, int W, int H, uint64_t frame_seed, uint32_t seed_stride, long long n, const int32_t* x, const int32_t* y,
-                  const int32_t* sample, float* origin, float* dir, uint32_t* next);
-int hk_kat_store(long long n, const float* color, int spp, int32_t* out);
-}
+#include "host_kernel/hk_api.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }

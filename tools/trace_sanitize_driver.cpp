@@ -9,15 +9,7 @@
 #include <limits>
 #include <vector>
 
-extern "C" {
-void* hk_scene_load(const char* rts_path, const char* texdir);
-void hk_scene_free(void* h);
-const char* hk_last_error();
-int hk_trace(void* hv, int traversal, int tree, int mode, long long n, const float* o, const float* d, const float* tmax, float* t, int32_t* idx,
-             int32_t* occluded, int32_t* slot, int32_t* visits);
-int hk_ray_surface(void* hv, int tree, long long n, const float* o, const float* d, const float* t, const int32_t* slot, int32_t* material, float* distance,
-                   float* normal, float* uv, float* albedo);
-}
+#include "host_kernel/hk_api.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s TEXTURE_DIR scene.rts...\n", argv[0]); return 2; }
