@@ -50,6 +50,7 @@ const Option OPTIONS[] = {
     {"trace_kernel", /* (as above) */ &dr_context::trace_kernel, 0, 2, 0, false},
     {"radiance_kernel", /* (as above) */ &dr_context::radiance_kernel, 0, 2, 0, false},
     {"allhits_kernel", /* (as above) */ &dr_context::allhits_kernel, 0, 2, 0, false},
+    {"sample_order", /* (as above) */ &dr_context::sample_order, 0, 1, 0, false},
 };
 
 const Option* find_option(const std::string& name) {

@@ -101,6 +101,11 @@ constexpr int LAUNCH_COUNTERS = MAX_REGIONS + 1;      // a launch's block of the
 
 }  // namespace dr
 
+// option sample_order's default (the macro serves variant libraries of an A/B, as DR_SKY_CHUNK does)
+#ifndef DR_SAMPLE_ORDER
+#define DR_SAMPLE_ORDER 1
+#endif
+
 struct dr_context {
   template <class T> using DevMem = dr::DevMem<T>;
   int device = 0;
@@ -191,6 +196,7 @@ struct dr_context {
   // persistent kernel (context_render.cpp enqueue_frame).  The split is made on the launch's stream and kept while the words and the order it was
   // made from are the same (sky_key: cert_gen, order in use, order_gen, tiles, regions -- sky_split_kernel takes 0.53 % of a 32-frame launch of the bench
   // view, profiles/sky_tiles_ab.txt); tile_order / region_start above stay whole
+  int sample_order = DR_SAMPLE_ORDER;                   // option: which samples of a tile share a unit of the queue (launch_plan.hpp tile_sample): 0 a frame's 64 pixels, 1 a pixel's frames
   int sky_tiles = 2;                       // option: 0 every tile goes through the persistent kernel; 1 sky_tiles_kernel in front of it; 2 its retiring waves
   DevMem<int> launch_order, launch_region_start, sky_list;
   DevMem<unsigned> sky_counts;             // [0] sky tiles, [1] geometry tiles of the last split

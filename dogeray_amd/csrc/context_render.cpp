@@ -159,6 +159,7 @@ bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles
 int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in) {
   RenderParams P = P_in;
   const int tiles = P.ncols * P.gy;
+  P.sample_magic = sample_order_magic(c->sample_order, P.batch);      // every launch comes through here with its batch set (dr_render_accumulate, the pipeline's groups)
   if (uses_persistent(c)) {
     if (c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS) {
       (void)hipMemsetAsync(c->tile_counters, 0, TILE_COUNTERS * sizeof(unsigned), site.stream);

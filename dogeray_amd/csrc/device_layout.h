@@ -194,6 +194,8 @@ struct RenderParams {
   const unsigned* sky_counts;
   unsigned* sky_cursor;
   int32_t sky_chunk;
+  uint32_t sample_magic;          // option sample_order (launch_plan.hpp sample_order_magic of this launch's batch): 0 a unit of the queue is one frame of its tile's 64 pixels,
+                                  // else ceil(2^32 / batch): a unit is consecutive frames of one or two pixels (tile_sample)
 };
 
 // The denoiser's parameters (dr_denoise_params; defaults and ranges: params_host.hpp) and its material markers (device_denoise.hpp)

@@ -220,6 +220,68 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, int x, int y,
   else { px[0] = r; px[1] = g; px[2] = b; }
 }
 
+#ifndef DR_HOST_BUILD
+// STORES_MERGED (the macro serves the variant libraries of tools/exp_variant.sh): with option sample_order = 1 the lanes of a wave that end a path in one
+// phase are mostly frames of the same pixel and would each add their three words to the same three addresses; store_pixels_merged adds one sum per pixel
+// instead.  Integer addition is exact in any grouping: the same bytes.  Only for launches that add atomically with a frame-minor order (never one frame).
+#ifndef DR_STORES_MERGED
+#define DR_STORES_MERGED 2
+#endif
+constexpr int STORES_MERGED = DR_STORES_MERGED;      // 0 every lane adds on its own; 1 store_pixels_merged; 2 store_pixels_merged_lds (the wide builds)
+// the sum of v over the wave (all 64 lanes active), as a scalar: an inclusive scan within each row of 16 (row_shr 1, 2, 4, 8; lanes shifted in read 0), then
+// lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast15), lane 31 into rows 2 and 3 (row_bcast31): lane 63 holds the total
+__device__ __forceinline__ int wave_sum(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, true);
+  return __builtin_amdgcn_readlane(v, 63);
+}
+// store_pixel's atomic adds (P.accumulate == 2) for the lanes with store_me, one set per pixel: called by the whole wave; key names the lane's pixel
+// (two lanes with the same key have the same x, y).  A turn per distinct pixel among the storing lanes; its lowest lane adds the group's sums.
+__device__ __forceinline__ void store_pixels_merged(const RenderParams& P, bool store_me, int key, int x, int y, V3 color) {
+  const int r = f2i(color.x * 255 * P.scale), g = f2i(color.y * 255 * P.scale), b = f2i(color.z * 255 * P.scale);
+  unsigned long long todo = __ballot(store_me);
+  while (todo != 0ull) {
+    const int lead = __builtin_ctzll(todo);
+    const bool mine = store_me && key == __builtin_amdgcn_readlane(key, lead);
+    const int sr = wave_sum(mine ? r : 0), sg = wave_sum(mine ? g : 0), sb = wave_sum(mine ? b : 0);
+    if ((int)(threadIdx.x & 63) == lead) {
+      int32_t* px = P.out + ((size_t)x * (size_t)P.H + (size_t)y) * 3;
+      atomicAdd(px + 0, sr); atomicAdd(px + 1, sg); atomicAdd(px + 2, sb);
+    }
+    todo &= ~__ballot(mine);
+  }
+}
+// The same through five LDS words per slot that the caller has free (word w of slot s at ws[w * 64 + s - lane], s = 0 .. 63, private to the wave): a pixel's slot is
+// the low six bits of its key.  The storing lanes write their key to their slot and clear its three sums; the lanes that find their own key there -- all the
+// lanes of one pixel: two pixels on one slot are rare, the loser's lanes add on their own -- add into the sums with LDS atomics and write their lane number;
+// the lane that finds its own number adds the sums to the pixel.  A wave's LDS instructions run in order, and the compiler barriers keep it from forwarding
+// a lane's own write to its read.  The cost does not depend on how many pixels end in the phase.
+// (the three integers are formed where they are used, a channel at a time: held beside the colour they cost the lean build two spilled registers)
+__device__ __forceinline__ void store_pixels_merged_lds(const RenderParams& P, int* ws, int lane, bool store_me, int key, int x, int y, V3 color) {
+  if (!store_me) return;
+  int* const slot = ws + ((key & 63) - lane);      // words: 0 key, 1 lane, 2 .. 4 sums (ws: the first word of slot `lane`, which the caller has at hand)
+  slot[0] = key; slot[2 * 64] = 0; slot[3 * 64] = 0; slot[4 * 64] = 0;
+  asm volatile("" ::: "memory");
+  const bool ok = slot[0] == key;
+  if (ok) {
+    slot[1 * 64] = lane;
+    atomicAdd(slot + 2 * 64, f2i(color.x * 255 * P.scale)); atomicAdd(slot + 3 * 64, f2i(color.y * 255 * P.scale)); atomicAdd(slot + 4 * 64, f2i(color.z * 255 * P.scale));
+  }
+  asm volatile("" ::: "memory");
+  int r, g, b;
+  if (ok) {
+    if (slot[1 * 64] != lane) return;
+    r = slot[2 * 64]; g = slot[3 * 64]; b = slot[4 * 64];
+  } else { r = f2i(color.x * 255 * P.scale); g = f2i(color.y * 255 * P.scale); b = f2i(color.z * 255 * P.scale); }
+  int32_t* px = P.out + ((size_t)x * (size_t)P.H + (size_t)y) * 3;
+  atomicAdd(px + 0, r); atomicAdd(px + 1, g); atomicAdd(px + 2, b);
+}
+#endif
+
 // Kernel K:998-1093 for one pixel (the camera basis comes precomputed in P).
 template <bool COUNT, class Closest>
 __device__ __forceinline__ void render_pixel(const RenderParams& P, const Closest& closest, int x, int y, Ctr& c, bool* camera_ray_next = nullptr /* set before every path: its first ray is a camera ray */) {

@@ -175,13 +175,15 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   // first (longest-processing-time-first: the kernel's duration is otherwise set by whichever
   // expensive tile happens to start last).
   // A launch may cover a batch of frames (same view, consecutive seeds): position q is tile
-  // order[q / batch] of frame q % batch, so the expensive tiles of ALL frames start first and the
-  // tail of one frame (its longest paths) overlaps the bulk of the others.
+  // order[q / batch], unit q % batch, so the expensive tiles of ALL frames start first and the
+  // tail of one frame (its longest paths) overlaps the bulk of the others.  A unit is 64 of the
+  // tile's 64 x batch samples: the tile's pixels of frame q % batch, or -- option sample_order = 1 --
+  // consecutive frames of one or two of its pixels (launch_plan.hpp tile_sample).
   // The queue is split into P.regions contiguous parts (tiles are numbered column by column, so a part
   // is a band of the image).  With 8 regions every XCD drains "its" band first -- its 4 MiB L2 then holds
   // the part of the scene that band sees instead of competing for all of it -- and helps the next band
   // once its own is empty.  Region r owns positions [region_start[r], region_start[r+1]) of the order.
-  int cur_tile = ntiles, cur_frame = 0;        // chunk being handed out; ntiles = none
+  int cur_tile = ntiles, cur_frame = 0;        // chunk being handed out: tile (ntiles = none) and unit of the tile (with sample_order 0 the frame)
   unsigned cur_cert = 0u;          // lean build: cur_tile's word of P.cert_level (wave-uniform) -- in the low ENTRY_SHIFT bits its grade in the view's grazing certificate (0: its
                                    // camera rays keep the scene's margin), above them the entry code of its camera rays (0: the root)
   int cur_next = 64;               // next unassigned lane-in-tile of cur_tile (64 = exhausted: fetch first)
@@ -340,12 +342,21 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       }
       // ---- lanes between paths: next sample of the same pixel, or store and take a new pixel
       bool want_pixel = false;
+      // (a launch that adds a frame-minor batch atomically: the lanes that end the same pixel in this phase add one sum -- device_shade.hpp; wave-uniform)
+      // (the five stash words from WS_COLOR_Y on are registers between the unstash and the restore, in every lane: the merge's slots)
+      static_assert(WS_SAMPLE - WS_COLOR_Y == 4, "five consecutive stash words");
+      const bool merged = STORES_MERGED != 0 && WIDE && !PERFRAME && P.sample_magic != 0u && P.accumulate == 2;
+      if (merged) {
+        const bool store_me = tr.node == LANE_REFILL && px >= 0 && !((float)sample < P.spp_f && !degenerate);
+        if (STORES_MERGED == 2) store_pixels_merged_lds(P, reinterpret_cast<int*>(st) + WS_COLOR_Y * 64, lane, store_me, pcode, px, py, color);
+        else store_pixels_merged(P, store_me, pcode, px, py, color);
+      }
       if (tr.node == LANE_REFILL) {
         if (px >= 0 && (float)sample < P.spp_f && !degenerate) {
           // same pixel, next sample (K:1059)
         } else {
           if (px >= 0) {
-            store_pixel(P, px, py, color, PERFRAME ? (size_t)frame * (size_t)P.out_frame_stride : (size_t)0);
+            if (!merged) store_pixel(P, px, py, color, PERFRAME ? (size_t)frame * (size_t)P.out_frame_stride : (size_t)0);
             if (pixel_cost) pixel_cost[pcode & PCODE_MASK] = steps;
           }
           px = -1;
@@ -407,12 +418,14 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
         const int avail = cur_limit - cur_next;
         if (want_pixel && rank < avail) {
-          const int l = cur_next + rank;
+          // slot l of unit cur_frame is sample 64 cur_frame + l of the tile: which pixel of the tile and which frame that is, is option sample_order's
+          // (launch_plan.hpp tile_sample; a split tile's parts exist in launches of one frame only, where it is the identity)
+          const TileSample ts = tile_sample(P.sample_magic, P.batch, cur_frame * 64 + cur_next + rank);
           const int col = cur_tile / P.gy, by = cur_tile - col * P.gy;
-          px = (P.stripe_rem + col * P.stripe_mod) * 8 + (l >> 3);
-          py = by * 8 + (l & 7);
-          pcode = (cur_tile * 64 + l) | (cur_split ? PCODE_SPLIT : 0);
-          frame = cur_frame;
+          px = (P.stripe_rem + col * P.stripe_mod) * 8 + (ts.p >> 3);
+          py = by * 8 + (ts.p & 7);
+          pcode = (cur_tile * 64 + ts.p) | (cur_split ? PCODE_SPLIT : 0);
+          frame = ts.f;
           steps = 0;
           sample = 0;
           color = mk(0, 0, 0);

@@ -128,6 +128,24 @@ constexpr SkyUnit sky_unit(unsigned u, int batch, int chunk) {
   return SkyUnit{(int)index, first, batch - first < frames ? batch - first : frames};
 }
 
+// Option sample_order: which of a tile's 64 x batch samples (pixel-in-tile p, frame f) share a unit of the queue.  A tile's units are
+// numbered 0 .. batch - 1 and unit u hands out the sample indices j = 64 u + l, l = 0 .. 63, in ascending order.  Order 0: p = j % 64, f = j / 64 -- a
+// unit is the tile's 64 pixels of one frame.  Order 1 (frame-minor): p = j / batch, f = j % batch -- a unit is consecutive frames of one or two pixels
+// (of at most ceil(64 / batch) + 1).  Either is a bijection of [0, 64 batch) onto [0, 64) x [0, batch), and with batch = 1 the identity.
+// The division by the batch is a multiply-high by sample_order_magic's word m = ceil(2^32 / batch): j m = (j / batch) 2^32 + rest with
+// 0 <= rest < 2^32 as long as j (m batch - 2^32) < 2^32, and m batch - 2^32 < batch <= 256, j < 2^14.  ceil(2^32 / 1) does not fit a word: the word is
+// 0 for batch 1 and for order 0, and 0 means order 0 (wave-uniform in the kernel).  (constexpr: the kernel and the host build call the same functions.)
+constexpr int SAMPLE_ORDER_MAX_BATCH = 256;      // (dr_context's batch_frames ends there)
+struct TileSample { int p, f; };
+constexpr uint32_t sample_order_magic(int order, int batch) {
+  return order == 1 && batch > 1 && batch <= SAMPLE_ORDER_MAX_BATCH ? (uint32_t)((0x100000000ull + (uint64_t)batch - 1ull) / (uint64_t)batch) : 0u;
+}
+constexpr TileSample tile_sample(uint32_t magic, int batch, int j) {
+  if (magic == 0u) return TileSample{j & 63, j >> 6};
+  const int p = (int)(uint32_t)(((uint64_t)(uint32_t)j * (uint64_t)magic) >> 32);
+  return TileSample{p, j - p * batch};
+}
+
 // Tile queues of a launch of `tiles` tiles (batch_hint frames of them): one per XCD, or one
 inline int plan_regions(int tiles, int batch_hint, bool xcd_regions, bool short_one_queue, int tiles_per_wave, int num_cus) {
   int regions = xcd_regions ? MAX_REGIONS : 1;

@@ -65,6 +65,7 @@ inline const char* fill_view_params(const float* st, int W, int H, float backgro
   P.backtex = hf2i(st[12]);
   P.batch = 1;
   P.batch_seed_stride = 0;
+  P.sample_magic = 0;                                             // (one frame: both sample orders are the identity)
   return nullptr;
 }
 

@@ -209,6 +209,10 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   the time the launch waits for its slowest wave; 1 in a kernel of their own in front of the persistent kernel; 0 every tile
  *                   goes through the persistent kernel's queues.  The same bits with every value.  Not used by the counting and work-sharing
  *                   builds nor by pipelined launches
+ *   "sample_order"  which of a tile's 64 x B samples share a unit of the persistent kernel's queue in a launch of B frames (batch_frames, a pipelined
+ *                   group): 0 a unit is the tile's 64 pixels of one frame; 1 (default) a unit is consecutive frames of one or two pixels
+ *                   of the tile, so the lanes a wave refills together are jittered samples of the same pixel.  A pixel's arithmetic depends on
+ *                   (x, y, frame) only and the batch is summed in integers: the same bits either way.  Launches of one frame are the same launch
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)

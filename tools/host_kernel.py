@@ -69,6 +69,9 @@ _API = [
     ("hk_persistent_can_store_per_frame", _I, [_PI]),
     ("hk_persistent_builds", _I, [_P, _I]),
     ("hk_plan_regions", _I, [_I] * 6),
+    ("hk_sample_order_magic", C.c_uint, [_I, _I]),
+    ("hk_tile_sample", None, [C.c_uint, _I, _I, _PI]),
+    ("hk_tile_samples", None, [_I, _I, _PI]),
     ("hk_plan_split_limit", _I, [_I] * 4),
     ("hk_plan_sky_split", _I, [_PI, _Q, _I, _I, _I]),
     ("hk_trace_plan", None, [_Q, _I, _I, _I, _I, _P]),

@@ -32,6 +32,18 @@ int hk_plan_sky_split(const int* cfg6, long long work, int coop_steps, int per_f
 int hk_sky_split(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order, int* launch_region_start, int* sky_list) {
   return sky_split_plain(order, region_start, word, tiles, regions, launch_order, launch_region_start, sky_list);
 }
+// launch_plan.hpp's sample orders (option sample_order; tests/test_sample_order_host.py): the word RenderParams carries, and sample j of a tile as
+// out2 = (pixel-in-tile, frame) through that word -- the kernel's own call
+unsigned hk_sample_order_magic(int order, int batch) { return sample_order_magic(order, batch); }
+void hk_tile_sample(unsigned magic, int batch, int j, int* out2) {
+  const TileSample s = tile_sample(magic, batch, j);
+  out2[0] = s.p; out2[1] = s.f;
+}
+// ... every sample of a tile at once: out[2 * j], out[2 * j + 1] for j = 0 .. 64 * batch - 1
+void hk_tile_samples(int order, int batch, int* out) {
+  const unsigned magic = sample_order_magic(order, batch);
+  for (int j = 0; j < 64 * batch; j++) hk_tile_sample(magic, batch, j, out + 2 * j);
+}
 int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 // launch_plan.hpp plan_trace: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
 void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
