@@ -288,6 +288,7 @@ _API = [
     ("dr_kat_miss", C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int, C.c_float, _VP]),
     ("dr_kat_camera", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int] + [_VP] * 6),
     ("dr_kat_store", C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP]),
+    ("dr_kat_store_merged", C.c_int, [_VP, C.c_int, C.c_int] + [_VP] * 5 + [C.c_int] * 3 + [_VP] * 3),
     ("dr_stats_tile_order", C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t), _VP, _VP]),
     ("dr_kat_tile_feedback", C.c_int, [_VP] + [C.c_int] * 5 + [_VP] * 4),
 ]
@@ -1313,6 +1314,26 @@ class Context:
 
     def kat_store(self, color, spp):
         return self._kat("store", (color,), mid=(int(spp),))[0]
+
+    def kat_store_merged(self, form, store_me, key, x, y, color, spp, acc, lds_in):
+        """dr_kat_store_merged: the stores of whole waves (lane i of the arrays is lane i % 64 of wave i / 64) added to a copy of acc, int32[W, H, 3]
+        -- form 0 store_pixel per lane, 1 store_pixels_merged, 2 store_pixels_merged_lds; lds_in: int32[waves, 7, 64], the waves' LDS rows before
+        the store.  Returns (acc afterwards, the LDS rows afterwards).  Not in KAT_HOOKS: the accumulator goes in and out and no array but the
+        lanes' has n items, so the shapes are judged here -- ValueError before the library is touched."""
+        ins = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((store_me, np.int32), (key, np.int32), (x, np.int32), (y, np.int32), (color, np.float32))]
+        n = ins[0].shape[0]
+        for a, name, tail in zip(ins, ("store_me", "key", "x", "y", "color"), ((), (), (), (), (3,))):
+            if a.shape != (n,) + tail:
+                raise ValueError("kat_store_merged: %s must be [%s]" % (name, ", ".join(["n"] + [str(k) for k in tail])))
+        out = np.array(acc, dtype=np.int32, order="C")
+        if out.ndim != 3 or out.shape[2] != 3:
+            raise ValueError("kat_store_merged: acc must be [W, H, 3]")
+        rows = np.ascontiguousarray(lds_in, dtype=np.int32)
+        if rows.shape != (n // 64, 7, 64):
+            raise ValueError("kat_store_merged: lds_in must be [n / 64, 7, 64]")
+        after = np.zeros_like(rows)
+        _check(lib().dr_kat_store_merged(self._h, int(form), n, *[_p(a) for a in ins], int(spp), out.shape[0], out.shape[1], _p(out), _p(rows), _p(after)))
+        return out, after
 
     def kat_tile_feedback(self, pixel_cost, regions, heavy_factor, split_steps, split_limit, ntiles=None):
         """The feedback kernels on a flat uint32 plane of ntiles * 64 pixel costs (dr_kat_tile_feedback): (tile_cost uint32[ntiles],

@@ -1,6 +1,7 @@
 // Measurement probes (dr_context_probe_*) and the known-answer hooks of single device functions (dr_kat_*).
 #include <deque>
 #include <initializer_list>
+#include <map>
 #include <utility>
 
 #include "context.hpp"
@@ -176,6 +177,8 @@ struct KatStage {
   template <class T> T* in(const T* host, size_t count) { return static_cast<T*>(stage(host, nullptr, count * sizeof(T), -1)); }
   // a device buffer of count elements that finish() copies to host (null: it stays on the device); preset_byte >= 0: every byte set to it on the stream
   template <class T> T* out(T* host, size_t count, int preset_byte = -1) { return static_cast<T*>(stage(nullptr, host, count * sizeof(T), preset_byte)); }
+  // both: a device copy of host[0 .. count) that finish() copies back
+  template <class T> T* inout(T* host, size_t count) { return static_cast<T*>(stage(host, host, count * sizeof(T), -1)); }
   // launch(args...) unless a staging step failed -- the in() and out() calls among args have run by now --, then: the launch's error, the stream
   // drained, the outputs in the caller's arrays
   template <class Launch, class... Args> int finish(Launch launch, Args&&... args) {
@@ -360,6 +363,33 @@ int dr_kat_store(dr_context* c, int n, const float* color, int spp, int32_t* out
   const size_t m = (size_t)n * 3;
   P.W = n; P.H = 1; P.out = k.out(out, m); P.accumulate = 0;                   // colour i is pixel (i, 0) of an n x 1 frame
   return k.finish(launch_kat_store, c->stream, P, n, k.in(color, m));
+}
+
+int dr_kat_store_merged(dr_context* c, int form, int n_lanes, const int32_t* store_me, const int32_t* key, const int32_t* x, const int32_t* y,
+                        const float* color, int spp, int W, int H, int32_t* acc, const int32_t* lds_in, int32_t* lds_out) {
+  KAT_BEGIN(k, c, n_lanes, false, store_me, key, x, y, color, acc, lds_in, lds_out);
+  if (form < 0 || form > 2) { set_error("store_merged: form must be 0, 1 or 2"); return DR_ERR_INVALID; }
+  if (n_lanes % 64 != 0) { set_error("store_merged: n_lanes must be a multiple of 64 (whole waves)"); return DR_ERR_INVALID; }
+  if (spp < 1) { set_error("store_merged: spp < 1"); return DR_ERR_INVALID; }
+  if (W < 1 || H < 1) { set_error("store_merged: W and H must be at least 1"); return DR_ERR_INVALID; }
+  // the kernel adds at (x * H + y) * 3 of acc without a test of its own: every storing lane is judged here
+  std::map<int32_t, std::pair<int32_t, int32_t>> pixel_of;
+  for (int i = 0; i < n_lanes; i++) {
+    if (!store_me[i]) continue;
+    if (x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H) { set_error("store_merged: lane " + std::to_string(i) + " stores outside the frame"); return DR_ERR_INVALID; }
+    if (key[i] < 0) { set_error("store_merged: lane " + std::to_string(i) + " has a negative key"); return DR_ERR_INVALID; }
+    const auto at = pixel_of.emplace(key[i], std::make_pair(x[i], y[i])).first;
+    if (at->second != std::make_pair(x[i], y[i])) { set_error("store_merged: lane " + std::to_string(i) + " has the key of another pixel"); return DR_ERR_INVALID; }
+  }
+  DR_TRY(join_pipeline(c));
+  const float st[13] = {0, 0, 2, 0, 0, 0, 0, 1, 45, 1, (float)spp, 1, -1};      // any view, as dr_kat_store: the stores read its sample scale alone
+  RenderParams P;
+  memset(&P, 0, sizeof(P));
+  if (const char* why = fill_view_params(st, 8, 8, 0.0f, 0, 1, 0, P)) { set_error(why); return DR_ERR_INVALID; }
+  const size_t m = (size_t)n_lanes, words = m / 64 * KAT_MERGE_ROWS * 64;
+  P.W = W; P.H = H; P.out = k.inout(acc, (size_t)W * (size_t)H * 3); P.accumulate = 2;
+  return k.finish(launch_kat_store_merged, c->stream, P, form, n_lanes, k.in(store_me, m), k.in(key, m), k.in(x, m), k.in(y, m), k.in(color, 3 * m),
+                  k.in(lds_in, words), k.out(lds_out, words));
 }
 
 int dr_kat_hit(dr_context* c, int n, const float* o, const float* d, float* t, int32_t* idx, int32_t* visits) {

@@ -99,6 +99,11 @@ void launch_kat_miss(hipStream_t stream, const RenderParams& P, int n, const flo
 void launch_kat_camera(hipStream_t stream, const RenderParams& P, int n, const int32_t* x, const int32_t* y, const int32_t* s, float* origin2,
                        float* dir2, uint32_t* next2);
 void launch_kat_store(hipStream_t stream, const RenderParams& P, int n, const float* color);      // into P.out, pixel (i, 0) of an n x 1 frame
+// the stores of n / 64 whole waves into the P.W x P.H accumulator P.out (P.accumulate 2) -- form 0 store_pixel, 1 store_pixels_merged, 2 store_pixels_merged_lds;
+// lds_in / lds_out: KAT_MERGE_ROWS rows of 64 LDS words per wave, before and after (rows 1 .. 5 the slot rows)
+constexpr int KAT_MERGE_ROWS = 7;
+void launch_kat_store_merged(hipStream_t stream, const RenderParams& P, int form, int n, const int32_t* store_me, const int32_t* key, const int32_t* x,
+                             const int32_t* y, const float* color, const int32_t* lds_in, int32_t* lds_out);
 
 // kernels_aov.hip: the window (x0, y0, w, h) of the pixel grid and the channels to write (null: not written), each a row-major w x h plane
 // (pixel (x, y) at (y - y0) * w + (x - x0); normal / albedo / dir 3 floats per pixel, uv 2)

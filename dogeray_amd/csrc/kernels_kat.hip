@@ -130,6 +130,32 @@ __global__ __launch_bounds__(256) void kat_store_kernel(RenderParams P, int n, c
   kat_store_lane(P, i, color);
 }
 
+// ---- the merged stores of device_shade.hpp (dr_kat_store_merged): lane i of the call is lane i % 64 of wave i / 64, four waves to a block as in the render
+// kernel, n a multiple of 64 so that every wave that stores is whole (wave_sum needs its 64 lanes).  FORM 0: store_pixel, every storing lane on its own;
+// 1: store_pixels_merged; 2: store_pixels_merged_lds.  A wave owns KAT_MERGE_ROWS rows of 64 LDS words, filled from lds_in before the store and written to
+// lds_out after it: rows 1 .. 5 are the five slot rows, handed over as the render kernel hands its stash (the first word of slot `lane`); rows 0 and 6 are guards.
+template <int FORM>
+__global__ __launch_bounds__(256) void kat_store_merged_kernel(RenderParams P, int n, const int32_t* store_me, const int32_t* key, const int32_t* x,
+                                                               const int32_t* y, const float* color, const int32_t* lds_in, int32_t* lds_out) {
+  __shared__ int lds[4 * KAT_MERGE_ROWS * 64];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;                                    // whole waves: n is a multiple of 64
+  const int lane = threadIdx.x & 63;
+  int* const rows = lds + (threadIdx.x >> 6) * (KAT_MERGE_ROWS * 64);
+  const size_t first = (size_t)(i >> 6) * (KAT_MERGE_ROWS * 64);
+  for (int r = 0; r < KAT_MERGE_ROWS; r++) rows[r * 64 + lane] = lds_in[first + r * 64 + lane];
+  asm volatile("" ::: "memory");                         // (a wave's LDS instructions run in order: the other lanes' words are there, as at the call site)
+  __builtin_amdgcn_wave_barrier();
+  const bool s = store_me[i] != 0;
+  const V3 c = ld3(color + 3 * (size_t)i);
+  if (FORM == 2) store_pixels_merged_lds(P, rows + 64 + lane, lane, s, key[i], x[i], y[i], c);
+  else if (FORM == 1) store_pixels_merged(P, s, key[i], x[i], y[i], c);
+  else if (s) store_pixel(P, x[i], y[i], c);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  for (int r = 0; r < KAT_MERGE_ROWS; r++) lds_out[first + r * 64 + lane] = rows[r * 64 + lane];
+}
+
 // ------------------------------------------------------------------ launchers
 // every kernel but kat_rng_kernel (one wave: a single generator's sequence): blocks of 256 lanes, lane i the element i of n
 template <class Kernel, class... Args>
@@ -182,5 +208,11 @@ void launch_kat_camera(hipStream_t stream, const RenderParams& P, int n, const i
   kat_launch(kat_camera_kernel, stream, n, P, n, x, y, s, origin2, dir2, next2);
 }
 void launch_kat_store(hipStream_t stream, const RenderParams& P, int n, const float* color) { kat_launch(kat_store_kernel, stream, n, P, n, color); }
+void launch_kat_store_merged(hipStream_t stream, const RenderParams& P, int form, int n, const int32_t* store_me, const int32_t* key, const int32_t* x,
+                             const int32_t* y, const float* color, const int32_t* lds_in, int32_t* lds_out) {
+  if (form == 2) kat_launch(kat_store_merged_kernel<2>, stream, n, P, n, store_me, key, x, y, color, lds_in, lds_out);
+  else if (form == 1) kat_launch(kat_store_merged_kernel<1>, stream, n, P, n, store_me, key, x, y, color, lds_in, lds_out);
+  else kat_launch(kat_store_merged_kernel<0>, stream, n, P, n, store_me, key, x, y, color, lds_in, lds_out);
+}
 
 }  // namespace dr

@@ -900,6 +900,20 @@ int dr_kat_camera(dr_context* c, const float settings13[13], int W, int H, uint6
                   const int32_t* y, const int32_t* sample, float* origin, float* dir, uint32_t* next);
 /* store_pixel (not accumulating) of a pixel's summed colour for spp samples: out[n * 3] */
 int dr_kat_store(dr_context* c, int n, const float* color, int spp, int32_t* out);
+/* The stores of a batched launch (device_shade.hpp), on lanes the caller chooses: lane i of the call is lane i % 64 of wave i / 64, four waves to a
+ * workgroup as in the render kernel, all 64 lanes of a wave active at the store.  The lanes with store_me[i] != 0 add colour i (summed over spp
+ * samples, store_pixel's conversion) to pixel (x[i], y[i]) of acc, a W x H accumulator in store_pixel's layout, (x * H + y) * 3, read and written
+ * back; key[i] names the lane's pixel to the merge (the render kernel passes the pixel's code).  form 0: store_pixel, every storing lane adding
+ * atomically on its own; 1: store_pixels_merged (a DPP sum per distinct key); 2: store_pixels_merged_lds (the default build's).  Integer addition is
+ * exact in any grouping, so the three forms must return the same acc: the sum of the storing lanes' integers per pixel, wrapped to 32 bits.
+ * Every wave owns 7 rows of 64 LDS words, copied from lds_in before the store and to lds_out after it ((n_lanes / 64) * 7 * 64 words each, wave-major):
+ * rows 1 .. 5 are the five slot rows of form 2 -- word w of slot s of the wave at row 1 + w, column s --, rows 0 and 6 are guards; forms 0 and 1
+ * leave all seven as they came, form 2 writes only the slots key & 63 of storing lanes.
+ * The kernel does not test where it adds: DR_ERR_INVALID, before anything is staged, for form outside 0 .. 2, n_lanes no multiple of 64, spp < 1,
+ * W or H < 1, and for a lane with store_me that has x outside [0, W), y outside [0, H), a negative key, or the key of a storing lane of another
+ * pixel (the merge's precondition: one key, one pixel; two keys for one pixel are allowed).  There is no host mirror: LDS atomics and DPP have none. */
+int dr_kat_store_merged(dr_context* c, int form, int n_lanes, const int32_t* store_me, const int32_t* key, const int32_t* x, const int32_t* y,
+                        const float* color, int spp, int W, int H, int32_t* acc, const int32_t* lds_in, int32_t* lds_out);
 /* The plane arithmetic of the wide walk's node test (device_wide.hpp wide_node_test): for word w[i] (four plane bytes) t_mix[4 i + k] =
  * fma(byte_k read as the f16 denormal byte * 2^-24 inside v_fma_mix_f32, a[i] * 2^24, b[i]) and t_cvt[4 i + k] = fma((float)byte_k, a[i], b[i]):
  * the two must agree bit for bit (a[i] * 2^24 must not overflow) -- the check that the instruction keeps f16 denormals */

@@ -197,6 +197,44 @@ def test_two_samples_per_pixel(world, ctx):
     assert np.array_equal(one, want), _differ(one, want)
 
 
+@pytest.mark.parametrize("what, index", [("depth limit 0", 9), ("no samples", 10)])
+def test_a_degenerate_launch(world, ctx, what, index):
+    """A launch that traces nothing (depth limit 0, or a sample count of 0) still takes every pixel of every frame and stores it, black: every lane
+    with a pixel stores in its first phase -- the densest merge the kernel can produce, a whole wave of the frames of one or two pixels at once.  The
+    stores add zeros, so they are made on top of one ordinary frame: the accumulator of a batch of 20 is that of 20 launches of one frame, which is
+    that frame's, with either order, in the lean and in the counting build -- and the counting build's samples say that the pixels were taken."""
+    _load(world, "hf")
+    st, bg = world["st"]["hf"], world["bg"]["hf"]
+    nothing = np.array(st, np.float32).copy()
+    nothing[index] = 0
+
+    def run(B, launches, order, counting):
+        ctx.set_option("sample_order", order)
+        ctx.set_option("batch_frames", 1)
+        ctx.accum_reset(W, H)
+        ctx.render_accumulate(st, W, H, bg, SEED, STRIDE, 1)
+        ctx.set_option("batch_frames", B)
+        ctx.enable_counters(counting)
+        ctx.stats_reset()
+        for k in range(launches):
+            ctx.render_accumulate(nothing, W, H, bg, SEED + STRIDE * (1 + k * B), STRIDE, B)
+        s = ctx.stats()
+        ctx.enable_counters(False)
+        assert s["launches"] == launches, (what, B, order, s["launches"])
+        if counting:
+            assert s["samples"] == W * H * 20 and s["rays"] == 0, (what, B, order, s["samples"], s["rays"])
+        return ctx.accum_read().copy()
+
+    frame = _singles(world, "hf", st)[1]
+    assert frame.any()
+    for counting in (False, True):
+        want = run(1, 20, 1, counting)
+        assert np.array_equal(want, frame), "%s: 20 launches of one frame changed the accumulator: %s" % (what, _differ(want, frame))
+        for order in (0, 1):
+            got = run(20, 1, order, counting)
+            assert np.array_equal(got, want), "%s, order %d, counting %s: %s" % (what, order, counting, _differ(got, want))
+
+
 def test_pixel_cost_is_indexed_by_the_pixel(world, ctx):
     """A pixel's recorded cost is the node steps of one of its frames (the frames of a launch write the same word: the last one stays).  After a launch
     of three frames with order 1 every word is the cost the same pixel has in a single launch of one of the three, and it is zero exactly on the
