@@ -11,6 +11,7 @@ The Python surface mirrors the reference's host flow (kernel.cu main(), K:2021-2
     ctx.render_frame(settings13, ...)  ~ CudaStarter(outputr, ..., divisor) (K:2562)
     ProgressiveRenderer             ~ the present loop's preview ladder + accumulation (K:2154-2224)
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -428,37 +429,40 @@ def read_pfm(path):
     return np.ascontiguousarray(a[::-1])
 
 
-def denoise_params(**params):
-    """A DrDenoiseParams: the library's defaults (dr_denoise_defaults) with the given fields replaced."""
-    p = DrDenoiseParams()
-    _check(lib().dr_denoise_defaults(C.byref(p)))
-    for k, v in params.items():
-        if k not in dict(DrDenoiseParams._fields_):
-            raise TypeError("unknown denoise parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrDenoiseParams._fields_)))
+def _params(struct, defaults_fn, what, **fields):
+    """A parameter struct: the library's defaults (defaults_fn) with the given fields replaced."""
+    p = struct()
+    _check(getattr(lib(), defaults_fn)(C.byref(p)))
+    for k, v in fields.items():
+        if k not in dict(struct._fields_):
+            raise TypeError("unknown %s parameter %r (known: %s)" % (what, k, ", ".join(f[0] for f in struct._fields_)))
         setattr(p, k, v)
     return p
+
+
+def denoise_params(**params):
+    """A DrDenoiseParams: the library's defaults (dr_denoise_defaults) with the given fields replaced."""
+    return _params(DrDenoiseParams, "dr_denoise_defaults", "denoise", **params)
 
 
 def upscale_params(**params):
     """A DrUpscaleParams: the library's defaults (dr_upscale_defaults) with the given fields replaced."""
-    p = DrUpscaleParams()
-    _check(lib().dr_upscale_defaults(C.byref(p)))
-    for k, v in params.items():
-        if k not in dict(DrUpscaleParams._fields_):
-            raise TypeError("unknown upscale parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrUpscaleParams._fields_)))
-        setattr(p, k, v)
-    return p
+    return _params(DrUpscaleParams, "dr_upscale_defaults", "upscale", **params)
 
 
 def reproject_params(**params):
     """A DrReprojectParams: the library's defaults (dr_reproject_defaults) with the given fields replaced."""
-    p = DrReprojectParams()
-    _check(lib().dr_reproject_defaults(C.byref(p)))
-    for k, v in params.items():
-        if k not in dict(DrReprojectParams._fields_):
-            raise TypeError("unknown reproject parameter %r (known: %s)" % (k, ", ".join(f[0] for f in DrReprojectParams._fields_)))
-        setattr(p, k, v)
-    return p
+    return _params(DrReprojectParams, "dr_reproject_defaults", "reproject", **params)
+
+
+def _out_array(shape, dtype, dev=None):
+    """An output of this shape and numpy dtype -- a numpy array, or on dev a torch tensor -- and its address."""
+    if dev is None:
+        a = np.empty(shape, dtype=dtype)
+        return a, a.ctypes.data
+    import torch
+    a = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+    return a, a.data_ptr()
 
 
 def pack_settings13(s, divisor, spp=None, depth=None):
@@ -668,6 +672,38 @@ class Context:
         _check(lib().dr_context_stream(self._h, C.byref(p)))
         return p.value or 0
 
+    @contextlib.contextmanager
+    def _torch_handshake(self):
+        """The stream handshake of a call that reads or writes torch tensors, around the call: yields the torch device of this context's GPU; the
+        library's stream waits for torch's current stream first, torch's current stream waits for the library's afterwards."""
+        import torch
+        dev = self._torch_device()
+        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
+        cur = torch.cuda.current_stream(dev)
+        lib_stream.wait_stream(cur)
+        yield dev
+        cur.wait_stream(lib_stream)
+
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+
+    def _plane_read(self, read_fn, shape, dtype):
+        """One of the accumulator's planes on the host: read_fn = dr_accum_read, dr_accum_history_read or dr_accum_moments_read."""
+        out = np.empty(shape, dtype=dtype)
+        _check(getattr(lib(), read_fn)(self._h, _p(out)))
+        return out
+
+    def _sized_read(self, stats_fn, dtype, items=lambda n: n):
+        """An array the library sizes (dr_stats_cert_mask and its like): asked for its n first, then read into items(n) elements."""
+        n = C.c_int()
+        fn = getattr(lib(), stats_fn)
+        _check(fn(self._h, None, 0, C.byref(n)))
+        out = np.zeros(items(n.value), dtype=dtype)
+        if len(out):
+            _check(fn(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
+        return out
+
     def accum_pack_stripe(self, slot):
         """Queues the packing of this context's stripe into library buffer `slot` (0/1); returns (device pointer, bytes)."""
         p, n = _VP(), C.c_uint64()
@@ -679,9 +715,7 @@ class Context:
                                              C.c_void_p(stream_ptr) if stream_ptr else None))
 
     def accum_read(self):
-        out = np.empty(self._acc_shape, dtype=np.int32)
-        _check(lib().dr_accum_read(self._h, _p(out)))
-        return out
+        return self._plane_read("dr_accum_read", self._acc_shape, np.int32)
 
     def accum_present(self, divide_by):
         """uint8[H, W, 3] row-major image: clamp(acc / divide_by, 0, 255) (K:2287)."""
@@ -715,32 +749,17 @@ class Context:
     def cert_mask(self):
         """uint32 words of the last certified view's tile mask (dr_stats_cert_mask; bit set = the tile's camera rays keep the scene's margin),
         or an empty array when no certificate is in use."""
-        n = C.c_int()
-        _check(lib().dr_stats_cert_mask(self._h, None, 0, C.byref(n)))
-        out = np.zeros((n.value + 31) // 32, dtype=np.uint32)
-        if len(out):
-            _check(lib().dr_stats_cert_mask(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
-        return out
+        return self._sized_read("dr_stats_cert_mask", np.uint32, lambda n: (n + 31) // 32)
 
     def cert_levels(self):
         """uint8 grades of the last certified view's tiles (dr_stats_cert_levels; 0 = the tile's camera rays keep the scene's margin, g >= 1 = they
         carry the margin of step g - 1 of the certificate's ladder), or an empty array when no certificate is in use."""
-        n = C.c_int()
-        _check(lib().dr_stats_cert_levels(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=np.uint8)
-        if len(out):
-            _check(lib().dr_stats_cert_levels(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
-        return out
+        return self._sized_read("dr_stats_cert_levels", np.uint8)
 
     def camera_entry(self):
         """int32 entry codes of the last certified view's tiles (dr_stats_camera_entry; wide record << 1 | is-leaf at which the tile's camera rays start,
         0 = the root, -1 = nothing can be seen from the tile), or an empty array when no table is in use."""
-        n = C.c_int()
-        _check(lib().dr_stats_camera_entry(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=np.int32)
-        if len(out):
-            _check(lib().dr_stats_camera_entry(self._h, out.ctypes.data_as(_VP), len(out), C.byref(n)))
-        return out
+        return self._sized_read("dr_stats_camera_entry", np.int32)
 
     def sky_tiles(self):
         """(sky tiles, geometry tiles) of the last launch (dr_stats_sky_tiles): the tiles rendered without a walk (by sky_tiles_kernel, or by the persistent kernel's
@@ -838,23 +857,12 @@ class Context:
                 raise ValueError("unknown AOV channel %r (known: %s)" % (k, ", ".join(ALL)))
         shape = lambda k: (max(h, 0), max(w, 0)) + ((AOV_CHANNELS[k][1],) if AOV_CHANNELS[k][1] > 1 else ())
         bufs = DrAovBuffers()
-        if not device:
-            out = {k: np.empty(shape(k), dtype=AOV_CHANNELS[k][0]) for k in channels}
-            for k, a in out.items():
-                setattr(bufs, k, a.ctypes.data)
-            _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 0))
-            return out
-        import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty(shape(k), dtype=tdt[AOV_CHANNELS[k][0]], device=dev) for k in channels}
-        for k, a in out.items():
-            setattr(bufs, k, a.data_ptr())
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 1))
-        cur.wait_stream(lib_stream)
+        out = {}
+        with (self._torch_handshake() if device else contextlib.nullcontext()) as dev:
+            for k in channels:
+                out[k], address = _out_array(shape(k), AOV_CHANNELS[k][0], dev)
+                setattr(bufs, k, address)
+            _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 1 if device else 0))
         return out
 
     # ---- queries on the caller's lists (trace, radiance, trace_all, nearest): what they share
@@ -894,7 +902,7 @@ class Context:
         if not all(is_torch):
             raise TypeError("%s and %s must %s be numpy arrays or %s torch tensors" % ((", ".join(names[:-1]), names[-1]) + (("both",) * 2 if len(names) == 2 else ("all",) * 2)))
         import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        dev = self._torch_device()
         for name, a, _, _, tname in inputs:
             if a is None:
                 continue
@@ -907,13 +915,9 @@ class Context:
         n = None
         for group in groups:
             n = shapes_of(group, [g[1] for g in group], n)
-        tdt = {np.float32: torch.float32, np.int32: torch.int32}
-        out = {k: torch.empty((n,) + tuple(tail), dtype=tdt[dt], device=dev) for k, (dt, tail) in out_spec.items()}
-        lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-        cur = torch.cuda.current_stream(dev)
-        lib_stream.wait_stream(cur)
-        call({name: (a.data_ptr() if a is not None else None) for name, a, _, _, _ in inputs}, {k: a.data_ptr() for k, a in out.items()}, n, 1)
-        cur.wait_stream(lib_stream)
+        with self._torch_handshake():
+            out = {k: _out_array((n,) + tuple(tail), dt, dev)[0] for k, (dt, tail) in out_spec.items()}
+            call({name: (a.data_ptr() if a is not None else None) for name, a, _, _, _ in inputs}, {k: a.data_ptr() for k, a in out.items()}, n, 1)
         return out
 
     # ---- ray queries (dr_trace_rays)
@@ -1107,28 +1111,25 @@ class Context:
         accum_present's layout: out="rgb8" -> uint8[H, W, 3], "f32" -> float32[H, W, 3] (0..255 units, unclamped), "both" -> (rgb8, f32).
         params: the fields of dr_denoise_params (iterations, sigma_luminance, normal_power_log2, sigma_depth, demodulate, material_stop), the
         rest at their defaults.  device=True: torch tensors on this context's GPU, with render_aov's stream handshake."""
+        def prepare():
+            p = denoise_params(**params)
+            return lambda st, f, rgb, dp: lib().dr_accum_denoise(self._h, st, W, H, int(divide_by), C.byref(p), f, rgb, dp)
+        return self._image_stage(settings13, W, H, out, device, prepare)
+
+    def _image_stage(self, settings13, W, H, out, device, prepare):
+        """What denoise and upscale share: the settings and `out` judged, then the stage's own parameters (prepare() judges them and returns call),
+        the images allocated (numpy, or torch on this context's GPU inside the stream handshake) and call(settings13's address, f32's or None,
+        rgb8's or None, device_pointers) -> the C call's status."""
         st = _f32(settings13)
         assert st.shape == (13,)
         if out not in ("rgb8", "f32", "both"):
             raise ValueError("out must be 'rgb8', 'f32' or 'both', not %r" % (out,))
-        p = denoise_params(**params)
-        want_rgb, want_f32 = out in ("rgb8", "both"), out in ("f32", "both")
-        if not device:
-            rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
-            f = np.empty((H, W, 3), np.float32) if want_f32 else None
-            _check(lib().dr_accum_denoise(self._h, _p(st), W, H, int(divide_by), C.byref(p), _p(f) if f is not None else None,
-                                          _p(rgb) if rgb is not None else None, 0))
-        else:
-            import torch
-            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-            rgb = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev) if want_rgb else None
-            f = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev) if want_f32 else None
-            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-            cur = torch.cuda.current_stream(dev)
-            lib_stream.wait_stream(cur)
-            _check(lib().dr_accum_denoise(self._h, _p(st), W, H, int(divide_by), C.byref(p), f.data_ptr() if f is not None else None,
-                                          rgb.data_ptr() if rgb is not None else None, 1))
-            cur.wait_stream(lib_stream)
+        call = prepare()
+        shape = (max(H, 0), max(W, 0), 3) if device else (H, W, 3)      # (a size below 0: numpy refuses it here, behind torch the library does)
+        with (self._torch_handshake() if device else contextlib.nullcontext()) as dev:
+            rgb, rgb_at = _out_array(shape, np.uint8, dev) if out in ("rgb8", "both") else (None, None)
+            f, f_at = _out_array(shape, np.float32, dev) if out in ("f32", "both") else (None, None)
+            _check(call(_p(st), f_at, rgb_at, 1 if device else 0))
         return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
 
     # ---- upsampler (dr_accum_upscale)
@@ -1139,34 +1140,15 @@ class Context:
         material_stop), the rest at their defaults.  prefilter: None, True (the denoiser's defaults, demodulate as here) or a dict of
         dr_denoise_params fields -- the a-trous filter then runs on the low grid first.  device=True: torch tensors on this context's GPU, with
         render_aov's stream handshake."""
-        st = _f32(settings13)
-        assert st.shape == (13,)
-        if out not in ("rgb8", "f32", "both"):
-            raise ValueError("out must be 'rgb8', 'f32' or 'both', not %r" % (out,))
-        p = upscale_params(**params)
-        pre = None
-        if prefilter is not None and prefilter is not False:
-            d = {} if prefilter is True else dict(prefilter)
-            d.setdefault("demodulate", p.demodulate)
-            pre = C.byref(denoise_params(**d))
-        want_rgb, want_f32 = out in ("rgb8", "both"), out in ("f32", "both")
-        if not device:
-            rgb = np.empty((H, W, 3), np.uint8) if want_rgb else None
-            f = np.empty((H, W, 3), np.float32) if want_f32 else None
-            _check(lib().dr_accum_upscale(self._h, _p(st), W, H, int(divide_by), C.byref(p), pre, _p(f) if f is not None else None,
-                                          _p(rgb) if rgb is not None else None, 0))
-        else:
-            import torch
-            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-            rgb = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev) if want_rgb else None
-            f = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev) if want_f32 else None
-            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-            cur = torch.cuda.current_stream(dev)
-            lib_stream.wait_stream(cur)
-            _check(lib().dr_accum_upscale(self._h, _p(st), W, H, int(divide_by), C.byref(p), pre, f.data_ptr() if f is not None else None,
-                                          rgb.data_ptr() if rgb is not None else None, 1))
-            cur.wait_stream(lib_stream)
-        return rgb if out == "rgb8" else (f if out == "f32" else (rgb, f))
+        def prepare():
+            p = upscale_params(**params)
+            pre = None
+            if prefilter is not None and prefilter is not False:
+                d = {} if prefilter is True else dict(prefilter)
+                d.setdefault("demodulate", p.demodulate)
+                pre = C.byref(denoise_params(**d))
+            return lambda st, f, rgb, dp: lib().dr_accum_upscale(self._h, st, W, H, int(divide_by), C.byref(p), pre, f, rgb, dp)
+        return self._image_stage(settings13, W, H, out, device, prepare)
 
     # ---- temporal reprojection (dr_accum_reproject)
     def reproject(self, from_settings13, to_settings13, W, H, frames, **params):
@@ -1185,19 +1167,13 @@ class Context:
     def accum_history(self):
         """int32[W, H] indexed [x, y]: the samples each pixel of the accumulator carries in addition to the frames added since the last
         reproject (all zeros when there is no history plane)."""
-        W, H, _ = self._acc_shape
-        out = np.empty((W, H), dtype=np.int32)
-        _check(lib().dr_accum_history_read(self._h, _p(out)))
-        return out
+        return self._plane_read("dr_accum_history_read", self._acc_shape[:2], np.int32)
 
     # ---- second moments (option "moments", dr_accum_error)
     def accum_moments(self):
         """uint64[W, H] indexed [x, y]: the second-moment plane, the sum over the frames folded into the accumulator of their capped luma x 256,
         squared (all zeros when there is no plane: set_option("moments", 1) before accum_reset)."""
-        W, H, _ = self._acc_shape
-        out = np.empty((W, H), dtype=np.uint64)
-        _check(lib().dr_accum_moments_read(self._h, _p(out)))
-        return out
+        return self._plane_read("dr_accum_moments_read", self._acc_shape[:2], np.uint64)
 
     def error(self, settings13, W, H, divide_by, tolerance, sigma=False, device=False):
         """The noise estimate of the accumulator (include/dogeray_amd.h dr_accum_error): a dict with the fields of dr_error_result -- pixels,
@@ -1207,21 +1183,10 @@ class Context:
         st = _f32(settings13)
         assert st.shape == (13,)
         r = DrErrorResult()
-        plane = None
-        if not sigma:
-            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), None, C.byref(r), 0))
-        elif not device:
-            plane = np.empty((max(H, 0), max(W, 0)), np.float32)
-            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), _p(plane), C.byref(r), 0))
-        else:
-            import torch
-            dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-            plane = torch.empty((max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
-            lib_stream = torch.cuda.ExternalStream(self.stream_ptr(), device=dev)
-            cur = torch.cuda.current_stream(dev)
-            lib_stream.wait_stream(cur)
-            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), plane.data_ptr(), C.byref(r), 1))
-            cur.wait_stream(lib_stream)
+        device = bool(sigma and device)
+        with (self._torch_handshake() if device else contextlib.nullcontext()) as dev:
+            plane, plane_at = _out_array((max(H, 0), max(W, 0)), np.float32, dev) if sigma else (None, None)
+            _check(lib().dr_accum_error(self._h, _p(st), W, H, int(divide_by), float(tolerance), plane_at, C.byref(r), 1 if device else 0))
         d = r.as_dict()
         if sigma:
             d["sigma"] = plane

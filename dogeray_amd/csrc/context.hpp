@@ -89,6 +89,33 @@ struct GuideKey {
   }
 };
 
+// A set of first-hit guide planes over a grid of n pixels, in one allocation, and the key of the view traced into them.  In floats:
+//   quad(0) 4n | ... | quad(quads - 1) 4n | rgb 3n | material n | scalar n
+// the float4 planes first (hipMalloc's alignment, and n is a multiple of 64: every one of them is 16-byte aligned).  The denoiser's set has three
+// float4 planes -- the guide (n, z), then the colour planes A and B --, the upsampler's full-resolution set two -- the guide and a scratch --; rgb is
+// the albedo and scalar the depth gradient gz.  Plane 1 is where trace_guides (context_accum.cpp) has launch_aov write normal and depth before the
+// guide prepare packs them.  A set of dr_accum_reproject's pair has no float4 plane, and its scalar, t, comes first:
+//   scalar n | rgb 3n | material n          (rgb is the normal)
+// The casts live here only.
+struct GuidePlanes {
+  DevMem<float> mem;
+  GuideKey key;
+  size_t n = 0;
+  int quads = 0;
+  // room for `pixels` x (4 float4_planes + 5) floats; growing loses the contents, so the key no longer holds
+  int grow(size_t pixels, int float4_planes, hipStream_t stream) {
+    const size_t need = pixels * (size_t)(4 * float4_planes + 5);
+    if (need > mem.n) key.valid = false;
+    DR_TRY(mem.grow(need, stream));
+    n = pixels; quads = float4_planes;
+    return DR_OK;
+  }
+  float* quad(int k) const { return mem.p + 4 * n * (size_t)k; }
+  float* rgb() const { return quad(quads) + (quads ? 0 : n); }
+  int32_t* material() const { return reinterpret_cast<int32_t*>(rgb() + 3 * n); }
+  float* scalar() const { return quads ? rgb() + 4 * n : mem.p; }
+};
+
 // Where a render launch goes and what it may touch on the way
 struct LaunchSite {
   hipStream_t stream;       // the launch, the tile counters' memset, the certificate mask and the feedback kernels
@@ -126,49 +153,43 @@ struct dr_context {
   int n_prims = 0, n_tex = 0, tree_depth = 0;
   std::vector<int> slot_to_orig;
   DevMem<int32_t> slot_to_orig_dev;        // the same map on the device: uploaded by the first call that reads it after a scene upload (ensure_slot_to_orig)
-  // dr_render_aov with host pointers: the channels are written here, then downloaded
-  DevMem<uint8_t> aov_staging;
   // the queries on caller lists (dr_trace_rays, dr_trace_radiance, dr_query_nearest, dr_trace_all_hits; context_query.cpp): the staging of host inputs
-  // and results, the two words per entry between a walk kernel and its surface / finishing pass ({t or d2 bits, slot}), and the persistent kernels'
-  // cursor -- each made by the first call that needs it (a context that never queries allocates nothing).  One of each serves every query: they are
-  // used on `stream` only, one call's work queued behind the other's, and DevMem::grow drains `stream` before it frees what is too small, so no
-  // kernel of an earlier device-pointer call still reads what a later call replaces
+  // and results -- and of the host outputs of the accumulator's stages (dr_render_aov, dr_accum_denoise / _upscale / _error / _present) --, the
+  // two words per entry between a walk kernel and its surface / finishing pass ({t or d2 bits, slot}), and the persistent kernels' cursor -- each
+  // made by the first call that needs it (a context that never queries allocates nothing).  One of each serves every query: they are used on
+  // `stream` only, one call's work queued behind the other's, and DevMem::grow drains `stream` before it frees what is too small, so no kernel of
+  // an earlier device-pointer call still reads what a later call replaces
   DevMem<uint8_t> query_staging;
   DevMem<uint32_t> query_scratch;
   DevMem<unsigned> query_cursor;
   // options (private, for the tests): 0 the plan decides (launch_plan.hpp), 1 the one-ray-per-lane kernel, 2 the persistent kernel where it exists
   int trace_kernel = 0, radiance_kernel = 0, allhits_kernel = 0;
   float near_lmax = 0;                     // dr_query_nearest: the scene's largest |e1| + |e2| / radius (the pruning slack's constant, device_nearest.hpp)
-  // dr_accum_denoise: one allocation (made by the first call) carved into the guide planes and the two colour planes of the pixel grid, the cached
-  // guides' key (settings13, W, H, scene generation), and the staging of host outputs
-  DevMem<float> dn_planes;
-  dr::GuideKey dn_key;
-  DevMem<uint8_t> dn_staging;
-  // dr_accum_upscale: the full-resolution guides (one allocation made by the first guided call: guide 4n | scratch 4n | albedo 3n | material n |
-  // gz n floats over the full pixel grid), their key (settings13 with element 11 = 1, W, H, scene generation) and the AOV passes of the last call
-  DevMem<float> up_planes;
-  dr::GuideKey up_key;
+  // dr_accum_denoise: the guide planes and the two colour planes of the pixel grid (made by the first call), keyed by the view they were traced
+  // for (settings13, W, H, scene generation)
+  dr::GuidePlanes dn_guides;
+  // dr_accum_upscale: the full-resolution guides (made by the first guided call), keyed by settings13 with element 11 = 1, W, H, scene generation,
+  // and the AOV passes of the last call
+  dr::GuidePlanes up_guides;
   int up_passes = 0;
   uint64_t scene_gen = 0;                  // scene uploads so far: a guide cache of an earlier scene does not match
   // dr_accum_reproject: the second accumulator of the pair (swapped with `accum` by every reprojection), the two history planes (hist: the
   // current one, null until the first reprojection and after dr_accum_reset), the guide planes of two views (t n | normal 3n | material n
-  // floats each; set rp_cur holds the cached `to` view, keyed like the denoiser's guides), the class counts and the AOV passes of the last call
+  // floats each; set rp_cur holds the cached `to` view under its key, the other set's key is never valid), the class counts and the AOV passes of
+  // the last call
   DevMem<int32_t> accum2;
   DevMem<int32_t> hist_buf[2];
   int32_t* hist = nullptr; int hist_cur = 0;
-  DevMem<float> rp_planes[2];
-  dr::GuideKey rp_key; int rp_cur = 0;
+  dr::GuidePlanes rp_guides[2]; int rp_cur = 0;
   DevMem<unsigned long long> rp_counts;
   int rp_passes = 0;
   // the second-moment plane (option "moments", read by dr_accum_reset): m2 is the current plane (null: none), one of m2_buf -- the second one
-  // appears with the first reprojection, as for the history; the allocations outlive resets of the same size.  dr_accum_error's counts and the
-  // staging of its host output
+  // appears with the first reprojection, as for the history; the allocations outlive resets of the same size.  dr_accum_error's counts
   int moments_opt = 0;                     // option: dr_accum_reset gives the accumulator a plane
   int denoise_variance = 0;                // option: the denoiser's variance pre-pass takes the temporal variance from the plane (n >= 4)
   DevMem<unsigned long long> m2_buf[2];
   unsigned long long* m2 = nullptr; int m2_cur = 0;
   DevMem<unsigned long long> err_counts;
-  DevMem<float> err_staging;
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
   // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
   // and one byte per tile (its grade on the ladder of option cert_levels: what the render kernel reads), computed on the launch's stream by
@@ -207,7 +228,6 @@ struct dr_context {
   // frame + accumulator
   DevMem<int32_t> frame;
   DevMem<int32_t> accum; int accW = 0, accH = 0;
-  DevMem<uint8_t> present;
   // multi-GPU gather: two packed copies of this context's stripe (double buffer), sized for the accumulator
   DevMem<int32_t> packed[2];
   DevMem<unsigned long long> counters;
@@ -304,10 +324,12 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
 // context_pipeline.cpp
 int join_pipeline(dr_context* c);
 int pipeline_flush(dr_context* c);
-// context_query.cpp: a list of n caller items through the device and back
+// context_query.cpp: a list of n caller items through the device and back; an accumulator stage's host outputs are the channels of a list of pixels
+// without inputs
 struct QueryIn { const void* p; int words; };                 // a caller's input array (null: not given) and its 4-byte words per item
-struct QueryOut { void* p; int words; bool per_item; };       // a channel (null: not wanted), its 4-byte words per entry; per_item: one entry per item whatever K
-constexpr int QUERY_MAX_IN = 4, QUERY_MAX_OUT = 8;
+// a channel (null: not wanted), its words per entry, each of `unit` bytes (rgb8: 3 words of 1); per_item: one entry per item whatever K
+struct QueryOut { void* p; int words; bool per_item; int unit = 4; };
+constexpr int QUERY_MAX_IN = 4, QUERY_MAX_OUT = 9;
 struct QueryIo {
   const void* in[QUERY_MAX_IN];            // where the kernels read input k (null: not given) ...
   void* out[QUERY_MAX_OUT];                // ... and write channel k (null: not wanted): the caller's memory, or staging

@@ -1,5 +1,7 @@
 // The accumulator and what is computed from it on the device: reset, first-hit AOVs, the denoiser, the upscaler, temporal reprojection, the noise
-// estimate, present, the stripe copies of the multi-GPU gather, reads and device pointers.
+// estimate, present, the stripe copies of the multi-GPU gather, reads and device pointers.  A stage's entry checks what needs the context, has its
+// call judged and its launch struct filled by params_host.hpp's judge_* (the host build runs the same judges), adds the pointers -- guides from a
+// GuidePlanes set (context.hpp), host outputs staged as a query's channels (context_query.cpp) -- and launches.
 #include <utility>
 
 #include "context.hpp"
@@ -32,49 +34,48 @@ int accum_matches(const dr_context* c, const char* who, int W, int H) {
   return DR_OK;
 }
 
-// Traces the guides of view P over its gw x gh pixel grid: launch_aov writes normal and depth into `scratch` (3n + n floats), albedo and
-// material into their planes; the guide prepare packs (n, z) into `guide` and forms gz from them
-int trace_guides(dr_context* c, const RenderParams& P, int traversal, float focus, int gw, int gh, float* scratch, float* albedo, int32_t* mat,
-                 float* guide, float* gz) {
-  const size_t n = (size_t)gw * (size_t)gh;
+// A launch_aov over the window (x0, y0, w, h) of a view's pixel grid, no channel wanted yet
+AovLaunch aov_launch(const dr_context* c, float focus, int x0, int y0, int w, int h) {
   AovLaunch A;
   memset(&A, 0, sizeof(A));
-  A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
+  A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
   A.focus = focus;
   A.slot_to_orig = c->slot_to_orig_dev;
-  A.normal = scratch; A.depth = scratch + 3 * n; A.albedo = albedo; A.material = mat;
+  return A;
+}
+
+// The guides of view P (of settings13) over its gw x gh > 0 pixel grid in G, a set of `quads` float4 planes: traced unless G holds them already
+// (*passes then counts the pass).  launch_aov writes normal and depth into float4 plane 1 (3n + n floats), albedo and material into their planes;
+// the guide prepare packs (n, z) into plane 0 and forms gz from them
+int trace_guides(dr_context* c, GuidePlanes& G, int quads, const float settings13[13], int W, int H, const RenderParams& P, int traversal, int* passes) {
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  DR_TRY(G.grow((size_t)gw * (size_t)gh, quads, c->stream));
+  if (G.key.matches(settings13, W, H, c->scene_gen)) return DR_OK;
+  AovLaunch A = aov_launch(c, settings13[7], 0, 0, gw, gh);
+  A.normal = G.quad(1); A.depth = G.quad(1) + 3 * G.n; A.albedo = G.rgb(); A.material = G.material();
   launch_aov(c->stream, P, traversal, A);
   HIP_TRY(hipGetLastError());
-  DnLaunch G;
-  memset(&G, 0, sizeof(G));
-  G.gw = gw; G.gh = gh;
-  G.normal = scratch; G.depth = scratch + 3 * n; G.mat = mat; G.guide = guide; G.gz = gz;
-  launch_denoise_guides(c->stream, G);
+  DnLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = gw; L.gh = gh;
+  L.normal = A.normal; L.depth = A.depth; L.mat = A.material; L.guide = G.quad(0); L.gz = G.scalar();
+  launch_denoise_guides(c->stream, L);
   HIP_TRY(hipGetLastError());
+  G.key.store(settings13, W, H, c->scene_gen);
+  if (passes) ++*passes;
   return DR_OK;
 }
 
-// The low side of dr_accum_denoise and dr_accum_upscale over the pixel grid of settings13 (L.gw x L.gh > 0; L.D, L.acc, L.hist, L.m2 set by the
-// caller): the planes (allocated by the first call), the cached guides (traced when the key differs; *aov_passes counts that pass), colour stage 0
-// and -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  On return L.src is the plane of the result: (e, l) after stage 0,
-// (e, var) after the last pass; L.guide, L.albedo, L.mat and L.gz are the guides.
-int denoise_low_side(dr_context* c, const float settings13[13], int W, int H, const RenderParams& P, int traversal, DnLaunch& L, bool filter, int* aov_passes) {
-  const size_t n = (size_t)L.gw * (size_t)L.gh;
-  // planes, in floats: guide 4n | colour A 4n | colour B 4n | albedo 3n | material n | gz n (the float4 planes first: 16-byte aligned, n % 8 == 0)
-  if (17 * n > c->dn_planes.n) c->dn_key.valid = false;
-  DR_TRY(c->dn_planes.grow(17 * n, c->stream));
-  float* const guide = c->dn_planes;
-  float* const pa = guide + 4 * n;
-  float* const pb = pa + 4 * n;
-  float* const albedo = pb + 4 * n;
-  int32_t* const mat = reinterpret_cast<int32_t*>(albedo + 3 * n);
-  float* const gz = reinterpret_cast<float*>(mat + n);
-  L.albedo = albedo; L.mat = mat; L.guide = guide; L.gz = gz;
-  if (!c->dn_key.matches(settings13, W, H, c->scene_gen)) {
-    DR_TRY(trace_guides(c, P, traversal, settings13[7], L.gw, L.gh, pa, albedo, mat, guide, gz));      // (colour plane A is the scratch)
-    c->dn_key.store(settings13, W, H, c->scene_gen);
-    if (aov_passes) ++*aov_passes;
-  }
+// The low side of dr_accum_denoise and dr_accum_upscale over the pixel grid of settings13 (L as its judge filled it, L.gw x L.gh > 0, with the
+// accumulator's planes L.acc, L.hist, L.m2): the planes (allocated by the first call; colour plane A doubles as the trace's scratch), the cached
+// guides (*aov_passes counts a trace), colour stage 0 and -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  On return
+// L.src is the plane of the result: (e, l) after stage 0, (e, var) after the last pass; L.guide, L.albedo, L.mat and L.gz are the guides.
+int denoise_low_side(dr_context* c, const float settings13[13], const RenderParams& P, int traversal, DnLaunch& L, bool filter, int* aov_passes) {
+  GuidePlanes& G = c->dn_guides;
+  DR_TRY(trace_guides(c, G, 3, settings13, L.W, L.H, P, traversal, aov_passes));
+  float* const pa = G.quad(1);
+  float* const pb = G.quad(2);
+  L.albedo = G.rgb(); L.mat = G.material(); L.guide = G.quad(0); L.gz = G.scalar();
   L.dst = pa;
   launch_denoise_colour(c->stream, L, 0);                 // acc -> (e, l) in A
   L.src = pa; L.dst = pb;
@@ -91,20 +92,44 @@ int denoise_low_side(dr_context* c, const float settings13[13], int W, int H, co
   return DR_OK;
 }
 
-// Where the W x H outputs of dr_accum_denoise / dr_accum_upscale are written: the caller's device buffers, or the staging they are downloaded from
-int output_staging(dr_context* c, size_t npix, float* out_f32, uint8_t* out_rgb8, int device_pointers, float*& f32_dev, uint8_t*& rgb_dev) {
-  f32_dev = out_f32;
-  rgb_dev = out_rgb8;
-  if (device_pointers) return DR_OK;
-  DR_TRY(c->dn_staging.grow((out_f32 ? npix * 3 * sizeof(float) : 0) + (out_rgb8 ? npix * 3 : 0), c->stream));
-  f32_dev = out_f32 ? reinterpret_cast<float*>(c->dn_staging.p) : nullptr;
-  rgb_dev = out_rgb8 ? c->dn_staging + (out_f32 ? npix * 3 * sizeof(float) : 0) : nullptr;
+// The W x H x 3 image a stage hands out as floats, as bytes or as both: the channels of query_begin / query_end (context_query.cpp) over the pixels
+struct ImageOut {
+  QueryOut ch[2];
+  QueryIo io;
+  ImageOut(float* out_f32, uint8_t* out_rgb8) : ch{{out_f32, 3, true}, {out_rgb8, 3, true, 1}} {}
+  int begin(dr_context* c, int W, int H, int device_pointers) { return query_begin(c, (size_t)W * (size_t)H, 1, nullptr, 0, ch, 2, device_pointers != 0, io); }
+  float* f32() const { return (float*)io.out[0]; }
+  uint8_t* rgb8() const { return (uint8_t*)io.out[1]; }
+  int end(dr_context* c, int device_pointers) { return query_end(c, ch, 2, device_pointers != 0, io); }
+};
+
+// One of the accumulator's planes (the sums, the history, the second moments) and its bytes per pixel
+using PlaneOf = void* (*)(const dr_context*);
+void* sums_of(const dr_context* c) { return c->accum; }
+void* history_of(const dr_context* c) { return c->hist; }
+void* moments_of(const dr_context* c) { return c->m2; }
+
+// A plane read back behind the frames submitted before, or zeros where there is none (no history, no moments yet)
+int plane_read(dr_context* c, void* out, PlaneOf plane_of, size_t bytes_per_pixel) {
+  if (!c || !out || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
+  const void* const plane = plane_of(c);
+  const size_t bytes = (size_t)c->accW * c->accH * bytes_per_pixel;
+  if (!plane) { memset(out, 0, bytes); return DR_OK; }
+  HIP_TRY(hipMemcpyAsync(out, plane, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return DR_OK;
 }
-int output_download(dr_context* c, size_t npix, float* out_f32, uint8_t* out_rgb8, const float* f32_dev, const uint8_t* rgb_dev) {
-  if (out_f32) HIP_TRY(hipMemcpyAsync(out_f32, f32_dev, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, rgb_dev, npix * 3, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+
+// A plane's device address (null: there is none) and size.  The caller orders its own work on dr_context_stream(): the frames submitted before are
+// launched, and that stream waits for their adds
+int plane_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes, PlaneOf plane_of, size_t bytes_per_pixel) {
+  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
+  *dev_ptr = plane_of(c);
+  if (bytes) *bytes = *dev_ptr ? (uint64_t)c->accW * c->accH * bytes_per_pixel : 0;
   return DR_OK;
 }
 
@@ -150,35 +175,20 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
   }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
   DR_TRY(ensure_slot_to_orig(c));
-  AovLaunch A;
-  A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
-  A.focus = settings13[7];
-  A.slot_to_orig = c->slot_to_orig_dev;
-  // channel k: where the caller wants it, the device buffer it is written to, its words per pixel
-  void* const want[9] = {buffers->t, buffers->distance, buffers->depth, buffers->object, buffers->material, buffers->normal, buffers->uv, buffers->albedo, buffers->dir};
-  const int words[9] = {1, 1, 1, 1, 1, 3, 2, 3, 3};
-  void* dev[9] = {nullptr};
-  const size_t npix = (size_t)w * (size_t)h;
+  // the channels: where the caller wants each, its words per pixel
+  const QueryOut ch[9] = {{buffers->t, 1, true}, {buffers->distance, 1, true}, {buffers->depth, 1, true}, {buffers->object, 1, true}, {buffers->material, 1, true},
+                          {buffers->normal, 3, true}, {buffers->uv, 2, true}, {buffers->albedo, 3, true}, {buffers->dir, 3, true}};
   bool any = false;
-  if (device_pointers) {
-    for (int k = 0; k < 9; k++) { dev[k] = want[k]; any = any || want[k]; }
-  } else {
-    size_t bytes = 0;
-    for (int k = 0; k < 9; k++) if (want[k]) bytes += npix * (size_t)words[k] * 4;
-    if (bytes > 0) DR_TRY(c->aov_staging.grow(bytes, c->stream));
-    size_t off = 0;
-    for (int k = 0; k < 9; k++) if (want[k]) { dev[k] = c->aov_staging + off; off += npix * (size_t)words[k] * 4; any = true; }
-  }
+  for (int k = 0; k < 9; k++) any = any || ch[k].p;
   if (!any) return DR_OK;
-  A.t = (float*)dev[0]; A.distance = (float*)dev[1]; A.depth = (float*)dev[2]; A.object = (int32_t*)dev[3]; A.material = (int32_t*)dev[4];
-  A.normal = (float*)dev[5]; A.uv = (float*)dev[6]; A.albedo = (float*)dev[7]; A.dir = (float*)dev[8];
+  QueryIo io;
+  DR_TRY(query_begin(c, (size_t)w * (size_t)h, 1, nullptr, 0, ch, 9, device_pointers != 0, io));
+  AovLaunch A = aov_launch(c, settings13[7], x0, y0, w, h);
+  A.t = (float*)io.out[0]; A.distance = (float*)io.out[1]; A.depth = (float*)io.out[2]; A.object = (int32_t*)io.out[3]; A.material = (int32_t*)io.out[4];
+  A.normal = (float*)io.out[5]; A.uv = (float*)io.out[6]; A.albedo = (float*)io.out[7]; A.dir = (float*)io.out[8];
   launch_aov(c->stream, P, traversal, A);
   HIP_TRY(hipGetLastError());
-  if (device_pointers) return DR_OK;
-  for (int k = 0; k < 9; k++)
-    if (want[k]) HIP_TRY(hipMemcpyAsync(want[k], dev[k], npix * (size_t)words[k] * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
+  return query_end(c, ch, 9, device_pointers != 0, io);
 }
 
 int dr_denoise_defaults(dr_denoise_params* p) {
@@ -196,29 +206,21 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
   int traversal = 0;
   DR_TRY(aov_view(c, settings13, W, H, P, traversal));
   DR_TRY(accum_matches(c, "denoise", W, H));
-  if (divide_by < 1) { set_error("denoise: divide_by must be >= 1"); return DR_ERR_INVALID; }
-  const DnParams D = params ? dn_params(*params) : DN_DEFAULTS;
-  if (const char* why = check_denoise_params(D)) { set_error(std::string("denoise: ") + why); return DR_ERR_INVALID; }
+  DnLaunch L;
+  const std::string why = judge_denoise(P, divide_by, params, L);
+  if (!why.empty()) { set_error(why); return DR_ERR_INVALID; }
   if (!out_f32 && !out_rgb8) { set_error("denoise: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
-  const int gw = P.gx * 8, gh = P.gy * 8;
-  const size_t n = (size_t)gw * (size_t)gh, npix = (size_t)W * (size_t)H;
-  DnLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
-  L.D = D;
   L.acc = c->accum; L.hist = c->hist;
   L.m2 = c->denoise_variance ? c->m2 : nullptr;
-  if (D.iterations > 0 && n > 0) DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, true, nullptr));
-  float* f32_dev;
-  uint8_t* rgb_dev;
-  DR_TRY(output_staging(c, npix, out_f32, out_rgb8, device_pointers, f32_dev, rgb_dev));
-  L.out_f32 = f32_dev; L.out_rgb8 = rgb_dev;
+  if (L.D.iterations > 0 && L.gw > 0 && L.gh > 0) DR_TRY(denoise_low_side(c, settings13, P, traversal, L, true, nullptr));
+  ImageOut out(out_f32, out_rgb8);
+  DR_TRY(out.begin(c, W, H, device_pointers));
+  L.out_f32 = out.f32(); L.out_rgb8 = out.rgb8();
   launch_denoise_finish(c->stream, L);
   HIP_TRY(hipGetLastError());
-  if (device_pointers) return DR_OK;
-  return output_download(c, npix, out_f32, out_rgb8, f32_dev, rgb_dev);
+  return out.end(c, device_pointers);
 }
 
 int dr_upscale_defaults(dr_upscale_params* p) {
@@ -235,60 +237,33 @@ int dr_accum_upscale(dr_context* c, const float settings13[13], int W, int H, in
   int traversal = 0;
   DR_TRY(aov_view(c, settings13, W, H, P, traversal));
   float full13[13];                                        // the same view at full resolution
-  memcpy(full13, settings13, sizeof(full13));
-  full13[11] = 1.0f;
+  full_view13(settings13, full13);
   DR_TRY(aov_view(c, full13, W, H, PF, traversal));
   DR_TRY(accum_matches(c, "upscale", W, H));
-  if (divide_by < 1) { set_error("upscale: divide_by must be >= 1"); return DR_ERR_INVALID; }
-  const UpParams UP = params ? up_params(*params) : UP_DEFAULTS;
-  const DnParams PRE = prefilter ? dn_params(*prefilter) : DnParams{};
-  const DnParams* const pre = prefilter ? &PRE : nullptr;
-  const std::string why = check_upscale_params(UP, pre);
+  UpLaunch U;
+  DnLaunch L;                                              // the low side: the denoiser's planes; without a prefilter only the demodulated colour of stage 0
+  const std::string why = judge_upscale(P, PF, settings13, divide_by, params, prefilter, U, L);
   if (!why.empty()) { set_error(why); return DR_ERR_INVALID; }
   if (!out_f32 && !out_rgb8) { set_error("upscale: no output (both out_f32 and out_rgb8 are NULL)"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
-  const int gw = P.gx * 8, gh = P.gy * 8, FW = PF.gx * 8, FH = PF.gy * 8;
-  const size_t n = (size_t)gw * (size_t)gh, nf = (size_t)FW * (size_t)FH, npix = (size_t)W * (size_t)H;
-  UpLaunch U;
-  memset(&U, 0, sizeof(U));
-  U.gw = gw; U.gh = gh; U.FW = FW; U.FH = FH; U.W = W; U.H = H; U.div = n > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
-  U.U = UP;
   U.acc = c->accum; U.hist = c->hist;
   c->up_passes = 0;
-  if (UP.mode == UP_GUIDED && n > 0) {
-    // the low side: the denoiser's planes; without a prefilter only the demodulated colour of stage 0
-    DnLaunch L;
-    memset(&L, 0, sizeof(L));
-    L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by;
-    L.D = up_low_params(UP, pre);
+  if (U.U.mode == UP_GUIDED && U.gw > 0 && U.gh > 0) {
     L.acc = c->accum; L.hist = c->hist;
     L.m2 = c->denoise_variance ? c->m2 : nullptr;
-    DR_TRY(denoise_low_side(c, settings13, W, H, P, traversal, L, pre != nullptr, &c->up_passes));
+    DR_TRY(denoise_low_side(c, settings13, P, traversal, L, prefilter != nullptr, &c->up_passes));
     U.e = L.src; U.guide = L.guide; U.mat = L.mat;
-    // the full side: planes of its own (guide 4nf | scratch 4nf | albedo 3nf | material nf | gz nf floats), traced once per view
-    if (13 * nf > c->up_planes.n) c->up_key.valid = false;
-    DR_TRY(c->up_planes.grow(13 * nf, c->stream));
-    float* const fguide = c->up_planes;
-    float* const scratch = fguide + 4 * nf;
-    float* const falbedo = scratch + 4 * nf;
-    int32_t* const fmat = reinterpret_cast<int32_t*>(falbedo + 3 * nf);
-    float* const fgz = reinterpret_cast<float*>(fmat + nf);
-    if (!c->up_key.matches(full13, W, H, c->scene_gen)) {
-      DR_TRY(trace_guides(c, PF, traversal, full13[7], FW, FH, scratch, falbedo, fmat, fguide, fgz));
-      c->up_key.store(full13, W, H, c->scene_gen);
-      c->up_passes++;
-    }
-    U.Fguide = fguide; U.Falbedo = falbedo; U.Fmat = fmat; U.Fgz = fgz;
+    GuidePlanes& F = c->up_guides;                         // the full side: planes of its own, traced once per view
+    DR_TRY(trace_guides(c, F, 2, full13, W, H, PF, traversal, &c->up_passes));
+    U.Fguide = F.quad(0); U.Falbedo = F.rgb(); U.Fmat = F.material(); U.Fgz = F.scalar();
   }
-  float* f32_dev;
-  uint8_t* rgb_dev;
-  DR_TRY(output_staging(c, npix, out_f32, out_rgb8, device_pointers, f32_dev, rgb_dev));
-  U.out_f32 = f32_dev; U.out_rgb8 = rgb_dev;
+  ImageOut out(out_f32, out_rgb8);
+  DR_TRY(out.begin(c, W, H, device_pointers));
+  U.out_f32 = out.f32(); U.out_rgb8 = out.rgb8();
   launch_upscale(c->stream, U);
   HIP_TRY(hipGetLastError());
-  if (device_pointers) return DR_OK;
-  return output_download(c, npix, out_f32, out_rgb8, f32_dev, rgb_dev);
+  return out.end(c, device_pointers);
 }
 
 int dr_reproject_defaults(dr_reproject_params* p) {
@@ -305,20 +280,15 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   int traversal = 0;
   DR_TRY(aov_view(c, from_settings13, W, H, Pf, traversal));
   DR_TRY(aov_view(c, to_settings13, W, H, Pt, traversal));
-  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { set_error("reproject: the two views have different divisors"); return DR_ERR_INVALID; }
+  if (const char* why = check_reproject_views(Pf, Pt)) { set_error(why); return DR_ERR_INVALID; }      // (the judge's first check, ahead of the context's)
   if (c->stripe_mod != 1 || c->stripe_rem != 0) { set_error("reproject: the context renders a stripe (dr_context_set_stripe); only (1, 0) is supported"); return DR_ERR_INVALID; }
   DR_TRY(accum_matches(c, "reproject", W, H));
-  if (frames < 1) { set_error("reproject: frames must be >= 1"); return DR_ERR_INVALID; }
   RpLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.R = params ? rp_params(*params) : RP_DEFAULTS;
-  if (const char* why = check_reproject_params(L.R)) { set_error(why); return DR_ERR_INVALID; }
-  fill_reproject_camera(Pt, L.to);
-  fill_reproject_camera(Pf, L.from);
-  if (!fill_reproject_proj(L.from, L.J)) { set_error("reproject: the `from` view is degenerate (its focus plane has no normal facing the camera)"); return DR_ERR_INVALID; }
+  const std::string why = judge_reproject(Pf, Pt, frames, params, L);
+  if (!why.empty()) { set_error(why); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
-  const int gw = Pt.gx * 8, gh = Pt.gy * 8;
+  const int gw = L.gw, gh = L.gh;
   const size_t n = (size_t)gw * (size_t)gh, npix = (size_t)W * (size_t)H;
   DR_TRY(c->accum2.grow(npix * 3, c->stream));
   const int hto = c->hist ? 1 - c->hist_cur : 0;
@@ -328,31 +298,28 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   DR_TRY(c->rp_counts.grow(4, c->stream));
   // the guides: the cached planes serve as `from` when their key matches; the `to` view is traced into the other set (into none when it is
   // the `from` view itself) and becomes the cache
-  const bool warm = c->rp_key.matches(from_settings13, W, H, c->scene_gen);
+  const bool warm = c->rp_guides[c->rp_cur].key.matches(from_settings13, W, H, c->scene_gen);
   const bool same_view = memcmp(from_settings13, to_settings13, 13 * sizeof(float)) == 0;
   const int sf = warm ? c->rp_cur : 0, st = same_view ? sf : 1 - sf;
-  c->rp_key.valid = false;
+  c->rp_guides[c->rp_cur].key.valid = false;
   c->rp_passes = 0;
-  // (t, normal and material only, no guide prepare: not trace_guides)
-  auto trace = [&](int set, const RenderParams& P, const float* st13) -> int {
+  // (t, normal and material only, no float4 plane and no guide prepare: not trace_guides)
+  auto trace = [&](GuidePlanes& G, const RenderParams& P, const float* st13) -> int {
     if (n == 0) return DR_OK;
-    DR_TRY(c->rp_planes[set].grow(5 * n, c->stream));
-    AovLaunch A;
-    memset(&A, 0, sizeof(A));
-    A.x0 = 0; A.y0 = 0; A.w = gw; A.h = gh;
-    A.focus = st13[7];
-    A.t = c->rp_planes[set]; A.normal = c->rp_planes[set] + n; A.material = reinterpret_cast<int32_t*>(c->rp_planes[set] + 4 * n);
+    DR_TRY(G.grow(n, 0, c->stream));
+    AovLaunch A = aov_launch(c, st13[7], 0, 0, gw, gh);
+    A.t = G.scalar(); A.normal = G.rgb(); A.material = G.material();
     launch_aov(c->stream, P, traversal, A);
     HIP_TRY(hipGetLastError());
     c->rp_passes++;
     return DR_OK;
   };
-  if (!warm) DR_TRY(trace(sf, Pf, from_settings13));
-  if (!same_view) DR_TRY(trace(st, Pt, to_settings13));
-  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.frames = frames;
+  GuidePlanes &Gf = c->rp_guides[sf], &Gt = c->rp_guides[st];
+  if (!warm) DR_TRY(trace(Gf, Pf, from_settings13));
+  if (!same_view) DR_TRY(trace(Gt, Pt, to_settings13));
   if (n > 0) {
-    L.t_from = c->rp_planes[sf]; L.normal_from = c->rp_planes[sf] + n; L.mat_from = reinterpret_cast<const int32_t*>(c->rp_planes[sf] + 4 * n);
-    L.t_to = c->rp_planes[st]; L.normal_to = c->rp_planes[st] + n; L.mat_to = reinterpret_cast<const int32_t*>(c->rp_planes[st] + 4 * n);
+    L.t_from = Gf.scalar(); L.normal_from = Gf.rgb(); L.mat_from = Gf.material();
+    L.t_to = Gt.scalar(); L.normal_to = Gt.rgb(); L.mat_to = Gt.material();
   }
   L.acc_from = c->accum; L.hist_from = c->hist;
   L.acc_to = c->accum2; L.hist_to = c->hist_buf[hto];
@@ -373,8 +340,8 @@ int dr_accum_reproject(dr_context* c, const float from_settings13[13], const flo
   c->accum.swap(c->accum2);
   c->hist = c->hist_buf[hto]; c->hist_cur = hto;
   if (c->m2) { c->m2 = c->m2_buf[mto]; c->m2_cur = mto; }
-  c->rp_key.store(to_settings13, W, H, c->scene_gen);
-  c->rp_cur = st; c->rp_key.valid = n > 0;
+  Gt.key.store(to_settings13, W, H, c->scene_gen);
+  c->rp_cur = st; Gt.key.valid = n > 0;
   if (result) {
     result->pixels = (int64_t)n;
     result->valid = (int64_t)counts[RP_VALID]; result->masked = (int64_t)counts[RP_MASKED];
@@ -433,52 +400,23 @@ int dr_accum_unpack_stripes(dr_context* c, const void* packed_dev, uint64_t rank
 }
 
 int dr_accum_read(dr_context* c, int32_t* out_int3) {
-  if (!c || !out_int3 || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipMemcpyAsync(out_int3, c->accum, (size_t)c->accW * c->accH * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
+  return plane_read(c, out_int3, sums_of, 3 * sizeof(int32_t));
 }
-
 int dr_accum_history_read(dr_context* c, int32_t* out) {
-  if (!c || !out || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  const size_t n = (size_t)c->accW * c->accH;
-  if (!c->hist) { memset(out, 0, n * sizeof(int32_t)); return DR_OK; }
-  HIP_TRY(hipMemcpyAsync(out, c->hist, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
+  return plane_read(c, out, history_of, sizeof(int32_t));
 }
-
-int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
-  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // as dr_accum_device_ptr
-  *dev_ptr = c->hist;
-  if (bytes) *bytes = c->hist ? (uint64_t)c->accW * c->accH * sizeof(int32_t) : 0;
-  return DR_OK;
-}
-
 int dr_accum_moments_read(dr_context* c, uint64_t* out) {
-  if (!c || !out || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  const size_t n = (size_t)c->accW * c->accH;
-  if (!c->m2) { memset(out, 0, n * sizeof(uint64_t)); return DR_OK; }
-  HIP_TRY(hipMemcpyAsync(out, c->m2, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
+  return plane_read(c, out, moments_of, sizeof(uint64_t));
 }
 
+int dr_accum_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
+  return plane_device_ptr(c, dev_ptr, bytes, sums_of, 3 * sizeof(int32_t));
+}
+int dr_accum_history_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
+  return plane_device_ptr(c, dev_ptr, bytes, history_of, sizeof(int32_t));
+}
 int dr_accum_moments_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
-  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // as dr_accum_device_ptr
-  *dev_ptr = c->m2;
-  if (bytes) *bytes = c->m2 ? (uint64_t)c->accW * c->accH * sizeof(uint64_t) : 0;
-  return DR_OK;
+  return plane_device_ptr(c, dev_ptr, bytes, moments_of, sizeof(uint64_t));
 }
 
 int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int divide_by, float tolerance, float* out_sigma, dr_error_result* result,
@@ -489,23 +427,18 @@ int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int 
   DR_TRY(aov_view(c, settings13, W, H, P, traversal));
   DR_TRY(accum_matches(c, "error", W, H));
   if (!c->m2) { set_error("error: no moments plane (set option moments = 1 before dr_accum_reset)"); return DR_ERR_INVALID; }
-  if (divide_by < 0) { set_error("error: divide_by must be >= 0"); return DR_ERR_INVALID; }
-  if (!(tolerance >= 0.0f)) { set_error("error: tolerance must be >= 0"); return DR_ERR_INVALID; }
+  MoLaunch L;
+  const std::string why = judge_error(P, divide_by, tolerance, L);
+  if (!why.empty()) { set_error(why); return DR_ERR_INVALID; }
   if (!out_sigma && !result) { set_error("error: no output (both out_sigma and result are NULL)"); return DR_ERR_INVALID; }
   DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
 
-  const size_t npix = (size_t)W * (size_t)H;
-  MoLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by; L.tolerance = tolerance;
   L.acc = c->accum; L.hist = c->hist; L.m2 = c->m2;
-  float* sigma_dev = out_sigma;
-  if (out_sigma && !device_pointers) {
-    DR_TRY(c->err_staging.grow(npix, c->stream));
-    sigma_dev = c->err_staging;
-  }
-  L.out_sigma = sigma_dev;
-  if (sigma_dev && (L.gw < W || L.gh < H)) HIP_TRY(hipMemsetAsync(sigma_dev, 0, npix * sizeof(float), c->stream));      // pixels outside the grid are 0
+  const QueryOut ch[1] = {{out_sigma, 1, true}};
+  QueryIo io;
+  DR_TRY(query_begin(c, (size_t)W * (size_t)H, 1, nullptr, 0, ch, 1, device_pointers != 0, io));
+  L.out_sigma = (float*)io.out[0];
+  if (L.out_sigma && (L.gw < W || L.gh < H)) HIP_TRY(hipMemsetAsync(L.out_sigma, 0, io.out_bytes[0], c->stream));      // pixels outside the grid are 0
   if (result) {
     DR_TRY(c->err_counts.grow(MO_WORDS, c->stream));
     HIP_TRY(hipMemsetAsync(c->err_counts, 0, MO_WORDS * sizeof(unsigned long long), c->stream));
@@ -515,8 +448,8 @@ int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int 
   HIP_TRY(hipGetLastError());
   unsigned long long counts[MO_WORDS] = {0};
   if (result) HIP_TRY(hipMemcpyAsync(counts, c->err_counts, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-  if (out_sigma && !device_pointers) HIP_TRY(hipMemcpyAsync(out_sigma, sigma_dev, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (result || !device_pointers) HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(query_end(c, ch, 1, device_pointers != 0, io));
+  if (result && device_pointers) HIP_TRY(hipStreamSynchronize(c->stream));      // (the counts are read even when the plane stays on the device)
   if (result) {
     result->pixels = (int64_t)L.gw * (int64_t)L.gh;
     result->estimated = (int64_t)counts[MO_ESTIMATED]; result->above = (int64_t)counts[MO_ABOVE]; result->sum_var_q16 = counts[MO_SUM_VAR];
@@ -529,23 +462,12 @@ int dr_accum_present(dr_context* c, int divide_by, uint8_t* out_rgb8) {
   if (!c || !out_rgb8 || !c->accum || divide_by == 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   DR_TRY(join_pipeline(c));
-  size_t bytes = (size_t)c->accW * c->accH * 3;
-  DR_TRY(c->present.grow(bytes, c->stream));
-  launch_present(c->stream, c->accum, c->hist, c->present, c->accW, c->accH, divide_by);
+  const QueryOut ch[1] = {{out_rgb8, 3, true, 1}};
+  QueryIo io;
+  DR_TRY(query_begin(c, (size_t)c->accW * c->accH, 1, nullptr, 0, ch, 1, false, io));
+  launch_present(c->stream, c->accum, c->hist, (uint8_t*)io.out[0], c->accW, c->accH, divide_by);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_rgb8, c->present, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return DR_OK;
-}
-
-int dr_accum_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes) {
-  if (!c || !dev_ptr || !c->accum) { set_error("no accumulator"); return DR_ERR_INVALID; }
-  // the caller orders its own work on dr_context_stream(): the frames submitted before are launched, and that stream waits for their adds
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  *dev_ptr = c->accum;
-  if (bytes) *bytes = (uint64_t)c->accW * c->accH * 3 * sizeof(int32_t);
-  return DR_OK;
+  return query_end(c, ch, 1, false, io);
 }
 
 }  // extern "C"

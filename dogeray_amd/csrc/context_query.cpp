@@ -16,15 +16,16 @@ int ensure_slot_to_orig(dr_context* c) {
 
 // Fills io with the device addresses of the inputs and of the wanted channels of n > 0 items; an entry of a channel is an item (per_item) or one of an
 // item's K.  Host pointers: staging holds every input, given or not, in the order of `in`, then the wanted channels in the order of `out`; the given
-// inputs are copied in.  Staging is aligned as hipMalloc aligns and every offset is a multiple of 4 bytes only, so AN INPUT OF 8-BYTE ELEMENTS GOES
-// FIRST (dr_trace_radiance's seeds): at offset 0 it is aligned whatever n is.
+// inputs are copied in.  Staging is aligned as hipMalloc aligns and every offset is a multiple of 4 bytes only (a channel of bytes is padded to one),
+// so AN INPUT OF 8-BYTE ELEMENTS GOES FIRST (dr_trace_radiance's seeds): at offset 0 it is aligned whatever n is.  The accumulator's stages
+// (context_accum.cpp) come here with their pixels as the items and no input: the wanted outputs are carved and downloaded as a query's channels are.
 int query_begin(dr_context* c, size_t n, size_t K, const QueryIn* in, int n_in, const QueryOut* out, int n_out, bool device_pointers, QueryIo& io) {
   memset(&io, 0, sizeof(io));
   size_t bytes = 0;
   for (int k = 0; k < n_in; k++) bytes += n * (size_t)in[k].words * 4;
   for (int k = 0; k < n_out; k++) {
-    io.out_bytes[k] = (out[k].per_item ? n : n * K) * (size_t)out[k].words * 4;
-    if (out[k].p) bytes += io.out_bytes[k];
+    io.out_bytes[k] = (out[k].per_item ? n : n * K) * (size_t)out[k].words * (size_t)out[k].unit;
+    if (out[k].p) bytes += (io.out_bytes[k] + 3) & ~(size_t)3;
   }
   if (device_pointers) {
     for (int k = 0; k < n_in; k++) io.in[k] = in[k].p;
@@ -42,7 +43,7 @@ int query_begin(dr_context* c, size_t n, size_t K, const QueryIn* in, int n_in, 
     off += size;
   }
   for (int k = 0; k < n_out; k++)
-    if (out[k].p) { io.out[k] = c->query_staging + off; off += io.out_bytes[k]; }
+    if (out[k].p) { io.out[k] = c->query_staging + off; off += (io.out_bytes[k] + 3) & ~(size_t)3; }
   return DR_OK;
 }
 

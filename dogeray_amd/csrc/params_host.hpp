@@ -10,7 +10,7 @@
 #include <string>
 
 #include "../../include/dogeray_amd.h"
-#include "device_layout.h"
+#include "device_launch.h"
 
 namespace dr {
 
@@ -169,6 +169,72 @@ inline const char* check_reproject_params(const RpParams& R) {
   if (!(R.normal_cos >= -1.0f && R.normal_cos <= 1.0f)) return "reproject: normal_cos must be -1 .. 1";
   if (!(R.plane_tolerance >= 0.0f)) return "reproject: plane_tolerance must be >= 0";
   return nullptr;
+}
+
+// The judges of the accumulator stages' calls, one per stage, run by the library (context_accum.cpp) and by the host build (tools/host_kernel/
+// hk_accum.hpp) alike.  A judge is given the caller's arguments and the view(s) as fill_view_params filled them; it checks what needs no device, in
+// the order the library refuses, and fills the launch struct (zeroed first) with the grid, the sizes and the parameters -- the caller adds the
+// pointers.  Returns the refusal, or "".
+
+// settings13 at full resolution (element 11 = 1): the upsampler's second view
+inline void full_view13(const float* settings13, float* full13) {
+  memcpy(full13, settings13, 13 * sizeof(float));
+  full13[11] = 1.0f;
+}
+// the denoiser's launch over the pixel grid of view P: dr_accum_denoise's, and the low side of dr_accum_upscale
+inline DnLaunch low_launch(const RenderParams& P, int divide_by, const DnParams& D) {
+  DnLaunch L;
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = P.W; L.H = P.H; L.divide_by = divide_by; L.D = D;
+  return L;
+}
+inline std::string judge_denoise(const RenderParams& P, int divide_by, const dr_denoise_params* params, DnLaunch& L) {
+  if (divide_by < 1) return "denoise: divide_by must be >= 1";
+  const DnParams D = params ? dn_params(*params) : DN_DEFAULTS;
+  if (const char* why = check_denoise_params(D)) return std::string("denoise: ") + why;
+  L = low_launch(P, divide_by, D);
+  return "";
+}
+// P: the view of settings13, PF: of its full_view13.  L is the low side (run by a guided call on a grid that is not empty; its passes when there is a prefilter)
+inline std::string judge_upscale(const RenderParams& P, const RenderParams& PF, const float* settings13, int divide_by, const dr_upscale_params* params,
+                                 const dr_denoise_params* prefilter, UpLaunch& U, DnLaunch& L) {
+  if (divide_by < 1) return "upscale: divide_by must be >= 1";
+  const UpParams UP = params ? up_params(*params) : UP_DEFAULTS;
+  const DnParams PRE = prefilter ? dn_params(*prefilter) : DnParams{};
+  const DnParams* const pre = prefilter ? &PRE : nullptr;
+  const std::string why = check_upscale_params(UP, pre);
+  if (!why.empty()) return why;
+  memset(&U, 0, sizeof(U));
+  U.gw = P.gx * 8; U.gh = P.gy * 8; U.FW = PF.gx * 8; U.FH = PF.gy * 8; U.W = P.W; U.H = P.H;
+  U.div = U.gw > 0 && U.gh > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
+  U.U = UP;
+  L = low_launch(P, divide_by, up_low_params(UP, pre));
+  return "";
+}
+// Pf, Pt: the `from` and the `to` view.  The judge's first check is a function of its own: the library makes it ahead of its context's checks
+// (stripe, accumulator size), which stand before the judge's other refusals in dr_accum_reproject's order
+inline const char* check_reproject_views(const RenderParams& Pf, const RenderParams& Pt) {
+  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) return "reproject: the two views have different divisors";
+  return nullptr;
+}
+inline std::string judge_reproject(const RenderParams& Pf, const RenderParams& Pt, int frames, const dr_reproject_params* params, RpLaunch& L) {
+  if (const char* why = check_reproject_views(Pf, Pt)) return why;
+  if (frames < 1) return "reproject: frames must be >= 1";
+  memset(&L, 0, sizeof(L));
+  L.R = params ? rp_params(*params) : RP_DEFAULTS;
+  if (const char* why = check_reproject_params(L.R)) return why;
+  fill_reproject_camera(Pt, L.to);
+  fill_reproject_camera(Pf, L.from);
+  if (!fill_reproject_proj(L.from, L.J)) return "reproject: the `from` view is degenerate (its focus plane has no normal facing the camera)";
+  L.gw = Pt.gx * 8; L.gh = Pt.gy * 8; L.W = Pt.W; L.H = Pt.H; L.frames = frames;
+  return "";
+}
+inline std::string judge_error(const RenderParams& P, int divide_by, float tolerance, MoLaunch& L) {
+  if (divide_by < 0) return "error: divide_by must be >= 0";
+  if (!(tolerance >= 0.0f)) return "error: tolerance must be >= 0";
+  memset(&L, 0, sizeof(L));
+  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = P.W; L.H = P.H; L.divide_by = divide_by; L.tolerance = tolerance;
+  return "";
 }
 
 // The certificate's ladder for option cert_factor (CertView level_a, ascending; a_star stays level_a[base] = 1e-4 cert_factor): graded, cert_factor x

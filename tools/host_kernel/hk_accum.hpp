@@ -1,25 +1,20 @@
 // The accumulator stages on the host (hk_denoise, hk_upscale, hk_reproject, hk_moments_add, hk_error): the launch structs of device_launch.h filled with
-// host pointers and a loop over the pixels; no stage's arithmetic or indexing is written here.  Parameter defaults and ranges are params_host.hpp's.
-// Part of host_kernel.cpp.
+// host pointers and a loop over the pixels; no stage's arithmetic or indexing is written here.  A call is judged, and its launch struct's grid,
+// sizes and parameters filled, by params_host.hpp's judge_* -- the judges the library runs; an entry here adds the pointers.  Part of host_kernel.cpp.
 namespace {
-// a parameter set handed over as words: a dr_denoise_params, dr_upscale_params or dr_reproject_params
+// a parameter set handed over as words (null: the defaults): a dr_denoise_params, dr_upscale_params or dr_reproject_params
 template <class T>
-T params_from_words(const int32_t* words) { T p; memcpy(&p, words, sizeof(T)); return p; }
+struct ParamWords {
+  T p{};
+  bool given;
+  explicit ParamWords(const int32_t* words) : given(words != nullptr) { if (given) memcpy(&p, words, sizeof(T)); }
+  const T* get() const { return given ? &p : nullptr; }
+};
 
 // The low side of hk_denoise and hk_upscale over the L.gw x L.gh pixel grid (L.D, L.acc, L.hist, L.m2 and the AOV planes L.normal, L.depth,
 // L.albedo, L.mat set by the caller), stage by stage as denoise_low_side (context_accum.cpp) launches it: the guide prepare, colour stage 0 and
 // -- filter -- the variance pre-pass and the L.D.iterations a-trous passes.  The planes live in `planes`; on return L.src is the plane of the
 // result, (e, l) after stage 0, (e, var) after the last pass, and L.guide, L.gz are the guides.
-// the launch of the low side on the gw x gh grid: the denoiser's parameters, the accumulator's planes and the guides in dr_render_aov's layout
-DnLaunch host_low_launch(int gw, int gh, int W, int H, int divide_by, const DnParams& D, const int32_t* acc, const int32_t* hist, const unsigned long long* m2,
-                         const float* normal, const float* albedo, const float* depth, const int32_t* material) {
-  DnLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.gw = gw; L.gh = gh; L.W = W; L.H = H; L.divide_by = divide_by; L.D = D;
-  L.acc = acc; L.hist = hist; L.m2 = m2;
-  L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
-  return L;
-}
 struct HostLow {
   std::vector<float> guide, gz, pa, pb;      // float4 (n, z) | depth gradient | colour planes A, B (float4)
 };
@@ -54,12 +49,13 @@ int hk_denoise(const int32_t* acc, int W, int H, int divide_by, const float* set
   if (!acc || !settings13 || !normal || !albedo || !depth || !material) { hk_err = "bad argument"; return -1; }
   RenderParams P;
   if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
-  const DnParams D = params ? dn_params(params_from_words<dr_denoise_params>(params)) : DN_DEFAULTS;
-  if (divide_by < 1) { hk_err = "denoise: divide_by must be >= 1"; return -1; }
-  if (const char* why = check_denoise_params(D)) { hk_err = std::string("denoise: ") + why; return -1; }
-  DnLaunch L = host_low_launch(P.gx * 8, P.gy * 8, W, H, divide_by, D, acc, hist, m2, normal, albedo, depth, material);
+  DnLaunch L;
+  hk_err = judge_denoise(P, divide_by, ParamWords<dr_denoise_params>(params).get(), L);
+  if (!hk_err.empty()) return -1;
+  L.acc = acc; L.hist = hist; L.m2 = m2;
+  L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
   HostLow planes;
-  if (D.iterations > 0) host_denoise_low(L, true, nthreads, planes);
+  if (L.D.iterations > 0) host_denoise_low(L, true, nthreads, planes);
   L.out_f32 = out_f32; L.out_rgb8 = out_rgb8;
   host_grid(nthreads, W, H, [&](int x, int y) { dn_finish_pixel(L, x, y); });
   return 0;
@@ -78,27 +74,20 @@ int hk_upscale(const int32_t* acc, int W, int H, int divide_by, const float* set
   RenderParams P, PF;
   if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
   float full13[13];
-  memcpy(full13, settings13, sizeof(full13));
-  full13[11] = 1.0f;
+  full_view13(settings13, full13);
   if (const char* why = host_view(full13, W, H, 0.0f, 0, 1, 0, PF)) { hk_err = why; return -1; }
-  const UpParams UP = params ? up_params(params_from_words<dr_upscale_params>(params)) : UP_DEFAULTS;
-  const DnParams PRE = prefilter ? dn_params(params_from_words<dr_denoise_params>(prefilter)) : DnParams{};
-  const DnParams* const pre = prefilter ? &PRE : nullptr;
-  if (divide_by < 1) { hk_err = "upscale: divide_by must be >= 1"; return -1; }
-  hk_err = check_upscale_params(UP, pre);
-  if (!hk_err.empty()) return -1;
   UpLaunch U;
-  memset(&U, 0, sizeof(U));
-  U.gw = P.gx * 8; U.gh = P.gy * 8; U.FW = PF.gx * 8; U.FH = PF.gy * 8; U.W = W; U.H = H;
-  U.div = U.gw > 0 && U.gh > 0 ? (int)settings13[11] : 1; U.divide_by = divide_by;
-  U.U = UP;
+  DnLaunch L;                                                               // the low side: the denoiser's planes
+  hk_err = judge_upscale(P, PF, settings13, divide_by, ParamWords<dr_upscale_params>(params).get(), ParamWords<dr_denoise_params>(prefilter).get(), U, L);
+  if (!hk_err.empty()) return -1;
   U.acc = acc; U.hist = hist;
   HostLow low;
   std::vector<float> fguide, fgz;
-  if (UP.mode == UP_GUIDED && U.gw > 0 && U.gh > 0) {
+  if (U.U.mode == UP_GUIDED && U.gw > 0 && U.gh > 0) {
     if (!normal || !albedo || !depth || !material || !fnormal || !falbedo || !fdepth || !fmaterial) { hk_err = "bad argument"; return -1; }
-    DnLaunch L = host_low_launch(U.gw, U.gh, W, H, divide_by, up_low_params(UP, pre), acc, hist, m2, normal, albedo, depth, material);      // the denoiser's planes
-    host_denoise_low(L, pre != nullptr, nthreads, low);
+    L.acc = acc; L.hist = hist; L.m2 = m2;
+    L.normal = normal; L.depth = depth; L.albedo = albedo; L.mat = material;
+    host_denoise_low(L, prefilter != nullptr, nthreads, low);
     U.e = L.src; U.guide = L.guide; U.mat = L.mat;
     DnLaunch G;                                                             // the full side: the guide prepare over the full grid
     memset(&G, 0, sizeof(G));
@@ -142,16 +131,9 @@ int hk_reproject(const int32_t* acc_from, const int32_t* hist_from, int W, int H
   RenderParams Pf, Pt;
   if (const char* why = host_view(from_settings13, W, H, 0.0f, 0, 1, 0, Pf)) { hk_err = why; return -1; }
   if (const char* why = host_view(to_settings13, W, H, 0.0f, 0, 1, 0, Pt)) { hk_err = why; return -1; }
-  if (Pf.gx != Pt.gx || Pf.gy != Pt.gy || Pf.den_w != Pt.den_w || Pf.den_h != Pt.den_h) { hk_err = "reproject: the two views have different divisors"; return -1; }
-  if (frames < 1) { hk_err = "reproject: frames must be >= 1"; return -1; }
   RpLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.R = params ? rp_params(params_from_words<dr_reproject_params>(params)) : RP_DEFAULTS;
-  if (const char* why = check_reproject_params(L.R)) { hk_err = why; return -1; }
-  fill_reproject_camera(Pt, L.to);
-  fill_reproject_camera(Pf, L.from);
-  if (!fill_reproject_proj(L.from, L.J)) { hk_err = "reproject: the `from` view is degenerate"; return -1; }
-  L.gw = Pt.gx * 8; L.gh = Pt.gy * 8; L.W = W; L.H = H; L.frames = frames;
+  hk_err = judge_reproject(Pf, Pt, frames, ParamWords<dr_reproject_params>(params).get(), L);
+  if (!hk_err.empty()) return -1;
   L.t_to = t_to; L.normal_to = normal_to; L.mat_to = mat_to;
   L.t_from = t_from; L.normal_from = normal_from; L.mat_from = mat_from;
   L.acc_from = acc_from; L.hist_from = hist_from; L.acc_to = acc_to; L.hist_to = hist_to;
@@ -186,11 +168,9 @@ int hk_error(const int32_t* acc, const int32_t* hist, const unsigned long long* 
   if (!acc || !m2 || !settings13 || (!out_sigma && !result)) { hk_err = "bad argument"; return -1; }
   RenderParams P;
   if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
-  if (divide_by < 0) { hk_err = "error: divide_by must be >= 0"; return -1; }
-  if (!(tolerance >= 0.0f)) { hk_err = "error: tolerance must be >= 0"; return -1; }
   MoLaunch L;
-  memset(&L, 0, sizeof(L));
-  L.gw = P.gx * 8; L.gh = P.gy * 8; L.W = W; L.H = H; L.divide_by = divide_by; L.tolerance = tolerance;
+  hk_err = judge_error(P, divide_by, tolerance, L);
+  if (!hk_err.empty()) return -1;
   L.acc = acc; L.hist = hist; L.m2 = m2; L.out_sigma = out_sigma;
   if (grid2) { grid2[0] = L.gw; grid2[1] = L.gh; }
   if (out_sigma) memset(out_sigma, 0, (size_t)W * H * sizeof(float));
