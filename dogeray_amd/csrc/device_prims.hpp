@@ -62,6 +62,10 @@ __device__ __forceinline__ void pin_loads(u32x4& a, u32x4& b, u32x4& c, u32x4& d
 __device__ __forceinline__ unsigned bit_select(unsigned if0, unsigned if1, unsigned m) { return __builtin_amdgcn_bitop3_b32(if0, if1, m, 0xd8); }      // m ? if1 : if0, bit by bit
 __device__ __forceinline__ unsigned bit_and_or(unsigned a, unsigned b, unsigned c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xea); }
 __device__ __forceinline__ unsigned bit_andn(unsigned a, unsigned b, unsigned c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x08); }
+// the number of the lowest set bit, -1 for 0: v_ffbl_b32 as it is (__builtin_ctz leaves 0 undefined, the defined form costs a v_min_u32 more and gives 32)
+__device__ __forceinline__ int lowest_bit(unsigned w) { int j; asm("v_ffbl_b32 %0, %1" : "=v"(j) : "v"(w)); return j; }
+// max(v, -1) as ONE v_max_i32: spelled in C++ the compiler makes a compare and a select of it
+__device__ __forceinline__ int at_least_minus_one(int v) { int r; asm("v_max_i32 %0, -1, %1" : "=v"(r) : "v"(v)); return r; }
 
 // ---- The four plane bytes of a word as f16 denormals: (byte0, byte2) and (byte1, byte3), each pair in one register
 typedef _Float16 DrHalf2 __attribute__((ext_vector_type(2)));

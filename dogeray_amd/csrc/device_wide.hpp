@@ -151,6 +151,26 @@ __device__ __forceinline__ void wide_pop(Trav& tr, WideStack& ws, const int* __r
   ws.top = (ws.top & 15u) ? ws.top : 0u;
 }
 
+// wide_pop for the lean persistent build's six-wave kernel (kernels_render.hip; the same next record, remaining word and stack pointer:
+// tests/test_lean_pop_host.py) on ONE straight path.  wide_pop compiles there to three nested exec regions, two compares and five register copies around
+// some eleven instructions of work, in every leaf step and nearly every node step of the wave (profiles/pop_phase_trim.txt); here
+//  * only the LDS read is conditional, and its condition is one compare: the lean build hands no words over (sb == 0 throughout), and a stored word is
+//    at least 256 -- record 0 is the root and nobody's child (wide_builder.cpp), so a word's first child is 1 or more -- while sp <= WIDE_STACK: top < sp
+//    says "top is 0 and the stack is not empty";
+//  * the word popped from (w: top, or the stack's) is 0 exactly when nothing is left, and the record falls out of the same instructions then:
+//    lowest_bit(0) = -1 gives (0 - 1) << 1 | 0 = -2, which the max turns into LANE_DONE (-1) and leaves every record (>= 0) alone; the remaining word of 0 is 0.
+// A function of its own so that every other caller of wide_pop compiles as before.
+static_assert(WIDE_STACK < 256 && LANE_DONE == -1, "wide_pop_lean: top < sp, and the max");
+__device__ __forceinline__ void wide_pop_lean(Trav& tr, WideStack& ws, const int* __restrict__ stack) {
+  unsigned w = ws.top;
+  if (w < (unsigned)ws.sp) { ws.sp--; w = (unsigned)stack[ws.sp * 64]; }
+  const int j = lowest_bit(w);
+  const int rec = (int)((((w >> 8) + (unsigned)j) << 1) | ((w >> (4 + j)) & 1u));
+  tr.node = at_least_minus_one(rec);
+  const unsigned rest = w & (w - 1u);
+  ws.top = (rest & 15u) ? rest : 0u;
+}
+
 // One record = four 16-byte units; a node is its first three (device_layout.h), a leaf all four: the fourth is fetched by the lanes at a leaf only (a
 // lane knows from the parent's leaf mask which it is) -- every load instruction of a step costs about 1 % of the frame (profiles/r4_o_node_three_units.txt).
 // The empty asm pins the loads in front of the first use: without it hipcc sinks the leaf's primitive units behind the box test, a second dependent round trip.
@@ -165,7 +185,8 @@ __device__ __forceinline__ WideRec wide_fetch(WalkRsrc wide, int node) {
   return r;
 }
 
-template <bool COUNT, class Sign>
+// (POP_LEAN: the lean six-wave build's pop, wide_pop_lean above)
+template <bool COUNT, bool POP_LEAN = false, class Sign>
 __device__ __forceinline__ void wide_node_compute(const WideRec& r, const WideRay& wr, const Sign& sg, Trav& tr, WideStack& ws, int* __restrict__ stack, Ctr& c) {
   DR_MARK("node_begin");
   if (COUNT) c.V++;
@@ -184,7 +205,8 @@ __device__ __forceinline__ void wide_node_compute(const WideRec& r, const WideRa
     }
     tr.node = (int)(((base + (unsigned)near) << 1) | ((leafmask >> near) & 1u));
   } else {
-    wide_pop(tr, ws, stack);
+    if (POP_LEAN) wide_pop_lean(tr, ws, stack);
+    else wide_pop(tr, ws, stack);
   }
   DR_MARK("node_end");
 }
@@ -223,7 +245,7 @@ __device__ __forceinline__ void wide_leaf_compute(const WideRec& r, V3 o, V3 d, 
 // acceptance, ties included -- leaves the barycentrics tri_hit formed in its two stash words u_word, v_word, so that they are those of the best hit when
 // the walk ends (a sphere leaves what is there: nobody reads them for one).  The two LDS writes sit in the candidate branch, which 5 % of the lanes take.
 // A function of its own so that every other caller of wide_leaf_compute compiles as before.
-template <class Sign>
+template <bool POP_LEAN, class Sign>
 __device__ __forceinline__ void wide_leaf_compute_uv(const WideRec& r, V3 o, V3 d, V3 inv, const Sign& sg, Trav& tr, WideStack& ws, const int* __restrict__ stack,
                                                      float* u_word, float* v_word) {
   auto f = [](unsigned v) { return __uint_as_float(v); };
@@ -241,7 +263,8 @@ __device__ __forceinline__ void wide_leaf_compute_uv(const WideRec& r, V3 o, V3 
       *u_word = hit_u; *v_word = hit_v;
     }
   }
-  wide_pop(tr, ws, stack);
+  if (POP_LEAN) wide_pop_lean(tr, ws, stack);
+  else wide_pop(tr, ws, stack);
   DR_MARK("leaf_end");
 }
 

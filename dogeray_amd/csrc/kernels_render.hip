@@ -156,6 +156,9 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   int* const my_stack = my_lds + lane;                             // WIDE: word k of this lane's stack at my_stack[k * 64]
   // the lean build's forms of the hit's inputs (device_prims.hpp): u, v carried in WS_TOP / WS_STEPS (the stash layout above), the lazy fetches of shade_prepare
   constexpr bool UV_CARRIED = HIT_UV_CARRIED && WIDE && !COOP && !COUNT, FETCH_LAZY = HIT_FETCH_LAZY && WIDE && !COOP && !COUNT;
+  // the six-wave lean build pops its stack on one straight path (device_wide.hpp wide_pop_lean; it hands no words over: sb stays 0); every other build --
+  // its per-frame twin of the present pipeline too -- keeps wide_pop
+  constexpr bool POP_LEAN = WIDE && !COOP && !COUNT && !PERFRAME && OCC == 6;
   float* const uv_words = reinterpret_cast<float*>(my_stack) + WIDE_STACK * 64;      // this lane's stash, as the leaf step sees it (UV_CARRIED only)
   unsigned long long* const share_key = reinterpret_cast<unsigned long long*>(my_lds + (WIDE ? SHARE_OFF : 0));     // [64], WIDE && COOP only
   unsigned* const share_pend = reinterpret_cast<unsigned*>(my_lds + (WIDE ? SHARE_OFF : 0) + 128);                   // [64]
@@ -626,10 +629,10 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
         if (COUNT) { if (first_active_lane()) c.trav_slots += 64; }
         const WideRec r = wide_fetch(walk, tr.node);
         if (at_leaf) {
-          if (UV_CARRIED) wide_leaf_compute_uv(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
+          if (UV_CARRIED) wide_leaf_compute_uv<POP_LEAN>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
           else wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
         }
-        else wide_node_compute<COUNT>(r, wr, sg, tr, ws, my_stack, c);
+        else wide_node_compute<COUNT, POP_LEAN>(r, wr, sg, tr, ws, my_stack, c);
         steps++;
       }
       for (int u = 1; u < P_UNROLL; u++) {         // the further steps of an iteration decide anew
@@ -643,10 +646,10 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
           if (COUNT) { if (first_active_lane()) c.trav_slots += 64; }
           const WideRec r = wide_fetch(walk, tr.node);
           if (at_leaf2) {
-            if (UV_CARRIED) wide_leaf_compute_uv(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
+            if (UV_CARRIED) wide_leaf_compute_uv<POP_LEAN>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
             else wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
           }
-          else wide_node_compute<COUNT>(r, wr, sg, tr, ws, my_stack, c);
+          else wide_node_compute<COUNT, POP_LEAN>(r, wr, sg, tr, ws, my_stack, c);
           steps++;
         }
       }

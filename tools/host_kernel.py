@@ -57,6 +57,7 @@ _API = [
     ("hk_ray_margin_k", None, [_Q, _P, _P, _F, _F, _F, _F, _P]),
     ("hk_cert_factor_k", _F, [_D]),
     ("hk_slab", None, [_Q] + [_P] * 5),
+    ("hk_lean_pop", None, [_Q] + [_P] * 4),
     ("hk_tri_hit", None, [_Q] + [_P] * 6),
     ("hk_tri_hit_uv", None, [_Q] + [_P] * 7),
     ("hk_tri_barycentrics", None, [_Q] + [_P] * 6),
@@ -221,6 +222,17 @@ def slab(o, d, mn, mx):
     hit = np.zeros(o.shape[0], np.int32)
     lib().hk_slab(o.shape[0], *map(_ptr, (o, d, mn, mx, hit)))
     return hit
+
+
+def lean_pop(top, sp, stack):
+    """device_wide.hpp wide_pop and wide_pop_lean on n stack states (hk_lean_pop): top uint32[n], sp int32[n] in 0 .. 16, stack uint32[n, 16] (the
+    lane's stack words) -> (int32[n, 3], int32[n, 3]): next record, remaining word, stack pointer after wide_pop and after wide_pop_lean"""
+    top, sp, stack = _arr(top, np.uint32), _arr(sp, np.int32), _arr(stack, np.uint32)
+    n = top.shape[0]
+    assert sp.shape == (n,) and stack.shape == (n, 16) and sp.min() >= 0 and sp.max() <= 16
+    out = np.zeros((n, 2, 3), np.int32)
+    lib().hk_lean_pop(n, *map(_ptr, (top, sp, stack, out)))
+    return out[:, 0], out[:, 1]
 
 
 def tri_hit_uv(o, d, v0, e1, e2):

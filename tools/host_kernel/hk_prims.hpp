@@ -84,6 +84,22 @@ void hk_slab(long long n, const float* o, const float* d, const float* mn, const
     hit[i] = slab(ld3(o + 3 * i), mk(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z), mn + 3 * i, mx + 3 * i, dist) ? 1 : 0;
   }
 }
+// device_wide.hpp wide_pop and wide_pop_lean on n stack states (tests/test_lean_pop_host.py): state i is the register word top[i], the stack pointer sp[i]
+// (0 .. WIDE_STACK, sb = 0) and WIDE_STACK stack words below it, stack[WIDE_STACK * i + k]; out[6 * i ..] = next record, remaining word, stack pointer of
+// wide_pop, then the same three of wide_pop_lean
+void hk_lean_pop(long long n, const uint32_t* top, const int32_t* sp, const uint32_t* stack, int32_t* out) {
+  int lane_stack[WIDE_STACK * 64];
+  for (long long i = 0; i < n; i++) {
+    for (int form = 0; form < 2; form++) {
+      for (int k = 0; k < WIDE_STACK; k++) lane_stack[k * 64] = (int)stack[WIDE_STACK * i + k];
+      Trav tr; trav_begin(tr);
+      WideStack ws; ws.top = top[i]; ws.sp = sp[i]; ws.sb = 0;
+      if (form == 0) wide_pop(tr, ws, lane_stack);
+      else wide_pop_lean(tr, ws, lane_stack);
+      out[6 * i + 3 * form] = tr.node; out[6 * i + 3 * form + 1] = (int32_t)ws.top; out[6 * i + 3 * form + 2] = ws.sp;
+    }
+  }
+}
 // hit_tri (device_intersect.hpp tri_hit) on n ray / triangle pairs: t or -1
 void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* t) {
   for (long long i = 0; i < n; i++)

@@ -36,6 +36,8 @@ __device__ __forceinline__ void pin_loads(u32x4&, u32x4&, u32x4&, u32x4&) {}
 __device__ __forceinline__ unsigned bit_select(unsigned if0, unsigned if1, unsigned m) { return (if0 & ~m) | (if1 & m); }
 __device__ __forceinline__ unsigned bit_and_or(unsigned a, unsigned b, unsigned c) { return (a & b) | c; }
 __device__ __forceinline__ unsigned bit_andn(unsigned a, unsigned b, unsigned c) { return ~a & b & c; }
+__device__ __forceinline__ int lowest_bit(unsigned w) { return w ? __builtin_ctz(w) : -1; }
+__device__ __forceinline__ int at_least_minus_one(int v) { return v > -1 ? v : -1; }
 
 // ---- The four plane bytes of a word as f16 denormals: (byte0, byte2) and (byte1, byte3), each pair in one register
 struct PlanePairs { unsigned even, odd; };
