@@ -31,6 +31,14 @@ __device__ __forceinline__ uint32_t xorwow_combine(uint32_t t, uint32_t v4) {   
 // p in some lane of the wave (wave-uniform).  A macro: through a function the compiler orders the operands of the mask's s_and_b64 differently
 #define DR_WAVE_ANY(p) (__builtin_amdgcn_ballot_w64(p) != 0ull)
 __device__ __forceinline__ bool first_active_lane() { return __lane_id() == (unsigned)__ffsll((long long)__ballot(1)) - 1u; }
+// this lane's bit of a wave mask, as the condition of a branch or a select: the mask goes into exec as it is (s_and_saveexec_b64), no VALU instruction.
+// The mask MUST be wave-uniform, and the call sits where all 64 lanes are active (the step at the top level of the persistent kernel's loop).
+__device__ __forceinline__ bool lane_bit(unsigned long long wave_mask) { return __builtin_amdgcn_inverse_ballot_w64(wave_mask); }
+// the number of set bits of a wave mask as a SCALAR int (s_bcnt1_i32_b64), so that a compare with it is an s_cmp: __popcll(m) >= n compiles to a 64-bit
+// compare, which the scalar unit does not have -- a v_cmp_gt_u64 on an SGPR pair
+__device__ __forceinline__ int wave_count(unsigned long long wave_mask) { int n; asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(wave_mask) : "scc"); return n; }
+// a wave-uniform int that the compiler keeps in a VGPR, back on the scalar unit (v_readfirstlane_b32): what is compared with it is then scalar too
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #define DR_PIN(s) asm volatile("; " s)      // a comment in the assembly that the compiler moves nothing across (the host: nothing)
 // the leaf step of the wide walk may test the primitive before the box, the wave deciding together (device_wide.hpp wide_leaf_compute); the host keeps the reference's order
 constexpr bool LEAF_PRIM_FIRST = true;
@@ -57,6 +65,8 @@ __device__ __forceinline__ u32x4 ld_unit_raw(WalkRsrc r, unsigned byte_off) { re
 // the two halves of device_wide.hpp wide_fetch's pin: a register tuple that holds no value yet and costs no instruction, and loads kept in front of their first use
 __device__ __forceinline__ void no_value(u32x4& v) { asm volatile("" : "=v"(v)); }
 __device__ __forceinline__ void pin_loads(u32x4& a, u32x4& b, u32x4& c, u32x4& d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+// a value the compiler sees as a register and nothing more (no instruction): what is added to it stays an addition -- a load's immediate offset
+__device__ __forceinline__ unsigned one_register(unsigned v) { asm("" : "+v"(v)); return v; }
 
 // ---- three-input bit operations (one v_bitop3_b32 each on the device; spelled out, the compiler re-associates them into slower pairs)
 __device__ __forceinline__ unsigned bit_select(unsigned if0, unsigned if1, unsigned m) { return __builtin_amdgcn_bitop3_b32(if0, if1, m, 0xd8); }      // m ? if1 : if0, bit by bit

@@ -16,6 +16,19 @@ constexpr int LANE_DONE = -1;        // walk finished (what the walks leave behi
 constexpr int LANE_REFILL = -2;      // needs a new ray: the next sample, or a new pixel
 constexpr int LANE_RETIRED = -3;     // nothing left to take
 
+// Which lanes of a wave take one step of the wide walk (render_persistent_kernel's rule, as a function of masks alone: tests/test_step_masks_host.py).
+// leaves / nodes: the walking lanes that stand at a leaf / at a node.  The leaf lanes wait until `leaf_min` of them stand at one, nobody can take a node
+// step, or the wave drains; with exclusive steps the node lanes sit out a leaf step unless the wave drains.  A lane in neither mask never steps.
+struct StepMasks { unsigned long long step, leaf; };      // the lanes that step, and those of them that step as leaves
+__device__ __forceinline__ StepMasks step_masks(unsigned long long leaves, unsigned long long nodes, bool draining, int leaf_min, bool exclusive) {
+  const bool do_leaves = leaves != 0ull && (wave_count(leaves) >= leaf_min || nodes == 0ull || draining);
+  const bool do_nodes = !exclusive || !do_leaves || draining;
+  StepMasks m;
+  m.leaf = do_leaves ? leaves : 0ull;
+  m.step = m.leaf | (do_nodes ? nodes : 0ull);
+  return m;
+}
+
 // "No hit yet" is t = 10000: singlehit only returns distances below 10000 (K:449) and aabb2's exit distance starts at 10000 (K:246), so every
 // comparison against the running best (box entry < best, t < best) comes out as with the 1e7 of hit() K:470 -- and the wide walk's node
 // test needs no min(best, 10000) of its own.

@@ -184,6 +184,19 @@ __device__ __forceinline__ WideRec wide_fetch(WalkRsrc wide, int node) {
   pin_loads(r.A, r.B, r.C, r.D);
   return r;
 }
+// wide_fetch for a caller that knows already whether the lane stands at a leaf (the six-wave lean build: the lane's bit of a wave mask, device_prims.hpp
+// lane_bit), so that `node & 1` is not formed and compared again; the same loads, pinned the same way.  A function of its own so that every other caller
+// of wide_fetch compiles as before.  The record's offset is ONE register (one_register), the units at immediate offsets 16, 32, 48 of it: left to itself
+// the compiler folds the cleared bit 5 into the constants and forms (node << 5) | 32 and (node << 5) | 48 in registers of their own, an instruction each.
+__device__ __forceinline__ WideRec wide_fetch(WalkRsrc wide, int node, bool at_leaf) {
+  const unsigned off = one_register((unsigned)(node >> 1) << 6);
+  WideRec r;
+  r.A = ld_unit_raw(wide, off); r.B = ld_unit_raw(wide, off + 16); r.C = ld_unit_raw(wide, off + 32);
+  no_value(r.D);
+  if (at_leaf) r.D = ld_unit_raw(wide, off + 48);
+  pin_loads(r.A, r.B, r.C, r.D);
+  return r;
+}
 
 // (POP_LEAN: the lean six-wave build's pop, wide_pop_lean above)
 template <bool COUNT, bool POP_LEAN = false, class Sign>
@@ -256,8 +269,13 @@ __device__ __forceinline__ void wide_leaf_compute_uv(const WideRec& r, V3 o, V3 
   float hit_u, hit_v;      // written by every test that can return t > 0, read by a lane that accepts; no value on the other paths: no select, no copy
   const float t = prim_hit_kind((info >> WALK_SLOT_BITS) & 3, mk(f(r.B.w), f(r.C.x), f(r.C.y)), mk(f(r.C.z), f(r.C.w), f(r.D.x)), mk(f(r.D.y), f(r.D.z), f(r.D.w)), o, d, hit_u, hit_v);
   const int slot = info & ((1 << WALK_SLOT_BITS) - 1);
-  const bool cand = t > 0.0f && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot));
-  if (DR_WAVE_ANY(cand)) {
+  // (POP_LEAN: the wave is asked about the one compare `pos`, right where it is formed: its mask is the compare's own result.  `cand` is formed under
+  // branches, and its mask takes a select and a compare more to rebuild.  The gate only spares the wave the box: a wave it lets in without a candidate finds
+  // the lanes' own test closed.)
+  const bool pos = t > 0.0f;
+  const bool any_pos = POP_LEAN && DR_WAVE_ANY(pos);
+  const bool cand = pos && (t < tr.best_t || (t == tr.best_t && (unsigned)slot < (unsigned)tr.best_slot));
+  if (POP_LEAN ? any_pos : DR_WAVE_ANY(cand)) {
     if (cand && slab_sel(o, inv, sg, mn, mx, dist) && leaf_entry_admits(dist, slot, tr.best_t, tr.best_slot)) {
       tr.best_t = t; tr.best_slot = slot;
       *u_word = hit_u; *v_word = hit_v;

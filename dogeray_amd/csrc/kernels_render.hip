@@ -159,6 +159,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
   // the six-wave lean build pops its stack on one straight path (device_wide.hpp wide_pop_lean; it hands no words over: sb stays 0); every other build --
   // its per-frame twin of the present pipeline too -- keeps wide_pop
   constexpr bool POP_LEAN = WIDE && !COOP && !COUNT && !PERFRAME && OCC == 6;
+  // ... and decides who steps on the scalar unit (step_by_masks below): the same steps in the same order, from wave masks instead of per-lane flags
+  constexpr bool STEP_MASKS = POP_LEAN;
   float* const uv_words = reinterpret_cast<float*>(my_stack) + WIDE_STACK * 64;      // this lane's stash, as the leaf step sees it (UV_CARRIED only)
   unsigned long long* const share_key = reinterpret_cast<unsigned long long*>(my_lds + (WIDE ? SHARE_OFF : 0));     // [64], WIDE && COOP only
   unsigned* const share_pend = reinterpret_cast<unsigned*>(my_lds + (WIDE ? SHARE_OFF : 0) + 128);                   // [64]
@@ -255,7 +257,8 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
     }
     const bool waits_for_helpers = WIDE && COOP && share == SHARE_OWNER;      // (only ever true with tr.node == LANE_DONE here or while still walking)
     // (a holding wave -- long pixels, helpers walking for them -- shades as soon as a ray is finished: its pixels' latency is the point)
-    if ((__popcll(walking) < TRAV_MIN || (WIDE && COOP && held)) && (walking == 0ull || __ballot((tr.node == LANE_DONE && !waits_for_helpers) || tr.node == LANE_REFILL) != 0ull)) {
+    // (STEP_MASKS: the count as a scalar int, device_prims.hpp wave_count)
+    if (((STEP_MASKS ? wave_count(walking) < TRAV_MIN : __popcll(walking) < TRAV_MIN) || (WIDE && COOP && held)) && (walking == 0ull || __ballot((tr.node == LANE_DONE && !waits_for_helpers) || tr.node == LANE_REFILL) != 0ull)) {
       unsigned long long t0 = 0;
       DR_MARK("phase_begin");
       if (COUNT) { t0 = __builtin_readcyclecounter(); n_phase++; }
@@ -616,6 +619,30 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
       // (Leaf postponing, "leaves as soon as they outnumber the nodes" and other thresholds: measured and dropped, profiles/r3_t_*, r3_p_*.)
       // (the first step is written out and the further ones loop: one loop over all of them compiles to a 3.5 % slower lean kernel -- the same
       // work, another schedule; profiles/r4_a_cleanup_ab.txt)
+      if (STEP_MASKS) {
+        // STEP_MASKS: one step of the wide walk (the rule and its reasons: at the steps of the loop below, which every other build keeps).  Who steps is the same
+        // for the whole wave, so it is decided from the two ballots on the scalar unit (device_walk.hpp step_masks) and reaches the lanes as exec masks
+        // (device_prims.hpp lane_bit: the masks are wave-uniform, and this runs at the loop's top level with all 64 lanes active).  Spelled per lane the compiler
+        // writes do_leaves and do_nodes into registers, selects, masks and compares again, forms `node & 1` a second time for the fetch and compares cur_tile --
+        // wave-uniform, but held in a VGPR -- on the VALU: some ten vector instructions in front of every step (profiles/step_control_ab.txt).
+        auto step_by_masks = [&]() {
+          const unsigned long long on = __ballot(tr.node >= 0), odd = __ballot(tr.node & 1);
+          const StepMasks m = step_masks(on & odd, on & ~odd, wave_uniform(cur_tile) >= ntiles, PARK_MIN > 0 ? PARK_MIN : 1, !COOP);
+          const bool at_leaf = lane_bit(m.leaf);
+          if (lane_bit(m.step)) {
+            const WideRec r = wide_fetch(walk, tr.node, at_leaf);
+            if (at_leaf) {
+              if (UV_CARRIED) wide_leaf_compute_uv<POP_LEAN>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, uv_words + WS_TOP * 64, uv_words + WS_STEPS * 64);
+              else wide_leaf_compute<COUNT>(r, path.rayo, path.raydir, inv, sg, tr, ws, my_stack, c);
+            }
+            else wide_node_compute<COUNT, POP_LEAN>(r, wr, sg, tr, ws, my_stack, c);
+            steps++;
+          }
+        };
+        step_by_masks();
+        for (int u = 1; u < P_UNROLL; u++) step_by_masks();      // the further steps of an iteration decide anew
+        continue;
+      }
       const bool at_leaf = tr.node >= 0 && (tr.node & 1);
       const unsigned long long leaves = __ballot(at_leaf);
       const unsigned long long nodes = __ballot(tr.node >= 0 && !(tr.node & 1));

@@ -58,6 +58,7 @@ _API = [
     ("hk_cert_factor_k", _F, [_D]),
     ("hk_slab", None, [_Q] + [_P] * 5),
     ("hk_lean_pop", None, [_Q] + [_P] * 4),
+    ("hk_step_masks", None, [_Q] + [_P] * 5),
     ("hk_tri_hit", None, [_Q] + [_P] * 6),
     ("hk_tri_hit_uv", None, [_Q] + [_P] * 7),
     ("hk_tri_barycentrics", None, [_Q] + [_P] * 6),
@@ -233,6 +234,17 @@ def lean_pop(top, sp, stack):
     out = np.zeros((n, 2, 3), np.int32)
     lib().hk_lean_pop(n, *map(_ptr, (top, sp, stack, out)))
     return out[:, 0], out[:, 1]
+
+
+def step_masks(node, draining, leaf_min, exclusive):
+    """device_walk.hpp step_masks on n waves (hk_step_masks): node int32[n, 64] (each lane's link or LANE_* state), draining / leaf_min / exclusive
+    int32[n] -> (uint64[n], uint64[n]): the lanes that take the step, and those of them that take it as leaves"""
+    node, draining, leaf_min, exclusive = (_arr(a, np.int32) for a in (node, draining, leaf_min, exclusive))
+    n = node.shape[0]
+    assert node.shape == (n, 64) and draining.shape == leaf_min.shape == exclusive.shape == (n,)
+    out = np.zeros((n, 2), np.uint64)
+    lib().hk_step_masks(n, *map(_ptr, (node, draining, leaf_min, exclusive, out)))
+    return out[:, 0].copy(), out[:, 1].copy()
 
 
 def tri_hit_uv(o, d, v0, e1, e2):

@@ -100,6 +100,20 @@ void hk_lean_pop(long long n, const uint32_t* top, const int32_t* sp, const uint
     }
   }
 }
+// device_walk.hpp step_masks on n waves (tests/test_step_masks_host.py): wave i is the 64 lane words node[64 * i ..] (a record's link, or LANE_DONE /
+// LANE_REFILL / LANE_RETIRED), from which the two ballots are formed as render_persistent_kernel's step_by_masks forms them -- walking and odd, walking and
+// even --, with its flags draining[i], leaf_min[i], exclusive[i]; out[2 * i] = the lanes that step, out[2 * i + 1] = those of them that step as leaves
+void hk_step_masks(long long n, const int32_t* node, const int32_t* draining, const int32_t* leaf_min, const int32_t* exclusive, uint64_t* out) {
+  for (long long i = 0; i < n; i++) {
+    unsigned long long on = 0ull, odd = 0ull;
+    for (int l = 0; l < 64; l++) {
+      if (node[64 * i + l] >= 0) on |= 1ull << l;
+      if (node[64 * i + l] & 1) odd |= 1ull << l;
+    }
+    const StepMasks m = step_masks(on & odd, on & ~odd, draining[i] != 0, leaf_min[i], exclusive[i] != 0);
+    out[2 * i] = m.step; out[2 * i + 1] = m.leaf;
+  }
+}
 // hit_tri (device_intersect.hpp tri_hit) on n ray / triangle pairs: t or -1
 void hk_tri_hit(long long n, const float* o, const float* d, const float* v0, const float* e1, const float* e2, float* t) {
   for (long long i = 0; i < n; i++)

@@ -16,6 +16,9 @@ __device__ __forceinline__ uint32_t xorwow_combine(uint32_t t, uint32_t v4) { re
 // ---- the wave: one lane
 #define DR_WAVE_ANY(p) (p)
 __device__ __forceinline__ bool first_active_lane() { return true; }
+__device__ __forceinline__ bool lane_bit(unsigned long long wave_mask) { return (wave_mask & 1ull) != 0ull; }      // (the one lane is lane 0)
+__device__ __forceinline__ int wave_count(unsigned long long wave_mask) { return __builtin_popcountll(wave_mask); }
+__device__ __forceinline__ int wave_uniform(int v) { return v; }
 #define DR_PIN(s) do {} while (0)
 constexpr bool LEAF_PRIM_FIRST = false;      // the reference's order: the box, then the primitive (L counts primitives tested behind a passed box)
 constexpr bool HIT_UV_CARRIED = false, HIT_FETCH_LAZY = false;      // the host's walks and renders keep the plain shade path; hk_hit_inputs names the forms itself
@@ -31,6 +34,7 @@ __device__ __forceinline__ u32x4 ld_unit_raw(WalkRsrc r, unsigned byte_off) {
 }
 __device__ __forceinline__ void no_value(u32x4& v) { v = u32x4{0u, 0u, 0u, 0u}; }
 __device__ __forceinline__ void pin_loads(u32x4&, u32x4&, u32x4&, u32x4&) {}
+__device__ __forceinline__ unsigned one_register(unsigned v) { return v; }
 
 // ---- three-input bit operations
 __device__ __forceinline__ unsigned bit_select(unsigned if0, unsigned if1, unsigned m) { return (if0 & ~m) | (if1 & m); }
