@@ -11,46 +11,48 @@ using namespace dr;
 namespace {
 
 // The options dr_context_set_option stores, dr_context_get_option reads back and DOGERAY_OPTIONS parses: the member, the values accepted
-// (lo .. hi, of those the bits of `only` where it is not 0; lo == ANY: every value, stored as value != 0) and whether a change makes the
-// stored tile order stale.  What else setting one of them does is written out in set_option.
+// (lo .. hi, of those the bits of `only` where it is not 0; lo == ANY: every value, stored as value != 0) and which of a launch's caches a change
+// makes stale (context.hpp: ORDER the tile order, WORDS the camera rays' tile words).  What else setting one of them does is written out in set_option.
+// (ODDITY: sky_tiles drops the words, which do not depend on it; the sky split, which does not depend on it either, follows their recomputation.)
 constexpr int ANY = INT_MIN;
-struct Option { const char* name; int dr_context::*member; int lo, hi; unsigned only; bool reorders; };
+enum : unsigned { NOTHING = 0, ORDER = 1, WORDS = 2 };
+struct Option { const char* name; int dr_context::*member; int lo, hi; unsigned only; unsigned invalidates; };
 const Option OPTIONS[] = {
-    {"kernel", &dr_context::kernel, DR_KERNEL_TILE, DR_KERNEL_PERSISTENT, 0, false},
-    {"occupancy", &dr_context::occupancy, 4, 6, 0, false},
-    {"schedule", &dr_context::schedule, 0, 2, 0, false},
-    {"heavy_factor", &dr_context::heavy_factor, -1, 1000, 0, true},
-    {"coop_steps", &dr_context::coop_steps, 0, INT_MAX, 0, false},
-    {"coop_lanes", &dr_context::coop_lanes, 1, 64, 0, false},
-    {"split_parts", &dr_context::split_parts, 1, 8, 1u << 1 | 1u << 2 | 1u << 4 | 1u << 8, false},
-    {"split_waves", &dr_context::split_waves, 1, 1000, 0, true},
-    {"split_steps", &dr_context::split_steps, 16, 4080, 0, true},      // (stored rounded down to a multiple of 16)
-    {"short_one_queue", &dr_context::short_one_queue, ANY, 0, 0, true},
-    {"coop_rounds", &dr_context::coop_rounds, 1, 16, 0, false},
-    {"reserve_cus", &dr_context::reserve_cus, 0, 64, 0, false},
-    {"wave_log", &dr_context::wave_log_on, 0, 1, 0, false},
-    {"coop_tiles_per_wave", &dr_context::coop_tiles_per_wave, 0, INT_MAX, 0, false},
-    {"pipe_streams", &dr_context::pipe_streams, 2, dr_context::PIPE_STREAMS, 0, false},
-    {"pipe_lean", &dr_context::pipe_lean, ANY, 0, 0, false},
-    {"pipe_group", &dr_context::pipe_group, 1, dr_context::PIPE_GROUP_MAX, 0, false},
-    {"xcd_regions", &dr_context::xcd_regions, ANY, 0, 0, true},
-    {"batch_frames", &dr_context::batch_frames, 1, 256, 0, false},
-    {"feedback", &dr_context::feedback, ANY, 0, 0, true},
-    {"order_follows_camera", &dr_context::order_follows_camera, ANY, 0, 0, false},
-    {"feedback_every", &dr_context::feedback_every, 1, INT_MAX, 0, false},
-    {"wide_tree", &dr_context::wide_tree, 0, 2, 0, false},              // takes effect at the next dr_context_upload_scene
-    {"denoise_tiles", &dr_context::denoise_tiles, 0, 1, 0, false},
-    {"moments", &dr_context::moments_opt, 0, 1, 0, false},              // takes effect at the next dr_accum_reset
-    {"denoise_variance", &dr_context::denoise_variance, 0, 1, 0, false},
-    {"camera_cert", &dr_context::camera_cert, 0, 1, 0, false},
-    {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, false},
-    {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, false},
-    {"camera_entry", /* (as above) */ &dr_context::camera_entry, 0, 1, 0, false},
-    {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 2, 0, false},
-    {"trace_kernel", /* (as above) */ &dr_context::trace_kernel, 0, 2, 0, false},
-    {"radiance_kernel", /* (as above) */ &dr_context::radiance_kernel, 0, 2, 0, false},
-    {"allhits_kernel", /* (as above) */ &dr_context::allhits_kernel, 0, 2, 0, false},
-    {"sample_order", /* (as above) */ &dr_context::sample_order, 0, 1, 0, false},
+    {"kernel", &dr_context::kernel, DR_KERNEL_TILE, DR_KERNEL_PERSISTENT, 0, NOTHING},
+    {"occupancy", &dr_context::occupancy, 4, 6, 0, NOTHING},
+    {"schedule", &dr_context::schedule, 0, 2, 0, NOTHING},
+    {"heavy_factor", &dr_context::heavy_factor, -1, 1000, 0, ORDER},
+    {"coop_steps", &dr_context::coop_steps, 0, INT_MAX, 0, NOTHING},
+    {"coop_lanes", &dr_context::coop_lanes, 1, 64, 0, NOTHING},
+    {"split_parts", &dr_context::split_parts, 1, 8, 1u << 1 | 1u << 2 | 1u << 4 | 1u << 8, NOTHING},
+    {"split_waves", &dr_context::split_waves, 1, 1000, 0, ORDER},
+    {"split_steps", &dr_context::split_steps, 16, 4080, 0, ORDER},      // (stored rounded down to a multiple of 16)
+    {"short_one_queue", &dr_context::short_one_queue, ANY, 0, 0, ORDER},
+    {"coop_rounds", &dr_context::coop_rounds, 1, 16, 0, NOTHING},
+    {"reserve_cus", &dr_context::reserve_cus, 0, 64, 0, NOTHING},
+    {"wave_log", &dr_context::wave_log_on, 0, 1, 0, NOTHING},
+    {"coop_tiles_per_wave", &dr_context::coop_tiles_per_wave, 0, INT_MAX, 0, NOTHING},
+    {"pipe_streams", &dr_context::pipe_streams, 2, dr_context::PIPE_STREAMS, 0, NOTHING},
+    {"pipe_lean", &dr_context::pipe_lean, ANY, 0, 0, NOTHING},
+    {"pipe_group", &dr_context::pipe_group, 1, dr_context::PIPE_GROUP_MAX, 0, NOTHING},
+    {"xcd_regions", &dr_context::xcd_regions, ANY, 0, 0, ORDER},
+    {"batch_frames", &dr_context::batch_frames, 1, 256, 0, NOTHING},
+    {"feedback", &dr_context::feedback, ANY, 0, 0, ORDER},
+    {"order_follows_camera", &dr_context::order_follows_camera, ANY, 0, 0, NOTHING},
+    {"feedback_every", &dr_context::feedback_every, 1, INT_MAX, 0, NOTHING},
+    {"wide_tree", &dr_context::wide_tree, 0, 2, 0, NOTHING},              // takes effect at the next dr_context_upload_scene
+    {"denoise_tiles", &dr_context::denoise_tiles, 0, 1, 0, NOTHING},
+    {"moments", &dr_context::moments_opt, 0, 1, 0, NOTHING},              // takes effect at the next dr_accum_reset
+    {"denoise_variance", &dr_context::denoise_variance, 0, 1, 0, NOTHING},
+    {"camera_cert", &dr_context::camera_cert, 0, 1, 0, WORDS},
+    {"cert_factor", &dr_context::cert_factor, 1, 10000, 0, WORDS},
+    {"cert_levels", /* (the comment keeps tests/test_host.py's pinned count of rows; documented in the header like the rest) */ &dr_context::cert_levels, 0, 1, 0, WORDS},
+    {"camera_entry", /* (as above) */ &dr_context::camera_entry, 0, 1, 0, WORDS},
+    {"sky_tiles", /* (as above) */ &dr_context::sky_tiles, 0, 2, 0, WORDS},
+    {"trace_kernel", /* (as above) */ &dr_context::trace_kernel, 0, 2, 0, NOTHING},
+    {"radiance_kernel", /* (as above) */ &dr_context::radiance_kernel, 0, 2, 0, NOTHING},
+    {"allhits_kernel", /* (as above) */ &dr_context::allhits_kernel, 0, 2, 0, NOTHING},
+    {"sample_order", /* (as above) */ &dr_context::sample_order, 0, 1, 0, NOTHING},
 };
 
 const Option* find_option(const std::string& name) {
@@ -87,10 +89,28 @@ int set_option(dr_context* c, const std::string& name, int v) {
       c->pipe_next = 0; c->pipe_groups = 0;
     }
   }
-  else if (name == "camera_cert" || name == "cert_factor" || o->member == &dr_context::cert_levels || o->member == &dr_context::camera_entry ||
-           o->member == &dr_context::sky_tiles) c->cert_valid = false;
   c->*(o->member) = v;
-  if (o->reorders) c->order_valid = false;
+  if (o->invalidates & ORDER) c->order.invalidate();
+  if (o->invalidates & WORDS) c->words.invalidate();
+  return DR_OK;
+}
+
+// What the dr_stats_* read-backs share.  stats_ready: the device, the pipeline joined, `ready` asked -- in this order: a held frame's launch may compute
+// what is asked for -- and, when there is something to report, the stream drained.  stats_copy: the first min(have, room) elements to the host
+template <class Ready>
+int stats_ready(dr_context* c, bool& yes, Ready ready) {
+  HIP_TRY(hipSetDevice(c->device));
+  DR_TRY(join_pipeline(c));
+  yes = ready();
+  if (yes) HIP_TRY(hipStreamSynchronize(c->stream));
+  return DR_OK;
+}
+int stats_ready(dr_context* c) { bool yes; return stats_ready(c, yes, [] { return true; }); }
+template <class T, class U>
+int stats_copy(U* out, const T* src, size_t have, size_t room) {
+  static_assert(sizeof(T) == sizeof(U), "element for element");
+  const size_t n = have < room ? have : room;
+  if (n > 0) HIP_TRY(hipMemcpy(out, src, n * sizeof(T), hipMemcpyDeviceToHost));
   return DR_OK;
 }
 
@@ -244,11 +264,12 @@ int dr_context_get_option(const dr_context* c, const char* name, int* value) {
   else if (n == "cert_flagged_permille") {
     // per mille of the last certified view's tiles whose camera rays keep the scene's margin (-1: no certificate in use)
     *value = -1;
-    if (c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0) {
+    if (c->camera_cert && certificate_readable(c->words.state) && c->words.mask) {
+      const int tiles = c->words.state.tiles;
       uint32_t n_flagged = 0;
       if (hipStreamSynchronize(c->stream) != hipSuccess ||
-          hipMemcpy(&n_flagged, c->cert_mask + (c->cert_tiles + 31) / 32 + 1, sizeof(n_flagged), hipMemcpyDeviceToHost) != hipSuccess) { set_error("cannot read the certificate mask"); return DR_ERR_DEVICE; }
-      *value = (int)((1000ull * n_flagged + (unsigned)c->cert_tiles / 2) / (unsigned)c->cert_tiles);
+          hipMemcpy(&n_flagged, c->words.mask + (tiles + 31) / 32 + 1, sizeof(n_flagged), hipMemcpyDeviceToHost) != hipSuccess) { set_error("cannot read the certificate mask"); return DR_ERR_DEVICE; }
+      *value = (int)((1000ull * n_flagged + (unsigned)tiles / 2) / (unsigned)tiles);
     }
   }
   else if (n == "upscale_aov_passes") *value = c->up_passes;                 // AOV passes the last dr_accum_upscale traced
@@ -294,11 +315,9 @@ int dr_stats_reset(dr_context* c) {
 
 int dr_stats_get(dr_context* c, dr_stats* out) {
   if (!c || !out) { set_error("null argument"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(stats_ready(c));
   unsigned long long h[STAT_PHASE];
-  HIP_TRY(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
+  DR_TRY(stats_copy(h, c->counters.p, STAT_PHASE, STAT_PHASE));
   *out = c->stats;
   out->rays = h[STAT_RAYS]; out->node_visits = h[STAT_NODE_VISITS]; out->prim_tests = h[STAT_PRIM_TESTS]; out->shades = h[STAT_SHADES]; out->texels = h[STAT_TEXELS];
   if (c->count) out->samples = h[STAT_SAMPLES];
@@ -309,61 +328,50 @@ int dr_stats_get(dr_context* c, dr_stats* out) {
 
 int dr_stats_phase_counts(dr_context* c, unsigned long long* out, int n) {
   if (!c || !out || n < 0 || n > COUNTER_WORDS - STAT_PHASE) { set_error("bad argument"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (n > 0) HIP_TRY(hipMemcpy(out, c->counters + STAT_PHASE, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return DR_OK;
+  DR_TRY(stats_ready(c));
+  return stats_copy(out, c->counters + STAT_PHASE, (size_t)n, (size_t)n);
 }
 
 int dr_stats_cert_mask(dr_context* c, uint32_t* out, int max_words, int* n_tiles) {
   if (!c || !n_tiles || max_words < 0 || (max_words > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
-  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_mask && c->cert_tiles > 0)) return DR_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const int words = (c->cert_tiles + 31) / 32;
-  *n_tiles = c->cert_tiles;
-  if (max_words > 0) HIP_TRY(hipMemcpy(out, c->cert_mask, (size_t)(words < max_words ? words : max_words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return DR_OK;
+  bool have;
+  DR_TRY(stats_ready(c, have, [&] { return c->camera_cert && certificate_readable(c->words.state) && c->words.mask; }));
+  if (!have) return DR_OK;
+  *n_tiles = c->words.state.tiles;
+  return stats_copy(out, c->words.mask.p, (size_t)(*n_tiles + 31) / 32, (size_t)max_words);
 }
 
 int dr_stats_cert_levels(dr_context* c, uint8_t* out_bytes, int max, int* n_tiles) {
   if (!c || !n_tiles || max < 0 || (max > 0 && !out_bytes)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
-  if (!(c->camera_cert && c->cert_valid && c->cert_ok && c->cert_level && c->cert_tiles > 0)) return DR_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  *n_tiles = c->cert_tiles;
-  if (max > 0) HIP_TRY(hipMemcpy(out_bytes, c->cert_level, (size_t)(c->cert_tiles < max ? c->cert_tiles : max), hipMemcpyDeviceToHost));
-  return DR_OK;
+  bool have;
+  DR_TRY(stats_ready(c, have, [&] { return c->camera_cert && certificate_readable(c->words.state) && c->words.level; }));
+  if (!have) return DR_OK;
+  *n_tiles = c->words.state.tiles;
+  return stats_copy(out_bytes, reinterpret_cast<const uint8_t*>(c->words.level.p), (size_t)*n_tiles, (size_t)max);      // (a byte per tile, four to a word)
 }
 
 int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles) {
   if (!c || !n_tiles || max < 0 || (max > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_tiles = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
-  if (!(c->camera_entry && c->cert_valid && c->entry_ok && c->cert_word && c->cert_tiles > 0)) return DR_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  *n_tiles = c->cert_tiles;
-  const int n = c->cert_tiles < max ? c->cert_tiles : max;
-  if (n > 0) HIP_TRY(hipMemcpy(out, c->cert_word, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (int t = 0; t < n; t++) out[t] >>= ENTRY_SHIFT;      // (arithmetic: ENTRY_NONE stays -1)
+  bool have;
+  DR_TRY(stats_ready(c, have, [&] { return c->camera_entry && entry_table_readable(c->words.state) && c->words.word; }));
+  if (!have) return DR_OK;
+  *n_tiles = c->words.state.tiles;
+  DR_TRY(stats_copy(out, c->words.word.p, (size_t)*n_tiles, (size_t)max));
+  for (int t = 0; t < *n_tiles && t < max; t++) out[t] >>= ENTRY_SHIFT;      // (arithmetic: ENTRY_NONE stays -1)
   return DR_OK;
 }
 
 int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry) {
   if (!c || !n_sky || !n_geometry) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n_sky = 0; *n_geometry = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));      // (a held frame's launch may compute what is asked for)
-  if (!c->sky_split_last || !c->sky_counts) return DR_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  bool have;
+  DR_TRY(stats_ready(c, have, [&] { return c->sky.state.last && c->sky.counts; }));
+  if (!have) return DR_OK;
   unsigned h[2] = {0, 0};
-  HIP_TRY(hipMemcpy(h, c->sky_counts, sizeof(h), hipMemcpyDeviceToHost));
+  DR_TRY(stats_copy(h, c->sky.counts.p, 2, 2));
   *n_sky = (int)h[0]; *n_geometry = (int)h[1];
   return DR_OK;
 }
@@ -371,39 +379,32 @@ int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry) {
 int dr_stats_wave_log(dr_context* c, unsigned long long* out, int max_waves, int* n_waves) {
   if (!c || !out || !n_waves || max_waves < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wave_log) { set_error("wave log is off (option wave_log)"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  DR_TRY(stats_ready(c));
   const int n = c->wave_log_waves < max_waves ? c->wave_log_waves : max_waves;
-  if (n > 0) HIP_TRY(hipMemcpy(out, c->wave_log, (size_t)n * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  DR_TRY(stats_copy(out, c->wave_log.p, (size_t)n * 16, (size_t)n * 16));
   *n_waves = n;
   return DR_OK;
 }
 
 int dr_stats_pixel_cost(dr_context* c, unsigned* out, size_t capacity, size_t* n) {
   if (!c || !out || !n) { set_error("bad argument"); return DR_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const size_t have = c->pixel_cost ? (size_t)c->order_capacity * 64 : 0;      // pixel (tile, lane-in-tile) at tile * 64 + lane, tile = block column * gy + block row
-  const size_t m = have < capacity ? have : capacity;
-  if (m > 0) HIP_TRY(hipMemcpy(out, c->pixel_cost, m * sizeof(unsigned), hipMemcpyDeviceToHost));
-  *n = m;
+  DR_TRY(stats_ready(c));
+  const size_t have = c->order.pixel_cost ? (size_t)c->order.state.capacity * 64 : 0;      // pixel (tile, lane-in-tile) at tile * 64 + lane, tile = block column * gy + block row
+  DR_TRY(stats_copy(out, c->order.pixel_cost.p, have, capacity));
+  *n = have < capacity ? have : capacity;
   return DR_OK;
 }
 
 int dr_stats_tile_order(dr_context* c, int* order, size_t capacity, size_t* n, int* region_start, int* args) {
   if (!c || !n || !region_start || !args || (capacity > 0 && !order)) { set_error("bad argument"); return DR_ERR_INVALID; }
   *n = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  DR_TRY(join_pipeline(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (!c->order_valid || !c->tile_order || !c->region_start) return DR_OK;
-  for (int k = 0; k < 5; k++) args[k] = c->order_args[k];
-  const size_t tiles = (size_t)c->order_args[0];
-  HIP_TRY(hipMemcpy(region_start, c->region_start, (2 * MAX_REGIONS + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  const size_t m = tiles < capacity ? tiles : capacity;
-  if (m > 0) HIP_TRY(hipMemcpy(order, c->tile_order, m * sizeof(int), hipMemcpyDeviceToHost));
+  DR_TRY(stats_ready(c));
+  const dr::TileOrder& o = c->order;
+  if (!o.state.valid || !o.order || !o.region_start) return DR_OK;
+  for (int k = 0; k < 5; k++) args[k] = o.state.args[k];
+  const size_t tiles = (size_t)o.state.args[0];
+  DR_TRY(stats_copy(region_start, o.region_start.p, 2 * MAX_REGIONS + 1, 2 * MAX_REGIONS + 1));
+  DR_TRY(stats_copy(order, o.order.p, tiles, capacity));
   *n = tiles;
   return DR_OK;
 }

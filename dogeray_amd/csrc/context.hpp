@@ -1,7 +1,8 @@
 // The device context (struct dr_context: resident scene, options, accumulator, pipeline state) and what the context_*.cpp files share: the error
-// macros, the owning device buffer, the guide caches' key, the launch site, and the internal functions one file defines and another calls.
+// macros, the owning device buffer, the guide caches' key, the launch site, the owners of a render launch's three caches (launch_state.hpp: tile order,
+// camera words, sky split), and the internal functions one file defines and another calls.
 //   context.cpp            create / destroy / upload / stripe / traversal / options / statistics
-//   context_render.cpp     per-launch constants, cost feedback, grazing certificate, the launches of dr_render_frame / dr_render_accumulate*
+//   context_render.cpp     per-launch constants, the three caches around a launch, the launches of dr_render_frame / dr_render_accumulate*
 //   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
 //   context_query.cpp      what the queries on caller lists share: staging in and out, scratch, cursor, the object map's upload
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "launch_state.hpp"
 #include "params_host.hpp"
 #include "scene_host.hpp"
 
@@ -123,6 +125,64 @@ struct LaunchSite {
   bool lean;                // option pipe_lean: the launch counts 0 for coop_tiles_per_wave
 };
 
+// The three caches of a render launch (launch_state.hpp holds their state and every rule about it; context_render.cpp is the only writer).  Each owns
+// its buffers, and invalidate() is all that anything outside may do to it.
+
+// Cost feedback of the persistent kernel: per-pixel cost of the last frame, per-tile cost, and the tile order made from them
+struct TileOrder {
+  DevMem<unsigned> pixel_cost, tile_cost;
+  DevMem<int> order, region_start;
+  OrderState state;
+  void invalidate() { state.valid = false; }
+  // room for the state.capacity tiles order_begin asked for (OrderUse::grow: the stored order is gone already); none at all if that fails
+  int grow(hipStream_t stream) {
+    const size_t tiles = (size_t)state.capacity;
+    state.capacity = 0;
+    DR_TRY(pixel_cost.grow(tiles * 64, stream)); DR_TRY(tile_cost.grow(tiles, stream));
+    DR_TRY(region_start.grow(2 * MAX_REGIONS + 1, stream)); DR_TRY(order.grow(tiles, stream));
+    state.capacity = (int)tiles;
+    return DR_OK;
+  }
+};
+
+// The camera rays' grazing certificate and entry table of one view, computed on the launch's stream by launch_cert_mask and, behind
+// it, launch_camera_entry, and kept under one key: per tile one bit of the mask (set: its camera rays keep the scene's margin), one byte (its grade on
+// the ladder of option cert_levels) and one word, entry code << ENTRY_SHIFT | grade -- what the render kernel reads (RenderParams cert_level)
+struct CameraWords {
+  DevMem<uint32_t> mask;
+  DevMem<uint32_t> level;                  // the grades, four tiles to a word
+  DevMem<uint32_t> mm;                     // scratch: the lowest and the highest rank per tile
+  DevMem<uint32_t> word;
+  CameraWordsState state;
+  void invalidate() { state.valid = false; }
+  // room for the words of `tiles` tiles (mm_too: and the entry table's scratch); what the buffers held does not survive
+  int grow(int tiles, bool mm_too, hipStream_t stream) {
+    state.valid = false;
+    DR_TRY(level.grow(cert_level_words(tiles), stream)); DR_TRY(word.grow((size_t)tiles, stream));
+    if (mm_too) DR_TRY(mm.grow(entry_mm_words(tiles), stream));
+    return DR_OK;
+  }
+  int grow_mask(int tiles, int n_levels, hipStream_t stream) { state.valid = false; return mask.grow(cert_mask_words(tiles, n_levels), stream); }
+};
+
+// Sky tiles: a lean launch with an entry table hands the tiles of code ENTRY_NONE to sky_tiles_kernel, or to its own retiring waves,
+// and the rest of its order to the persistent kernel's queues (context_render.cpp sky_split).  The split is made on the launch's stream and kept while
+// the words and the order it was made from are the same (sky_split_kernel takes 0.53 % of a 32-frame launch of the bench view,
+// profiles/sky_tiles_ab.txt); TileOrder's order and region_start stay whole
+struct SkySplit {
+  DevMem<int> launch_order, launch_region_start, list;
+  DevMem<unsigned> counts;                 // [0] sky tiles, [1] geometry tiles of the last split
+  SkySplitState state;
+  void invalidate() { state.valid = false; }
+  bool room(int tiles) const { return launch_order.n >= (size_t)tiles && list.n >= (size_t)tiles && launch_region_start.p && counts.p; }
+  int grow(int tiles, hipStream_t stream) {
+    state.valid = false;
+    DR_TRY(launch_order.grow((size_t)tiles, stream)); DR_TRY(list.grow((size_t)tiles, stream));
+    DR_TRY(launch_region_start.grow(2 * MAX_REGIONS + 1, stream)); DR_TRY(counts.grow(2, stream));
+    return DR_OK;
+  }
+};
+
 constexpr int TILE_COUNTERS = 1024;
 constexpr int LAUNCH_COUNTERS = MAX_REGIONS + 1;      // a launch's block of them: a cursor per tile queue, then the sky units' cursor (option sky_tiles = 2)
 
@@ -191,40 +251,18 @@ struct dr_context {
   unsigned long long* m2 = nullptr; int m2_cur = 0;
   DevMem<unsigned long long> err_counts;
   int denoise_tiles = 1;                   // option: a-trous passes on 16x16 lattice tiles in LDS (1) or with every tap loaded from the planes (0)
-  // the camera rays' grazing certificate: per view, one bit per tile of the launch (set: its camera rays keep the scene's margin),
-  // and one byte per tile (its grade on the ladder of option cert_levels: what the render kernel reads), computed on the launch's stream by
-  // launch_cert_mask; keyed by settings13, frame, stripe, tile grid, scene upload, cert_factor and cert_levels
+  // the camera rays' grazing certificate and entry table: the options, the wide tree's side arrays the table is made from, and the
+  // words of the last view (launch_state.hpp same_words_view: keyed by settings13, frame, stripe, tile grid, scene upload and the four options)
   int camera_cert = 1;                     // option: camera rays of tiles the certificate clears carry the certified margin (0: every ray the scene's)
   int cert_factor = 40;                    // option: the certified |a^| in units of hit_tri's 1e-4 cut-off (a_star = cert_factor * 1e-4)
   int cert_levels = 1;                     // option: 1 the graded ladder cert_factor x {1/4, 1/2, 1, 2, 4} (params_host.hpp cert_ladder), 0 the single step cert_factor
-  DevMem<uint32_t> cert_mask;
-  DevMem<uint32_t> cert_level;             // the grades, four tiles to a word
-  bool cert_valid = false;                 // cert_key's mask is computed (or known to be unusable: cert_ok false)
-  bool cert_ok = false;                    // ... and the view has a certificate
-  bool entry_ok = false;                   // ... and an entry table (option camera_entry)
-  float cert_key[22] = {0};
-  float cert_seen[22] = {0};               // the key of the last single-frame launch that found no mask
-  float cert_k[dr::CERT_MAX_LEVELS + 1] = {1}; // the margin's factor of a tile of grade g ([0] = 1; [g] = 1e-4 / the ladder's step g - 1, rounded up)
-  int cert_tiles = 0;                      // tiles of the keyed launch
-  // the camera rays' entry table of the same view, computed behind the certificate by launch_camera_entry and kept under the same
-  // key: a word per tile, entry code << 3 | grade -- what the lean and the counting build read
   int camera_entry = 1;                    // option: a tile's camera rays start at the lowest record that holds every leaf they can reach (0: at the root)
   DevMem<uint32_t> wide_leaf_rec, wide_range;   // the wide tree's side arrays (linearise.hpp): rank -> leaf record; record -> the ranks under it
   int wide_leaves = 0;
-  DevMem<uint32_t> entry_mm;               // scratch: the lowest and the highest rank per tile
-  DevMem<uint32_t> cert_word;              // a word per tile: entry code << ENTRY_SHIFT | grade (RenderParams cert_level)
-  // sky tiles: a lean launch with an entry table hands the tiles of code ENTRY_NONE to sky_tiles_kernel and the rest of its order to the
-  // persistent kernel (context_render.cpp enqueue_frame).  The split is made on the launch's stream and kept while the words and the order it was
-  // made from are the same (sky_key: cert_gen, order in use, order_gen, tiles, regions -- sky_split_kernel takes 0.53 % of a 32-frame launch of the bench
-  // view, profiles/sky_tiles_ab.txt); tile_order / region_start above stay whole
-  int sample_order = DR_SAMPLE_ORDER;                   // option: which samples of a tile share a unit of the queue (launch_plan.hpp tile_sample): 0 a frame's 64 pixels, 1 a pixel's frames
+  dr::CameraWords words;
+  int sample_order = DR_SAMPLE_ORDER;      // option: which samples of a tile share a unit of the queue (launch_plan.hpp tile_sample): 0 a frame's 64 pixels, 1 a pixel's frames
   int sky_tiles = 2;                       // option: 0 every tile goes through the persistent kernel; 1 sky_tiles_kernel in front of it; 2 its retiring waves
-  DevMem<int> launch_order, launch_region_start, sky_list;
-  DevMem<unsigned> sky_counts;             // [0] sky tiles, [1] geometry tiles of the last split
-  bool sky_split_last = false;             // the last launch was split (dr_stats_sky_tiles)
-  uint64_t cert_gen = 0;                   // computations of the tiles' words so far (cert_prepare)
-  uint64_t order_gen = 0;                  // computations of tile_order so far (launch_tile_feedback)
-  uint64_t sky_key[5] = {0, 0, 0, 0, 0}; bool sky_key_valid = false;      // what the launch's own pair and sky_list were split from
+  dr::SkySplit sky;
   // frame + accumulator
   DevMem<int32_t> frame;
   DevMem<int32_t> accum; int accW = 0, accH = 0;
@@ -232,16 +270,11 @@ struct dr_context {
   DevMem<int32_t> packed[2];
   DevMem<unsigned long long> counters;
   DevMem<unsigned> tile_counters; int tile_cursor = 0; int num_cus = 256;
-  // cost feedback (persistent kernel): per-pixel cost of the last frame, per-tile cost, tile order
-  DevMem<unsigned> pixel_cost, tile_cost; DevMem<int> tile_order, region_start;
-  int order_capacity = 0;          // tiles the three buffers are sized for
-  bool order_valid = false;        // tile_order was computed for `order_key`
-  int order_age = 0;               // launches since the view (order_key) changed
+  // cost feedback (persistent kernel): its options, and the tile order of the last view
+  int feedback = 1;
   int order_follows_camera = 1;    // a view with the same frame geometry but other settings starts from the previous view's tile order
   int feedback_every = 8;          // ... the order is recomputed after the first two of them and then after every feedback_every-th
-  float order_key[18] = {0};       // settings13 + W, H, stripe, tile grid of the frame the order belongs to
-  int order_args[5] = {0, 0, 0, 0, 0};      // the last launch_tile_feedback enqueued: tiles, regions, heavy_factor, split_steps, split_limit (dr_stats_tile_order)
-  int feedback = 1;
+  dr::TileOrder order;
   int stripe_mod = 1, stripe_rem = 0;
   int traversal = DR_TRAVERSAL_WIDE;
   int count = 0;
@@ -318,6 +351,7 @@ inline bool uses_persistent(const dr_context* c) { return c->kernel == DR_KERNEL
 
 // context_render.cpp
 void fill_scene(const dr_context* c, RenderParams& P);      // the resident scene's buffers
+ViewKey view_key(const dr_context* c, const RenderParams& P);      // the launch's view: make_params' settings, P's geometry, the scene and the words' options
 int make_params(dr_context* c, const LaunchSite& site, const float* st, int W, int H, float background, uint64_t seed, RenderParams& P, int batch_hint = 1);
 PersistentCfg persistent_cfg(const dr_context* c, const LaunchSite& site);
 int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in);

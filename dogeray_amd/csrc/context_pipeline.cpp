@@ -126,14 +126,7 @@ int pipeline_flush_some(dr_context* c, int n) {
   const int tiles = P.ncols * P.gy;
   // the tile order and the costs it is made from are shared by all launches: a launch that refreshes them runs alone (after the other
   // streams' newest launches, and the launches after it wait for the refresh); all others read the order as it is
-  bool refresh = false;
-  if (c->feedback && uses_persistent(c) && tiles > 0) {
-    float geom[5];
-    order_geometry(P, geom);
-    // (a refresh costs the overlap of two launches, 0.89 against 0.82 ms/frame when every 8th single-frame launch refreshes: four times rarer here)
-    refresh = !c->order_valid || c->order_capacity < tiles || memcmp(c->order_key + 13, geom, sizeof(geom)) != 0 || c->order_age < 2 ||
-              c->order_age % (4 * c->feedback_every) == 0;
-  }
+  const bool refresh = c->feedback && uses_persistent(c) && tiles > 0 && order_pipeline_refresh(c->order.state, view_key(c, P), tiles, c->feedback_every);
   site.hold_order = !refresh;
   if (c->pipe_barrier_set) HIP_TRY(hipStreamWaitEvent(rs, c->pipe_barrier, 0));
   // the tile counters are cleared (on this launch's stream) when the cursor wraps: like a refresh, that launch runs alone -- nobody may

@@ -1,4 +1,4 @@
-// Render launches: settings13 -> per-launch constants, the cost feedback and the grazing certificate around a launch of the persistent or the
+// Render launches: settings13 -> per-launch constants, the three caches of launch_state.hpp (tile order, tile words, sky split) around a launch of the persistent or the
 // per-tile kernel, and the calls that render on the context's own stream (dr_render_frame, dr_render_accumulate, dr_render_accumulate_async,
 // dr_context_synchronize).  Replaces CudaStarter (kernel.cu K:2562-2669), which mallocs, uploads the whole scene, launches, synchronises,
 // downloads and frees on every call.
@@ -43,82 +43,62 @@ PersistentCfg persistent_cfg(const dr_context* c, const LaunchSite& site) {
   return cfg;
 }
 
-namespace {
-
-// Cost-feedback buffers for `tiles` tiles; returns the order to use for this launch (or null)
-// and the per-pixel cost buffer to fill (or null).
-void feedback_buffers(dr_context* c, const LaunchSite& site, const RenderParams& P, int tiles, const int*& order, unsigned*& pcost) {
-  order = nullptr; pcost = nullptr;
-  if (!c->feedback) return;
-  if (c->order_capacity < tiles) {
-    c->order_capacity = 0; c->order_valid = false;
-    if (c->pixel_cost.grow((size_t)tiles * 64, site.stream) != DR_OK || c->tile_cost.grow((size_t)tiles, site.stream) != DR_OK ||
-        c->region_start.grow(2 * MAX_REGIONS + 1, site.stream) != DR_OK || c->tile_order.grow((size_t)tiles, site.stream) != DR_OK)
-      return;
-    c->order_capacity = tiles;
-  }
-  // the stored order belongs to one view: same settings, size and stripe (progressive frames)
-  float key[18] = {0};
-  memcpy(key, c->cur_settings, 13 * sizeof(float));
-  order_geometry(P, key + 13);
-  if (c->order_valid && memcmp(c->order_key, key, sizeof(key)) == 0) order = c->tile_order;
-  else if (c->order_valid && c->order_follows_camera && memcmp(c->order_key + 13, key + 13, 5 * sizeof(float)) == 0) {
-    // same frame geometry, other camera / depth / samples (an interactive viewer moving the camera, K:2341-2500: every frame is a new
-    // view): the last view's costs are a better guess than none -- any order is a valid order -- and they are refreshed at once
-    order = c->tile_order;
-    memcpy(c->order_key, key, sizeof(key));
-    c->order_age = 0;
-  } else { memcpy(c->order_key, key, sizeof(key)); c->order_valid = false; }
-  pcost = c->pixel_cost;
+ViewKey view_key(const dr_context* c, const RenderParams& P) {
+  ViewKey k;
+  memcpy(k.st, c->cur_settings, sizeof(k.st));
+  k.W = P.W; k.H = P.H; k.stripe_mod = P.stripe_mod; k.stripe_rem = P.stripe_rem; k.ncols = P.ncols; k.gy = P.gy; k.regions = P.regions;
+  k.scene_gen = c->scene_gen;
+  k.cert_factor = c->cert_factor; k.cert_levels = c->cert_levels; k.camera_entry = c->camera_entry; k.camera_cert = c->camera_cert;
+  return k;
 }
 
-// The camera rays' grazing certificate of the launch's view and their entry table: reuses the cached tile words when the key matches,
-// recomputes them on the site's stream otherwise -- except in a pipelined launch that may run beside others reading them (site.hold_order): that one
-// keeps the scene's margin and the root.  The two are independent -- the certificate needs a tree with own bounds (option camera_cert), the table any
-// wide tree (option camera_entry) -- and share the view, the key and the word per tile that the kernel reads.
+namespace {
+
+// The cost feedback of a launch (launch_state.hpp order_begin): the order its queues hold (or null) and the per-pixel cost buffer it fills (or null)
+OrderUse feedback_buffers(dr_context* c, const LaunchSite& site, const ViewKey& key, int tiles, const int*& order, unsigned*& pcost) {
+  OrderUse use = order_begin(c->order.state, key, tiles, c->feedback != 0, c->order_follows_camera != 0, site.hold_order);
+  if (use.grow && c->order.grow(site.stream) != DR_OK) use = {false, false, false};
+  order = use.use_order ? c->order.order.p : nullptr;
+  pcost = use.record_costs ? c->order.pixel_cost.p : nullptr;
+  return use;
+}
+
+// The camera rays' grazing certificate of the launch's view and their entry table: what launch_state.hpp camera_words_plan says -- the
+// cached tile words are reused, or computed on the site's stream.  The two are independent -- the certificate needs a tree with own bounds (option
+// camera_cert), the table any wide tree (option camera_entry) -- and share the view, the key and the word per tile that the kernel reads.
 // Without either P keeps cert_level = null and wide_cert_k = 1: every ray carries the scene's margin and starts at the root, as before.
-void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles) {
+void cert_prepare(dr_context* c, const LaunchSite& site, const ViewKey& key, RenderParams& P, int tiles) {
   P.cert_level = nullptr;
   for (float& k : P.wide_cert_k) k = 1.0f;
+  CameraWords& w = c->words;
   const bool want_cert = c->camera_cert && c->wide_own_bounds > 0 && c->wide_mu.e > 0.0f;
   const bool want_entry = c->camera_entry && c->wide_leaf_rec && c->wide_range && c->wide_leaves > 0;
-  if ((!want_cert && !want_entry) || traversal_of(c) != DR_TRAVERSAL_WIDE || !c->wide || tiles <= 0) return;
-  float key[22] = {0};
-  memcpy(key, c->cur_settings, 13 * sizeof(float));
-  key[13] = (float)P.W; key[14] = (float)P.H; key[15] = (float)P.stripe_mod; key[16] = (float)P.stripe_rem; key[17] = (float)P.ncols; key[18] = (float)P.gy;
-  key[19] = (float)(c->scene_gen & 0xffffff); key[20] = (float)c->cert_factor; key[21] = (float)(c->cert_levels + 2 * c->camera_entry + 4 * c->camera_cert);
-  if (!(c->cert_valid && memcmp(c->cert_key, key, sizeof(key)) == 0)) {
-    if (site.hold_order) return;
-    // a single-frame launch of a view not seen before (a moving camera: every frame a new view) does not pay for the mask and the table (more than
-    // they save in one frame): the view's second launch, or any launch of several frames, computes them
-    if (P.batch < 2 && memcmp(c->cert_seen, key, sizeof(key)) != 0) { memcpy(c->cert_seen, key, sizeof(key)); return; }
+  const CameraWordsPlan plan = camera_words_plan(w.state, key, want_cert, want_entry, traversal_of(c) == DR_TRAVERSAL_WIDE && c->wide, tiles, site.hold_order, P.batch);
+  if (plan != WORDS_REUSE && plan != WORDS_COMPUTE) return;
+  if (plan == WORDS_COMPUTE) {
     const double a_star = 1e-4 * (double)c->cert_factor;
     CertView cv;
-    c->cert_valid = false;
-    c->cert_ok = c->entry_ok = false;
-    c->cert_gen++;
+    bool cert_ok = false, entry_ok = false;
+    camera_words_begin(w.state);
     // (the table asks nothing of the view's E: a scene without own bounds passes any)
     if (fill_cert_view(P, a_star, want_cert ? c->wide_mu.e : 1.0f, cv)) {
-      if (c->cert_level.grow(cert_level_words(tiles), site.stream) != DR_OK || c->cert_word.grow((size_t)tiles, site.stream) != DR_OK ||
-          (want_entry && c->entry_mm.grow(entry_mm_words(tiles), site.stream) != DR_OK)) return;
-      for (float& k : c->cert_k) k = 1.0f;
+      if (w.grow(tiles, want_entry, site.stream) != DR_OK) return;
+      for (float& k : w.state.k) k = 1.0f;
       if (want_cert) {
         cert_ladder(c->cert_factor, c->cert_levels != 0, cv);
-        if (c->cert_mask.grow(cert_mask_words(tiles, cv.n_levels), site.stream) != DR_OK) return;
-        launch_cert_mask(site.stream, c->prims, c->n_prims, cv, c->cert_mask, c->cert_level, tiles);
-        for (int g = 1; g <= CERT_MAX_LEVELS; g++) c->cert_k[g] = g <= cv.n_levels ? cert_factor_k(cv.level_a[g - 1]) : 1.0f;
+        if (w.grow_mask(tiles, cv.n_levels, site.stream) != DR_OK) return;
+        launch_cert_mask(site.stream, c->prims, c->n_prims, cv, w.mask, w.level, tiles);
+        for (int g = 1; g <= CERT_MAX_LEVELS; g++) w.state.k[g] = g <= cv.n_levels ? cert_factor_k(cv.level_a[g - 1]) : 1.0f;
       } else {
-        (void)hipMemsetAsync(c->cert_level, 0, cert_level_words(tiles) * sizeof(uint32_t), site.stream);      // no certificate: grade 0, the scene's margin
+        (void)hipMemsetAsync(w.level, 0, cert_level_words(tiles) * sizeof(uint32_t), site.stream);      // no certificate: grade 0, the scene's margin
       }
       // the tiles' words for the kernel: the grades, and the camera rays' entry records (no table: the root everywhere)
-      launch_camera_entry(site.stream, c->wide, c->wide_leaf_rec, c->wide_range, c->wide_leaves, cv, want_entry ? c->entry_mm.p : nullptr, c->cert_level, c->cert_word, tiles);
-      c->cert_ok = want_cert; c->entry_ok = want_entry;
+      launch_camera_entry(site.stream, c->wide, c->wide_leaf_rec, c->wide_range, c->wide_leaves, cv, want_entry ? w.mm.p : nullptr, w.level, w.word, tiles);
+      cert_ok = want_cert; entry_ok = want_entry;
     }
-    memcpy(c->cert_key, key, sizeof(key));
-    c->cert_tiles = tiles;
-    c->cert_valid = true;
+    camera_words_commit(w.state, key, tiles, cert_ok, entry_ok);
   }
-  if (c->cert_ok || c->entry_ok) { P.cert_level = c->cert_word; memcpy(P.wide_cert_k, c->cert_k, sizeof(P.wide_cert_k)); }
+  if (camera_words_in_use(w.state)) { P.cert_level = w.word; memcpy(P.wide_cert_k, w.state.k, sizeof(P.wide_cert_k)); }
 }
 
 // Sky tiles (option sky_tiles): when the launch runs the lean build over a view with an entry table, the tiles no leaf can be seen from
@@ -129,27 +109,23 @@ void cert_prepare(dr_context* c, const LaunchSite& site, RenderParams& P, int ti
 // persistent kernel's waves render the sky tiles when they retire, a unit of SKY_CHUNK frames at a time.  Only a launch that adds atomically
 // (P.accumulate == 2) may cut a tile's batch into several units; every other launch is of one frame, one unit per tile.
 bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles, const int*& order, const int*& region_start, unsigned* pcost, unsigned* cursor) {
-  if (!c->sky_tiles || !c->entry_ok || !P.cert_level || site.hold_order || site.stream != c->stream || P.out_frame_stride != 0) return false;
+  if (!c->sky_tiles || !c->words.state.entry_ok || !P.cert_level || site.hold_order || site.stream != c->stream || P.out_frame_stride != 0) return false;
   if (P.max_depth <= 0 || !(P.spp_f > 0.0f)) return false;
   if (!plan_sky_split(plan_persistent(persistent_cfg(c, site), (long long)tiles * P.batch, P.coop_steps, false, P.wave_log != nullptr))) return false;
   // the split of the same words and the same order is the same arrays: made once, on this stream, and reused by the launches behind it (every launch
   // that splits runs on this stream, so none reads the arrays while they are rewritten)
-  const uint64_t key[5] = {c->cert_gen, order ? 1u : 0u, order ? c->order_gen : 0u, (uint64_t)tiles, (uint64_t)P.regions};
-  const bool room = c->launch_order.n >= (size_t)tiles && c->sky_list.n >= (size_t)tiles && c->launch_region_start.p && c->sky_counts.p;
-  if (!(room && c->sky_key_valid && memcmp(c->sky_key, key, sizeof(key)) == 0)) {
-    c->sky_key_valid = false;
-    if (c->launch_order.grow((size_t)tiles, site.stream) != DR_OK || c->sky_list.grow((size_t)tiles, site.stream) != DR_OK ||
-        c->launch_region_start.grow(2 * MAX_REGIONS + 1, site.stream) != DR_OK || c->sky_counts.grow(2, site.stream) != DR_OK)
-      return false;
-    launch_sky_split(site.stream, order, region_start, P.region_start, P.cert_level, tiles, P.regions, c->launch_order, c->launch_region_start, c->sky_list, c->sky_counts);
-    memcpy(c->sky_key, key, sizeof(key));
-    c->sky_key_valid = true;
+  SkySplit& sky = c->sky;
+  const SkyKey key = sky_key(c->words.state, c->order.state, order != nullptr, tiles, P.regions);
+  if (!sky_split_reusable(sky.state, key, sky.room(tiles))) {
+    if (sky.grow(tiles, site.stream) != DR_OK) return false;
+    launch_sky_split(site.stream, order, region_start, P.region_start, P.cert_level, tiles, P.regions, sky.launch_order, sky.launch_region_start, sky.list, sky.counts);
+    sky_split_commit(sky.state, key);
   }
   if (c->sky_tiles == 2) {
-    P.sky_list = c->sky_list; P.sky_counts = c->sky_counts; P.sky_cursor = cursor;
+    P.sky_list = sky.list; P.sky_counts = sky.counts; P.sky_cursor = cursor;
     P.sky_chunk = sky_chunk_frames(P.batch, P.accumulate == 2 ? SKY_CHUNK : 0);
-  } else launch_sky_tiles(site.stream, P, c->sky_list, c->sky_counts, pcost);
-  order = c->launch_order; region_start = c->launch_region_start;
+  } else launch_sky_tiles(site.stream, P, sky.list, sky.counts, pcost);
+  order = sky.launch_order; region_start = sky.launch_region_start;
   return true;
 }
 
@@ -167,36 +143,27 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
     }
     unsigned* counter = c->tile_counters + c->tile_cursor;      // one counter per region, and the sky units' cursor behind them
     c->tile_cursor += LAUNCH_COUNTERS;
+    const ViewKey key = view_key(c, P);
+    // (a held launch runs beside the previous frame's: it may read the tile order but nobody may write it, or the costs, meanwhile)
     const int* order; unsigned* pcost;
-    if (site.hold_order) {
-      // a pipelined launch runs beside the previous frame's: it may read the tile order but nobody may write it (or the costs) meanwhile
-      float geom[5];
-      order_geometry(P, geom);
-      order = (c->order_valid && c->order_capacity >= tiles && memcmp(c->order_key + 13, geom, sizeof(geom)) == 0) ? c->tile_order.p : nullptr;
-      pcost = nullptr;
-    } else feedback_buffers(c, site, P, tiles, order, pcost);
+    const OrderUse use = feedback_buffers(c, site, key, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
-    cert_prepare(c, site, P, tiles);
-    const int* launch_order = order; const int* launch_rstart = c->region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
-    c->sky_split_last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
+    cert_prepare(c, site, key, P, tiles);
+    const int* launch_order = order; const int* launch_rstart = c->order.region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
+    c->sky.state.last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
     const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, launch_order, launch_rstart, pcost);
     if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
     c->wave_log_waves = log_waves;
-    // next launch's order from this launch's costs (stream-ordered, no host sync).  The view does not change between the frames of
-    // a progressive render, so after the first two launches of a view the order is refreshed every feedback_every-th launch only
-    // (the two kernels take 75 us: nothing for a launch of 32 frames, 6 % of a launch of one)
-    if (pcost && !order) c->order_age = 0;
-    if (pcost && (c->order_age < 2 || c->order_age % c->feedback_every == 0)) {
+    // next launch's order from this launch's costs (stream-ordered, no host sync), when launch_state.hpp order_end says so
+    if (order_end(c->order.state, use, c->feedback_every)) {
       const int split_limit = plan_split_limit(c->num_cus, c->occupancy, c->split_parts, c->split_waves);
-      launch_tile_feedback(site.stream, c->pixel_cost, c->tile_cost, c->tile_order, c->region_start, tiles, P.regions, c->heavy_factor, c->split_steps, split_limit);
-      c->order_gen++;
-      c->order_args[0] = tiles; c->order_args[1] = P.regions; c->order_args[2] = c->heavy_factor; c->order_args[3] = c->split_steps; c->order_args[4] = split_limit;
-      c->order_valid = true;
+      launch_tile_feedback(site.stream, c->order.pixel_cost, c->order.tile_cost, c->order.order, c->order.region_start, tiles, P.regions, c->heavy_factor, c->split_steps, split_limit);
+      const int args[5] = {tiles, P.regions, c->heavy_factor, c->split_steps, split_limit};
+      memcpy(c->order.state.args, args, sizeof(args));
     }
-    c->order_age++;
     return DR_OK;
   }
-  c->sky_split_last = false;
+  c->sky.state.last = false;
   launch_tile_kernel(site.stream, P, traversal_of(c), c->count != 0, c->occupancy);
   return DR_OK;
 }

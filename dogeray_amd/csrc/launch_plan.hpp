@@ -252,10 +252,4 @@ inline AllHitsPlan plan_allhits(long long n, bool has_wide, int num_cus, int for
   return {l.kernel, has_wide, l.blocks};
 }
 
-// The last five floats of dr_context::order_key: frame, stripe and queues, tile grid (the preview divisor changes it with W and H unchanged)
-inline void order_geometry(const RenderParams& P, float out[5]) {
-  out[0] = (float)P.W; out[1] = (float)P.H; out[2] = (float)(P.stripe_mod * 1024 + P.stripe_rem) + 0.125f * (float)P.regions;
-  out[3] = (float)P.ncols; out[4] = (float)P.gy;
-}
-
 }  // namespace dr

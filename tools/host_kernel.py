@@ -79,6 +79,17 @@ _API = [
     ("hk_trace_plan", None, [_Q, _I, _I, _I, _I, _P]),
     ("hk_radiance_plan", None, [_Q, _I, _I, _I, _I, _P]),
     ("hk_allhits_plan", None, [_Q, _I, _I, _I, _P]),
+    ("hk_launch_state_new", _P, []),
+    ("hk_launch_state_free", None, [_P]),
+    ("hk_launch_state_read", None, [_P, _P]),
+    ("hk_launch_state_invalidate", None, [_P, _I]),
+    ("hk_order_begin", _I, [_P, _P, _P, _I, _I, _I, _I]),
+    ("hk_order_end", _I, [_P, _I, _I]),
+    ("hk_order_pipeline_refresh", _I, [_P, _P, _P, _I, _I]),
+    ("hk_camera_words_plan", _I, [_P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    ("hk_camera_words_compute", None, [_P, _P, _P, _I, _I, _I]),
+    ("hk_camera_words_readable", _I, [_P]),
+    ("hk_sky_split_launch", _I, [_P, _I, _I, _I, _I, _I]),
     ("hk_sky_split", _I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     ("hk_sky_pixel", _I, _VIEW + [_F, _U64, _U64, _I, _I, _P, _P, _P]),
     ("hk_sky_units", C.c_uint, [C.c_uint, _I, _I]),
@@ -741,3 +752,70 @@ def plan_regions(tiles, batch_hint, xcd_regions, short_one_queue, tiles_per_wave
 
 def plan_split_limit(num_cus, occupancy, split_parts, split_waves):
     return int(lib().hk_plan_split_limit(int(num_cus), int(occupancy), int(split_parts), int(split_waves)))
+
+
+KEY_FIELDS = ("W", "H", "stripe_mod", "stripe_rem", "ncols", "gy", "regions", "scene_gen", "cert_factor", "cert_levels", "camera_entry", "camera_cert")
+WORDS_PLANS = ("not wanted", "reuse", "skip: held", "skip: first sight", "compute")
+
+
+class LaunchState:
+    """launch_state.hpp's three states (tile order, camera words, sky split) and the rules on them (hk_order_*, hk_camera_words_*, hk_sky_split_launch).
+    A view is (settings13, dict of KEY_FIELDS)."""
+
+    def __init__(self):
+        self.h = lib().hk_launch_state_new()
+
+    def __del__(self):
+        try:
+            lib().hk_launch_state_free(self.h)
+        except Exception:
+            pass
+
+    @staticmethod
+    def _key(view):
+        st, k = view
+        return _arr(st, np.float32, (13,)), np.array([int(k[f]) for f in KEY_FIELDS], np.int64)
+
+    def read(self):
+        """the whole state as a dict: order / words / sky, keys as (tuple of settings13's 13 words, tuple of KEY_FIELDS' values)"""
+        w = np.zeros(96, np.int64)
+        lib().hk_launch_state_read(self.h, w.ctypes.data)
+        w = [int(v) for v in w]
+        key = lambda at: (tuple(w[at:at + 13]), tuple(w[at + 13:at + 25]))
+        return {"order": {"valid": w[0], "capacity": w[1], "age": w[2], "gen": w[3], "args": tuple(w[4:9]), "key": key(9)},
+                "words": {"valid": w[34], "cert_ok": w[35], "entry_ok": w[36], "tiles": w[37], "gen": w[38], "key": key(39), "seen": key(64)},
+                "sky": {"valid": w[89], "last": w[90], "words_gen": w[91], "ordered": w[92], "order_gen": w[93], "tiles": w[94], "regions": w[95]}}
+
+    def invalidate(self, order=False, words=False, sky=False):
+        lib().hk_launch_state_invalidate(self.h, int(bool(order)) + 2 * int(bool(words)) + 4 * int(bool(sky)))
+
+    def order_begin(self, view, tiles, feedback, follows_camera, hold_order):
+        """-> (use_order, record_costs, grow)"""
+        st, k = self._key(view)
+        u = lib().hk_order_begin(self.h, st.ctypes.data, k.ctypes.data, int(tiles), int(feedback), int(follows_camera), int(hold_order))
+        return bool(u & 1), bool(u & 2), bool(u & 4)
+
+    def order_end(self, use, feedback_every):
+        return bool(lib().hk_order_end(self.h, int(use[0]) + 2 * int(use[1]) + 4 * int(use[2]), int(feedback_every)))
+
+    def order_pipeline_refresh(self, view, tiles, feedback_every):
+        st, k = self._key(view)
+        return bool(lib().hk_order_pipeline_refresh(self.h, st.ctypes.data, k.ctypes.data, int(tiles), int(feedback_every)))
+
+    def camera_words_plan(self, view, want_cert, want_entry, wide, tiles, hold_order, batch):
+        """-> one of WORDS_PLANS"""
+        st, k = self._key(view)
+        return WORDS_PLANS[lib().hk_camera_words_plan(self.h, st.ctypes.data, k.ctypes.data, int(want_cert), int(want_entry), int(wide), int(tiles), int(hold_order), int(batch))]
+
+    def camera_words_compute(self, view, tiles, cert_ok, entry_ok):
+        st, k = self._key(view)
+        lib().hk_camera_words_compute(self.h, st.ctypes.data, k.ctypes.data, int(tiles), int(cert_ok), int(entry_ok))
+
+    def camera_words_readable(self):
+        """-> (a certificate can be read back, an entry table can, the launch reads the words)"""
+        r = lib().hk_camera_words_readable(self.h)
+        return bool(r & 1), bool(r & 2), bool(r & 4)
+
+    def sky_split_launch(self, split, use_order, tiles, regions, room=True):
+        """-> the stored split served the launch"""
+        return bool(lib().hk_sky_split_launch(self.h, int(split), int(use_order), int(tiles), int(regions), int(room)))

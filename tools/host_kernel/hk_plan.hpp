@@ -118,4 +118,81 @@ long long hk_sky_units_render(void* hv, const float* settings13, int W, int H, f
   }
   return (long long)n_units;
 }
+// launch_state.hpp on the host (tests/test_launch_state_host.py): one set of the three caches' states behind a handle, and the rules on it.  A view
+// key is settings13 and k12 = W, H, stripe mod, stripe rem, ncols, gy, regions, scene generation, cert_factor, cert_levels, camera_entry, camera_cert
+struct HkLaunchState { OrderState order; CameraWordsState words; SkySplitState sky; };
+static ViewKey hk_view_key(const float* st13, const long long* k12) {
+  ViewKey k;
+  memcpy(k.st, st13, sizeof(k.st));
+  k.W = (int)k12[0]; k.H = (int)k12[1]; k.stripe_mod = (int)k12[2]; k.stripe_rem = (int)k12[3]; k.ncols = (int)k12[4]; k.gy = (int)k12[5]; k.regions = (int)k12[6];
+  k.scene_gen = (uint64_t)k12[7];
+  k.cert_factor = (int)k12[8]; k.cert_levels = (int)k12[9]; k.camera_entry = (int)k12[10]; k.camera_cert = (int)k12[11];
+  return k;
+}
+static long long* hk_put_key(const ViewKey& k, long long* out) {      // 13 words of settings13, then k12
+  for (int i = 0; i < 13; i++) { uint32_t w; memcpy(&w, &k.st[i], 4); *out++ = w; }
+  const long long v[12] = {k.W, k.H, k.stripe_mod, k.stripe_rem, k.ncols, k.gy, k.regions, (long long)k.scene_gen, k.cert_factor, k.cert_levels, k.camera_entry, k.camera_cert};
+  memcpy(out, v, sizeof(v));
+  return out + 12;
+}
+void* hk_launch_state_new() { return new HkLaunchState(); }
+void hk_launch_state_free(void* h) { delete (HkLaunchState*)h; }
+// the whole state as 96 words: order valid, capacity, age, gen, args[5], key (25); words valid, cert_ok, entry_ok, tiles, gen, key (25), seen (25);
+// sky valid, last, words_gen, ordered, order_gen, tiles, regions
+void hk_launch_state_read(void* h, long long* out96) {
+  const HkLaunchState& s = *(HkLaunchState*)h;
+  long long* o = out96;
+  *o++ = s.order.valid; *o++ = s.order.capacity; *o++ = s.order.age; *o++ = (long long)s.order.gen;
+  for (int a : s.order.args) *o++ = a;
+  o = hk_put_key(s.order.key, o);
+  *o++ = s.words.valid; *o++ = s.words.cert_ok; *o++ = s.words.entry_ok; *o++ = s.words.tiles; *o++ = (long long)s.words.gen;
+  o = hk_put_key(s.words.key, o);
+  o = hk_put_key(s.words.seen, o);
+  *o++ = s.sky.valid; *o++ = s.sky.last; *o++ = (long long)s.sky.key.words_gen; *o++ = s.sky.key.ordered; *o++ = (long long)s.sky.key.order_gen; *o++ = s.sky.key.tiles; *o++ = s.sky.key.regions;
+}
+// what an option does from outside (the owners' invalidate()): which = 1 the order, 2 the words, 4 the sky split, or their sum
+void hk_launch_state_invalidate(void* h, int which) {
+  HkLaunchState& s = *(HkLaunchState*)h;
+  if (which & 1) s.order.valid = false;
+  if (which & 2) s.words.valid = false;
+  if (which & 4) s.sky.valid = false;
+}
+// order_begin: returns use_order | record_costs << 1 | grow << 2 (the buffers are taken to grow: the capacity stays as the rule set it)
+int hk_order_begin(void* h, const float* st13, const long long* k12, int tiles, int feedback, int follows_camera, int hold_order) {
+  const OrderUse u = order_begin(((HkLaunchState*)h)->order, hk_view_key(st13, k12), tiles, feedback != 0, follows_camera != 0, hold_order != 0);
+  return (u.use_order ? 1 : 0) | (u.record_costs ? 2 : 0) | (u.grow ? 4 : 0);
+}
+// order_end of the launch whose order_begin returned `use`: 1 when the feedback pass runs
+int hk_order_end(void* h, int use, int feedback_every) {
+  return order_end(((HkLaunchState*)h)->order, OrderUse{(use & 1) != 0, (use & 2) != 0, (use & 4) != 0}, feedback_every) ? 1 : 0;
+}
+int hk_order_pipeline_refresh(void* h, const float* st13, const long long* k12, int tiles, int feedback_every) {
+  return order_pipeline_refresh(((HkLaunchState*)h)->order, hk_view_key(st13, k12), tiles, feedback_every) ? 1 : 0;
+}
+// camera_words_plan: returns the CameraWordsPlan (0 not wanted, 1 reuse, 2 skip: held, 3 skip: first sight, 4 compute)
+int hk_camera_words_plan(void* h, const float* st13, const long long* k12, int want_cert, int want_entry, int wide, int tiles, int hold_order, int batch) {
+  return (int)camera_words_plan(((HkLaunchState*)h)->words, hk_view_key(st13, k12), want_cert != 0, want_entry != 0, wide != 0, tiles, hold_order != 0, batch);
+}
+// what follows a plan of WORDS_COMPUTE: camera_words_begin and camera_words_commit with the two flags
+void hk_camera_words_compute(void* h, const float* st13, const long long* k12, int tiles, int cert_ok, int entry_ok) {
+  CameraWordsState& s = ((HkLaunchState*)h)->words;
+  camera_words_begin(s);
+  camera_words_commit(s, hk_view_key(st13, k12), tiles, cert_ok != 0, entry_ok != 0);
+}
+// certificate_readable | entry_table_readable << 1 | camera_words_in_use << 2
+int hk_camera_words_readable(void* h) {
+  const CameraWordsState& s = ((HkLaunchState*)h)->words;
+  return (certificate_readable(s) ? 1 : 0) | (entry_table_readable(s) ? 2 : 0) | (camera_words_in_use(s) ? 4 : 0);
+}
+// a launch that is split (use_order: it uses the stored order; room: the arrays are large enough): 1 when the stored split serves it, else 0 and the
+// split is made anew (sky_split_commit); `split` 0: the launch is not split at all.  Either way the state's `last` is `split`
+int hk_sky_split_launch(void* h, int split, int use_order, int tiles, int regions, int room) {
+  HkLaunchState& s = *(HkLaunchState*)h;
+  s.sky.last = split != 0;
+  if (!split) return 0;
+  const SkyKey key = sky_key(s.words, s.order, use_order != 0, tiles, regions);
+  if (sky_split_reusable(s.sky, key, room != 0)) return 1;
+  sky_split_commit(s.sky, key);
+  return 0;
+}
 }  // extern "C"
