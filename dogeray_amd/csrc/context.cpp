@@ -32,9 +32,9 @@ const Option OPTIONS[] = {
     {"reserve_cus", &dr_context::reserve_cus, 0, 64, 0, NOTHING},
     {"wave_log", &dr_context::wave_log_on, 0, 1, 0, NOTHING},
     {"coop_tiles_per_wave", &dr_context::coop_tiles_per_wave, 0, INT_MAX, 0, NOTHING},
-    {"pipe_streams", &dr_context::pipe_streams, 2, dr_context::PIPE_STREAMS, 0, NOTHING},
+    {"pipe_streams", &dr_context::pipe_streams, 2, PIPE_STREAMS, 0, NOTHING},
     {"pipe_lean", &dr_context::pipe_lean, ANY, 0, 0, NOTHING},
-    {"pipe_group", &dr_context::pipe_group, 1, dr_context::PIPE_GROUP_MAX, 0, NOTHING},
+    {"pipe_group", &dr_context::pipe_group, 1, PIPE_GROUP_MAX, 0, NOTHING},
     {"xcd_regions", &dr_context::xcd_regions, ANY, 0, 0, ORDER},
     {"batch_frames", &dr_context::batch_frames, 1, 256, 0, NOTHING},
     {"feedback", &dr_context::feedback, ANY, 0, 0, ORDER},
@@ -63,7 +63,7 @@ const Option* find_option(const std::string& name) {
 // One rule for whatever changes the state a launch reads (an option, the stripe, the traversal, the counters switch): frames submitted before the change
 // are launched with the state they were submitted under -- the frames still held go first.  (Nothing is held while a context is being created.)
 int flush_held(dr_context* c) {
-  if (c->pipe_pending.empty()) return DR_OK;
+  if (c->pipe.book.held.empty()) return DR_OK;
   HIP_TRY(hipSetDevice(c->device));
   return pipeline_flush(c);
 }
@@ -84,9 +84,7 @@ int set_option(dr_context* c, const std::string& name, int v) {
   else if (name == "pipe_streams") {
     if (v != c->pipe_streams) {               // slots and streams are numbered by ticket: drain, then start again from ticket 0
       if (hipSetDevice(c->device) != hipSuccess || join_pipeline(c) != DR_OK || hipStreamSynchronize(c->stream) != hipSuccess) { set_error("pipe_streams: cannot drain the pipeline"); return DR_ERR_DEVICE; }
-      for (int k = 0; k < dr_context::PIPE_DEPTH; k++) { c->pipe_slot[k].drained = true; c->pipe_slot[k].count = 0; c->pipe_slot[k].unwaited = 0; }
-      c->pipe_parked.clear();                 // (images kept for tickets of the old numbering)
-      c->pipe_next = 0; c->pipe_groups = 0;
+      c->pipe.book.restart_numbering(v);
     }
   }
   c->*(o->member) = v;
@@ -116,22 +114,13 @@ int stats_copy(U* out, const T* src, size_t have, size_t room) {
 
 }  // namespace
 
-// every stream that may still touch the buffers is drained before the members -- the buffers -- go
+// every stream that may still touch the buffers is drained before the members -- the buffers, the pipeline's and the batches' events -- go
 dr_context::~dr_context() {
   (void)hipSetDevice(device);
   if (stream) (void)hipStreamSynchronize(stream);
-  for (int k = 1; k < PIPE_STREAMS; k++) if (pipe_stream[k]) (void)hipStreamSynchronize(pipe_stream[k]);
-  if (acc_stream) (void)hipStreamSynchronize(acc_stream);
+  pipe.drain();
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
-  for (int k = 0; k < 2; k++) { if (pev0[k]) (void)hipEventDestroy(pev0[k]); if (pev1[k]) (void)hipEventDestroy(pev1[k]); }
-  for (PipeSlot& sl : pipe_slot) {
-    if (sl.rendered) (void)hipEventDestroy(sl.rendered);
-    for (hipEvent_t e : sl.added) if (e) (void)hipEventDestroy(e);
-  }
-  for (hipEvent_t e : {pipe_last[0], pipe_last[1], pipe_last[2], pipe_last[3], pipe_barrier, pipe_sync}) if (e) (void)hipEventDestroy(e);
-  for (int k = 1; k < PIPE_STREAMS; k++) if (pipe_stream[k]) (void)hipStreamDestroy(pipe_stream[k]);
-  if (acc_stream) (void)hipStreamDestroy(acc_stream);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -174,8 +163,7 @@ int dr_context_create(int device_ordinal, dr_context** out) {
   memset(&c->stats, 0, sizeof(c->stats));
   // the stream first: every memset below is ordered on it, like the kernels that use the buffers
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
-      hipEventCreate(&c->ev1) != hipSuccess || hipEventCreate(&c->pev0[0]) != hipSuccess || hipEventCreate(&c->pev1[0]) != hipSuccess ||
-      hipEventCreate(&c->pev0[1]) != hipSuccess || hipEventCreate(&c->pev1[1]) != hipSuccess) {
+      hipEventCreate(&c->ev1) != hipSuccess || !c->async.create()) {
     set_error("cannot create stream/events");
     delete c;
     return DR_ERR_DEVICE;

@@ -1,9 +1,10 @@
 // The device context (struct dr_context: resident scene, options, accumulator, pipeline state) and what the context_*.cpp files share: the error
 // macros, the owning device buffer, the guide caches' key, the launch site, the owners of a render launch's three caches (launch_state.hpp: tile order,
-// camera words, sky split), and the internal functions one file defines and another calls.
+// camera words, sky split), the owner of the pipelined present loop (pipeline_state.hpp: the ticket book and the ordering plans), and the internal functions
+// one file defines and another calls.
 //   context.cpp            create / destroy / upload / stripe / traversal / options / statistics
 //   context_render.cpp     per-launch constants, the three caches around a launch, the launches of dr_render_frame / dr_render_accumulate*
-//   context_pipeline.cpp   pipelined single frames (dr_pipeline_*)
+//   context_pipeline.cpp   pipelined single frames (dr_pipeline_*): asks pipeline_state.hpp's book, issues its plans, launches; FramePipeline's setup / drain
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
 //   context_query.cpp      what the queries on caller lists share: staging in and out, scratch, cursor, the object map's upload
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
@@ -24,6 +25,7 @@
 #include "kernels.hpp"
 #include "launch_state.hpp"
 #include "params_host.hpp"
+#include "pipeline_state.hpp"
 #include "scene_host.hpp"
 
 #define HIP_TRY(expr)                                                                      \
@@ -75,6 +77,8 @@ struct DevMem {
   int put(const T* src, size_t count) { if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice)); return DR_OK; }
   int get(T* dst, size_t count) const { if (count) HIP_TRY(hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost)); return DR_OK; }
 };
+template <class T, bool PINNED>
+void swap(DevMem<T, PINNED>& a, DevMem<T, PINNED>& b) { a.swap(b); }
 
 // The key of a cached set of first-hit guides: the view's settings13, the frame size and the scene upload they were traced for
 struct GuideKey {
@@ -186,6 +190,59 @@ struct SkySplit {
 constexpr int TILE_COUNTERS = 1024;
 constexpr int LAUNCH_COUNTERS = MAX_REGIONS + 1;      // a launch's block of them: a cursor per tile queue, then the sky units' cursor (option sky_tiles = 2)
 
+// Pipelined single frames (dr_pipeline_*): render streams the groups alternate between, a stream that folds finished frames into the
+// accumulator in ticket order, PIPE_DEPTH slots of frame / present buffers that rotate, and the book that says which ticket is where
+// (pipeline_state.hpp holds it and every rule about it; context_pipeline.cpp asks, issues and launches).  Outside it: restart_numbering(), drain()
+struct FramePipeline {
+  typedef DevMem<uint8_t, true> Image;             // a frame's present, pinned
+  hipStream_t stream[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr}, acc_stream = nullptr;      // stream[0] is the context's own (not owned)
+  struct Slot {
+    DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;         // cap_frames buffers of elems_each int32, one after the other
+    int rect[6] = {-1, 0, 0, 0, 0, 0};             // W, H, gx, gy, stripe mod, stripe rem the buffers were last rendered with (their margins are 0)
+    hipEvent_t rendered = nullptr;                 // end of the group's launch
+    hipEvent_t added[PIPE_GROUP_MAX] = {nullptr};  // frame f of the group has been added (and presented)
+    DevMem<uint8_t> rgb_dev[PIPE_GROUP_MAX]; Image rgb_host[PIPE_GROUP_MAX];      // frame f's present: on the device, and its pinned copy
+  };
+  Slot slot[PIPE_DEPTH];
+  hipEvent_t last[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr};        // end of the newest launch on each render stream
+  hipEvent_t barrier = nullptr;                    // end of the newest launch that ran alone: later launches read the order it left
+  hipEvent_t sync = nullptr;                       // orders the pipeline after earlier work on the context's stream
+  bool ready = false;                              // every stream and event exists (setup)
+  TicketBook<Image> book;
+  int setup(hipStream_t own);                      // context_pipeline.cpp: creates what is missing
+  void drain() const;                              // ... waits for the streams it owns
+  ~FramePipeline();                                // ... destroys its events and streams (drained by then); the buffers then free themselves
+};
+
+// dr_render_accumulate_async: two batches may be in flight, each with its own pair of events
+struct AsyncBatches {
+  struct Batch { hipEvent_t ev0 = nullptr, ev1 = nullptr; bool pending = false; uint64_t frames = 0, samples = 0; };
+  Batch batch[2];
+  int next = 0;                                    // the batch the next call uses: the older of the two
+  int older() const { return next; }
+  int newer() const { return next ^ 1; }
+  bool create() {
+    for (Batch& b : batch) if (hipEventCreate(&b.ev0) != hipSuccess || hipEventCreate(&b.ev1) != hipSuccess) return false;
+    return true;
+  }
+  // batch k's time, if its events are still outstanding (waits for that batch, not for later ones): collect_time(ev0, ev1, frames, samples) adds it
+  template <class CollectTime>
+  int collect(int k, CollectTime collect_time) {
+    Batch& b = batch[k];
+    if (!b.pending) return DR_OK;
+    DR_TRY(collect_time(b.ev0, b.ev1, b.frames, b.samples));
+    b.pending = false;
+    return DR_OK;
+  }
+  // the older batch's events now bracket a new batch: the other one is the older
+  void started(uint64_t frames, uint64_t samples) {
+    Batch& b = batch[next];
+    b.pending = true; b.frames = frames; b.samples = samples;
+    next ^= 1;
+  }
+  ~AsyncBatches() { for (Batch& b : batch) { if (b.ev0) (void)hipEventDestroy(b.ev0); if (b.ev1) (void)hipEventDestroy(b.ev1); } }
+};
+
 }  // namespace dr
 
 // option sample_order's default (the macro serves variant libraries of an A/B, as DR_SKY_CHUNK does)
@@ -198,9 +255,7 @@ struct dr_context {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // dr_render_accumulate_async: two batches may be in flight, each with its own pair of events
-  hipEvent_t pev0[2] = {nullptr, nullptr}, pev1[2] = {nullptr, nullptr};
-  bool pending[2] = {false, false}; uint64_t pending_frames[2] = {0, 0}, pending_samples[2] = {0, 0}; int pending_next = 0;
+  dr::AsyncBatches async;
   // resident scene
   DevMem<dr::DevUnit> walk; size_t walk_bytes = 0;
   DevMem<dr::DevUnit> wide; size_t wide_bytes = 0; int wide_depth = 0, wide_nodes = 0; float wide_pmax = 0; dr::WideMu wide_mu = {0, 0, 0}; int wide_own_bounds = 0;   // null: scene not representable (threaded walk is used)
@@ -298,49 +353,14 @@ struct dr_context {
   int batch_frames = 32;    // persistent kernel: at most this many frames per launch in dr_render_accumulate
   float cur_settings[13] = {0};
   dr_stats stats;
-  // pipelined single frames (dr_pipeline_*): a second render stream, a stream that folds finished frames into the accumulator in
-  // frame order, and PIPE_DEPTH frame buffers / present buffers that rotate
-  static constexpr int PIPE_STREAMS = 4;           // render streams (stream itself is number 0); option pipe_streams uses 2 .. 4 of them
-  static constexpr int PIPE_DEPTH = PIPE_STREAMS + 1;
-  int pipe_streams = 2;     // render streams the pipeline alternates between
+  // pipelined single frames (dr_pipeline_*): the three options (the option table holds int members) and the pipeline itself
+  int pipe_streams = 2;     // render streams the pipeline alternates between (a change restarts the ticket numbering)
   int pipe_lean = 0;        // pipelined launches run the lean build with one queue per XCD instead of the work-sharing build (their tails overlap other frames)
-  hipStream_t pipe_stream[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr}, acc_stream = nullptr;      // pipe_stream[0] = stream
-  // a slot = one GROUP of frames in flight: frames submitted one after the other (same view, seeds in arithmetic progression) share one launch -- each
-  // rendered into a buffer of its own -- and are added to the accumulator and presented one by one, in ticket order (option pipe_group; 1 = a launch per frame)
-  static constexpr int PIPE_GROUP_MAX = 16;
-  struct PipeSlot {
-    DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;         // cap_frames buffers of elems_each int32, one after the other
-    int rect[6] = {-1, 0, 0, 0, 0, 0};             // W, H, gx, gy, stripe mod, stripe rem the buffers were last rendered with (their margins are 0)
-    hipEvent_t rendered = nullptr;                 // end of the group's launch
-    hipEvent_t added[PIPE_GROUP_MAX] = {nullptr};  // frame f of the group has been added (and presented)
-    DevMem<uint8_t> rgb_dev[PIPE_GROUP_MAX]; dr::DevMem<uint8_t, true> rgb_host[PIPE_GROUP_MAX];      // frame f's present: on the device, and its pinned copy
-    int div[PIPE_GROUP_MAX] = {0};                 // divisor frame f was presented with (0: not presented)
-    bool fwaited[PIPE_GROUP_MAX] = {false};        // dr_pipeline_wait has returned for frame f
-    int unwaited = 0;                              // frames of the group that were presented and have not been waited for: their images are owed
-    uint64_t first = 0; int count = 0;             // tickets [first, first + count)
-    bool drained = true;                           // the host has waited for the group's last add: its buffers may be reused at once
-  };
-  PipeSlot pipe_slot[PIPE_DEPTH];
-  uint64_t pipe_groups = 0;                        // groups launched so far (slot = group % (streams + 1), render stream = group % streams)
-  int pipe_group = 8;                              // most frames per group
-  struct PipePending { float st[13]; int W, H; float bg; uint64_t seed; int div; };
-  std::vector<PipePending> pipe_pending;           // submitted, not launched yet: tickets [pipe_next - size, pipe_next)
-  uint64_t pipe_next = 0;                          // ticket of the next frame
-  // a ticket stays waitable until it has been waited for: when a slot is reused, the pinned images of its frames that were presented and not yet
-  // waited for move here (swapped, not copied; their adds have run).  An entry goes at the first launch after its wait; dr_pipeline_submit refuses
-  // a frame whose launch could leave more than PIPE_PARKED_MAX images owed
-  static constexpr int PIPE_PARKED_MAX = 2 * PIPE_GROUP_MAX;
-  struct PipeParked { dr::DevMem<uint8_t, true> rgb; bool waited = false; };
-  std::map<uint64_t, PipeParked> pipe_parked;      // by ticket
-  hipEvent_t pipe_last[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr};    // end of the newest launch on each render stream
-  bool pipe_last_set[PIPE_STREAMS] = {false, false, false, false};
-  hipEvent_t pipe_barrier = nullptr; bool pipe_barrier_set = false;      // end of the newest tile-order refresh: later launches read that order
-  hipEvent_t pipe_sync = nullptr;                  // orders the pipeline after earlier work on `stream`
-  bool pipe_dirty = false;                         // frames have gone through the pipeline since the last join
-  bool pipe_ready = false;                         // every stream and event of the pipeline exists (pipeline_setup)
+  int pipe_group = 8;       // most frames per group (1 = a launch per frame)
+  dr::FramePipeline pipe;
 
   dr::LaunchSite own_site() const { return {stream, false, false}; }      // an ordinary launch: on `stream`, with cost feedback
-  ~dr_context();            // context.cpp: drains every stream, destroys events and streams; the buffers then free themselves
+  ~dr_context();            // context.cpp: drains every stream, destroys its own events and stream; the members then release theirs
 };
 
 namespace dr {

@@ -197,10 +197,7 @@ int collect_time(dr_context* c, hipEvent_t e0, hipEvent_t e1, uint64_t frames, u
 
 // time of an asynchronous batch whose events are still outstanding (waits for that batch, not for later ones)
 int collect_pending(dr_context* c, int k) {
-  if (!c->pending[k]) return DR_OK;
-  DR_TRY(collect_time(c, c->pev0[k], c->pev1[k], c->pending_frames[k], c->pending_samples[k]));
-  c->pending[k] = false;
-  return DR_OK;
+  return c->async.collect(k, [c](hipEvent_t e0, hipEvent_t e1, uint64_t frames, uint64_t samples) { return collect_time(c, e0, e1, frames, samples); });
 }
 
 // enqueues the launches of `nframes` frames between two event records; no host synchronisation
@@ -283,12 +280,11 @@ int dr_render_accumulate_async(dr_context* c, const float settings13[13], int W,
   if (!c) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (nframes == 0) return DR_OK;
   if (c->m2) { set_error("dr_render_accumulate_async cannot feed a second-moment plane (option moments): use dr_render_accumulate or the pipeline"); return DR_ERR_INVALID; }
-  const int k = c->pending_next;
+  const int k = c->async.older();
   DR_TRY(collect_pending(c, k));           // at most two batches in flight: reusing a pair of events waits for the batch before last
   uint64_t samples = 0;
-  DR_TRY(accumulate_enqueue(c, settings13, W, H, background, frame_seed, seed_stride, nframes, c->pev0[k], c->pev1[k], samples));
-  c->pending[k] = true; c->pending_frames[k] = (uint64_t)nframes; c->pending_samples[k] = samples;
-  c->pending_next = k ^ 1;
+  DR_TRY(accumulate_enqueue(c, settings13, W, H, background, frame_seed, seed_stride, nframes, c->async.batch[k].ev0, c->async.batch[k].ev1, samples));
+  c->async.started((uint64_t)nframes, samples);
   return DR_OK;
 }
 
@@ -296,8 +292,8 @@ int dr_context_synchronize(dr_context* c) {
   if (!c) { set_error("null context"); return DR_ERR_INVALID; }
   HIP_TRY(hipSetDevice(c->device));
   DR_TRY(join_pipeline(c));
-  DR_TRY(collect_pending(c, c->pending_next));       // older first
-  DR_TRY(collect_pending(c, c->pending_next ^ 1));
+  DR_TRY(collect_pending(c, c->async.older()));
+  DR_TRY(collect_pending(c, c->async.newer()));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DR_OK;
 }

@@ -374,3 +374,68 @@ def test_submit_refuses_rather_than_drop_an_image(world, ctx):
     assert np.array_equal(ctx.pipeline_wait(t, want_image=True), image(total, n + 1))
     _assert_sums(ctx, total, "%d frames" % (n + 1))
     _assert_counts(ctx, n + 1, n + 1)
+
+
+def _image_call(dr, c, ticket):
+    """dr_pipeline_image(ticket): (return code, error text, pointer)"""
+    ptr = C.c_void_p()
+    rc = dr.lib().dr_pipeline_image(c._h, ticket, C.byref(ptr))
+    return rc, (dr.lib().dr_last_error().decode() if rc != 0 else ""), ptr.value
+
+
+def test_a_ticket_whose_slot_was_reused_keeps_its_image_and_its_order_of_calls(world, ctx):
+    """9.  Five presented frames of five views -- five groups of one for three slots: the launches of tickets 3 and 4 reuse the slots of tickets 0
+    and 1, whose images are kept aside.  dr_pipeline_image of such a ticket is refused before its wait, as it is for a ticket still in its slot;
+    the wait then returns exactly that ticket's image, and dr_pipeline_image the same bytes."""
+    dr = world["dr"]
+    _preconditions(world, ctx)
+    views = []
+    for k in range(5):
+        st = world["st"]["A"].copy()
+        st[0] += 0.05 * k
+        views.append(st)
+    frames = [frame(world, "A", st, seed) for st, seed in zip(views, _seeds(5))]
+    tickets = [ctx.pipeline_submit(st, W, H, world["bg"]["A"], seed, present_divide_by=k + 1) for k, (st, seed) in enumerate(zip(views, _seeds(5)))]
+    assert tickets == [0, 1, 2, 3, 4]
+    ctx.synchronize()                        # ticket 4, held, is launched: five launches
+    _assert_counts(ctx, 5, 5)
+    for t in (0, 1, 4):                      # two whose slot has been reused, one in its slot
+        rc, text, _ = _image_call(dr, ctx, t)
+        assert rc == ERR_INVALID and "dr_pipeline_wait(ticket) comes first" in text, (t, rc, text)
+    totals = np.cumsum(np.stack(frames), axis=0)
+    for t in (1, 0, 4):                      # in no particular order
+        want = image(totals[t], t + 1)
+        got = ctx.pipeline_wait(t, want_image=True)
+        assert np.array_equal(got, want), "image of ticket %d: %d pixels differ" % (t, int((got != want).any(axis=2).sum()))
+        rc, text, ptr = _image_call(dr, ctx, t)
+        assert rc == 0 and ptr, (t, rc, text)
+        again = np.frombuffer((C.c_uint8 * (W * H * 3)).from_address(ptr), dtype=np.uint8).reshape(H, W, 3)
+        assert np.array_equal(again, want), "dr_pipeline_image of ticket %d" % t
+    _assert_sums(ctx, totals[4], "5 views")
+
+
+def test_tickets_start_again_from_0_after_pipe_streams_with_exact_images(world, ctx):
+    """10.  Two held frames, then pipe_streams 2 -> 3 -> 4 -> 2 with three presented frames after each change: the change launches what is held, the
+    tickets after it count from 0 again, and every image is still the exact image of all the frames so far."""
+    _preconditions(world, ctx)
+    st = world["st"]["A"]
+    seeds = _seeds(11)
+    frames = [frame(world, "A", st, seed) for seed in seeds]
+    tickets = _submit(world, ctx, "A", seeds[:2])
+    assert tickets == [0, 1]
+    total, done = None, 0
+    try:
+        for streams in (3, 4, 2):
+            ctx.set_option("pipe_streams", streams)
+            if done == 0:
+                _assert_counts(ctx, 2, 1)    # the two held frames: ONE launch, under the numbering they were submitted in
+                total = frames[0] + frames[1]
+                done = 2
+            tickets = _submit(world, ctx, "A", seeds[done:done + 3], first_div=done + 1)
+            assert tickets == [0, 1, 2], (streams, tickets)
+            total = _wait_all(ctx, tickets, frames[done:done + 3], total, first_div=done + 1)
+            done += 3
+    finally:
+        ctx.set_option("pipe_streams", 2)
+    _assert_sums(ctx, total, "11 frames across three changes of pipe_streams")
+    _assert_counts(ctx, 11, 4)

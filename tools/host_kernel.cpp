@@ -15,6 +15,7 @@
 //   hk_prims.hpp   primitives and generator checks on caller arrays: hk_check_uniform, hk_check_reject, hk_slab, hk_tri_hit, hk_hit_inputs, ...
 //   hk_cert.hpp    the camera rays' certificate and entry table with their checks: hk_cert_check, hk_cert_levels, hk_camera_entry(_check), hk_wide_leaves
 //   hk_plan.hpp    launch_plan.hpp, launch_state.hpp and device_sky.hpp: hk_persistent_plan, hk_trace_plan, ..., hk_order_begin, ..., hk_sky_split, hk_sky_pixel, hk_sky_units_render
+//   hk_pipeline.hpp pipeline_state.hpp: the pipelined present loop's ticket book and ordering plans, hk_pipeline_*
 //   hk_kat.hpp     the shading step's known-answer hooks: hk_kat_sample .. hk_kat_store
 //   hk_rays.hpp    caller rays: hk_hit, hk_trace, hk_ray_surface, hk_radiance, hk_allhits, hk_allhits_brute
 //   hk_nearest.hpp caller points: hk_nearest, hk_nearest_brute, hk_nearest_prim(s), hk_nearest_records
@@ -45,6 +46,7 @@
 #include "../dogeray_amd/csrc/launch_state.hpp"
 #include "../dogeray_amd/csrc/linearise.hpp"
 #include "../dogeray_amd/csrc/params_host.hpp"
+#include "../dogeray_amd/csrc/pipeline_state.hpp"
 #include "../dogeray_amd/csrc/scene_host.hpp"
 
 using namespace dr;
@@ -54,6 +56,7 @@ using namespace dr;
 #include "host_kernel/hk_prims.hpp"
 #include "host_kernel/hk_cert.hpp"
 #include "host_kernel/hk_plan.hpp"
+#include "host_kernel/hk_pipeline.hpp"
 #include "host_kernel/hk_kat.hpp"
 #include "host_kernel/hk_rays.hpp"
 #include "host_kernel/hk_nearest.hpp"

@@ -90,6 +90,28 @@ _API = [
     ("hk_camera_words_compute", None, [_P, _P, _P, _I, _I, _I]),
     ("hk_camera_words_readable", _I, [_P]),
     ("hk_sky_split_launch", _I, [_P, _I, _I, _I, _I, _I]),
+    ("hk_pipeline_new", _P, []),
+    ("hk_pipeline_free", None, [_P]),
+    ("hk_pipeline_parked_max", _I, []),                       # the constant
+    ("hk_pipeline_group_room", _I, [_I, _I]),                 # frames
+    ("hk_pipeline_locate", None, [_P, _U64, _PI]),
+    ("hk_pipeline_submit_closes", _I, [_P, _I, _U64]),        # 1 / 0
+    ("hk_pipeline_owed_after", _I, [_P, _I]),                 # images
+    ("hk_pipeline_submit_overfills", _I, [_P, _I]),           # 1 / 0
+    ("hk_pipeline_hold", _U64, [_P, _I, _U64, _I]),
+    ("hk_pipeline_group_full", _I, [_P, _I]),                 # 1 / 0
+    ("hk_pipeline_flush_size", _I, [_P, _I]),                 # frames
+    ("hk_pipeline_drop_held", None, [_P]),
+    ("hk_pipeline_group_begin", None, [_P, _I, _P]),
+    ("hk_pipeline_group_plan", None, [_P, _I, _I, _PI]),
+    ("hk_pipeline_group_take_slot", None, [_P]),
+    ("hk_pipeline_group_commit", None, [_P, _P]),
+    ("hk_pipeline_mark_waited", _I, [_P, _U64]),              # 1 / 0
+    ("hk_pipeline_image", _Q, [_P, _U64]),
+    ("hk_pipeline_all_drained", None, [_P]),
+    ("hk_pipeline_join", None, [_P, _PI]),
+    ("hk_pipeline_restart_numbering", None, [_P, _I]),
+    ("hk_pipeline_dump", _I, [_P, _P, _I]),                   # words
     ("hk_sky_split", _I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     ("hk_sky_pixel", _I, _VIEW + [_F, _U64, _U64, _I, _I, _P, _P, _P]),
     ("hk_sky_units", C.c_uint, [C.c_uint, _I, _I]),
@@ -819,3 +841,94 @@ class LaunchState:
     def sky_split_launch(self, split, use_order, tiles, regions, room=True):
         """-> the stored split served the launch"""
         return bool(lib().hk_sky_split_launch(self.h, int(split), int(use_order), int(tiles), int(regions), int(room)))
+
+
+TICKET_PLACES = ("held", "slot", "parked", "finished", "never")
+GROUP_PLAN_FIELDS = ("start_behind", "host_wait_slot", "stream_wait_slot", "slot_last", "wait_barrier", "alone", "wait_streams")
+
+
+class PipelineBook:
+    """pipeline_state.hpp's ticket book with an integer for a frame's image, the slots' images and the group between group_begin and group_commit
+    (hk_pipeline_*).  A view is an integer (hk_pipeline.hpp)."""
+    PARKED_MAX = property(lambda self: lib().hk_pipeline_parked_max())
+
+    def __init__(self):
+        self.h = lib().hk_pipeline_new()
+
+    def __del__(self):
+        try:
+            lib().hk_pipeline_free(self.h)
+        except Exception:
+            pass
+
+    def locate(self, ticket):
+        """-> (one of TICKET_PLACES, slot, frame, waited for, presented)"""
+        out = (C.c_int * 5)()
+        lib().hk_pipeline_locate(self.h, ticket, out)
+        return TICKET_PLACES[out[0]], out[1], out[2], bool(out[3]), bool(out[4])
+
+    def submit_closes(self, view, seed):
+        return bool(lib().hk_pipeline_submit_closes(self.h, view, seed))
+
+    def owed_after(self, launches):
+        return lib().hk_pipeline_owed_after(self.h, launches)
+
+    def submit_overfills(self, closes):
+        return bool(lib().hk_pipeline_submit_overfills(self.h, int(closes)))
+
+    def hold(self, view, seed, div):
+        return lib().hk_pipeline_hold(self.h, view, seed, div)
+
+    def group_full(self, room):
+        return bool(lib().hk_pipeline_group_full(self.h, room))
+
+    def flush_size(self, room):
+        return lib().hk_pipeline_flush_size(self.h, room)
+
+    def drop_held(self):
+        lib().hk_pipeline_drop_held(self.h)
+
+    def group_begin(self, n):
+        """-> (slot, stream, first ticket, seed stride, tuple of the frames to park)"""
+        out = np.zeros(5 + 16, np.int64)
+        lib().hk_pipeline_group_begin(self.h, n, out.ctypes.data)
+        return int(out[0]), int(out[1]), int(out[2]) % 2 ** 64, int(out[3]) % 2 ** 64, tuple(int(v) for v in out[5:5 + int(out[4])])
+
+    def group_plan(self, refresh, cursor_wraps):
+        """-> dict of GROUP_PLAN_FIELDS"""
+        out = (C.c_int * 7)()
+        lib().hk_pipeline_group_plan(self.h, int(refresh), int(cursor_wraps), out)
+        return dict(zip(GROUP_PLAN_FIELDS, (int(v) for v in out)))
+
+    def group_take_slot(self):
+        lib().hk_pipeline_group_take_slot(self.h)
+
+    def group_commit(self, tokens):
+        t = np.array(list(tokens), np.int64)
+        lib().hk_pipeline_group_commit(self.h, t.ctypes.data)
+
+    def mark_waited(self, ticket):
+        return bool(lib().hk_pipeline_mark_waited(self.h, ticket))
+
+    def image(self, ticket):
+        return lib().hk_pipeline_image(self.h, ticket)
+
+    def all_drained(self):
+        lib().hk_pipeline_all_drained(self.h)
+
+    def join(self):
+        """join_plan and joined -> (tuple of the (slot, frame) whose adds `stream` waits for, mask of the streams whose newest launch)"""
+        out = (C.c_int * 12)()
+        lib().hk_pipeline_join(self.h, out)
+        n = out[0]
+        return tuple((out[1 + 2 * k], out[2 + 2 * k]) for k in range(n)), out[1 + 2 * n]
+
+    def restart_numbering(self, streams):
+        lib().hk_pipeline_restart_numbering(self.h, streams)
+
+    def dump(self):
+        """the whole book as a tuple of ints (hk_pipeline_dump lists the words)"""
+        n = lib().hk_pipeline_dump(self.h, None, 0)
+        out = np.zeros(n, np.int64)
+        lib().hk_pipeline_dump(self.h, out.ctypes.data, n)
+        return tuple(int(v) % 2 ** 64 for v in out)

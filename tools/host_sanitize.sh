@@ -1,6 +1,7 @@
 #!/bin/bash
 # Host C++ (reader, BVH builder, lineariser, wide-walk builder, .rtsb) under AddressSanitizer + UBSan on fuzzed, malformed
 # and golden scenes, plus BVH arrays with corrupted links (as a hand-made .rtsb or a caller's arrays could carry) (GPU sanitizers are not available on the pool; the device code is covered by the parity tests instead).
+# The driver first replays the pipelined present loop's ticket book (pipeline_state.hpp) through its scenarios.
 # usage: tools/host_sanitize.sh      (from the repo root; exits non-zero on any finding)
 set -e
 D=${TMPDIR:-/tmp}/dogeray_asan; rm -rf $D; mkdir -p $D/sc
