@@ -186,6 +186,16 @@ class DrErrorResult(C.Structure):
         return d
 
 
+class DrAdaptiveParams(C.Structure):
+    """struct dr_adaptive_params (include/dogeray_amd.h dr_render_adaptive)."""
+    _fields_ = [("tolerance", C.c_float), ("min_samples", C.c_int), ("max_samples", C.c_int), ("tile_pixels", C.c_int)]
+
+
+class DrAdaptiveResult(C.Structure):
+    """struct dr_adaptive_result: the tiles and pixels of one pass; samples_added = active_tiles * 64 * nframes."""
+    _fields_ = [("tiles", C.c_int64), ("active_tiles", C.c_int64), ("pixels", C.c_int64), ("asking_pixels", C.c_int64), ("samples_added", C.c_int64)]
+
+
 # every symbol include/dogeray_amd.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _API = [
@@ -227,6 +237,9 @@ _API = [
     ("dr_accum_moments_read", C.c_int, [_VP, _VP]),
     ("dr_accum_moments_device_ptr", C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     ("dr_accum_error", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.POINTER(DrErrorResult), C.c_int]),
+    ("dr_adaptive_defaults", C.c_int, [C.POINTER(DrAdaptiveParams)]),
+    ("dr_render_adaptive", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.POINTER(DrAdaptiveParams),
+                                     C.POINTER(DrAdaptiveResult)]),
     ("dr_reproject_defaults", C.c_int, [C.POINTER(DrReprojectParams)]),
     ("dr_accum_reproject", C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(DrReprojectParams), C.POINTER(DrReprojectResult)]),
     ("dr_render_accumulate_async", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_int]),
@@ -269,6 +282,7 @@ _API = [
     ("dr_stats_cert_levels", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_camera_entry", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_sky_tiles", C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("dr_stats_adaptive_tiles", C.c_int, [_VP, _VP, C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_wave_log", C.c_int, [_VP, C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
     ("dr_stats_pixel_cost", C.c_int, [_VP, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("dr_context_probe_gather", C.c_int, [_VP, C.c_uint32, C.c_int, C.POINTER(C.c_double)]),
@@ -453,6 +467,11 @@ def upscale_params(**params):
 def reproject_params(**params):
     """A DrReprojectParams: the library's defaults (dr_reproject_defaults) with the given fields replaced."""
     return _params(DrReprojectParams, "dr_reproject_defaults", "reproject", **params)
+
+
+def adaptive_params(**params):
+    """A DrAdaptiveParams: the library's defaults (dr_adaptive_defaults) with the given fields replaced."""
+    return _params(DrAdaptiveParams, "dr_adaptive_defaults", "adaptive", **params)
 
 
 def _out_array(shape, dtype, dev=None):
@@ -1214,6 +1233,52 @@ class Context:
                 break
         return frames, result
 
+    # ---- adaptive sampling (dr_render_adaptive)
+    def render_adaptive(self, settings13, W, H, background, frame_seed, seed_stride, nframes, divide_by, **params):
+        """One adaptive pass (include/dogeray_amd.h dr_render_adaptive): nframes frames (seeds frame_seed + k * seed_stride) into the 8x8 tiles whose
+        pixels still ask for samples -- n = history + divide_by below min_samples, or a noise estimate above tolerance -- and into no other pixel;
+        params = fields of dr_adaptive_params.  Needs a second-moment plane.  Returns a dict with the fields of dr_adaptive_result."""
+        st = _f32(settings13)
+        assert st.shape == (13,)
+        p = adaptive_params(**params)
+        r = DrAdaptiveResult()
+        _check(lib().dr_render_adaptive(self._h, _p(st), W, H, float(background), int(frame_seed) & (2 ** 64 - 1), int(seed_stride) & (2 ** 64 - 1),
+                                        int(nframes), int(divide_by), C.byref(p), C.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in DrAdaptiveResult._fields_}
+
+    def adaptive_tiles(self):
+        """uint8 flags of the last adaptive pass's tiles (dr_stats_adaptive_tiles; tile = block column * tile rows + row, 1 = rendered); empty
+        before the first pass."""
+        return self._sized_read("dr_stats_adaptive_tiles", np.uint8)
+
+    def render_until_adaptive(self, settings13, W, H, background, seed, stride, tolerance, permille, max_frames, check_every=8, frames_before=0, **params):
+        """render_until with the frames going where the noise is: max(min_samples - frames_before, 0) uniform frames through the pipeline, rounded up
+        to check_every, then adaptive passes of check_every frames with consecutive seeds (params = the other fields of dr_adaptive_params) until
+        the noise estimate says stop -- converged(error(...), permille) at `tolerance` --, a pass finds no active tile, or max_frames seeds have been
+        used (the uniform frames count, as render_until counts frames; the last pass is cut to what is left).  Every pixel's own count is in the history plane from the first pass on: present / error / denoise with the
+        uniform count frames_before + uniform frames.  Returns (uniform frames, passes, samples added by the passes, the last error() dict)."""
+        assert check_every >= 1 and max_frames >= 1
+        st = _f32(settings13)
+        p = adaptive_params(tolerance=tolerance, **params)
+        uniform = -(-max(p.min_samples - int(frames_before), 0) // check_every) * check_every
+        if uniform:
+            self.render_accumulate_pipelined(st, W, H, background, int(seed), stride, uniform)
+        div = int(frames_before) + uniform
+        frames, passes, samples = uniform, 0, 0
+        result = self.error(st, W, H, div, tolerance)
+        # (seeds are counted as render_until counts frames: the uniform frames and every pass's, max_frames in all, so that with every tile active
+        # the two leave the same sums)
+        while not self.converged(result, permille) and frames < max_frames:
+            n = min(check_every, max_frames - frames)
+            r = self.render_adaptive(st, W, H, background, int(seed) + frames * int(stride), stride, n, div, tolerance=tolerance, **params)
+            passes += 1
+            frames += n
+            samples += r["samples_added"]
+            if r["active_tiles"] == 0:
+                break
+            result = self.error(st, W, H, div, tolerance)
+        return uniform, passes, samples, result
+
     # ---- known-answer hooks (tests): shapes and dtypes in KAT_HOOKS, the marshalling in kat_marshal
     def _kat(self, hook, arrays, head=(), mid=(), outs=lambda out: [_p(a) for a in out], n=None):
         """kat_marshal calling dr_kat_<hook>(context, *head, n, inputs, *mid, outs(output arrays))"""
@@ -1497,3 +1562,17 @@ class ProgressiveRenderer:
         self.frames_rendered += frames
         self.iter += frames
         return frames, result
+
+    def run_until_adaptive(self, tolerance, permille, max_frames, check_every=8, **params):
+        """run_until with adaptive passes (Context.render_until_adaptive; params = fields of dr_adaptive_params).  iter -- and with it the
+        divide_by of step() / image() -- advances by the uniform frames only: what the passes add is counted per pixel in the history plane.
+        Returns (uniform frames, passes, samples added by the passes, the last Context.error dict)."""
+        assert self.iter >= 4, "run the preview ladder (four step() calls) first"
+        s, c = self.s, self.ctx
+        c._acc_shape = (self.W, self.H, 3)
+        before = self.iter - self._pnum
+        uniform, passes, samples, result = c.render_until_adaptive(pack_settings13(s, 1), self.W, self.H, s.background, self._seed(), self.seed_stride, tolerance,
+                                                                   permille, max_frames, check_every=check_every, frames_before=before, **params)
+        self.frames_rendered += min(uniform + passes * check_every, max_frames) if passes else uniform      # the seeds used: the last pass may be cut at max_frames
+        self.iter += uniform
+        return uniform, passes, samples, result

@@ -7,10 +7,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdogeray_amd.so")
 HOST_SOURCES = ["rts_reader.cpp", "bvh_builder.cpp", "linearise.cpp", "wide_builder.cpp", "capi_host.cpp", "group.cpp", "context.cpp", "context_render.cpp",
-                "context_pipeline.cpp", "context_accum.cpp", "context_query.cpp", "context_trace.cpp", "context_radiance.cpp", "context_nearest.cpp", "context_allhits.cpp",
+                "context_pipeline.cpp", "context_accum.cpp", "context_adaptive.cpp", "context_query.cpp", "context_trace.cpp", "context_radiance.cpp", "context_nearest.cpp", "context_allhits.cpp",
                 "context_probe.cpp"]
 # one translation unit per family of kernels (kernels.hpp)
-DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip",
+DEVICE_SOURCES = ["kernels_render.hip", "kernels_aux.hip", "kernels_aov.hip", "kernels_denoise.hip", "kernels_reproject.hip", "kernels_moments.hip", "kernels_adaptive.hip",
                   "kernels_upscale.hip", "kernels_trace.hip", "kernels_radiance.hip", "kernels_nearest.hip", "kernels_allhits.hip",
                   "kernels_kat.hip"]
 # -ffp-contract=off: no FMA contraction on host or device -- the BVH build and the kernel's

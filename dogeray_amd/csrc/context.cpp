@@ -364,6 +364,16 @@ int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry) {
   return DR_OK;
 }
 
+int dr_stats_adaptive_tiles(dr_context* c, uint8_t* out, int max, int* n_tiles) {
+  if (!c || !n_tiles || max < 0 || (max > 0 && !out)) { set_error("bad argument"); return DR_ERR_INVALID; }
+  *n_tiles = 0;
+  bool have;
+  DR_TRY(stats_ready(c, have, [&] { return c->adaptive.tiles > 0 && c->adaptive.flags; }));
+  if (!have) return DR_OK;
+  *n_tiles = c->adaptive.tiles;
+  return stats_copy(out, c->adaptive.flags.p, (size_t)*n_tiles, (size_t)max);
+}
+
 int dr_stats_wave_log(dr_context* c, unsigned long long* out, int max_waves, int* n_waves) {
   if (!c || !out || !n_waves || max_waves < 0) { set_error("bad argument"); return DR_ERR_INVALID; }
   if (!c->wave_log) { set_error("wave log is off (option wave_log)"); return DR_ERR_INVALID; }

@@ -6,6 +6,7 @@
 //   context_render.cpp     per-launch constants, the three caches around a launch, the launches of dr_render_frame / dr_render_accumulate*
 //   context_pipeline.cpp   pipelined single frames (dr_pipeline_*): asks pipeline_state.hpp's book, issues its plans, launches; FramePipeline's setup / drain
 //   context_accum.cpp      the accumulator: reset, AOV, denoise, upscale, reproject, error, present, stripes, reads
+//   context_adaptive.cpp   adaptive sampling (dr_render_adaptive): selection, the launches over the tile subset, the masked fold
 //   context_query.cpp      what the queries on caller lists share: staging in and out, scratch, cursor, the object map's upload
 //   context_trace.cpp      ray queries on caller rays (dr_trace_rays)
 //   context_radiance.cpp   radiance queries on caller rays (dr_trace_radiance)
@@ -123,10 +124,12 @@ struct GuidePlanes {
 };
 
 // Where a render launch goes and what it may touch on the way
+struct TileSubset;
 struct LaunchSite {
   hipStream_t stream;       // the launch, the tile counters' memset, the certificate mask and the feedback kernels
   bool hold_order;          // use the stored tile order as it is, record no costs, compute no mask (a pipelined launch beside another one)
   bool lean;                // option pipe_lean: the launch counts 0 for coop_tiles_per_wave
+  TileSubset* subset = nullptr;      // the launch renders the flagged tiles only (dr_render_adaptive; launch_state.hpp site_use); null everywhere else
 };
 
 // The three caches of a render launch (launch_state.hpp holds their state and every rule about it; context_render.cpp is the only writer).  Each owns
@@ -183,6 +186,30 @@ struct SkySplit {
     state.valid = false;
     DR_TRY(launch_order.grow((size_t)tiles, stream)); DR_TRY(list.grow((size_t)tiles, stream));
     DR_TRY(launch_region_start.grow(2 * MAX_REGIONS + 1, stream)); DR_TRY(counts.grow(2, stream));
+    return DR_OK;
+  }
+};
+
+// The tiles of one adaptive pass (dr_render_adaptive; context_adaptive.cpp is the only writer): a flag per tile of the view and the two
+// counts, made by the selection on the context's stream; the launch's own order / region_start pair, split from the order each of the pass's launches
+// would have used (context_render.cpp subset_split) and read by the persistent kernel and by the fold behind it; and the frame buffers the launches
+// render into.  No cache: every pass selects anew, `tiles` only says what dr_stats_adaptive_tiles may read back
+struct TileSubset {
+  DevMem<uint8_t> flags;
+  DevMem<unsigned> counts;                 // [AD_ACTIVE] active tiles, [AD_ASKING] asking pixels of the last selection
+  DevMem<int> launch_order, launch_region_start;
+  DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;      // cap_frames buffers of elems_each int32, one after the other
+  int tiles = 0;                           // tiles of the last pass's selection (0: none to read back)
+  void invalidate() { tiles = 0; }
+  int grow(int ntiles, size_t elems, int nframes, hipStream_t stream) {
+    tiles = 0;
+    DR_TRY(flags.grow((size_t)ntiles, stream)); DR_TRY(counts.grow(AD_WORDS, stream));
+    DR_TRY(launch_order.grow((size_t)ntiles, stream)); DR_TRY(launch_region_start.grow(2 * MAX_REGIONS + 1, stream));
+    if (elems_each != elems || cap_frames < nframes || !frames) {
+      cap_frames = 0;
+      DR_TRY(frames.grow(elems * (size_t)nframes, stream));
+      elems_each = elems; cap_frames = (int)(frames.n / elems);
+    }
     return DR_OK;
   }
 };
@@ -318,6 +345,7 @@ struct dr_context {
   int sample_order = DR_SAMPLE_ORDER;      // option: which samples of a tile share a unit of the queue (launch_plan.hpp tile_sample): 0 a frame's 64 pixels, 1 a pixel's frames
   int sky_tiles = 2;                       // option: 0 every tile goes through the persistent kernel; 1 sky_tiles_kernel in front of it; 2 its retiring waves
   dr::SkySplit sky;
+  dr::TileSubset adaptive;                 // dr_render_adaptive's tiles, launch pair and frame buffers
   // frame + accumulator
   DevMem<int32_t> frame;
   DevMem<int32_t> accum; int accW = 0, accH = 0;
@@ -378,6 +406,7 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
 // context_pipeline.cpp
 int join_pipeline(dr_context* c);
 int pipeline_flush(dr_context* c);
+int pipeline_group_room(const dr_context* c);      // how many frames a group may hold right now (the pipeline's groups, and dr_render_adaptive's)
 // context_query.cpp: a list of n caller items through the device and back; an accumulator stage's host outputs are the channels of a list of pixels
 // without inputs
 struct QueryIn { const void* p; int words; };                 // a caller's input array (null: not given) and its 4-byte words per item

@@ -39,6 +39,11 @@ FramePipeline::~FramePipeline() {
   if (acc_stream) (void)hipStreamDestroy(acc_stream);
 }
 
+// how many frames a group may hold right now
+int pipeline_group_room(const dr_context* c) {
+  return group_room(c->pipe_group, !c->pipe_lean && uses_persistent(c) && persistent_can_store_per_frame(persistent_cfg(c, c->own_site())));
+}
+
 // Work queued through the pipeline runs on streams of its own: everything else (which uses `stream`) is ordered behind it here.
 int join_pipeline(dr_context* c) {
   FramePipeline& p = c->pipe;
@@ -55,11 +60,6 @@ int join_pipeline(dr_context* c) {
 using namespace dr;
 
 namespace {
-
-// how many frames a group may hold right now
-int pipeline_group_room(const dr_context* c) {
-  return group_room(c->pipe_group, !c->pipe_lean && uses_persistent(c) && persistent_can_store_per_frame(persistent_cfg(c, c->own_site())));
-}
 
 // launches the first n held frames as one group
 int pipeline_flush_some(dr_context* c, int n) {

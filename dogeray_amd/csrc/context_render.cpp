@@ -129,13 +129,27 @@ bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles
   return true;
 }
 
+// A launch over the site's tile subset (dr_render_adaptive): order / region_start become the subset's own pair, split on the launch's stream from the
+// order this launch would have used and the subset's flags.  Made for every such launch -- a pass's groups may differ in their queues -- and read
+// behind it by the fold (launch_adaptive_add), on the same stream.
+void subset_split(const LaunchSite& site, const RenderParams& P, int tiles, const int*& order, const int*& region_start) {
+  TileSubset& sub = *site.subset;
+  launch_subset_split(site.stream, order, region_start, P.region_start, sub.flags, tiles, P.regions, sub.launch_order, sub.launch_region_start);
+  order = sub.launch_order; region_start = sub.launch_region_start;
+}
+
 }  // namespace
 
-// enqueue one launch (P.batch frames) at `site`; no events, no sync
-int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_in) {
+// enqueue one launch (P.batch frames) at `site_in`; no events, no sync
+int enqueue_frame(dr_context* c, const LaunchSite& site_in, const RenderParams& P_in) {
   RenderParams P = P_in;
   const int tiles = P.ncols * P.gy;
   P.sample_magic = sample_order_magic(c->sample_order, P.batch);      // every launch comes through here with its batch set (dr_render_accumulate, the pipeline's groups)
+  // (a held launch runs beside the previous frame's: it may read the tile order but nobody may write it, or the costs, meanwhile; a launch over a
+  // tile subset is held too -- its costs would be a part of the view's: launch_state.hpp site_use)
+  const SiteUse su = site_use(site_in.hold_order, site_in.subset != nullptr);
+  LaunchSite site = site_in;
+  site.hold_order = su.hold;
   if (uses_persistent(c)) {
     if (c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS) {
       (void)hipMemsetAsync(c->tile_counters, 0, TILE_COUNTERS * sizeof(unsigned), site.stream);
@@ -144,13 +158,13 @@ int enqueue_frame(dr_context* c, const LaunchSite& site, const RenderParams& P_i
     unsigned* counter = c->tile_counters + c->tile_cursor;      // one counter per region, and the sky units' cursor behind them
     c->tile_cursor += LAUNCH_COUNTERS;
     const ViewKey key = view_key(c, P);
-    // (a held launch runs beside the previous frame's: it may read the tile order but nobody may write it, or the costs, meanwhile)
     const int* order; unsigned* pcost;
     const OrderUse use = feedback_buffers(c, site, key, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
     cert_prepare(c, site, key, P, tiles);
     const int* launch_order = order; const int* launch_rstart = c->order.region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
-    c->sky.state.last = sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
+    c->sky.state.last = su.sky_split && sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
+    if (su.subset_pair) subset_split(site, P, tiles, launch_order, launch_rstart);
     const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, launch_order, launch_rstart, pcost);
     if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
     c->wave_log_waves = log_waves;

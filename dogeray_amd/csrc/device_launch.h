@@ -88,6 +88,30 @@ struct MoLaunch {
   unsigned long long* counts;
 };
 
+// kernels_adaptive.hip (dr_render_adaptive; device_adaptive.hpp): one pass over the gx x gy tiles of the view's pixel grid -- tile t = col * gy + by,
+// its lane l pixel (8 col + (l >> 3), 8 by + (l & 7)), as in the render kernels.  The selection reads the three planes and writes a flag per tile
+// and the two counts; the fold adds `nframes` frame buffers (frame f at frames + f * frame_stride, the accumulator's layout) into the planes of the
+// tiles a compacted list names.
+struct AdParams {
+  float tolerance;
+  int min_samples, max_samples, tile_pixels;
+};
+constexpr int AD_ACTIVE = 0, AD_ASKING = 1, AD_WORDS = 2;      // the counts: active tiles, asking pixels
+struct AdLaunch {
+  int gx, gy;                     // the tile grid
+  int W, H;                       // the accumulator: sums column-major (x * H + y) * 3, history and M2 at x * H + y
+  int divide_by;
+  AdParams A;
+  int nframes;                    // the fold: frames per pixel
+  size_t frame_stride;            // ... and the int32 words from one frame buffer to the next
+  int32_t* acc;
+  int32_t* hist;                  // the selection: null = no history plane (0 everywhere); the fold needs one
+  unsigned long long* m2;
+  const int32_t* frames;
+  uint8_t* flags;                 // a byte per tile: 1 active
+  unsigned* counts;               // AD_WORDS words, added to
+};
+
 // kernels_radiance.hip (dr_trace_radiance): n caller rays (origin / dir 3 floats per ray), their seeds (null: base_seed + i) and the generator outputs
 // to discard after seeding (null: none), spp samples each; radiance (3 floats per ray: the samples' float sum) and bounces (closest-hit queries of all
 // samples), null: not written.  max_depth, the background and backtex travel in RenderParams, where trace_path reads them.

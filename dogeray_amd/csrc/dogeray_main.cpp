@@ -128,7 +128,7 @@ void usage() {
           "usage: dogeray [scene.rts] [--textures DIR] [--frames N] [--out FILE.bmp|.ppm] [--width W] [--height H]\n"
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
           "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm] [--move-to CX,CY,CZ,LX,LY,LZ] [--move-frames N]\n"
-          "               [--until-sigma T[,PERMILLE]] [--max-frames N] [--sigma-out FILE.pfm] [--preview PREFIX] [--preview-block]\n"
+          "               [--until-sigma T[,PERMILLE]] [--adaptive] [--max-frames N] [--sigma-out FILE.pfm] [--preview PREFIX] [--preview-block]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -149,6 +149,8 @@ void usage() {
           "  --until-sigma  instead of --frames: add full-resolution frames, eight at a time, until at most PERMILLE per mille (default 10) of the pixels\n"
           "               have a standard error of the displayed mean luma above T (0..255 units; dr_accum_error, option moments) or --max-frames N\n"
           "               (default 1024) have been added; one line reports which (one context only: not with --gpus)\n"
+          "  --adaptive   with --until-sigma: after the first eight frames only the 8x8 tiles with a pixel above T are rendered on, eight frames a pass\n"
+          "               (dr_render_adaptive, default parameters; the line also reports the uniform frames and the samples the passes added)\n"
           "  --sigma-out  after the render, write that standard error per pixel as a one-channel .pfm (needs no --until-sigma)\n"
           "  --preview    write the three low stages of the preview ladder (1/8, 1/4, 1/2 resolution) at full size as PREFIX_8.bmp, PREFIX_4.bmp and\n"
           "               PREFIX_2.bmp: the AOV-guided upsample of each stage (dr_accum_upscale, default parameters)\n"
@@ -164,7 +166,7 @@ int main(int argc, char** argv) {
   float move_to[6] = {0, 0, 0, 0, 0, 0};
   int move_frames = 1;
   std::string sigma_path;
-  bool until = false;
+  bool until = false, adaptive = false;
   float until_sigma = 0;
   int until_permille = 10, max_frames = 1024;
   const char* texdir = nullptr;
@@ -201,6 +203,7 @@ int main(int argc, char** argv) {
       if (got < 1 || !(until_sigma >= 0.0f) || until_permille < 0) { usage(); return 2; }
       until = true;
     }
+    else if (a == "--adaptive") adaptive = true;
     else if (a == "--max-frames") max_frames = atoi(next());
     else if (a == "--sigma-out") sigma_path = next();
     else if (a == "--preview") preview_prefix = next();
@@ -214,6 +217,7 @@ int main(int argc, char** argv) {
 
   const bool moments = until || !sigma_path.empty();
   if (moments && gpus >= 1) { fprintf(stderr, "dogeray: --until-sigma / --sigma-out need a single context (no --gpus)\n"); return 2; }
+  if (adaptive && !until) { fprintf(stderr, "dogeray: --adaptive needs --until-sigma\n"); return 2; }
   if (until && max_frames < 1) { fprintf(stderr, "dogeray: --max-frames must be >= 1\n"); return 2; }
   if (until) frames = 0;                 // the frames after the preview ladder are counted by the noise estimate
 
@@ -366,18 +370,43 @@ int main(int argc, char** argv) {
     dr_error_result er;
     memset(&er, 0, sizeof(er));
     bool converged = false;
-    while (added < max_frames && !converged) {
+    auto judge = [&](int div) {
+      if (dr_accum_error(ctx, st, W, H, div, until_sigma, nullptr, &er, 0) != DR_OK) die("error estimate");
+      converged = (er.above + (er.pixels - er.estimated)) * 1000 <= (int64_t)until_permille * er.pixels;
+    };
+    int uniform = 0;                     // --adaptive: the frames every pixel got; the passes' frames are counted per pixel in the history plane
+    long long samples_added = 0;
+    if (adaptive) {                      // the loop of Context.render_until_adaptive
+      dr_adaptive_params ap;
+      dr_adaptive_defaults(&ap);
+      ap.tolerance = until_sigma;
+      uniform = ap.min_samples > before ? (ap.min_samples - before + 7) / 8 * 8 : 0;
+      if (uniform > 0 && dr_render_accumulate_pipelined(ctx, st, W, H, s.background, seed + frame_no * seed_stride, seed_stride, uniform) != DR_OK) die("render");
+      frame_no += (uint64_t)uniform; added = uniform;
+      judge(before + uniform);
+      while (added < max_frames && !converged) {
+        const int n = max_frames - added < 8 ? max_frames - added : 8;
+        dr_adaptive_result ar;
+        if (dr_render_adaptive(ctx, st, W, H, s.background, seed + frame_no * seed_stride, seed_stride, n, before + uniform, &ap, &ar) != DR_OK) die("adaptive pass");
+        frame_no += (uint64_t)n; added += n;
+        samples_added += (long long)ar.samples_added;
+        if (ar.active_tiles == 0) break;
+        judge(before + uniform);
+      }
+    }
+    while (!adaptive && added < max_frames && !converged) {
       const int n = max_frames - added < 8 ? max_frames - added : 8;
       if (dr_render_accumulate_pipelined(ctx, st, W, H, s.background, seed + frame_no * seed_stride, seed_stride, n) != DR_OK) die("render");
       frame_no += (uint64_t)n; added += n;
-      if (dr_accum_error(ctx, st, W, H, before + added, until_sigma, nullptr, &er, 0) != DR_OK) die("error estimate");
-      converged = (er.above + (er.pixels - er.estimated)) * 1000 <= (int64_t)until_permille * er.pixels;
+      judge(before + added);
     }
     memcpy(last_st, st, sizeof(last_st));
-    divide_by = before + added;
+    divide_by = before + (adaptive ? uniform : added);
     if (dr_accum_present(ctx, divide_by, rgb.data()) != DR_OK) die("present");
-    printf("%s after %d frames: %lld of %lld pixels above %g\n", converged ? "converged" : "not converged", added, (long long)er.above, (long long)er.pixels,
+    printf("%s after %d frames: %lld of %lld pixels above %g", converged ? "converged" : "not converged", added, (long long)er.above, (long long)er.pixels,
            (double)until_sigma);
+    if (adaptive) printf("; adaptive: %d uniform frames, %lld samples added", uniform, samples_added);
+    printf("\n");
   }
 
   if (move) {                            // a camera move: carry the image into the new view, then add frames there

@@ -11,6 +11,7 @@
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
 //   kernels_moments.hip       the second-moment plane: the fused frame add and the per-pixel noise estimate (option "moments", dr_accum_error)
+//   kernels_adaptive.hip      adaptive sampling: the tiles that ask for samples, the launch's order without the others, the masked fold (dr_render_adaptive)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp and the context_*.cpp files (host only: resident scene, options, the C ABI) call these and never see a kernel.
 #pragma once
@@ -177,5 +178,14 @@ void launch_reproject(hipStream_t stream, const RpLaunch& L);
 // acc += frame and m2 += the frame's capped luma squared, in one pass (npix pixels; acc / frame column-major x 3, m2 one word per pixel)
 void launch_moments_add(hipStream_t stream, int32_t* acc, const int32_t* frame, unsigned long long* m2, size_t npix);
 void launch_moments_error(hipStream_t stream, const MoLaunch& L);
+
+// kernels_adaptive.hip (dr_render_adaptive; device_adaptive.hpp describes the arrays)
+void launch_adaptive_select(hipStream_t stream, const AdLaunch& L);      // the planes -> L.flags, L.counts
+// the split of a launch's order by a flag per tile -- order / region_start as the persistent kernel would take them (order null: the identity, regions
+// from own_region_start, MAX_REGIONS + 1 ints on the host) -- into launch_order / launch_region_start for the persistent kernel and launch_adaptive_add
+void launch_subset_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint8_t* flag, int tiles, int regions,
+                         int* launch_order, int* launch_region_start);
+// L.nframes frame buffers into the planes of the launch_region_start[regions] tiles at the head of launch_order
+void launch_adaptive_add(hipStream_t stream, const AdLaunch& L, const int* launch_order, const int* launch_region_start, int regions);
 
 }  // namespace dr

@@ -154,4 +154,15 @@ inline bool sky_split_reusable(const SkySplitState& s, const SkyKey& key, bool r
          s.key.regions == key.regions;
 }
 
+// ---- a launch over a subset of the view's tiles (dr_render_adaptive): the launch's own order / region_start pair holds the tiles its site names and
+// none of the three caches is rewritten (the order's age counts the launch, as it counts every held one).  What the site's two fields make of a launch: it is held -- the stored order as it is (or the identity), no costs,
+// no feedback pass, the view's cached tile words or none (order_begin and camera_words_plan with hold_order) -- whenever it has a subset; a subset is
+// never split again for the sky (its sky tiles go through the queues: the same bits); and the queues take the subset's pair
+struct SiteUse {
+  bool hold;                 // what order_begin, camera_words_plan and sky_split are told for hold_order
+  bool sky_split;            // the sky split may be asked at all
+  bool subset_pair;          // the persistent kernel's queues hold the subset's pair
+};
+inline SiteUse site_use(bool hold_order, bool has_subset) { return {hold_order || has_subset, !has_subset, has_subset}; }
+
 }  // namespace dr

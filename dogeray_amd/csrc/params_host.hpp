@@ -237,6 +237,26 @@ inline std::string judge_error(const RenderParams& P, int divide_by, float toler
   return "";
 }
 
+// dr_render_adaptive: the defaults, the ranges and the pass's launch over the tile grid of view P
+constexpr AdParams AD_DEFAULTS = {1.0f, 4, 0, 1};
+inline AdParams ad_params(const dr_adaptive_params& p) { return {p.tolerance, p.min_samples, p.max_samples, p.tile_pixels}; }
+inline const char* check_adaptive_params(const AdParams& A) {
+  if (!(A.tolerance >= 0.0f)) return "adaptive: tolerance must be >= 0";
+  if (A.min_samples < 2) return "adaptive: min_samples must be >= 2";
+  if (A.max_samples != 0 && A.max_samples <= A.min_samples) return "adaptive: max_samples must be 0 or > min_samples";
+  if (A.tile_pixels < 1 || A.tile_pixels > 64) return "adaptive: tile_pixels must be 1 .. 64";
+  return nullptr;
+}
+inline std::string judge_adaptive(const RenderParams& P, int nframes, int divide_by, const dr_adaptive_params* params, AdLaunch& L) {
+  if (nframes < 1) return "adaptive: nframes must be >= 1";
+  if (divide_by < 0) return "adaptive: divide_by must be >= 0";
+  const AdParams A = params ? ad_params(*params) : AD_DEFAULTS;
+  if (const char* why = check_adaptive_params(A)) return why;
+  memset(&L, 0, sizeof(L));
+  L.gx = P.gx; L.gy = P.gy; L.W = P.W; L.H = P.H; L.divide_by = divide_by; L.A = A; L.nframes = nframes;
+  return "";
+}
+
 // The certificate's ladder for option cert_factor (CertView level_a, ascending; a_star stays level_a[base] = 1e-4 cert_factor): graded, cert_factor x
 // {1/4, 1/2, 1, 2, 4}, each step at least the 1e-4 cut-off itself (the lemma needs a_star >= 1e-4); otherwise the single step cert_factor.
 inline void cert_ladder(int cert_factor, bool graded, CertView& cv) {

@@ -742,6 +742,46 @@ int dr_accum_error(dr_context* c, const float settings13[13], int W, int H, int 
 int dr_accum_moments_read(dr_context* c, uint64_t* out /* W*H */);
 int dr_accum_moments_device_ptr(dr_context* c, void** dev_ptr, uint64_t* bytes);
 
+/* ------------------------------------------------------------------ adaptive sampling ---- */
+/* Acting on the noise estimate: one call is one PASS, which adds nframes frames to the 8x8 tiles whose pixels still ask for samples and to no other
+ * pixel.  The render kernels are the ones every other call launches, over a shorter tile order.  All arithmetic is the second
+ * moments' above, so the GPU is bit-identical to the host build of the same source (dogeray_amd/csrc/device_adaptive.hpp) and to the numpy
+ * restatement in the tests.
+ *   selection  made from the planes as they are when the call is reached in stream order, behind the frames submitted before it.  For grid pixel p,
+ *              n = hist_p + divide_by (hist_p = 0 without a history plane; a "sample" is a frame, as everywhere else).  The pixel ASKS when
+ *                n < min_samples, or
+ *                (max_samples == 0 or n < max_samples) and n >= 2 and sigma_p > tolerance -- var_p, sigma_p and the float comparison exactly as
+ *                dr_accum_error forms dr_error_result.above
+ *              The view's pixel grid is cut into the render kernels' tiles: tile t = col * gy + by (gy = H / div / 8 tile rows, col the block
+ *              column), its lane l the pixel (8 col + (l >> 3), 8 by + (l & 7)).  A tile is ACTIVE when at least tile_pixels of its 64 pixels ask
+ *   render     frames k = 0 .. nframes - 1 with seeds frame_seed + k * seed_stride are rendered in the active tiles only; F_k below is, bit for bit,
+ *              what dr_render_frame returns for that seed
+ *   fold       for every pixel of an active tile, and every k: acc += F_k (wrapping) and M2 = M2 + yc(F_k)^2 (saturating: the add above); then
+ *              hist += nframes.  Every other pixel of the three planes keeps its bits.  Without a history plane one of zeros is made first (it stays
+ *              until dr_accum_reset, and dr_accum_present and the other stages divide by it from then on: pass the count of the uniform frames)
+ *   limits     choosing where to sample from the samples' own variance is not exactly unbiased: a pixel whose first samples happen to agree stops
+ *              early.  min_samples and the tile granularity (a tile is rendered whole) are the guard; nothing stronger is claimed
+ * dr_stats.samples grows by the samples really traced and dr_stats.launches by the launches; dr_stats.frames does not change. */
+typedef struct dr_adaptive_params {
+  float tolerance;       /* >= 0, not NaN: the sigma_p a pixel may keep (0..255 units) */
+  int min_samples;       /* >= 2 (default 4): pixels with fewer samples ask whatever their estimate says */
+  int max_samples;       /* 0: no limit (default); otherwise > min_samples: pixels with that many samples do not ask */
+  int tile_pixels;       /* 1 .. 64 (default 1): asking pixels that make a tile active */
+} dr_adaptive_params;
+typedef struct dr_adaptive_result {
+  int64_t tiles;         /* gx * gy, the tiles of the pixel grid of settings13 */
+  int64_t active_tiles;
+  int64_t pixels;        /* 64 * tiles */
+  int64_t asking_pixels;
+  int64_t samples_added; /* active_tiles * 64 * nframes */
+} dr_adaptive_result;
+int dr_adaptive_defaults(dr_adaptive_params* p);      /* tolerance 1.0 */
+/* One pass (params NULL: the defaults; result may be NULL).  Returns when the pass has been folded.  DR_ERR_INVALID, and no plane touched, for: no
+ * scene, no accumulator or W / H not the accumulator's, no moments plane, a stripe other than (1, 0), the tile-per-launch kernel or the ordered
+ * traversal (the pass needs the persistent kernel's queues), nframes < 1, divide_by < 0, parameters outside their ranges; settings13 as dr_render_frame. */
+int dr_render_adaptive(dr_context* c, const float settings13[13], int W, int H, float background, uint64_t frame_seed, uint64_t seed_stride, int nframes,
+                       int divide_by, const dr_adaptive_params* params, dr_adaptive_result* result);
+
 /* ------------------------------------------------------------------ multi-GPU group ----- */
 /* One process, one context and one host thread per GPU (the reference is single-device, K:2614-2615).  Rank r of n
  * renders the block columns bx % n == r of every frame (scene replicated); every `gather_every` frames each rank packs
@@ -805,6 +845,9 @@ int dr_stats_camera_entry(dr_context* c, int32_t* out, int max, int* n_tiles);
 /* The last launch's split (option sky_tiles): *n_sky = the tiles rendered by the sky kernel (entry code -1), *n_geometry = the tiles left to the
  * persistent kernel; both 0 when the launch was not split. */
 int dr_stats_sky_tiles(dr_context* c, int* n_sky, int* n_geometry);
+/* The last adaptive pass's tiles (dr_render_adaptive): one byte per tile, tile = block column * tile rows + row, 1 = active (rendered), 0 = left alone.
+ * *n_tiles = 0 when no pass has run since the context was made; otherwise the tiles, and the first min(max, n_tiles) bytes are copied to out. */
+int dr_stats_adaptive_tiles(dr_context* c, uint8_t* out, int max, int* n_tiles);
 
 /* Timeline of the last SHORT persistent-kernel launch (fewer than coop_tiles_per_wave tiles per wave: one frame, a thin stripe;
  * option "wave_log" = 1 before the launch): sixteen words per wave --

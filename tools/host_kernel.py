@@ -90,6 +90,7 @@ _API = [
     ("hk_camera_words_compute", None, [_P, _P, _P, _I, _I, _I]),
     ("hk_camera_words_readable", _I, [_P]),
     ("hk_sky_split_launch", _I, [_P, _I, _I, _I, _I, _I]),
+    ("hk_site_use", _I, [_I, _I]),                            # bits
     ("hk_pipeline_new", _P, []),
     ("hk_pipeline_free", None, [_P]),
     ("hk_pipeline_parked_max", _I, []),                       # the constant
@@ -143,6 +144,9 @@ _API = [
     ("hk_reproject", _I, [_P, _P, _I, _I, _I] + [_P] * 12 + [_I, _P, _P]),
     ("hk_moments_add", _I, [_P, _P, _P, _Q]),
     ("hk_error", _I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _I]),
+    ("hk_adaptive_select", _I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    ("hk_subset_split", _I, [_P, _P, _P, _I, _I, _P, _P]),    # flagged tiles
+    ("hk_adaptive_add", _I, [_P, _P, _P, _I, _I, _P, _P, _I, _P, _I]),
 ] + [("hk_" + k, t, []) for k, t in _CONSTANTS]
 API_SYMBOLS = [a[0] for a in _API]
 
@@ -691,6 +695,59 @@ def error(acc, hist, m2, settings13, divide_by, tolerance, nthreads=4):
                        grid.ctypes.data, nthreads))
     d = {"pixels": int(grid[0]) * int(grid[1]), "estimated": int(res[0]), "above": int(res[1]), "sum_var_q16": int(res[2]), "bins": [int(v) for v in res[3:]]}
     return sigma, d
+
+
+ADAPTIVE_DEFAULTS = {"tolerance": 1.0, "min_samples": 4, "max_samples": 0, "tile_pixels": 1}      # dr_adaptive_defaults
+
+
+def _adaptive_words(params):
+    """a dr_adaptive_params as four words (float, int, int, int)"""
+    p = dict(ADAPTIVE_DEFAULTS, **params)
+    w = np.zeros(4, np.int32)
+    w[:1] = np.array([p["tolerance"]], np.float32).view(np.int32)
+    w[1:] = [int(p["min_samples"]), int(p["max_samples"]), int(p["tile_pixels"])]
+    return w
+
+
+def adaptive_select(acc, hist, m2, settings13, divide_by, **params):
+    """dr_render_adaptive's selection on the host (device_adaptive.hpp): the accumulator's planes as error() takes them, params = fields of
+    dr_adaptive_params -> (flags uint8[gx * gy], tile = block column * gy + row; dict active_tiles, asking_pixels, tiles, pixels, gx, gy)."""
+    acc = _arr(acc, np.int32)
+    W, H = acc.shape[0], acc.shape[1]
+    st, m2, hist = _arr(settings13, np.float32), _arr(m2, np.uint64, (W, H)), _arr(hist, np.int32, (W, H))
+    d = _div(st)
+    flags, counts, grid, words = np.zeros(max(1, (W // d // 8) * (H // d // 8)), np.uint8), np.zeros(2, np.int64), np.zeros(2, np.int32), _adaptive_words(params)
+    _ok(lib().hk_adaptive_select(acc.ctypes.data, _ptr(hist), m2.ctypes.data, W, H, int(divide_by), st.ctypes.data, words.ctypes.data, flags.ctypes.data,
+                                 counts.ctypes.data, grid.ctypes.data))
+    tiles = int(grid[0]) * int(grid[1])
+    return flags[:tiles], {"tiles": tiles, "active_tiles": int(counts[0]), "pixels": 64 * tiles, "asking_pixels": int(counts[1]), "gx": int(grid[0]), "gy": int(grid[1])}
+
+
+def subset_split(order, region_start, flags, regions):
+    """device_adaptive.hpp subset_split_plain (hk_subset_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], flags
+    uint8[tiles] -> (launch_order int32[flagged tiles], launch_region_start int32[17])."""
+    flags, rs, o = _arr(flags, np.uint8), _arr(region_start, np.int32), _arr(order, np.int32)
+    tiles = len(flags)
+    lo, lrs = np.zeros(max(1, tiles), np.int32), np.zeros(17, np.int32)
+    n = lib().hk_subset_split(_ptr(o), rs.ctypes.data, flags.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data)
+    return lo[:n], lrs
+
+
+def adaptive_add(acc, hist, m2, settings13, frames, tiles):
+    """dr_render_adaptive's fold on the host (device_adaptive.hpp ad_fold_pixel): frames int32[n, W, H, 3] into acc int32[W, H, 3], m2 uint64[W, H]
+    and hist int32[W, H] (+= n) at the pixels of the listed tiles, IN PLACE; the planes must be C-contiguous arrays of exactly these types."""
+    assert acc.dtype == np.int32 and m2.dtype == np.uint64 and hist.dtype == np.int32 and acc.flags.c_contiguous and m2.flags.c_contiguous and hist.flags.c_contiguous
+    W, H = acc.shape[0], acc.shape[1]
+    frames, st, tiles = _arr(frames, np.int32), _arr(settings13, np.float32), _arr(tiles, np.int32)
+    assert frames.ndim == 4 and frames.shape[1:] == (W, H, 3) and m2.shape == (W, H) and hist.shape == (W, H)
+    _ok(lib().hk_adaptive_add(acc.ctypes.data, hist.ctypes.data, m2.ctypes.data, W, H, st.ctypes.data, frames.ctypes.data, frames.shape[0], _ptr(tiles), len(tiles)))
+    return acc, hist, m2
+
+
+def site_use(hold_order, has_subset):
+    """launch_state.hpp site_use -> (hold, sky_split, subset_pair)"""
+    u = lib().hk_site_use(int(bool(hold_order)), int(bool(has_subset)))
+    return bool(u & 1), bool(u & 2), bool(u & 4)
 
 
 BUILD_FIELDS = ("count", "occ", "trav_min", "park_min", "unroll", "wide", "coop", "perframe")

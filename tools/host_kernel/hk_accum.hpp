@@ -1,4 +1,4 @@
-// The accumulator stages on the host (hk_denoise, hk_upscale, hk_reproject, hk_moments_add, hk_error): the launch structs of device_launch.h filled with
+// The accumulator stages on the host (hk_denoise, hk_upscale, hk_reproject, hk_moments_add, hk_error, hk_adaptive_select / _add): the launch structs of device_launch.h filled with
 // host pointers and a loop over the pixels; no stage's arithmetic or indexing is written here.  A call is judged, and its launch struct's grid,
 // sizes and parameters filled, by params_host.hpp's judge_* -- the judges the library runs; an entry here adds the pointers.  Part of host_kernel.cpp.
 namespace {
@@ -190,6 +190,52 @@ int hk_error(const int32_t* acc, const int32_t* hist, const unsigned long long* 
   });
   if (result)
     for (int w = 0; w < MO_WORDS; w++) { result[w] = 0; for (int y = 0; y < L.gh; y++) result[w] += part[(size_t)y * MO_WORDS + (size_t)w]; }
+  return 0;
+}
+
+// dr_render_adaptive's selection on the host: device_adaptive.hpp over the tiles of settings13's pixel grid.  Planes as hk_error's (hist may be NULL);
+// params: a dr_adaptive_params (NULL: the defaults); flags: a byte per tile; counts[2]: active tiles, asking pixels; grid2: gx, gy.
+// Returns 0, or -1 with hk_last_error (the library's refusals of nframes -- pass 1 --, divide_by and the parameters).
+int hk_adaptive_select(const int32_t* acc, const int32_t* hist, const unsigned long long* m2, int W, int H, int divide_by, const float* settings13,
+                       const int32_t* params, uint8_t* flags, long long* counts, int* grid2) {
+  if (!acc || !m2 || !settings13 || !flags || !counts) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  AdLaunch L;
+  hk_err = judge_adaptive(P, 1, divide_by, ParamWords<dr_adaptive_params>(params).get(), L);
+  if (!hk_err.empty()) return -1;
+  L.acc = const_cast<int32_t*>(acc); L.hist = const_cast<int32_t*>(hist); L.m2 = const_cast<unsigned long long*>(m2);
+  if (grid2) { grid2[0] = L.gx; grid2[1] = L.gy; }
+  counts[AD_ACTIVE] = counts[AD_ASKING] = 0;
+  for (int t = 0; t < L.gx * L.gy; t++) {
+    int asking = 0;
+    for (int lane = 0; lane < 64; lane++) asking += ad_asks(L, t, lane) ? 1 : 0;
+    flags[t] = ad_tile_active(L, asking) ? 1 : 0;
+    counts[AD_ACTIVE] += flags[t]; counts[AD_ASKING] += asking;
+  }
+  return 0;
+}
+
+// device_adaptive.hpp subset_split_plain: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of flagged tiles
+int hk_subset_split(const int* order, const int* region_start, const uint8_t* flag, int tiles, int regions, int* launch_order, int* launch_region_start) {
+  return subset_split_plain(order, region_start, flag, tiles, regions, launch_order, launch_region_start);
+}
+
+// dr_render_adaptive's fold on the host: ad_fold_pixel over the n tiles of list (tile = block column * gy + row of settings13's grid), IN PLACE --
+// nframes frames in the accumulator's layout, frame f at frames + f * W * H * 3.  Returns 0, or -1 with hk_last_error.
+int hk_adaptive_add(int32_t* acc, int32_t* hist, unsigned long long* m2, int W, int H, const float* settings13, const int32_t* frames, int nframes,
+                    const int* list, int n) {
+  if (!acc || !hist || !m2 || !settings13 || !frames || (n > 0 && !list)) { hk_err = "bad argument"; return -1; }
+  RenderParams P;
+  if (const char* why = host_view(settings13, W, H, 0.0f, 0, 1, 0, P)) { hk_err = why; return -1; }
+  AdLaunch L;
+  hk_err = judge_adaptive(P, nframes, 0, nullptr, L);
+  if (!hk_err.empty()) return -1;
+  L.acc = acc; L.hist = hist; L.m2 = m2; L.frames = frames; L.frame_stride = (size_t)W * H * 3;
+  for (int i = 0; i < n; i++) {
+    if (list[i] < 0 || list[i] >= L.gx * L.gy) { hk_err = "adaptive: a listed tile is outside the grid"; return -1; }
+    for (int lane = 0; lane < 64; lane++) ad_fold_pixel(L, list[i], lane);
+  }
   return 0;
 }
 }  // extern "C"

@@ -195,4 +195,9 @@ int hk_sky_split_launch(void* h, int split, int use_order, int tiles, int region
   sky_split_commit(s.sky, key);
   return 0;
 }
+// launch_state.hpp site_use: hold | sky_split << 1 | subset_pair << 2
+int hk_site_use(int hold_order, int has_subset) {
+  const SiteUse u = site_use(hold_order != 0, has_subset != 0);
+  return (u.hold ? 1 : 0) | (u.sky_split ? 2 : 0) | (u.subset_pair ? 4 : 0);
+}
 }  // extern "C"
