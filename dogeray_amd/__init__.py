@@ -306,6 +306,7 @@ _API = [
     ("dr_kat_store_merged", C.c_int, [_VP, C.c_int, C.c_int] + [_VP] * 5 + [C.c_int] * 3 + [_VP] * 3),
     ("dr_stats_tile_order", C.c_int, [_VP, _VP, C.c_size_t, C.POINTER(C.c_size_t), _VP, _VP]),
     ("dr_kat_tile_feedback", C.c_int, [_VP] + [C.c_int] * 5 + [_VP] * 4),
+    ("dr_kat_order_split", C.c_int, [_VP] + [C.c_int] * 3 + [_VP] * 7),
 ]
 API_SYMBOLS = [a[0] for a in _API]
 
@@ -371,6 +372,8 @@ KAT_HOOKS = {
     "camera": ((("x", _I32, ()), ("y", _I32, ()), ("sample", _I32, ())), ((_F32, (2, "n", 3)), (_F32, (2, "n", 3)), (_U32, (2, "n", 2)))),
     "store": ((("color", _F32, (3,)),), ((_I32, ("n", 3)),)),
     "tile_feedback": ((("pixel_cost", _U32, (64,)),), ((_U32, ("n",)), (_I32, ("n",)), (_I32, (2 * MAX_REGIONS + 1,)))),
+    "order_split": ((("order", _I32, ()), ("region_start", _I32, ()), ("key", _U32, ())),
+                    ((_I32, ("n",)), (_I32, (2 * MAX_REGIONS + 1,)), (_I32, ("n",)), (_U32, (2,)))),
 }
 
 
@@ -378,7 +381,7 @@ def kat_marshal(hook, arrays, call, n=None):
     """The marshalling of a known-answer hook (KAT_HOOKS[hook]): converts `arrays` to the inputs' dtypes, takes n from the first one, raises
     ValueError unless every input is [n] + its tail (leading dimension n, n * prod(tail) elements), allocates the outputs zeroed and calls
     call(n, input pointers, output arrays), which makes the library call and raises on its status.  Returns the outputs as a tuple.  A hook
-    that has its own rule for the count (kat_rng, kat_tile_feedback) passes n: the inputs are then only converted, and the outputs hold
+    that has its own rule for the count (kat_rng, kat_tile_feedback, kat_order_split) passes n: the inputs are then only converted, and the outputs hold
     max(n, 0) items.  Everything before `call` touches no library."""
     ins_spec, outs_spec = KAT_HOOKS[hook]
     assert len(arrays) == len(ins_spec)
@@ -1376,6 +1379,24 @@ class Context:
         def call(n, ins, out):
             _check(lib().dr_kat_tile_feedback(self._h, n, int(regions), int(heavy_factor), int(split_steps), int(split_limit), *ins, *[_p(a) for a in out]))
         return kat_marshal("tile_feedback", (pixel_cost,), call, n)
+
+    def kat_order_split(self, kind, regions, order, region_start, key):
+        """The kernel that splits a launch's tile order, on caller arrays (dr_kat_order_split): order int32[ntiles] or None (the identity),
+        region_start int32[regions + 1 or more], key one entry per tile -- kind 0 the tiles' uint32 words, kind 1 byte flags -> (launch_order
+        int32[ntiles], launch_region_start int32[17], dropped_list int32[ntiles], counts uint32[2] = dropped, kept); entries the kernel did not
+        write are -1 (kind 1: all of dropped_list and counts)."""
+        n = int(np.size(key))
+        if order is not None and np.size(order) != n:
+            raise ValueError("kat_order_split: order must be [n]")
+        if np.size(region_start) < int(regions) + 1:
+            raise ValueError("kat_order_split: region_start must hold regions + 1 entries")
+        flags = np.ascontiguousarray(key, dtype=np.uint8) if int(kind) == 1 else None      # (the table states the words' type; flags are bytes)
+
+        def call(n, ins, out):
+            _check(lib().dr_kat_order_split(self._h, int(kind), n, int(regions), ins[0] if order is not None else None, ins[1],
+                                            ins[2] if flags is None else _p(flags), *[_p(a) for a in out]))
+        return kat_marshal("order_split", (np.zeros(0, np.int32) if order is None else order, region_start, np.zeros(0, np.uint32) if flags is not None else key),
+                           call, n)
 
 
 class Group:

@@ -172,21 +172,44 @@ struct CameraWords {
   int grow_mask(int tiles, int n_levels, hipStream_t stream) { state.valid = false; return mask.grow(cert_mask_words(tiles, n_levels), stream); }
 };
 
+// A launch's own order / region_start pair: what launch_order_split (kernels.hpp) writes and the persistent kernel's queues then hold instead of TileOrder's
+struct LaunchPair {
+  DevMem<int> order, region_start;
+  bool room(int tiles) const { return order.n >= (size_t)tiles && region_start.p; }
+  int grow(int tiles, hipStream_t stream) { DR_TRY(order.grow((size_t)tiles, stream)); return region_start.grow(2 * MAX_REGIONS + 1, stream); }
+};
+
+// The frame buffers of a launch of several frames: cap_frames buffers of elems_each int32, one after the other
+struct FrameBuffers {
+  DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;
+  operator int32_t*() const { return frames.p; }
+  // room for `need` buffers of `elems` int32: made anew (*regrown), `cap` >= need of them, when a buffer's size changes or they are too few; stream: DevMem::grow's
+  int fit(size_t elems, int need, int cap, hipStream_t stream, bool* regrown = nullptr) {
+    const bool stale = elems_each != elems || cap_frames < need || !frames;
+    if (regrown) *regrown = stale;
+    if (!stale) return DR_OK;
+    cap_frames = 0;
+    DR_TRY(frames.grow(elems * (size_t)cap, stream));
+    elems_each = elems; cap_frames = cap;
+    return DR_OK;
+  }
+};
+
 // Sky tiles: a lean launch with an entry table hands the tiles of code ENTRY_NONE to sky_tiles_kernel, or to its own retiring waves,
 // and the rest of its order to the persistent kernel's queues (context_render.cpp sky_split).  The split is made on the launch's stream and kept while
-// the words and the order it was made from are the same (sky_split_kernel takes 0.53 % of a 32-frame launch of the bench view,
-// profiles/sky_tiles_ab.txt); TileOrder's order and region_start stay whole
+// the words and the order it was made from are the same (the split's kernel takes 0.53 % of a 32-frame launch of the bench view,
+// profiles/sky_tiles_ab.txt)
 struct SkySplit {
-  DevMem<int> launch_order, launch_region_start, list;
+  LaunchPair pair;
+  DevMem<int> list;
   DevMem<unsigned> counts;                 // [0] sky tiles, [1] geometry tiles of the last split
   SkySplitState state;
   void invalidate() { state.valid = false; }
-  bool room(int tiles) const { return launch_order.n >= (size_t)tiles && list.n >= (size_t)tiles && launch_region_start.p && counts.p; }
+  bool room(int tiles) const { return pair.room(tiles) && list.n >= (size_t)tiles && counts.p; }
   int grow(int tiles, hipStream_t stream) {
     state.valid = false;
-    DR_TRY(launch_order.grow((size_t)tiles, stream)); DR_TRY(list.grow((size_t)tiles, stream));
-    DR_TRY(launch_region_start.grow(2 * MAX_REGIONS + 1, stream)); DR_TRY(counts.grow(2, stream));
-    return DR_OK;
+    DR_TRY(pair.grow(tiles, stream)); DR_TRY(list.grow((size_t)tiles, stream));
+    return counts.grow(2, stream);
   }
 };
 
@@ -197,20 +220,15 @@ struct SkySplit {
 struct TileSubset {
   DevMem<uint8_t> flags;
   DevMem<unsigned> counts;                 // [AD_ACTIVE] active tiles, [AD_ASKING] asking pixels of the last selection
-  DevMem<int> launch_order, launch_region_start;
-  DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;      // cap_frames buffers of elems_each int32, one after the other
+  LaunchPair pair;
+  FrameBuffers frames;
   int tiles = 0;                           // tiles of the last pass's selection (0: none to read back)
   void invalidate() { tiles = 0; }
   int grow(int ntiles, size_t elems, int nframes, hipStream_t stream) {
     tiles = 0;
     DR_TRY(flags.grow((size_t)ntiles, stream)); DR_TRY(counts.grow(AD_WORDS, stream));
-    DR_TRY(launch_order.grow((size_t)ntiles, stream)); DR_TRY(launch_region_start.grow(2 * MAX_REGIONS + 1, stream));
-    if (elems_each != elems || cap_frames < nframes || !frames) {
-      cap_frames = 0;
-      DR_TRY(frames.grow(elems * (size_t)nframes, stream));
-      elems_each = elems; cap_frames = (int)(frames.n / elems);
-    }
-    return DR_OK;
+    DR_TRY(pair.grow(ntiles, stream));
+    return frames.fit(elems, nframes, nframes, stream);
   }
 };
 
@@ -224,7 +242,7 @@ struct FramePipeline {
   typedef DevMem<uint8_t, true> Image;             // a frame's present, pinned
   hipStream_t stream[PIPE_STREAMS] = {nullptr, nullptr, nullptr, nullptr}, acc_stream = nullptr;      // stream[0] is the context's own (not owned)
   struct Slot {
-    DevMem<int32_t> frames; size_t elems_each = 0; int cap_frames = 0;         // cap_frames buffers of elems_each int32, one after the other
+    FrameBuffers frames;
     int rect[6] = {-1, 0, 0, 0, 0, 0};             // W, H, gx, gy, stripe mod, stripe rem the buffers were last rendered with (their margins are 0)
     hipEvent_t rendered = nullptr;                 // end of the group's launch
     hipEvent_t added[PIPE_GROUP_MAX] = {nullptr};  // frame f of the group has been added (and presented)

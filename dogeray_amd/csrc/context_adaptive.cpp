@@ -65,7 +65,7 @@ int dr_render_adaptive(dr_context* c, const float settings13[13], int W, int H, 
     DR_TRY(enqueue_frame(c, site, P));
     HIP_TRY(hipGetLastError());
     L.nframes = n;
-    launch_adaptive_add(c->stream, L, sub.launch_order, sub.launch_region_start, P.regions);
+    launch_adaptive_add(c->stream, L, sub.pair.order, sub.pair.region_start, P.regions);
     HIP_TRY(hipGetLastError());
     launches++;
   }

@@ -92,18 +92,14 @@ int pipeline_flush_some(dr_context* c, int n) {
   if (plan.stream_wait_slot) HIP_TRY(hipStreamWaitEvent(rs, sl.added[plan.slot_last], 0));
   p.book.group_take_slot(g, sl.rgb_host);
   // the buffers
-  if (sl.elems_each != elems || sl.cap_frames < n || !sl.frames) {
-    const int cap = n > c->pipe_group ? n : c->pipe_group;      // (ODDITY: room for the option's group, whatever this one holds)
-    sl.cap_frames = 0;
-    DR_TRY(sl.frames.grow((size_t)cap * elems, p.acc_stream));
-    sl.elems_each = elems; sl.cap_frames = cap;
-    sl.rect[0] = -1;
-  }
+  bool regrown;
+  DR_TRY(sl.frames.fit(elems, n, n > c->pipe_group ? n : c->pipe_group, p.acc_stream, &regrown));      // (ODDITY: room for the option's group, whatever this one holds)
+  if (regrown) sl.rect[0] = -1;
   // pixels outside the rendered block grid are 0 (K:2633-2636): the buffers are cleared when that grid changes, every frame of a grid
   // overwrites the same pixels (ODDITY: keyed by the rectangle alone, all cap_frames buffers at once)
   const int rect[6] = {W, H, P.gx, P.gy, P.stripe_mod, P.stripe_rem};
   if (memcmp(rect, sl.rect, sizeof(rect)) != 0) {
-    HIP_TRY(hipMemsetAsync(sl.frames, 0, (size_t)sl.cap_frames * elems * sizeof(int32_t), rs));
+    HIP_TRY(hipMemsetAsync(sl.frames, 0, (size_t)sl.frames.cap_frames * elems * sizeof(int32_t), rs));
     memcpy(sl.rect, rect, sizeof(rect));
   }
   P.out = sl.frames;

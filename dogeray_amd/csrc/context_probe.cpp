@@ -450,4 +450,33 @@ int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_facto
                   k.out(region_start, (size_t)(2 * MAX_REGIONS + 1), 0xff), ntiles, regions, heavy_factor, split_steps, split_limit);
 }
 
+int dr_kat_order_split(dr_context* c, int kind, int ntiles, int regions, const int* order_or_null, const int* region_start, const void* key, int* launch_order,
+                       int* launch_region_start, int* dropped_list, unsigned* counts) {
+  // the kernel trusts its inputs (it places by them): everything it relies on is judged here
+  if (kind != SPLIT_BY_WORD && kind != SPLIT_BY_FLAG) { set_error("order split: kind must be 0 (tile words) or 1 (byte flags)"); return DR_ERR_INVALID; }
+  if (ntiles < 1) { set_error("order split: ntiles must be at least 1"); return DR_ERR_INVALID; }
+  if (regions < 1 || regions > MAX_REGIONS) { set_error("order split: regions must be 1 .. 8"); return DR_ERR_INVALID; }
+  KAT_BEGIN(k, c, ntiles, false, region_start, key, launch_order, launch_region_start, dropped_list, counts);
+  bool monotone = region_start[0] == 0 && region_start[regions] == ntiles;
+  for (int r = 0; r < regions && monotone; r++) monotone = region_start[r] <= region_start[r + 1];
+  if (!monotone) { set_error("order split: region_start must be non-decreasing from 0 to ntiles"); return DR_ERR_INVALID; }
+  const size_t n = (size_t)ntiles;
+  if (order_or_null) {
+    std::vector<bool> seen(n, false);
+    for (size_t i = 0; i < n; i++) {
+      const int t = order_or_null[i];
+      if (t < 0 || t >= ntiles || seen[(size_t)t]) { set_error("order split: order must be a permutation of 0 .. ntiles - 1"); return DR_ERR_INVALID; }
+      seen[(size_t)t] = true;
+    }
+  }
+  DR_TRY(join_pipeline(c));
+  int own[MAX_REGIONS + 1];      // the identity order's regions travel by value; behind [regions]: ntiles, as make_params leaves them
+  for (int r = 0; r <= MAX_REGIONS; r++) own[r] = region_start[r < regions ? r : regions];
+  const void* key_dev = kind == SPLIT_BY_WORD ? (const void*)k.in(static_cast<const uint32_t*>(key), n) : (const void*)k.in(static_cast<const uint8_t*>(key), n);
+  // every output preset: an entry the kernel does not write reads as -1
+  return k.finish(launch_order_split, c->stream, kind, order_or_null ? k.in(order_or_null, n) : nullptr, k.in(region_start, (size_t)(regions + 1)), own, key_dev,
+                  ntiles, regions, k.out(launch_order, n, 0xff), k.out(launch_region_start, (size_t)(2 * MAX_REGIONS + 1), 0xff), k.out(dropped_list, n, 0xff),
+                  k.out(counts, (size_t)2, 0xff));
+}
+
 }  // extern "C"

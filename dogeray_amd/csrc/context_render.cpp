@@ -118,14 +118,15 @@ bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles
   const SkyKey key = sky_key(c->words.state, c->order.state, order != nullptr, tiles, P.regions);
   if (!sky_split_reusable(sky.state, key, sky.room(tiles))) {
     if (sky.grow(tiles, site.stream) != DR_OK) return false;
-    launch_sky_split(site.stream, order, region_start, P.region_start, P.cert_level, tiles, P.regions, sky.launch_order, sky.launch_region_start, sky.list, sky.counts);
+    launch_order_split(site.stream, SPLIT_BY_WORD, order, region_start, P.region_start, P.cert_level, tiles, P.regions, sky.pair.order, sky.pair.region_start, sky.list,
+                       sky.counts);
     sky_split_commit(sky.state, key);
   }
   if (c->sky_tiles == 2) {
     P.sky_list = sky.list; P.sky_counts = sky.counts; P.sky_cursor = cursor;
     P.sky_chunk = sky_chunk_frames(P.batch, P.accumulate == 2 ? SKY_CHUNK : 0);
   } else launch_sky_tiles(site.stream, P, sky.list, sky.counts, pcost);
-  order = sky.launch_order; region_start = sky.launch_region_start;
+  order = sky.pair.order; region_start = sky.pair.region_start;
   return true;
 }
 
@@ -134,8 +135,8 @@ bool sky_split(dr_context* c, const LaunchSite& site, RenderParams& P, int tiles
 // behind it by the fold (launch_adaptive_add), on the same stream.
 void subset_split(const LaunchSite& site, const RenderParams& P, int tiles, const int*& order, const int*& region_start) {
   TileSubset& sub = *site.subset;
-  launch_subset_split(site.stream, order, region_start, P.region_start, sub.flags, tiles, P.regions, sub.launch_order, sub.launch_region_start);
-  order = sub.launch_order; region_start = sub.launch_region_start;
+  launch_order_split(site.stream, SPLIT_BY_FLAG, order, region_start, P.region_start, sub.flags, tiles, P.regions, sub.pair.order, sub.pair.region_start, nullptr, nullptr);
+  order = sub.pair.order; region_start = sub.pair.region_start;
 }
 
 }  // namespace

@@ -1,9 +1,10 @@
 // Device functions of adaptive sampling (dr_render_adaptive): which pixels of the accumulator still ask for samples, which 8x8 tiles
 // are therefore rendered, the launch's tile order without the others, and the fold of the new frames into the planes of the rendered tiles only.
 // Everything a pixel or a tile does is written once, here, over the launch struct AdLaunch (device_launch.h): ad_asks is one pixel of the selection,
-// ad_tile_active a tile's verdict, ad_fold_pixel one pixel of the fold, subset_split_plain the split as plain C++.  The gfx950 kernels
-// (kernels_adaptive.hip) map a wave to a tile and its lanes to the pixels, ballot and count; the host build (tools/host_kernel/hk_accum.hpp
-// hk_adaptive_select / hk_subset_split / hk_adaptive_add) loops and counts; tests/adaptive_checks.py restates it in numpy, independently.  The noise
+// ad_tile_active a tile's verdict, ad_fold_pixel one pixel of the fold, FlagKeep the predicate of the split (device_split.hpp order_split_plain is
+// the split as plain C++, kernels_aux.hip order_split_kernel the one workgroup that computes it).  The gfx950 kernels (kernels_adaptive.hip) map a
+// wave to a tile and its lanes to the pixels, ballot and count; the host build (tools/host_kernel/hk_accum.hpp hk_adaptive_select /
+// hk_subset_split / hk_adaptive_add) loops and counts; tests/adaptive_checks.py and tests/split_cases.py restate it in numpy, independently.  The noise
 // estimate is device_moments.hpp's, the comparison dr_error_result.above's: include/dogeray_amd.h has the definition, operation by operation.
 #pragma once
 #include "device_moments.hpp"
@@ -51,24 +52,13 @@ __device__ __forceinline__ void ad_fold_pixel(const AdLaunch& L, int tile, int l
   L.hist[p] = (int32_t)((uint32_t)L.hist[p] + (uint32_t)L.nframes);
 }
 
-// The split of a launch's order by a flag per tile: device_sky.hpp sky_split_plain with "flag set" for "not a sky tile" and no second list.  order
-// (null: the identity) and region_start in the persistent kernel's format (region r owns positions [region_start[r], region_start[r + 1]) of the
-// order, region_start[regions] = tiles).
-//   launch_order          the flagged tiles, in the order they had (a stable partition)
-//   launch_region_start   2 * MAX_REGIONS + 1 ints: the starts of the compacted regions, [regions] = the flagged tiles; the split counts
-//                         [MAX_REGIONS + 1 + r] = 0
-// Returns the number of flagged tiles.
-inline int subset_split_plain(const int* order, const int* region_start, const uint8_t* flag, int tiles, int regions, int* launch_order,
-                              int* launch_region_start) {
-  int n = 0, r = 0;
-  for (int k = 0; k < 2 * MAX_REGIONS + 1; k++) launch_region_start[k] = 0;
-  for (int i = 0; i < tiles; i++) {
-    while (r <= regions && region_start[r] <= i) launch_region_start[r++] = n;
-    const int t = order ? order[i] : i;
-    if (flag[t]) launch_order[n++] = t;
-  }
-  while (r <= regions) launch_region_start[r++] = n;
-  return n;
-}
+// The split's predicate over the selection's flags: a tile is kept when its flag is set (load and test apart, as device_sky.hpp SkyKeep)
+struct FlagKeep {
+  typedef uint8_t Value;
+  const uint8_t* flag;
+  __host__ __device__ __forceinline__ Value load(int t) const { return flag[t]; }
+  __host__ __device__ __forceinline__ static bool keep(Value v) { return v != 0; }
+  __host__ __device__ __forceinline__ bool operator()(int t) const { return keep(load(t)); }
+};
 
 }  // namespace dr

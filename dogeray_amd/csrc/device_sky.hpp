@@ -1,8 +1,8 @@
 // Tiles that see nothing of the scene (entry code ENTRY_NONE in the view's entry table): every path of their pixels misses, so a frame
 // of such a pixel is spp camera rays and spp backgrounds -- no walk, no path pool.  sky_pixel is that frame, written with the functions the render
-// kernels run (render_pixel with a `closest` that always misses); sky_split_plain is the partition of a launch's tile order into the geometry tiles
-// the persistent kernel keeps and the sky tiles, as plain C++ (kernels_aux.hip sky_split_kernel computes the same arrays with one workgroup; the
-// host build exports this one, tests/test_sky_tiles_host.py).
+// kernels run (render_pixel with a `closest` that always misses); SkyKeep is the predicate by which a launch's tile order is split into the geometry
+// tiles the persistent kernel keeps and the sky tiles (device_split.hpp order_split_plain says what the split writes; kernels_aux.hip
+// order_split_kernel computes it with one workgroup; the host build exports the plain one, tests/test_sky_tiles_host.py).
 #pragma once
 #include "device_shade.hpp"
 #include "launch_plan.hpp"
@@ -11,6 +11,15 @@ namespace dr {
 
 // a tile's word (entry code << ENTRY_SHIFT | grade, RenderParams cert_level) says that no leaf can be seen from the tile
 __host__ __device__ __forceinline__ bool sky_word(uint32_t word) { return ((int)word >> ENTRY_SHIFT) == ENTRY_NONE; }
+// the split's predicate over the tiles' words: a tile is kept unless it is a sky tile (load and test apart: the kernel issues a round trip's loads
+// before it uses any of them)
+struct SkyKeep {
+  typedef uint32_t Value;
+  const uint32_t* word;
+  __host__ __device__ __forceinline__ Value load(int t) const { return word[t]; }
+  __host__ __device__ __forceinline__ static bool keep(Value v) { return !sky_word(v); }
+  __host__ __device__ __forceinline__ bool operator()(int t) const { return keep(load(t)); }
+};
 
 // What store_pixel adds for pixel (x, y) and frame `frame` of the launch when every sample's path misses (max_depth > 0: the first ray of a path
 // is always shaded)
@@ -45,27 +54,6 @@ __device__ __forceinline__ void sky_tile_frames(const RenderParams& P, int tile,
   else if (P.accumulate) { px[0] += r; px[1] += g; px[2] += b; }
   else { px[0] = r; px[1] = g; px[2] = b; }
   if (pixel_cost && first == 0) pixel_cost[(size_t)tile * 64 + lane] = 0u;
-}
-
-// The split of a launch's order: order (null: the identity) and region_start in the persistent kernel's format (region r owns positions
-// [region_start[r], region_start[r + 1]) of the order, region_start[regions] = tiles); word = a word per tile.
-//   launch_order          the tiles that are not sky, in the order they had (a stable partition: every region keeps its heavy-first, then natural order)
-//   launch_region_start   2 * MAX_REGIONS + 1 ints: the starts of the compacted regions, [regions] = the geometry tiles; the split counts
-//                         [MAX_REGIONS + 1 + r] = 0
-//   sky_list              the sky tiles, ascending
-// Returns the number of sky tiles.
-inline int sky_split_plain(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order,
-                           int* launch_region_start, int* sky_list) {
-  int n_geometry = 0, n_sky = 0, r = 0;
-  for (int k = 0; k < 2 * MAX_REGIONS + 1; k++) launch_region_start[k] = 0;
-  for (int i = 0; i < tiles; i++) {
-    while (r <= regions && region_start[r] <= i) launch_region_start[r++] = n_geometry;
-    const int t = order ? order[i] : i;
-    if (!sky_word(word[t])) launch_order[n_geometry++] = t;
-    if (sky_word(word[i])) sky_list[n_sky++] = i;
-  }
-  while (r <= regions) launch_region_start[r++] = n_geometry;
-  return n_sky;
 }
 
 }  // namespace dr

@@ -1,6 +1,6 @@
 // Launchers of the device code, one translation unit per family of kernels:
 //   kernels_render.hip        the per-tile kernel (reference launch shape) and the persistent kernel (waves as pools of 64 path slots)
-//   kernels_aux.hip           tile-order feedback, the sky tiles' split and kernel, present divide, stripe copies of the multi-GPU gather, gather probe, trace-only probe
+//   kernels_aux.hip           tile-order feedback, the split of a launch's order, the sky tiles' kernel, present divide, stripe copies of the multi-GPU gather, gather probe, trace-only probe
 //   kernels_kat.hip           known-answer kernels behind dr_kat_*: generator, intersections, optics, normal, closest hit; the shading step
 //   kernels_aov.hip           first-hit AOV buffers of a window of pinhole camera rays (dr_render_aov)
 //   kernels_trace.hip         closest hit and occlusion of caller rays (dr_trace_rays)
@@ -11,7 +11,7 @@
 //   kernels_reproject.hip     temporal reprojection of the accumulator and its history plane into another view (dr_accum_reproject)
 //   kernels_upscale.hip       the AOV-guided upsampler of a low-resolution accumulator (dr_accum_upscale)
 //   kernels_moments.hip       the second-moment plane: the fused frame add and the per-pixel noise estimate (option "moments", dr_accum_error)
-//   kernels_adaptive.hip      adaptive sampling: the tiles that ask for samples, the launch's order without the others, the masked fold (dr_render_adaptive)
+//   kernels_adaptive.hip      adaptive sampling: the tiles that ask for samples, the masked fold (dr_render_adaptive)
 // (the measured-slower kernels of rounds 2 and 3 -- two paths per lane, waves with roles, the pool kernel -- are archived under tools/experiments/)
 // context.cpp and the context_*.cpp files (host only: resident scene, options, the C ABI) call these and never see a kernel.
 #pragma once
@@ -62,12 +62,15 @@ void launch_cert_mask(hipStream_t stream, const DevPrim* prims, int n, const Cer
 inline size_t entry_mm_words(int ntiles) { return 2 * (size_t)ntiles + 1; }
 void launch_camera_entry(hipStream_t stream, const DevUnit* wide, const uint32_t* leaf_rec, const uint32_t* range, int n_leaves, const CertView& cv,
                          uint32_t* mm, const uint32_t* level, uint32_t* word, int ntiles);
-// sky tiles (option sky_tiles; device_sky.hpp sky_split_plain describes the arrays): the split of a launch's order -- order / region_start as the
-// persistent kernel would take them (order null: the identity, regions from own_region_start, MAX_REGIONS + 1 ints on the host), word = the tiles' words --
-// into launch_order / launch_region_start for the persistent kernel and sky_list with counts ([0] sky tiles, [1] geometry tiles) for launch_sky_tiles,
-// which renders P.batch frames of the listed tiles (one wave per tile; pixel_cost non-null: their costs, 0)
-void launch_sky_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint32_t* word, int tiles, int regions,
-                      int* launch_order, int* launch_region_start, int* sky_list, unsigned* counts);
+// The split of a launch's order (device_split.hpp order_split_plain describes the arrays) -- order / region_start as the persistent kernel would take
+// them (order null: the identity, regions from own_region_start, MAX_REGIONS + 1 ints on the host) -- into launch_order / launch_region_start for the
+// persistent kernel.  kind SPLIT_BY_WORD (option sky_tiles): key = the tiles' words (uint32_t), a sky tile is dropped; dropped_list with counts ([0] sky
+// tiles, [1] geometry tiles) are written for launch_sky_tiles.  kind SPLIT_BY_FLAG (dr_render_adaptive): key = a flag per tile (uint8_t), a tile without
+// one is dropped; no list, no counts (both may be null), launch_adaptive_add reads the pair behind the launch.  One 1 024-thread workgroup
+enum SplitKind { SPLIT_BY_WORD = 0, SPLIT_BY_FLAG = 1 };
+void launch_order_split(hipStream_t stream, int kind, const int* order, const int* region_start, const int* own_region_start, const void* key, int tiles,
+                        int regions, int* launch_order, int* launch_region_start, int* dropped_list, unsigned* counts);
+// renders P.batch frames of the listed sky tiles (one wave per tile; pixel_cost non-null: their costs, 0)
 void launch_sky_tiles(hipStream_t stream, const RenderParams& P, const int* sky_list, const unsigned* counts, unsigned* pixel_cost);
 // hist: the history plane (int32 per pixel at x * H + y; the divisor of pixel p is hist[p] + div, a divisor of 0 gives 0), or null: acc / div
 void launch_present(hipStream_t stream, const int32_t* acc, const int32_t* hist, uint8_t* rgb, int W, int H, int div);
@@ -181,10 +184,6 @@ void launch_moments_error(hipStream_t stream, const MoLaunch& L);
 
 // kernels_adaptive.hip (dr_render_adaptive; device_adaptive.hpp describes the arrays)
 void launch_adaptive_select(hipStream_t stream, const AdLaunch& L);      // the planes -> L.flags, L.counts
-// the split of a launch's order by a flag per tile -- order / region_start as the persistent kernel would take them (order null: the identity, regions
-// from own_region_start, MAX_REGIONS + 1 ints on the host) -- into launch_order / launch_region_start for the persistent kernel and launch_adaptive_add
-void launch_subset_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint8_t* flag, int tiles, int regions,
-                         int* launch_order, int* launch_region_start);
 // L.nframes frame buffers into the planes of the launch_region_start[regions] tiles at the head of launch_order
 void launch_adaptive_add(hipStream_t stream, const AdLaunch& L, const int* launch_order, const int* launch_region_start, int regions);
 

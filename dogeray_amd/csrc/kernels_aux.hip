@@ -1,4 +1,4 @@
-// Everything on the device that is not a render kernel: tile-order feedback of the persistent kernels, the display divide,
+// Everything on the device that is not a render kernel: tile-order feedback of the persistent kernels, the split of a launch's order, the display divide,
 // the stripe copies of the multi-GPU gather, the gather-ceiling probe and the trace-only probe.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,8 @@
 #include "device_cert.hpp"
 #include "device_surface.hpp"
 #include "device_sky.hpp"
+#include "device_adaptive.hpp"
+#include "device_block.hpp"
 #include "kernels.hpp"
 #include "../../include/dogeray_amd.h"
 
@@ -66,9 +68,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const unsigned* __rest
   // Wave w owns the contiguous range [w0, w1) of the tile numbering and walks it 64 tiles at a time, lane l on tile g + l: the light
   // tiles keep their natural order through ballots and prefix counts (a range at a time, a region at a time), the expensive ones are
   // binned by cost class.  (One thread per 32-tile chunk with everything per tile took 70-100 us on the one CU this block has.)
-  const int per = ((ntiles + WAVES - 1) / WAVES + 63) & ~63;
-  const int w0 = w * per < ntiles ? w * per : ntiles, w1 = w0 + per < ntiles ? w0 + per : ntiles;
-  auto mbcnt = [](unsigned long long m) { return (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
+  const int w0 = wave_range(ntiles, WAVES, w).w0, w1 = wave_range(ntiles, WAVES, w).w1;
   // body(t, cost, valid, rcur): rcur = region of the 64-tile group's first tile (wave-uniform); a lane's own region is rcur or rcur + 1
   auto for_range = [&](auto&& body) {
     int rcur = 0;
@@ -152,24 +152,26 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const unsigned* __rest
     const bool light = valid && !heavy;
     const unsigned long long b0 = __ballot(light && r == rcur), b1 = __ballot(light && r != rcur);
     if (light) {
-      if (r == rcur) order[light_start[r] + light_cnt[w][r] + placed0 + mbcnt(b0)] = t;
-      else order[light_start[r] + light_cnt[w][r] + placed1 + mbcnt(b1)] = t;
+      if (r == rcur) order[light_start[r] + light_cnt[w][r] + placed0 + lanes_before(b0)] = t;
+      else order[light_start[r] + light_cnt[w][r] + placed1 + lanes_before(b1)] = t;
     }
     placed0 += (unsigned)__popcll(b0); placed1 += (unsigned)__popcll(b1);
   });
 }
 
-// ---- sky tiles (option sky_tiles): the tiles of a lean launch whose entry code is ENTRY_NONE leave the persistent kernel's queue
-// One workgroup splits the launch's order (device_sky.hpp sky_split_plain says what comes out): wave w owns a contiguous range of the order's positions
-// -- and, for the sky list, of the tile numbering -- and walks it 64 at a time, twice: counting, then placing through ballots and prefix counts, as
-// tile_order_kernel places its light tiles.  own: the region starts of the identity order (order null).  counts: [0] sky tiles, [1] geometry tiles.
-struct SkyRegions { int start[MAX_REGIONS + 1]; };
-__global__ __launch_bounds__(1024) void sky_split_kernel(const int* __restrict__ order, const int* __restrict__ region_start, SkyRegions own,
-                                                          const uint32_t* __restrict__ word, int ntiles, int regions, int* __restrict__ launch_order,
-                                                          int* __restrict__ launch_region_start, int* __restrict__ sky_list, unsigned* __restrict__ counts) {
-  constexpr int WAVES = 16, GROUPS = 8;
+// ---- the split of a launch's order (device_split.hpp order_split_plain says what comes out): the tiles a predicate keeps stay in the
+// persistent kernel's queues.  One workgroup: wave w owns a contiguous range of the order's positions -- and, for the list of the dropped tiles, of the tile
+// numbering -- and walks it GROUPS x 64 at a time, twice: counting, then placing through ballots and prefix counts, as tile_order_kernel places its light
+// tiles; a round trip's loads are all issued before any is used.  Two instances: SkyKeep over the tiles' words (option sky_tiles: with the list, counts [0]
+// dropped = sky tiles, [1] kept = geometry tiles) and FlagKeep over an adaptive pass's flags (no list, no counts).  own: the identity order's region starts.
+struct OrderRegions { int start[MAX_REGIONS + 1]; };
+template <class Keep, bool LIST, int GROUPS>
+__global__ __launch_bounds__(1024) void order_split_kernel(const int* __restrict__ order, const int* __restrict__ region_start, OrderRegions own, Keep keep,
+                                                            int ntiles, int regions, int* __restrict__ launch_order, int* __restrict__ launch_region_start,
+                                                            int* __restrict__ dropped_list, unsigned* __restrict__ counts) {
+  constexpr int WAVES = 16; typedef typename Keep::Value Value;
   __shared__ int rs[MAX_REGIONS + 1];
-  __shared__ unsigned geo_cnt[WAVES], sky_cnt[WAVES];
+  __shared__ unsigned cnt[LIST ? 2 : 1][WAVES];            // per wave: [0] kept tiles of its positions, [1] dropped tiles of its tile numbers
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid <= MAX_REGIONS) {
     int v = ntiles;
@@ -182,52 +184,53 @@ __global__ __launch_bounds__(1024) void sky_split_kernel(const int* __restrict__
     }
     rs[tid] = v;
   }
-  if (tid > regions && tid < 2 * MAX_REGIONS + 1) launch_region_start[tid] = 0;      // (the split counts among them: a lean launch hands out no tile in parts)
+  if (tid > regions && tid < 2 * MAX_REGIONS + 1) launch_region_start[tid] = 0;      // (the split counts among them: such a launch hands out no tile in parts)
   __syncthreads();
-  const int per = ((ntiles + WAVES - 1) / WAVES + 63) & ~63;
-  const int w0 = w * per < ntiles ? w * per : ntiles, w1 = w0 + per < ntiles ? w0 + per : ntiles;
-  auto mbcnt = [](unsigned long long m) { return (unsigned)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)); };
-  // body(i, t, geometry, sky): position i of the order holds tile t, which is (not) kept; tile i is a sky tile
+  const int w0 = wave_range(ntiles, WAVES, w).w0, w1 = wave_range(ntiles, WAVES, w).w1;
+  // body(i, t, kept, dropped): position i of the order holds tile t, which is (not) kept; tile i is dropped (never, without a list).  Whole waves come
+  // here, i >= w1 in the lanes past the range
   auto for_range = [&](auto&& body) {
     for (int g0 = w0; g0 < w1; g0 += 64 * GROUPS) {
-      int t[GROUPS]; uint32_t wt[GROUPS], wi[GROUPS];
+      int t[GROUPS]; Value vt[GROUPS], vi[GROUPS] = {};
 #pragma unroll
       for (int k = 0; k < GROUPS; k++) { const int i = g0 + 64 * k + lane; t[k] = i < w1 ? (order ? order[i] : i) : -1; }
 #pragma unroll
       for (int k = 0; k < GROUPS; k++) {
         const int i = g0 + 64 * k + lane;
-        wi[k] = i < w1 ? word[i] : 0u;
-        wt[k] = (unsigned)t[k] < (unsigned)ntiles ? word[t[k]] : 0u;
+        if constexpr (LIST) vi[k] = i < w1 ? keep.load(i) : Value(0);
+        vt[k] = (unsigned)t[k] < (unsigned)ntiles ? keep.load(t[k]) : Value(0);
       }
 #pragma unroll
       for (int k = 0; k < GROUPS; k++) {
         const int i = g0 + 64 * k + lane;
-        if (g0 + 64 * k < w1) body(i, t[k], i < w1 && !sky_word(wt[k]), i < w1 && sky_word(wi[k]));
+        if (g0 + 64 * k < w1) body(i, t[k], (unsigned)t[k] < (unsigned)ntiles && Keep::keep(vt[k]), LIST && i < w1 && !Keep::keep(vi[k]));
       }
     }
   };
-  {
-    unsigned ng = 0, ns = 0;
-    for_range([&](int, int, bool geometry, bool sky) { ng += (unsigned)__popcll(__ballot(geometry)); ns += (unsigned)__popcll(__ballot(sky)); });
-    if (lane == 0) { geo_cnt[w] = ng; sky_cnt[w] = ns; }
-  }
+  unsigned nk = 0, nd = 0;
+  for_range([&](int, int, bool kept, bool dropped) { nk += (unsigned)__popcll(__ballot(kept)); if constexpr (LIST) nd += (unsigned)__popcll(__ballot(dropped)); });
+  if (lane == 0) { cnt[0][w] = nk; if constexpr (LIST) cnt[1][w] = nd; }
   __syncthreads();
-  unsigned gbase = 0, sbase = 0, gtotal = 0, stotal = 0;
+  unsigned kbase = 0, dbase = 0, ktotal = 0, dtotal = 0;
   for (int k = 0; k < WAVES; k++) {
-    if (k < w) { gbase += geo_cnt[k]; sbase += sky_cnt[k]; }
-    gtotal += geo_cnt[k]; stotal += sky_cnt[k];
+    if (k < w) { kbase += cnt[0][k]; if constexpr (LIST) dbase += cnt[1][k]; }
+    ktotal += cnt[0][k]; if constexpr (LIST) dtotal += cnt[1][k];
   }
-  for_range([&](int i, int t, bool geometry, bool sky) {
-    const unsigned long long bg = __ballot(geometry), bs = __ballot(sky);
-    const unsigned p = gbase + mbcnt(bg);                    // geometry tiles in front of position i
+  for_range([&](int i, int t, bool kept, bool dropped) {
+    const unsigned long long bk = __ballot(kept);
+    const unsigned p = kbase + lanes_before(bk);             // kept tiles in front of position i
     if (i < w1)
       for (int r = 0; r <= regions; r++) if (i == rs[r]) launch_region_start[r] = (int)p;
-    if (geometry) launch_order[p] = t;
-    if (sky) sky_list[sbase + mbcnt(bs)] = i;
-    gbase += (unsigned)__popcll(bg); sbase += (unsigned)__popcll(bs);
+    if (kept) launch_order[p] = t;
+    kbase += (unsigned)__popcll(bk);
+    if constexpr (LIST) {
+      const unsigned long long bd = __ballot(dropped);
+      if (dropped) dropped_list[dbase + lanes_before(bd)] = i;
+      dbase += (unsigned)__popcll(bd);
+    }
   });
-  if (tid <= regions && rs[tid] >= ntiles) launch_region_start[tid] = (int)gtotal;      // (the end, and regions that start there)
-  if (tid == 0) { counts[0] = stotal; counts[1] = gtotal; }
+  if (tid <= regions && rs[tid] >= ntiles) launch_region_start[tid] = (int)ktotal;      // (the end, and regions that start there)
+  if constexpr (LIST) if (tid == 0) { counts[0] = dtotal; counts[1] = ktotal; }
 }
 // One wave per sky tile and the launch's whole batch (device_sky.hpp sky_tile_frames: the body it shares with the lean build's retiring waves, option
 // sky_tiles = 2).
@@ -458,12 +461,18 @@ void launch_tile_feedback(hipStream_t stream, const unsigned* pixel_cost, unsign
   hipLaunchKernelGGL(tile_cost_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, pixel_cost, tile_cost, tiles);
   hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, tile_cost, tile_order, region_start, tiles, regions, heavy_factor, split_steps, split_limit);
 }
-void launch_sky_split(hipStream_t stream, const int* order, const int* region_start, const int* own_region_start, const uint32_t* word, int tiles, int regions,
-                      int* launch_order, int* launch_region_start, int* sky_list, unsigned* counts) {
-  SkyRegions own;
+void launch_order_split(hipStream_t stream, int kind, const int* order, const int* region_start, const int* own_region_start, const void* key, int tiles,
+                        int regions, int* launch_order, int* launch_region_start, int* dropped_list, unsigned* counts) {
+  if (tiles <= 0) return;
+  OrderRegions own;
   for (int r = 0; r <= MAX_REGIONS; r++) own.start[r] = own_region_start[r];
-  hipLaunchKernelGGL(sky_split_kernel, dim3(1), dim3(1024), 0, stream, order, order ? region_start : nullptr, own, word, tiles, regions, launch_order,
-                     launch_region_start, sky_list, counts);
+  if (!order) region_start = nullptr;
+  if (kind == SPLIT_BY_WORD)
+    hipLaunchKernelGGL((order_split_kernel<SkyKeep, true, 8>), dim3(1), dim3(1024), 0, stream, order, region_start, own, SkyKeep{static_cast<const uint32_t*>(key)},
+                       tiles, regions, launch_order, launch_region_start, dropped_list, counts);
+  else
+    hipLaunchKernelGGL((order_split_kernel<FlagKeep, false, 1>), dim3(1), dim3(1024), 0, stream, order, region_start, own, FlagKeep{static_cast<const uint8_t*>(key)},
+                       tiles, regions, launch_order, launch_region_start, nullptr, nullptr);
 }
 void launch_sky_tiles(hipStream_t stream, const RenderParams& P, const int* sky_list, const unsigned* counts, unsigned* pixel_cost) {
   const int tiles = P.ncols * P.gy;

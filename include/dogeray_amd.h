@@ -896,8 +896,8 @@ int dr_context_probe_rays(dr_context* c, const float settings13[13], int W, int 
  * pointer; otherwise a null pointer is DR_ERR_INVALID ("null argument") -- only dr_kat_hit's visits may be null -- and a hook that reads the resident
  * scene without one is DR_ERR_INVALID ("no scene uploaded").  Values are judged next (each hook says which), and nothing reaches the device before
  * every check has passed.  The call is ordered behind the frames submitted before it (dr_pipeline_submit), runs on the context's stream and returns
- * after the results are in the caller's arrays; a launch error is DR_ERR_DEVICE.  (dr_kat_tile_feedback counts tiles: its refusals come first, and
- * it has no empty call.) */
+ * after the results are in the caller's arrays; a launch error is DR_ERR_DEVICE.  (dr_kat_tile_feedback and dr_kat_order_split count tiles: their
+ * refusals of a count come first, and they have no empty call; dr_kat_order_split's order may be null.) */
 int dr_kat_rng(dr_context* c, uint64_t seed, int n, double* out);
 int dr_kat_aabb(dr_context* c, int n, const float* o, const float* d, const float* mn, const float* mx,
                 int32_t* hit, float* dist);
@@ -978,6 +978,18 @@ int dr_kat_trace(dr_context* c, int variant, int n, const float* o, const float*
  * ntiles < 1, regions other than 1 or 8, 8 regions of fewer than 512 tiles, split_limit < 0. */
 int dr_kat_tile_feedback(dr_context* c, int ntiles, int regions, int heavy_factor, int split_steps, int split_limit,
                          const unsigned* pixel_cost, unsigned* tile_cost, int* order, int* region_start);
+/* The one-workgroup kernel that splits a launch's tile order, on caller data and scratch buffers (no cache of the context is touched): the stable
+ * partition of order[ntiles] (NULL: the identity) with region_start[regions + 1] -- region r owns positions [region_start[r], region_start[r + 1]) --
+ * by a key per tile.  kind 0: key = uint32_t[ntiles], the tiles' words; a tile whose entry code is "sees no leaf" is dropped (the sky tiles of option
+ * sky_tiles), and the dropped tiles are listed.  kind 1: key = uint8_t[ntiles], a tile is kept when its byte is not 0 (dr_render_adaptive's flags);
+ * nothing is listed.  Out: launch_order[ntiles], the kept tiles in the order they had, in its first `kept` entries; launch_region_start[17], [r] the
+ * compacted start of region r, [regions] = kept, every later entry 0; kind 0 only: dropped_list[ntiles], the dropped tiles in ascending tile number
+ * in its first `dropped` entries, and counts[2] = {dropped, kept}.  All four outputs are filled with 0xff bytes before the launch: an entry the kernel
+ * did not write -- the tails of the two lists, and for kind 1 all of dropped_list and counts -- reads as -1.  The kernel trusts its inputs, so
+ * DR_ERR_INVALID, before anything is staged, for kind other than 0 or 1, ntiles < 1, regions outside 1 .. 8, a region_start that is not
+ * non-decreasing from 0 to ntiles over [0 .. regions], and an order that is not a permutation of 0 .. ntiles - 1. */
+int dr_kat_order_split(dr_context* c, int kind, int ntiles, int regions, const int* order_or_null, const int* region_start, const void* key,
+                       int* launch_order, int* launch_region_start, int* dropped_list, unsigned* counts);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """A numpy restatement of adaptive sampling (include/dogeray_amd.h "adaptive sampling", dogeray_amd/csrc/device_adaptive.hpp), independent of the
 source under test: the selection over whole planes at once (int64 / uint64 / float64, float32 for sigma and its comparison -- the arithmetic of
-tests/moments_checks.py), the split of a tile order as a stable partition, and the fold under a tile mask.  Shared by
+tests/moments_checks.py) and the fold under a tile mask (the split of a tile order: tests/split_cases.py).  Shared by
 tests/test_adaptive_host.py and tests/test_gpu_adaptive.py.  Planes are indexed [x, y] like dr_accum_read."""
 import numpy as np
 
@@ -56,20 +56,6 @@ def select(acc, hist, m2, gx, gy, divide_by, **params):
 def tile_max_sigma(acc, hist, m2, gx, gy, divide_by):
     """float32[gx * gy]: the largest sigma of each tile"""
     return tiles_of(sigma(acc, hist, m2, gx, gy, divide_by)[1], gx, gy).max(axis=1)
-
-
-def split(order, region_start, flags, regions):
-    """(launch_order, launch_region_start int32[17]): the stable partition of the order (None: the identity) by the flags; region r's compacted
-    start is the number of flagged tiles at the positions in front of region_start[r]; the split counts [9 ..] are 0"""
-    flags = np.asarray(flags)
-    tiles = len(flags)
-    order = np.arange(tiles, dtype=np.int32) if order is None else np.asarray(order, np.int32)
-    kept = flags[order] != 0
-    before = np.concatenate([[0], np.cumsum(kept)])
-    lrs = np.zeros(17, np.int32)
-    for r in range(regions + 1):
-        lrs[r] = before[min(int(region_start[r]), tiles)]
-    return order[kept].astype(np.int32), lrs
 
 
 def pixel_mask(flags, gx, gy, W, H):

@@ -13,6 +13,7 @@ from conftest import ROOT
 import adaptive_checks as ac
 import moments_checks as mc
 import plane_cases as pc
+import split_cases as sp
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
@@ -167,34 +168,23 @@ def test_judge_refuses(hk):
 @pytest.mark.parametrize("regions,tiles", [(1, 40), (8, 512), (1, 512), (8, 40), (8, 1)])
 def test_split_is_a_stable_partition(hk, regions, tiles):
     rng = np.random.default_rng(1000 * regions + tiles)
-    for kind in ("random", "none", "all", "region", "random", "random"):
-        for identity in (False, True):
-            if identity:
-                rs = np.array([(tiles * r + regions - 1) // regions for r in range(regions + 1)], np.int32)      # make_params' bands
-                order = None
-            else:
-                cuts = np.sort(rng.integers(0, tiles + 1, regions - 1)).astype(np.int32)                          # (empty regions among them)
-                rs = np.concatenate([[0], cuts, [tiles]]).astype(np.int32)
-                order = rng.permutation(tiles).astype(np.int32)
-            flags = (rng.random(tiles) < rng.random()).astype(np.uint8)
-            if kind == "none": flags[:] = 0
-            if kind == "all": flags[:] = 1
-            if kind == "region":                                                                                  # one whole region emptied
-                emptied = int(rng.integers(0, regions))
-                held = np.arange(tiles, dtype=np.int32)[rs[emptied]:rs[emptied + 1]] if order is None else order[rs[emptied]:rs[emptied + 1]]
-                flags[held] = 0
-            rs_in = np.concatenate([rs, np.full(2 * MAX_REGIONS + 1 - len(rs), 7, np.int32)])                    # (what lies behind [regions] is not read)
-            lo, lrs = hk.subset_split(order, rs_in, flags, regions)
-            want_lo, want_lrs = ac.split(order, rs, flags, regions)
-            assert np.array_equal(lo, want_lo) and np.array_equal(lrs, want_lrs), (kind, identity, lrs, want_lrs)
-            # the properties, plainly: every flagged tile once, the regions' tiles in the order they had, the length in [regions], no split counts
-            assert np.array_equal(np.sort(lo), np.nonzero(flags)[0]) and lrs[regions] == flags.sum() and not lrs[regions + 1:].any()
-            full = np.arange(tiles, dtype=np.int32) if order is None else order
-            for r in range(regions):
-                mine = full[rs[r]:rs[r + 1]]
-                assert np.array_equal(lo[lrs[r]:lrs[r + 1]], mine[flags[mine] != 0]), (kind, identity, r)
-            if kind == "region":
-                assert lrs[emptied] == lrs[emptied + 1]
+    cases_run = 0
+    for c in sp.cases(rng, regions, tiles):
+        kind, identity, order, rs, emptied = c.kind, c.identity, c.order, c.rs, c.emptied
+        flags = sp.flags(c.kept)
+        lo, lrs = hk.subset_split(order, c.rs_in(), flags, regions)
+        want_lo, want_lrs, _ = sp.partition(order, rs, flags, regions)
+        assert np.array_equal(lo, want_lo) and np.array_equal(lrs, want_lrs), (kind, identity, lrs, want_lrs)
+        # the properties, plainly: every flagged tile once, the regions' tiles in the order they had, the length in [regions], no split counts
+        assert np.array_equal(np.sort(lo), np.nonzero(flags)[0]) and lrs[regions] == flags.sum() and not lrs[regions + 1:].any()
+        full = np.arange(tiles, dtype=np.int32) if order is None else order
+        for r in range(regions):
+            mine = full[rs[r]:rs[r + 1]]
+            assert np.array_equal(lo[lrs[r]:lrs[r + 1]], mine[flags[mine] != 0]), (kind, identity, r)
+        if kind == "region":
+            assert lrs[emptied] == lrs[emptied + 1]
+        cases_run += 1
+    assert cases_run == 12
 
 
 def test_fold_equals_the_restatement(hk):

@@ -5,7 +5,7 @@ hooks"), on the generated scene of tests/shade_cases.py and n = 0, 1 and 257 ite
       alignment in the staging shows here (every element is computed from its own inputs alone; tests/shade_checks.py holds the merged sampler,
       whose lanes share a loop, equal to the per-element reference, so it holds there too);
   (c) through ctypes with n = 1, a hook with one required pointer NULL returns DR_ERR_INVALID and leaves the caller's arrays alone; dr_kat_hit with
-      visits NULL succeeds.
+      visits NULL, and dr_kat_order_split with order NULL, succeed.
 What the hooks compute is the parity tests' business (test_gpu_parity, test_gpu_shade, test_gpu_rays): no oracle here."""
 import ctypes as C
 
@@ -170,6 +170,7 @@ def c_args(hook, arrays, outs):
     if hook == "camera": return [sc.camera_views()[VIEW], sc.CAMERA_W, sc.CAMERA_H, FRAME_SEED, STRIDE, 1] + arrays + outs
     if hook == "store": return [1] + arrays + [3] + outs
     if hook == "tile_feedback": return [1, 1, 1, 400, 0] + arrays + outs
+    if hook == "order_split": return [0, 1, 1] + arrays + outs      # kind 0: every output is written
     return [1] + arrays + outs
 
 
@@ -177,11 +178,13 @@ def as_c(a):
     return a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a
 
 
-@pytest.mark.parametrize("hook", HOOKS + ("tile_feedback",))
+@pytest.mark.parametrize("hook", HOOKS + ("tile_feedback", "order_split"))
 def test_a_null_pointer_is_refused(dr, ctx, items, hook):
     f = getattr(dr.lib(), "dr_kat_" + hook)
     if hook == "tile_feedback":
         arrays, spec = [np.arange(64, dtype=U32)], ((U32, 1), (I, 1), (I, 2 * dr.MAX_REGIONS + 1))
+    elif hook == "order_split":      # one tile, one region, the identity spelled out; the tile's word: the root
+        arrays, spec = [np.zeros(1, I), np.array([0, 1], I), np.zeros(1, U32)], ((I, 1), (I, 2 * dr.MAX_REGIONS + 1), (I, 1), (U32, 2))
     else:
         arrays, spec = [np.ascontiguousarray(a[N - 1:]) for a in items[hook]], C_OUT[hook]
     fresh = lambda: [np.full(k, 0x5a, np.uint8).view(dt) for dt, k in ((dt, np.dtype(dt).itemsize * per) for dt, per in spec)]
@@ -194,11 +197,11 @@ def test_a_null_pointer_is_refused(dr, ctx, items, hook):
     for k in pointers:
         outs = fresh()
         args = c_args(hook, arrays, outs)
-        optional = hook == "hit" and args[k] is outs[2]
+        optional = (hook == "hit" and args[k] is outs[2]) or (hook == "order_split" and args[k] is arrays[0])
         args[k] = None
         rc = f(ctx._h, *[as_c(a) for a in args])
         if optional:
-            assert rc == 0 and outs[0].tobytes() != fresh()[0].tobytes()          # visits may be NULL
+            assert rc == 0 and outs[0].tobytes() != fresh()[0].tobytes()          # visits may be NULL, and the split's order
             continue
         assert rc == dr.ERR_INVALID and dr.lib().dr_last_error() == b"null argument", (hook, k, rc)
         assert all(a.tobytes() == b.tobytes() for a, b in zip(outs, fresh())), "a refused call leaves the caller's arrays alone"

@@ -33,6 +33,7 @@ ARRAYS = {
     "camera": (("x", I, ()), ("y", I, ()), ("sample", I, ())),
     "store": (("color", F, (3,)),),
     "tile_feedback": (("pixel_cost", U32, (64,)),),
+    "order_split": (("order", I, ()), ("region_start", I, ()), ("key", U32, ())),
 }
 ST = np.array([0, 0, 2, 0, 0, 0, 0, 1, 45, 1, 1, 1, -1], F)
 # how a wrapper f takes the arrays a beside its other arguments
@@ -86,12 +87,12 @@ def expect_refusals(hook, f):
 
 def test_the_table_states_the_signatures():
     import dogeray_amd as dr
-    assert set(dr.KAT_HOOKS) == set(ARRAYS) and len(ARRAYS) == 17
+    assert set(dr.KAT_HOOKS) == set(ARRAYS) and len(ARRAYS) == 18
     for hook, ins in ARRAYS.items():
         assert tuple((name, np.dtype(dt), tail) for name, dt, tail in dr.KAT_HOOKS[hook][0]) == tuple((name, np.dtype(dt), tail) for name, dt, tail in ins), hook
 
 
-@pytest.mark.parametrize("hook", [h for h in ARRAYS if h not in ("rng", "tile_feedback")])
+@pytest.mark.parametrize("hook", [h for h in ARRAYS if h not in ("rng", "tile_feedback", "order_split")])
 def test_context_wrapper_judges_shapes_before_the_library(monkeypatch, hook):
     import dogeray_amd as dr
     monkeypatch.setattr(dr, "lib", touched)
@@ -117,6 +118,26 @@ def test_the_two_wrappers_with_a_count_of_their_own(monkeypatch):
         ctx.kat_tile_feedback(pix, 1, 1, 400, 0)                    # its own count: two whole tiles
     with pytest.raises(Touched):
         ctx.kat_tile_feedback(pix.reshape(1, -1), 1, 1, 400, 0, ntiles=0)      # (the library refuses that one)
+
+
+def test_the_order_split_wrapper_counts_its_key(monkeypatch):
+    """kat_order_split counts tiles by its key; the order, if there is one, has as many entries, region_start at least regions + 1"""
+    import dogeray_amd as dr
+    monkeypatch.setattr(dr, "lib", touched)
+    ctx = dr.Context.__new__(dr.Context)
+    ctx._h = None
+    rs = np.array([0, 2, 5], I)
+    for kind, key in ((0, np.zeros(5, U32)), (1, np.ones(5, np.uint8))):
+        with pytest.raises(ValueError) as e:
+            ctx.kat_order_split(kind, 2, np.arange(4, dtype=I), rs, key)
+        assert str(e.value) == "kat_order_split: order must be [n]"
+        with pytest.raises(ValueError) as e:
+            ctx.kat_order_split(kind, 3, None, rs, key)
+        assert str(e.value) == "kat_order_split: region_start must hold regions + 1 entries"
+        with pytest.raises(Touched):
+            ctx.kat_order_split(kind, 2, None, rs, key)
+        with pytest.raises(Touched):
+            ctx.kat_order_split(kind, 2, np.arange(5, dtype=I)[::-1], rs, key)
 
 
 @pytest.mark.parametrize("hook", HOST_FUNCTIONS + HOST_METHODS)

@@ -1,6 +1,6 @@
 """Sky tiles (option sky_tiles) on the host build of the kernel's own code (tools/host_kernel.cpp):
  * hk_sky_split, the partition of a launch's tile order into the geometry tiles the persistent kernel keeps and the sky tiles (device_sky.hpp
-   sky_split_plain), against a stable partition written in numpy;
+   SkyKeep, device_split.hpp order_split_plain), against the stable partition written in numpy (tests/split_cases.py);
  * hk_sky_pixel, the per-pixel body of sky_tiles_kernel (device_sky.hpp sky_pixel), against the host kernel's own render of the same pixels from the
    root, int for int, for every tile the views' entry tables give the code ENTRY_NONE;
  * the launch plan's decision: only the lean build of the wide walk that adds a batch into one buffer is split.
@@ -15,10 +15,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "..", "tools"))
 import camera_entry_cases as cases
+import split_cases as sp
 from camera_entry_cases import SEED, SIZES, STRIDE
 
-MAX_REGIONS = 8
-ENTRY_SHIFT = 3
 SKY_NAMES = ("hf_1", "hf_0.1", "cube", "tiny_2", "grid_small", "matball")
 
 
@@ -33,53 +32,23 @@ def paths(synth, tmp_path_factory):
     return cases.paths(synth, tmp_path_factory.mktemp("skyhost"))
 
 
-def _words(rng, sky):
-    """a word per tile: entry code << ENTRY_SHIFT | grade, code -1 for the sky tiles and a record (or the root) for the others"""
-    code = np.where(sky, -1, rng.integers(0, 1 << 20, len(sky)) * rng.integers(0, 2, len(sky))).astype(np.int64)
-    return ((code << ENTRY_SHIFT) | rng.integers(0, 6, len(sky))).astype(np.int64).astype(np.uint32)
-
-
-def _partition(order, rs, sky, regions):
-    """the stable partition, plainly: what stays of the order, where the regions of what stays begin, and the sky tiles"""
-    order = np.arange(len(sky), dtype=np.int32) if order is None else order
-    keep = ~sky[order]
-    before = np.concatenate([[0], np.cumsum(keep)])      # kept tiles in front of position i
-    lrs = np.zeros(2 * MAX_REGIONS + 1, np.int32)
-    lrs[:regions + 1] = before[rs[:regions + 1]]
-    return order[keep], lrs, np.nonzero(sky)[0].astype(np.int32)
-
-
 @pytest.mark.parametrize("regions,tiles", [(1, 40), (8, 512), (1, 512), (8, 40)])
 def test_split_is_a_stable_partition(regions, tiles):
     import host_kernel
     rng = np.random.default_rng(100 * regions + tiles)
     cases_run = 0
-    for kind in ("random", "none", "all", "region", "random", "random"):
-        for identity in (False, True):
-            if identity:
-                rs = np.array([(tiles * r + regions - 1) // regions for r in range(regions + 1)], np.int32)      # make_params' bands
-                order = None
-            else:
-                cuts = np.sort(rng.integers(0, tiles + 1, regions - 1)).astype(np.int32)                          # (empty regions among them)
-                rs = np.concatenate([[0], cuts, [tiles]]).astype(np.int32)
-                order = rng.permutation(tiles).astype(np.int32)
-            sky = rng.random(tiles) < rng.random()
-            if kind == "none": sky[:] = False
-            if kind == "all": sky[:] = True
-            if kind == "region":                                                                                  # one whole region sky
-                r = int(rng.integers(0, regions))
-                held = np.arange(tiles, dtype=np.int32)[rs[r]:rs[r + 1]] if order is None else order[rs[r]:rs[r + 1]]
-                sky[held] = True
-            word = _words(rng, sky)
-            rs_in = np.concatenate([rs, np.full(2 * MAX_REGIONS + 1 - len(rs), 7, np.int32)])                    # (what lies behind [regions] is not read)
-            lo, lrs, sl = host_kernel.sky_split(order, rs_in, word, regions)
-            want_lo, want_lrs, want_sl = _partition(order, rs, sky, regions)
-            assert np.array_equal(lo, want_lo), (kind, identity)
-            assert np.array_equal(lrs, want_lrs), (kind, identity, lrs, want_lrs)
-            assert np.array_equal(sl, want_sl), (kind, identity)
-            assert np.array_equal(np.sort(np.concatenate([lo, sl])), np.arange(tiles)), (kind, identity)
-            assert lrs[regions] == len(lo) and not lrs[MAX_REGIONS + 1:].any()
-            cases_run += 1
+    for c in sp.cases(rng, regions, tiles):
+        kind, identity, order, rs, sky = c.kind, c.identity, c.order, c.rs, ~c.kept      # (a "region" case: one whole region sky)
+        word = sp.words(rng, c.kept)
+        lo, lrs, sl = host_kernel.sky_split(order, c.rs_in(), word, regions)
+        want_lo, want_lrs, want_sl = sp.partition(order, rs, ~sky, regions)
+        assert np.array_equal(lo, want_lo), (kind, identity)
+        assert np.array_equal(lrs, want_lrs), (kind, identity, lrs, want_lrs)
+        assert np.array_equal(sl, want_sl), (kind, identity)
+        assert np.array_equal(sl, np.nonzero(sky)[0]), (kind, identity)
+        assert np.array_equal(np.sort(np.concatenate([lo, sl])), np.arange(tiles)), (kind, identity)
+        assert lrs[regions] == len(lo) and not lrs[sp.MAX_REGIONS + 1:].any()
+        cases_run += 1
     assert cases_run == 12
 
 

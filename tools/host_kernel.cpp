@@ -14,7 +14,7 @@
 //                  write_aov_channels, host_rows / host_grid; hk_last_error, hk_wide_info
 //   hk_prims.hpp   primitives and generator checks on caller arrays: hk_check_uniform, hk_check_reject, hk_slab, hk_tri_hit, hk_hit_inputs, ...
 //   hk_cert.hpp    the camera rays' certificate and entry table with their checks: hk_cert_check, hk_cert_levels, hk_camera_entry(_check), hk_wide_leaves
-//   hk_plan.hpp    launch_plan.hpp, launch_state.hpp and device_sky.hpp: hk_persistent_plan, hk_trace_plan, ..., hk_order_begin, ..., hk_site_use, hk_sky_split, hk_sky_pixel, hk_sky_units_render
+//   hk_plan.hpp    launch_plan.hpp, launch_state.hpp, device_sky.hpp and device_split.hpp: hk_persistent_plan, hk_trace_plan, ..., hk_order_begin, ..., hk_site_use, hk_sky_split, hk_sky_pixel, hk_sky_units_render
 //   hk_pipeline.hpp pipeline_state.hpp: the pipelined present loop's ticket book and ordering plans, hk_pipeline_*
 //   hk_kat.hpp     the shading step's known-answer hooks: hk_kat_sample .. hk_kat_store
 //   hk_rays.hpp    caller rays: hk_hit, hk_trace, hk_ray_surface, hk_radiance, hk_allhits, hk_allhits_brute
@@ -43,6 +43,7 @@
 #include "../dogeray_amd/csrc/device_radiance.hpp"
 #include "../dogeray_amd/csrc/device_reproject.hpp"
 #include "../dogeray_amd/csrc/device_sky.hpp"
+#include "../dogeray_amd/csrc/device_split.hpp"
 #include "../dogeray_amd/csrc/device_upscale.hpp"
 #include "../dogeray_amd/csrc/launch_plan.hpp"
 #include "../dogeray_amd/csrc/launch_state.hpp"

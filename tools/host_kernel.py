@@ -723,13 +723,19 @@ def adaptive_select(acc, hist, m2, settings13, divide_by, **params):
     return flags[:tiles], {"tiles": tiles, "active_tiles": int(counts[0]), "pixels": 64 * tiles, "asking_pixels": int(counts[1]), "gx": int(grid[0]), "gy": int(grid[1])}
 
 
+def _order_split(entry, order, region_start, key, regions, with_list):
+    """device_split.hpp order_split_plain through hk_sky_split / hk_subset_split: (the entry's count, launch_order int32[tiles], launch_region_start
+    int32[17], the dropped tiles int32[tiles] or None)"""
+    rs, o, tiles = _arr(region_start, np.int32), _arr(order, np.int32), len(key)
+    lo, lrs, dropped = np.zeros(max(1, tiles), np.int32), np.zeros(17, np.int32), np.zeros(max(1, tiles), np.int32) if with_list else None
+    n = entry(_ptr(o), rs.ctypes.data, key.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data, *([dropped.ctypes.data] if with_list else []))
+    return n, lo, lrs, dropped
+
+
 def subset_split(order, region_start, flags, regions):
-    """device_adaptive.hpp subset_split_plain (hk_subset_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], flags
+    """The split by device_adaptive.hpp FlagKeep (hk_subset_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], flags
     uint8[tiles] -> (launch_order int32[flagged tiles], launch_region_start int32[17])."""
-    flags, rs, o = _arr(flags, np.uint8), _arr(region_start, np.int32), _arr(order, np.int32)
-    tiles = len(flags)
-    lo, lrs = np.zeros(max(1, tiles), np.int32), np.zeros(17, np.int32)
-    n = lib().hk_subset_split(_ptr(o), rs.ctypes.data, flags.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data)
+    n, lo, lrs, _ = _order_split(lib().hk_subset_split, order, region_start, _arr(flags, np.uint8), regions, False)
     return lo[:n], lrs
 
 
@@ -806,13 +812,10 @@ def plan_sky_split(cfg, work, coop_steps, per_frame, wave_log_on):
 
 
 def sky_split(order, region_start, word, regions):
-    """device_sky.hpp sky_split_plain (hk_sky_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], word uint32[tiles]
-    -> (launch_order int32[geometry tiles], launch_region_start int32[17], sky_list int32[sky tiles])."""
-    word, rs, o = _arr(word, np.uint32), _arr(region_start, np.int32), _arr(order, np.int32)
-    tiles = len(word)
-    lo, lrs, sky = np.zeros(max(1, tiles), np.int32), np.zeros(17, np.int32), np.zeros(max(1, tiles), np.int32)
-    n = lib().hk_sky_split(_ptr(o), rs.ctypes.data, word.ctypes.data, tiles, int(regions), lo.ctypes.data, lrs.ctypes.data, sky.ctypes.data)
-    return lo[:tiles - n], lrs, sky[:n]
+    """The split by device_sky.hpp SkyKeep (hk_sky_split): order int32[tiles] or None (identity), region_start int32[regions + 1 or more], word
+    uint32[tiles] -> (launch_order int32[geometry tiles], launch_region_start int32[17], sky_list int32[sky tiles])."""
+    n, lo, lrs, sky = _order_split(lib().hk_sky_split, order, region_start, _arr(word, np.uint32), regions, True)
+    return lo[:len(word) - n], lrs, sky[:n]
 
 
 def sky_units(n_sky, batch, chunk):

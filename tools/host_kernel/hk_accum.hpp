@@ -216,9 +216,9 @@ int hk_adaptive_select(const int32_t* acc, const int32_t* hist, const unsigned l
   return 0;
 }
 
-// device_adaptive.hpp subset_split_plain: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of flagged tiles
+// device_split.hpp order_split_plain by FlagKeep: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of flagged tiles
 int hk_subset_split(const int* order, const int* region_start, const uint8_t* flag, int tiles, int regions, int* launch_order, int* launch_region_start) {
-  return subset_split_plain(order, region_start, flag, tiles, regions, launch_order, launch_region_start);
+  return order_split_plain(order, region_start, FlagKeep{flag}, tiles, regions, launch_order, launch_region_start, nullptr).kept;
 }
 
 // dr_render_adaptive's fold on the host: ad_fold_pixel over the n tiles of list (tile = block column * gy + row of settings13's grid), IN PLACE --

@@ -28,9 +28,9 @@ int hk_plan_sky_split(const int* cfg6, long long work, int coop_steps, int per_f
   const PersistentCfg cfg = {cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], cfg6[5] != 0};
   return plan_sky_split(plan_persistent(cfg, work, coop_steps, per_frame != 0, wave_log_on != 0)) ? 1 : 0;
 }
-// device_sky.hpp sky_split_plain: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of sky tiles
+// device_split.hpp order_split_plain by SkyKeep: order may be NULL (identity); launch_region_start 2 * MAX_REGIONS + 1 ints; returns the number of sky tiles
 int hk_sky_split(const int* order, const int* region_start, const uint32_t* word, int tiles, int regions, int* launch_order, int* launch_region_start, int* sky_list) {
-  return sky_split_plain(order, region_start, word, tiles, regions, launch_order, launch_region_start, sky_list);
+  return order_split_plain(order, region_start, SkyKeep{word}, tiles, regions, launch_order, launch_region_start, sky_list).dropped;
 }
 // launch_plan.hpp's sample orders (option sample_order; tests/test_sample_order_host.py): the word RenderParams carries, and sample j of a tile as
 // out2 = (pixel-in-tile, frame) through that word -- the kernel's own call
