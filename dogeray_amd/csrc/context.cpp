@@ -53,6 +53,8 @@ const Option OPTIONS[] = {
     {"radiance_kernel", /* (as above) */ &dr_context::radiance_kernel, 0, 2, 0, NOTHING},
     {"allhits_kernel", /* (as above) */ &dr_context::allhits_kernel, 0, 2, 0, NOTHING},
     {"sample_order", /* (as above) */ &dr_context::sample_order, 0, 1, 0, NOTHING},
+    {"queue_cursor_stride", /* (as above) */ &dr_context::queue_cursor_stride, 1, QUEUE_CURSOR_STRIDE_MAX, 0, NOTHING},
+    {"queue_cursor_skew", /* (as above) */ &dr_context::queue_cursor_skew, 0, CURSOR_LINE_WORDS - 1, 0, NOTHING},
 };
 
 const Option* find_option(const std::string& name) {
@@ -168,8 +170,8 @@ int dr_context_create(int device_ordinal, dr_context** out) {
     delete c;
     return DR_ERR_DEVICE;
   }
-  if (c->tile_counters.alloc(TILE_COUNTERS) != DR_OK ||
-      hipMemsetAsync(c->tile_counters, 0, TILE_COUNTERS * sizeof(unsigned), c->stream) != hipSuccess ||
+  if (c->tile_counters.alloc(CURSOR_RING_ALLOC) != DR_OK ||
+      hipMemsetAsync(c->tile_counters, 0, CURSOR_RING_ALLOC * sizeof(unsigned), c->stream) != hipSuccess ||
       c->counters.alloc(COUNTER_WORDS) != DR_OK ||
       hipMemsetAsync(c->counters, 0, COUNTER_WORDS * sizeof(unsigned long long), c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess) {

@@ -232,9 +232,6 @@ struct TileSubset {
   }
 };
 
-constexpr int TILE_COUNTERS = 1024;
-constexpr int LAUNCH_COUNTERS = MAX_REGIONS + 1;      // a launch's block of them: a cursor per tile queue, then the sky units' cursor (option sky_tiles = 2)
-
 // Pipelined single frames (dr_pipeline_*): render streams the groups alternate between, a stream that folds finished frames into the
 // accumulator in ticket order, PIPE_DEPTH slots of frame / present buffers that rotate, and the book that says which ticket is where
 // (pipeline_state.hpp holds it and every rule about it; context_pipeline.cpp asks, issues and launches).  Outside it: restart_numbering(), drain()
@@ -370,7 +367,10 @@ struct dr_context {
   // multi-GPU gather: two packed copies of this context's stripe (double buffer), sized for the accumulator
   DevMem<int32_t> packed[2];
   DevMem<unsigned long long> counters;
-  DevMem<unsigned> tile_counters; int tile_cursor = 0; int num_cus = 256;
+  // the ring of the queues' cursors, where the last launch's block ended, and the layout's two options (launch_plan.hpp cursor_take holds the rule)
+  DevMem<unsigned> tile_counters; int tile_cursor = 0;
+  int queue_cursor_stride = dr::QUEUE_CURSOR_STRIDE, queue_cursor_skew = 0;
+  int num_cus = 256;
   // cost feedback (persistent kernel): its options, and the tile order of the last view
   int feedback = 1;
   int order_follows_camera = 1;    // a view with the same frame geometry but other settings starts from the previous view's tile order

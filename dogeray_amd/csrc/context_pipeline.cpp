@@ -80,7 +80,7 @@ int pipeline_flush_some(dr_context* c, int n) {
   // and nobody may start on the new ones before they are cleared
   const bool refresh = c->feedback && uses_persistent(c) && tiles > 0 && order_pipeline_refresh(c->order.state, view_key(c, P), tiles, c->feedback_every);
   site.hold_order = !refresh;
-  const GroupPlan plan = p.book.group_plan(g, refresh, c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS);
+  const GroupPlan plan = p.book.group_plan(g, refresh, uses_persistent(c) && cursor_take(c->tile_cursor, c->queue_cursor_stride, c->queue_cursor_skew).wrap);
   // the waits for the slot: its previous group's adds must have run, and the presents nobody has waited for yet stay waitable (they park)
   if (plan.start_behind) {
     HIP_TRY(hipEventRecord(p.sync, c->stream));

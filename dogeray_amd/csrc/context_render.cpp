@@ -152,21 +152,19 @@ int enqueue_frame(dr_context* c, const LaunchSite& site_in, const RenderParams& 
   LaunchSite site = site_in;
   site.hold_order = su.hold;
   if (uses_persistent(c)) {
-    if (c->tile_cursor + LAUNCH_COUNTERS > TILE_COUNTERS) {
-      (void)hipMemsetAsync(c->tile_counters, 0, TILE_COUNTERS * sizeof(unsigned), site.stream);
-      c->tile_cursor = 0;
-    }
-    unsigned* counter = c->tile_counters + c->tile_cursor;      // one counter per region, and the sky units' cursor behind them
-    c->tile_cursor += LAUNCH_COUNTERS;
+    const CursorTake take = cursor_take(c->tile_cursor, c->queue_cursor_stride, c->queue_cursor_skew);
+    if (take.wrap) (void)hipMemsetAsync(c->tile_counters, 0, CURSOR_RING_ALLOC * sizeof(unsigned), site.stream);
+    unsigned* counter = c->tile_counters + take.block;      // a cursor per region, queue_cursor_stride words apart, and the sky units' cursor in the last slot
+    c->tile_cursor = take.next;
     const ViewKey key = view_key(c, P);
     const int* order; unsigned* pcost;
     const OrderUse use = feedback_buffers(c, site, key, tiles, order, pcost);
     if (!c->wave_log_on) P.wave_log = nullptr;
     cert_prepare(c, site, key, P, tiles);
     const int* launch_order = order; const int* launch_rstart = c->order.region_start;      // what the persistent kernel's queues hold: the order, or the split's part of it
-    c->sky.state.last = su.sky_split && sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + MAX_REGIONS);
+    c->sky.state.last = su.sky_split && sky_split(c, site, P, tiles, launch_order, launch_rstart, pcost, counter + cursor_sky_slot(c->queue_cursor_stride));
     if (su.subset_pair) subset_split(site, P, tiles, launch_order, launch_rstart);
-    const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, launch_order, launch_rstart, pcost);
+    const int log_waves = launch_persistent_kernel(site.stream, P, persistent_cfg(c, site), counter, c->queue_cursor_stride, launch_order, launch_rstart, pcost);
     if (log_waves < 0) { set_error("the persistent kernel has no build for this launch (launch_plan.hpp)"); return DR_ERR_DEVICE; }
     c->wave_log_waves = log_waves;
     // next launch's order from this launch's costs (stream-ordered, no host sync), when launch_state.hpp order_end says so

@@ -28,7 +28,8 @@ namespace dr {
 // kernels_render.hip
 void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal, bool count, int occupancy);
 // launches the build plan_persistent (launch_plan.hpp) picks; returns the plan's log_waves, or -1: the plan names a build that is not instantiated
-int launch_persistent_kernel(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
+// (tile_counter, cursor_stride: the launch's block of queue cursors, zero, and the words between two of them -- launch_plan.hpp cursor_take)
+int launch_persistent_kernel(hipStream_t stream, const RenderParams& P, const PersistentCfg& cfg, unsigned* tile_counter, int cursor_stride, const int* order,
                              const int* region_start, unsigned* pixel_cost);
 
 // The 64-bit words of a context's statistics buffer (RenderParams counters).  The render kernels write them, context.cpp reads them

@@ -133,7 +133,7 @@ __device__ __attribute__((noinline)) void sky_units_run(ArgBlock args, int lane,
 template <bool COUNT, int OCC, int TRAV_MIN, int PARK_MIN, int P_UNROLL, bool WIDE, bool COOP = true, bool PERFRAME = false>
 __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParams P, unsigned* __restrict__ tile_counter,
                                                                      const int* __restrict__ tile_order, const int* __restrict__ region_start,
-                                                                     unsigned* __restrict__ pixel_cost) {
+                                                                     unsigned* __restrict__ pixel_cost, int cursor_stride) {
   const int lane = threadIdx.x & 63;
   const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6);
   // a launch whose retiring waves render its sky tiles (sky_units_run, at the end): the waves walk at priority 1 and drop to 0 for the sky units.  The
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256, OCC) void render_persistent_kernel(RenderParam
             const int r0 = region_start ? region_start[region] : P.region_start[region];
             const int r1 = region_start ? region_start[region + 1] : P.region_start[region + 1];
             unsigned t = 0;
-            if (lane == 0) t = atomicAdd(tile_counter + region, 1u);
+            if (lane == 0) t = atomicAdd(tile_counter + region * cursor_stride, 1u);      // (a line per cursor: launch_plan.hpp cursor_take)
             const int q = (int)__builtin_amdgcn_readfirstlane(t);
             const int nsplit = splitting ? region_start[MAX_REGIONS + 1 + region] : 0;
             if (q < (r1 - r0 + nsplit * (P.split_parts - 1)) * P.batch) {
@@ -753,7 +753,7 @@ struct TileEntry { bool count; int mode, occ; void (*kernel)(RenderParams); };
 const TileEntry TILE_BUILDS[] = {DR_TILE_BUILDS(DR_ENTRY)};
 #undef DR_ENTRY
 
-struct PersistentEntry { PersistentBuild build; void (*kernel)(RenderParams, unsigned*, const int*, const int*, unsigned*); };
+struct PersistentEntry { PersistentBuild build; void (*kernel)(RenderParams, unsigned*, const int*, const int*, unsigned*, int); };
 #define DR_ENTRY(COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME) \
   {{COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME}, render_persistent_kernel<COUNT, OCC, T, P, U, WIDE, COOP, PERFRAME>},
 const PersistentEntry PERSISTENT_BUILDS[] = {DR_PERSISTENT_BUILDS(DR_ENTRY)};
@@ -771,7 +771,7 @@ void launch_tile_kernel(hipStream_t stream, const RenderParams& P, int traversal
     }
 }
 
-int launch_persistent_kernel(hipStream_t stream, const RenderParams& P_in, const PersistentCfg& cfg, unsigned* tile_counter, const int* order,
+int launch_persistent_kernel(hipStream_t stream, const RenderParams& P_in, const PersistentCfg& cfg, unsigned* tile_counter, int cursor_stride, const int* order,
                              const int* region_start, unsigned* pixel_cost) {
   RenderParams P = P_in;
   const PersistentPlan plan = plan_persistent(cfg, (long long)P.ncols * P.gy * P.batch, P.coop_steps, P.out_frame_stride != 0, P.wave_log != nullptr);
@@ -779,7 +779,7 @@ int launch_persistent_kernel(hipStream_t stream, const RenderParams& P_in, const
   const int* rstart = order ? region_start : nullptr;        // identity order: the split travels in P.region_start
   for (const PersistentEntry& e : PERSISTENT_BUILDS)
     if (e.build == plan.build) {
-      hipLaunchKernelGGL(e.kernel, dim3((unsigned)plan.blocks), dim3(256), 0, stream, P, tile_counter, order, rstart, pixel_cost);
+      hipLaunchKernelGGL(e.kernel, dim3((unsigned)plan.blocks), dim3(256), 0, stream, P, tile_counter, order, rstart, pixel_cost, cursor_stride);
       return plan.log_waves;
     }
   return -1;      // no such build: nothing is launched in its place

@@ -157,6 +157,42 @@ inline int plan_regions(int tiles, int batch_hint, bool xcd_regions, bool short_
   return regions;
 }
 
+// ---- the queues' cursors.  Every launch takes a block of zeroed words out of a ring: a cursor per tile queue, `stride` words apart
+// (the kernel adds to tile_counter[region * stride]), and in the block's last slot the sky units' cursor (option sky_tiles = 2).  Every wave of every
+// XCD adds to these words with device-scope atomics, which are served where the word's line lives: cursors that share a line queue up behind each
+// other, and how many of a packed block's nine words share one depended on the launch's number (profiles/queue_cursors_ab.txt).  With the default
+// stride no two cursors share a 128-byte line.  The block is (MAX_REGIONS + 1) * stride words, and the blocks follow each other, so each is aligned
+// to the stride.  Options: queue_cursor_stride (1: the packed layout) and queue_cursor_skew, a measuring aid: s > 0 starts every launch's block s
+// words into a 128-byte line (the blocks' pitch is then rounded up to whole lines), which pins the alignment that a packed block otherwise gets
+// from the launch's number.  (The skew is how profiles/queue_cursors_ab.txt showed the cause and that a strided block does not care where it
+// starts; it is not for production use -- cursor_block_pitch's second arm serves it alone.)
+// The ring: CURSOR_RING_LAUNCHES blocks, or as many as the allocation holds (stride 64: 113; stride 1024: 7).  Taking the block that no longer fits
+// wraps: the whole allocation is cleared first (256 KiB, a few microseconds once per 128 launches) and the launch runs alone in the pipeline
+// (pipeline_state.hpp group_plan).  The words from the cursor on are zero whatever layout the earlier blocks had, so an option may change between two
+// launches: a cursor that is no multiple of the new pitch wraps, any other goes on.
+constexpr int QUEUE_CURSOR_STRIDE = 32;                           // option queue_cursor_stride's default: a 128-byte line per cursor
+constexpr int QUEUE_CURSOR_STRIDE_MAX = 1024;
+constexpr int CURSOR_LINE_WORDS = 32;
+constexpr int CURSOR_RING_LAUNCHES = 128;
+constexpr int CURSOR_RING_ALLOC = 1 << 16;                        // words allocated (and cleared at a wrap)
+constexpr int cursor_block_words(int stride) { return (MAX_REGIONS + 1) * stride; }
+constexpr int cursor_sky_slot(int stride) { return MAX_REGIONS * stride; }      // the sky units' cursor: the block's last slot
+constexpr int cursor_block_pitch(int stride, int skew) {
+  return skew > 0 ? (skew + cursor_block_words(stride) + CURSOR_LINE_WORDS - 1) / CURSOR_LINE_WORDS * CURSOR_LINE_WORDS : cursor_block_words(stride);
+}
+constexpr int cursor_ring_blocks(int stride, int skew) {
+  return CURSOR_RING_ALLOC / cursor_block_pitch(stride, skew) < CURSOR_RING_LAUNCHES ? CURSOR_RING_ALLOC / cursor_block_pitch(stride, skew) : CURSOR_RING_LAUNCHES;
+}
+static_assert(cursor_ring_blocks(QUEUE_CURSOR_STRIDE_MAX, CURSOR_LINE_WORDS - 1) >= 2, "the ring holds the widest block");
+// The one rule "next block, and does taking it wrap the ring": `cursor` is where the previous launch's block ended
+struct CursorTake { int block, next; bool wrap; };      // the launch's block (first word), the cursor behind it, the ring is cleared first
+constexpr CursorTake cursor_take(int cursor, int stride, int skew) {
+  const int pitch = cursor_block_pitch(stride, skew);
+  const bool wrap = cursor < 0 || cursor % pitch != 0 || cursor + pitch > cursor_ring_blocks(stride, skew) * pitch;
+  const int at = wrap ? 0 : cursor;
+  return CursorTake{at + (skew > 0 ? skew : 0), at + pitch, wrap};
+}
+
 // Tile order: at most split_waves % of the waves start with a part of a split tile.  ODDITY: the device's num_cus again, and never six waves
 inline int plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) {
   return split_parts > 1 ? (int)((long long)num_cus * (occupancy >= 5 ? 5 : 4) * 4 * split_waves / (100 * split_parts)) : 0;

@@ -213,6 +213,10 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   group): 0 a unit is the tile's 64 pixels of one frame; 1 (default) a unit is consecutive frames of one or two pixels
  *                   of the tile, so the lanes a wave refills together are jittered samples of the same pixel.  A pixel's arithmetic depends on
  *                   (x, y, frame) only and the batch is summed in integers: the same bits either way.  Launches of one frame are the same launch
+ *   "queue_cursor_stride" words between the cursors of two tile queues in a launch's block of the persistent kernel's cursor ring: 32
+ *                   (default) a 128-byte line per cursor, 1 the cursors packed into consecutive words; 1 .. 1024.  The same bits with every value
+ *   "queue_cursor_skew" (a measuring aid) 0 (default) the launches' blocks follow each other in the ring; s = 1 .. 31: every launch's block starts s
+ *                   words into a 128-byte line, which pins the alignment a packed block otherwise gets from the launch's number.  The same bits
  *   "cert_flagged_permille" (read only) per mille of the last certified view's tiles whose camera rays keep the scene's margin; -1 none
  *   "reproject_aov_passes" (read only) first-hit AOV passes the last dr_accum_reproject traced: 2 with a cold guide cache, 1 when its `from`
  *                   view was the previous call's `to` view (0 / 1 when both views are the same settings)

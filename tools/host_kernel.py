@@ -75,6 +75,9 @@ _API = [
     ("hk_tile_sample", None, [C.c_uint, _I, _I, _PI]),
     ("hk_tile_samples", None, [_I, _I, _PI]),
     ("hk_plan_split_limit", _I, [_I] * 4),
+    ("hk_cursor_take", None, [_I, _I, _I, _PI]),
+    ("hk_cursor_layout", None, [_PI]),
+    ("hk_cursor_ring_blocks", _I, [_I, _I]),
     ("hk_plan_sky_split", _I, [_PI, _Q, _I, _I, _I]),
     ("hk_trace_plan", None, [_Q, _I, _I, _I, _I, _P]),
     ("hk_radiance_plan", None, [_Q, _I, _I, _I, _I, _P]),
@@ -834,6 +837,21 @@ def plan_regions(tiles, batch_hint, xcd_regions, short_one_queue, tiles_per_wave
 
 def plan_split_limit(num_cus, occupancy, split_parts, split_waves):
     return int(lib().hk_plan_split_limit(int(num_cus), int(occupancy), int(split_parts), int(split_waves)))
+
+
+def cursor_take(cursor, stride, skew=0):
+    """launch_plan.hpp cursor_take: (first word of the launch's block of queue cursors, the cursor behind it, the ring is cleared first)"""
+    block, nxt, wrap = _ints(3, lib().hk_cursor_take, int(cursor), int(stride), int(skew))
+    return block, nxt, bool(wrap)
+
+
+def cursor_layout():
+    """launch_plan.hpp's cursor constants: default stride, largest stride, words of a line, launches a ring lasts at most, words allocated, slots of a block"""
+    return dict(zip(("stride", "stride_max", "line_words", "ring_launches", "alloc_words", "slots"), _ints(6, lib().hk_cursor_layout)))
+
+
+def cursor_ring_blocks(stride, skew=0):
+    return int(lib().hk_cursor_ring_blocks(int(stride), int(skew)))
 
 
 KEY_FIELDS = ("W", "H", "stripe_mod", "stripe_rem", "ncols", "gy", "regions", "scene_gen", "cert_factor", "cert_levels", "camera_entry", "camera_cert")

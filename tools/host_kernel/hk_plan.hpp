@@ -44,6 +44,17 @@ void hk_tile_samples(int order, int batch, int* out) {
   const unsigned magic = sample_order_magic(order, batch);
   for (int j = 0; j < 64 * batch; j++) hk_tile_sample(magic, batch, j, out + 2 * j);
 }
+// launch_plan.hpp's ring of queue cursors (tests/test_queue_cursors_host.py): cursor_take as out3 = (block, next, wrap), and the layout's constants as
+// out6 = (default stride, largest stride, line words, ring launches, words allocated, slots of a block)
+void hk_cursor_take(int cursor, int stride, int skew, int* out3) {
+  const CursorTake t = cursor_take(cursor, stride, skew);
+  out3[0] = t.block; out3[1] = t.next; out3[2] = t.wrap ? 1 : 0;
+}
+void hk_cursor_layout(int* out6) {
+  const int v[6] = {QUEUE_CURSOR_STRIDE, QUEUE_CURSOR_STRIDE_MAX, CURSOR_LINE_WORDS, CURSOR_RING_LAUNCHES, CURSOR_RING_ALLOC, MAX_REGIONS + 1};
+  memcpy(out6, v, sizeof(v));
+}
+int hk_cursor_ring_blocks(int stride, int skew) { return cursor_ring_blocks(stride, skew); }
 int hk_plan_split_limit(int num_cus, int occupancy, int split_parts, int split_waves) { return plan_split_limit(num_cus, occupancy, split_parts, split_waves); }
 // launch_plan.hpp plan_trace: out3 = kernel (QUERY_KERNEL_*), the traversal really walked, workgroups
 void hk_trace_plan(long long n, int traversal, int has_wide, int num_cus, int force, int* out3) {
