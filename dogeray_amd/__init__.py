@@ -80,6 +80,18 @@ AOV_CHANNELS = {"t": (np.float32, 1), "distance": (np.float32, 1), "depth": (np.
 ALL = tuple(AOV_CHANNELS)
 
 
+class DrAovLensBuffers(C.Structure):
+    """struct dr_aov_lens_buffers: one pointer per lens-averaged channel (NULL: not computed)."""
+    _fields_ = [("coverage", C.c_void_p), ("depth", C.c_void_p), ("distance", C.c_void_p), ("material", C.c_void_p), ("normal", C.c_void_p),
+                ("albedo", C.c_void_p)]
+
+
+# the channels of Context.render_aov_lens: name -> (dtype, components per pixel)
+AOV_LENS_CHANNELS = {"coverage": (np.float32, 1), "depth": (np.float32, 1), "distance": (np.float32, 1), "material": (np.int32, 1),
+                     "normal": (np.float32, 3), "albedo": (np.float32, 3)}
+GUIDE_SEED = 0x67756964656C656E      # DR_GUIDE_SEED: the frame seed of the guides option "guide_frames" traces
+
+
 class DrRayBuffers(C.Structure):
     """struct dr_ray_buffers (include/dogeray_amd.h dr_trace_rays): origin, dir (3 floats per ray), tmax (one, or NULL)."""
     _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("tmax", C.c_void_p)]
@@ -253,6 +265,8 @@ _API = [
     ("dr_accum_unpack_stripes", C.c_int, [_VP, _VP, C.c_uint64, C.c_int, C.c_int, _VP]),
     ("dr_accum_reserve_pack", C.c_int, [_VP, C.c_int]),
     ("dr_render_aov", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DrAovBuffers), C.c_int]),
+    ("dr_render_aov_lens", C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
+                                     C.POINTER(DrAovLensBuffers), C.c_int]),
     ("dr_trace_rays", C.c_int, [_VP, C.c_int, C.c_int64, C.POINTER(DrRayBuffers), C.POINTER(DrHitBuffers), C.c_int]),
     ("dr_radiance_defaults", C.c_int, [C.POINTER(DrRadianceParams)]),
     ("dr_trace_radiance", C.c_int, [_VP, C.c_int64, C.POINTER(DrRadianceRays), C.POINTER(DrRadianceParams), C.POINTER(DrRadianceOut), C.c_int]),
@@ -867,6 +881,11 @@ class Context:
         [h, w] (t, distance, depth: float32; object, material: int32) or [h, w, k] (normal, albedo, dir: 3; uv: 2), row index = the
         renderer's y.  window (x0, y0, w, h) inside the pixel grid, None = all of it.  device=True: torch tensors on this context's GPU,
         written on the library's stream, which waits for torch's current stream first; torch's current stream waits for it afterwards."""
+        return self._aov_window(settings13, W, H, window, channels, device, AOV_CHANNELS, DrAovBuffers(),
+                                lambda st, win, bufs, dp: lib().dr_render_aov(self._h, _p(st), W, H, *win, C.byref(bufs), dp))
+
+    def _aov_window(self, settings13, W, H, window, channels, device, known, bufs, call):
+        """what render_aov and render_aov_lens share: the window, the channels' arrays, the call(st, window, bufs, device_pointers)"""
         st = _f32(settings13)
         assert st.shape == (13,)
         if window is None:
@@ -875,17 +894,27 @@ class Context:
         x0, y0, w, h = (int(v) for v in window)
         channels = tuple(channels)
         for k in channels:
-            if k not in AOV_CHANNELS:
-                raise ValueError("unknown AOV channel %r (known: %s)" % (k, ", ".join(ALL)))
-        shape = lambda k: (max(h, 0), max(w, 0)) + ((AOV_CHANNELS[k][1],) if AOV_CHANNELS[k][1] > 1 else ())
-        bufs = DrAovBuffers()
+            if k not in known:
+                raise ValueError("unknown AOV channel %r (known: %s)" % (k, ", ".join(known)))
+        shape = lambda k: (max(h, 0), max(w, 0)) + ((known[k][1],) if known[k][1] > 1 else ())
         out = {}
         with (self._torch_handshake() if device else contextlib.nullcontext()) as dev:
             for k in channels:
-                out[k], address = _out_array(shape(k), AOV_CHANNELS[k][0], dev)
+                out[k], address = _out_array(shape(k), known[k][0], dev)
                 setattr(bufs, k, address)
-            _check(lib().dr_render_aov(self._h, _p(st), W, H, x0, y0, w, h, C.byref(bufs), 1 if device else 0))
+            _check(call(st, (x0, y0, w, h), bufs, 1 if device else 0))
         return out
+
+    # ---- lens-averaged AOVs (dr_render_aov_lens)
+    def render_aov_lens(self, settings13, W, H, frame_seed, seed_stride, nframes, window=None, channels=None, device=False):
+        """The first-hit buffers averaged over the renderer's own camera rays -- jittered, from a point on the lens -- of nframes frames seeded
+        as render_accumulate(.., frame_seed, seed_stride, nframes) seeds them (include/dogeray_amd.h dr_render_aov_lens): a dict channel ->
+        array [h, w] (coverage, depth, distance: float32; material: int32) or [h, w, 3] (normal, albedo).  nframes * spp must be 1 .. 256.
+        window, channels (None: all of them) and device as render_aov's."""
+        u64 = lambda v: int(v) & (2 ** 64 - 1)
+        return self._aov_window(settings13, W, H, window, tuple(AOV_LENS_CHANNELS) if channels is None else channels, device, AOV_LENS_CHANNELS,
+                                DrAovLensBuffers(), lambda st, win, bufs, dp: lib().dr_render_aov_lens(
+                                    self._h, _p(st), W, H, *win, u64(frame_seed), u64(seed_stride), int(nframes), C.byref(bufs), dp))
 
     # ---- queries on the caller's lists (trace, radiance, trace_all, nearest): what they share
     def _list_query(self, inputs, out_spec, call):

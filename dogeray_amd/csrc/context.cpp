@@ -55,6 +55,8 @@ const Option OPTIONS[] = {
     {"sample_order", /* (as above) */ &dr_context::sample_order, 0, 1, 0, NOTHING},
     {"queue_cursor_stride", /* (as above) */ &dr_context::queue_cursor_stride, 1, QUEUE_CURSOR_STRIDE_MAX, 0, NOTHING},
     {"queue_cursor_skew", /* (as above) */ &dr_context::queue_cursor_skew, 0, CURSOR_LINE_WORDS - 1, 0, NOTHING},
+    {"guide_frames", /* (as above) */ &dr_context::guide_frames, 0, AOV_LENS_MAX, 0, NOTHING},      // (the guides' key holds it: a change re-traces)
+    {"aov_lens_loop", /* (as above) */ &dr_context::aov_lens_loop, AOV_LENS_NESTED, AOV_LENS_REFILL, 0, NOTHING},
 };
 
 const Option* find_option(const std::string& name) {

@@ -81,18 +81,20 @@ struct DevMem {
 template <class T, bool PINNED>
 void swap(DevMem<T, PINNED>& a, DevMem<T, PINNED>& b) { a.swap(b); }
 
-// The key of a cached set of first-hit guides: the view's settings13, the frame size and the scene upload they were traced for
+// The key of a cached set of first-hit guides: the view's settings13, the frame size and the scene upload they were traced for, and the frames
+// they were averaged over (option guide_frames; 0: the pinhole pass, which is all dr_accum_reproject's pair ever holds)
 struct GuideKey {
   bool valid = false;
   float st[13] = {0};
   int W = 0, H = 0;
   uint64_t gen = 0;
-  bool matches(const float* settings13, int w, int h, uint64_t scene_gen) const {
-    return valid && W == w && H == h && gen == scene_gen && memcmp(st, settings13, sizeof(st)) == 0;
+  int frames = 0;
+  bool matches(const float* settings13, int w, int h, uint64_t scene_gen, int guide_frames = 0) const {
+    return valid && W == w && H == h && gen == scene_gen && frames == guide_frames && memcmp(st, settings13, sizeof(st)) == 0;
   }
-  void store(const float* settings13, int w, int h, uint64_t scene_gen) {
+  void store(const float* settings13, int w, int h, uint64_t scene_gen, int guide_frames = 0) {
     memcpy(st, settings13, sizeof(st));
-    W = w; H = h; gen = scene_gen; valid = true;
+    W = w; H = h; gen = scene_gen; frames = guide_frames; valid = true;
   }
 };
 
@@ -329,6 +331,8 @@ struct dr_context {
   // and the AOV passes of the last call
   dr::GuidePlanes up_guides;
   int up_passes = 0;
+  int guide_frames = 0;                    // option: 0 the guides are the pinhole pass's; G > 0 the lens kernel's over G frames of DR_GUIDE_SEED (trace_guides)
+  int aov_lens_loop = 0;                   // private option: the lens kernel's loop shape (kernels.hpp AOV_LENS_*: 0 nested, 1 refilling), for the A/B
   uint64_t scene_gen = 0;                  // scene uploads so far: a guide cache of an earlier scene does not match
   // dr_accum_reproject: the second accumulator of the pair (swapped with `accum` by every reprojection), the two history planes (hist: the
   // current one, null until the first reprojection and after dr_accum_reset), the guide planes of two views (t n | normal 3n | material n

@@ -44,16 +44,42 @@ AovLaunch aov_launch(const dr_context* c, float focus, int x0, int y0, int w, in
   return A;
 }
 
+// A launch_aov_lens over the window (x0, y0, w, h) of the view in P (as aov_view filled it), no channel wanted yet: nframes frames of the view's
+// spp = (int)settings13[10] samples, frame k seeded frame_seed + k * seed_stride, N = nframes * spp in 1 .. AOV_LENS_MAX (`who` starts the refusal)
+int aov_lens_launch(const float settings13[13], int x0, int y0, int w, int h, uint64_t frame_seed, uint64_t seed_stride, int nframes, const char* who,
+                    RenderParams& P, AovLensLaunch& A) {
+  const int spp = hf2i(settings13[10]);
+  if (nframes < 1 || spp < 1 || (long long)nframes * spp > AOV_LENS_MAX) {
+    set_error(std::string(who) + ": " + std::to_string(nframes) + " frames of " + std::to_string(spp) + " samples per pixel; a lens pass takes 1 .. " +
+              std::to_string(AOV_LENS_MAX) + " samples");
+    return DR_ERR_INVALID;
+  }
+  memset(&A, 0, sizeof(A));
+  A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+  A.focus = settings13[7];
+  A.nframes = nframes; A.spp = spp;
+  P.seed = frame_seed; P.batch_seed_stride = seed_stride;
+  return DR_OK;
+}
+
 // The guides of view P (of settings13) over its gw x gh > 0 pixel grid in G, a set of `quads` float4 planes: traced unless G holds them already
 // (*passes then counts the pass).  launch_aov writes normal and depth into float4 plane 1 (3n + n floats), albedo and material into their planes;
 // the guide prepare packs (n, z) into plane 0 and forms gz from them
 int trace_guides(dr_context* c, GuidePlanes& G, int quads, const float settings13[13], int W, int H, const RenderParams& P, int traversal, int* passes) {
   const int gw = P.gx * 8, gh = P.gy * 8;
   DR_TRY(G.grow((size_t)gw * (size_t)gh, quads, c->stream));
-  if (G.key.matches(settings13, W, H, c->scene_gen)) return DR_OK;
+  const int frames = c->guide_frames;
+  if (G.key.matches(settings13, W, H, c->scene_gen, frames)) return DR_OK;
   AovLaunch A = aov_launch(c, settings13[7], 0, 0, gw, gh);
   A.normal = G.quad(1); A.depth = G.quad(1) + 3 * G.n; A.albedo = G.rgb(); A.material = G.material();
-  launch_aov(c->stream, P, traversal, A);
+  if (frames > 0) {      // option guide_frames: the same planes from the renderer's own camera rays, averaged over `frames` frames of DR_GUIDE_SEED
+    AovLensLaunch AL;
+    RenderParams PL = P;
+    DR_TRY(aov_lens_launch(settings13, 0, 0, gw, gh, DR_GUIDE_SEED, 1, frames, "guide_frames", PL, AL));
+    AL.as_guides = 1;
+    AL.normal = A.normal; AL.depth = A.depth; AL.albedo = A.albedo; AL.material = A.material;
+    launch_aov_lens(c->stream, PL, traversal, c->aov_lens_loop, AL);
+  } else launch_aov(c->stream, P, traversal, A);
   HIP_TRY(hipGetLastError());
   DnLaunch L;
   memset(&L, 0, sizeof(L));
@@ -61,7 +87,7 @@ int trace_guides(dr_context* c, GuidePlanes& G, int quads, const float settings1
   L.normal = A.normal; L.depth = A.depth; L.mat = A.material; L.guide = G.quad(0); L.gz = G.scalar();
   launch_denoise_guides(c->stream, L);
   HIP_TRY(hipGetLastError());
-  G.key.store(settings13, W, H, c->scene_gen);
+  G.key.store(settings13, W, H, c->scene_gen, frames);
   if (passes) ++*passes;
   return DR_OK;
 }
@@ -189,6 +215,36 @@ int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x
   launch_aov(c->stream, P, traversal, A);
   HIP_TRY(hipGetLastError());
   return query_end(c, ch, 9, device_pointers != 0, io);
+}
+
+int dr_render_aov_lens(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, uint64_t frame_seed, uint64_t seed_stride,
+                       int nframes, const dr_aov_lens_buffers* buffers, int device_pointers) {
+  if (!c || !settings13 || !buffers) { set_error("null argument"); return DR_ERR_INVALID; }
+  RenderParams P;
+  int traversal = 0;
+  DR_TRY(aov_view(c, settings13, W, H, P, traversal));
+  const int gw = P.gx * 8, gh = P.gy * 8;
+  if (w <= 0 || h <= 0) { set_error("empty AOV window"); return DR_ERR_INVALID; }
+  if (x0 < 0 || y0 < 0 || x0 > gw - w || y0 > gh - h) {
+    set_error("AOV window (" + std::to_string(x0) + ", " + std::to_string(y0) + ", " + std::to_string(w) + ", " + std::to_string(h) +
+              ") is not inside the " + std::to_string(gw) + " x " + std::to_string(gh) + " pixel grid");
+    return DR_ERR_INVALID;
+  }
+  AovLensLaunch A;
+  DR_TRY(aov_lens_launch(settings13, x0, y0, w, h, frame_seed, seed_stride, nframes, "render_aov_lens", P, A));
+  DR_TRY(join_pipeline(c));      // ordered behind the frames submitted before
+  const QueryOut ch[6] = {{buffers->coverage, 1, true}, {buffers->depth, 1, true}, {buffers->distance, 1, true}, {buffers->material, 1, true},
+                          {buffers->normal, 3, true}, {buffers->albedo, 3, true}};
+  bool any = false;
+  for (int k = 0; k < 6; k++) any = any || ch[k].p;
+  if (!any) return DR_OK;
+  QueryIo io;
+  DR_TRY(query_begin(c, (size_t)w * (size_t)h, 1, nullptr, 0, ch, 6, device_pointers != 0, io));
+  A.coverage = (float*)io.out[0]; A.depth = (float*)io.out[1]; A.distance = (float*)io.out[2]; A.material = (int32_t*)io.out[3];
+  A.normal = (float*)io.out[4]; A.albedo = (float*)io.out[5];
+  launch_aov_lens(c->stream, P, traversal, c->aov_lens_loop, A);
+  HIP_TRY(hipGetLastError());
+  return query_end(c, ch, 6, device_pointers != 0, io);
 }
 
 int dr_denoise_defaults(dr_denoise_params* p) {

@@ -18,6 +18,7 @@
 //   device_surface.hpp    reflect / refract, texture fetch, surface normal
 //   device_shade.hpp      one bounce, one path, the camera ray, the pixel's store
 //   device_aov.hpp        the first hit of a pixel's pinhole ray
+//   device_aov_lens.hpp   the first hits of a pixel's own camera rays, averaged
 // device_coop.hpp (wave-level code of the persistent kernel) is device only and not part of the umbrella: kernels_render.hip includes it itself.
 #pragma once
 #include "device_prims.hpp"
@@ -30,3 +31,4 @@
 #include "device_surface.hpp"
 #include "device_shade.hpp"
 #include "device_aov.hpp"
+#include "device_aov_lens.hpp"

@@ -129,6 +129,7 @@ void usage() {
           "               [--spp S] [--depth D] [--seed N] [--device I] [--gpus N] [--group G] [--gather-every K] [--cache] [--quiet]\n"
           "               [--aov PREFIX] [--autofocus] [--denoise FILE.bmp|.ppm|.pfm] [--move-to CX,CY,CZ,LX,LY,LZ] [--move-frames N]\n"
           "               [--until-sigma T[,PERMILLE]] [--adaptive] [--max-frames N] [--sigma-out FILE.pfm] [--preview PREFIX] [--preview-block]\n"
+          "               [--guide-frames N]\n"
           "  scene        .rts file (default scene.rts, as the reference)\n"
           "  --textures   directory scanned for *ppm* textures (default: current directory, as the reference)\n"
           "  --frames     full-resolution frames to accumulate after the 4 preview stages (default 64)\n"
@@ -154,7 +155,9 @@ void usage() {
           "  --sigma-out  after the render, write that standard error per pixel as a one-channel .pfm (needs no --until-sigma)\n"
           "  --preview    write the three low stages of the preview ladder (1/8, 1/4, 1/2 resolution) at full size as PREFIX_8.bmp, PREFIX_4.bmp and\n"
           "               PREFIX_2.bmp: the AOV-guided upsample of each stage (dr_accum_upscale, default parameters)\n"
-          "  --preview-block  with --preview: every low pixel fills a block instead, as the reference displays these stages\n");
+          "  --preview-block  with --preview: every low pixel fills a block instead, as the reference displays these stages\n"
+          "  --guide-frames  with --denoise / --preview: the guides are the first hits of the renderer's own camera rays -- jittered, from the lens --\n"
+          "               averaged over N frames (option guide_frames, 1 .. 256 / spp) instead of the pinhole rays': for scenes with an aperture\n");
 }
 
 }  // namespace
@@ -170,7 +173,7 @@ int main(int argc, char** argv) {
   float until_sigma = 0;
   int until_permille = 10, max_frames = 1024;
   const char* texdir = nullptr;
-  int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0;
+  int frames = 64, device = 0, group = 8, width = 0, height = 0, spp = 0, depth = 0, gpus = 0, gather_every = 0, guide_frames = 0;
   uint64_t seed = 1;
   bool quiet = false, have_scene = false, use_cache = false, autofocus = false;
   for (int i = 1; i < argc; i++) {
@@ -208,6 +211,7 @@ int main(int argc, char** argv) {
     else if (a == "--sigma-out") sigma_path = next();
     else if (a == "--preview") preview_prefix = next();
     else if (a == "--preview-block") preview_block = true;
+    else if (a == "--guide-frames") guide_frames = atoi(next());
     else if (a == "-h" || a == "--help") { usage(); return 0; }
     else if (!have_scene && a[0] != '-') { scene_path = a; have_scene = true; }
     else { usage(); return 2; }
@@ -265,6 +269,7 @@ int main(int argc, char** argv) {
     if (moments && dr_context_set_option(ctx, "moments", 1) != DR_OK) die("cannot enable the second-moment plane");
     if (dr_accum_reset(ctx, W, H) != DR_OK) die("cannot allocate the accumulator");
   }
+  if (guide_frames != 0 && dr_context_set_option(ctx, "guide_frames", guide_frames) != DR_OK) die("--guide-frames");
   if (autofocus) {                       // K:2471-2483 sets the focus by hand; here: what the centre pixel of the full-resolution grid sees
     float st[13];
     pack13(s, 1, s.spp, s.max_depth, st);

@@ -121,6 +121,21 @@ struct AovLaunch {
   float* normal; float* uv; float* albedo; float* dir;
 };
 void launch_aov(hipStream_t stream, const RenderParams& P, int traversal, const AovLaunch& A);
+// ... and the lens-averaged channels of the same window (dr_render_aov_lens; device_aov_lens.hpp): N = nframes * spp samples per pixel, 1 .. AOV_LENS_MAX,
+// with P.seed the frame seed and P.batch_seed_stride the stride between frames.  loop: AOV_LENS_NESTED the plain nested loop (the faster one as
+// measured, DESIGN.md 4.22: the default), AOV_LENS_REFILL the refilling walk loop (private option aov_lens_loop: the A/B; the same bits)
+constexpr int AOV_LENS_MAX = 256;
+constexpr int AOV_LENS_NESTED = 0, AOV_LENS_REFILL = 1;
+struct AovLensLaunch {
+  int x0, y0, w, h;
+  float focus;                    // settings13[7]
+  int nframes, spp;
+  int as_guides;                  // trace_guides' form: a pixel whose material is -1 a miss in every channel, albedo + (1 - coverage)
+  float* coverage; float* depth; float* distance;
+  int32_t* material;
+  float* normal; float* albedo;
+};
+void launch_aov_lens(hipStream_t stream, const RenderParams& P, int traversal, int loop, const AovLensLaunch& A);
 
 // kernels_trace.hip: n caller rays (origin / dir 3 floats per ray, tmax one or null: every ray 10000) and what to write per ray (null: not written).
 // The trace kernel writes t (-1: miss), object (slot_to_orig of the slot, -1: miss), occluded (1 / 0) and hit -- {t bits, slot}, miss {-1, -1}: what

@@ -233,6 +233,14 @@ int dr_context_set_traversal(dr_context* c, int mode);
  *                   one-ray-per-lane kernel, 2 the persistent kernel wherever it exists (the wide walk over a scene with a wide tree).  The same bits either way
  *   "allhits_kernel" (private, for the tests) which kernel dr_trace_all_hits runs: 0 (default) the launch plan decides by the ray count, 1 the
  *                   one-ray-per-lane kernel, 2 the persistent kernel wherever it exists (a scene with a wide tree).  The same bits either way
+ *   "guide_frames"  where dr_accum_denoise and dr_accum_upscale (both of its guide sets) take their guides from: 0 (default) the pinhole pass of
+ *                   dr_render_aov, the code and the bits as before; G = 1 .. 256: the lens-averaged pass of dr_render_aov_lens in its guide form over
+ *                   nframes = G, frame_seed = DR_GUIDE_SEED, seed_stride = 1, so that with aperture > 0 the edge stops and the albedo see the blur the
+ *                   renderer integrates.  G * (int)settings13[10] > 256 is refused by the call that traces (DR_ERR_INVALID).  The cached guides are
+ *                   keyed by it: a change in either direction traces again.  dr_accum_reproject keeps its pinhole pair: it reprojects positions
+ *   "aov_lens_loop" (private, for the tests and the A/B) the loop shape of dr_render_aov_lens's kernel: 0 (default, the faster one as measured) the
+ *                   nested loop, every sample's walk waiting for the wave's slowest lane; 1 one walk loop per wave whose lanes start their next
+ *                   sample as soon as their walk ends.  The same bits either way
  * The environment variable DOGERAY_OPTIONS="name=value,..." applies the same at context creation. */
 enum { DR_KERNEL_TILE = 0, DR_KERNEL_PERSISTENT = 1 };
 int dr_context_set_option(dr_context* c, const char* name, int value);
@@ -372,6 +380,47 @@ typedef struct dr_aov_buffers {
  * upload copies the slot -> object map to the device. */
 int dr_render_aov(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, const dr_aov_buffers* buffers,
                   int device_pointers);
+
+/* ------------------------------------------------------------------ lens-averaged AOVs -- */
+/* The same window of the same pixel grid, seen through the rays the RENDERER traces: the jittered rays that leave from a point on the lens
+ * (K:1065-1073, lens radius settings13[6] / 2, K:1052), averaged over N samples per pixel.  With aperture > 0 a defocused edge is a ramp of coverage
+ * and a blend of albedos here, where dr_render_aov shows the sharp pinhole edge; with aperture 0 what remains is the pixel jitter.
+ *   samples     of pixel (x, y): frame k = 0 .. nframes - 1 outer, sample s = 0 .. spp - 1 inner, spp = (int)settings13[10]; N = nframes * spp,
+ *               1 <= N <= 256 (one call costs about N pinhole passes)
+ *   ray         sample (k, s) seeds a fresh generator with frame_seed + k * seed_stride + s * 0x9E3779B97F4A7C15 + (x + y * 8 * gx) (64-bit
+ *               wrapping; gx = W / div / 8: the unstriped view's launch width, K:1065) and draws the jitter and the lens point as K:1066-1073 do:
+ *               exactly the camera rays dr_render_accumulate(settings13, W, H, ., frame_seed, seed_stride, nframes) traces on an unstriped context,
+ *               and dr_kat_camera's (frame seed frame_seed + k * seed_stride, stride 8 * gx)
+ *   per sample  the closest hit (hit() K:468-512, as dr_render_aov) and, there, what dr_trace_rays' surface channels report: t, distance, the
+ *               facing normal, ocolor, mat.  h = the number of samples that hit
+ * Every sum below is a plain float + in sample order starting from 0 (a product is rounded before it is added: no FMA contraction), every quotient
+ * one division at the end; there is no random draw beyond the camera ray's and no counter.  Channels (NULL: not computed), laid out as dr_render_aov's:
+ *   coverage  f32    (float)h / (float)N                                                        h = 0: 0
+ *   depth     f32    (sum over the hits of t * settings13[7]) / (float)h: the lens offset lies in the u, v plane, so every lens ray keeps the focus
+ *                    distance as its component along -w (K:1047-1049) and t * focus is still the distance along the view axis      h = 0: +inf
+ *   distance  f32    (sum over the hits of dr_trace_rays' distance) / (float)h                  h = 0: +inf
+ *   normal    3 f32  (sum over the hits of the facing normal, K:807-825) / (float)h, not renormalised: shorter where the normals disagree    h = 0: 0
+ *   albedo    3 f32  (sum over the hits of ocolor, K:826-844) / (float)N: premultiplied by coverage    h = 0: 0
+ *   material  i32    the Boyer-Moore majority candidate of the per-sample values in sample order, a sample's value being its mat (K:852-944) on a
+ *                    hit and -1 on a miss: cnt = 0; for each value v: if cnt == 0 { cand = v; cnt = 1 } else if v == cand cnt++ else cnt--; the
+ *                    result is cand -- the majority whenever there is one.  material != -1 implies h >= 1              h = 0: -1
+ * The GPU is bit-identical to the host build of the same source (dogeray_amd/csrc/device_aov_lens.hpp) and to the fold of dr_kat_camera's rays
+ * through dr_trace_rays written out in tests/aov_lens_checks.py, with every traversal and every loop shape (option "aov_lens_loop").
+ * Not here: t, uv, dir and object channels, stripes and dr_group, more than 256 samples per call. */
+#define DR_GUIDE_SEED 0x67756964656C656Eull /* the frame_seed of the guides option "guide_frames" traces ("guidelen") */
+typedef struct dr_aov_lens_buffers {
+  float* coverage;
+  float* depth;
+  float* distance;
+  int32_t* material;
+  float* normal;   /* w * h * 3 */
+  float* albedo;   /* w * h * 3 */
+} dr_aov_lens_buffers;
+/* The channels of the window (x0, y0, w, h) of the pixel grid.  Windows, host / device buffers, stream ordering and error codes as dr_render_aov;
+ * changes neither the accumulator, nor dr_stats, the stripe or any option (the context's stripe is ignored: the view is the unstriped one).
+ * DR_ERR_INVALID also for N = nframes * spp outside 1 .. 256. */
+int dr_render_aov_lens(dr_context* c, const float settings13[13], int W, int H, int x0, int y0, int w, int h, uint64_t frame_seed, uint64_t seed_stride,
+                       int nframes, const dr_aov_lens_buffers* buffers, int device_pointers);
 
 /* ------------------------------------------------------------------ ray queries --------- */
 /* Closest hit and occlusion on the CALLER's rays -- line of sight, ambient occlusion, baking, picking along arbitrary rays, a tensor of rays in a
@@ -572,7 +621,10 @@ int dr_trace_all_hits(dr_context* c, int64_t n, const dr_ray_buffers* rays, cons
  *              (uint8)(int)fminf(fmaxf(f, 0), 255) -- dr_accum_present's layout; pixels outside the grid are 0
  *   iterations 0: no filter and no demodulation, f = c: out_rgb8 is dr_accum_present(divide_by) byte for byte for divide_by < 65536 and
  *              |acc| < 2^24
- * The guides are pinhole rays through the pixel centres: with aperture > 0 the defocused parts of the image are filtered against sharp guides. */
+ * By default the guides are pinhole rays through the pixel centres: with aperture > 0 the defocused parts of the image are then filtered against
+ * sharp guides.  Option "guide_frames" = G > 0 takes them from dr_render_aov_lens over G frames instead, in its guide form: a pixel whose material
+ * is -1 is a miss in every channel (n = 0, z = +inf, a = 0), and a = albedo + (1 - coverage) per channel -- a missed sample counts as albedo 1, so
+ * demodulation leaves the sky's share alone; a' above then applies unchanged. */
 typedef struct dr_denoise_params {
   int iterations;          /* 0 .. 10, default 5 */
   float sigma_luminance;   /* >= 0, default 4 */
@@ -610,7 +662,8 @@ int dr_accum_denoise(dr_context* c, const float settings13[13], int W, int H, in
  *              allocated beyond the staging of host outputs
  *   guides     full: N_P, Z_P, M_P, A_P = normal, depth, material, albedo of dr_render_aov for settings13 with element 11 set to 1.0f; gz_P
  *              the denoiser's depth gradient over P's four neighbours in the full grid; A'_P = a'(A_P, M_P).  Low: n_q, z_q, m_q, a_q the same
- *              channels for settings13 itself, a'_q; e_q = c_q / a'_q per channel
+ *              channels for settings13 itself, a'_q; e_q = c_q / a'_q per channel.  Option "guide_frames" = G > 0: both sets are
+ *              dr_render_aov_lens's guide form over G frames instead, as for dr_accum_denoise
  *   position   in integers: tx = 2 X + 1 - div, x0 = floor(tx / (2 div)) (-1 on the left edge), rx = tx - 2 div x0, fx = (float)rx /
  *              (float)(2 div); y0, fy likewise.  bx = (1.0f - fx, fx), by = (1.0f - fy, fy)
  *   taps       j = 0, 1 outer, i = 0, 1 inner, q = (x0 + i, y0 + j), b = bx_i * by_j.  No tap when q is outside the low grid, b == 0, exactly
@@ -693,7 +746,8 @@ int dr_reproject_defaults(dr_reproject_params* p);
  * pass instead of two (option "reproject_aov_passes").  Ordered behind the frames submitted before it (dr_pipeline_submit); returns when the
  * counts are known; changes neither dr_stats nor any option.  Both settings are accepted or refused as by dr_render_aov; DR_ERR_INVALID for no
  * scene, no accumulator, W / H not the accumulator's, frames < 1, views with different divisors, a stripe other than (1, 0), a degenerate
- * `from` view, or parameters outside their ranges.  The guides are pinhole rays: the lens is ignored, as by the denoiser. */
+ * `from` view, or parameters outside their ranges.  The guides are pinhole rays whatever option "guide_frames" says: what is
+ * reprojected is a position, and the lens-averaged channels (dr_render_aov_lens) are no position. */
 int dr_accum_reproject(dr_context* c, const float from_settings13[13], const float to_settings13[13], int W, int H, int frames,
                        const dr_reproject_params* params, dr_reproject_result* result);
 

@@ -141,6 +141,7 @@ _API = [
     ("hk_nearest_records", _Q, [_P, _I, _I]),
     ("hk_render", _I, _VIEW + [_F, _U64, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     ("hk_aov", _I, _VIEW + [_I] * 6 + [_P] * 9),
+    ("hk_aov_lens", _I, _VIEW + [_I] * 4 + [_U64, _U64] + [_I] * 4 + [_P] * 6),
     ("hk_denoise", _I, [_P, _I, _I, _I] + [_P] * 8 + [_I, _P, _P]),
     ("hk_upscale", _I, [_P, _I, _I, _I] + [_P] * 14 + [_I, _P, _P]),
     ("hk_camera_block", _I, [_P, _I, _I, _P, _P, _P]),
@@ -202,12 +203,13 @@ def _rays(o, d, tmax=None):
 
 # the channels the queries return: dtype and width -- 0 one value per ray, 1 one per entry (ray, point, pixel, or list entry), w > 1 a vector per entry
 _CHANNELS = {"count": (np.int32, 0), "occluded": (np.int32, 1), "bounces": (np.int32, 1), "object": (np.int32, 1), "material": (np.int32, 1),
-             "t": (np.float32, 1), "distance": (np.float32, 1), "d2": (np.float32, 1), "depth": (np.float32, 1), "uv": (np.float32, 2),
+             "t": (np.float32, 1), "distance": (np.float32, 1), "d2": (np.float32, 1), "depth": (np.float32, 1), "coverage": (np.float32, 1), "uv": (np.float32, 2),
              "normal": (np.float32, 3), "albedo": (np.float32, 3), "point": (np.float32, 3), "dir": (np.float32, 3), "radiance": (np.float32, 3)}
 NEAREST_CHANNELS = ("distance", "d2", "object", "material", "point", "uv")      # in the order of dr_nearest_buffers
 ALLHITS_CHANNELS = ("count", "t", "object", "material", "distance", "normal", "uv", "albedo")      # in the order of dr_allhits_buffers
 _SURFACE_CHANNELS = ("material", "distance", "normal", "uv", "albedo")          # what hk_ray_surface writes
 _AOV_CHANNELS = ("t", "distance", "depth", "object", "material", "normal", "uv", "albedo", "dir")
+_AOV_LENS_CHANNELS = ("coverage", "depth", "distance", "material", "normal", "albedo")      # in the order of dr_aov_lens_buffers
 
 
 def _channels(lead, names, K=None):
@@ -555,6 +557,20 @@ class Scene:
         x0, y0, w, h = (int(v) for v in window)
         out = _channels((h, w), _AOV_CHANNELS)
         _ok(lib().hk_aov(self.h, st.ctypes.data, W, H, x0, y0, w, h, traversal, nthreads, *_ptrs(out, _AOV_CHANNELS)))
+        return out
+
+    def aov_lens(self, settings13, W, H, frame_seed, seed_stride, nframes, window=None, as_guides=False, traversal=2, nthreads=4):
+        """dr_render_aov_lens on the host (device_aov_lens.hpp aov_lens_pixel, the nested loop): every channel of the window as a dict of arrays
+        shaped like dogeray_amd.Context.render_aov_lens's.  as_guides: the form option guide_frames = nframes hands the denoiser and the upscaler
+        (with frame_seed = dogeray_amd.GUIDE_SEED, seed_stride = 1) -- "normal", "albedo", "depth", "material" then go into denoise() / upscale()
+        where hk.aov's would."""
+        st = _arr(settings13, np.float32)
+        if window is None:
+            window = (0, 0, W // _div(st) // 8 * 8, H // _div(st) // 8 * 8)
+        x0, y0, w, h = (int(v) for v in window)
+        out = _channels((h, w), _AOV_LENS_CHANNELS)
+        _ok(lib().hk_aov_lens(self.h, st.ctypes.data, W, H, x0, y0, w, h, _u64(frame_seed), _u64(seed_stride), int(nframes), int(bool(as_guides)),
+                              traversal, nthreads, *_ptrs(out, _AOV_LENS_CHANNELS)))
         return out
 
 

@@ -38,7 +38,7 @@ void host_denoise_low(DnLaunch& L, bool filter, int nthreads, HostLow& planes) {
 }  // namespace
 extern "C" {
 // dr_accum_denoise on the host: the stage bodies of device_denoise.hpp over the pixel grid of settings13 (host_denoise_low, then the finish), from guides given
-// as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's or the GPU's own.  acc: the column-major
+// as arrays in dr_render_aov's layout (normal / albedo gw x gh x 3, depth / material gw x gh) -- hk_aov's, hk_aov_lens's guide form (option guide_frames) or the GPU's own.  acc: the column-major
 // W x H x 3 accumulator; params: a dr_denoise_params (NULL: the defaults); out_f32 / out_rgb8 (either may be NULL): row-major W x H x 3.
 // hist (may be NULL): the accumulator's history plane, W x H at x * H + y -- pixel p's divisor is hist[p] + divide_by.
 // m2 (may be NULL): the second-moment plane, W x H at x * H + y -- option "denoise_variance" = 1: the variance pre-pass takes the temporal variance

@@ -113,4 +113,40 @@ int hk_aov(void* hv, const float* settings13, int W, int H, int x0, int y0, int 
   });
   return 0;
 }
+
+// dr_render_aov_lens on the host: device_aov_lens.hpp aov_lens_pixel -- the plain nested loop over the pixel's nframes * spp camera rays -- for every pixel
+// of the window, with the given traversal; the channels (null: not written) in dr_render_aov_lens's layout.  as_guides: trace_guides' form (option
+// guide_frames: frame_seed DR_GUIDE_SEED, seed_stride 1).  Returns 0, or -1 with hk_last_error.
+int hk_aov_lens(void* hv, const float* settings13, int W, int H, int x0, int y0, int w, int h, uint64_t frame_seed, uint64_t seed_stride, int nframes,
+                int as_guides, int traversal, int nthreads, float* coverage, float* depth, float* distance, int32_t* material, float* normal, float* albedo) {
+  HkScene* h_ = (HkScene*)hv;
+  if (!h_ || !settings13) { hk_err = "bad argument"; return -1; }
+  const DeviceImage& img = h_->img;
+  RenderParams P;
+  if (const char* why = host_view(img, settings13, W, H, 0.0f, frame_seed, 1, 0, P)) { hk_err = why; return -1; }
+  if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > P.gx * 8 - w || y0 > P.gy * 8 - h) { hk_err = "window is empty or not inside the pixel grid"; return -1; }
+  const int spp = hf2i(settings13[10]);
+  if (nframes < 1 || spp < 1 || (long long)nframes * spp > 256) { hk_err = "a lens pass takes 1 .. 256 samples"; return -1; }
+  fill_image(img, P);
+  P.batch_seed_stride = seed_stride;
+  const float focus = settings13[7];
+  if (nthreads < 1) nthreads = 1;
+  host_rows(nthreads, nthreads, [&](int k) {
+    HostStack stack;
+    with_closest<false>(P, traversal, stack.data(), [&](auto closest) {
+      for (int wy = k; wy < h; wy += nthreads)
+        for (int wx = 0; wx < w; wx++) {
+          const AovLens a = aov_lens_pixel(P, closest, focus, x0 + wx, y0 + wy, nframes, spp, as_guides != 0);
+          const size_t i = (size_t)wy * (size_t)w + (size_t)wx;
+          if (coverage) coverage[i] = a.coverage;
+          if (depth) depth[i] = a.depth;
+          if (distance) distance[i] = a.distance;
+          if (material) material[i] = a.mat;
+          if (normal) st3(normal + 3 * i, a.normal);
+          if (albedo) st3(albedo + 3 * i, a.albedo);
+        }
+    });
+  });
+  return 0;
+}
 }  // extern "C"
